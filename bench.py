@@ -6,15 +6,20 @@ A "step" = forward of both sides (one 2B batch) + contrastive Loss + backward + 
 Workload at every N (weak scaling): BASELINE.json configs[1] -- ShfitScaleFormer_v3 "tiny"
 (depth [3,2,1]) on 4 scales [32,64,128,256] x 4 channels, 32 pairs per GPU, bf16 operands.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--pairs B] [--depth 3,2,1] [--no-cpu-baseline]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--pairs B] [--depth 3,2,1] [--dump-outputs DIR] [--full [--no-cpu-baseline]]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ... bench.py --gpus N ...
+
+A plain run sets up, warms up, times exactly K steps and prints the headline line.  `--full` adds everything else the line can
+carry, after the timed steps: the per-kernel roofline passes, the CPU baseline, the secondary measurements (`extras`, the
+at-tolerance throughput) and, with several ranks, the exchange breakdown.  `--dump-outputs DIR` writes what the last timed step
+computed (see `dump_outputs`); the inputs and initial weights are seeded, so two builds can be compared output for output.
 
 `python bench.py --gpus N` with N > 1 and no WORLD_SIZE in the environment launches itself: the parent (which never imports torch or
 touches a GPU) starts N children of this script, one rank per GPU, with RANK / LOCAL_RANK / WORLD_SIZE / MASTER_ADDR=127.0.0.1 /
 MASTER_PORT set, passes rank 0's single JSON line through and exits non-zero if any child fails (`launch_ranks`).  The reference has
 one device only (`net.cuda()`, /root/reference/Train_SMT.py:160-161); this is the multi-GPU path the build adds.
 
-Rank 0 prints ONE JSON line (see DESIGN.md "Measurement" for the roofline / cpu_baseline fields).
+Rank 0 prints ONE JSON line (see DESIGN.md "Measurement" for the roofline / cpu_baseline fields of a `--full` run).
 """
 import argparse
 import ctypes
@@ -64,6 +69,34 @@ def synth_batch(B, scales, in_c, device, seed):
 
 def log(msg):
     print(f"[bench {time.strftime('%H:%M:%S')}] {msg}", file=sys.stderr, flush=True)
+
+
+DUMP_SAMPLE = 1 << 22       # sampled positions per parameter-sized array: params + grads = 32 MB of float32
+
+
+def dump_outputs(path, trainer, loss):
+    """What the timed path computed in its last step, as `path`/<name>.npy in float32: `loss` (the value step() returned),
+    `params` (the parameters after that step's Adam update) and `grads` (that step's gradients).  params / grads are the
+    trainable parameters concatenated in named_parameters() order (independent of the flat buffer's layout), sampled at
+    DUMP_SAMPLE sorted positions drawn from a fixed seed: the whole buffers are 195 MB each at the headline model."""
+    import numpy as np
+    import torch
+    fp = trainer.fp
+    where = {id(p): (o, p.numel()) for p, o in zip(fp.params, fp.offsets)}
+    spans = [where[id(p)] for _, p in trainer.net.named_parameters() if id(p) in where]
+    total = sum(n for _, n in spans)
+    idx = None
+    if total > DUMP_SAMPLE:
+        idx = torch.randint(total, (DUMP_SAMPLE,), generator=torch.Generator().manual_seed(20240601)).sort().values.to(fp.flat.device)
+
+    def sample(buf):
+        whole = torch.cat([buf[o:o + n] for o, n in spans])
+        return (whole if idx is None else whole[idx]).float().cpu().numpy()
+    os.makedirs(path, exist_ok=True)
+    arrays = {"loss": loss.detach().float().cpu().numpy(), "params": sample(fp.flat), "grads": sample(fp.grad)}
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+    log(f"outputs of the last timed step written to {path}: " + ", ".join(f"{k} {list(a.shape)}" for k, a in arrays.items()))
 
 
 def usable_cores():
@@ -336,11 +369,14 @@ def main():
     ap.add_argument("--pairs", type=int, default=32, help="pairs per GPU per step")
     ap.add_argument("--depth", type=str, default="3,2,1")
     ap.add_argument("--numerics", type=str, default="bf16", choices=["bf16", "fp32", "bf16x3"])
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true", help="after the timed steps also run the per-kernel roofline passes, the CPU baseline, the "
+                    "secondary measurements (extras, at tolerance) and, with several ranks, the exchange breakdown")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed step computed as DIR/<name>.npy (dump_outputs)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--cpu-pairs", type=int, default=0, help="pairs per CPU-baseline step (0 = the same batch as --pairs, SURVEY 8d)")
     ap.add_argument("--cpu-steps", type=int, default=3, help="timed CPU-baseline steps after one warm-up")
-    ap.add_argument("--no-extras", action="store_true", help="skip the secondary measurements (fp32 parity mode, BASELINE configs 3 / 4 / 5) that "
-                    "the default one-GPU run appends to the JSON line")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the secondary measurements (fp32 parity mode, BASELINE configs 3 / 4 / 5, "
+                    "at tolerance) that a one-GPU run appends to the JSON line")
     ap.add_argument("--backend", type=str, default="nccl", choices=["nccl", "gloo"],
                     help="collective backend for --gpus > 1 (gloo only to rehearse the DP path with several ranks on ONE GPU)")
     ap.add_argument("--compress-grads", type=str, default="none", choices=["none", "bf16"],
@@ -349,6 +385,8 @@ def main():
                     help="replay the step's compute from captured hipGraphs (auto = on; with several ranks one graph per backward segment, "
                          "the bucket all-reduces are launched eagerly between them)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         raise SystemExit(launch_ranks(args.gpus, sys.argv[1:]))
 
@@ -420,7 +458,7 @@ def main():
         batch = trainer.graph_inputs()
     lib = _lib.lib()
     sync()
-    if not use_graph:
+    if args.full and not use_graph:
         lib.dm_prof_enable(1)
     t0 = time.perf_counter()
     for _ in range(args.steps):
@@ -429,6 +467,8 @@ def main():
     dt = time.perf_counter() - t0
     lib.dm_prof_enable(0)
     log(f"timed region: {args.steps} steps in {dt:.3f} s")
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, trainer, loss)       # before anything below steps the model again
     prof_steps, prof_note = args.steps, "hipEvents around every launch of the timed region"
 
     def collect():
@@ -436,7 +476,7 @@ def main():
         n = lib.dm_prof_collect(rows, 256)
         return {rows[i].name.decode(): (rows[i].launches, rows[i].total_ms, rows[i].total_flops, rows[i].total_bytes) for i in range(n)}
     prof = None
-    if use_graph:
+    if args.full and use_graph:
         # graph replays carry no per-kernel events: time the same kernels on the same stream in eager steps right after.  Two passes
         # of 3 steps, per kernel class the faster pass: one stalled launch (a 25 ms outlier was seen once on the shared pool) would
         # otherwise name the wrong dominant class
@@ -457,24 +497,8 @@ def main():
         tt = torch.tensor([dt], device=dev, dtype=torch.float64)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         dt = float(tt.item())
-        # what the exchange costs: (a) the same steps with the collectives skipped (compute only), (b) the bucketed all-reduce
-        # of the gradient buffer alone, back to back -- both outside the timed region, same process, same buffers
         calls0, bytes0 = trainer.stats["allreduce_calls"], trainer.stats["allreduce_bytes"]
         steps_seen = max(1, trainer.step_count)
-        trainer.exchange = False
-        sync(); t1 = time.perf_counter()
-        for _ in range(args.steps):
-            trainer.step(*batch)
-        sync(); dt_compute = time.perf_counter() - t1
-        trainer.exchange = True
-        sync(); t1 = time.perf_counter()
-        for _ in range(args.steps):
-            for bi in range(len(trainer.bucket_slices)):
-                trainer._launch_bucket(bi)
-            trainer._wait_exchange()
-        sync(); dt_xchg = time.perf_counter() - t1
-        tx = torch.tensor([dt_compute, dt_xchg], device=dev, dtype=torch.float64)
-        dist.all_reduce(tx, op=dist.ReduceOp.MAX)
         try:
             nccl_version = ".".join(str(v) for v in torch.cuda.nccl.version()) if args.backend == "nccl" else None
         except Exception:
@@ -482,13 +506,30 @@ def main():
         dp = {"world": world, "backend": args.backend, "nccl_version": nccl_version, "n_buckets": len(trainer.bucket_slices),
               "bucket_MB": [round((b.stop - b.start) * 4 / 1e6, 1) for b in trainer.bucket_slices],
               "allreduce_calls_per_step": round(calls0 / steps_seen, 2), "allreduce_bytes_per_step": int(bytes0 / steps_seen),
-              "exchange_ms_per_step": round(1e3 * float(tx[1]) / args.steps, 3),
-              "compute_only_ms_per_step": round(1e3 * float(tx[0]) / args.steps, 3),
-              "exposed_exchange_ms_per_step": round(1e3 * (dt - float(tx[0])) / args.steps, 3),
               "segmented_backward": bool(trainer.segmented), "graph_capture_error": trainer.graph_error,
               "bucket_dtype": "bf16" if trainer.compress_grads else "f32",
               "rehearsal_single_rank": bool(force_dp and world == 1)}
-    if prof is None:
+        if args.full:
+            # what the exchange costs: (a) the same steps with the collectives skipped (compute only), (b) the bucketed all-reduce
+            # of the gradient buffer alone, back to back -- both outside the timed region, same process, same buffers
+            trainer.exchange = False
+            sync(); t1 = time.perf_counter()
+            for _ in range(args.steps):
+                trainer.step(*batch)
+            sync(); dt_compute = time.perf_counter() - t1
+            trainer.exchange = True
+            sync(); t1 = time.perf_counter()
+            for _ in range(args.steps):
+                for bi in range(len(trainer.bucket_slices)):
+                    trainer._launch_bucket(bi)
+                trainer._wait_exchange()
+            sync(); dt_xchg = time.perf_counter() - t1
+            tx = torch.tensor([dt_compute, dt_xchg], device=dev, dtype=torch.float64)
+            dist.all_reduce(tx, op=dist.ReduceOp.MAX)
+            dp.update({"exchange_ms_per_step": round(1e3 * float(tx[1]) / args.steps, 3),
+                       "compute_only_ms_per_step": round(1e3 * float(tx[0]) / args.steps, 3),
+                       "exposed_exchange_ms_per_step": round(1e3 * (dt - float(tx[0])) / args.steps, 3)})
+    if args.full and prof is None:
         prof = collect()
 
     if rank == 0:
@@ -539,11 +580,11 @@ def main():
             "data_parallel": dp,
             "roofline": roof,
         }
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             out["cpu_baseline"] = cpu_baseline(scales, in_c, depth, args.cpu_pairs or args.pairs, args.cpu_steps)
         else:
             out["cpu_baseline"] = None
-        if world == 1 and not args.no_extras:
+        if args.full and world == 1 and not args.no_extras:
             ex = extras(args, scales, in_c, depth, dev)
             # the line stays short enough for a record that keeps only its tail: scalars here, the nested per-config dicts on stderr
             log("extras (details): " + json.dumps({k: v for k, v in ex.items() if isinstance(v, dict)}))

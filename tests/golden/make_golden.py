@@ -246,6 +246,42 @@ def gen_model(S2F, Losses):
     print("model_v3.npz", len(fx))
 
 
+def gen_model_f64(S2F, Losses):
+    """gen_model's three Adam steps with the reference modules, weights and inputs in float64 (model_v3_f64.npz, keys `<tag>/f64/...`).  In fp32 the
+    post-Adam values depend on the host's CPU code paths (noise-level gradients move their entries by O(lr)); in float64 they do not."""
+    fx = {}
+    for tag, scales, in_c, depth in (("v3_3s3c_642", [32, 64, 128], 3, [6, 4, 2]),
+                                     ("v3_4s4c_321", [32, 64, 128, 256], 4, [3, 2, 1]),
+                                     ("v3_3s3c_111", [32, 64, 128], 3, [1, 1, 1]),
+                                     ("v3_4s4c_642", [32, 64, 128, 256], 4, [6, 4, 2])):
+        PE = S2F.PatchEmbed if in_c == 3 else (
+            lambda img_size, patch_size, in_c, out_c, _c=in_c: S2F.PatchEmbed(img_size=img_size, patch_size=patch_size, in_c=_c, out_c=out_c))
+        net = S2F.ShfitScaleFormer_v3(is_designed_feature_embedding=True, PatchEmbed=PE, cube_size=[8, 8],
+                                      input_image_scales=list(scales), embed_dim=768, depth=list(depth))
+        load_det_weights(net, "")
+        net.double().train()
+        left, ld, right, rd, flag = model_inputs(tag, scales, in_c, 4)
+        left, ld, right, rd = [x.double() for x in left], ld.double(), [x.double() for x in right], rd.double()
+        crit = Losses.Loss(margin=1.0, lamda=0.1, belta=0)
+        opt = torch.optim.Adam(filter(lambda p: p.requires_grad, net.parameters()), lr=1e-4)
+        watch = [k[len(tag + "/adam1/"):-len("/shape")] for k in np.load(os.path.join(HERE, "model_v3.npz")).files
+                 if k.startswith(tag + "/adam1/") and k.endswith("/shape")]
+        named = dict(net.named_parameters())
+        for step in range(1, 4):
+            out_a, out_b = net(left, ld, right, rd)
+            loss = crit(out_a, out_b, flag)
+            opt.zero_grad()
+            loss.backward()
+            opt.step()
+            fx[tag + f"/f64/loss_step{step}"] = np.float64(loss.item())
+            if step in (1, 3):
+                for n in watch:
+                    add(fx, tag + f"/f64/adam{step}/" + n, named[n], k=1024)
+        print(tag, "f64 losses", [fx[tag + f"/f64/loss_step{s}"] for s in (1, 2, 3)])
+    np.savez_compressed(os.path.join(HERE, "model_v3_f64.npz"), **fx)      # (host-independent: regenerated whole)
+    print("model_v3_f64.npz", len(fx))
+
+
 def gen_variants(S2F, Losses):
     """Single-stage variants v1 / v2 (cube [4,7,7], N = 196) and the designed-features-only v6."""
     fx = {}
@@ -727,6 +763,8 @@ def main():
         gen_ops(S2F, Losses)
     if "model" in which:
         gen_model(S2F, Losses)
+    if "model" in which or "model_f64" in which:
+        gen_model_f64(S2F, Losses)
     if "vit" in which:
         gen_vit(vit_model, Losses)
     if "variants" in which:

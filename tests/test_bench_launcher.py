@@ -77,8 +77,8 @@ def test_bench_refuses_mismatched_world():
 
 def test_bench_fails_fast_without_enough_gpus_for_rccl():
     """One rank per GPU over RCCL: a node with fewer devices than ranks is refused with a clear message before any process group
-    exists (no device at all in this container)."""
-    env = dict(os.environ, WORLD_SIZE="2", RANK="0", LOCAL_RANK="0")
+    exists.  The child sees no device (an empty HIP_VISIBLE_DEVICES), so the case is the same on a host with GPUs."""
+    env = dict(os.environ, WORLD_SIZE="2", RANK="0", LOCAL_RANK="0", HIP_VISIBLE_DEVICES="")
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2"], capture_output=True, text=True, timeout=300, env=env)
     assert r.returncode != 0 and "needs 2 GPUs on this node, found 0" in r.stderr
 

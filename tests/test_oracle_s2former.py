@@ -160,24 +160,33 @@ def test_whole_model_forward_backward_adam(tag):
     assert O.model_name(cfg) == str(fx[tag + "/name"])
     n_params = sum(int(np.prod(s)) for s, dt in spec.values() if dt == "float32")
     assert n_params == int(fx[tag + "/n_params"])
-    # --- one training step
+    # --- one training step in fp32 (outputs, gradients), then three Adam steps in float64: in fp32 the post-Adam values depend on
+    # the host's CPU code paths (noise-level gradients move their entries by O(lr)), so they are pinned to the reference's float64 run
     p = model_params(cfg)
     left, ld, right, rd, flag = model_inputs(tag, cfg.scales, cfg.in_c, 4)
+    _run_steps(tag, fx, cfg, p, left, ld, right, rd, flag, steps=1, pfx="")
+    p = {k: (v.detach().double().requires_grad_(v.requires_grad) if v.dtype == torch.float32 else v) for k, v in model_params(cfg).items()}
+    left, ld, right, rd = [t.double() for t in left], ld.double(), [t.double() for t in right], rd.double()
+    _run_steps(tag, {**fx, **load_fx("model_v3_f64.npz")}, cfg, p, left, ld, right, rd, flag, steps=3, pfx="f64/")
+
+
+def _run_steps(tag, fx, cfg, p, left, ld, right, rd, flag, steps, pfx):
     fparams = {k: v for k, v in p.items() if v.dtype.is_floating_point}
     m = {k: torch.zeros_like(v) for k, v in fparams.items()}
     v2 = {k: torch.zeros_like(v) for k, v in fparams.items()}
-    watch = [k[len(tag + "/adam1/"):-len("/shape")] for k in fx.files
+    watch = [k[len(tag + "/adam1/"):-len("/shape")] for k in fx
              if k.startswith(tag + "/adam1/") and k.endswith("/shape")]
     assert len(watch) >= 6
-    for step in range(1, 4):
+    for step in range(1, steps + 1):
         for t in fparams.values():
             t.grad = None
         fa, fb = O.forward_pair(p, left, ld, right, rd, cfg)
         loss = OL.contrastive_loss(fa, fb, flag, 1.0)
         loss.backward()
-        want_loss = float(fx[tag + f"/loss_step{step}"])
+        # fp32 steps against the reference's fp32 run; the float64 keys are the reference's run in float64
+        want_loss = float(fx[tag + f"/{pfx}loss_step{step}"])
         assert abs(loss.item() - want_loss) <= 2e-5 * abs(want_loss), (step, loss.item(), want_loss)
-        if step == 1:
+        if step == 1 and pfx == "":
             recipe.check_summary(tag + "/out_a", fa.detach().numpy(), fx, RTOL)
             recipe.check_summary(tag + "/out_b", fb.detach().numpy(), fx, RTOL)
             none = sorted(str(s) for s in fx[tag + "/grad_none"])
@@ -197,7 +206,7 @@ def test_whole_model_forward_backward_adam(tag):
             for k in watch:
                 # Adam normalises by sqrt(v): entries whose gradient is at fp32-noise level move by
                 # O(lr) in a noise-determined direction, so the post-step pin is looser than the grads'.
-                recipe.check_summary(tag + f"/adam{step}/" + k, p[k].detach().numpy(), fx, 1e-4, k=1024)
+                recipe.check_summary(tag + f"/{pfx}adam{step}/" + k, p[k].detach().numpy(), fx, 1e-4, k=1024)
 
 
 def test_flops_formula_matches_baseline_table():

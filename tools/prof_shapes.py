@@ -52,7 +52,7 @@ if "--config" in sys.argv and sys.argv[sys.argv.index("--config") + 1] == "3":
     print("config 3: ViT-B/16 224x224x3, 128 pairs / step, bf16 (eager steps, hipEvents per launch)")
     table(ms, tf, steps)
 else:
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--no-cpu-baseline", "--no-extras"] + sys.argv[1:],
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--no-cpu-baseline", "--no-extras"] + sys.argv[1:],
                          env=dict(os.environ), capture_output=True, text=True)
     line = [l for l in out.stdout.splitlines() if l.startswith("{")][-1]
     r = json.loads(line)["roofline"]

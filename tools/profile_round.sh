@@ -8,7 +8,7 @@ ROOT="${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}"
 cd /tmp && export TMPDIR=/tmp && cd "$ROOT"
 OUT=gpurun_out/${TAG}_prof
 rm -rf $OUT && mkdir -p $OUT
-ARGS="bench.py --steps 20 --warmup 3 --no-cpu-baseline --no-extras"
+ARGS="bench.py --full --steps 20 --warmup 3 --no-cpu-baseline --no-extras"
 rocprofv3 --kernel-trace --stats -d $OUT/trace -- python3 $ARGS > $OUT/bench_under_rocprof.json 2> $OUT/trace.log
 DB=$(find $OUT/trace -name "*.db" | head -1)
 python tools/rocpd_stats.py $DB 26 $OUT/kernel_stats.md > /dev/null
@@ -20,6 +20,6 @@ rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_WAIT_A
 python tools/pmc_dump.py $OUT/mfma gemm > $OUT/gemm_counters.txt
 python tools/pmc_dump.py $OUT/mfma attn >> $OUT/gemm_counters.txt
 cp $OUT/pmc_traffic.json profiles/pmc_traffic.json      # same sources: the bench line below quotes it (copy it back into the repo with the rest)
-python bench.py --steps 50 --warmup 3 > $OUT/bench.json 2> $OUT/bench.err
+python bench.py --full --steps 50 --warmup 3 > $OUT/bench.json 2> $OUT/bench.err
 rm -rf $OUT/trace $OUT/fetch $OUT/write $OUT/mfma
 ls -la $OUT
