@@ -9,6 +9,8 @@ features resident in HBM and runs the sweep as two kernels:
     dm_segment_mean      per-polygon mean over its sample points (CSR: ptr[S+1], idx[P])
     dm_edge_similarity   per-edge simi + merge = simi < margin
 The arithmetic order of both is pinned (oracle/sweep_strict.c), so `merge` is bit-exact.
+The reference's dense helpers `Euclidean_distance` / `MC_Lyu_2020` (ExtractFeatures.py:119-147, :228-237) run on
+dm_pairwise_distance (one fused kernel: norms, product and epilogue).
 """
 from __future__ import annotations
 
@@ -146,6 +148,26 @@ def rag_similarity_sweep(features: torch.Tensor, ptr: torch.Tensor, idx: torch.T
     pooled = ops.segment_mean(features.contiguous(), ptr.to(torch.int32).contiguous(), idx.to(torch.int32).contiguous())
     simi, merge = ops.edge_similarity(pooled, edges.to(torch.int32).contiguous(), margin)
     return pooled, simi, merge.bool()
+
+
+def Euclidean_distance(X, Y):
+    """`Euclidean_distance(X, Y)` of ExtractFeatures.py:119-147 (and Train_SMT.py:115-131): X [n,p], Y [m,p] -> D [n,m] distance
+    matrix, computed on the device by one dm_pairwise_distance launch (ops.pairwise_distance).  numpy arrays and CPU tensors go to
+    the current GPU and the result comes back as the input's type and dtype (float32 or float64, as the reference computes in
+    the input dtype); CUDA tensors stay on their device."""
+    if isinstance(X, torch.Tensor) and isinstance(Y, torch.Tensor) and X.is_cuda and Y.is_cuda:
+        return ops.pairwise_distance(X, Y)
+    as_numpy = not isinstance(X, torch.Tensor)
+    tx = torch.as_tensor(X) if not isinstance(X, torch.Tensor) else X
+    ty = torch.as_tensor(Y) if not isinstance(Y, torch.Tensor) else Y
+    dev = tx.device if tx.is_cuda else (ty.device if ty.is_cuda else torch.device("cuda", torch.cuda.current_device()))
+    D = ops.pairwise_distance(tx.to(dev), ty.to(dev))
+    return D.cpu().numpy() if as_numpy else D.cpu()
+
+
+def MC_Lyu_2020(X, Y):
+    """`MC_Lyu_2020(X, Y)` of ExtractFeatures.py:228-237: the same distance matrix as Euclidean_distance."""
+    return Euclidean_distance(X, Y)
 
 
 def near_margin_count(simi: torch.Tensor, margin: float = 1.0, band: float = 1e-4) -> int:

@@ -19,6 +19,7 @@ HEADER_PATH = os.path.join(ROOT, "include", "deepmerge_hip.h")
 DM_F32, DM_BF16 = 0, 1
 DM_NT, DM_NN, DM_TN = 0, 1, 2
 DM_BF16_PAIR = 2      # DmGemmArgs.c_dtype: C as a hi / lo plane pair
+DM_F64 = 3            # dm_pairwise_distance only
 DM_EPI_NONE, DM_EPI_GELU, DM_EPI_DGELU, DM_EPI_GELU_GRAD, DM_EPI_MUL = 0, 1, 2, 3, 4
 
 _STATUS = {-1: "bad shape", -2: "bad dtype", -3: "bad alignment", -4: "workspace", -5: "HIP error", -6: "unsupported"}
@@ -111,6 +112,7 @@ SIGNATURES = {
     "dm_adam_step_dev_pair": (_I, [_P, _P, _P, _P, _P, _P, _L, _P, _D, _D, _D, _D, _P]),
     "dm_segment_mean": (_I, [_P, _P, _P, _P, _I, _I, _P]),
     "dm_edge_similarity": (_I, [_P, _P, _P, _P, _I, _I, _F, _P]),
+    "dm_pairwise_distance": (_I, [_P, _P, _P, _I, _I, _I, _I, _P]),
     "dm_patch_pyramid": (_I, [_P, _I, _I, _I, _P, _P, _I, _I, _I, _I, _P, _P]),
     "dm_patch_pyramid_cols": (_I, [_P, _I, _I, _I, _P, _P, _I, _I, _I, _I, _I, _P, _I, _P]),
     "dm_pair_batch_gather": (_I, [_P, _I, _I, _I, _I, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _I, _P, _P, _P, _P]),

@@ -890,6 +890,35 @@ def edge_similarity(pooled: torch.Tensor, edges: torch.Tensor, margin: float = 1
     return simi, merge
 
 
+_DIST_DTYPES = {torch.float32: DM_F32, torch.float64: _lib.DM_F64}
+
+
+def pairwise_distance(X: torch.Tensor, Y: torch.Tensor) -> torch.Tensor:
+    """D[n,m] = sqrt(max(0, |x_i|^2 + |y_j|^2 - 2 x_i.y_j)) of X [n,p] and Y [m,p] (the reference's Euclidean_distance) in ONE
+    kernel launch on the current stream: fp32 -> fp32, fp64 -> fp64, no gradient.  Rows that are equal bit for bit give exactly 0.
+    Empty n or m gives an empty [n, m] and p == 0 gives zeros (numpy's answers), without a launch."""
+    _need_cuda(X, Y)
+    if X.dim() != 2 or Y.dim() != 2:
+        raise ValueError(f"pairwise_distance: X and Y must be 2-D, got {tuple(X.shape)} and {tuple(Y.shape)}")
+    if X.shape[1] != Y.shape[1]:
+        raise ValueError(f"pairwise_distance: feature widths differ ({X.shape[1]} != {Y.shape[1]})")
+    if X.dtype != Y.dtype or X.dtype not in _DIST_DTYPES:
+        raise ValueError(f"pairwise_distance: X and Y must both be float32 or float64, got {X.dtype} and {Y.dtype}")
+    if X.device != Y.device:
+        raise ValueError(f"pairwise_distance: X on {X.device}, Y on {Y.device}")
+    n, m, p = X.shape[0], Y.shape[0], X.shape[1]
+    if n == 0 or m == 0:
+        return torch.empty((n, m), dtype=X.dtype, device=X.device)
+    if p == 0:
+        return torch.zeros((n, m), dtype=X.dtype, device=X.device)
+    X, Y = X.detach().contiguous(), Y.detach().contiguous()
+    D = torch.empty((n, m), dtype=X.dtype, device=X.device)
+    with torch.cuda.device(X.device):
+        check(_lib.lib().dm_pairwise_distance(X.data_ptr(), Y.data_ptr(), D.data_ptr(), n, m, p, _DIST_DTYPES[X.dtype], _stream()),
+              "dm_pairwise_distance")
+    return D
+
+
 # ------------------------------------------------------------------------------------------------
 # autograd Functions
 # ------------------------------------------------------------------------------------------------

@@ -28,7 +28,8 @@ extern "C" {
 #endif
 
 typedef enum { DM_F32 = 0, DM_BF16 = 1,
-               DM_BF16_PAIR = 2      /* ABI 4, DmGemmArgs.c_dtype only: C is written as a hi / lo plane pair (see c_plane) */
+               DM_BF16_PAIR = 2,     /* ABI 4, DmGemmArgs.c_dtype only: C is written as a hi / lo plane pair (see c_plane) */
+               DM_F64 = 3            /* dm_pairwise_distance only */
 } DmDtype;
 
 typedef enum {
@@ -353,6 +354,13 @@ int dm_segment_mean(const float *F, const int32_t *ptr, const int32_t *idx, floa
  * Summation order is fixed and documented in oracle/sweep_strict.c (bit-exact contract). */
 int dm_edge_similarity(const float *pooled, const int32_t *edges, float *simi, uint8_t *merge,
                        int32_t E, int32_t D, float margin, void *stream);
+/* Dense pairwise distance (ExtractFeatures.py:119-147 `Euclidean_distance`, called at :215; ExtractFeatures.py:228-237
+ * `MC_Lyu_2020`; Train_SMT.py:115-131 `Euclidean_distance`): X [n,p], Y [m,p] row-major contiguous -> D [n,m] row-major,
+ *   D[i,j] = sqrt(max(0, (x2[i] + y2[j]) - 2 xy[i,j]))   (NaN stays NaN; correctly rounded sqrt), one launch per call.
+ * dtype DM_F32 (xy on the f32-input MFMA) or DM_F64 (fma(double) chains).  xy, x2 and y2 are the same k-ordered fma chain
+ * from +0, so a row of X that equals a row of Y bit for bit gives exactly 0, and every entry depends on its two rows only
+ * (same bits for any n, m, tile position or row subset).  n, m, p >= 1; n * m may exceed 2^31. */
+int dm_pairwise_distance(const void *X, const void *Y, void *D, int32_t n, int32_t m, int32_t p, int32_t dtype, void *stream);
 
 /* ---- patch pyramid gather --------------------------------------------------------------------
  * Replaces, for one scale, the per-point loader work of MyUtils1.py:116-223 / MyUtils2.py:286-437:
