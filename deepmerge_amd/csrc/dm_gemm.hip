@@ -42,6 +42,8 @@ bool dm_gemm256_plan(GemmParams &p, int layout, int ab_dtype, bool can_split, lo
 void dm_gemm256_launch(const GemmParams &p, int layout, hipStream_t s);
 int dm_gemm_ring_plan(GemmParams &p, int layout, int ab_dtype, bool aligned8);      // dm_gemm_ring.hip
 void dm_gemm_ring_launch(const GemmParams &p, int wm, hipStream_t s);
+bool dm_gemm_q4_plan(GemmParams &p, int layout, int ab_dtype, bool aligned8);      // dm_gemm_q4.hip
+void dm_gemm_q4_launch(const GemmParams &p, int layout, hipStream_t s);
 int dm_gemm_w4_plan(GemmParams &p, int layout, int ab_dtype, bool aligned8, bool can_split, long long workspace_bytes);   // dm_gemm_w4.hip (grid size, 0 = not taken)
 void dm_gemm_w4_launch(const GemmParams &p, int layout, int grid, hipStream_t s);
 int dm_gemm_w4_grouped(GemmParams *ps, int n, hipStream_t s, bool launch, const DmGroupedExtra &x);      // dm_gemm_w4.hip: n weight gradients in one launch (0 = not taken, 1 = one K slice per tile, 2 = stream-K)
@@ -687,8 +689,8 @@ void launch_mfma(const GemmParams &p, int layout, int grid, hipStream_t s) {
 
 // DM_GEMM_ROUTE (see dm_gemm): per-product family override for in-step A/B runs; restores the environment when it goes out of scope.
 struct DmRouteOverride {
-  static constexpr int NKEY = 5;
-  const char *keys[NKEY] = {"DM_GEMM_W4", "DM_GEMM_W4_TN", "DM_GEMM_RING", "DM_GEMM_256", "DM_GEMM_FORCE_TILE"};
+  static constexpr int NKEY = 6;
+  const char *keys[NKEY] = {"DM_GEMM_W4", "DM_GEMM_W4_TN", "DM_GEMM_RING", "DM_GEMM_256", "DM_GEMM_FORCE_TILE", "DM_GEMM_Q4"};
   char saved[NKEY][16];
   bool had[NKEY];
   bool active = false;
@@ -700,12 +702,13 @@ struct DmRouteOverride {
     const char *hit = strstr(e, want);
     if (!hit) return;
     const char *fam = hit + strlen(want);
-    const char *vals[NKEY] = {"0", "0", "0", "0", nullptr};
+    const char *vals[NKEY] = {"0", "0", "0", "0", nullptr, "0"};
     if (!strncmp(fam, "w4", 2)) { vals[0] = "2"; vals[1] = "2"; }
     else if (!strncmp(fam, "ring", 4)) vals[2] = "2";
     else if (!strncmp(fam, "256", 3)) vals[3] = "2";
     else if (!strncmp(fam, "128", 3)) vals[4] = "128";
     else if (!strncmp(fam, "64", 2)) vals[4] = "64";
+    else if (!strncmp(fam, "q4", 2)) vals[5] = "2";
     else return;
     active = true;
     for (int i = 0; i < NKEY; ++i) {
@@ -919,18 +922,20 @@ extern "C" int dm_gemm(const DmGemmArgs *a, void *stream) {
   const bool fwd_slices_ok = a->layout != DM_TN && a->ab_dtype == DM_BF16 && a->split_k == 0 && ring_aligned && a->N % 8 == 0 &&
                              (a->residual == nullptr || a->ldr % 8 == 0) && a->workspace != nullptr && slab_bytes > 0;
   // A/B aid (tools/routing_check.py finds candidates in a cold microbenchmark; the decision is taken INSIDE the step): DM_GEMM_ROUTE names a
-  // kernel family for single products, e.g. "NT:16384x2304x768=ring,NN:16384x3072x768=256" (families: w4, ring, 256, 128, 64).  The plans
+  // kernel family for single products, e.g. "NT:16384x2304x768=ring,NN:16384x3072x768=256" (families: w4, ring, 256, 128, 64, q4).  The plans
   // below read their switches per call, so the override sets them for this call only.  Not thread-safe; never set in production.
   DmRouteOverride route_guard(a->layout, a->M, a->N, a->K);
   const int w4 = w4_ok ? dm_gemm_w4_plan(p, a->layout, a->ab_dtype, true, a->layout == DM_TN ? can_split : fwd_slices_ok, slab_bytes) : 0;
   const bool persistent = w4 != 0;
-  const int ring = persistent ? 0 : dm_gemm_ring_plan(p, a->layout, a->ab_dtype, ring_aligned);
-  const bool big = !persistent && !ring && dm_gemm256_plan(p, a->layout, a->ab_dtype, can_split, slab_bytes, a->split_k);
-  int tile = w4 ? 1924 : ring ? (ring == 8 ? 2568 : 1288) : big ? 256 : pick_tile(a->layout, a->M, a->N, a->K);
-  int split = w4 ? p.split_k : (ring || persistent) ? 1 : p.split_k;
+  // four-workgroups-per-CU 128 x 128 tiles (dm_gemm_q4.hip) for the short-contraction forward / dgrad products
+  const bool q4 = !persistent && dm_gemm_q4_plan(p, a->layout, a->ab_dtype, ring_aligned && a->split_k <= 1);
+  const int ring = (persistent || q4) ? 0 : dm_gemm_ring_plan(p, a->layout, a->ab_dtype, ring_aligned);
+  const bool big = !persistent && !q4 && !ring && dm_gemm256_plan(p, a->layout, a->ab_dtype, can_split, slab_bytes, a->split_k);
+  int tile = w4 ? 1924 : q4 ? 1284 : ring ? (ring == 8 ? 2568 : 1288) : big ? 256 : pick_tile(a->layout, a->M, a->N, a->K);
+  int split = w4 ? p.split_k : (ring || q4 || persistent) ? 1 : p.split_k;
   // forward / dgrad K slices (plan_fwd_split): bf16, automatic slice count, 8-column epilogue legal, slab inside the workspace
   bool fwd_split = persistent && a->layout != DM_TN && p.split_k > 1;      // the 4-wave kernel planned slices
-  if (!big && !ring && !persistent && fwd_slices_ok) {
+  if (!big && !ring && !q4 && !persistent && fwd_slices_ok) {
     int ft;
     const int fs = plan_fwd_split(a->layout, a->M, a->N, a->K, ft);
     if (fs > 1 && (int64_t)fs * a->M * a->N * 4 <= slab_bytes && !getenv("DM_GEMM_FORCE_TILE")) {
@@ -938,7 +943,7 @@ extern "C" int dm_gemm(const DmGemmArgs *a, void *stream) {
       tile = ft;
     }
   }
-  if (!big && !ring && !persistent) {
+  if (!big && !ring && !q4 && !persistent) {
     p.tiles_m = (a->M + tile - 1) / tile;
     p.tiles_n = (a->N + tile - 1) / tile;
     const int bk = (a->ab_dtype == DM_BF16) ? 64 : 32;
@@ -986,10 +991,12 @@ extern "C" int dm_gemm(const DmGemmArgs *a, void *stream) {
     DmProfScope prof(pname, s, 2.0 * a->M * a->N * a->K,
                      esz * ((double)a->M * a->K + (double)a->N * a->K) + csz * mn * (a->accumulate ? 2.0 : 1.0) +
                          (a->residual ? 4.0 * mn : 0.0) + (a->aux ? ((a->aux_dtype == DM_BF16) ? 2.0 : 4.0) * mn : 0.0));
-    const bool cs_t64 = !big && !w4 && !ring && a->layout == DM_TN && a->ab_dtype == DM_BF16 && tile == 64 && a->colsum_a != nullptr && split <= 128;
+    const bool cs_t64 = !big && !w4 && !ring && !q4 && a->layout == DM_TN && a->ab_dtype == DM_BF16 && tile == 64 && a->colsum_a != nullptr && split <= 128;
     p.colsum_slab = ((big || (w4 && a->layout == DM_TN) || cs_t64) && cs_region) ? cs_region : nullptr;
     if (w4) {
       dm_gemm_w4_launch(p, a->layout, w4, s);
+    } else if (q4) {
+      dm_gemm_q4_launch(p, a->layout, s);
     } else if (ring) {
       dm_gemm_ring_launch(p, ring, s);
     } else if (big) {
@@ -1009,7 +1016,7 @@ extern "C" int dm_gemm(const DmGemmArgs *a, void *stream) {
   }
   DM_LAUNCH_CHECK("dm_gemm");
   if (fwd_split) return DM_OK;
-  const bool cs_t64 = !big && !w4 && !ring && a->layout == DM_TN && a->ab_dtype == DM_BF16 && tile == 64 && a->colsum_a != nullptr && split <= 128;
+  const bool cs_t64 = !big && !w4 && !ring && !q4 && a->layout == DM_TN && a->ab_dtype == DM_BF16 && tile == 64 && a->colsum_a != nullptr && split <= 128;
   const bool cs_fused = big || (w4 && a->layout == DM_TN) || cs_t64;      // these kernels produce the partial column sums of A themselves
   const int cs_rows_per_slice = big ? 4 : 1;      // (256x256 pipeline: one row per wave column; 64x64 tiles and the 4-wave kernel: one per slice)
   if (split > 1) {

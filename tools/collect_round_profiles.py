@@ -29,7 +29,13 @@ out = head + ["| kernel | launches/step | ms/step | avg us |", "|---|---|---|---
 out += [f"| `{n}` | {c} | {d / 1000:.3f} | {d / c:.1f} |" for n, (c, d) in sorted(rows.items(), key=lambda kv: -kv[1][1])]
 out.append(f"\nGPU-busy total: {sum(v[1] for v in rows.values()) / 1000:.3f} ms/step ({sum(v[0] for v in rows.values())} launches)")
 open(x3, "w").write("\n".join(out) + "\n")
+# the traced kernels cannot take longer per step than the whole step: GPU-busy of the kernel table against the bench record of the same
+# round (profile_round.sh's plain run), with 5 % for box spread -- a larger sum means the table is normalised by the wrong step count
+busy = next(float(l.split(":")[1].split()[0]) for l in open(os.path.join(dst, f"{tag}_kernel_stats.md")) if l.startswith("GPU-busy total:"))
+step_ms = json.loads(open(os.path.join(src, "bench.json")).read().strip().splitlines()[-1])["ms_per_step"]
+norm_ok = busy <= step_ms * 1.05
+print(f"kernel table: GPU-busy {busy:.3f} ms/step against bench {step_ms:.3f} ms/step:", "ok" if norm_ok else "TOO LARGE (step count?)")
 import bench
 ok = json.load(open(os.path.join(dst, "pmc_traffic.json")))["_csrc_sha256"] == bench.csrc_hash()
 print("copied", len(pairs) + 3, "files; source stamp", "ok" if ok else "STALE")
-sys.exit(0 if ok else 1)
+sys.exit(0 if ok and norm_ok else 1)

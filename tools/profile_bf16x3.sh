@@ -6,5 +6,5 @@ rm -rf $OUT && mkdir -p $OUT
 rocprofv3 --kernel-trace -d $OUT/trace -- python3 bench.py --full --steps 20 --warmup 3 --no-cpu-baseline --no-extras --numerics bf16x3 > $OUT/bench.json 2> $OUT/trace.log
 DB=$(find $OUT/trace -name "*.db" | head -1)
 python tools/rocpd_gaps.py $DB $OUT/gaps.md $OUT/seq.txt > /dev/null
-python tools/rocpd_stats.py $DB 26 $OUT/kernel_stats.md > /dev/null
+python tools/rocpd_stats.py $DB auto $OUT/kernel_stats.md > /dev/null
 rm -rf $OUT/trace

@@ -11,7 +11,7 @@ rm -rf $OUT && mkdir -p $OUT
 ARGS="bench.py --full --steps 20 --warmup 3 --no-cpu-baseline --no-extras"
 rocprofv3 --kernel-trace --stats -d $OUT/trace -- python3 $ARGS > $OUT/bench_under_rocprof.json 2> $OUT/trace.log
 DB=$(find $OUT/trace -name "*.db" | head -1)
-python tools/rocpd_stats.py $DB 26 $OUT/kernel_stats.md > /dev/null
+python tools/rocpd_stats.py $DB auto $OUT/kernel_stats.md > /dev/null
 PARGS="bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-extras --graph off"
 rocprofv3 --kernel-trace --pmc FETCH_SIZE -d $OUT/fetch -- python3 $PARGS > /dev/null 2> $OUT/fetch.log
 rocprofv3 --kernel-trace --pmc WRITE_SIZE -d $OUT/write -- python3 $PARGS > /dev/null 2> $OUT/write.log
