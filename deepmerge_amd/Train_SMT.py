@@ -1,0 +1,122 @@
+"""Drop-in for the reference's training entry point `Train_SMT.train` (Train_SMT.py:143-356): the epoch loop over a device-resident
+pair dataset (deepmerge_amd/dataset.py), with the reference's schedule, checkpoint cadence, file names and checkpoint dict.
+
+Per epoch: the lr of MultiStepLR(milestones, gamma) stepped once per epoch; ONE dm_pair_epoch_draw launch for the epoch's shuffled
+pair draw (MyUtils1.py:275-293 + DataLoader(shuffle=True), keyed by (dataset seed, epoch)); per full batch a
+feed.PairFeed gather straight into the captured step's inputs and a PairTrainer hipGraph replay; the partial last batch
+(drop_last=False) through a second feed sized to it and an eager step.  Step losses are summed on the device and read once per epoch.
+
+Resume (`is_retrained`): weights, Adam moments and the saved lr come back from the checkpoint; `start_epoch = epoch + 1`, and the
+milestones are counted again from the resumed epoch, as upstream (the scheduler is created afresh and its state is not saved).
+Because the draw is keyed by (seed, epoch), a resumed run sees the same data as an uninterrupted one.
+"""
+from __future__ import annotations
+
+import os
+import time
+from collections import Counter
+from typing import List, Sequence, Tuple
+
+import torch
+import torch.distributed as dist
+
+from . import ops
+from .checkpoint import load_checkpoint, save_checkpoint
+from .dataset import PairDataset
+from .ExtractFeatures import Euclidean_distance  # noqa: F401  (Train_SMT.Euclidean_distance, Train_SMT.py:115-131)
+from .feed import PairFeed
+from .trainer import PairTrainer, stacked_pair_inputs
+
+NUM_EPOCHS = 100                 # config.py num_epochs
+MODEL_PARAS_PATH = "./model/"    # config.py model_paras_path
+
+
+def epoch_lr(lr0: float, k: int, milestones: Sequence[int] = (40, 80), gamma: float = 0.2) -> float:
+    """The lr of torch.optim.lr_scheduler.MultiStepLR after k per-epoch steps from lr0 (Train_SMT.py:194, :351), in torch's own
+    chained form: at each milestone the current lr is multiplied by gamma ** (times the milestone is listed).  (The closed form
+    lr0 * gamma ** n can differ from it in the last bit.)"""
+    lr, count = float(lr0), Counter(int(m) for m in milestones)
+    for e in range(1, int(k) + 1):
+        if e in count:
+            lr = lr * gamma ** count[e]
+    return lr
+
+
+def checkpoint_due(epoch: int) -> bool:
+    """Train_SMT.py:317: a checkpoint after every fifth epoch and after each of the last ten of a 100-epoch run."""
+    return (epoch + 1) % 5 == 0 or epoch + 1 >= 90
+
+
+def checkpoint_name(epoch: int, num_epochs: int, net_name: str, t: time.struct_time) -> str:
+    """The reference's file names (Train_SMT.py:318-341)."""
+    if epoch + 1 == 100:
+        return "model-{0}-{1}-{2}_{3}-{4}-{5}_{6}epochs.pth".format(t.tm_year, t.tm_mon, t.tm_mday, t.tm_hour, t.tm_min, net_name, num_epochs)
+    return "model-{0}-{1}-{2}_{3}-{4}_{5}epochs.pth".format(t.tm_year, t.tm_mon, t.tm_mday, t.tm_hour, t.tm_min, epoch + 1)
+
+
+def train(net, margin, train_bs, lr_init, normMean, normStd, lamda, belta, is_retrained=False, checkpoint_path=None, *,
+          dataset: PairDataset = None, num_epochs: int = NUM_EPOCHS, milestones: Sequence[int] = (40, 80), gamma: float = 0.2,
+          model_paras_path: str = MODEL_PARAS_PATH) -> Tuple[List[int], List[float]]:
+    """`Train_SMT.train` with the reference's positional signature (normMean / normStd are unused, as upstream; lamda / belta go
+    to Loss).  `dataset` replaces the reference's hard-coded shapefile folders; the draw's seed is the dataset's.  Returns
+    (epoch indices, per-epoch mean loss = sum of step losses / number of steps), one entry per epoch run."""
+    if dataset is None:
+        raise ValueError("train() needs dataset=PairDataset.from_arrays(...) (the reference's hard-coded folders are not portable)")
+    if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
+        raise NotImplementedError("train() runs on one GPU; data-parallel sharding of the epoch is not implemented")
+    if int(train_bs) < 1:
+        raise ValueError(f"train_bs must be >= 1, got {train_bs}")
+    scales = [int(s) for s in getattr(net, "input_image_scales", ())]
+    if not scales:
+        raise ValueError(f"{type(net).__name__} has no input_image_scales: train() feeds patch pyramids")
+    dev = dataset.device
+    net.to(dev)
+    rows = stacked_pair_inputs(net)            # v3 family: patch-embed rows; other models: fp32 patch tensors
+    numerics = getattr(net, "numerics", ops.get_numerics())
+    max_window = dataset.max_window(len(scales))
+    trainer = PairTrainer(net, margin=margin, lr=lr_init, lamda=lamda, belta=belta)
+    start_epoch, lr0 = 0, float(lr_init)
+    if is_retrained:
+        state = load_checkpoint(checkpoint_path, net, trainer)
+        start_epoch = int(state["epoch"]) + 1
+        if start_epoch >= num_epochs:
+            raise ValueError("start_epoch must be smaller than number of epochs")
+        lr0 = float(trainer.lr)                 # optimizer.load_state_dict brings the saved lr back (Train_SMT.py:196-197)
+
+    B, N = int(train_bs), len(dataset)
+    n_full, tail = N // B, N % B
+    feed = tail_feed = None
+    if n_full:
+        trainer.enable_graph(warmup=1)
+        feed = PairFeed(dataset.tiles, scales, B, max_window, rows=rows, numerics=numerics, trainer=trainer if rows else None)
+    if tail:
+        tail_feed = PairFeed(dataset.tiles, scales, tail, max_window, rows=rows, numerics=numerics)
+    name = getattr(net, "name", type(net).__name__)
+    print(N, dataset.positive_pair_number, dataset.negative_pair_number)
+    iteration_history_train, loss_history_train = [], []
+    previous_time = 0.0
+    start_time = time.time()
+    for epoch in range(start_epoch, num_epochs):
+        lr = epoch_lr(lr0, epoch - start_epoch, milestones, gamma)
+        trainer.lr = lr                         # what the optimizer holds this epoch (checkpoint.optimizer_state_dict writes it)
+        table = dataset.epoch(epoch, B)
+        total = torch.zeros((), dtype=torch.float32, device=dev)
+        for s in range(len(table)):
+            if s < n_full:
+                total += trainer.step(*feed.fill(table.step(s)), lr=lr)
+            else:
+                total += trainer.step(*tail_feed.fill(table.step(s)), lr=lr, eager=True)
+        mean_loss = float(total) / len(table)
+        for f in (feed, tail_feed):
+            if f is not None:
+                f.check()
+        end_time = time.time()
+        iteration_history_train.append(epoch)
+        loss_history_train.append(mean_loss)
+        print(f"epoch {epoch + 1}/{num_epochs}: lr {lr:.3e} mean loss {mean_loss:.6f} time {end_time - start_time:.2f} s", flush=True)
+        if checkpoint_due(epoch):
+            os.makedirs(model_paras_path, exist_ok=True)
+            path = os.path.join(model_paras_path, checkpoint_name(epoch, num_epochs, name, time.localtime()))
+            save_checkpoint(path, trainer, epoch, end_time - start_time + previous_time)
+    print(f"training finished: {round(time.time() - start_time + previous_time, 2)} s")
+    return iteration_history_train, loss_history_train

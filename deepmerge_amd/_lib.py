@@ -53,6 +53,18 @@ class DmReduceItem(C.Structure):
                 ("nrows", C.c_int32), ("width", C.c_int32), ("split", C.c_int32), ("accumulate", C.c_int32)]
 
 
+class DmPairDraw(C.Structure):
+    _fields_ = [("pairs", C.c_void_p), ("pair_flag", C.c_void_p), ("poly_off", C.c_void_p), ("poly_pts", C.c_void_p),
+                ("pt_tile", C.c_void_p), ("pt_xy", C.c_void_p), ("pt_inner", C.c_void_p), ("pt_obj", C.c_void_p),
+                ("pt_region", C.c_void_p),
+                ("tile_id", C.c_void_p), ("xy", C.c_void_p), ("inner", C.c_void_p), ("obj", C.c_void_p),
+                ("region", C.c_void_p), ("flag", C.c_void_p),
+                ("point_id", C.c_void_p),
+                ("seed", C.c_uint64),
+                ("n_pairs", C.c_int32), ("n_poly", C.c_int32), ("n_poly_pts", C.c_int32), ("n_pts", C.c_int32),
+                ("epoch", C.c_int32), ("batch", C.c_int32)]
+
+
 class DmProfRow(C.Structure):
     _fields_ = [("name", C.c_char * 64), ("launches", C.c_int64), ("total_ms", C.c_double),
                 ("total_flops", C.c_double), ("total_bytes", C.c_double)]
@@ -116,6 +128,7 @@ SIGNATURES = {
     "dm_patch_pyramid": (_I, [_P, _I, _I, _I, _P, _P, _I, _I, _I, _I, _P, _P]),
     "dm_patch_pyramid_cols": (_I, [_P, _I, _I, _I, _P, _P, _I, _I, _I, _I, _I, _P, _I, _P]),
     "dm_pair_batch_gather": (_I, [_P, _I, _I, _I, _I, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _I, _P, _P, _P, _P]),
+    "dm_pair_epoch_draw": (_I, [C.POINTER(DmPairDraw), _P]),
     "dm_label_stats": (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P]),
     "dm_label_features": (_I, [_P, _P, _P, _P, _P, _I, _I, _P, _P]),
     "dm_rag_edges": (_I, [_P, _I, _I, _I, _P, _P, _I, _P, _P, _I, _P, _P, _P]),

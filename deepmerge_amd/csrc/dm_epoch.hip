@@ -1,0 +1,115 @@
+// Per-epoch pair draw (gfx950): the epoch's whole training sample table in ONE launch, already in the per-step blocked layout
+// feed.PairFeed consumes -- the device counterpart of the dataset rebuild the reference runs on the host every epoch
+// (MyUtils1.py:275-293: one uniform sample point per polygon of every pair, Python `random`) followed by
+// DataLoader(shuffle=True) (Train_SMT.py:218-220: a fresh permutation per epoch, torch's global RNG).
+// Here both are counter-based and keyed by (seed, epoch), so epoch e draws the same table whether or not the run was
+// interrupted (DESIGN.md 3.9 is the contract; tests/train_smt_ref.py restates it in numpy, bit for bit):
+//   philox(ctr, key)  Philox4x32-10 (Salmon et al. 2011), key = (seed & 0xffffffff, seed >> 32)
+//   shuffle           position j takes pair src = perm(j): a 4-round balanced Feistel network on [0, 2^b) (b = ceil(log2 N)
+//                     rounded up to even, >= 2; round r: L, R = R, L ^ (philox((R, epoch, 2, r))[0] & (2^h - 1)), h = b / 2),
+//                     cycle-walked until the value is < N
+//   draw              r = philox((src, epoch, 1, 0)): left point = poly_pts[poly_off[pl] + umulhi(r[0], cnt_l)], right point
+//                     likewise with r[1] -- keyed by the pair, so shuffle and draw are independent
+// One thread per position: integer VALU work plus a gather of the two 80-byte point rows.  A pair whose polygon id, point list or
+// point id is out of range (the host validates them once, at dataset construction) reads nothing out of range: its sample gets
+// point_id -1, tile id -1 (which the feed's gather flags) and zeros.
+#include "dm_common.h"
+
+namespace {
+
+constexpr uint32_t PHILOX_M0 = 0xD2511F53u, PHILOX_M1 = 0xCD9E8D57u;
+constexpr uint32_t PHILOX_W0 = 0x9E3779B9u, PHILOX_W1 = 0xBB67AE85u;
+
+__device__ __forceinline__ u32x4 philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1) {
+#pragma unroll
+  for (int r = 0; r < 10; ++r) {
+    if (r > 0) { k0 += PHILOX_W0; k1 += PHILOX_W1; }
+    const uint32_t hi0 = __umulhi(PHILOX_M0, c0), lo0 = PHILOX_M0 * c0;
+    const uint32_t hi1 = __umulhi(PHILOX_M1, c2), lo1 = PHILOX_M1 * c2;
+    const uint32_t n0 = hi1 ^ c1 ^ k0, n2 = hi0 ^ c3 ^ k1;
+    c0 = n0; c1 = lo1; c2 = n2; c3 = lo0;
+  }
+  u32x4 out;
+  out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
+  return out;
+}
+
+// perm(j) for j < n: the Feistel bijection of [0, 2^(2h)), cycle-walked back into [0, n)
+__device__ __forceinline__ uint32_t epoch_perm(uint32_t j, uint32_t n, int h, uint32_t epoch, uint32_t k0, uint32_t k1) {
+  const uint32_t mask = (1u << h) - 1u;
+  uint32_t x = j;
+  do {
+    uint32_t L = x >> h, R = x & mask;
+#pragma unroll
+    for (uint32_t r = 0; r < 4; ++r) {
+      const uint32_t f = philox4x32_10(R, epoch, 2u, r, k0, k1)[0] & mask;
+      const uint32_t t = L ^ f;
+      L = R;
+      R = t;
+    }
+    x = (L << h) | R;
+  } while (x >= n);
+  return x;
+}
+
+// the global point id of the sample drawn from polygon p with random word u; -1 when p or its point list is out of range
+__device__ __forceinline__ int32_t draw_point(const DmPairDraw &a, int32_t p, uint32_t u) {
+  if (p < 0 || p >= a.n_poly) return -1;
+  const int32_t lo = a.poly_off[p], hi = a.poly_off[p + 1];
+  if (lo < 0 || hi <= lo || hi > a.n_poly_pts) return -1;
+  const int32_t pt = a.poly_pts[lo + (int32_t)__umulhi(u, (uint32_t)(hi - lo))];
+  return (pt >= 0 && pt < a.n_pts) ? pt : -1;
+}
+
+__device__ __forceinline__ void write_sample(const DmPairDraw &a, int64_t row, int32_t pt) {
+  const bool ok = pt >= 0;
+  a.tile_id[row] = ok ? a.pt_tile[pt] : -1;
+  a.xy[2 * row] = ok ? a.pt_xy[2 * (int64_t)pt] : 0;
+  a.xy[2 * row + 1] = ok ? a.pt_xy[2 * (int64_t)pt + 1] : 0;
+  a.inner[row] = ok ? a.pt_inner[pt] : 0;
+  a.obj[row] = ok ? a.pt_obj[pt] : 0;
+  const float *src = a.pt_region + 15 * (int64_t)(ok ? pt : 0);
+  float *dst = a.region + 15 * row;
+#pragma unroll
+  for (int c = 0; c < 15; ++c) dst[c] = ok ? src[c] : 0.0f;
+  if (a.point_id) a.point_id[row] = pt;
+}
+
+__global__ __launch_bounds__(256) void pair_epoch_draw_kernel(DmPairDraw a, int h) {
+  const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= a.n_pairs) return;
+  const uint32_t k0 = (uint32_t)(a.seed & 0xffffffffull), k1 = (uint32_t)(a.seed >> 32);
+  const uint32_t epoch = (uint32_t)a.epoch;
+  const uint32_t src = epoch_perm((uint32_t)j, (uint32_t)a.n_pairs, h, epoch, k0, k1);
+  const u32x4 r = philox4x32_10(src, epoch, 1u, 0u, k0, k1);
+  const int32_t pl = a.pairs[2 * (int64_t)src], pr = a.pairs[2 * (int64_t)src + 1];
+  // step s owns rows [2 s batch, 2 s batch + 2 b_s) as [left b_s; right b_s]
+  const int64_t batch = a.batch, s = j / batch;
+  const int64_t b_s = min(batch, (int64_t)a.n_pairs - s * batch);
+  const int64_t row_l = s * batch + j;                 // 2 s batch + (j - s batch)
+  write_sample(a, row_l, draw_point(a, pl, r[0]));
+  write_sample(a, row_l + b_s, draw_point(a, pr, r[1]));
+  a.flag[j] = (float)a.pair_flag[src];
+}
+
+}  // namespace
+
+extern "C" int dm_pair_epoch_draw(const DmPairDraw *args, void *stream) {
+  DM_REQUIRE(args != nullptr, DM_ERR_BAD_SHAPE, "dm_pair_epoch_draw: null arguments");
+  const DmPairDraw &a = *args;
+  DM_REQUIRE(a.n_pairs >= 1 && a.n_pairs <= (1 << 30), DM_ERR_BAD_SHAPE, "dm_pair_epoch_draw: %d pairs (1 .. 2^30)", a.n_pairs);
+  DM_REQUIRE(a.batch >= 1, DM_ERR_BAD_SHAPE, "dm_pair_epoch_draw: batch %d < 1", a.batch);
+  DM_REQUIRE(a.epoch >= 0, DM_ERR_BAD_SHAPE, "dm_pair_epoch_draw: epoch %d < 0", a.epoch);
+  DM_REQUIRE(a.n_poly >= 1 && a.n_poly_pts >= 1 && a.n_pts >= 1, DM_ERR_BAD_SHAPE,
+             "dm_pair_epoch_draw: empty polygon table (%d polygons, %d polygon points, %d points)", a.n_poly, a.n_poly_pts, a.n_pts);
+  DM_REQUIRE(a.pairs && a.pair_flag && a.poly_off && a.poly_pts && a.pt_tile && a.pt_xy && a.pt_inner && a.pt_obj && a.pt_region,
+             DM_ERR_BAD_SHAPE, "dm_pair_epoch_draw: bad arguments (null input)");
+  DM_REQUIRE(a.tile_id && a.xy && a.inner && a.obj && a.region && a.flag, DM_ERR_BAD_SHAPE, "dm_pair_epoch_draw: bad arguments (null output)");
+  int b = 2;
+  while ((1ll << b) < (long long)a.n_pairs) b += 2;      // ceil(log2 N), rounded up to even, >= 2
+  const int threads = 256;
+  const int blocks = (int)((a.n_pairs + threads - 1) / threads);
+  hipLaunchKernelGGL(pair_epoch_draw_kernel, dim3(blocks), dim3(threads), 0, reinterpret_cast<hipStream_t>(stream), a, b / 2);
+  DM_LAUNCH_CHECK("dm_pair_epoch_draw");
+  return DM_OK;
+}

@@ -817,6 +817,38 @@ def pair_batch_gather(tiles: torch.Tensor, tile_id: Optional[torch.Tensor], xy: 
                                           _ptr(region_features), _ptr(designed), _ptr(error_flag), _stream()), "dm_pair_batch_gather")
 
 
+def pair_epoch_draw(pairs: torch.Tensor, pair_flag: torch.Tensor, poly_off: torch.Tensor, poly_pts: torch.Tensor, pt_tile: torch.Tensor,
+                    pt_xy: torch.Tensor, pt_inner: torch.Tensor, pt_obj: torch.Tensor, pt_region: torch.Tensor, seed: int, epoch: int, batch: int,
+                    tile_id: torch.Tensor, xy: torch.Tensor, inner: torch.Tensor, obj: torch.Tensor, region: torch.Tensor, flag: torch.Tensor,
+                    point_id: Optional[torch.Tensor] = None) -> None:
+    """One epoch's sample table in ONE launch (dm_pair_epoch_draw): the shuffled per-pair point draw keyed by
+    (seed, epoch), written into the caller's tensors in the per-step blocked layout (step s = rows [2 s batch, 2 s batch + 2 b_s),
+    [left b_s; right b_s]).  Inputs: pairs int32 [N, 2], pair_flag int32 [N], the polygon -> points CSR poly_off int32 [n_poly + 1] /
+    poly_pts int32, the point table pt_tile / pt_inner / pt_obj int32 [n_pts], pt_xy int32 [n_pts, 2], pt_region float32 [n_pts, 15].
+    Outputs: tile_id / inner / obj int32 [2N], xy int32 [2N, 2], region float32 [2N, 15], flag float32 [N], point_id int32 [2N] or None."""
+    if pairs.dim() != 2 or pairs.shape[1] != 2:
+        raise ValueError(f"pair_epoch_draw: pairs must be [N, 2], got {tuple(pairs.shape)}")
+    N, n_pts = pairs.shape[0], pt_tile.numel()
+    cols = {"pairs": (pairs, torch.int32, 2 * N), "pair_flag": (pair_flag, torch.int32, N), "poly_off": (poly_off, torch.int32, poly_off.numel()),
+            "poly_pts": (poly_pts, torch.int32, poly_pts.numel()), "pt_tile": (pt_tile, torch.int32, n_pts), "pt_xy": (pt_xy, torch.int32, 2 * n_pts),
+            "pt_inner": (pt_inner, torch.int32, n_pts), "pt_obj": (pt_obj, torch.int32, n_pts), "pt_region": (pt_region, torch.float32, 15 * n_pts),
+            "tile_id": (tile_id, torch.int32, 2 * N), "xy": (xy, torch.int32, 4 * N), "inner": (inner, torch.int32, 2 * N),
+            "obj": (obj, torch.int32, 2 * N), "region": (region, torch.float32, 30 * N), "flag": (flag, torch.float32, N),
+            "point_id": (point_id, torch.int32, 2 * N)}
+    _need_cuda(*(t for t, _, _ in cols.values()))
+    for name, (t, dtype, numel) in cols.items():
+        if t is not None and (t.dtype != dtype or not t.is_contiguous() or t.numel() != numel):
+            raise ValueError(f"pair_epoch_draw: {name} must be a contiguous {dtype} tensor of {numel} elements, got {t.dtype} {tuple(t.shape)}")
+    a = _lib.DmPairDraw()
+    for name, (t, _, _) in cols.items():
+        setattr(a, name, _ptr(t))
+    a.seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+    a.n_pairs, a.n_poly, a.n_poly_pts, a.n_pts = N, poly_off.numel() - 1, poly_pts.numel(), n_pts
+    a.epoch, a.batch = int(epoch), int(batch)
+    with torch.cuda.device(pairs.device):
+        check(_lib.lib().dm_pair_epoch_draw(C.byref(a), _stream()), "dm_pair_epoch_draw")
+
+
 def patch_pyramid_cols(tile: torch.Tensor, xy: torch.Tensor, windows: torch.Tensor, target: int, grid: int = 8,
                        dtype: torch.dtype = torch.bfloat16, max_window: Optional[int] = None, resize: str = "opencv") -> PatchCols:
     """One scale of the patch pyramid as patch-embed GEMM rows (dm_patch_pyramid_cols); `resize` as in `patch_pyramid`."""

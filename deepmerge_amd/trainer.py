@@ -182,6 +182,13 @@ def _v3_forward():
     return ShfitScaleFormer_v3.forward
 
 
+def stacked_pair_inputs(net: torch.nn.Module) -> bool:
+    """Whether the model takes both sides of a pair batch stacked along the batch (forward_pair_batched, the v3 family): the form
+    whose captured step a feed.PairFeed fills with patch-embed rows directly."""
+    return type(net).__dict__.get("forward_pair_batched") is not None or \
+        (hasattr(net, "forward_pair_batched") and type(net).forward is _v3_forward())
+
+
 class _Cuts:
     """Autograd cut points of one forward pass.  The model calls `net._dp_cut(x)` at its segment boundaries (after every stage-0
     block for the v3 family); the value that flows on is a detached leaf, so the backward pass can be run segment by segment:
@@ -385,9 +392,7 @@ class PairTrainer:
     def _static_inputs(self, st, left, left_designed, right, right_designed, flag):
         # models that take the two sides pre-stacked ([left; right] along the batch) get static buffers of that form, so
         # the step's inputs are copied once and the captured graph holds no torch.cat
-        batched = type(self.net).__dict__.get("forward_pair_batched") is not None or \
-            (hasattr(self.net, "forward_pair_batched") and type(self.net).forward is _v3_forward())
-        if batched:
+        if stacked_pair_inputs(self.net):
             both = [ops.cat_batch(l, r) for l, r in zip(left, right)]      # (image tensors or ops.PatchCols: patch-embed rows from a feed)
             Bp = left[0].shape[0]
             st["left"], st["right"] = [t[:Bp] for t in both], [t[Bp:] for t in both]
@@ -568,12 +573,13 @@ class PairTrainer:
 
     # -- the step ----------------------------------------------------------------------------------
     def step(self, left: Sequence[torch.Tensor], left_designed, right: Sequence[torch.Tensor], right_designed, flag,
-             lr: Optional[float] = None) -> torch.Tensor:
+             lr: Optional[float] = None, eager: bool = False) -> torch.Tensor:
         """forward -> Loss -> zero_grad -> backward -> (all-reduce) -> Adam.  Returns the local loss tensor
         (no host sync; the reference's per-step `.item()` at Train_SMT.py:301 is left to the caller).
         After enable_graph() the same work is replayed from captured hipGraphs (the returned tensor is then a
-        static buffer that the next step overwrites)."""
-        if self._graph is not None:
+        static buffer that the next step overwrites).  eager=True runs this step's launches directly even after enable_graph()
+        (a batch of another size, e.g. an epoch's partial last batch) and leaves the graph and its warm-up count alone."""
+        if self._graph is not None and not eager:
             self.net.train()
             return self._graph_step(left, left_designed, right, right_designed, flag, lr)
         return self._eager_step(left, left_designed, right, right_designed, flag, lr)

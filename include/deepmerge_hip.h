@@ -44,7 +44,8 @@ typedef enum {
 
 /* ---- library ------------------------------------------------------------------------- */
 int dm_abi_version(void);   /* 2: dm_patch_pyramid / dm_patch_pyramid_cols take a resize rule; 3: table-reading and split-bf16 attention entry points, dm_split_bf16_colsum (round 3);
-                             * 4: DmGemmArgs.k_fold / a_fold / b_fold, dm_split_bf16_planes (round 4); 5: dm_pair_batch_gather (round 5); 6: dm_gemm_grouped (round 5) */
+                             * 4: DmGemmArgs.k_fold / a_fold / b_fold, dm_split_bf16_planes (round 4); 5: dm_pair_batch_gather (round 5); 6: dm_gemm_grouped (round 5);
+                             * additive in 6: dm_pairwise_distance, dm_pair_epoch_draw */
 const char *dm_last_error(void);
 /* Name of the code object architecture the library was built for ("gfx950"). */
 const char *dm_arch(void);
@@ -401,6 +402,31 @@ int dm_pair_batch_gather(const uint8_t *tiles, int32_t n_tiles, int32_t bands, i
                          const int32_t *xy, const int32_t *inner, const int32_t *obj, int32_t scale_index, int32_t max_window,
                          int32_t P, int32_t target, int32_t grid, int32_t resize_rule, void *out, int32_t dtype,
                          const float *region_features, float *designed, int32_t *error_flag, void *stream);
+
+/* ---- per-epoch pair draw: the epoch's whole sample table in one launch (additive in ABI 6) ---------------------------------
+ * Replaces the dataset rebuild of every epoch (MyUtils1.py:275-293: for each pair of the positive / negative lists, one sample
+ * point drawn uniformly from each polygon's `PointID` list) and the shuffled loader over it (Train_SMT.py:218-220:
+ * DataLoader(shuffle=True), drop_last=False) with a counter-based draw keyed by (seed, epoch) -- DESIGN.md 3.9 states the
+ * Philox4x32-10 / Feistel contract.  Nothing is read back.
+ *   pairs int32 [N, 2] global polygon ids, pair_flag int32 [N] (1 = merge); polygon -> points CSR poly_off int32 [n_poly + 1],
+ *   poly_pts int32 [n_poly_pts]; point table pt_tile int32 [n_pts], pt_xy int32 [n_pts, 2] (pixels), pt_inner / pt_obj int32
+ *   [n_pts], pt_region float32 [n_pts, 15].
+ *   Output in per-step blocked layout: position j belongs to step s = j / batch with b_s = min(batch, N - s batch) pairs; its
+ *   left sample goes to row 2 s batch + (j - s batch), its right sample to that row + b_s (rows [2 s batch, 2 s batch + 2 b_s)
+ *   are step s's feed.PairTable).  tile_id int32 [2N], xy int32 [2N, 2], inner / obj int32 [2N], region float32 [2N, 15],
+ *   flag float32 [N] in position order, point_id int32 [2N] (may be NULL).  A polygon id, point list or point id out of range
+ *   reads nothing out of range: that sample gets point_id -1, tile id -1 and zeros. */
+typedef struct {
+  const int32_t *pairs, *pair_flag, *poly_off, *poly_pts;
+  const int32_t *pt_tile, *pt_xy, *pt_inner, *pt_obj;
+  const float *pt_region;
+  int32_t *tile_id, *xy, *inner, *obj;
+  float *region, *flag;
+  int32_t *point_id;
+  uint64_t seed;
+  int32_t n_pairs, n_poly, n_poly_pts, n_pts, epoch, batch;
+} DmPairDraw;
+int dm_pair_epoch_draw(const DmPairDraw *args, void *stream);
 
 /* ---- region-adjacency graph + superpixel statistics from a label raster ---------------------------
  * Replaces, on the device, the inputs the reference reads from files written by external GIS software: the RAG edge
