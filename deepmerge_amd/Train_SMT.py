@@ -9,20 +9,27 @@ feed.PairFeed gather straight into the captured step's inputs and a PairTrainer 
 Resume (`is_retrained`): weights, Adam moments and the saved lr come back from the checkpoint; `start_epoch = epoch + 1`, and the
 milestones are counted again from the resumed epoch, as upstream (the scheduler is created afresh and its state is not saved).
 Because the draw is keyed by (seed, epoch), a resumed run sees the same data as an uninterrupted one.
+
+Validation (`val_dataset=`): after each epoch's steps and loss read, and before the checkpoint, one evaluate.PairEvaluator (built
+once, with the training margin) runs over the held-out pairs -- loss and merge P/R/F at the margin, logged through
+callbacks.LossHistory when `log_dir` is given.  It reads no RNG and touches no parameter, gradient, optimizer state or captured
+graph input, so the training run is the same, bit for bit, with or without it.
 """
 from __future__ import annotations
 
 import os
 import time
 from collections import Counter
-from typing import List, Sequence, Tuple
+from typing import List, Optional, Sequence, Tuple
 
 import torch
 import torch.distributed as dist
 
 from . import ops
+from .callbacks import LossHistory
 from .checkpoint import load_checkpoint, save_checkpoint
 from .dataset import PairDataset
+from .evaluate import PairEvaluator, format_result
 from .ExtractFeatures import Euclidean_distance  # noqa: F401  (Train_SMT.Euclidean_distance, Train_SMT.py:115-131)
 from .feed import PairFeed
 from .trainer import PairTrainer, stacked_pair_inputs
@@ -56,12 +63,22 @@ def checkpoint_name(epoch: int, num_epochs: int, net_name: str, t: time.struct_t
 
 def train(net, margin, train_bs, lr_init, normMean, normStd, lamda, belta, is_retrained=False, checkpoint_path=None, *,
           dataset: PairDataset = None, num_epochs: int = NUM_EPOCHS, milestones: Sequence[int] = (40, 80), gamma: float = 0.2,
-          model_paras_path: str = MODEL_PARAS_PATH) -> Tuple[List[int], List[float]]:
+          model_paras_path: str = MODEL_PARAS_PATH, val_dataset: Optional[PairDataset] = None, val_batch: int = 1000,
+          val_thresholds: Optional[Sequence[float]] = None, log_dir: Optional[str] = None,
+          val_history: Optional[list] = None) -> Tuple[List[int], List[float]]:
     """`Train_SMT.train` with the reference's positional signature (normMean / normStd are unused, as upstream; lamda / belta go
     to Loss).  `dataset` replaces the reference's hard-coded shapefile folders; the draw's seed is the dataset's.  Returns
-    (epoch indices, per-epoch mean loss = sum of step losses / number of steps), one entry per epoch run."""
+    (epoch indices, per-epoch mean loss = sum of step losses / number of steps), one entry per epoch run.
+
+    val_dataset: a held-out PairDataset (not `dataset` itself: a dataset reuses one table buffer), evaluated after every epoch by
+    evaluate.PairEvaluator(net, val_dataset, val_batch, margin, val_thresholds); `(epoch, PairEvalResult)` is appended to
+    `val_history` when given.  log_dir: a callbacks.LossHistory there gets (mean train loss, val loss, F at the margin) per epoch --
+    without val_dataset, what upstream writes: (mean loss, mean loss, elapsed seconds rounded to 2 places)."""
     if dataset is None:
         raise ValueError("train() needs dataset=PairDataset.from_arrays(...) (the reference's hard-coded folders are not portable)")
+    if val_dataset is not None and val_dataset is dataset:
+        raise ValueError("val_dataset must not be the training dataset: a PairDataset keeps one table buffer, and the held-out pairs "
+                         "must be pairs the model does not train on")
     if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
         raise NotImplementedError("train() runs on one GPU; data-parallel sharding of the epoch is not implemented")
     if int(train_bs) < 1:
@@ -91,6 +108,9 @@ def train(net, margin, train_bs, lr_init, normMean, normStd, lamda, belta, is_re
         feed = PairFeed(dataset.tiles, scales, B, max_window, rows=rows, numerics=numerics, trainer=trainer if rows else None)
     if tail:
         tail_feed = PairFeed(dataset.tiles, scales, tail, max_window, rows=rows, numerics=numerics)
+    evaluator = PairEvaluator(net, val_dataset, batch=val_batch, margin=margin, thresholds=val_thresholds) \
+        if val_dataset is not None else None
+    history = LossHistory(log_dir) if log_dir is not None else None
     name = getattr(net, "name", type(net).__name__)
     print(N, dataset.positive_pair_number, dataset.negative_pair_number)
     iteration_history_train, loss_history_train = [], []
@@ -110,10 +130,21 @@ def train(net, margin, train_bs, lr_init, normMean, normStd, lamda, belta, is_re
         for f in (feed, tail_feed):
             if f is not None:
                 f.check()
+        val = evaluator.run() if evaluator is not None else None
         end_time = time.time()
         iteration_history_train.append(epoch)
         loss_history_train.append(mean_loss)
-        print(f"epoch {epoch + 1}/{num_epochs}: lr {lr:.3e} mean loss {mean_loss:.6f} time {end_time - start_time:.2f} s", flush=True)
+        line = f"epoch {epoch + 1}/{num_epochs}: lr {lr:.3e} mean loss {mean_loss:.6f}"
+        if val is not None:
+            line += " " + format_result(val)
+            if val_history is not None:
+                val_history.append((epoch, val))
+        print(f"{line} time {end_time - start_time:.2f} s", flush=True)
+        if history is not None:
+            if val is not None:
+                history.append_loss(mean_loss, val.loss, val.f_score)
+            else:                               # upstream's stand-ins (Train_SMT.py:350)
+                history.append_loss(mean_loss, mean_loss, round(end_time - start_time, 2))
         if checkpoint_due(epoch):
             os.makedirs(model_paras_path, exist_ok=True)
             path = os.path.join(model_paras_path, checkpoint_name(epoch, num_epochs, name, time.localtime()))

@@ -922,6 +922,63 @@ def edge_similarity(pooled: torch.Tensor, edges: torch.Tensor, margin: float = 1
     return simi, merge
 
 
+def contrastive_terms(a: torch.Tensor, b: torch.Tensor, flag: torch.Tensor, margin: float = 1.0,
+                      d2: Optional[torch.Tensor] = None, term: Optional[torch.Tensor] = None):
+    """Per-pair contrastive terms (dm_contrastive_terms, the per-pair form of Losses.py:34-38): a, b fp32 [B, D], flag fp32 [B] ->
+    (d2, term) fp32 [B], d2 = |a - b|^2 and term = f*d2 + (1-f)*max(margin - d2, 0) in the pinned order of DESIGN.md 3.10.
+    d2 / term: contiguous fp32 [B] tensors to write into (e.g. views of a larger buffer); allocated when None.  No host sync."""
+    _need_cuda(a, b, flag, d2, term)
+    if a.dim() != 2 or tuple(a.shape) != tuple(b.shape) or a.shape[0] < 1 or a.shape[1] < 1:
+        raise ValueError(f"contrastive_terms: a and b must be the same non-empty [B, D], got {tuple(a.shape)} and {tuple(b.shape)}")
+    B = a.shape[0]
+    for name, t, shape in (("a", a, tuple(a.shape)), ("b", b, tuple(a.shape)), ("flag", flag, (B,)), ("d2", d2, (B,)), ("term", term, (B,))):
+        if t is not None and (t.dtype != torch.float32 or not t.is_contiguous() or tuple(t.shape) != shape):
+            raise ValueError(f"contrastive_terms: {name} must be a contiguous float32 tensor of shape {shape}, got {t.dtype} {tuple(t.shape)}")
+    d2 = torch.empty(B, dtype=torch.float32, device=a.device) if d2 is None else d2
+    term = torch.empty(B, dtype=torch.float32, device=a.device) if term is None else term
+    with torch.cuda.device(a.device):
+        check(_lib.lib().dm_contrastive_terms(a.data_ptr(), b.data_ptr(), flag.data_ptr(), float(margin), d2.data_ptr(), term.data_ptr(),
+                                              B, a.shape[1], _stream()), "dm_contrastive_terms")
+    return d2, term
+
+
+PAIR_EVAL_MAX_THRESHOLDS = 1024
+
+
+def pair_eval_summary(term: torch.Tensor, simi: torch.Tensor, flag: torch.Tensor, thresholds: torch.Tensor, validate: bool = True,
+                      out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """One pass over N evaluated pairs (dm_pair_eval_summary): term / simi / flag fp32 [N], thresholds fp32 [T] on the device
+    (finite, strictly ascending, 1 <= T <= 1024).  Returns the result block, an int64 [2 T + 2] device tensor: element 0 holds the
+    fp64 bits of loss_sum (`block[:1].view(torch.float64)`), element 1 n_pos, elements 2.. merged [2, T] (row 0: flag 1 pairs with
+    simi < thresholds[j], row 1: the others).  validate: one host read of the thresholds to check them (pass False when the caller
+    has); the pairs themselves are never read back.  out: an int64 [2 T + 2] tensor to write the block into."""
+    _need_cuda(term, simi, flag, thresholds, out)
+    N = term.numel()
+    for name, t in (("term", term), ("simi", simi), ("flag", flag)):
+        if t.dtype != torch.float32 or not t.is_contiguous() or t.dim() != 1 or t.numel() != N:
+            raise ValueError(f"pair_eval_summary: {name} must be a contiguous float32 [N] tensor (N = {N}), got {t.dtype} {tuple(t.shape)}")
+    if not 1 <= N <= 2 ** 31 - 1:
+        raise ValueError(f"pair_eval_summary: N = {N} pairs (1 .. 2^31 - 1)")
+    T = thresholds.numel()
+    if thresholds.dtype != torch.float32 or not thresholds.is_contiguous() or thresholds.dim() != 1 or not 1 <= T <= PAIR_EVAL_MAX_THRESHOLDS:
+        raise ValueError(f"pair_eval_summary: thresholds must be a contiguous float32 [T] tensor with 1 <= T <= {PAIR_EVAL_MAX_THRESHOLDS}, "
+                         f"got {thresholds.dtype} {tuple(thresholds.shape)}")
+    if validate:
+        th = thresholds.cpu()
+        if not bool(torch.isfinite(th).all()) or (T > 1 and not bool((th[1:] > th[:-1]).all())):
+            raise ValueError("pair_eval_summary: thresholds must be finite and strictly ascending")
+    if out is None:
+        out = torch.empty(2 * T + 2, dtype=torch.int64, device=term.device)
+    elif out.dtype != torch.int64 or not out.is_contiguous() or out.numel() != 2 * T + 2:
+        raise ValueError(f"pair_eval_summary: out must be a contiguous int64 tensor of {2 * T + 2} elements")
+    lib = _lib.lib()
+    ws = workspace(lib.dm_pair_eval_workspace_bytes(N, T), term.device, slot="eval")
+    with torch.cuda.device(term.device):
+        check(lib.dm_pair_eval_summary(term.data_ptr(), simi.data_ptr(), flag.data_ptr(), N, thresholds.data_ptr(), T, ws.data_ptr(),
+                                       out.data_ptr(), out.data_ptr() + 16, out.data_ptr() + 8, _stream()), "dm_pair_eval_summary")
+    return out
+
+
 _DIST_DTYPES = {torch.float32: DM_F32, torch.float64: _lib.DM_F64}
 
 

@@ -45,7 +45,7 @@ typedef enum {
 /* ---- library ------------------------------------------------------------------------- */
 int dm_abi_version(void);   /* 2: dm_patch_pyramid / dm_patch_pyramid_cols take a resize rule; 3: table-reading and split-bf16 attention entry points, dm_split_bf16_colsum (round 3);
                              * 4: DmGemmArgs.k_fold / a_fold / b_fold, dm_split_bf16_planes (round 4); 5: dm_pair_batch_gather (round 5); 6: dm_gemm_grouped (round 5);
-                             * additive in 6: dm_pairwise_distance, dm_pair_epoch_draw */
+                             * additive in 6: dm_pairwise_distance, dm_pair_epoch_draw, dm_contrastive_terms, dm_pair_eval_summary */
 const char *dm_last_error(void);
 /* Name of the code object architecture the library was built for ("gfx950"). */
 const char *dm_arch(void);
@@ -427,6 +427,26 @@ typedef struct {
   int32_t n_pairs, n_poly, n_poly_pts, n_pts, epoch, batch;
 } DmPairDraw;
 int dm_pair_epoch_draw(const DmPairDraw *args, void *stream);
+
+/* ---- held-out pair evaluation (additive in ABI 6; deepmerge_amd/evaluate.py) ---------------------------
+ * Per-pair contrastive terms -- the per-pair form of the reference's contrastive loss (Losses.py:34-38, before its mean):
+ *   d2[r] = sum_c (a[r,c] - b[r,c])^2,   term[r] = f*d2 + (1-f)*max(margin - d2, 0),   f = flag[r]
+ * a, b [B, D] fp32 row-major, flag / d2 / term [B] fp32.  The order is pinned (no FMA contraction): lane l of the pair's wave
+ * sums its columns l, l+64, ... in order, the partials are combined by the xor butterfly 32, 16, ..., 1, then the term is
+ * evaluated left to right (a NaN d2 gives a NaN term).  B, D >= 1 (DM_ERR_BAD_SHAPE). */
+int dm_contrastive_terms(const float *a, const float *b, const float *flag, float margin, float *d2, float *term, int32_t B, int32_t D,
+                         void *stream);
+/* One pass over the N pairs of an evaluation -- what the reference meant to log per epoch as val_loss / f_score
+ * (callbacks.py:41-57 `append_loss`, called at Train_SMT.py:350 with the training loss and the elapsed time in their place):
+ *   merged[0][j] = #{r : flag[r] == 1 and simi[r] < thresholds[j]},  merged[1][j] the same for flag[r] != 1   (int64 [2, T])
+ *   n_pos = #{r : flag[r] == 1},   loss_sum = sum_r term[r] in fp64
+ * The merge rule is the sweep's (`simi < margin`): simi == t does not merge and a NaN simi never merges.  thresholds fp32 [T] on
+ * the device, finite and strictly ascending (the caller checks), 1 <= T <= 1024 (DM_ERR_UNSUPPORTED); 1 <= N <= 2^31 - 1
+ * (DM_ERR_BAD_SHAPE).  Counts are exact; loss_sum is summed over a partition that depends on N only, in a fixed order (bit-identical
+ * from run to run).  workspace: dm_pair_eval_workspace_bytes(N, T) bytes, 8-byte aligned.  No host synchronisation. */
+int64_t dm_pair_eval_workspace_bytes(int64_t N, int32_t T);
+int dm_pair_eval_summary(const float *term, const float *simi, const float *flag, int64_t N, const float *thresholds, int32_t T,
+                         void *workspace, double *loss_sum, int64_t *merged, int64_t *n_pos, void *stream);
 
 /* ---- region-adjacency graph + superpixel statistics from a label raster ---------------------------
  * Replaces, on the device, the inputs the reference reads from files written by external GIS software: the RAG edge
