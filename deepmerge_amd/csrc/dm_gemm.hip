@@ -38,13 +38,13 @@
 #include "dm_prof.h"
 
 // dm_gemm256.hip: the 256x256 LDS-DMA pipeline for large bf16 products
-bool dm_gemm256_plan(GemmParams &p, int layout, int ab_dtype, bool can_split, long long workspace_bytes, int user_split);
+bool dm_gemm256_plan(GemmParams &p, const GemmSwitches &sw, int layout, int ab_dtype, bool can_split, long long workspace_bytes, int user_split);
 void dm_gemm256_launch(const GemmParams &p, int layout, hipStream_t s);
-int dm_gemm_ring_plan(GemmParams &p, int layout, int ab_dtype, bool aligned8);      // dm_gemm_ring.hip
+int dm_gemm_ring_plan(GemmParams &p, const GemmSwitches &sw, int layout, int ab_dtype, bool aligned8);      // dm_gemm_ring.hip
 void dm_gemm_ring_launch(const GemmParams &p, int wm, hipStream_t s);
-bool dm_gemm_q4_plan(GemmParams &p, int layout, int ab_dtype, bool aligned8);      // dm_gemm_q4.hip
+bool dm_gemm_q4_plan(GemmParams &p, const GemmSwitches &sw, int layout, int ab_dtype, bool aligned8);      // dm_gemm_q4.hip
 void dm_gemm_q4_launch(const GemmParams &p, int layout, hipStream_t s);
-int dm_gemm_w4_plan(GemmParams &p, int layout, int ab_dtype, bool aligned8, bool can_split, long long workspace_bytes);   // dm_gemm_w4.hip (grid size, 0 = not taken)
+int dm_gemm_w4_plan(GemmParams &p, const GemmSwitches &sw, int layout, int ab_dtype, bool aligned8, bool can_split, long long workspace_bytes);   // dm_gemm_w4.hip (grid size, 0 = not taken)
 void dm_gemm_w4_launch(const GemmParams &p, int layout, int grid, hipStream_t s);
 int dm_gemm_w4_grouped(GemmParams *ps, int n, hipStream_t s, bool launch, const DmGroupedExtra &x);      // dm_gemm_w4.hip: n weight gradients in one launch (0 = not taken, 1 = one K slice per tile, 2 = stream-K)
 long long dm_gemm_w4_grouped_ws_bytes();
@@ -314,7 +314,7 @@ __global__ __launch_bounds__(NTHREADS, (TM == 4 ? WG_PER_CU : 4)) void gemm_kern
   // trip per pass (proj forward reads 50 MB of residual stream, the dgrad of fc2 100 MB of GELU').  One row per lane, one dword
   // per 128-byte line; the values are not read before the epilogue (the asm at its top is the use that keeps the loads alive).
   float tv0 = 0.f, tv1 = 0.f;
-  const int touch_at = (TM == 4 && sizeof(T) == 2 && p.split_k <= 1 && !(p.debug & 0x200) && (p.residual || (p.aux && (p.epilogue == DM_EPI_DGELU || p.epilogue == DM_EPI_MUL))))
+  const int touch_at = (TM == 4 && sizeof(T) == 2 && p.split_k <= 1 && !(p.debug & DM_DBG_TOUCH_OFF) && (p.residual || (p.aux && (p.epilogue == DM_EPI_DGELU || p.epilogue == DM_EPI_MUL))))
                            ? max(0, nk - 4) : -1;
   for (int kt = 0; kt < nk; ++kt) {
     const int cur = kt & 1;
@@ -374,7 +374,7 @@ __global__ __launch_bounds__(NTHREADS, (TM == 4 ? WG_PER_CU : 4)) void gemm_kern
     }
   }
 #ifdef DM_GEMM_ABLATE
-  if (p.debug & 0x800) {                 // (ablation builds, DM_GEMM_NOEPI=1: no epilogue at all -- what the K loops alone cost; the asm keeps the MFMAs alive)
+  if (p.debug & DM_DBG_NO_EPILOGUE) {                 // (ablation builds, DM_GEMM_NOEPI=1: no epilogue at all -- what the K loops alone cost; the asm keeps the MFMAs alive)
 #pragma unroll
     for (int i = 0; i < TM; ++i)
 #pragma unroll
@@ -401,7 +401,7 @@ __global__ __launch_bounds__(NTHREADS, (TM == 4 ? WG_PER_CU : 4)) void gemm_kern
     // through a private piece of the (now idle) operand stage, so bias / residual / aux reads and the C stores are 128-byte rows instead
     // of 8-byte strips of 16 different rows (the dgrad of fc2 reads 100 MB of GELU' that way): in the step 137 -> 120 us for that
     // product, 53 -> 47 us for the proj forward.  (The 64 x 64 variant gained nothing from the same change and keeps its strips.)
-    const bool rows_ok = !(p.debug & 0x100) && (p.N % 8 == 0) && (p.ldc % 8 == 0) && (p.aux == nullptr || p.ldaux % 8 == 0) &&
+    const bool rows_ok = !(p.debug & DM_DBG_ROWS_OFF) && (p.N % 8 == 0) && (p.ldc % 8 == 0) && (p.aux == nullptr || p.ldaux % 8 == 0) &&
                          (p.rows_per_group == 0 || p.group_stride % 8 == 0) && (p.residual == nullptr || p.ldr % 8 == 0);
     if (rows_ok) {
       static_assert(2 * LDS_STAGES * G::STAGE >= 4 * 16 * DM_EPI_PITCH, "epilogue staging must fit the operand stage");
@@ -411,7 +411,7 @@ __global__ __launch_bounds__(NTHREADS, (TM == 4 ? WG_PER_CU : 4)) void gemm_kern
     }
   }
 #ifndef DM_TM2_STRIPS_OLD      // (A/B builds: the one-step strips below keep the 64 x 64 kernel at 64-76 registers instead of 94; step A/B: no difference)
-  if (TM == 2 && !(p.debug & 0x400)) {
+  if (TM == 2 && !(p.debug & DM_DBG_LEAN_OFF)) {
     // 64 x 64 tiles (the 4096- / 1024-token stages, the patch embeds): all loads of the wave's four strips first, then the stores
     // (dm_gemm_common.h: a load behind a store waits for the store's acknowledgement)
     DmGemmRow rbs[TM];
@@ -687,53 +687,47 @@ void launch_mfma(const GemmParams &p, int layout, int grid, hipStream_t s) {
   }
 }
 
-// DM_GEMM_ROUTE (see dm_gemm): per-product family override for in-step A/B runs; restores the environment when it goes out of scope.
-struct DmRouteOverride {
-  static constexpr int NKEY = 6;
-  const char *keys[NKEY] = {"DM_GEMM_W4", "DM_GEMM_W4_TN", "DM_GEMM_RING", "DM_GEMM_256", "DM_GEMM_FORCE_TILE", "DM_GEMM_Q4"};
-  char saved[NKEY][16];
-  bool had[NKEY];
-  bool active = false;
-  DmRouteOverride(int layout, int M, int N, int K) {
-    static const char *const e = getenv("DM_GEMM_ROUTE");      // read once: unset (the product's case) costs nothing per call
-    if (!e || !*e) return;
-    char want[64];
-    snprintf(want, sizeof(want), "%s:%dx%dx%d=", layout == DM_NT ? "NT" : layout == DM_NN ? "NN" : "TN", M, N, K);
-    const char *hit = strstr(e, want);
-    if (!hit) return;
-    const char *fam = hit + strlen(want);
-    const char *vals[NKEY] = {"0", "0", "0", "0", nullptr, "0"};
-    if (!strncmp(fam, "w4", 2)) { vals[0] = "2"; vals[1] = "2"; }
-    else if (!strncmp(fam, "ring", 4)) vals[2] = "2";
-    else if (!strncmp(fam, "256", 3)) vals[3] = "2";
-    else if (!strncmp(fam, "128", 3)) vals[4] = "128";
-    else if (!strncmp(fam, "64", 2)) vals[4] = "64";
-    else if (!strncmp(fam, "q4", 2)) vals[5] = "2";
-    else return;
-    active = true;
-    for (int i = 0; i < NKEY; ++i) {
-      const char *old = getenv(keys[i]);
-      had[i] = old != nullptr;
-      snprintf(saved[i], sizeof(saved[i]), "%s", old ? old : "");
-      if (vals[i]) setenv(keys[i], vals[i], 1); else unsetenv(keys[i]);
-    }
-  }
-  ~DmRouteOverride() {
-    if (!active) return;
-    for (int i = 0; i < NKEY; ++i) {
-      if (had[i]) setenv(keys[i], saved[i], 1); else unsetenv(keys[i]);
-    }
-  }
-};
+// The family switches as the environment has them NOW: read on every call (tests and A/B tools flip them between calls).
+inline GemmSwitches read_switches() {
+  GemmSwitches sw;
+  if (const char *e = getenv("DM_GEMM_W4")) sw.w4 = atoi(e);
+  if (const char *e = getenv("DM_GEMM_W4_TN")) sw.w4_tn = atoi(e);
+  if (const char *e = getenv("DM_GEMM_Q4")) sw.q4 = atoi(e);
+  if (const char *e = getenv("DM_GEMM_RING")) sw.ring = atoi(e);
+  if (const char *e = getenv("DM_GEMM_256")) sw.p256 = atoi(e);
+  if (const char *e = getenv("DM_GEMM_FORCE_TILE")) { sw.force_tile = atoi(e); sw.force_tile_set = true; }
+  return sw;
+}
+
+// A/B aid (tools/routing_check.py finds candidates in a cold microbenchmark; the decision is taken INSIDE the step): DM_GEMM_ROUTE names a
+// kernel family for single products, e.g. "NT:16384x2304x768=ring,NN:16384x3072x768=256" (families: w4, ring, 256, 128, 64, q4).  For a named
+// product the call's own copy of the switches is replaced: the named family "whenever legal", every other family off, a forced tile only
+// for 128 / 64.  The environment is not touched.  Never set in production.
+inline void apply_route(GemmSwitches &sw, int layout, int M, int N, int K) {
+  static const char *const e = getenv("DM_GEMM_ROUTE");      // read once: unset (the product's case) costs nothing per call
+  if (!e || !*e) return;
+  char want[64];
+  snprintf(want, sizeof(want), "%s:%dx%dx%d=", layout == DM_NT ? "NT" : layout == DM_NN ? "NN" : "TN", M, N, K);
+  const char *hit = strstr(e, want);
+  if (!hit) return;
+  const char *fam = hit + strlen(want);
+  GemmSwitches r;
+  r.w4 = r.w4_tn = r.q4 = r.ring = r.p256 = 0;
+  if (!strncmp(fam, "w4", 2)) r.w4 = r.w4_tn = 2;
+  else if (!strncmp(fam, "ring", 4)) r.ring = 2;
+  else if (!strncmp(fam, "256", 3)) r.p256 = 2;
+  else if (!strncmp(fam, "128", 3)) { r.force_tile = 128; r.force_tile_set = true; }
+  else if (!strncmp(fam, "64", 2)) { r.force_tile = 64; r.force_tile_set = true; }
+  else if (!strncmp(fam, "q4", 2)) r.q4 = 2;
+  else return;
+  sw = r;
+}
 
 // 64x64 tiles when the product has too few 128x128 tiles to give every CU its share
 // Measured on MI355X (tools/microbench.py, A/B in one process): 64x64 wins only when there are fewer 128x128 tiles than
 // CUs; for wgrad (long contraction, small output) 128x128 + split-K stays ahead unless the contraction is short.
-inline int pick_tile(int layout, int M, int N, int K) {
-  if (const char *f = getenv("DM_GEMM_FORCE_TILE")) {   // tuning / A-B aid: 64 or 128
-    const int v = atoi(f);
-    if (v == 64 || v == 128) return v;
-  }
+inline int pick_tile(const GemmSwitches &sw, int layout, int M, int N, int K) {
+  if (sw.force_tile == 64 || sw.force_tile == 128) return sw.force_tile;   // tuning / A-B aid
   const long long t128 = (long long)((M + 127) / 128) * ((N + 127) / 128);
   if (t128 >= 256) return 128;
   // (round 5, tools/routing_check.py: the 768 x 768 weight gradient -- 36 tiles of 128x128 -- at K = 5120 .. 12288 runs 23-36 us on 64x64
@@ -778,6 +772,49 @@ static int64_t colsum_region_floats(int M) {
   return (fused > alone ? fused : alone) + 64;
 }
 
+// A caller's workspace cut in two: the tail belongs to the column sums of A (when they are wanted), the rest to the split-K slab.
+// Returns the slab's bytes; cs_region = the start of the tail, NULL when no sums are wanted or the workspace cannot hold their region.
+static int64_t cut_workspace(void *workspace, int64_t bytes, int M, bool colsum, float *&cs_region) {
+  cs_region = nullptr;
+  if (!colsum) return bytes;
+  const int64_t need = colsum_region_floats(M) * 4;
+  if (workspace == nullptr || bytes < need) return 0;
+  const int64_t slab_bytes = (bytes - need) & ~15LL;
+  cs_region = reinterpret_cast<float *>(reinterpret_cast<char *>(workspace) + slab_bytes);
+  return slab_bytes;
+}
+
+// Are the arguments of a folded contraction (k_fold > 0) legal?  0 = yes, 1 = operand type / K / k_fold, 2 = a segment offset.
+static int k_fold_fault(const DmGemmArgs &a) {
+  if (!(a.ab_dtype == DM_BF16 && a.K == 3 * a.k_fold && a.k_fold % 64 == 0)) return 1;
+  for (int sgm = 0; sgm < 3; ++sgm)
+    if (!(a.a_fold[sgm] >= 0 && a.a_fold[sgm] < (1LL << 30) && a.b_fold[sgm] >= 0 && a.b_fold[sgm] < (1LL << 30) &&
+          a.a_fold[sgm] % 8 == 0 && a.b_fold[sgm] % 8 == 0))
+      return 2;
+  return 0;
+}
+
+int dm_gemm_cu_count() {
+  // DM_GEMM_CUS_RESERVED = n plans the one-workgroup-per-CU grids for n CUs fewer than the device has: a collective running next to
+  // the backward pass (RCCL kernels hold CUs for the length of an all-reduce) otherwise pushes the last workgroups of such a grid
+  // into a second round.  Default 0 -- to be tuned on a multi-GPU node, none was available to this build.
+  static const int n = [] {
+    int dev = 0, cus = 0;
+    if (hipGetDevice(&dev) != hipSuccess) return 0;
+    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) return 0;
+    const char *e = getenv("DM_GEMM_CUS_RESERVED");
+    const int r = e ? atoi(e) : 0;
+    return (r > 0 && r < cus) ? cus - r : cus;
+  }();
+  return n;
+}
+
+// DM_PROF_SHAPES=1: one profiler row per (layout, shape, epilogue) instead of per layout (tuning aid)
+static bool prof_by_shape() {
+  static const bool on = [] { const char *e = getenv("DM_PROF_SHAPES"); return e && e[0] == '1'; }();
+  return on;
+}
+
 extern "C" int64_t dm_gemm_workspace_bytes(int32_t layout, int32_t M, int32_t N, int32_t K) {
   if (layout != DM_TN) {
     // forward / dgrad K slices (plan_fwd_split, dm_gemm_w4_plan): at most 4 partial tiles
@@ -787,13 +824,67 @@ extern "C" int64_t dm_gemm_workspace_bytes(int32_t layout, int32_t M, int32_t N,
     const int64_t sliced = (N % 8 == 0 && K >= 1536 && t128 < 256) ? (int64_t)4 * M * N * 4 : 0;
     return skinny > sliced ? skinny : sliced;
   }
-  const int tile = pick_tile(layout, M, N, K);
+  const int tile = pick_tile(read_switches(), layout, M, N, K);      // (honours DM_GEMM_FORCE_TILE, like the call itself)
   const int tiles = ((M + tile - 1) / tile) * ((N + tile - 1) / tile);
   const int s = choose_split(tiles, K, 32);
   return (s > 1 ? (int64_t)s * M * N * 4 : 0) + colsum_region_floats(M) * 4;
 }
 
-extern "C" int dm_gemm(const DmGemmArgs *a, void *stream) {
+namespace {
+
+// One dm_gemm call after validation: the launch parameters and the caller's workspace as cut_workspace cut it.
+struct GemmCall {
+  const DmGemmArgs *a;
+  hipStream_t s;
+  GemmParams p;
+  int64_t slab_bytes;
+  float *cs_region;
+};
+
+enum class GemmFamily { W4, Q4, RING, P256, TILE };      // in the order of precedence; TILE = the register-staged 128x128 / 64x64 kernel
+
+// What dm_gemm decided for one product on the MFMA path (the grid geometry itself is in GemmParams: tiles_m / tiles_n / split_k / k_per_split).
+struct GemmPlan {
+  GemmFamily family;
+  int w4_grid;               // W4: workgroups
+  int ring_wm;               // RING: wave height, 8 or 4
+  int tile;                  // TILE: 128 or 64
+  int split;                 // K slices (1 = none)
+  bool fwd_split;            // the slices of a forward / dgrad product: summed by splitk_epilogue_kernel, which applies the fused epilogue
+  bool cs_fused;             // the kernel produces the partial column sums of A itself ...
+  int cs_rows_per_slice;     // ... as this many rows [M] per K slice
+};
+
+// the `_t<code>` suffix of the DM_PROF_SHAPES=1 row names: tools (tools/which_kernel.py) and tests read the family from it
+int prof_family_code(const GemmPlan &pl) {
+  switch (pl.family) {
+    case GemmFamily::W4: return 1924;
+    case GemmFamily::Q4: return 1284;
+    case GemmFamily::RING: return pl.ring_wm == 8 ? 2568 : 1288;
+    case GemmFamily::P256: return 256;
+    default: return pl.tile;
+  }
+}
+
+// p.debug of a launch, written here and nowhere else: the ring kernel's ablation code (DM_RING_DEBUG, read per call, ring launches only)
+// with the epilogues' A/B bits on top.  The plans run before this and see p.debug == 0.
+int gemm_debug_bits(bool ring) {
+  int debug = 0;
+  if (ring) { const char *e = getenv("DM_RING_DEBUG"); debug = e ? atoi(e) : 0; }
+  static const bool rows_off = [] { const char *e = getenv("DM_GEMM_T128_ROWS"); return e && e[0] == '0'; }();   // A/B aid: 4-column epilogue in the 128x128 kernel
+  if (rows_off && !ring) debug |= DM_DBG_ROWS_OFF;
+  static const bool touch_off = [] { const char *e = getenv("DM_GEMM_T128_TOUCH"); return e && e[0] == '0'; }();  // A/B aid: no early touch of the epilogue operands
+  if (touch_off) debug |= DM_DBG_TOUCH_OFF;
+  static const bool lean_off = [] { const char *e = getenv("DM_GEMM_EPI_LEAN"); return e && e[0] == '0'; }();     // A/B aid: the generic whole-line epilogue (dm_gemm_common.h)
+  if (lean_off) debug |= DM_DBG_LEAN_OFF;
+#ifdef DM_GEMM_ABLATE
+  { const char *e = getenv("DM_GEMM_NOEPI"); if (e && e[0] == '1') debug |= DM_DBG_NO_EPILOGUE; }
+#endif
+  return debug;
+}
+
+// Argument checks, GemmParams, the workspace cut; mfma_ok = the shapes and alignments allow the MFMA kernels.
+int gemm_prepare(const DmGemmArgs *a, void *stream, GemmCall &c, bool &mfma_ok) {
   DM_REQUIRE(a != nullptr, DM_ERR_BAD_SHAPE, "dm_gemm: null args");
   DM_REQUIRE(a->M > 0 && a->N > 0 && a->K > 0, DM_ERR_BAD_SHAPE, "dm_gemm: M,N,K must be positive (got %d,%d,%d)", a->M, a->N, a->K);
   DM_REQUIRE(a->layout >= DM_NT && a->layout <= DM_TN, DM_ERR_BAD_SHAPE, "dm_gemm: bad layout %d", a->layout);
@@ -809,9 +900,11 @@ extern "C" int dm_gemm(const DmGemmArgs *a, void *stream) {
              "dm_gemm: accumulate cannot be combined with an aux-reading epilogue (DM_EPI_DGELU / DM_EPI_MUL)");
   DM_REQUIRE(a->epilogue == DM_EPI_NONE || a->epilogue == DM_EPI_GELU || a->aux != nullptr, DM_ERR_BAD_SHAPE,
              "dm_gemm: this epilogue needs aux (only DM_EPI_GELU may run without one: inference)");
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  c.a = a;
+  c.s = reinterpret_cast<hipStream_t>(stream);
 
-  GemmParams p{};
+  GemmParams &p = c.p;
+  p = GemmParams{};
   p.A = a->A; p.B = a->B; p.C = a->C; p.bias = a->bias; p.residual = a->residual; p.aux = a->aux;
   p.lda = a->lda; p.ldb = a->ldb; p.ldc = a->ldc; p.ldr = a->ldr; p.ldaux = a->ldaux;
   p.group_stride = a->group_stride; p.rows_per_group = a->rows_per_group;
@@ -820,31 +913,21 @@ extern "C" int dm_gemm(const DmGemmArgs *a, void *stream) {
 
   // folded contraction (hi / lo plane pairs of the "bf16x3" products): three K segments of k_fold, each a plain operand at its offset
   p.c_plane = a->c_dtype == DM_BF16_PAIR ? a->c_plane : 0;
-  p.k_fold = 0;
   if (a->k_fold > 0) {
-    DM_REQUIRE(a->ab_dtype == DM_BF16 && a->K == 3 * a->k_fold && a->k_fold % 64 == 0, DM_ERR_UNSUPPORTED,
+    const int fault = k_fold_fault(*a);
+    DM_REQUIRE(fault != 1, DM_ERR_UNSUPPORTED,
                "dm_gemm: k_fold needs bf16 operands, K == 3 * k_fold and k_fold %% 64 == 0 (K=%d k_fold=%d)", a->K, a->k_fold);
+    DM_REQUIRE(fault == 0, DM_ERR_UNSUPPORTED, "dm_gemm: k_fold segment offsets must be multiples of 8 in [0, 2^30)");
     for (int sgm = 0; sgm < 3; ++sgm) {
-      DM_REQUIRE(a->a_fold[sgm] >= 0 && a->a_fold[sgm] < (1LL << 30) && a->b_fold[sgm] >= 0 && a->b_fold[sgm] < (1LL << 30) &&
-                     a->a_fold[sgm] % 8 == 0 && a->b_fold[sgm] % 8 == 0,
-                 DM_ERR_UNSUPPORTED, "dm_gemm: k_fold segment offsets must be multiples of 8 in [0, 2^30)");
       p.a_fold[sgm] = a->a_fold[sgm];
       p.b_fold[sgm] = a->b_fold[sgm];
     }
     p.k_fold = a->k_fold;
   }
-  const bool folded = p.k_fold > 0;
-  // the tail of the workspace belongs to the column sums of A, the rest to the split-K slab
-  float *cs_region = nullptr;
-  int64_t slab_bytes = a->workspace_bytes;
-  if (a->colsum_a) {
-    DM_REQUIRE(a->layout == DM_TN, DM_ERR_UNSUPPORTED, "dm_gemm: colsum_a goes with DM_TN (column sums of A = dy)");
-    const int64_t need = colsum_region_floats(a->M) * 4;
-    DM_REQUIRE(a->workspace != nullptr && a->workspace_bytes >= need, DM_ERR_BAD_SHAPE,
-               "dm_gemm: colsum_a needs %lld bytes of workspace (got %lld)", (long long)need, (long long)a->workspace_bytes);
-    slab_bytes = (a->workspace_bytes - need) & ~15LL;
-    cs_region = reinterpret_cast<float *>(reinterpret_cast<char *>(a->workspace) + slab_bytes);
-  }
+  if (a->colsum_a) DM_REQUIRE(a->layout == DM_TN, DM_ERR_UNSUPPORTED, "dm_gemm: colsum_a goes with DM_TN (column sums of A = dy)");
+  c.slab_bytes = cut_workspace(a->workspace, a->workspace_bytes, a->M, a->colsum_a != nullptr, c.cs_region);
+  DM_REQUIRE(!a->colsum_a || c.cs_region, DM_ERR_BAD_SHAPE, "dm_gemm: colsum_a needs %lld bytes of workspace (got %lld)",
+             (long long)(colsum_region_floats(a->M) * 4), (long long)a->workspace_bytes);
   // Which extents must be chunk (16-byte) multiples for the MFMA path.
   {
     const long long esz = (a->ab_dtype == DM_BF16) ? 2 : 4;
@@ -854,53 +937,65 @@ extern "C" int dm_gemm(const DmGemmArgs *a, void *stream) {
   const int epc = (a->ab_dtype == DM_BF16) ? 8 : 4;
   const int a_inner = (a->layout == DM_TN) ? a->M : a->K;   // contiguous extent of A rows
   const int b_inner = (a->layout == DM_NT) ? a->K : a->N;
-  const bool mfma_ok = (a_inner % epc == 0) && (b_inner % epc == 0) && (a->lda % epc == 0) && (a->ldb % epc == 0) &&
-                       dm_aligned16(a->A) && dm_aligned16(a->B) && (a->N % 4 == 0) && (a->ldc % 4 == 0) &&
-                       (a->residual == nullptr || (a->ldr % 4 == 0 && dm_aligned16(a->residual))) &&
-                       (a->aux == nullptr || a->ldaux % 4 == 0) && (a->bias == nullptr || dm_aligned16(a->bias)) &&
-                       dm_aligned16(a->C) && (a->rows_per_group == 0 || a->group_stride % 4 == 0) &&
-                       // skinny fp32 products of the tail (M = batch) have too few 128x128 tiles to fill the chip
-                       !(a->ab_dtype == DM_F32 && a->layout != DM_TN && a->rows_per_group == 0 && a->c_dtype == DM_F32 &&
-                         (a->aux == nullptr || a->aux_dtype == DM_F32) &&
-                         ((a->M + BM - 1) / BM) * ((a->N + BN - 1) / BN) < 16);
-  if (!mfma_ok) {
-    DM_REQUIRE(!folded && a->c_dtype != DM_BF16_PAIR, DM_ERR_UNSUPPORTED, "dm_gemm: k_fold / a plane-pair result need the MFMA path's alignment (M=%d N=%d K=%d)", a->M, a->N, a->K);
-    DM_REQUIRE(a->ab_dtype == DM_F32 && a->c_dtype == DM_F32 && (a->aux == nullptr || a->aux_dtype == DM_F32),
-               DM_ERR_BAD_ALIGN, "dm_gemm: shape/alignment needs the generic path, which is fp32-only "
-               "(M=%d N=%d K=%d lda=%lld ldb=%lld)", a->M, a->N, a->K, (long long)a->lda, (long long)a->ldb);
-    DM_REQUIRE(a->rows_per_group == 0, DM_ERR_UNSUPPORTED, "dm_gemm: grouped rows need the MFMA path");
-    dim3 grid((a->N + 15) / 16, (a->M + 15) / 16);
-    // skinny products with a long contraction (the head: 64 x 100 over 3840 features = 28 tiles, 36 us on 28 workgroups): K slices
-    // over gridDim.z, summed in slice order by a second small launch.  DM_GEMM_SKINNY=0 for A/B runs.
-    static const bool skinny_on = [] { const char *e = getenv("DM_GEMM_SKINNY"); return !(e && atoi(e) == 0); }();
-    const long long tiles16 = (long long)grid.x * grid.y;
-    int slices = 1;
-    if (skinny_on && a->workspace && !a->colsum_a && a->K >= 1024 && tiles16 <= 128) {
-      slices = (int)(512 / tiles16);
-      if (slices > a->K / 128) slices = a->K / 128;
-      if (slices > 32) slices = 32;
-      while (slices > 1 && (int64_t)slices * a->M * a->N * 4 > slab_bytes) slices >>= 1;
-    }
-    if (slices > 1) {
-      p.workspace = reinterpret_cast<float *>(a->workspace);
-      p.k_per_split = ((a->K + slices - 1) / slices + 31) / 32 * 32;
-      slices = (a->K + p.k_per_split - 1) / p.k_per_split;
-      grid.z = slices;
-    }
-    switch (a->layout) {
-      // (a 16-wave instance -- K split 16 ways, 8 stages instead of 30 for the 3840-wide head product -- measured 92 us against ~36 us for
-      // this one: not used)
-      case DM_NT: hipLaunchKernelGGL((sgemm_small_kernel<DM_NT>), grid, dim3(256), 0, s, p); break;
-      case DM_NN: hipLaunchKernelGGL((sgemm_small_kernel<DM_NN>), grid, dim3(256), 0, s, p); break;
-      default: hipLaunchKernelGGL((sgemm_small_kernel<DM_TN>), grid, dim3(256), 0, s, p); break;
-    }
-    if (slices > 1)
-      hipLaunchKernelGGL(sgemm_small_reduce_kernel, dim3((unsigned)(((long long)a->M * a->N + 255) / 256)), dim3(256), 0, s, p, slices);
-    DM_LAUNCH_CHECK("dm_gemm(generic)");
-    if (a->colsum_a) return dm_colsum(a->A, a->ab_dtype, a->lda, a->colsum_a, a->K, a->M, a->colsum_accumulate, cs_region, stream);
-    return DM_OK;
-  }
+  mfma_ok = (a_inner % epc == 0) && (b_inner % epc == 0) && (a->lda % epc == 0) && (a->ldb % epc == 0) &&
+            dm_aligned16(a->A) && dm_aligned16(a->B) && (a->N % 4 == 0) && (a->ldc % 4 == 0) &&
+            (a->residual == nullptr || (a->ldr % 4 == 0 && dm_aligned16(a->residual))) &&
+            (a->aux == nullptr || a->ldaux % 4 == 0) && (a->bias == nullptr || dm_aligned16(a->bias)) &&
+            dm_aligned16(a->C) && (a->rows_per_group == 0 || a->group_stride % 4 == 0) &&
+            // skinny fp32 products of the tail (M = batch) have too few 128x128 tiles to fill the chip
+            !(a->ab_dtype == DM_F32 && a->layout != DM_TN && a->rows_per_group == 0 && a->c_dtype == DM_F32 &&
+              (a->aux == nullptr || a->aux_dtype == DM_F32) &&
+              ((a->M + BM - 1) / BM) * ((a->N + BN - 1) / BN) < 16);
+  return DM_OK;
+}
 
+// The generic (non-MFMA) fp32 path: 16 x 16 outputs per workgroup, K slices for skinny products.
+int gemm_generic(GemmCall &c) {
+  const DmGemmArgs *a = c.a;
+  GemmParams &p = c.p;
+  hipStream_t s = c.s;
+  DM_REQUIRE(p.k_fold == 0 && a->c_dtype != DM_BF16_PAIR, DM_ERR_UNSUPPORTED, "dm_gemm: k_fold / a plane-pair result need the MFMA path's alignment (M=%d N=%d K=%d)", a->M, a->N, a->K);
+  DM_REQUIRE(a->ab_dtype == DM_F32 && a->c_dtype == DM_F32 && (a->aux == nullptr || a->aux_dtype == DM_F32),
+             DM_ERR_BAD_ALIGN, "dm_gemm: shape/alignment needs the generic path, which is fp32-only "
+             "(M=%d N=%d K=%d lda=%lld ldb=%lld)", a->M, a->N, a->K, (long long)a->lda, (long long)a->ldb);
+  DM_REQUIRE(a->rows_per_group == 0, DM_ERR_UNSUPPORTED, "dm_gemm: grouped rows need the MFMA path");
+  dim3 grid((a->N + 15) / 16, (a->M + 15) / 16);
+  // skinny products with a long contraction (the head: 64 x 100 over 3840 features = 28 tiles, 36 us on 28 workgroups): K slices
+  // over gridDim.z, summed in slice order by a second small launch.  DM_GEMM_SKINNY=0 for A/B runs.
+  static const bool skinny_on = [] { const char *e = getenv("DM_GEMM_SKINNY"); return !(e && atoi(e) == 0); }();
+  const long long tiles16 = (long long)grid.x * grid.y;
+  int slices = 1;
+  if (skinny_on && a->workspace && !a->colsum_a && a->K >= 1024 && tiles16 <= 128) {
+    slices = (int)(512 / tiles16);
+    if (slices > a->K / 128) slices = a->K / 128;
+    if (slices > 32) slices = 32;
+    while (slices > 1 && (int64_t)slices * a->M * a->N * 4 > c.slab_bytes) slices >>= 1;
+  }
+  if (slices > 1) {
+    p.workspace = reinterpret_cast<float *>(a->workspace);
+    p.k_per_split = ((a->K + slices - 1) / slices + 31) / 32 * 32;
+    slices = (a->K + p.k_per_split - 1) / p.k_per_split;
+    grid.z = slices;
+  }
+  switch (a->layout) {
+    // (a 16-wave instance -- K split 16 ways, 8 stages instead of 30 for the 3840-wide head product -- measured 92 us against ~36 us for
+    // this one: not used)
+    case DM_NT: hipLaunchKernelGGL((sgemm_small_kernel<DM_NT>), grid, dim3(256), 0, s, p); break;
+    case DM_NN: hipLaunchKernelGGL((sgemm_small_kernel<DM_NN>), grid, dim3(256), 0, s, p); break;
+    default: hipLaunchKernelGGL((sgemm_small_kernel<DM_TN>), grid, dim3(256), 0, s, p); break;
+  }
+  if (slices > 1)
+    hipLaunchKernelGGL(sgemm_small_reduce_kernel, dim3((unsigned)(((long long)a->M * a->N + 255) / 256)), dim3(256), 0, s, p, slices);
+  DM_LAUNCH_CHECK("dm_gemm(generic)");
+  if (a->colsum_a) return dm_colsum(a->A, a->ab_dtype, a->lda, a->colsum_a, a->K, a->M, a->colsum_accumulate, c.cs_region, c.s);
+  return DM_OK;
+}
+
+// Which kernel family runs the product, and its K slices.  Fills the grid geometry of c.p and, last, c.p.debug.
+int gemm_plan(GemmCall &c, GemmPlan &pl) {
+  const DmGemmArgs *a = c.a;
+  GemmParams &p = c.p;
+  const int64_t slab_bytes = c.slab_bytes;
   const bool can_split = (a->layout == DM_TN) && a->epilogue == DM_EPI_NONE && !a->bias && !a->residual &&
                          a->c_dtype == DM_F32 && a->rows_per_group == 0 && a->workspace != nullptr && slab_bytes > 0;
   if (a->split_k > 1) {
@@ -914,144 +1009,164 @@ extern "C" int dm_gemm(const DmGemmArgs *a, void *stream) {
   // two-workgroups-per-CU ring kernel (k-contiguous operands, 16-byte row pieces in the epilogue)
   const bool ring_aligned = (a->ldc % 8 == 0) && (a->aux == nullptr || a->ldaux % 8 == 0) &&
                             (a->rows_per_group == 0 || a->group_stride % 8 == 0) && a->split_k <= 1 && !a->colsum_a;
-  // the 4-wave register-staged persistent kernel, then the ring kernel, then the 256x256 pipeline
-  p.workspace = reinterpret_cast<float *>(a->workspace);
   const bool w4_ok = (a->layout == DM_TN) ? (a->split_k == 0 && a->ldc % 4 == 0) : ring_aligned;     // wgrad: automatic slice count only
-  // forward / dgrad K slices (w4: (tile, slice) per workgroup; 128 x 128 / 64 x 64: plan_fwd_split): automatic slice count only, the
+  // forward / dgrad K slices (w4: (tile, slice) per workgroup; 128 x 128 / 64 x 64: plan_fwd_split): bf16, automatic slice count only, the
   // 8-column epilogue of splitk_epilogue_kernel must be legal, and the caller's workspace holds the slab
   const bool fwd_slices_ok = a->layout != DM_TN && a->ab_dtype == DM_BF16 && a->split_k == 0 && ring_aligned && a->N % 8 == 0 &&
                              (a->residual == nullptr || a->ldr % 8 == 0) && a->workspace != nullptr && slab_bytes > 0;
-  // A/B aid (tools/routing_check.py finds candidates in a cold microbenchmark; the decision is taken INSIDE the step): DM_GEMM_ROUTE names a
-  // kernel family for single products, e.g. "NT:16384x2304x768=ring,NN:16384x3072x768=256" (families: w4, ring, 256, 128, 64, q4).  The plans
-  // below read their switches per call, so the override sets them for this call only.  Not thread-safe; never set in production.
-  DmRouteOverride route_guard(a->layout, a->M, a->N, a->K);
-  const int w4 = w4_ok ? dm_gemm_w4_plan(p, a->layout, a->ab_dtype, true, a->layout == DM_TN ? can_split : fwd_slices_ok, slab_bytes) : 0;
-  const bool persistent = w4 != 0;
-  // four-workgroups-per-CU 128 x 128 tiles (dm_gemm_q4.hip) for the short-contraction forward / dgrad products
-  const bool q4 = !persistent && dm_gemm_q4_plan(p, a->layout, a->ab_dtype, ring_aligned && a->split_k <= 1);
-  const int ring = (persistent || q4) ? 0 : dm_gemm_ring_plan(p, a->layout, a->ab_dtype, ring_aligned);
-  const bool big = !persistent && !q4 && !ring && dm_gemm256_plan(p, a->layout, a->ab_dtype, can_split, slab_bytes, a->split_k);
-  int tile = w4 ? 1924 : q4 ? 1284 : ring ? (ring == 8 ? 2568 : 1288) : big ? 256 : pick_tile(a->layout, a->M, a->N, a->K);
-  int split = w4 ? p.split_k : (ring || q4 || persistent) ? 1 : p.split_k;
-  // forward / dgrad K slices (plan_fwd_split): bf16, automatic slice count, 8-column epilogue legal, slab inside the workspace
-  bool fwd_split = persistent && a->layout != DM_TN && p.split_k > 1;      // the 4-wave kernel planned slices
-  if (!big && !ring && !q4 && !persistent && fwd_slices_ok) {
-    int ft;
-    const int fs = plan_fwd_split(a->layout, a->M, a->N, a->K, ft);
-    if (fs > 1 && (int64_t)fs * a->M * a->N * 4 <= slab_bytes && !getenv("DM_GEMM_FORCE_TILE")) {
-      fwd_split = true;
-      tile = ft;
-    }
-  }
-  if (!big && !ring && !q4 && !persistent) {
-    p.tiles_m = (a->M + tile - 1) / tile;
-    p.tiles_n = (a->N + tile - 1) / tile;
-    const int bk = (a->ab_dtype == DM_BF16) ? 64 : 32;
-    split = a->split_k;
-    if (fwd_split) { int ft; split = plan_fwd_split(a->layout, a->M, a->N, a->K, ft); }
-    else if (split == 0) split = can_split ? choose_split(p.tiles_m * p.tiles_n, a->K, bk) : 1;
-    if (split > 1)
-      while (split > 1 && (int64_t)split * a->M * a->N * 4 > slab_bytes) split >>= 1;
-    int kps = ((a->K + split - 1) / split + bk - 1) / bk * bk;
-    split = (a->K + kps - 1) / kps;
-    p.split_k = split;
-    p.k_per_split = kps;
-  }
+  GemmSwitches sw = read_switches();
+  apply_route(sw, a->layout, a->M, a->N, a->K);
   p.workspace = reinterpret_cast<float *>(a->workspace);
-  {
-    static const bool rows_off = [] { const char *e = getenv("DM_GEMM_T128_ROWS"); return e && e[0] == '0'; }();   // A/B aid: 4-column epilogue in the 128x128 kernel
-    if (rows_off && !ring) p.debug |= 0x100;
-    static const bool touch_off = [] { const char *e = getenv("DM_GEMM_T128_TOUCH"); return e && e[0] == '0'; }();  // A/B aid: no early touch of the epilogue operands
-    if (touch_off) p.debug |= 0x200;
-    static const bool lean_off = [] { const char *e = getenv("DM_GEMM_EPI_LEAN"); return e && e[0] == '0'; }();     // A/B aid: the generic whole-line epilogue (dm_gemm_common.h)
-    if (lean_off) p.debug |= 0x400;
-#ifdef DM_GEMM_ABLATE
-    { const char *e = getenv("DM_GEMM_NOEPI"); if (e && e[0] == '1') p.debug |= 0x800; }
-#endif
-  }
   {
     static const int forced = [] { const char *e = getenv("DM_GEMM_GROUP_M"); return e ? atoi(e) : -1; }();
     p.group_m = forced >= 0 ? forced : 8;   // measured over the encoder's step: 8 > 4 > 0 (column-fastest) > 16 > 32, within 2 %
   }
-  const int grid = p.tiles_m * p.tiles_n * split;
-  {
-    static const char *kNames[2][3] = {{"gemm_f32_NT", "gemm_f32_NN", "gemm_f32_TN"}, {"gemm_bf16_NT", "gemm_bf16_NN", "gemm_bf16_TN"}};
-    const double esz = (a->ab_dtype == DM_BF16) ? 2.0 : 4.0;
-    const double csz = (a->c_dtype == DM_BF16) ? 2.0 : 4.0;
-    // DM_PROF_SHAPES=1: one profiler row per (layout, shape, epilogue) instead of per layout (tuning aid)
-    static const bool by_shape = [] { const char *e = getenv("DM_PROF_SHAPES"); return e && e[0] == '1'; }();
-    char shaped[64];
-    const char *pname = kNames[a->ab_dtype == DM_BF16][a->layout];
-    if (by_shape) {
-      snprintf(shaped, sizeof(shaped), "%s_%lldx%lldx%lld_e%d%s%s_t%d", pname, (long long)a->M, (long long)a->N, (long long)a->K, a->epilogue,
-               a->residual ? "r" : "", a->c_dtype == DM_BF16 ? "h" : "f", tile);
-      pname = shaped;
+
+  // the 4-wave register-staged persistent kernel, then the four-workgroups-per-CU 128 x 128 tiles (dm_gemm_q4.hip) for the short-contraction
+  // forward / dgrad products, then the ring kernel, then the 256x256 pipeline, then the register-staged tiles.  A plan that takes the
+  // product fills p.tiles_m / tiles_n / split_k / k_per_split.
+  pl = GemmPlan{};
+  pl.family = GemmFamily::TILE;
+  if (w4_ok && (pl.w4_grid = dm_gemm_w4_plan(p, sw, a->layout, a->ab_dtype, true, a->layout == DM_TN ? can_split : fwd_slices_ok, slab_bytes)) != 0)
+    pl.family = GemmFamily::W4;
+  else if (dm_gemm_q4_plan(p, sw, a->layout, a->ab_dtype, ring_aligned))
+    pl.family = GemmFamily::Q4;
+  else if ((pl.ring_wm = dm_gemm_ring_plan(p, sw, a->layout, a->ab_dtype, ring_aligned)) != 0)
+    pl.family = GemmFamily::RING;
+  else if (dm_gemm256_plan(p, sw, a->layout, a->ab_dtype, can_split, slab_bytes, a->split_k))
+    pl.family = GemmFamily::P256;
+
+  if (pl.family != GemmFamily::TILE) {
+    pl.split = p.split_k;
+    pl.fwd_split = pl.family == GemmFamily::W4 && a->layout != DM_TN && p.split_k > 1;      // the 4-wave kernel planned slices
+  } else {
+    pl.tile = pick_tile(sw, a->layout, a->M, a->N, a->K);
+    const int bk = (a->ab_dtype == DM_BF16) ? 64 : 32;
+    int split = a->split_k;
+    if (fwd_slices_ok) {
+      int ft;
+      const int fs = plan_fwd_split(a->layout, a->M, a->N, a->K, ft);
+      if (fs > 1 && (int64_t)fs * a->M * a->N * 4 <= slab_bytes && !sw.force_tile_set) {
+        pl.fwd_split = true;
+        pl.tile = ft;
+        split = fs;
+      }
     }
+    p.tiles_m = (a->M + pl.tile - 1) / pl.tile;
+    p.tiles_n = (a->N + pl.tile - 1) / pl.tile;
+    if (!pl.fwd_split && split == 0) split = can_split ? choose_split(p.tiles_m * p.tiles_n, a->K, bk) : 1;
+    while (split > 1 && (int64_t)split * a->M * a->N * 4 > slab_bytes) split >>= 1;
+    const int kps = ((a->K + split - 1) / split + bk - 1) / bk * bk;
+    pl.split = p.split_k = (a->K + kps - 1) / kps;
+    p.k_per_split = kps;
+  }
+  // these kernels produce the partial column sums of A themselves
+  // (256x256 pipeline: one row per wave column; 64x64 tiles and the 4-wave kernel: one per slice)
+  const bool cs_t64 = pl.family == GemmFamily::TILE && a->layout == DM_TN && a->ab_dtype == DM_BF16 && pl.tile == 64 && a->colsum_a != nullptr && pl.split <= 128;
+  pl.cs_fused = pl.family == GemmFamily::P256 || (pl.family == GemmFamily::W4 && a->layout == DM_TN) || cs_t64;
+  pl.cs_rows_per_slice = pl.family == GemmFamily::P256 ? 4 : 1;
+  p.colsum_slab = pl.cs_fused ? c.cs_region : nullptr;
+  p.debug = gemm_debug_bits(pl.family == GemmFamily::RING);
+  return DM_OK;
+}
+
+// The product's launch (and the reduction of forward / dgrad K slices) under one profiler scope.
+int gemm_launch(const GemmCall &c, const GemmPlan &pl) {
+  const DmGemmArgs *a = c.a;
+  const GemmParams &p = c.p;
+  hipStream_t s = c.s;
+  static const char *kNames[2][3] = {{"gemm_f32_NT", "gemm_f32_NN", "gemm_f32_TN"}, {"gemm_bf16_NT", "gemm_bf16_NN", "gemm_bf16_TN"}};
+  const double esz = (a->ab_dtype == DM_BF16) ? 2.0 : 4.0;
+  const double csz = (a->c_dtype == DM_BF16) ? 2.0 : 4.0;
+  char shaped[64];
+  const char *pname = kNames[a->ab_dtype == DM_BF16][a->layout];
+  if (prof_by_shape()) {
+    snprintf(shaped, sizeof(shaped), "%s_%lldx%lldx%lld_e%d%s%s_t%d", pname, (long long)a->M, (long long)a->N, (long long)a->K, a->epilogue,
+             a->residual ? "r" : "", a->c_dtype == DM_BF16 ? "h" : "f", prof_family_code(pl));
+    pname = shaped;
+  }
+  {
     const double mn = (double)a->M * a->N;
     DmProfScope prof(pname, s, 2.0 * a->M * a->N * a->K,
                      esz * ((double)a->M * a->K + (double)a->N * a->K) + csz * mn * (a->accumulate ? 2.0 : 1.0) +
                          (a->residual ? 4.0 * mn : 0.0) + (a->aux ? ((a->aux_dtype == DM_BF16) ? 2.0 : 4.0) * mn : 0.0));
-    const bool cs_t64 = !big && !w4 && !ring && !q4 && a->layout == DM_TN && a->ab_dtype == DM_BF16 && tile == 64 && a->colsum_a != nullptr && split <= 128;
-    p.colsum_slab = ((big || (w4 && a->layout == DM_TN) || cs_t64) && cs_region) ? cs_region : nullptr;
-    if (w4) {
-      dm_gemm_w4_launch(p, a->layout, w4, s);
-    } else if (q4) {
-      dm_gemm_q4_launch(p, a->layout, s);
-    } else if (ring) {
-      dm_gemm_ring_launch(p, ring, s);
-    } else if (big) {
-      dm_gemm256_launch(p, a->layout, s);
-    } else if (a->ab_dtype == DM_BF16) {
-      if (tile == 128) launch_mfma<bf16_t, 4>(p, a->layout, grid, s); else launch_mfma<bf16_t, 2>(p, a->layout, grid, s);
-    } else {
-      if (tile == 128) launch_mfma<float, 4>(p, a->layout, grid, s); else launch_mfma<float, 2>(p, a->layout, grid, s);
+    switch (pl.family) {
+      case GemmFamily::W4: dm_gemm_w4_launch(p, a->layout, pl.w4_grid, s); break;
+      case GemmFamily::Q4: dm_gemm_q4_launch(p, a->layout, s); break;
+      case GemmFamily::RING: dm_gemm_ring_launch(p, pl.ring_wm, s); break;
+      case GemmFamily::P256: dm_gemm256_launch(p, a->layout, s); break;
+      case GemmFamily::TILE: {
+        const int grid = p.tiles_m * p.tiles_n * pl.split;
+        if (a->ab_dtype == DM_BF16) {
+          if (pl.tile == 128) launch_mfma<bf16_t, 4>(p, a->layout, grid, s); else launch_mfma<bf16_t, 2>(p, a->layout, grid, s);
+        } else {
+          if (pl.tile == 128) launch_mfma<float, 4>(p, a->layout, grid, s); else launch_mfma<float, 2>(p, a->layout, grid, s);
+        }
+      }
     }
-    if (fwd_split && split > 1) {      // (inside the profiler scope: the class time of these products includes their reduction)
+    if (pl.fwd_split && pl.split > 1) {      // (inside the profiler scope: the class time of these products includes their reduction)
       const long long n8 = (long long)a->M * a->N / 8;
       const long long want = (n8 + 255) / 256;
       GemmParams q = p;
       q.split_k = 1;
-      hipLaunchKernelGGL(splitk_epilogue_kernel, dim3((unsigned)(want < 4096 ? want : 4096)), dim3(256), 0, s, q, p.workspace, split);
+      hipLaunchKernelGGL(splitk_epilogue_kernel, dim3((unsigned)(want < 4096 ? want : 4096)), dim3(256), 0, s, q, p.workspace, pl.split);
     }
   }
   DM_LAUNCH_CHECK("dm_gemm");
-  if (fwd_split) return DM_OK;
-  const bool cs_t64 = !big && !w4 && !ring && !q4 && a->layout == DM_TN && a->ab_dtype == DM_BF16 && tile == 64 && a->colsum_a != nullptr && split <= 128;
-  const bool cs_fused = big || (w4 && a->layout == DM_TN) || cs_t64;      // these kernels produce the partial column sums of A themselves
-  const int cs_rows_per_slice = big ? 4 : 1;      // (256x256 pipeline: one row per wave column; 64x64 tiles and the 4-wave kernel: one per slice)
-  if (split > 1) {
+  return DM_OK;
+}
+
+// What follows the launch of a product without forward slices: the sum of the split-K slab and the column sums of A.
+int gemm_finish(const GemmCall &c, const GemmPlan &pl) {
+  const DmGemmArgs *a = c.a;
+  const GemmParams &p = c.p;
+  hipStream_t s = c.s;
+  if (pl.split > 1) {
     const long long n4 = (long long)a->M * a->N / 4;
     const long long want = (n4 + 255) / 256;
     const int rgrid = (int)(want < 2048 ? want : 2048);
-    const bool fold_cs = a->colsum_a && cs_fused;     // the pipelines' [split * 4 | 2][M] partial column sums ride along
+    const bool fold_cs = a->colsum_a && pl.cs_fused;     // the pipelines' [split * 4 | 2][M] partial column sums ride along
     const int cs_blocks = fold_cs ? (a->M + 255) / 256 : 0;
     hipLaunchKernelGGL(splitk_reduce_kernel, dim3(rgrid + cs_blocks), dim3(256), 0, s, p.workspace,
-                       reinterpret_cast<float *>(a->C), (long long)a->ldc, a->M, a->N, split, a->accumulate, rgrid,
-                       fold_cs ? cs_region : nullptr, fold_cs ? a->colsum_a : nullptr, a->M, split * cs_rows_per_slice, a->colsum_accumulate);
+                       reinterpret_cast<float *>(a->C), (long long)a->ldc, a->M, a->N, pl.split, a->accumulate, rgrid,
+                       fold_cs ? c.cs_region : nullptr, fold_cs ? a->colsum_a : nullptr, a->M, pl.split * pl.cs_rows_per_slice, a->colsum_accumulate);
     DM_LAUNCH_CHECK("dm_gemm(split-k reduce)");
     if (fold_cs) return DM_OK;
   }
-  if (a->colsum_a) {
-    if (cs_fused) {      // fold the pipeline's partial rows, in row order
-      hipLaunchKernelGGL(colsum_rows_reduce_kernel, dim3((a->M + 63) / 64), dim3(64), 0, s, cs_region, a->colsum_a, a->M, split * cs_rows_per_slice,
-                         a->colsum_accumulate);
-      DM_LAUNCH_CHECK("dm_gemm(colsum reduce)");
-    } else if (folded) {      // the distinct pieces of A, one pass each: colsum(hi) + colsum(lo)
-      int accum = a->colsum_accumulate;
-      for (int sgm = 0; sgm < 3; ++sgm) {
-        bool first = true;
-        for (int e = 0; e < sgm; ++e) first = first && a->a_fold[e] != a->a_fold[sgm];
-        if (!first) continue;
-        const int rc = dm_colsum(reinterpret_cast<const unsigned short *>(a->A) + a->a_fold[sgm], a->ab_dtype, a->lda, a->colsum_a, a->k_fold, a->M, accum, cs_region, stream);
-        if (rc != DM_OK) return rc;
-        accum = 1;
-      }
-    } else {
-      const int rc = dm_colsum(a->A, a->ab_dtype, a->lda, a->colsum_a, a->K, a->M, a->colsum_accumulate, cs_region, stream);
+  if (!a->colsum_a) return DM_OK;
+  if (pl.cs_fused) {      // fold the pipeline's partial rows, in row order
+    hipLaunchKernelGGL(colsum_rows_reduce_kernel, dim3((a->M + 63) / 64), dim3(64), 0, s, c.cs_region, a->colsum_a, a->M, pl.split * pl.cs_rows_per_slice,
+                       a->colsum_accumulate);
+    DM_LAUNCH_CHECK("dm_gemm(colsum reduce)");
+  } else if (p.k_fold > 0) {      // the distinct pieces of A, one pass each: colsum(hi) + colsum(lo)
+    int accum = a->colsum_accumulate;
+    for (int sgm = 0; sgm < 3; ++sgm) {
+      bool first = true;
+      for (int e = 0; e < sgm; ++e) first = first && a->a_fold[e] != a->a_fold[sgm];
+      if (!first) continue;
+      const int rc = dm_colsum(reinterpret_cast<const unsigned short *>(a->A) + a->a_fold[sgm], a->ab_dtype, a->lda, a->colsum_a, a->k_fold, a->M, accum, c.cs_region, c.s);
       if (rc != DM_OK) return rc;
+      accum = 1;
     }
+  } else {
+    return dm_colsum(a->A, a->ab_dtype, a->lda, a->colsum_a, a->K, a->M, a->colsum_accumulate, c.cs_region, c.s);
   }
   return DM_OK;
+}
+
+}  // namespace
+
+// validate, plan, launch, finish
+extern "C" int dm_gemm(const DmGemmArgs *a, void *stream) {
+  GemmCall c;
+  bool mfma_ok = false;
+  int rc = gemm_prepare(a, stream, c, mfma_ok);
+  if (rc != DM_OK) return rc;
+  if (!mfma_ok) return gemm_generic(c);
+  GemmPlan pl;
+  if ((rc = gemm_plan(c, pl)) != DM_OK) return rc;
+  if ((rc = gemm_launch(c, pl)) != DM_OK) return rc;
+  return pl.fwd_split ? DM_OK : gemm_finish(c, pl);
 }
 
 // n independent products, results as n dm_gemm calls in order would give them (weight gradients: up to the order of the fp32 additions
@@ -1091,39 +1206,26 @@ extern "C" int dm_gemm_grouped(const DmGemmArgs *args, int32_t n, void *workspac
     p.epilogue = DM_EPI_NONE; p.accumulate = a.accumulate ? 1 : 0; p.c_dtype = DM_F32; p.aux_dtype = DM_F32;
     p.group_m = 8;
     if (a.k_fold > 0) {      // hi / lo plane pairs: dm_gemm's own preconditions, then the segments as given
-      fast = a.K == 3 * a.k_fold && a.k_fold % 64 == 0;
-      for (int sgm = 0; fast && sgm < 3; ++sgm) {
-        fast = a.a_fold[sgm] >= 0 && a.a_fold[sgm] < (1LL << 30) && a.b_fold[sgm] >= 0 && a.b_fold[sgm] < (1LL << 30) && a.a_fold[sgm] % 8 == 0 && a.b_fold[sgm] % 8 == 0;
+      fast = k_fold_fault(a) == 0;
+      if (!fast) break;
+      for (int sgm = 0; sgm < 3; ++sgm) {
         p.a_fold[sgm] = a.a_fold[sgm];
         p.b_fold[sgm] = a.b_fold[sgm];
       }
-      if (!fast) break;
       p.k_fold = a.k_fold;
     }
     x.cs_out[i] = a.colsum_a;
     x.cs_acc[i] = a.colsum_accumulate ? 1 : 0;
-    {      // the product's own workspace, cut as dm_gemm cuts it: split-K slab, then the column-sum rows (the sliced form of the group)
-      int64_t sb = a.workspace ? a.workspace_bytes : 0;
-      x.cs_region[i] = nullptr;
-      if (a.colsum_a && a.workspace) {
-        const int64_t need = colsum_region_floats(a.M) * 4;
-        if (a.workspace_bytes >= need) {
-          sb = (a.workspace_bytes - need) & ~15LL;
-          x.cs_region[i] = reinterpret_cast<float *>(reinterpret_cast<char *>(a.workspace) + sb);
-        } else sb = 0;
-      }
-      x.slab[i] = sb > 0 ? reinterpret_cast<float *>(a.workspace) : nullptr;
-      x.slab_bytes[i] = sb;
-    }
+    // the product's own workspace, cut as dm_gemm cuts it: split-K slab, then the column-sum rows (the sliced form of the group)
+    x.slab_bytes[i] = cut_workspace(a.workspace, a.workspace ? a.workspace_bytes : 0, a.M, a.colsum_a != nullptr, x.cs_region[i]);
+    x.slab[i] = x.slab_bytes[i] > 0 ? reinterpret_cast<float *>(a.workspace) : nullptr;
     if (a.colsum_a) {
       if (!a.colsum_accumulate) {
         p.colsum_slab = a.colsum_a;                      // form 1, first write of the step: the launch stores the sums where they belong
       } else {
-        const int64_t need = colsum_region_floats(a.M) * 4;
-        fast = a.workspace != nullptr && a.workspace_bytes >= need;
+        fast = x.cs_region[i] != nullptr;                // (the workspace holds the column-sum region)
         if (!fast) break;
-        cs_rows[i] = reinterpret_cast<float *>(reinterpret_cast<char *>(a.workspace) + ((a.workspace_bytes - need) & ~15LL));
-        p.colsum_slab = cs_rows[i];
+        p.colsum_slab = cs_rows[i] = x.cs_region[i];
       }
     }
     ps[i] = p;
@@ -1135,10 +1237,9 @@ extern "C" int dm_gemm_grouped(const DmGemmArgs *args, int32_t n, void *workspac
       flops += 2.0 * args[i].M * args[i].N * args[i].K;
       bytes += 2.0 * ((double)args[i].M * args[i].K + (double)args[i].N * args[i].K) + 4.0 * (double)args[i].M * args[i].N * (args[i].accumulate ? 2.0 : 1.0);
     }
-    static const bool by_shape = [] { const char *e = getenv("DM_PROF_SHAPES"); return e && e[0] == '1'; }();
     char shaped[64];
     const char *pname = "gemm_bf16_TN";
-    if (by_shape) {
+    if (prof_by_shape()) {
       snprintf(shaped, sizeof(shaped), "gemm_bf16_TN_grouped%d_K%d_%s", n, args[0].K, form == 2 ? "streamk" : form == 3 ? "sliced" : "1slice");
       pname = shaped;
     }

@@ -529,17 +529,6 @@ template <int LAYOUT> bool set_lds_limit_p() {
   return hipFuncSetAttribute(reinterpret_cast<const void *>(dm256::gemm256p_kernel<LAYOUT>), hipFuncAttributeMaxDynamicSharedMemorySize,
                              dm256::LDS256P) == hipSuccess;
 }
-int p256_cu_count() {
-  static const int n = [] {
-    int dev = 0, cus = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return 0;
-    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) return 0;
-    const char *e = getenv("DM_GEMM_CUS_RESERVED");
-    const int rsv = e ? atoi(e) : 0;
-    return (rsv > 0 && rsv < cus) ? cus - rsv : cus;
-  }();
-  return n;
-}
 template <int LAYOUT, bool FOLD = false> bool set_lds_limit() {
   return hipFuncSetAttribute(reinterpret_cast<const void *>(dm256::gemm256_kernel<LAYOUT, FOLD>), hipFuncAttributeMaxDynamicSharedMemorySize,
                              dm256::LDS256) == hipSuccess;
@@ -549,9 +538,8 @@ using namespace dm256;
 
 // Decides whether the 256x256 pipeline runs this product and, if so, fills p.tiles_m / tiles_n / split_k / k_per_split.
 // Called by dm_gemm after argument validation (alignment, N % 4, ...).
-bool dm_gemm256_plan(GemmParams &p, int layout, int ab_dtype, bool can_split, long long workspace_bytes, int user_split) {
-  const char *menv = getenv("DM_GEMM_256");              // 0 = off, 2 = always (A/B runs); read per call: tests flip it
-  const int mode = menv ? atoi(menv) : 1;
+bool dm_gemm256_plan(GemmParams &p, const GemmSwitches &sw, int layout, int ab_dtype, bool can_split, long long workspace_bytes, int user_split) {
+  const int mode = sw.p256;                              // DM_GEMM_256: 0 = off, 2 = always (A/B runs)
   if (mode == 0 || ab_dtype != DM_BF16) return false;
   if (p.K < BK256) return false;
   if (p.k_fold > 0 && p.k_fold % BK256 != 0) return false;              // folded contraction: segments of whole K tiles
@@ -628,7 +616,7 @@ void dm_gemm256_launch(const GemmParams &p_in, int layout, hipStream_t s) {
     // overlap with matrix work when accumulators are double-buffered; and the 16-row staging block makes the epilogue itself slower.
     const char *penv = getenv("DM_GEMM_256P");
     const int pmode = penv ? atoi(penv) : 0;
-    const int cus = p256_cu_count();
+    const int cus = dm_gemm_cu_count();
     const long long tiles = (long long)p.tiles_m * p.tiles_n;
     const bool rows_ok = (p.N % 8 == 0) && (p.ldc % 8 == 0) && (p.aux == nullptr || p.ldaux % 8 == 0) && (p.rows_per_group == 0 || p.group_stride % 8 == 0) &&
                          (p.residual == nullptr || p.ldr % 8 == 0);

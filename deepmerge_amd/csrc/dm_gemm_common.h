@@ -24,6 +24,24 @@ struct GemmParams {
   long long c_plane;    // c_dtype == DM_BF16_PAIR: element offset of the lo plane behind C (the hi plane)
 };
 
+// p.debug bits above the ring kernel's ablation codes: A/B aids of the epilogues, set by dm_gemm (gemm_debug_bits) and read on the device
+constexpr int DM_DBG_ROWS_OFF = 0x100;       // DM_GEMM_T128_ROWS=0: 4-column epilogue in the 128x128 kernel
+constexpr int DM_DBG_TOUCH_OFF = 0x200;      // DM_GEMM_T128_TOUCH=0: no early touch of the epilogue operands
+constexpr int DM_DBG_LEAN_OFF = 0x400;       // DM_GEMM_EPI_LEAN=0: the generic whole-line epilogue
+constexpr int DM_DBG_NO_EPILOGUE = 0x800;    // DM_GEMM_NOEPI=1 (ablation builds): no epilogue at all
+
+// The per-call modes of the kernel families (0 = off, 1 = routing rules, 2 = whenever legal; the 4-wave kernel knows more: dm_gemm_w4_plan)
+// and the forced tile.  dm_gemm reads them from the environment once per call (DM_GEMM_W4, DM_GEMM_W4_TN, DM_GEMM_Q4, DM_GEMM_RING,
+// DM_GEMM_256, DM_GEMM_FORCE_TILE), lets DM_GEMM_ROUTE edit its copy, and hands it to the plans.
+struct GemmSwitches {
+  int w4 = 1, w4_tn = 1, q4 = 1, ring = 1, p256 = 1;
+  int force_tile = 0;              // 64 / 128 force that tile of the register-staged kernel (tuning / A-B aid); anything else does not,
+  bool force_tile_set = false;     // but the variable's mere presence turns the forward K slices of that kernel off
+};
+
+// CUs the one-workgroup-per-CU grids are planned for (dm_gemm.hip)
+int dm_gemm_cu_count();
+
 // dm_gemm_grouped -> dm_gemm_w4_grouped: where the column sums of A go (stream-K form) and the group's workspace
 struct DmGroupedExtra {
   float *cs_out[8]; int cs_acc[8]; void *ws; long long ws_bytes;
@@ -516,12 +534,12 @@ __device__ __forceinline__ void dm_epilogue_rows_lean(const GemmParams &p, f32x4
 }
 
 // Structure key of an epilogue item (RES | YL << 1 | C32 << 3 | XS << 4) if the lean form's preconditions hold for a wave block of
-// `rows` rows, -1 otherwise (grouped rows, 32-bit offsets, DM_GEMM_EPI_LEAN=0 = p.debug bit 0x400).  Host and device.
+// `rows` rows, -1 otherwise (grouped rows, 32-bit offsets, DM_GEMM_EPI_LEAN=0 = DM_DBG_LEAN_OFF).  Host and device.
 __host__ __device__ inline int dm_epi_lean_key(const GemmParams &p, int rows) {
   const long long lim = (1LL << 31) / ((long long)rows * 4);
   const bool aux_read = p.aux && (p.epilogue == DM_EPI_DGELU || p.epilogue == DM_EPI_MUL);
   const bool aux_write = p.aux && (p.epilogue == DM_EPI_GELU || p.epilogue == DM_EPI_GELU_GRAD);
-  const bool lean = p.rows_per_group == 0 && !(p.debug & 0x400) && p.ldc < lim && p.ldr < lim && p.ldaux < lim &&
+  const bool lean = p.rows_per_group == 0 && !(p.debug & DM_DBG_LEAN_OFF) && p.ldc < lim && p.ldr < lim && p.ldaux < lim &&
                     !(aux_read && p.accumulate);          // (one prefetch slot serves the old C or the aux operand)
   if (!lean) return -1;
   if (p.c_dtype == DM_BF16_PAIR) return 1 << 8;           // plane-pair results: the run-time lean form (no straight-line instance)

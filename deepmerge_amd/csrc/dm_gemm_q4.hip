@@ -162,7 +162,7 @@ __global__ __launch_bounds__(NTHREADS, 4) void gemm_q4_kernel(const GemmParams p
   // Epilogue read operands (fp32 residual; the saved GELU' of the fc2 dgrad) are touched towards L2 a few K tiles before the end, as in
   // the 128 x 128 kernel: one row per lane, one dword per 128-byte line, kept alive by the asm at the top of the epilogue.
   float tv0 = 0.f, tv1 = 0.f;
-  const int touch_at = (!(p.debug & 0x200) && (p.residual || (p.aux && (p.epilogue == DM_EPI_DGELU || p.epilogue == DM_EPI_MUL)))) ? max(0, nk - 4) : -1;
+  const int touch_at = (!(p.debug & DM_DBG_TOUCH_OFF) && (p.residual || (p.aux && (p.epilogue == DM_EPI_DGELU || p.epilogue == DM_EPI_MUL)))) ? max(0, nk - 4) : -1;
 
   stage(0);
   for (int kt = 0; kt < nk; ++kt) {
@@ -225,10 +225,9 @@ __global__ __launch_bounds__(NTHREADS, 4) void gemm_q4_kernel(const GemmParams p
 }  // namespace dmq4
 
 // Decides whether this family runs the product; fills p.tiles_m / tiles_n / split_k.  Returns true when taken.
-//   DM_GEMM_Q4: 0 = off, 1 = routing rules, 2 = whenever legal (read per call: tests flip it).
-bool dm_gemm_q4_plan(GemmParams &p, int layout, int ab_dtype, bool aligned8) {
-  const char *env = getenv("DM_GEMM_Q4");
-  const int mode = env ? atoi(env) : 1;
+//   sw.q4 (DM_GEMM_Q4): 0 = off, 1 = routing rules, 2 = whenever legal.
+bool dm_gemm_q4_plan(GemmParams &p, const GemmSwitches &sw, int layout, int ab_dtype, bool aligned8) {
+  const int mode = sw.q4;
   if (mode == 0 || (layout != DM_NT && layout != DM_NN) || ab_dtype != DM_BF16 || !aligned8) return false;
   // whole K tiles, plain operands and results, the whole-line epilogue's alignment (dm_gemm.hip's rows_ok)
   if (p.K % dmq4::BK != 0 || p.N % 8 != 0 || p.k_fold > 0 || p.c_dtype == DM_BF16_PAIR) return false;

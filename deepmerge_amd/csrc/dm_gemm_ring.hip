@@ -179,9 +179,8 @@ template <int WM, bool FOLD = false> bool set_lds_limit() {
 }  // namespace dmring
 
 // Decides whether the ring kernel runs this product; fills p.tiles_m / tiles_n / split_k and returns the wave height (8 or 4), 0 = no.
-int dm_gemm_ring_plan(GemmParams &p, int layout, int ab_dtype, bool aligned8) {
-  const char *env = getenv("DM_GEMM_RING");                      // 0 = off, 1 = routing rules, 2 = whenever legal (read per call: tests flip it)
-  const int mode = env ? atoi(env) : 1;
+int dm_gemm_ring_plan(GemmParams &p, const GemmSwitches &sw, int layout, int ab_dtype, bool aligned8) {
+  const int mode = sw.ring;                                      // DM_GEMM_RING: 0 = off, 1 = routing rules, 2 = whenever legal
   if (mode == 0 || layout != DM_NT || ab_dtype != DM_BF16 || !aligned8) return 0;
   if (p.K % dmring::BK != 0 || p.N % 8 != 0) return 0;
   if (p.k_fold > 0 && p.k_fold % dmring::BK != 0) return 0;      // folded contraction: segments of whole K tiles
@@ -216,8 +215,6 @@ int dm_gemm_ring_plan(GemmParams &p, int layout, int ab_dtype, bool aligned8) {
   p.tiles_n = (p.N + 127) / 128;
   p.split_k = 1;
   p.k_per_split = p.K;
-  const char *denv = getenv("DM_RING_DEBUG");
-  p.debug = denv ? atoi(denv) : 0;
   return wm;
 }
 

@@ -941,28 +941,13 @@ template <int LAYOUT, int DBG = 0, int EK = 0, bool FOLD = false, bool CS = true
   return hipFuncSetAttribute(reinterpret_cast<const void *>(dmw4::gemm_w4_kernel<LAYOUT, DBG, EK, FOLD, CS>), hipFuncAttributeMaxDynamicSharedMemorySize,
                              dmw4::LDS_BYTES) == hipSuccess;
 }
-int w4_cu_count() {
-  // DM_GEMM_CUS_RESERVED = n plans the one-workgroup-per-CU grids for n CUs fewer than the device has: a collective running next to
-  // the backward pass (RCCL kernels hold CUs for the length of an all-reduce) otherwise pushes the last workgroups of such a grid
-  // into a second round.  Default 0 -- to be tuned on a multi-GPU node, none was available to this build.
-  static const int n = [] {
-    int dev = 0, cus = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return 0;
-    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) return 0;
-    const char *e = getenv("DM_GEMM_CUS_RESERVED");
-    const int r = e ? atoi(e) : 0;
-    return (r > 0 && r < cus) ? cus - r : cus;
-  }();
-  return n;
-}
 }  // namespace
 
 // Decides whether the 4-wave persistent kernel runs this product (bf16 NT / NN); fills p.tiles_m / tiles_n and returns the grid
 // size (0 = not taken).  `aligned8`: the 8-column epilogue (dm_gemm_emit8) is legal for C / aux / grouped rows.
-int dm_gemm_w4_plan(GemmParams &p, int layout, int ab_dtype, bool aligned8, bool can_split, long long workspace_bytes) {
+int dm_gemm_w4_plan(GemmParams &p, const GemmSwitches &sw, int layout, int ab_dtype, bool aligned8, bool can_split, long long workspace_bytes) {
   using namespace dmw4;
-  const char *env = getenv("DM_GEMM_W4");         // 0 = off, 1 = routing rule, 2 = every legal product, 3 = every whole-round shape (read per call: tests flip it)
-  const int mode = env ? atoi(env) : 1;
+  const int mode = sw.w4;         // DM_GEMM_W4: 0 = off, 1 = routing rule, 2 = every legal product, 3 = every whole-round shape
   if (mode == 0 || ab_dtype != DM_BF16 || !aligned8) return 0;
   // FOLD instances: K steps of 32 contraction positions on both pieces of both operands (see the kernel): the standard plane-pair
   // pattern only -- left operand (hi, hi, lo), right operand (hi, lo, hi) -- and an even number of steps per tile
@@ -979,12 +964,11 @@ int dm_gemm_w4_plan(GemmParams &p, int layout, int ab_dtype, bool aligned8, bool
   }
   if (layout == DM_TN) {
     // wgrad: one (256 x 192 tile, K slice) per workgroup; slices of an even number of K steps chosen so that tiles x slices fills the CUs
-    const char *tenv = getenv("DM_GEMM_W4_TN");     // 0 = off, 1 = routing rule (default), 2 = every legal product
-    const int tmode = tenv ? atoi(tenv) : 1;
+    const int tmode = sw.w4_tn;     // DM_GEMM_W4_TN: 0 = off, 1 = routing rule (default), 2 = every legal product
     if (tmode == 0 || p.M % TM != 0 || p.N % TN != 0 || k_eff % (2 * bk_eff) != 0 || p.M % 8 != 0 || p.N % 8 != 0) return 0;
     if (!can_split || p.c_dtype != DM_F32) return 0;
     if (((long long)k_eff * p.lda + (fold ? p.a_fold[2] : 0)) * 2 >= (1LL << 31) || ((long long)k_eff * p.ldb + (fold ? p.b_fold[1] : 0)) * 2 >= (1LL << 31)) return 0;
-    const int cus = w4_cu_count();
+    const int cus = dm_gemm_cu_count();
     const long long tiles = (long long)(p.M / TM) * (p.N / TN);
     if (cus <= 0 || tiles > cus) return 0;
     const int steps = k_eff / bk_eff;
@@ -1020,7 +1004,7 @@ int dm_gemm_w4_plan(GemmParams &p, int layout, int ab_dtype, bool aligned8, bool
   if (spanA >= (1LL << 31) || spanB >= (1LL << 31)) return 0;
   const int tiles_m = (p.M + TM - 1) / TM, tiles_n = p.N / TN;
   const long long tiles = (long long)tiles_m * tiles_n;
-  const int cus = w4_cu_count();
+  const int cus = dm_gemm_cu_count();
   if (cus <= 0) return 0;
   {
     // Round 4: few tiles and a long contraction (the 4096-token stage's fc2 forward, fc1 / qkv dgrad: 64 tiles, K = 2304 .. 4096):
@@ -1032,7 +1016,8 @@ int dm_gemm_w4_plan(GemmParams &p, int layout, int ab_dtype, bool aligned8, bool
     // reduction -- OFF by default (DM_GEMM_W4_SLICES=1 for A/B runs); the M <= 1024 products gain from slices on 64 x 64 tiles instead.
     static const bool slices_on = [] { const char *e = getenv("DM_GEMM_W4_SLICES"); return e && atoi(e) == 1; }();
     constexpr long long LIM = (1LL << 31) / (128LL * 4);
-    if (slices_on && p.k_fold == 0 && can_split && mode != 0 && tiles * 2 <= cus && p.K >= 1536 && p.N < LIM && !(p.debug & 0x400)) {
+    // (no test of DM_DBG_LEAN_OFF here: dm_gemm sets the p.debug bits after the plans, so this rule has never seen the bit set)
+    if (slices_on && p.k_fold == 0 && can_split && mode != 0 && tiles * 2 <= cus && p.K >= 1536 && p.N < LIM) {
       const int steps = p.K / BK;
       int split = (int)(cus / tiles);
       if (split > 4) split = 4;
@@ -1104,7 +1089,7 @@ void dm_gemm_w4_launch(const GemmParams &p, int layout, int grid, hipStream_t s)
   // Which epilogue: the lean form (dm_gemm_common.h) where its preconditions hold -- plain rows, 32-bit offsets inside a wave pair's
   // 128 rows -- and the item structure is one of the instantiated ones; the generic form otherwise (and with DM_GEMM_EPI_LEAN=0).
   constexpr long long LIM = (1LL << 31) / (128LL * 4);
-  const bool lean_ok = !(p.debug & 0x400) && p.rows_per_group == 0 && p.ldc < LIM && p.ldr < LIM && p.ldaux < LIM && p.N < LIM && p.c_dtype != DM_BF16_PAIR;
+  const bool lean_ok = !(p.debug & DM_DBG_LEAN_OFF) && p.rows_per_group == 0 && p.ldc < LIM && p.ldr < LIM && p.ldaux < LIM && p.N < LIM && p.c_dtype != DM_BF16_PAIR;
   const bool c32 = p.c_dtype == DM_F32, x32 = p.aux_dtype == DM_F32;
   const bool aux_read = p.aux && (p.epilogue == DM_EPI_DGELU || p.epilogue == DM_EPI_MUL);
   const bool aux_write = p.aux && (p.epilogue == DM_EPI_GELU || p.epilogue == DM_EPI_GELU_GRAD);
@@ -1164,7 +1149,7 @@ void dm_gemm_w4_launch(const GemmParams &p, int layout, int grid, hipStream_t s)
 //   2  stream-K (long contractions): see gemm_w4_streamk_kernel; needs x.ws (dm_gemm_w4_grouped_ws_bytes), column sums to x.cs_out.
 // Returns the form taken, 0 = none (nothing launched).  launch = false: decide only.
 long long dm_gemm_w4_grouped_ws_bytes() {
-  const int cus = w4_cu_count();
+  const int cus = dm_gemm_cu_count();
   return (long long)(cus > 0 ? cus : 256) * 3 * (dmw4::TM * dmw4::TN + dmw4::TM) * 4;
 }
 int dm_gemm_w4_grouped(GemmParams *ps, int n, hipStream_t s, bool launch, const DmGroupedExtra &x) {
@@ -1174,7 +1159,7 @@ int dm_gemm_w4_grouped(GemmParams *ps, int n, hipStream_t s, bool launch, const 
   const char *menv = getenv("DM_GEMM_GROUPED");
   const int mode = menv ? atoi(menv) : 1;
   if (mode == 0 || n < 1 || n > GROUP_MAX) return 0;
-  const int cus = w4_cu_count();
+  const int cus = dm_gemm_cu_count();
   if (cus <= 0) return 0;
   GemmGroupSk sk{};
   GemmGroup &grp = sk.g;
