@@ -531,6 +531,7 @@ template <typename T> int dispatch(int which, const AttnParams &p, hipStream_t s
   return 0;
 }
 
+// (the message texts describe the generic path's limits -- a call beyond N <= 256 / D = 64 that gets here is also beyond those)
 int check_common(const char *who, int B, int N, int H, int D, int dtype) {
   DM_REQUIRE(B > 0 && H > 0 && N > 0 && N <= 256, DM_ERR_BAD_SHAPE, "%s: need 0 < N <= 4096 tokens and head dim <= 256 (got N=%d, D=%d, B=%d, H=%d)", who, N, D, B, H);
   DM_REQUIRE(D == HD, DM_ERR_BAD_SHAPE, "%s: head dim must be in 1..256 (got %d)", who, D);
@@ -541,7 +542,7 @@ int check_common(const char *who, int B, int N, int H, int D, int dtype) {
 
 }  // namespace
 
-// samples one dq workgroup walks: as many as keeps >= ~1.2 workgroups per CU in flight
+// samples one dq workgroup of the register kernels walks: as many as keeps >= ~1.2 workgroups per CU in flight
 static int batch_chunk(int B, int N, int H) {
   const int per_sample = ((N + QB - 1) / QB) * H;
   for (int c = 8; c > 1; c >>= 1)
@@ -549,10 +550,144 @@ static int batch_chunk(int B, int N, int H) {
   return 1;
 }
 
+// ---- the plan (dm_attention_plan.h): every routing rule of the attention entry points, once -----------------------------------
+const AttnSwitches &attn_switches() {
+  static const AttnSwitches sw = [] {
+    AttnSwitches v;
+    if (const char *e = getenv("DM_ATTN_PIPE")) v.pipe = atoi(e);
+    if (const char *e = getenv("DM_ATTN_Q32")) v.q32 = atoi(e);
+    if (const char *e = getenv("DM_ATTN_Q32_BWD")) v.q32_bwd = atoi(e);
+    if (const char *e = getenv("DM_ATTN_Q32_TABKV")) v.q32_tabkv = atoi(e) != 0;
+    if (const char *e = getenv("DM_ATTN_Q32_W8")) v.q32_w8 = atoi(e) != 0;
+    if (const char *e = getenv("DM_ATTN_Q32_TABW")) v.q32_tabw = atoi(e);
+    if (const char *e = getenv("DM_ATTN_PF")) v.pf = atoi(e) != 0;
+    if (const char *e = getenv("DM_ATTN_XCD")) v.xcd = atoi(e) != 0;
+    if (const char *e = getenv("DM_ATTN_X3")) v.x3 = atoi(e) != 0;
+    if (const char *e = getenv("DM_ATTN_X3_W8")) v.x3_w8 = atoi(e) != 0;
+    return v;
+  }();
+  return sw;
+}
+
+namespace {
+
+bool tokens32(const AttnCall &c) { return c.N > 128 && c.N <= 256; }      // 5 .. 8 key tiles of 32
+// a table form exists for cubes of 3 or 4 scales of 8 x 8 tokens (the entry points pass cube_s = 0 for any other cube)
+bool cube_fits(const AttnCall &c) { return c.N == 64 * c.cube_s && (c.cube_s == 3 || c.cube_s == 4); }
+// The persistent families' common gate under their switch `mode`: on, one sample's rows within a 32-bit DMA offset, and enough
+// (sample, head) pairs to keep persistent workgroups busy -- mode 2 lifts that last rule, and only for the family whose switch it is.
+bool persistent_gate(const AttnCall &c, int mode) {
+  return mode != 0 && (long long)c.N * 3 * c.H * 64 * 2 < (1LL << 31) && (mode == 2 || c.B * c.H >= 96);
+}
+
+AttnPass pass32(const AttnCall &c, AttnFamily f, AttnBias bias, int waves, int rows) {
+  AttnPass g{f, (c.N + 31) / 32, c.N % 32 != 0, bias, waves, 0, 0, 0};
+  attn_chunks(c.B, c.N, c.H, rows, g.nblk, g.chunks, g.bchunk);
+  return g;
+}
+// 16-row pipeline: exact tilings 128 / 192 / 256 unmasked, every other N masked with the tile count rounded up to an even number
+bool ragged16(const AttnCall &c) { return !(c.N == 128 || c.N == 192 || c.N == 256); }
+AttnPass pass_pipe16(const AttnCall &c, AttnBias bias) {
+  const int nkt = (c.N + 15) / 16;
+  AttnPass g{ATTN_PIPE16, ragged16(c) ? (nkt + 1) / 2 * 2 : nkt, ragged16(c), bias, 8, 0, 0, 0};
+  attn_chunks(c.B, c.N, c.H, 128, g.nblk, g.chunks, g.bchunk);
+  return g;
+}
+// register kernels: one workgroup per (64-row block, head, sample); the dQ kernel walks `bchunk` samples (it sums the slab)
+AttnPass pass_reg16(const AttnCall &c, int bchunk) {
+  return AttnPass{ATTN_REG16, (c.N + 15) / 16, c.N % 16 != 0, c.dense ? ATTN_BIAS_DENSE : ATTN_BIAS_NONE, 4, (c.N + QB - 1) / QB, (c.B + bchunk - 1) / bchunk, bchunk};
+}
+// bias-free 32-row forward / dQ: 8 waves (two per SIMD) where <= 7 tiles let K / V be staged once per (sample, head)
+int waves32(const AttnCall &c, const AttnSwitches &sw) { return (c.N + 31) / 32 <= 7 && sw.q32_w8 ? 8 : 4; }
+
+// the split entries take any batch (no B * H rule) and have no pipeline gate
+bool split_shape(const AttnCall &c, const AttnSwitches &sw) {
+  return sw.x3 && c.D == HD && tokens32(c) && c.B > 0 && c.H > 0 && persistent_gate(c, 2) && (!c.table || cube_fits(c));
+}
+
+}  // namespace
+
+AttnFwdPlan attn_plan_fwd(const AttnCall &c, const AttnSwitches &sw) {
+  AttnFwdPlan pl{};
+  pl.pf = sw.pf;
+  pl.xcd = sw.xcd;
+  if (c.split) {
+    if (!split_shape(c, sw)) pl.refused = ATTN_SHAPE_NOT_TAKEN;
+    else pl.pass = pass32(c, ATTN_X3, c.table ? ATTN_BIAS_TABLE : ATTN_BIAS_NONE, sw.x3_w8 ? 8 : 4, 128);      // (chunks of 128 rows on 8 waves too)
+    return pl;
+  }
+  pl.pass = pass_reg16(c, 1);                  // fp32, N <= 128 and whatever the gates below leave
+  if (c.D != HD || c.N > 256) {                            // checked before everything else (its own argument check: dm_attention_fwd)
+    pl.pass.family = ATTN_GENERIC;
+  } else if (c.dtype == DM_BF16) {
+    // The 32-row gate is DM_ATTN_Q32 alone (the backward's sits behind the pipeline's as well); a ragged N with dense rows stays
+    // here too.  The table form requires that no dense rows are given.  (Dense rows are 16-byte aligned here: the entry points
+    // reject a misaligned `bias` with DM_ERR_BAD_ALIGN before they ask for a plan, so the plan carries no alignment bit.)
+    if (tokens32(c) && persistent_gate(c, sw.q32) && !(c.table && (c.dense || !cube_fits(c)))) {
+      if (c.table) pl.pass = pass32(c, ATTN_Q32, ATTN_BIAS_TABLE, sw.q32_tabw == 4 ? 4 : 8, sw.q32_tabw == 4 ? 128 : 256);      // DM_ATTN_Q32_TABW: forward only
+      else if (c.dense) pl.pass = pass32(c, ATTN_Q32, ATTN_BIAS_DENSE, 4, 128);
+      else pl.pass = pass32(c, ATTN_Q32, ATTN_BIAS_NONE, waves32(c, sw), 32 * waves32(c, sw));
+    } else if (c.N >= 128 && persistent_gate(c, sw.pipe)) {
+      pl.pass = pass_pipe16(c, c.dense ? ATTN_BIAS_DENSE : ATTN_BIAS_NONE);
+    }
+  }
+  // a table without dense rows: only the 32-row table form may run -- every other kernel would drop the bias
+  if (c.table && !c.dense && !(pl.pass.family == ATTN_Q32 && pl.pass.bias == ATTN_BIAS_TABLE)) pl.refused = ATTN_SHAPE_NOT_TAKEN;
+  return pl;
+}
+
+AttnBwdPlan attn_plan_bwd(const AttnCall &c, const AttnSwitches &sw) {
+  AttnBwdPlan pl{};
+  pl.xcd = sw.xcd;
+  if (c.split) {
+    if (c.B > 0 && c.H > 0) {      // (filled for any N: dm_attention_split_bwd_chunks has always answered without asking the shape)
+      const AttnBias bias = c.table ? ATTN_BIAS_TABLE : ATTN_BIAS_NONE;
+      pl.dq = pass32(c, ATTN_X3, bias, sw.x3_w8 ? 8 : 4, 128);
+      pl.dkv = pass32(c, ATTN_X3, bias, 4, 128);
+      pl.slab_chunks = pl.dkv.chunks;
+    }
+    if (!split_shape(c, sw)) pl.refused = ATTN_SHAPE_NOT_TAKEN;
+    return pl;
+  }
+  // Register kernels: fp32 always, N < 128, and a ragged N with dense rows or a slab (v5's 193: the pipelined dK / dV would spill).
+  // Their dQ kernel sums the slab over its own batch_chunk.
+  pl.dq = pass_reg16(c, batch_chunk(c.B, c.N, c.H));
+  pl.dkv = pass_reg16(c, 1);
+  pl.slab_chunks = pl.dq.chunks;
+  if (c.D != HD || c.N > 256) {      // checked before everything else; takes no slab (dm_attention_bwd_batch_chunks still answers as for the register kernels)
+    pl.dq.family = pl.dkv.family = ATTN_GENERIC;
+    return pl;
+  }
+  const bool table_only = c.table && !c.dense;      // only the two table-reading kernels may run: every other kernel would drop the bias
+  if (c.dtype != DM_BF16) {
+    if (table_only) pl.refused = ATTN_TABLE_NEEDS_BF16;
+    return pl;
+  }
+  // The pipeline's gate stands in front of the 32-row kernels as well: DM_ATTN_PIPE, its B * H rule, no ragged N with rows or a slab.
+  if (c.N >= 128 && persistent_gate(c, sw.pipe) && !(ragged16(c) && (c.dense || c.slab))) {
+    // (a slab without dense rows still takes the pipelined dK / dV's bias instance: that is the one that sums dS)
+    pl.dq = pass_pipe16(c, c.dense ? ATTN_BIAS_DENSE : ATTN_BIAS_NONE);
+    pl.dkv = pass_pipe16(c, c.dense || c.slab ? ATTN_BIAS_DENSE : ATTN_BIAS_NONE);
+    // 32-row dQ under DM_ATTN_Q32_BWD's own gate.  A table whose cube fits is read, also when dense rows are given as well; a table
+    // whose cube does not fit refuses the pass altogether (the pipeline runs on the dense rows); no table: dense rows if given.
+    if (tokens32(c) && persistent_gate(c, sw.q32_bwd) && !(c.table && !cube_fits(c))) {
+      if (c.table) pl.dq = pass32(c, ATTN_Q32, ATTN_BIAS_TABLE, 8, 256);
+      else if (c.dense) pl.dq = pass32(c, ATTN_Q32, ATTN_BIAS_DENSE, 4, 128);
+      else pl.dq = pass32(c, ATTN_Q32, ATTN_BIAS_NONE, waves32(c, sw), 32 * waves32(c, sw));
+      // 32-row dK / dV only behind a 32-row dQ, and not under DM_ATTN_Q32_BWD=3 (pipelined dK / dV after the 32-row dQ).  The
+      // table-reading one comes first, also when dense rows are given as well; the other takes neither rows nor a slab.
+      const int w = (c.N + 31) / 32 <= 7 ? 8 : 4;
+      if (sw.q32_bwd != 3 && c.table && sw.q32_tabkv) pl.dkv = pass32(c, ATTN_Q32_TABKV, ATTN_BIAS_TABLE, 4, 128);
+      else if (sw.q32_bwd != 3 && !c.dense && !c.slab) pl.dkv = pass32(c, ATTN_Q32, ATTN_BIAS_NONE, w, 32 * w);
+    }
+    pl.slab_chunks = pl.dkv.chunks;      // (128 key rows per workgroup in both kernels that fill a slab)
+  }
+  if (table_only && pl.dkv.family != ATTN_Q32_TABKV) pl.refused = ATTN_TABLE_NOT_TAKEN;
+  return pl;
+}
+
 extern "C" int32_t dm_attention_bwd_batch_chunks(int32_t B, int32_t N, int32_t H, int32_t dtype) {
-  if (const int pc = dm_attn_bwd_pipe_chunks(B, N, H, dtype == DM_BF16)) return pc;     // pipelined kernels (dm_attention_pipe.hip)
-  const int c = batch_chunk(B, N, H);
-  return (B + c - 1) / c;
+  return attn_plan_bwd(AttnCall{B, N, H, HD, dtype == DM_BF16 ? DM_BF16 : DM_F32, true, false, 0, true, false}, attn_switches()).slab_chunks;
 }
 
 // dm_attention_generic.hip: any head dim <= 256 / up to 4096 tokens, fp32 arithmetic (ViT-H/14: D = 80, N = 257)
@@ -574,19 +709,20 @@ extern "C" int dm_attention_fwd(const void *qkv, const float *bias, void *out, f
   if (int rc = check_common("dm_attention_fwd", B, N, H, D, dtype)) return rc;
   DM_REQUIRE(qkv && out && lse, DM_ERR_BAD_SHAPE, "dm_attention_fwd: null pointer");
   DM_REQUIRE(dm_aligned16(qkv) && dm_aligned16(out) && dm_aligned16(bias), DM_ERR_BAD_ALIGN, "dm_attention_fwd: qkv/out/bias must be 16-byte aligned");
-  AttnParams p{};
-  p.qkv = qkv; p.bias = bias; p.out = out; p.lse = lse; p.B = B; p.N = N; p.H = H; p.scale = scale; p.bchunk = 1;
+  const AttnFwdPlan pl = attn_plan_fwd(AttnCall{B, N, H, D, dtype, bias != nullptr, false, 0, false, false}, attn_switches());
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   {
     const double esz = (dtype == DM_BF16) ? 2.0 : 4.0;
     DmProfScope prof(dtype == DM_BF16 ? "attn_fwd_bf16" : "attn_fwd_f32", s, 4.0 * B * H * (double)N * N * HD,
                      esz * 4.0 * B * H * (double)N * HD);
-    bool piped = false;
-    if (dtype == DM_BF16) {      // persistent LDS-DMA pipeline for the big stage (dm_attention_pipe.hip)
-      AttnPipeParams pp{qkv, bias, out, lse, B, N, H, scale};
-      piped = dm_attn_fwd_q32(pp, s) || dm_attn_fwd_pipe(pp, s);     // 32 rows per wave (dm_attention_q32.hip), else 16 rows per wave
-    }
-    if (!piped) {
+    const AttnPipeParams pp{qkv, bias, out, lse, B, N, H, scale};
+    if (pl.pass.family == ATTN_Q32) {
+      DM_REQUIRE(dm_attn_fwd_q32(pl, pp, s), DM_ERR_HIP, "dm_attention_fwd: kernel could not be configured");
+    } else if (pl.pass.family == ATTN_PIPE16) {
+      dm_attn_fwd_pipe(pl, pp, s);
+    } else {
+      AttnParams p{};
+      p.qkv = qkv; p.bias = bias; p.out = out; p.lse = lse; p.B = B; p.N = N; p.H = H; p.scale = scale; p.bchunk = 1;
       if (dtype == DM_BF16) dispatch<bf16_t>(0, p, s); else dispatch<float>(0, p, s);
     }
   }
@@ -594,41 +730,38 @@ extern "C" int dm_attention_fwd(const void *qkv, const float *bias, void *out, f
   return DM_OK;
 }
 
-// Forward with the relative-position bias formed inside the kernel from the table (no dense [H, N, N] rows): the 32-rows-per-wave
-// kernel with the head's table in LDS (dm_attention_q32.hip).  Token cube (cube_s, 8, 8), scale-major then row-major.
-static bool relpos_inkernel(int32_t B, int32_t N, int32_t H, int32_t D, int32_t cube_s, int32_t cube_h, int32_t cube_w, int32_t dtype) {
-  if (dtype != DM_BF16 || D != HD || cube_h != 8 || cube_w != 8 || B <= 0 || H <= 0) return false;
-  AttnPipeParams pp{nullptr, nullptr, nullptr, nullptr, B, N, H, 1.f};
-  pp.table = reinterpret_cast<const float *>(16);      // (shape decision only)
-  pp.cube_s = cube_s;
-  if (!dm_attn_fwd_q32_takes(pp)) return false;
-  // the backward pass must take the table too: a caller told "in kernel" holds no dense rows, and the 16-row / generic
-  // backward kernels would then run WITHOUT the bias (the forward and backward switches and B * H rules differ)
-  AttnPipeBwdParams bp{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, B, N, H, 1.f};
-  bp.table = pp.table;
-  bp.cube_s = cube_s;
-  return dm_attn_bwd_tab_takes(bp);
+// The call of the table-reading entry points: a relative-position table of a (cube_s, cube_h, cube_w) token cube (scale-major, then
+// row-major) and no dense rows.  Only (s, 8, 8) cubes have a table form: any other cube is passed on as cube_s = 0, which fits nothing.
+static AttnCall table_call(int32_t B, int32_t N, int32_t H, int32_t D, int32_t cube_s, int32_t cube_h, int32_t cube_w, int32_t dtype, bool split) {
+  return AttnCall{B, N, H, D, dtype, false, true, cube_h == 8 && cube_w == 8 ? cube_s : 0, false, split};
 }
 
+// 1: the caller may hold NO dense bias rows -- the forward takes the table itself AND so do both backward passes (their switches
+// and B * H rules differ); otherwise the 16-row / generic backward kernels would run WITHOUT the bias.
 extern "C" int32_t dm_attention_relpos_inkernel(int32_t B, int32_t N, int32_t H, int32_t D, int32_t cube_s, int32_t cube_h, int32_t cube_w,
                                                 int32_t dtype) {
-  return relpos_inkernel(B, N, H, D, cube_s, cube_h, cube_w, dtype) ? 1 : 0;
+  if (B <= 0 || H <= 0) return 0;
+  const AttnCall c = table_call(B, N, H, D, cube_s, cube_h, cube_w, dtype, false);
+  return !attn_plan_fwd(c, attn_switches()).refused && !attn_plan_bwd(c, attn_switches()).refused ? 1 : 0;
 }
 
+// Forward with the relative-position bias formed inside the kernel from the table (no dense [H, N, N] rows): the 32-rows-per-wave
+// kernel with the head's table in LDS (dm_attention_q32.hip).
 extern "C" int dm_attention_fwd_relpos(const void *qkv, const float *table, int32_t cube_s, int32_t cube_h, int32_t cube_w, void *out,
                                        float *lse, int32_t B, int32_t N, int32_t H, int32_t D, float scale, int32_t dtype, void *stream) {
-  DM_REQUIRE(relpos_inkernel(B, N, H, D, cube_s, cube_h, cube_w, dtype), DM_ERR_UNSUPPORTED,
+  DM_REQUIRE(dm_attention_relpos_inkernel(B, N, H, D, cube_s, cube_h, cube_w, dtype), DM_ERR_UNSUPPORTED,
              "dm_attention_fwd_relpos: shape not taken (B=%d N=%d H=%d D=%d cube=%dx%dx%d dtype=%d); gather the bias and call dm_attention_fwd",
              B, N, H, D, cube_s, cube_h, cube_w, dtype);
   DM_REQUIRE(qkv && table && out && lse, DM_ERR_BAD_SHAPE, "dm_attention_fwd_relpos: null pointer");
   DM_REQUIRE(dm_aligned16(qkv) && dm_aligned16(out), DM_ERR_BAD_ALIGN, "dm_attention_fwd_relpos: qkv/out must be 16-byte aligned");
+  const AttnFwdPlan pl = attn_plan_fwd(table_call(B, N, H, D, cube_s, cube_h, cube_w, dtype, false), attn_switches());
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   {
     DmProfScope prof("attn_fwd_bf16", s, 4.0 * B * H * (double)N * N * HD, 2.0 * 4.0 * B * H * (double)N * HD);
     AttnPipeParams pp{qkv, nullptr, out, lse, B, N, H, scale};
     pp.table = table;
     pp.cube_s = cube_s;
-    DM_REQUIRE(dm_attn_fwd_q32(pp, s), DM_ERR_UNSUPPORTED, "dm_attention_fwd_relpos: kernel could not be configured");
+    DM_REQUIRE(dm_attn_fwd_q32(pl, pp, s), DM_ERR_UNSUPPORTED, "dm_attention_fwd_relpos: kernel could not be configured");
   }
   DM_LAUNCH_CHECK("dm_attention_fwd_relpos");
   return DM_OK;
@@ -651,36 +784,32 @@ static int attention_bwd(const void *qkv, const float *bias, const float *bias_t
   DM_REQUIRE(dm_aligned16(qkv) && dm_aligned16(out) && dm_aligned16(dout) && dm_aligned16(dqkv) && dm_aligned16(bias) &&
              dm_aligned16(bias_t) && dm_aligned16(lse) && dm_aligned16(delta) && dm_aligned16(dbias_slab), DM_ERR_BAD_ALIGN,
              "dm_attention_bwd: tensors must be 16-byte aligned");
-  AttnParams p{};
-  p.qkv = qkv; p.bias = bias; p.bias_t = bias ? bias_t : nullptr; p.out = out; p.dout = dout; p.lse = const_cast<float *>(lse);
-  p.delta = delta; p.dqkv = dqkv; p.slab = dbias_slab;
-  p.B = B; p.N = N; p.H = H; p.scale = scale; p.bchunk = batch_chunk(B, N, H);
+  // (with dense rows the table's cube goes to the plan as given: cube_h / cube_w are looked at only where no rows are given)
+  const AttnBwdPlan pl = attn_plan_bwd(AttnCall{B, N, H, D, dtype, bias != nullptr, table != nullptr, cube_s, dbias_slab != nullptr, false}, attn_switches());
+  DM_REQUIRE(pl.refused != ATTN_TABLE_NEEDS_BF16, DM_ERR_UNSUPPORTED, "dm_attention_bwd_relpos: the table-reading kernels are bf16 only");
+  DM_REQUIRE(!pl.refused, DM_ERR_UNSUPPORTED,
+             "dm_attention_bwd_relpos: the table-reading backward kernels do not take this call (B=%d N=%d H=%d, switches "
+             "DM_ATTN_PIPE / DM_ATTN_Q32_BWD / DM_ATTN_Q32_TABKV) and no dense bias rows were given", B, N, H);
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   {
     const double esz = (dtype == DM_BF16) ? 2.0 : 4.0;
     DmProfScope prof(dtype == DM_BF16 ? "attn_bwd_bf16" : "attn_bwd_f32", s, 10.0 * B * H * (double)N * N * HD,
                      esz * 8.0 * B * H * (double)N * HD);
-    bool piped = false;
-    DM_REQUIRE(!(table && !bias) || dtype == DM_BF16, DM_ERR_UNSUPPORTED, "dm_attention_bwd_relpos: the table-reading kernels are bf16 only");
-    if (dtype == DM_BF16) {
+    if (pl.dkv.family == ATTN_REG16) {
+      AttnParams p{};
+      p.qkv = qkv; p.bias = bias; p.bias_t = bias ? bias_t : nullptr; p.out = out; p.dout = dout; p.lse = const_cast<float *>(lse);
+      p.delta = delta; p.dqkv = dqkv; p.slab = dbias_slab;
+      p.B = B; p.N = N; p.H = H; p.scale = scale; p.bchunk = pl.dq.bchunk;
+      if (dtype == DM_BF16) { dispatch<bf16_t>(1, p, s); dispatch<bf16_t>(2, p, s); }
+      else { dispatch<float>(1, p, s); dispatch<float>(2, p, s); }
+    } else {
       AttnPipeBwdParams pp{qkv, bias, out, dout, lse, delta, dqkv, dbias_slab, B, N, H, scale};
       pp.table = table;
       pp.cube_s = cube_s;
-      // a table without dense rows: only the two table-reading kernels may run -- every other kernel would drop the bias
-      const bool table_only = table && !bias;
-      DM_REQUIRE(!table_only || dm_attn_bwd_tab_takes(pp), DM_ERR_UNSUPPORTED,
-                 "dm_attention_bwd_relpos: the table-reading backward kernels do not take this call (B=%d N=%d H=%d, switches "
-                 "DM_ATTN_PIPE / DM_ATTN_Q32_BWD / DM_ATTN_Q32_TABKV) and no dense bias rows were given", B, N, H);
-      if (dm_attn_bwd_pipe_ok(pp)) {      // 32 rows per wave where those kernels take the pass (dm_attention_q32_bwd.hip), else 16
-        const bool dq = dm_attn_bwd_dq_q32(pp, s);
-        const bool dkv = dq && dm_attn_bwd_dkv_q32(pp, s);
-        DM_REQUIRE(!table_only || dkv, DM_ERR_HIP, "dm_attention_bwd_relpos: a table-reading backward kernel could not be configured");
-        piped = dkv || dm_attn_bwd_pipe(pp, s, dq);
-      }
-    }
-    if (!piped) {
-      if (dtype == DM_BF16) { dispatch<bf16_t>(1, p, s); dispatch<bf16_t>(2, p, s); }
-      else { dispatch<float>(1, p, s); dispatch<float>(2, p, s); }
+      // (with a plan there is no next family to fall through to when an instance cannot be configured)
+      DM_REQUIRE(pl.dq.family != ATTN_Q32 || dm_attn_bwd_dq_q32(pl, pp, s), DM_ERR_HIP, "dm_attention_bwd: the dQ kernel could not be configured");
+      if (pl.dkv.family == ATTN_PIPE16) dm_attn_bwd_pipe(pl, pp, s);      // (and its dQ kernel first, where that pass is the pipeline's too)
+      else DM_REQUIRE(dm_attn_bwd_dkv_q32(pl, pp, s), DM_ERR_HIP, "dm_attention_bwd: the dK / dV kernel could not be configured");
     }
   }
   DM_LAUNCH_CHECK("dm_attention_bwd");
@@ -700,22 +829,23 @@ extern "C" int dm_attention_bwd_relpos(const void *qkv, const float *table, int3
                                        float *dbias_slab, int32_t B, int32_t N, int32_t H, int32_t D, float scale, int32_t dtype, void *stream) {
   DM_REQUIRE(table, DM_ERR_BAD_SHAPE, "dm_attention_bwd_relpos: null table");
   // (with dense rows given, the A/B switches may route either pass to the kernels that read them; without, attention_bwd refuses)
-  DM_REQUIRE(bias || relpos_inkernel(B, N, H, D, cube_s, cube_h, cube_w, dtype), DM_ERR_UNSUPPORTED,
+  DM_REQUIRE(bias || dm_attention_relpos_inkernel(B, N, H, D, cube_s, cube_h, cube_w, dtype), DM_ERR_UNSUPPORTED,
              "dm_attention_bwd_relpos: shape not taken (B=%d N=%d H=%d D=%d cube=%dx%dx%d dtype=%d); call dm_attention_bwd", B, N, H, D, cube_s,
              cube_h, cube_w, dtype);
   return attention_bwd(qkv, bias, bias_t, table, cube_s, out, dout, lse, dqkv, delta, dbias_slab, B, N, H, D, scale, dtype, stream);
 }
 
 // ---- "bf16x3" numerics mode: fp32 tensors, split-bf16 products (dm_attention_x3.hip) ------------------------------------------------------------
-static bool split_shape(int32_t B, int32_t N, int32_t H, int32_t D, int32_t has_table, int32_t cube_s, int32_t cube_h, int32_t cube_w) {
-  if (D != HD) return false;
-  if (has_table && (cube_h != 8 || cube_w != 8)) return false;
-  return dm_attn_x3_shape(B, N, H, has_table != 0, cube_s);
+static AttnCall split_call(int32_t B, int32_t N, int32_t H, int32_t D, bool has_table, int32_t cube_s, int32_t cube_h, int32_t cube_w, bool slab) {
+  AttnCall c = table_call(B, N, H, D, cube_s, cube_h, cube_w, DM_F32, true);
+  c.table = has_table;
+  c.slab = slab;
+  return c;
 }
 
 extern "C" int32_t dm_attention_split_ok(int32_t B, int32_t N, int32_t H, int32_t D, int32_t has_table, int32_t cube_s, int32_t cube_h,
                                          int32_t cube_w) {
-  return split_shape(B, N, H, D, has_table, cube_s, cube_h, cube_w) ? 1 : 0;
+  return attn_plan_fwd(split_call(B, N, H, D, has_table != 0, cube_s, cube_h, cube_w, false), attn_switches()).refused ? 0 : 1;
 }
 
 static int split_fwd_impl(const float *qkv, void *qkv_hi, void *qkv_lo, const float *table, int32_t cube_s, int32_t cube_h, int32_t cube_w, float *out,
@@ -733,7 +863,8 @@ extern "C" int dm_attention_split_fwd_pair(const float *qkv, void *qkv_hi, void 
 }
 static int split_fwd_impl(const float *qkv, void *qkv_hi, void *qkv_lo, const float *table, int32_t cube_s, int32_t cube_h, int32_t cube_w, float *out,
                           void *out_pair, float *lse, int32_t B, int32_t N, int32_t H, int32_t D, float scale, void *stream) {
-  DM_REQUIRE(split_shape(B, N, H, D, table != nullptr, cube_s, cube_h, cube_w), DM_ERR_UNSUPPORTED,
+  const AttnFwdPlan pl = attn_plan_fwd(split_call(B, N, H, D, table != nullptr, cube_s, cube_h, cube_w, false), attn_switches());
+  DM_REQUIRE(!pl.refused, DM_ERR_UNSUPPORTED,
              "dm_attention_split_fwd: shape not taken (B=%d N=%d H=%d D=%d cube=%dx%dx%d); use dm_attention_fwd", B, N, H, D, cube_s, cube_h, cube_w);
   DM_REQUIRE(qkv_hi && qkv_lo && out && lse, DM_ERR_BAD_SHAPE, "dm_attention_split_fwd: null pointer");
   DM_REQUIRE(dm_aligned16(qkv) && dm_aligned16(qkv_hi) && dm_aligned16(qkv_lo) && dm_aligned16(out), DM_ERR_BAD_ALIGN,
@@ -744,13 +875,15 @@ static int split_fwd_impl(const float *qkv, void *qkv_hi, void *qkv_lo, const fl
     if (qkv) dm_attn_x3_split(qkv, qkv_hi, qkv_lo, (long long)B * N * 3 * H * HD, s);      // (NULL: the caller filled the two images -- a DM_BF16_PAIR product)
     AttnX3Params p{reinterpret_cast<const bf16_t *>(qkv_hi), reinterpret_cast<const bf16_t *>(qkv_lo), table, cube_s, out, lse, B, N, H, scale,
                    reinterpret_cast<bf16_t *>(out_pair)};
-    DM_REQUIRE(dm_attn_fwd_x3(p, s), DM_ERR_UNSUPPORTED, "dm_attention_split_fwd: kernel could not be configured");
+    DM_REQUIRE(dm_attn_fwd_x3(pl, p, s), DM_ERR_UNSUPPORTED, "dm_attention_split_fwd: kernel could not be configured");
   }
   DM_LAUNCH_CHECK("dm_attention_split_fwd");
   return DM_OK;
 }
 
-extern "C" int32_t dm_attention_split_bwd_chunks(int32_t B, int32_t N, int32_t H) { return dm_attn_x3_chunks(B, N, H); }
+extern "C" int32_t dm_attention_split_bwd_chunks(int32_t B, int32_t N, int32_t H) {
+  return attn_plan_bwd(split_call(B, N, H, HD, false, 0, 0, 0, false), attn_switches()).slab_chunks;
+}
 
 static int split_bwd_impl(const void *qkv_hi, const void *qkv_lo, const float *table, int32_t cube_s, int32_t cube_h, int32_t cube_w,
                           const float *out, const float *dout, void *dout_hi, void *dout_lo, const float *lse, float *dqkv, void *dqkv_pair,
@@ -770,7 +903,8 @@ extern "C" int dm_attention_split_bwd_pair(const void *qkv_hi, const void *qkv_l
 static int split_bwd_impl(const void *qkv_hi, const void *qkv_lo, const float *table, int32_t cube_s, int32_t cube_h, int32_t cube_w,
                           const float *out, const float *dout, void *dout_hi, void *dout_lo, const float *lse, float *dqkv, void *dqkv_pair,
                           float *delta, float *dbias_slab, int32_t B, int32_t N, int32_t H, int32_t D, float scale, void *stream) {
-  DM_REQUIRE(split_shape(B, N, H, D, table != nullptr, cube_s, cube_h, cube_w), DM_ERR_UNSUPPORTED,
+  const AttnBwdPlan pl = attn_plan_bwd(split_call(B, N, H, D, table != nullptr, cube_s, cube_h, cube_w, dbias_slab != nullptr), attn_switches());
+  DM_REQUIRE(!pl.refused, DM_ERR_UNSUPPORTED,
              "dm_attention_split_bwd: shape not taken (B=%d N=%d H=%d D=%d cube=%dx%dx%d); use dm_attention_bwd", B, N, H, D, cube_s, cube_h, cube_w);
   DM_REQUIRE(qkv_hi && qkv_lo && out && dout && dout_hi && dout_lo && lse && (dqkv || dqkv_pair) && delta, DM_ERR_BAD_SHAPE, "dm_attention_split_bwd: null pointer");
   DM_REQUIRE(table || !dbias_slab, DM_ERR_BAD_SHAPE, "dm_attention_split_bwd: a bias-gradient slab needs the table");
@@ -784,7 +918,7 @@ static int split_bwd_impl(const void *qkv_hi, const void *qkv_lo, const float *t
     AttnX3BwdParams p{reinterpret_cast<const bf16_t *>(qkv_hi), reinterpret_cast<const bf16_t *>(qkv_lo), reinterpret_cast<const bf16_t *>(dout_hi),
                       reinterpret_cast<const bf16_t *>(dout_lo), out, dout, lse, delta, dqkv, reinterpret_cast<bf16_t *>(dqkv_pair),
                       (long long)B * N * 3 * H * HD, dbias_slab, table, cube_s, B, N, H, scale};
-    DM_REQUIRE(dm_attn_bwd_dq_x3(p, s) && dm_attn_bwd_dkv_x3(p, s), DM_ERR_UNSUPPORTED, "dm_attention_split_bwd: kernels could not be configured");
+    DM_REQUIRE(dm_attn_bwd_dq_x3(pl, p, s) && dm_attn_bwd_dkv_x3(pl, p, s), DM_ERR_UNSUPPORTED, "dm_attention_split_bwd: kernels could not be configured");
   }
   DM_LAUNCH_CHECK("dm_attention_split_bwd");
   return DM_OK;

@@ -11,7 +11,7 @@
 //     the hardware-transposed LDS read).
 // LDS images: K [N keys][128 B], 16-byte chunk index XOR (key & 7) (conflict-free ds_read_b128 fragments);
 //             V [N keys][128 B], 32-byte slot index XOR ((key >> 1) & 3) (each half-wave of a transposed read covers all banks).
-#include <cstdlib>
+#include <type_traits>
 
 #include "dm_attention_pipe.h"
 #include "dm_common.h"
@@ -80,11 +80,7 @@ __device__ __forceinline__ bool pipe_coords(int nblk, int H, int chunks, int &h,
   chunk = group / H;
   return true;
 }
-inline bool pipe_xcd_map() {
-  static const bool on = [] { const char *e = getenv("DM_ATTN_XCD"); return !(e && atoi(e) == 0); }();
-  return on;
-}
-inline int pipe_grid_size(int nblk, int H, int chunks) { return pipe_xcd_map() ? (H * chunks + 7) / 8 * 8 * nblk : H * chunks * nblk; }
+inline int pipe_grid_size(int nblk, int H, int chunks, bool xcd) { return xcd ? (H * chunks + 7) / 8 * 8 * nblk : H * chunks * nblk; }
 
 // RAGGED: N is not NKT * 16 (ViT's 197 / 198, v5's 193): tokens >= N are zero-filled by the DMA descriptor and masked.
 template <int NKT, bool RAGGED, bool PF>
@@ -717,16 +713,8 @@ __global__ __launch_bounds__(512) void attn_bwd_dkv_pipe_kernel(const AttnPipeBw
   }
 }
 
-inline void pipe_grid(int B, int N, int H, int &nblk, int &chunks, int &bchunk) {
-  nblk = (N + ROWS - 1) / ROWS;
-  chunks = 256 / (H * nblk);
-  if (chunks < 1) chunks = 1;
-  if (chunks > B) chunks = B;
-  bchunk = (B + chunks - 1) / chunks;
-  chunks = (B + bchunk - 1) / bchunk;
-}
-
-template <int NKT, bool RAGGED> void launch_bwd(const AttnPipeBwdParams &p, hipStream_t s, bool dq_done) {
+// dQ unless the plan gave that pass to another family (the 32-row kernel has then written dQ and delta), then dK / dV (+ slab)
+template <int NKT, bool RAGGED> void launch_bwd(const AttnBwdPlan &pl, const AttnPipeBwdParams &p, hipStream_t s) {
   constexpr int NP = NKT * 16;
   constexpr int LDS_DQ = 4 * NP * 128 + WB_BYTES, LDS_DKV = 2 * (2 * NP * 128 + 2048) + WB_BYTES;
   static const bool ok = hipFuncSetAttribute(reinterpret_cast<const void *>(attn_bwd_dq_pipe_kernel<NKT, RAGGED>),
@@ -736,95 +724,51 @@ template <int NKT, bool RAGGED> void launch_bwd(const AttnPipeBwdParams &p, hipS
                          hipFuncSetAttribute(reinterpret_cast<const void *>(attn_bwd_dkv_pipe_kernel<NKT, RAGGED, false>),
                                              hipFuncAttributeMaxDynamicSharedMemorySize, LDS_DKV) == hipSuccess;
   (void)ok;
-  int nblk, chunks, bchunk;
-  pipe_grid(p.B, p.N, p.H, nblk, chunks, bchunk);
-  if (!dq_done)       // (dQ and delta may already have been written by the 32-row kernel of dm_attention_q32_bwd.hip)
-    hipLaunchKernelGGL((attn_bwd_dq_pipe_kernel<NKT, RAGGED>), dim3(pipe_grid_size(nblk, p.H, chunks)), dim3(512), LDS_DQ, s, p, bchunk, nblk, pipe_xcd_map() ? chunks : -chunks);
-  if (p.bias || p.slab)
-    hipLaunchKernelGGL((attn_bwd_dkv_pipe_kernel<NKT, RAGGED, true>), dim3(pipe_grid_size(nblk, p.H, chunks)), dim3(512), LDS_DKV, s, p, bchunk, nblk, pipe_xcd_map() ? chunks : -chunks);
+  const AttnPass &g = pl.dkv;
+  const dim3 grid(pipe_grid_size(g.nblk, p.H, g.chunks, pl.xcd));
+  const int chunks = pl.xcd ? g.chunks : -g.chunks;
+  if (pl.dq.family == ATTN_PIPE16)
+    hipLaunchKernelGGL((attn_bwd_dq_pipe_kernel<NKT, RAGGED>), grid, dim3(512), LDS_DQ, s, p, g.bchunk, g.nblk, chunks);
+  if (g.bias != ATTN_BIAS_NONE)
+    hipLaunchKernelGGL((attn_bwd_dkv_pipe_kernel<NKT, RAGGED, true>), grid, dim3(512), LDS_DKV, s, p, g.bchunk, g.nblk, chunks);
   else
-    hipLaunchKernelGGL((attn_bwd_dkv_pipe_kernel<NKT, RAGGED, false>), dim3(pipe_grid_size(nblk, p.H, chunks)), dim3(512), LDS_DKV, s, p, bchunk, nblk, pipe_xcd_map() ? chunks : -chunks);
+    hipLaunchKernelGGL((attn_bwd_dkv_pipe_kernel<NKT, RAGGED, false>), grid, dim3(512), LDS_DKV, s, p, g.bchunk, g.nblk, chunks);
 }
 
-
-template <int NKT, bool RAGGED, bool PF> void launch_pf(const AttnPipeParams &p, hipStream_t s);
-template <int NKT, bool RAGGED> void launch(const AttnPipeParams &p, hipStream_t s) {
-  static const bool pf = [] { const char *e = getenv("DM_ATTN_PF"); return !(e && atoi(e) == 0); }();
-  if (pf) launch_pf<NKT, RAGGED, true>(p, s);
-  else launch_pf<NKT, RAGGED, false>(p, s);
-}
-template <int NKT, bool RAGGED, bool PF> void launch_pf(const AttnPipeParams &p, hipStream_t s) {
+// one workgroup per CU (two K/V buffers fill the LDS)
+template <int NKT, bool RAGGED, bool PF> void launch_fwd(const AttnFwdPlan &pl, const AttnPipeParams &p, hipStream_t s) {
   constexpr int NP = NKT * 16;
   constexpr int LDS = 4 * NP * 128 + WB_BYTES;
   static const bool ok = hipFuncSetAttribute(reinterpret_cast<const void *>(attn_fwd_pipe_kernel<NKT, RAGGED, PF>),
                                              hipFuncAttributeMaxDynamicSharedMemorySize, LDS) == hipSuccess;
   (void)ok;
-  // one workgroup per CU (two K/V buffers fill the LDS): as many chunks as fit one round of the 256 CUs
-  int nblk, chunks, bchunk;
-  pipe_grid(p.B, p.N, p.H, nblk, chunks, bchunk);
-  hipLaunchKernelGGL((attn_fwd_pipe_kernel<NKT, RAGGED, PF>), dim3(pipe_grid_size(nblk, p.H, chunks)), dim3(512), LDS, s, p, bchunk, nblk, pipe_xcd_map() ? chunks : -chunks);
+  const AttnPass &g = pl.pass;
+  hipLaunchKernelGGL((attn_fwd_pipe_kernel<NKT, RAGGED, PF>), dim3(pipe_grid_size(g.nblk, p.H, g.chunks, pl.xcd)), dim3(512), LDS, s, p, g.bchunk,
+                     g.nblk, pl.xcd ? g.chunks : -g.chunks);
+}
+
+// The instances that exist: exact tilings 128 / 192 / 256 (8 / 12 / 16 tiles) unmasked, every other N in (128, 256) masked with
+// the tile count rounded up to an even number.  f(tiles, ragged) with both as compile-time constants.
+template <typename F> void with_tiles16(const AttnPass &g, F &&f) {
+  using std::integral_constant;
+  switch (g.nkt) {
+    case 8: f(integral_constant<int, 8>{}, std::false_type{}); break;
+    case 10: f(integral_constant<int, 10>{}, std::true_type{}); break;
+    case 12: if (g.ragged) f(integral_constant<int, 12>{}, std::true_type{}); else f(integral_constant<int, 12>{}, std::false_type{}); break;
+    case 14: f(integral_constant<int, 14>{}, std::true_type{}); break;
+    default: if (g.ragged) f(integral_constant<int, 16>{}, std::true_type{}); else f(integral_constant<int, 16>{}, std::false_type{}); break;
+  }
 }
 
 }  // namespace dmpipe
 
-// Which instance serves N tokens: exact tilings 128 / 192 / 256 use the unmasked kernels, every other N in (128, 256]
-// (ViT's 197 / 198, v5's 193, ...) the masked ones with the tile count rounded up to an even number.
-static bool pipe_shape_ok(int B, int N, int H) {
-  static const int mode = [] { const char *e = getenv("DM_ATTN_PIPE"); return e ? atoi(e) : 1; }();
-  if (mode == 0) return false;
-  if (N < 128 || N > 256) return false;
-  if ((long long)N * 3 * H * 64 * 2 >= (1LL << 31)) return false;            // one sample's rows must fit a 32-bit DMA offset
-  if (mode != 2 && B * H < 96) return false;                                  // too little work for persistent workgroups
-  return true;
-}
-static int pipe_tiles(int N, bool &ragged) {
-  ragged = !(N == 128 || N == 192 || N == 256);
-  const int nkt = (N + 15) / 16;
-  return ragged ? (nkt + 1) / 2 * 2 : nkt;
+void dm_attn_fwd_pipe(const AttnFwdPlan &pl, const AttnPipeParams &p, hipStream_t s) {
+  dmpipe::with_tiles16(pl.pass, [&](auto nkt, auto ragged) {
+    if (pl.pf) dmpipe::launch_fwd<nkt.value, ragged.value, true>(pl, p, s);
+    else dmpipe::launch_fwd<nkt.value, ragged.value, false>(pl, p, s);
+  });
 }
 
-bool dm_attn_fwd_pipe(const AttnPipeParams &p, hipStream_t s) {
-  if (!pipe_shape_ok(p.B, p.N, p.H)) return false;
-  bool ragged;
-  switch (pipe_tiles(p.N, ragged)) {
-    case 8: dmpipe::launch<8, false>(p, s); return true;
-    case 10: dmpipe::launch<10, true>(p, s); return true;
-    case 12: if (ragged) dmpipe::launch<12, true>(p, s); else dmpipe::launch<12, false>(p, s); return true;
-    case 14: dmpipe::launch<14, true>(p, s); return true;
-    case 16: if (ragged) dmpipe::launch<16, true>(p, s); else dmpipe::launch<16, false>(p, s); return true;
-    default: return false;
-  }
-}
-
-int dm_attn_bwd_pipe_chunks(int B, int N, int H, int dtype_is_bf16) {
-  if (!dtype_is_bf16 || !pipe_shape_ok(B, N, H)) return 0;
-  bool ragged;
-  pipe_tiles(N, ragged);
-  if (ragged) return 0;          // a masked backward only runs without a bias (below), where no slab exists
-  int nblk, chunks, bchunk;
-  dmpipe::pipe_grid(B, N, H, nblk, chunks, bchunk);
-  return chunks;
-}
-
-bool dm_attn_bwd_pipe_ok(const AttnPipeBwdParams &p) {
-  if (!pipe_shape_ok(p.B, p.N, p.H)) return false;
-  bool ragged;
-  const int nkt = pipe_tiles(p.N, ragged);
-  // masked + bias (v5's N = 193): the dK/dV kernel would need > 256 registers (it spills); the generic kernels take it
-  if (ragged && (p.bias || p.slab)) return false;
-  return nkt >= 8 && nkt <= 16 && nkt % 2 == 0;
-}
-
-bool dm_attn_bwd_pipe(const AttnPipeBwdParams &p, hipStream_t s, bool dq_done) {
-  if (!dm_attn_bwd_pipe_ok(p)) return false;
-  bool ragged;
-  const int nkt = pipe_tiles(p.N, ragged);
-  switch (nkt) {
-    case 8: dmpipe::launch_bwd<8, false>(p, s, dq_done); return true;
-    case 10: dmpipe::launch_bwd<10, true>(p, s, dq_done); return true;
-    case 12: if (ragged) dmpipe::launch_bwd<12, true>(p, s, dq_done); else dmpipe::launch_bwd<12, false>(p, s, dq_done); return true;
-    case 14: dmpipe::launch_bwd<14, true>(p, s, dq_done); return true;
-    case 16: if (ragged) dmpipe::launch_bwd<16, true>(p, s, dq_done); else dmpipe::launch_bwd<16, false>(p, s, dq_done); return true;
-    default: return false;
-  }
+void dm_attn_bwd_pipe(const AttnBwdPlan &pl, const AttnPipeBwdParams &p, hipStream_t s) {
+  dmpipe::with_tiles16(pl.dkv, [&](auto nkt, auto ragged) { dmpipe::launch_bwd<nkt.value, ragged.value>(pl, p, s); });
 }

@@ -2,7 +2,7 @@
 // inline-asm MFMAs with explicit register classes, the asm LDS-DMA, lane-exchange helpers, the workgroup -> (head, block, chunk) map.
 // Why the MFMAs are asm and what that obliges the kernels to do by hand is explained at the top of dm_attention_q32.hip.
 #pragma once
-#include <cstdlib>
+#include <type_traits>
 
 #include "dm_attention_pipe.h"
 #include "dm_common.h"
@@ -114,5 +114,16 @@ __device__ __forceinline__ bool coords(int nblk, int H, int chunks, int &h, int 
   return true;
 }
 inline int grid_size(int nblk, int H, int chunks) { return (H * chunks + 7) / 8 * 8 * nblk; }
+
+
+// f(tiles) with the plan's key-tile count as a compile-time constant: 5 .. 8 tiles of 32 keys (128 < N <= 256)
+template <typename F> bool with_tiles32(int nkt, F &&f) {
+  switch (nkt) {
+    case 5: return f(std::integral_constant<int, 5>{});
+    case 6: return f(std::integral_constant<int, 6>{});
+    case 7: return f(std::integral_constant<int, 7>{});
+    default: return f(std::integral_constant<int, 8>{});
+  }
+}
 
 }  // namespace dmq32

@@ -624,65 +624,33 @@ __global__ __launch_bounds__(64 * NW, NW / 4) void attn_fwd_q32_kernel(const Att
 #endif
 }
 
-inline void grid(int B, int N, int H, int rows, int &nblk, int &chunks, int &bchunk) {
-  nblk = (N + rows - 1) / rows;
-  chunks = 256 / (H * nblk);
-  if (chunks < 1) chunks = 1;
-  if (chunks > B) chunks = B;
-  bchunk = (B + chunks - 1) / chunks;
-  chunks = (B + bchunk - 1) / bchunk;
-}
-
-template <int NKT, bool RAGGED, int BM, int NW> bool launch(const AttnPipeParams &p, hipStream_t s) {
+template <int NKT, bool RAGGED, int BM, int NW> bool launch(const AttnPass &g, const AttnPipeParams &p, hipStream_t s) {
   constexpr int LDS = 4 * NKT * 32 * 128 + (BM == 2 && NW == 8 ? 0 : NW * WB_WAVE) + (BM == 2 ? (NKT - 1) * 15 * TAB_PITCH * 4 * (NW == 8 ? 2 : 1) : 0);
   static_assert(LDS <= 160 * 1024, "LDS budget");
   static const bool ok = hipFuncSetAttribute(reinterpret_cast<const void *>(attn_fwd_q32_kernel<NKT, RAGGED, BM, NW>),
                                              hipFuncAttributeMaxDynamicSharedMemorySize, LDS) == hipSuccess;
-  if (!ok) return false;
-  int nblk, chunks, bchunk;
-  grid(p.B, p.N, p.H, 32 * NW, nblk, chunks, bchunk);
-  const int wgs = NW == 8 ? (p.B * p.H < 256 ? p.B * p.H : 256) : grid_size(nblk, p.H, chunks);      // 8 waves: one run of units per CU
-  hipLaunchKernelGGL((attn_fwd_q32_kernel<NKT, RAGGED, BM, NW>), dim3(wgs), dim3(64 * NW), LDS, s, p, bchunk, nblk, chunks);
+  if (!ok) return false;      // (not reachable on gfx950: every instance is under the 160 KB of the static_assert)
+  const int wgs = NW == 8 ? (p.B * p.H < 256 ? p.B * p.H : 256) : grid_size(g.nblk, p.H, g.chunks);      // 8 waves: one run of units per CU
+  hipLaunchKernelGGL((attn_fwd_q32_kernel<NKT, RAGGED, BM, NW>), dim3(wgs), dim3(64 * NW), LDS, s, p, g.bchunk, g.nblk, g.chunks);
   return true;
 }
 
-template <int NKT> bool launch_n(const AttnPipeParams &p, hipStream_t s) {
-  const bool ragged = p.N != NKT * 32;
+// The plan's (bias mode, waves, ragged) -> the instance.  Table: 6 or 8 tiles (a cube of 3 or 4 scales), never ragged, on 8 waves
+// (two per SIMD) or 4; dense rows: 4 waves (128 bias registers); none: 8 waves where <= 7 tiles let K / V be staged once per
+// (sample, head), else 4.
+template <int NKT> bool launch_n(const AttnPass &g, const AttnPipeParams &p, hipStream_t s) {
   if constexpr (NKT % 2 == 0) {
-    if (p.table) {                               // DM_ATTN_Q32_TABW=4: the table form with one wave per SIMD (A/B runs)
-      static const int tabw = [] { const char *e = getenv("DM_ATTN_Q32_TABW"); return e ? atoi(e) : 8; }();
-      return tabw == 4 ? launch<NKT, false, 2, 4>(p, s) : launch<NKT, false, 2, 8>(p, s);
-    }
+    if (g.bias == ATTN_BIAS_TABLE) return g.waves == 4 ? launch<NKT, false, 2, 4>(g, p, s) : launch<NKT, false, 2, 8>(g, p, s);
   }
-  if (p.bias) return ragged ? launch<NKT, true, 1, 4>(p, s) : launch<NKT, false, 1, 4>(p, s);
-  if constexpr (NKT <= 7) {                     // 8 waves: two per SIMD, K / V staged once per (sample, head); DM_ATTN_Q32_W8=0 for A/B runs
-    static const bool w8 = [] { const char *e = getenv("DM_ATTN_Q32_W8"); return !(e && atoi(e) == 0); }();
-    if (w8) return ragged ? launch<NKT, true, 0, 8>(p, s) : launch<NKT, false, 0, 8>(p, s);
+  if (g.bias == ATTN_BIAS_DENSE) return g.ragged ? launch<NKT, true, 1, 4>(g, p, s) : launch<NKT, false, 1, 4>(g, p, s);
+  if constexpr (NKT <= 7) {
+    if (g.waves == 8) return g.ragged ? launch<NKT, true, 0, 8>(g, p, s) : launch<NKT, false, 0, 8>(g, p, s);
   }
-  return ragged ? launch<NKT, true, 0, 4>(p, s) : launch<NKT, false, 0, 4>(p, s);
+  return g.ragged ? launch<NKT, true, 0, 4>(g, p, s) : launch<NKT, false, 0, 4>(g, p, s);
 }
 
 }  // namespace dmq32
 
-// bf16, head dim 64, 128 < N <= 256 (5 .. 8 key tiles of 32).  DM_ATTN_Q32=0 keeps the 16-row pipelined kernels (A/B runs).
-bool dm_attn_fwd_q32_takes(const AttnPipeParams &p) {
-  static const int mode = [] { const char *e = getenv("DM_ATTN_Q32"); return e ? atoi(e) : 1; }();
-  if (mode == 0) return false;
-  if (p.N <= 128 || p.N > 256) return false;
-  if ((long long)p.N * 3 * p.H * 64 * 2 >= (1LL << 31)) return false;          // one sample's rows must fit a 32-bit DMA offset
-  if (mode != 2 && p.B * p.H < 96) return false;                              // too little work for persistent workgroups
-  if (p.bias && (reinterpret_cast<uintptr_t>(p.bias) & 15u)) return false;
-  if (p.table && (p.bias || p.N != 64 * p.cube_s || (p.cube_s != 3 && p.cube_s != 4))) return false;
-  return true;
-}
-
-bool dm_attn_fwd_q32(const AttnPipeParams &p, hipStream_t s) {
-  if (!dm_attn_fwd_q32_takes(p)) return false;
-  switch ((p.N + 31) / 32) {
-    case 5: return dmq32::launch_n<5>(p, s);
-    case 6: return dmq32::launch_n<6>(p, s);
-    case 7: return dmq32::launch_n<7>(p, s);
-    case 8: return dmq32::launch_n<8>(p, s);
-    default: return false;
-  }
+bool dm_attn_fwd_q32(const AttnFwdPlan &pl, const AttnPipeParams &p, hipStream_t s) {
+  return dmq32::with_tiles32(pl.pass.nkt, [&](auto nkt) { return dmq32::launch_n<nkt.value>(pl.pass, p, s); });
 }

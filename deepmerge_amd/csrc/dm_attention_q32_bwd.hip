@@ -1025,120 +1025,62 @@ __global__ __launch_bounds__(256, 1) void attn_bwd_dkv_tab_kernel(const AttnPipe
   }
 }
 
-inline void grid_bwd(int B, int N, int H, int rows, int &nblk, int &chunks, int &bchunk) {
-  nblk = (N + rows - 1) / rows;
-  chunks = 256 / (H * nblk);
-  if (chunks < 1) chunks = 1;
-  if (chunks > B) chunks = B;
-  bchunk = (B + chunks - 1) / chunks;
-  chunks = (B + bchunk - 1) / bchunk;
-}
-
-template <int NKT, bool RAGGED, int BM, int NW> bool launch_dq(const AttnPipeBwdParams &p, hipStream_t s) {
+template <int NKT, bool RAGGED, int BM, int NW> bool launch_dq(const AttnPass &g, const AttnPipeBwdParams &p, hipStream_t s) {
   constexpr int LDS = 4 * NKT * 32 * 128 + (BM == 2 ? 0 : NW * WB_WAVE) + (BM == 2 ? (NKT - 1) * 15 * TAB_PITCH * 4 : 0);
   static_assert(LDS <= 160 * 1024, "LDS budget");
   static const bool ok = hipFuncSetAttribute(reinterpret_cast<const void *>(attn_bwd_dq_q32_kernel<NKT, RAGGED, BM, NW>),
                                              hipFuncAttributeMaxDynamicSharedMemorySize, LDS) == hipSuccess;
-  if (!ok) return false;
-  int nblk, chunks, bchunk;
-  grid_bwd(p.B, p.N, p.H, 32 * NW, nblk, chunks, bchunk);
-  const int wgs = NW == 8 ? (p.B * p.H < 256 ? p.B * p.H : 256) : grid_size(nblk, p.H, chunks);      // 8 waves: one run of units per CU
-  hipLaunchKernelGGL((attn_bwd_dq_q32_kernel<NKT, RAGGED, BM, NW>), dim3(wgs), dim3(64 * NW), LDS, s, p, bchunk, nblk, chunks);
+  if (!ok) return false;      // (not reachable on gfx950: every instance is under the 160 KB of the static_assert)
+  const int wgs = NW == 8 ? (p.B * p.H < 256 ? p.B * p.H : 256) : grid_size(g.nblk, p.H, g.chunks);      // 8 waves: one run of units per CU
+  hipLaunchKernelGGL((attn_bwd_dq_q32_kernel<NKT, RAGGED, BM, NW>), dim3(wgs), dim3(64 * NW), LDS, s, p, g.bchunk, g.nblk, g.chunks);
   return true;
 }
 
-template <int NKT> bool launch_dq_n(const AttnPipeBwdParams &p, hipStream_t s) {
-  const bool ragged = p.N != NKT * 32;
+// The plan's (bias mode, waves, ragged) -> the instance, as in the forward (dm_attention_q32.hip); the table form has 8 waves only.
+template <int NKT> bool launch_dq_n(const AttnPass &g, const AttnPipeBwdParams &p, hipStream_t s) {
   if constexpr (NKT % 2 == 0) {
-    if (p.table && !ragged) return launch_dq<NKT, false, 2, 8>(p, s);
+    if (g.bias == ATTN_BIAS_TABLE) return launch_dq<NKT, false, 2, 8>(g, p, s);
   }
-  if (p.bias) return ragged ? launch_dq<NKT, true, 1, 4>(p, s) : launch_dq<NKT, false, 1, 4>(p, s);
+  if (g.bias == ATTN_BIAS_DENSE) return g.ragged ? launch_dq<NKT, true, 1, 4>(g, p, s) : launch_dq<NKT, false, 1, 4>(g, p, s);
   if constexpr (NKT <= 7) {
-    static const bool w8 = [] { const char *e = getenv("DM_ATTN_Q32_W8"); return !(e && atoi(e) == 0); }();
-    if (w8) return ragged ? launch_dq<NKT, true, 0, 8>(p, s) : launch_dq<NKT, false, 0, 8>(p, s);
+    if (g.waves == 8) return g.ragged ? launch_dq<NKT, true, 0, 8>(g, p, s) : launch_dq<NKT, false, 0, 8>(g, p, s);
   }
-  return ragged ? launch_dq<NKT, true, 0, 4>(p, s) : launch_dq<NKT, false, 0, 4>(p, s);
+  return g.ragged ? launch_dq<NKT, true, 0, 4>(g, p, s) : launch_dq<NKT, false, 0, 4>(g, p, s);
 }
 
-template <int NKT, bool RAGGED, int NW> bool launch_dkv(const AttnPipeBwdParams &p, hipStream_t s) {
+template <int NKT, bool RAGGED, int NW> bool launch_dkv(const AttnPass &g, const AttnPipeBwdParams &p, hipStream_t s) {
   constexpr int LDS = 4 * NKT * 32 * 128 + 2 * (2 * NKT * 32 * 4) + NW * WB_WAVE;
   static_assert(LDS <= 160 * 1024, "LDS budget");
   static const bool ok = hipFuncSetAttribute(reinterpret_cast<const void *>(attn_bwd_dkv_q32_kernel<NKT, RAGGED, NW>),
                                              hipFuncAttributeMaxDynamicSharedMemorySize, LDS) == hipSuccess;
   if (!ok) return false;
-  int nblk, chunks, bchunk;
-  grid_bwd(p.B, p.N, p.H, 32 * NW, nblk, chunks, bchunk);
-  hipLaunchKernelGGL((attn_bwd_dkv_q32_kernel<NKT, RAGGED, NW>), dim3(grid_size(nblk, p.H, chunks)), dim3(64 * NW), LDS, s, p, bchunk, nblk, chunks);
+  hipLaunchKernelGGL((attn_bwd_dkv_q32_kernel<NKT, RAGGED, NW>), dim3(grid_size(g.nblk, p.H, g.chunks)), dim3(64 * NW), LDS, s, p, g.bchunk, g.nblk, g.chunks);
   return true;
 }
 
-template <int NKT> bool launch_dkv_tab(const AttnPipeBwdParams &p, hipStream_t s) {
+template <int NKT> bool launch_dkv_tab(const AttnPass &g, const AttnPipeBwdParams &p, hipStream_t s) {
   constexpr int LDS = 4 * NKT * 32 * 128 + 2 * (2 * NKT * 32 * 4) + 4 * WB_WAVE + (NKT - 1) * 15 * TAB_PITCH * 4;
   static_assert(LDS <= 160 * 1024, "LDS budget");
   static const bool ok = hipFuncSetAttribute(reinterpret_cast<const void *>(attn_bwd_dkv_tab_kernel<NKT>),
                                              hipFuncAttributeMaxDynamicSharedMemorySize, LDS) == hipSuccess;
   if (!ok) return false;
-  int nblk, chunks, bchunk;
-  grid_bwd(p.B, p.N, p.H, 128, nblk, chunks, bchunk);            // the same chunks as dm_attn_bwd_pipe_chunks: one slab per chunk
-  hipLaunchKernelGGL((attn_bwd_dkv_tab_kernel<NKT>), dim3(grid_size(nblk, p.H, chunks)), dim3(256), LDS, s, p, bchunk, nblk, chunks);
+  hipLaunchKernelGGL((attn_bwd_dkv_tab_kernel<NKT>), dim3(grid_size(g.nblk, p.H, g.chunks)), dim3(256), LDS, s, p, g.bchunk, g.nblk, g.chunks);
   return true;
 }
 
-template <int NKT> bool launch_dkv_n(const AttnPipeBwdParams &p, hipStream_t s) {
-  const bool ragged = p.N != NKT * 32;
-  if constexpr (NKT <= 7) return ragged ? launch_dkv<NKT, true, 8>(p, s) : launch_dkv<NKT, false, 8>(p, s);
-  else return ragged ? launch_dkv<NKT, true, 4>(p, s) : launch_dkv<NKT, false, 4>(p, s);
+// bias-free dK / dV: 8 waves for <= 7 tiles, 4 for 8 (the plan's `waves` says the same)
+template <int NKT> bool launch_dkv_n(const AttnPass &g, const AttnPipeBwdParams &p, hipStream_t s) {
+  if constexpr (NKT <= 7) return g.ragged ? launch_dkv<NKT, true, 8>(g, p, s) : launch_dkv<NKT, false, 8>(g, p, s);
+  else return g.ragged ? launch_dkv<NKT, true, 4>(g, p, s) : launch_dkv<NKT, false, 4>(g, p, s);
 }
 
 }  // namespace dmq32
 
-// dK / dV pass without a bias (reads p.delta, written by a dQ pass): bf16, head dim 64, 128 < N <= 256; true if it took the call.
-bool dm_attn_bwd_dkv_q32(const AttnPipeBwdParams &p, hipStream_t s) {
-  static const int mode = [] { const char *e = getenv("DM_ATTN_Q32_BWD"); return e ? atoi(e) : 1; }();
-  if (mode == 0 || mode == 3) return false;                       // 3: new dQ only (A/B runs)
-  if (p.table && p.N == 64 * p.cube_s && (p.cube_s == 3 || p.cube_s == 4) && (mode == 2 || p.B * p.H >= 96) &&
-      (long long)p.N * 3 * p.H * 64 * 2 < (1LL << 31)) {
-    static const bool tabkv = [] { const char *e = getenv("DM_ATTN_Q32_TABKV"); return !(e && atoi(e) == 0); }();      // A/B switch
-    if (tabkv) return p.cube_s == 3 ? dmq32::launch_dkv_tab<6>(p, s) : dmq32::launch_dkv_tab<8>(p, s);
-  }
-  if (p.bias || p.slab) return false;
-  if (p.N <= 128 || p.N > 256) return false;
-  if ((long long)p.N * 3 * p.H * 64 * 2 >= (1LL << 31)) return false;
-  if (mode != 2 && p.B * p.H < 96) return false;
-  switch ((p.N + 31) / 32) {
-    case 5: return dmq32::launch_dkv_n<5>(p, s);
-    case 6: return dmq32::launch_dkv_n<6>(p, s);
-    case 7: return dmq32::launch_dkv_n<7>(p, s);
-    case 8: return dmq32::launch_dkv_n<8>(p, s);
-    default: return false;
-  }
+bool dm_attn_bwd_dkv_q32(const AttnBwdPlan &pl, const AttnPipeBwdParams &p, hipStream_t s) {
+  if (pl.dkv.family == ATTN_Q32_TABKV) return pl.dkv.nkt == 6 ? dmq32::launch_dkv_tab<6>(pl.dkv, p, s) : dmq32::launch_dkv_tab<8>(pl.dkv, p, s);
+  return dmq32::with_tiles32(pl.dkv.nkt, [&](auto nkt) { return dmq32::launch_dkv_n<nkt.value>(pl.dkv, p, s); });
 }
 
-bool dm_attn_bwd_tab_takes(const AttnPipeBwdParams &p) {
-  static const int mode = [] { const char *e = getenv("DM_ATTN_Q32_BWD"); return e ? atoi(e) : 1; }();
-  static const bool tabkv = [] { const char *e = getenv("DM_ATTN_Q32_TABKV"); return !(e && atoi(e) == 0); }();
-  if (mode == 0 || mode == 3 || !tabkv || !p.table) return false;
-  if (p.N != 64 * p.cube_s || (p.cube_s != 3 && p.cube_s != 4)) return false;
-  if ((long long)p.N * 3 * p.H * 64 * 2 >= (1LL << 31)) return false;
-  if (mode != 2 && p.B * p.H < 96) return false;
-  return dm_attn_bwd_pipe_ok(p);      // attention_bwd only reaches the 32-row kernels behind this gate (DM_ATTN_PIPE, B * H)
-}
-
-// dQ pass (+ delta) of the backward: bf16, head dim 64, 128 < N <= 256.  The dK / dV pass that follows reads p.delta.
-// true if it took the call; DM_ATTN_Q32_BWD=0 keeps the 16-row pipelined dQ kernel (A/B runs).
-bool dm_attn_bwd_dq_q32(const AttnPipeBwdParams &p, hipStream_t s) {
-  static const int mode = [] { const char *e = getenv("DM_ATTN_Q32_BWD"); return e ? atoi(e) : 1; }();
-  if (mode == 0) return false;
-  if (p.N <= 128 || p.N > 256) return false;
-  if ((long long)p.N * 3 * p.H * 64 * 2 >= (1LL << 31)) return false;
-  if (mode != 2 && p.B * p.H < 96) return false;
-  if (p.bias && (reinterpret_cast<uintptr_t>(p.bias) & 15u)) return false;
-  if (p.table && (p.N != 64 * p.cube_s || (p.cube_s != 3 && p.cube_s != 4))) return false;      // (the dense rows take the pass if given)
-  switch ((p.N + 31) / 32) {
-    case 5: return dmq32::launch_dq_n<5>(p, s);
-    case 6: return dmq32::launch_dq_n<6>(p, s);
-    case 7: return dmq32::launch_dq_n<7>(p, s);
-    case 8: return dmq32::launch_dq_n<8>(p, s);
-    default: return false;
-  }
+bool dm_attn_bwd_dq_q32(const AttnBwdPlan &pl, const AttnPipeBwdParams &p, hipStream_t s) {
+  return dmq32::with_tiles32(pl.dq.nkt, [&](auto nkt) { return dmq32::launch_dq_n<nkt.value>(pl.dq, p, s); });
 }

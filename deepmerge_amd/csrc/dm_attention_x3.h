@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "dm_attention_plan.h"
 #include "dm_common.h"
 
 struct AttnX3Params {
@@ -15,11 +16,10 @@ struct AttnX3Params {
   bf16_t *out_pair;        // or NULL: the hi / lo plane pair of `out` on the side (lo plane B*N*H*64 elements behind the hi plane)
 };
 
-// shapes the kernels take: head dim 64, 128 < N <= 256, bias absent or a (3 | 4, 8, 8) cube's table; DM_ATTN_X3=0 switches them off
-bool dm_attn_x3_shape(int B, int N, int H, bool has_table, int cube_s);
 // x [n] fp32 -> hi = bf16(x), lo = bf16(x - hi); n % 4 == 0
 void dm_attn_x3_split(const float *x, void *hi, void *lo, long long n, hipStream_t s);
-bool dm_attn_fwd_x3(const AttnX3Params &p, hipStream_t s);
+// The three launchers launch exactly the instance the plan names (ATTN_X3); false if its dynamic LDS size could not be set.
+bool dm_attn_fwd_x3(const AttnFwdPlan &pl, const AttnX3Params &p, hipStream_t s);
 
 struct AttnX3BwdParams {
   const bf16_t *hi, *lo;       // split images of qkv (from the forward pass)
@@ -36,6 +36,5 @@ struct AttnX3BwdParams {
   int B, N, H;
   float scale;
 };
-bool dm_attn_bwd_dq_x3(const AttnX3BwdParams &p, hipStream_t s);
-bool dm_attn_bwd_dkv_x3(const AttnX3BwdParams &p, hipStream_t s);
-int dm_attn_x3_chunks(int B, int N, int H);
+bool dm_attn_bwd_dq_x3(const AttnBwdPlan &pl, const AttnX3BwdParams &p, hipStream_t s);
+bool dm_attn_bwd_dkv_x3(const AttnBwdPlan &pl, const AttnX3BwdParams &p, hipStream_t s);

@@ -900,100 +900,63 @@ __global__ __launch_bounds__(256, 1) void attn_bwd_dkv_x3_kernel(const AttnX3Bwd
   }
 }
 
-inline void grid(int B, int N, int H, int &nblk, int &chunks, int &bchunk) {
-  nblk = (N + 127) / 128;
-  chunks = 256 / (H * nblk);
-  if (chunks < 1) chunks = 1;
-  if (chunks > B) chunks = B;
-  bchunk = (B + chunks - 1) / chunks;
-  chunks = (B + bchunk - 1) / bchunk;
-}
-
-// DM_ATTN_X3_W8=0: the one-wave-per-SIMD forms of the forward / dQ kernels (A/B runs)
-inline bool x3_w8() {
-  static const bool on = [] { const char *e = getenv("DM_ATTN_X3_W8"); return !(e && atoi(e) == 0); }();
-  return on;
-}
-
-template <int NKT, bool RAGGED, bool TAB, int NW> bool launch_fwd_nw(const AttnX3Params &p, hipStream_t s) {
+template <int NKT, bool RAGGED, bool TAB, int NW> bool launch_fwd_nw(const AttnPass &g, const AttnX3Params &p, hipStream_t s) {
   constexpr int LDS = 4 * NKT * 32 * 128 + (TAB ? (NKT - 1) * 15 * TAB_PITCH * 4 : 0);
   static_assert(LDS <= 160 * 1024, "LDS budget");
   static const bool ok = hipFuncSetAttribute(reinterpret_cast<const void *>(attn_fwd_x3_kernel<NKT, RAGGED, TAB, NW>),
                                              hipFuncAttributeMaxDynamicSharedMemorySize, LDS) == hipSuccess;
-  if (!ok) return false;
-  int nblk, chunks, bchunk;
-  grid(p.B, p.N, p.H, nblk, chunks, bchunk);
-  const int wgs = NW == 8 ? (p.B * p.H < 256 ? p.B * p.H : 256) : grid_size(nblk, p.H, chunks);      // 8 waves: one run of units per CU
-  hipLaunchKernelGGL((attn_fwd_x3_kernel<NKT, RAGGED, TAB, NW>), dim3(wgs), dim3(64 * NW), LDS, s, p, bchunk, nblk, chunks);
+  if (!ok) return false;      // (not reachable on gfx950: every instance is under the 160 KB of the static_assert)
+  const int wgs = NW == 8 ? (p.B * p.H < 256 ? p.B * p.H : 256) : grid_size(g.nblk, p.H, g.chunks);      // 8 waves: one run of units per CU
+  hipLaunchKernelGGL((attn_fwd_x3_kernel<NKT, RAGGED, TAB, NW>), dim3(wgs), dim3(64 * NW), LDS, s, p, g.bchunk, g.nblk, g.chunks);
   return true;
 }
-template <int NKT, bool RAGGED, bool TAB> bool launch_fwd(const AttnX3Params &p, hipStream_t s) {
-  return x3_w8() ? launch_fwd_nw<NKT, RAGGED, TAB, 8>(p, s) : launch_fwd_nw<NKT, RAGGED, TAB, 4>(p, s);
-}
-
-template <int NKT> bool launch_fwd_n(const AttnX3Params &p, hipStream_t s) {
-  const bool ragged = p.N != NKT * 32;
-  if constexpr (NKT % 2 == 0) {
-    if (p.table) return !ragged && launch_fwd<NKT, false, true>(p, s);
+// (the three launchers are static members so that launch_n below can take them as one template argument)
+template <int NKT, bool RAGGED, bool TAB> struct Fwd {
+  static bool go(const AttnPass &g, const AttnX3Params &p, hipStream_t s) {
+    return g.waves == 8 ? launch_fwd_nw<NKT, RAGGED, TAB, 8>(g, p, s) : launch_fwd_nw<NKT, RAGGED, TAB, 4>(g, p, s);
   }
-  if (p.table) return false;
-  return ragged ? launch_fwd<NKT, true, false>(p, s) : launch_fwd<NKT, false, false>(p, s);
-}
+};
 
-template <int NKT, bool RAGGED, bool TAB, int NW> bool launch_dq_nw(const AttnX3BwdParams &p, hipStream_t s) {
+template <int NKT, bool RAGGED, bool TAB, int NW> bool launch_dq_nw(const AttnPass &g, const AttnX3BwdParams &p, hipStream_t s) {
   constexpr int LDS = 4 * NKT * 32 * 128 + (TAB ? (NKT - 1) * 15 * TAB_PITCH * 4 : 0);
   static const bool ok = hipFuncSetAttribute(reinterpret_cast<const void *>(attn_bwd_dq_x3_kernel<NKT, RAGGED, TAB, NW>),
                                              hipFuncAttributeMaxDynamicSharedMemorySize, LDS) == hipSuccess;
   if (!ok) return false;
-  int nblk, chunks, bchunk;
-  grid(p.B, p.N, p.H, nblk, chunks, bchunk);
-  const int wgs = NW == 8 ? (p.B * p.H < 256 ? p.B * p.H : 256) : grid_size(nblk, p.H, chunks);
-  hipLaunchKernelGGL((attn_bwd_dq_x3_kernel<NKT, RAGGED, TAB, NW>), dim3(wgs), dim3(64 * NW), LDS, s, p, bchunk, nblk, chunks);
+  const int wgs = NW == 8 ? (p.B * p.H < 256 ? p.B * p.H : 256) : grid_size(g.nblk, p.H, g.chunks);
+  hipLaunchKernelGGL((attn_bwd_dq_x3_kernel<NKT, RAGGED, TAB, NW>), dim3(wgs), dim3(64 * NW), LDS, s, p, g.bchunk, g.nblk, g.chunks);
   return true;
 }
-template <int NKT, bool RAGGED, bool TAB> bool launch_dq(const AttnX3BwdParams &p, hipStream_t s) {
-  return x3_w8() ? launch_dq_nw<NKT, RAGGED, TAB, 8>(p, s) : launch_dq_nw<NKT, RAGGED, TAB, 4>(p, s);
-}
-
-template <int NKT> bool launch_dq_n(const AttnX3BwdParams &p, hipStream_t s) {
-  const bool ragged = p.N != NKT * 32;
-  if constexpr (NKT % 2 == 0) {
-    if (p.table) return !ragged && launch_dq<NKT, false, true>(p, s);
+template <int NKT, bool RAGGED, bool TAB> struct Dq {
+  static bool go(const AttnPass &g, const AttnX3BwdParams &p, hipStream_t s) {
+    return g.waves == 8 ? launch_dq_nw<NKT, RAGGED, TAB, 8>(g, p, s) : launch_dq_nw<NKT, RAGGED, TAB, 4>(g, p, s);
   }
-  if (p.table) return false;
-  return ragged ? launch_dq<NKT, true, false>(p, s) : launch_dq<NKT, false, false>(p, s);
-}
+};
 
-template <int NKT, bool RAGGED, bool TAB> bool launch_dkv(const AttnX3BwdParams &p, hipStream_t s) {
-  constexpr int LDS = 4 * NKT * 32 * 128 + 2 * NKT * 32 * 4 + (TAB ? (NKT - 1) * 15 * TAB_PITCH * 4 : 0);
-  static_assert(LDS <= 160 * 1024, "LDS budget");
-  static const bool ok = hipFuncSetAttribute(reinterpret_cast<const void *>(attn_bwd_dkv_x3_kernel<NKT, RAGGED, TAB>),
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, LDS) == hipSuccess;
-  if (!ok) return false;
-  int nblk, chunks, bchunk;
-  grid(p.B, p.N, p.H, nblk, chunks, bchunk);
-  hipLaunchKernelGGL((attn_bwd_dkv_x3_kernel<NKT, RAGGED, TAB>), dim3(grid_size(nblk, p.H, chunks)), dim3(256), LDS, s, p, bchunk, nblk, chunks);
-  return true;
-}
-
-template <int NKT> bool launch_dkv_n(const AttnX3BwdParams &p, hipStream_t s) {
-  const bool ragged = p.N != NKT * 32;
-  if constexpr (NKT % 2 == 0) {
-    if (p.table) return !ragged && launch_dkv<NKT, false, true>(p, s);
+template <int NKT, bool RAGGED, bool TAB> struct Dkv {
+  static bool go(const AttnPass &g, const AttnX3BwdParams &p, hipStream_t s) {
+    constexpr int LDS = 4 * NKT * 32 * 128 + 2 * NKT * 32 * 4 + (TAB ? (NKT - 1) * 15 * TAB_PITCH * 4 : 0);
+    static_assert(LDS <= 160 * 1024, "LDS budget");
+    static const bool ok = hipFuncSetAttribute(reinterpret_cast<const void *>(attn_bwd_dkv_x3_kernel<NKT, RAGGED, TAB>),
+                                               hipFuncAttributeMaxDynamicSharedMemorySize, LDS) == hipSuccess;
+    if (!ok) return false;
+    hipLaunchKernelGGL((attn_bwd_dkv_x3_kernel<NKT, RAGGED, TAB>), dim3(grid_size(g.nblk, p.H, g.chunks)), dim3(256), LDS, s, p, g.bchunk, g.nblk, g.chunks);
+    return true;
   }
-  if (p.table) return false;
-  return ragged ? launch_dkv<NKT, true, false>(p, s) : launch_dkv<NKT, false, false>(p, s);
+};
+
+// The plan's (bias mode, ragged) -> the instance of one of the three launchers above: the table form exists for 6 and 8 tiles (a
+// cube of 3 or 4 scales) and is never ragged.
+template <template <int, bool, bool> class L, typename P> bool launch_n(const AttnPass &g, const P &p, hipStream_t s) {
+  return with_tiles32(g.nkt, [&](auto nkt) {
+    constexpr int NKT = nkt.value;
+    if constexpr (NKT % 2 == 0) {
+      if (g.bias == ATTN_BIAS_TABLE) return L<NKT, false, true>::go(g, p, s);
+    }
+    return g.ragged ? L<NKT, true, false>::go(g, p, s) : L<NKT, false, false>::go(g, p, s);
+  });
 }
 
 }  // namespace dmx3
-
-bool dm_attn_x3_shape(int B, int N, int H, bool has_table, int cube_s) {
-  static const bool on = [] { const char *e = getenv("DM_ATTN_X3"); return !(e && atoi(e) == 0); }();
-  if (!on || N <= 128 || N > 256 || B <= 0 || H <= 0) return false;
-  if ((long long)N * 3 * H * 64 * 2 >= (1LL << 31)) return false;
-  if (has_table && (N != 64 * cube_s || (cube_s != 3 && cube_s != 4))) return false;
-  return true;
-}
 
 void dm_attn_x3_split(const float *x, void *hi, void *lo, long long n, hipStream_t s) {
   const long long n4 = n / 4;
@@ -1002,42 +965,6 @@ void dm_attn_x3_split(const float *x, void *hi, void *lo, long long n, hipStream
   hipLaunchKernelGGL(dmx3::split2_kernel, dim3((unsigned)blocks), dim3(256), 0, s, x, reinterpret_cast<bf16_t *>(hi), reinterpret_cast<bf16_t *>(lo), n4);
 }
 
-bool dm_attn_fwd_x3(const AttnX3Params &p, hipStream_t s) {
-  if (!dm_attn_x3_shape(p.B, p.N, p.H, p.table != nullptr, p.cube_s)) return false;
-  switch ((p.N + 31) / 32) {
-    case 5: return dmx3::launch_fwd_n<5>(p, s);
-    case 6: return dmx3::launch_fwd_n<6>(p, s);
-    case 7: return dmx3::launch_fwd_n<7>(p, s);
-    case 8: return dmx3::launch_fwd_n<8>(p, s);
-    default: return false;
-  }
-}
-
-bool dm_attn_bwd_dq_x3(const AttnX3BwdParams &p, hipStream_t s) {
-  if (!dm_attn_x3_shape(p.B, p.N, p.H, p.table != nullptr, p.cube_s)) return false;
-  switch ((p.N + 31) / 32) {
-    case 5: return dmx3::launch_dq_n<5>(p, s);
-    case 6: return dmx3::launch_dq_n<6>(p, s);
-    case 7: return dmx3::launch_dq_n<7>(p, s);
-    case 8: return dmx3::launch_dq_n<8>(p, s);
-    default: return false;
-  }
-}
-
-bool dm_attn_bwd_dkv_x3(const AttnX3BwdParams &p, hipStream_t s) {
-  if (!dm_attn_x3_shape(p.B, p.N, p.H, p.table != nullptr, p.cube_s)) return false;
-  switch ((p.N + 31) / 32) {
-    case 5: return dmx3::launch_dkv_n<5>(p, s);
-    case 6: return dmx3::launch_dkv_n<6>(p, s);
-    case 7: return dmx3::launch_dkv_n<7>(p, s);
-    case 8: return dmx3::launch_dkv_n<8>(p, s);
-    default: return false;
-  }
-}
-
-// slab chunks of the dK / dV pass (first dimension of AttnX3BwdParams::slab)
-int dm_attn_x3_chunks(int B, int N, int H) {
-  int nblk, chunks, bchunk;
-  dmx3::grid(B, N, H, nblk, chunks, bchunk);
-  return chunks;
-}
+bool dm_attn_fwd_x3(const AttnFwdPlan &pl, const AttnX3Params &p, hipStream_t s) { return dmx3::launch_n<dmx3::Fwd>(pl.pass, p, s); }
+bool dm_attn_bwd_dq_x3(const AttnBwdPlan &pl, const AttnX3BwdParams &p, hipStream_t s) { return dmx3::launch_n<dmx3::Dq>(pl.dq, p, s); }
+bool dm_attn_bwd_dkv_x3(const AttnBwdPlan &pl, const AttnX3BwdParams &p, hipStream_t s) { return dmx3::launch_n<dmx3::Dkv>(pl.dkv, p, s); }
