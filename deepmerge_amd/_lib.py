@@ -65,6 +65,20 @@ class DmPairDraw(C.Structure):
                 ("epoch", C.c_int32), ("batch", C.c_int32)]
 
 
+class DmMergeFold(C.Structure):
+    _fields_ = [("ptr", C.c_void_p), ("idx", C.c_void_p), ("edges", C.c_void_p), ("root", C.c_void_p), ("pick", C.c_void_p),
+                ("rep", C.c_void_p), ("region_of", C.c_void_p),
+                ("simi", C.c_void_p), ("weights", C.c_void_p),
+                ("count", C.c_void_p), ("sum", C.c_void_p), ("sumsq", C.c_void_p), ("bbox", C.c_void_p), ("peri", C.c_void_p),
+                ("new_id", C.c_void_p), ("hist_rank", C.c_void_p), ("new_ptr", C.c_void_p), ("new_idx", C.c_void_p),
+                ("new_rep", C.c_void_p), ("new_region_of", C.c_void_p), ("n_regions", C.c_void_p),
+                ("new_count", C.c_void_p), ("new_sum", C.c_void_p), ("new_sumsq", C.c_void_p), ("new_bbox", C.c_void_p),
+                ("new_peri", C.c_void_p),
+                ("history", C.c_void_p), ("history_simi", C.c_void_p),
+                ("C", C.c_int32), ("P", C.c_int32), ("E", C.c_int32), ("S0", C.c_int32), ("bands", C.c_int32), ("round", C.c_int32),
+                ("hist_base", C.c_int32), ("hist_cap", C.c_int32)]
+
+
 class DmProfRow(C.Structure):
     _fields_ = [("name", C.c_char * 64), ("launches", C.c_int64), ("total_ms", C.c_double),
                 ("total_flops", C.c_double), ("total_bytes", C.c_double)]
@@ -136,6 +150,12 @@ SIGNATURES = {
     "dm_label_features": (_I, [_P, _P, _P, _P, _P, _I, _I, _P, _P]),
     "dm_rag_edges": (_I, [_P, _I, _I, _I, _P, _P, _I, _P, _P, _I, _P, _P, _P]),
     "dm_merge_round": (_I, [_P, _P, _I, _I, _P, _P, _I, _P]),
+    "dm_merge_best": (_I, [_P, _P, _I, _I, _F, _P, _P]),
+    "dm_merge_match": (_I, [_P, _P, _I, _I, _P, _P, _P, _P, _P]),
+    "dm_merge_fold_regions": (_I, [C.POINTER(DmMergeFold), _P]),
+    "dm_merge_edge_keys": (_I, [_P, _P, _P, _I, _I, _P, _P]),
+    "dm_merge_fold_edges": (_I, [_P, _P, _P, _I, _P, _P, _P, _P]),
+    "dm_relabel_raster": (_I, [_P, _P, _P, _L, _I, _P]),
     "dm_gru_cell_fwd": (_I, [_P, _L, _P, _P, _P, _P, _I, _I, _P]),
     "dm_gru_cell_bwd": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _P]),
     "dm_prof_enable": (_I, [_I]),

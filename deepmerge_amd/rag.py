@@ -7,7 +7,9 @@ makes the ExtractFeatures pipeline self-contained on the GPU.  Definitions: orac
 """
 from __future__ import annotations
 
-from typing import Dict, Tuple
+import ctypes
+from dataclasses import dataclass, field
+from typing import Dict, List, Optional, Tuple
 
 import torch
 
@@ -134,3 +136,208 @@ def merge_partition(ptr: torch.Tensor, idx: torch.Tensor, edges: torch.Tensor, r
     keys = torch.unique(lo * C + hi)
     new_edges = torch.stack((keys // C, keys % C), 1).to(torch.int32)
     return new_id.to(torch.int32), new_ptr.to(torch.int32), new_idx, new_edges
+
+
+# ---- mutual-best-neighbour merging (csrc/dm_merge.hip; the rule: include/deepmerge_hip.h) --------------------
+_STAT_KEYS = ("count", "sum", "sumsq", "bbox", "peri")
+
+
+@dataclass
+class MergeResult:
+    """What `merge_regions` leaves: the final partition in the form it took as input, and how it got there.
+
+    region_of int32 [S0]: final region of every original superpixel; ptr / idx / edges / weights / stats: the final partition
+    (weights / stats None when none were given); pooled [C,D], simi [E]: the scoring of the final partition; rep int32 [C]: the
+    smallest original superpixel id of each region (regions are numbered in that order); rounds: rounds applied; history int32
+    [M,3] = (round, rep of the surviving region, rep of the absorbed one) with history_simi float32 [M], in merge order;
+    regions_per_round: region count before round 1 and after every applied round (rounds + 1 entries)."""
+    region_of: torch.Tensor
+    ptr: torch.Tensor
+    idx: torch.Tensor
+    edges: torch.Tensor
+    weights: Optional[torch.Tensor]
+    stats: Optional[Dict[str, torch.Tensor]]
+    pooled: torch.Tensor
+    simi: torch.Tensor
+    rep: torch.Tensor
+    rounds: int
+    history: torch.Tensor
+    history_simi: torch.Tensor
+    regions_per_round: List[int]
+    merges_per_round: List[int] = field(default_factory=list)
+
+    def labels(self, raster: torch.Tensor) -> torch.Tensor:
+        """Merged label raster: out[y,x] = region_of[raster[y,x]] (int32 [H,W]; ids outside [0, S0) are copied through)."""
+        return relabel_raster(raster, self.region_of)
+
+    def region_of_at(self, round: int) -> torch.Tensor:
+        """int32 [S0]: the map from original superpixels to regions after the first `round` rounds, replayed from `history`
+        (region ids dense, in order of the region's smallest original id, as every round numbers them)."""
+        if not 0 <= round <= self.rounds:
+            raise ValueError(f"round must be in 0..{self.rounds}, got {round}")
+        S0 = self.region_of.numel()
+        m = sum(self.merges_per_round[:round])
+        parent = torch.arange(S0, dtype=torch.int64, device=self.region_of.device)
+        if m:
+            h = self.history[:m].long()
+            parent[h[:, 2]] = h[:, 1]                      # every region is absorbed at most once
+            for _ in range(max(1, S0.bit_length())):       # pointer doubling: a chain of absorptions is at most S0 long
+                parent = parent[parent]
+        dense = torch.cumsum((parent == torch.arange(S0, device=parent.device)).to(torch.int64), 0) - 1
+        return dense[parent].to(torch.int32)
+
+
+def relabel_raster(raster: torch.Tensor, mapping: torch.Tensor) -> torch.Tensor:
+    """out[y,x] = mapping[raster[y,x]] for an int32 raster (dm_relabel_raster); ids outside [0, len(mapping)) stay as they are."""
+    _need_cuda(raster, mapping)
+    if raster.dtype != torch.int32 or raster.dim() != 2 or mapping.dtype != torch.int32 or mapping.dim() != 1 or mapping.numel() < 1:
+        raise ValueError("raster must be int32 [H,W] and mapping int32 [S], S >= 1")
+    raster, mapping = raster.contiguous(), mapping.contiguous()
+    out = torch.empty_like(raster)
+    if raster.numel():
+        check(_lib.lib().dm_relabel_raster(raster.data_ptr(), mapping.data_ptr(), out.data_ptr(), raster.numel(), mapping.numel(),
+                                           _stream()), "dm_relabel_raster")
+    return out
+
+
+_INPUT_ERRORS = ("ptr must start at 0, be non-decreasing and end at len(idx)",
+                 "idx must index rows of features",
+                 "an edge has a negative endpoint (-1 = 'no polygon' edges cannot be relabelled: filter them with "
+                 "edges[(edges >= 0).all(1)])",
+                 "edge endpoints must be region ids with a < b",
+                 "edges must be sorted by (a, b) and unique")
+
+
+def _check_merge_inputs(features, ptr, idx, edges, S0):
+    """One device check (one readback) before round 1: an id out of range would be an out-of-bounds access on the device."""
+    dev = ptr.device
+    flags = [((ptr[1:] < ptr[:-1]).any() | (ptr[0] != 0) | (ptr[-1] != idx.numel()))]
+    flags.append(((idx < 0) | (idx >= features.shape[0])).any() if idx.numel() else torch.zeros((), dtype=torch.bool, device=dev))
+    if edges.shape[0]:
+        a, b = edges[:, 0].long(), edges[:, 1].long()
+        key = a * S0 + b
+        flags += [(edges < 0).any(), ((a >= b) | (b >= S0)).any(), (key[1:] <= key[:-1]).any()]
+    code = sum(f.to(torch.int32) << i for i, f in enumerate(flags))
+    code = int(code)
+    for i, msg in enumerate(_INPUT_ERRORS):
+        if code >> i & 1:
+            raise ValueError(f"merge_regions: {msg}")
+
+
+def merge_regions(features: torch.Tensor, ptr: torch.Tensor, idx: torch.Tensor, edges: torch.Tensor, *, margin: float = 1.0,
+                  weights: Optional[torch.Tensor] = None, stats: Optional[Dict[str, torch.Tensor]] = None,
+                  max_rounds: Optional[int] = None, min_regions: int = 0) -> MergeResult:
+    """Mutual-best-neighbour region merging on the device, from the sweep's inputs to the final partition.
+
+    features fp32 [P,D]; ptr int32 [S0+1] / idx int32 [P']: the superpixels' point lists; edges int32 [E,2], a < b, sorted by
+    (a, b), unique (as `rag_edges` returns them); weights int32 [E]: shared boundary lengths; stats: `label_stats`' dict (needs
+    weights: the inner perimeter cannot be folded without them).  Per round: score the regions as they are (segment mean +
+    edge similarity, the sweep's kernels), let every region choose its best neighbour among the edges with simi < margin
+    (smallest simi, then smallest id), merge the pairs that chose each other, and fold point lists, edges, weights, statistics.
+    Stops when a round merges nothing (then no edge has simi < margin), after `max_rounds` rounds, or before a round that would
+    leave fewer than `min_regions` regions (that round is not applied, so more regions than asked may remain).
+    The inputs are not modified.  One small readback per round; everything else stays on the device."""
+    _need_cuda(features, ptr, idx, edges, weights, *((stats or {}).get(k) for k in _STAT_KEYS))
+    if features.dtype != torch.float32 or features.dim() != 2 or features.shape[1] < 1:
+        raise ValueError("features must be float32 [P,D]")
+    if ptr.dtype != torch.int32 or ptr.dim() != 1 or ptr.numel() < 2 or idx.dtype != torch.int32 or idx.dim() != 1:
+        raise ValueError("ptr must be int32 [S+1] with S >= 1 and idx int32 [P]")
+    if edges.dtype != torch.int32 or edges.dim() != 2 or edges.shape[1] != 2:
+        raise ValueError("edges must be int32 [E,2]")
+    S0, P, E0, D = ptr.numel() - 1, idx.numel(), edges.shape[0], features.shape[1]
+    if P < 1 or features.shape[0] < 1:
+        raise ValueError("merge_regions needs at least one sample point")
+    if S0 > 1 << 24:
+        raise ValueError(f"merge_regions takes at most 2^24 regions, got {S0}")
+    if weights is not None and (weights.dtype != torch.int32 or tuple(weights.shape) != (E0,)):
+        raise ValueError("weights must be int32 [E]")
+    if max_rounds is not None and max_rounds < 0:
+        raise ValueError("max_rounds must be >= 0 or None")
+    nb = 0
+    if stats is not None:
+        if weights is None:
+            raise ValueError("stats need weights: the inner perimeter of a merged region is peri_a + peri_b - 2 weight(a, b)")
+        nb = int(stats["bands"])
+        want = {"count": (torch.int64, (S0,)), "sum": (torch.int64, (S0, nb)), "sumsq": (torch.int64, (S0, nb)),
+                "bbox": (torch.int32, (S0, 4)), "peri": (torch.int64, (S0, 2))}
+        for k, (dt, shape) in want.items():
+            if stats[k].dtype != dt or tuple(stats[k].shape) != shape:
+                raise ValueError(f"stats[{k!r}] must be {dt} {list(shape)} (as label_stats returns it)")
+        if not 1 <= nb <= 3:
+            raise ValueError("stats['bands'] must be 1..3")
+    features, ptr, idx, edges = features.contiguous(), ptr.contiguous(), idx.contiguous(), edges.contiguous()
+    _check_merge_inputs(features, ptr, idx, edges, S0)
+    dev, lib, i32 = ptr.device, _lib.lib(), torch.int32
+
+    def new_state():
+        st = {"ptr": torch.empty(S0 + 1, dtype=i32, device=dev), "idx": torch.empty(P, dtype=i32, device=dev),
+              "edges": torch.empty((E0, 2), dtype=i32, device=dev), "rep": torch.empty(S0, dtype=i32, device=dev),
+              "region_of": torch.empty(S0, dtype=i32, device=dev),
+              "weights": torch.empty(E0, dtype=i32, device=dev) if weights is not None else None}
+        if stats is not None:
+            st.update({k: torch.empty_like(stats[k]) for k in _STAT_KEYS})
+        return st
+
+    ident = torch.arange(S0, dtype=i32, device=dev)
+    cur = {"ptr": ptr, "idx": idx, "edges": edges, "rep": ident, "region_of": ident,
+           "weights": weights.contiguous() if weights is not None else None}
+    if stats is not None:
+        cur.update({k: stats[k].contiguous() for k in _STAT_KEYS})
+    spare = [new_state(), new_state()] if E0 else []
+    pooled = torch.empty((S0, D), dtype=torch.float32, device=dev)
+    simi = torch.empty(E0, dtype=torch.float32, device=dev)
+    best = torch.empty(S0, dtype=torch.int64, device=dev)
+    picked = torch.empty(E0, dtype=torch.uint8, device=dev)
+    root, pick, new_id, hist_rank = (torch.empty(S0, dtype=i32, device=dev) for _ in range(4))
+    keys = torch.empty(E0, dtype=torch.int64, device=dev)
+    meta = torch.zeros(3, dtype=i32, device=dev)                 # picked edges, new C, new E: the round's one readback
+    history = torch.empty((S0, 3), dtype=i32, device=dev)
+    history_simi = torch.empty(S0, dtype=torch.float32, device=dev)
+    ptr_of = lambda t: None if t is None else t.data_ptr()
+
+    C, E, rounds, n_hist = S0, E0, 0, 0
+    regions, merges = [S0], []
+    while True:
+        stream = _stream()
+        check(lib.dm_segment_mean(features.data_ptr(), cur["ptr"].data_ptr(), cur["idx"].data_ptr(), pooled.data_ptr(), C, D, stream),
+              "dm_segment_mean")
+        if E:
+            check(lib.dm_edge_similarity(pooled.data_ptr(), cur["edges"].data_ptr(), simi.data_ptr(), None, E, D, margin, stream),
+                  "dm_edge_similarity")
+        if E == 0 or C <= max(min_regions, 1) or (max_rounds is not None and rounds >= max_rounds):
+            break
+        nxt = spare[rounds & 1]
+        check(lib.dm_merge_best(cur["edges"].data_ptr(), simi.data_ptr(), E, C, margin, best.data_ptr(), stream), "dm_merge_best")
+        check(lib.dm_merge_match(cur["edges"].data_ptr(), best.data_ptr(), E, C, picked.data_ptr(), root.data_ptr(), pick.data_ptr(),
+                                 meta.data_ptr(), stream), "dm_merge_match")
+        f = _lib.DmMergeFold()
+        for k in ("ptr", "idx", "edges", "rep", "region_of", "weights") + (_STAT_KEYS if stats is not None else ()):
+            setattr(f, k, ptr_of(cur[k]))
+        for k in ("ptr", "idx", "rep", "region_of") + (_STAT_KEYS if stats is not None else ()):
+            setattr(f, "new_" + k, ptr_of(nxt[k]))
+        f.root, f.pick, f.simi, f.new_id, f.hist_rank = root.data_ptr(), pick.data_ptr(), simi.data_ptr(), new_id.data_ptr(), hist_rank.data_ptr()
+        f.n_regions, f.history, f.history_simi = meta[1:].data_ptr(), history.data_ptr(), history_simi.data_ptr()
+        f.C, f.P, f.E, f.S0, f.bands, f.round, f.hist_base, f.hist_cap = C, P, E, S0, nb, rounds, n_hist, S0
+        check(lib.dm_merge_fold_regions(ctypes.byref(f), stream), "dm_merge_fold_regions")
+        check(lib.dm_merge_edge_keys(cur["edges"].data_ptr(), root.data_ptr(), new_id.data_ptr(), E, C, keys.data_ptr(), stream),
+              "dm_merge_edge_keys")
+        skeys, order = torch.sort(keys[:E])                      # canonical (a, b) order of the relabelled edges
+        check(lib.dm_merge_fold_edges(skeys.data_ptr(), order.data_ptr(), ptr_of(cur["weights"]), E, nxt["edges"].data_ptr(),
+                                      ptr_of(nxt["weights"]), meta[2:].data_ptr(), stream), "dm_merge_fold_edges")
+        n_pick, C_new, E_new = meta.tolist()
+        if n_pick == 0 or C_new < min_regions:                   # nothing merged / the round would go too far: it is dropped whole
+            break
+        cur = {k: (None if v is None else v[:C_new + 1] if k == "ptr" else v[:E_new] if k in ("edges", "weights") else
+                   v if k in ("idx", "region_of") else v[:C_new]) for k, v in nxt.items()}
+        C, E, rounds, n_hist = C_new, E_new, rounds + 1, n_hist + n_pick
+        regions.append(C)
+        merges.append(n_pick)
+
+    out_stats = None
+    if stats is not None:
+        out_stats = {k: cur[k].clone() for k in _STAT_KEYS}
+        out_stats["bands"] = nb
+    return MergeResult(region_of=cur["region_of"].clone(), ptr=cur["ptr"].clone(), idx=cur["idx"].clone(), edges=cur["edges"].clone(),
+                       weights=None if weights is None else cur["weights"].clone(), stats=out_stats, pooled=pooled[:C].clone(),
+                       simi=simi[:E].clone(), rep=cur["rep"].clone(), rounds=rounds, history=history[:n_hist].clone(),
+                       history_simi=history_simi[:n_hist].clone(), regions_per_round=regions, merges_per_round=merges)

@@ -478,6 +478,60 @@ int dm_rag_edges(const int32_t *labels, int32_t H, int32_t W, int32_t S, int64_t
 int dm_merge_round(const int32_t *edges, const uint8_t *merge, int32_t E, int32_t S, int32_t *parent, int32_t *changed,
                    int32_t init, void *stream);
 
+/* ---- mutual-best-neighbour region merging (additive in ABI 6; csrc/dm_merge.hip, DESIGN.md 3.5, rag.merge_regions) -------
+ * The rule.  State of a round: C regions with dense ids 0..C-1, point lists ptr int32 [C+1] / idx int32 [P], edges int32 [E,2]
+ * with a < b, sorted by (a, b), unique, weights int32 [E] (shared boundary length), statistics as dm_label_stats writes them,
+ * rep int32 [C] = the smallest ORIGINAL superpixel id inside each region.
+ *   1. score: pooled = dm_segment_mean, simi = dm_edge_similarity (unchanged).
+ *   2. best neighbour: an edge is a candidate iff simi < margin (float compare; NaN is none).  best[r] = the smallest key
+ *      (bits(simi) << 32) | other_id over the candidate edges at r, as an unsigned 64-bit integer (simi >= +0, so the bit pattern
+ *      orders like the value; ties go to the smaller neighbour id); all-ones = no candidate.
+ *   3. match: edge (a, b) is picked iff best[a] names b and best[b] names a.  Picked edges form a matching (two picked edges
+ *      sharing r would give best[r] two values); b is absorbed into a.
+ *   4. fold: new dense ids in order of the surviving region's old id; new point list = points of a, then points of b, each in
+ *      their old order; edges relabelled, self edges dropped, duplicates folded with their weights ADDED, sorted by (a, b);
+ *      count / sum / sumsq added, bbox min / max, peri[:,1] added, peri[:,0]' = peri_a + peri_b - 2 weight(a, b); rep' = rep[a].
+ *   5. history: one row per picked edge, in edge order within the round: (round, rep[a], rep[b]) int32 and simi float32.
+ * All results are integers or floats copied bit for bit; every reduction is an integer min / add (order-independent).
+ * Every entry point validates before any launch, launches on `stream`, never synchronises and never allocates.
+ *
+ * dm_merge_best: best uint64 [C] (cleared by the call), one pass over the E >= 1 edges.  1 <= C <= 2^24.
+ * dm_merge_match: picked uint8 [E]; root int32 [C] (root[b] = a for a picked edge, else the identity); pick int32 [C] = index of
+ *   the picked edge at its surviving region a, else -1; n_picked[0] = number of picked edges.  All (re)initialised by the call.
+ * dm_merge_fold_regions: step 4 for regions and step 5 (see DmMergeFold).  dm_merge_edge_keys + dm_merge_fold_edges: step 4 for
+ *   edges, around a sort of the keys that the caller provides (any stable or unstable ascending sort of int64):
+ *   keys[e] = (min(na, nb) << 32) | max(na, nb) for na = new_id[root[a]] != nb, INT64_MAX for a self edge;
+ *   dm_merge_fold_edges(sorted keys, order = source index of every sorted key, weights or NULL) -> new_edges [n,2], new_weights [n],
+ *   n_edges[0] = n.  One looping workgroup does the scan of either fold (DESIGN.md 3.5 states what that costs).
+ * dm_relabel_raster: out[i] = map[labels[i]] for n int32 pixels, ids outside [0, S) copied through; 16-byte accesses when both
+ *   rasters are 16-byte aligned, a scalar kernel for the tail or for unaligned rasters.  out may not alias labels partially. */
+typedef struct {
+  /* the round's state (read only) */
+  const int32_t *ptr, *idx, *edges, *root, *pick, *rep, *region_of;   /* region_of int32 [S0]: current region of every original id */
+  const float *simi;                                                  /* [E], this round's scores */
+  const int32_t *weights;                                             /* [E]; needed only with statistics */
+  const int64_t *count, *sum, *sumsq;                                 /* statistics: all five or count == NULL (none) */
+  const int32_t *bbox;
+  const int64_t *peri;
+  /* results; new_id [C] is written for surviving regions only (an absorbed region's id is new_id[root[r]]), hist_rank [C] scratch */
+  int32_t *new_id, *hist_rank, *new_ptr, *new_idx, *new_rep, *new_region_of, *n_regions;
+  int64_t *new_count, *new_sum, *new_sumsq;
+  int32_t *new_bbox;
+  int64_t *new_peri;
+  int32_t *history;                                                   /* int32 [hist_cap, 3]; rows hist_base .. are this round's */
+  float *history_simi;                                                /* float32 [hist_cap] */
+  int32_t C, P, E, S0, bands, round, hist_base, hist_cap;
+} DmMergeFold;
+int dm_merge_best(const int32_t *edges, const float *simi, int32_t E, int32_t C, float margin, uint64_t *best, void *stream);
+int dm_merge_match(const int32_t *edges, const uint64_t *best, int32_t E, int32_t C, uint8_t *picked, int32_t *root, int32_t *pick,
+                   int32_t *n_picked, void *stream);
+int dm_merge_fold_regions(const DmMergeFold *args, void *stream);
+int dm_merge_edge_keys(const int32_t *edges, const int32_t *root, const int32_t *new_id, int32_t E, int32_t C, int64_t *keys,
+                       void *stream);
+int dm_merge_fold_edges(const int64_t *sorted_keys, const int64_t *order, const int32_t *weights, int32_t E, int32_t *new_edges,
+                        int32_t *new_weights, int32_t *n_edges, void *stream);
+int dm_relabel_raster(const int32_t *labels, const int32_t *map, int32_t *out, int64_t n, int32_t S, void *stream);
+
 /* BatchNorm2d (+ ReLU, + Dropout2d mask) of the auxiliary heads (reference nets/ShfitScaleFormer.py:329-368: Conv2d ->
  * BatchNorm2d -> ReLU -> Dropout2d(0.3)) on the channels-last matrix the convolution GEMM produces: x, y fp32 [M, C] with
  * M = samples * rows_per_sample.  training != 0: batch statistics (biased variance, eps inside the sqrt), running_mean /
