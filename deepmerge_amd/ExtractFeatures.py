@@ -84,6 +84,23 @@ class FeatureIO:
         return self._extract_local(tile, points_xy, inner, obj, region_features, batch_size)
 
     @torch.no_grad()
+    def merge_tile(self, tile: torch.Tensor, labels: torch.Tensor, n_labels: int, k: int = 3, margin: float = 1.0, batch_size: int = 2000,
+                   **merge_kwargs):
+        """From an image tile (uint8 [bands, H, W]) and its segmentation (labels int32 [H, W], ids 0..n_labels-1) to the merged
+        partition: label_stats -> designed_features -> rag_edges -> sample_points -> extract_features_from_tile ->
+        merge_regions(weights=, stats=), nothing else.  Returns (MergeResult, PointSamples); `result.labels(labels)` is the merged
+        raster.  `merge_kwargs` go to merge_regions (max_rounds, min_regions).  Under a process group the encode is sharded by
+        extract_features_from_tile and the graph stages run replicated."""
+        from . import rag
+        stats = rag.label_stats(labels, tile, n_labels)
+        designed = rag.designed_features(stats)
+        edges, weights = rag.rag_edges(labels, n_labels)
+        pts = rag.sample_points(labels, n_labels, k=k)
+        features = self.extract_features_from_tile(tile, pts.xy, pts.inner, pts.obj, pts.region_features(designed), batch_size=batch_size)
+        result = rag.merge_regions(features, pts.ptr, pts.idx, edges, margin=margin, weights=weights, stats=stats, **merge_kwargs)
+        return result, pts
+
+    @torch.no_grad()
     def _extract_local(self, tile, points_xy, inner, obj, region_features, batch_size):
         from .patches import point_batch_cols
         P = points_xy.shape[0]

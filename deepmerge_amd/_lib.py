@@ -156,6 +156,9 @@ SIGNATURES = {
     "dm_merge_edge_keys": (_I, [_P, _P, _P, _I, _I, _P, _P]),
     "dm_merge_fold_edges": (_I, [_P, _P, _P, _I, _P, _P, _P, _P]),
     "dm_relabel_raster": (_I, [_P, _P, _P, _L, _I, _P]),
+    "dm_label_clearance": (_I, [_P, _I, _I, _I, _P, _P, _P, _P]),
+    "dm_point_select_round": (_I, [_P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P]),
+    "dm_point_emit": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P]),
     "dm_gru_cell_fwd": (_I, [_P, _L, _P, _P, _P, _P, _I, _I, _P]),
     "dm_gru_cell_bwd": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _P]),
     "dm_prof_enable": (_I, [_I]),

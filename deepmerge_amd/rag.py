@@ -4,6 +4,8 @@ The reference consumes a RAG edge list and 15 per-superpixel attributes that ext
 shapefiles (`lines.shp` LEFT_FID / RIGHT_FID, MyUtils2.py:155-193; attribute order MyUtils1.py:79-114).  This module
 derives both from the segmentation's label raster and the image tile with three HIP kernels (csrc/dm_rag.hip), which
 makes the ExtractFeatures pipeline self-contained on the GPU.  Definitions: oracle/rag.py (the build's own spec).
+The sample points, their `inner` / `object` window fields and point lists, which the reference reads from a point shapefile,
+come from the label raster as well (csrc/dm_points.hip: `clearance`, `sample_points`; spec tests/points_ref.py).
 """
 from __future__ import annotations
 
@@ -341,3 +343,96 @@ def merge_regions(features: torch.Tensor, ptr: torch.Tensor, idx: torch.Tensor, 
                        weights=None if weights is None else cur["weights"].clone(), stats=out_stats, pooled=pooled[:C].clone(),
                        simi=simi[:E].clone(), rep=cur["rep"].clone(), rounds=rounds, history=history[:n_hist].clone(),
                        history_simi=history_simi[:n_hist].clone(), regions_per_round=regions, merges_per_round=merges)
+
+
+# ---- sample points and window sides from the label raster (csrc/dm_points.hip; the rule: include/deepmerge_hip.h) ----
+MAX_WINDOW = 384          # dataset.MAX_WINDOW: the gather's LDS staging limit
+MAX_POINTS = 16           # points per superpixel (csrc/dm_points.hip KMAX)
+
+
+@dataclass
+class PointSamples:
+    """What `sample_points` leaves: one row per sample point, sorted by (superpixel, round).
+
+    xy int32 [P,2] = (x, y) pixel position; label int32 [P]: the point's superpixel; inner / obj int32 [P]: the window fields the
+    crop consumes (inner = 2 clearance - 1, obj = min(longer bounding-box side, (max_window + 2 inner) // 3)); ptr int32 [S+1] /
+    idx int32 [P] = arange(P): the superpixels' point lists in the form the sweep and `merge_regions` take; bbox int32 [S,4] =
+    xmin, ymin, xmax, ymax as `label_stats` writes it; round int32 [P]: the selection round that chose the point (0 = the pixel
+    farthest from the superpixel's boundary)."""
+    xy: torch.Tensor
+    label: torch.Tensor
+    inner: torch.Tensor
+    obj: torch.Tensor
+    ptr: torch.Tensor
+    idx: torch.Tensor
+    bbox: torch.Tensor
+    round: torch.Tensor
+
+    def region_features(self, designed: torch.Tensor) -> torch.Tensor:
+        """[P,15]: every point's row of `designed_features` (designed[label]), as the encoder takes them."""
+        if designed.dim() != 2 or designed.shape[0] != self.bbox.shape[0]:
+            raise ValueError(f"designed must be [S,15] with S = {self.bbox.shape[0]} rows (as designed_features returns it)")
+        return designed[self.label.long()]
+
+
+def _check_raster(labels: torch.Tensor, max_window: int, what: str):
+    _need_cuda(labels)
+    if labels.dtype != torch.int32 or labels.dim() != 2 or labels.numel() < 1:
+        raise ValueError("labels must be int32 [H,W] with at least one pixel")
+    if labels.numel() >= 1 << 31:
+        raise ValueError(f"{what} takes rasters of fewer than 2^31 pixels, got {labels.numel()}")
+    if not 1 <= int(max_window) <= MAX_WINDOW:
+        raise ValueError(f"max_window must be in 1..{MAX_WINDOW}, got {max_window}")
+
+
+def clearance(labels: torch.Tensor, max_window: int = MAX_WINDOW) -> torch.Tensor:
+    """uint16 [H,W]: Chebyshev distance from every pixel to the nearest pixel of another label or outside the raster, capped at
+    (max_window + 1) // 2.  The largest odd square centred on the pixel inside its superpixel has side 2 c - 1."""
+    _check_raster(labels, max_window, "clearance")
+    labels = labels.contiguous()
+    H, W = labels.shape
+    dev = labels.device
+    bits = torch.empty(H * ((W + 63) // 64), dtype=torch.int64, device=dev)
+    row_dist = torch.empty((H, W), dtype=torch.uint8, device=dev)
+    out = torch.empty((H, W), dtype=torch.uint16, device=dev)
+    check(_lib.lib().dm_label_clearance(labels.data_ptr(), H, W, int(max_window), bits.data_ptr(), row_dist.data_ptr(), out.data_ptr(),
+                                        _stream()), "dm_label_clearance")
+    return out
+
+
+def sample_points(labels: torch.Tensor, n_labels: int, k: int = 3, max_window: int = MAX_WINDOW) -> PointSamples:
+    """Sample points and their window fields from the label raster alone (what the reference reads from a point shapefile).
+
+    Every superpixel gets min(k, area) points: the pixel farthest from its boundary first, then pixels that trade clearance
+    against distance to the points already chosen (the rule: include/deepmerge_hip.h).  `inner` is the largest odd square around
+    the point inside the superpixel, `obj` the superpixel's longer bounding-box side, clamped so that the largest window the crop
+    derives (3 obj - 2 inner) stays within max_window.  Ids outside [0, n_labels) get no points.  The input is not modified.
+    One readback (the number of points); everything else stays on the device."""
+    _check_raster(labels, max_window, "sample_points")
+    if n_labels < 1:
+        raise ValueError(f"n_labels must be >= 1, got {n_labels}")
+    if not 1 <= int(k) <= MAX_POINTS:
+        raise ValueError(f"k must be in 1..{MAX_POINTS}, got {k}")
+    if n_labels * int(k) >= 1 << 31:
+        raise ValueError(f"n_labels * k must be below 2^31, got {n_labels * int(k)}")
+    labels = labels.contiguous()
+    H, W = labels.shape
+    S, k, dev, lib, i32 = int(n_labels), int(k), labels.device, _lib.lib(), torch.int32
+    clr = clearance(labels, max_window)
+    best = torch.empty(S, dtype=torch.int64, device=dev)
+    pts = torch.empty((S, k, 2), dtype=i32, device=dev)
+    pclr = torch.empty((S, k), dtype=i32, device=dev)
+    cnt = torch.empty(S, dtype=i32, device=dev)
+    bbox = torch.empty((S, 4), dtype=i32, device=dev)
+    for j in range(k):
+        check(lib.dm_point_select_round(labels.data_ptr(), clr.data_ptr(), H, W, S, k, j, best.data_ptr(), pts.data_ptr(), pclr.data_ptr(),
+                                        cnt.data_ptr(), bbox.data_ptr(), _stream()), "dm_point_select_round")
+    cap = S * k
+    ptr = torch.empty(S + 1, dtype=i32, device=dev)
+    xy = torch.empty((cap, 2), dtype=i32, device=dev)
+    label, inner, obj, rnd = (torch.empty(cap, dtype=i32, device=dev) for _ in range(4))
+    check(lib.dm_point_emit(cnt.data_ptr(), pts.data_ptr(), pclr.data_ptr(), bbox.data_ptr(), S, k, int(max_window), cap, ptr.data_ptr(),
+                            xy.data_ptr(), label.data_ptr(), inner.data_ptr(), obj.data_ptr(), rnd.data_ptr(), _stream()), "dm_point_emit")
+    P = int(ptr[S])                                            # the one readback: sizes the views below
+    return PointSamples(xy=xy[:P], label=label[:P], inner=inner[:P], obj=obj[:P], ptr=ptr, idx=torch.arange(P, dtype=i32, device=dev),
+                        bbox=bbox, round=rnd[:P])

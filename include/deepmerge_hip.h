@@ -532,6 +532,42 @@ int dm_merge_fold_edges(const int64_t *sorted_keys, const int64_t *order, const 
                         int32_t *new_weights, int32_t *n_edges, void *stream);
 int dm_relabel_raster(const int32_t *labels, const int32_t *map, int32_t *out, int64_t n, int32_t S, void *stream);
 
+/* ---- sample points and window sides from a label raster (additive in ABI 6; csrc/dm_points.hip, DESIGN.md 3.5.2,
+ * rag.clearance / rag.sample_points) ------------------------------------------------------------------------------------------
+ * Replaces, on the device, the point shapefile the reference reads (pixel position and the `inner` / `object` window fields,
+ * MyUtils1.py:64-66, MyUtils2.py:234-236, and the polygons' `PointID` lists).  The reference never defines these; the rule is
+ * this build's (restated in numpy in tests/points_ref.py).  All arithmetic is on integers; results are bit-exact.
+ * The rule.  labels int32 [H,W], H*W < 2^31, S superpixel ids 0..S-1, 1 <= k <= 16, 1 <= max_window <= 384.  Ids outside
+ * [0,S) are never sampled but are "another label" to their neighbours (raw ids are compared).
+ *   clearance: c(p) = Chebyshev distance from pixel p to the nearest pixel that carries a different id or lies outside the
+ *     raster, capped at cap = (max_window + 1) / 2.  c >= 1; the largest odd square centred on p inside p's superpixel has
+ *     side 2c - 1 (up to the cap).
+ *   points: superpixel s gets min(k, area(s)) points in rounds j = 0..k-1.  Round j takes the pixel of s with the largest
+ *     score_j(p) = min(c(p), Chebyshev distance from p to every point already chosen for s); ties go to the smallest linear
+ *     index y*W + x; a round yields a point only if its best score is >= 1 (chosen pixels score 0).  As a 64-bit key
+ *     (score << 32) | (0xFFFFFFFF - linear) a round is one unsigned integer max per superpixel.
+ *   windows: inner = 2 c(p) - 1; side = max(bbox width, bbox height) of s; obj = min(side, (max_window + 2 inner) / 3).
+ *     Hence inner <= obj and 3 obj - 2 inner (the largest of the four window sides get_scales derives) <= max_window.
+ *   order: points sorted by (superpixel, round); ptr int32 [S+1] = exclusive scan of the per-superpixel counts.
+ * Every entry point validates before any launch, launches on `stream`, never synchronises and never allocates.
+ *
+ * dm_label_clearance: the clearance rule.  clearance uint16 [H,W]; scratch: bits uint64 [H * ceil(W/64)] (one bit per pixel:
+ *   has an 8-neighbour of another id or is on the raster edge), row_dist uint8 [H,W] (distance to the nearest such pixel of
+ *   the row, capped at cap - 1).
+ * dm_point_select_round: round `round` (0..k-1, to be called in that order) of the points rule over the whole raster.
+ *   State: best uint64 [S], points int32 [S,k,2] = (x, y), point_clearance int32 [S,k] = c at the point, counts int32 [S],
+ *   bbox int32 [S,4] = xmin,ymin,xmax,ymax (INT_MAX,INT_MAX,-1,-1 for an id that never occurs, as dm_label_stats writes it).
+ *   Round 0 (re)initialises best, counts and bbox and computes bbox; every round appends at most one point per superpixel.
+ * dm_point_emit: the windows and order rules.  ptr int32 [S+1]; xy int32 [capacity,2], label / inner / obj / round int32
+ *   [capacity]: rows 0 .. ptr[S]-1 are written (capacity >= ptr[S]; S*k always suffices), round = the point's round j. */
+int dm_label_clearance(const int32_t *labels, int32_t H, int32_t W, int32_t max_window, uint64_t *bits, uint8_t *row_dist,
+                       uint16_t *clearance, void *stream);
+int dm_point_select_round(const int32_t *labels, const uint16_t *clearance, int32_t H, int32_t W, int32_t S, int32_t k, int32_t round,
+                          uint64_t *best, int32_t *points, int32_t *point_clearance, int32_t *counts, int32_t *bbox, void *stream);
+int dm_point_emit(const int32_t *counts, const int32_t *points, const int32_t *point_clearance, const int32_t *bbox, int32_t S, int32_t k,
+                  int32_t max_window, int32_t capacity, int32_t *ptr, int32_t *xy, int32_t *label, int32_t *inner, int32_t *obj,
+                  int32_t *round, void *stream);
+
 /* BatchNorm2d (+ ReLU, + Dropout2d mask) of the auxiliary heads (reference nets/ShfitScaleFormer.py:329-368: Conv2d ->
  * BatchNorm2d -> ReLU -> Dropout2d(0.3)) on the channels-last matrix the convolution GEMM produces: x, y fp32 [M, C] with
  * M = samples * rows_per_sample.  training != 0: batch statistics (biased variance, eps inside the sqrt), running_mean /
