@@ -11,11 +11,11 @@
 #include <climits>
 
 #include "dm_common.h"
+#include "dm_table.h"
 
 namespace {
 
 constexpr int STRIP = 16;
-constexpr long long EMPTY_KEY = -1;
 constexpr int TSLOTS_LOG2 = 6, TSLOTS = 1 << TSLOTS_LOG2;      // labels per 64x64 tile kept in LDS (more: global atomics)
 constexpr int ESLOTS_LOG2 = 7, ESLOTS = 1 << ESLOTS_LOG2;      // label pairs per tile kept in LDS
 
@@ -202,33 +202,7 @@ __global__ void label_features_kernel(const long long *__restrict__ count, const
 }
 
 // ---- adjacency: open-addressing table keyed by a * S + b (a < b), value = number of shared pixel edges --------------------
-__device__ __forceinline__ unsigned long long mix64(unsigned long long k) {
-  k ^= k >> 33; k *= 0xff51afd7ed558ccdULL; k ^= k >> 33; k *= 0xc4ceb9fe1a85ec53ULL; k ^= k >> 33;
-  return k;
-}
-__device__ __forceinline__ void table_add(long long *keys, int *cnt, unsigned mask, long long key, int c, int *overflow) {
-  unsigned slot = (unsigned)mix64((unsigned long long)key) & mask;
-  for (unsigned probe = 0; probe <= mask; ++probe) {
-    const long long seen = (long long)atomicCAS(reinterpret_cast<unsigned long long *>(keys + slot), (unsigned long long)EMPTY_KEY,
-                                                (unsigned long long)key);
-    if (seen == EMPTY_KEY || seen == key) {
-      atomicAdd(cnt + slot, c);
-      return;
-    }
-    slot = (slot + 1) & mask;
-    if (probe > 4096) break;
-  }
-  atomicExch(overflow, 1);
-}
-
-__global__ void table_clear_kernel(long long *keys, int *cnt, long long n, int *overflow, int *n_out) {
-  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
-    keys[i] = EMPTY_KEY;
-    cnt[i] = 0;
-  }
-  if (blockIdx.x == 0 && threadIdx.x == 0) { *overflow = 0; *n_out = 0; }
-}
-
+// (the table itself: dm_table.h)
 template <bool VEC>
 __global__ __launch_bounds__(256) void rag_edges_kernel(const int *__restrict__ labels, int H, int W, int S, long long *__restrict__ keys,
                                                         int *__restrict__ cnt, unsigned mask, int *__restrict__ overflow) {
@@ -293,21 +267,6 @@ __global__ __launch_bounds__(256) void rag_edges_kernel(const int *__restrict__ 
   __syncthreads();
   for (int i = threadIdx.x; i < ESLOTS; i += blockDim.x)
     if (e_key[i] != EMPTY_KEY) table_add(keys, cnt, mask, e_key[i], e_cnt[i], overflow);
-}
-
-__global__ void table_compact_kernel(const long long *__restrict__ keys, const int *__restrict__ cnt, long long n,
-                                     long long *__restrict__ out_keys, int *__restrict__ out_cnt, int *__restrict__ n_out, int max_out) {
-  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
-    const long long k = keys[i];
-    if (k == EMPTY_KEY) continue;
-    const int pos = atomicAdd(n_out, 1);
-    if (pos < max_out) { out_keys[pos] = k; out_cnt[pos] = cnt[i]; }
-  }
-}
-
-inline int grid_for(long long items, int cap = 8192) {
-  long long g = (items + 255) / 256;
-  return (int)(g < 1 ? 1 : (g > cap ? cap : g));
 }
 
 }  // namespace

@@ -18,7 +18,7 @@ from typing import Dict, List, Sequence
 import numpy as np
 import torch
 
-from . import ops
+from . import ops, rag
 from .feed import PairTable
 from .patches import geo_to_pixel
 
@@ -165,6 +165,19 @@ def build_host(images: Sequence[Dict], n_scales: int = 3) -> HostPairs:
                      max_windows=[int(m) for m in max_windows])
 
 
+def holdout_hash(seed: int, image: int, a, b) -> np.ndarray:
+    """uint64 hash of (seed, image, a, b) per pair (a, b int arrays): the key of from_rasters' train / validation split.  Fixed
+    integer arithmetic (the 64-bit finaliser of MurmurHash3 over the packed fields), the same on every machine."""
+    m = (1 << 64) - 1
+    base = ((int(seed) * 0x9E3779B97F4A7C15) ^ ((int(image) + 1) * 0xC2B2AE3D27D4EB4F)) & m
+    k = np.uint64(base) ^ ((np.asarray(a).astype(np.uint64) << np.uint64(32)) | (np.asarray(b).astype(np.uint64) & np.uint64(0xFFFFFFFF)))
+    with np.errstate(over="ignore"):
+        k ^= k >> np.uint64(33); k *= np.uint64(0xff51afd7ed558ccd)
+        k ^= k >> np.uint64(33); k *= np.uint64(0xc4ceb9fe1a85ec53)
+        k ^= k >> np.uint64(33)
+    return k
+
+
 class EpochTable:
     """One epoch's sample table on the device, in the per-step blocked layout: `len()` steps, step s is a feed.PairTable of
     b_s = min(batch, N - s batch) pairs made of views (rows [2 s batch, 2 s batch + 2 b_s), flags [s batch, s batch + b_s))."""
@@ -221,6 +234,49 @@ class PairDataset:
         seed: the key of the per-epoch draw -- a resumed run that uses the same seed sees the same epochs.
         n_scales: how many of the four window sides are checked against the gather's 1..384 (the model's scale count)."""
         return cls(build_host(images, n_scales), seed=seed, device=device)
+
+    @classmethod
+    def from_rasters(cls, images: Sequence[Dict], k: int = 3, min_purity: float = 0.6, n_scales: int = 3, max_window: int = MAX_WINDOW,
+                     holdout: float = 0.0, seed: int = 0, device="cuda:0"):
+        """A dataset from tiles, their over-segmentations and ground-truth maps alone -- no pair lists, no shapefiles.
+        images: one dict per training image:
+          tile            uint8 [bands, H, W]
+          labels, n_labels   int32 [H, W] superpixel ids 0..n_labels-1 (others ignored)
+          truth, n_truth     int32 [H, W] object ids 0..n_truth-1 (any other value: unlabelled)
+        (arrays or tensors).  Per image, on the device: rag.label_stats -> designed_features -> rag_edges -> sample_points(k,
+        max_window) -> label_overlap -> pair_flags(min_purity); the points become xy / inner / obj / polygon_points, the designed
+        attributes `region`, the edges flagged 1 / 0 `positive` / `negative` (ambiguous edges are no training pairs), and
+        `build_host` takes it from there.  holdout in [0, 1): 0 returns one dataset; otherwise (train, val), where a pair of image t
+        goes to val iff holdout_hash(seed, t, a, b) % 10^6 < round(holdout * 10^6) -- disjoint, reproducible, the form
+        train(val_dataset=) takes.  Raises ValueError naming the image that yields no unambiguous pair."""
+        if not 0.0 <= float(holdout) < 1.0:
+            raise ValueError(f"holdout must be in [0, 1), got {holdout}")
+        dev = torch.device(device)
+        cut = int(round(float(holdout) * 1000000))
+        up = lambda a: (a if isinstance(a, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(a))).to(dev)
+        train, val = [], []
+        with torch.cuda.device(dev):
+            for t, im in enumerate(images):
+                tile, labels, truth, S = up(im["tile"]), up(im["labels"]), up(im["truth"]), int(im["n_labels"])
+                designed = rag.designed_features(rag.label_stats(labels, tile, S))
+                edges, _ = rag.rag_edges(labels, S)
+                pts = rag.sample_points(labels, S, k=k, max_window=max_window)
+                flags = rag.pair_flags(edges, rag.label_overlap(labels, truth, S, int(im["n_truth"])), min_purity).cpu().numpy()
+                edges = edges.cpu().numpy()
+                if not (flags >= 0).any():
+                    raise ValueError(f"image {t}: no unambiguous pair among {len(edges)} edges at min_purity = {min_purity} "
+                                     f"(does the truth raster overlap the labels?)")
+                ptr = pts.ptr.cpu().numpy()
+                base = {"tile": np.asarray(im["tile"].cpu() if isinstance(im["tile"], torch.Tensor) else im["tile"]),
+                        "xy": pts.xy.cpu().numpy(), "inner": pts.inner.cpu().numpy(), "obj": pts.obj.cpu().numpy(),
+                        "region": pts.region_features(designed).cpu().numpy(),
+                        "polygon_points": [np.arange(ptr[s], ptr[s + 1]) for s in range(S)]}
+                to_val = holdout_hash(seed, t, edges[:, 0], edges[:, 1]) % np.uint64(1000000) < np.uint64(cut)
+                for part, lst in ((~to_val, train), (to_val, val)):
+                    lst.append(dict(base, positive=edges[part & (flags == 1)], negative=edges[part & (flags == 0)]))
+        if float(holdout) == 0.0:
+            return cls(build_host(train, n_scales), seed=seed, device=device)
+        return cls(build_host(train, n_scales), seed=seed, device=device), cls(build_host(val, n_scales), seed=seed, device=device)
 
     def __len__(self):
         return len(self.host.pairs)

@@ -6,6 +6,8 @@ derives both from the segmentation's label raster and the image tile with three 
 makes the ExtractFeatures pipeline self-contained on the GPU.  Definitions: oracle/rag.py (the build's own spec).
 The sample points, their `inner` / `object` window fields and point lists, which the reference reads from a point shapefile,
 come from the label raster as well (csrc/dm_points.hip: `clearance`, `sample_points`; spec tests/points_ref.py).
+Against a ground-truth raster, `label_overlap` counts the overlap table once; `pair_flags` labels the RAG edges for training and
+`Overlap.coarsen(...).scores()` scores any merged partition (csrc/dm_truth.hip; spec tests/truth_ref.py).
 """
 from __future__ import annotations
 
@@ -187,6 +189,11 @@ class MergeResult:
                 parent = parent[parent]
         dense = torch.cumsum((parent == torch.arange(S0, device=parent.device)).to(torch.int64), 0) - 1
         return dense[parent].to(torch.int32)
+
+    def scores(self, overlap: "Overlap", round: Optional[int] = None) -> "PartitionScores":
+        """The partition scored against a ground-truth map: `overlap` = label_overlap(superpixel raster, truth, S0, G), coarsened by
+        the final map (round None) or the map after `round` rounds.  No pass over the raster."""
+        return overlap.coarsen(self.region_of if round is None else self.region_of_at(round)).scores()
 
 
 def relabel_raster(raster: torch.Tensor, mapping: torch.Tensor) -> torch.Tensor:
@@ -436,3 +443,156 @@ def sample_points(labels: torch.Tensor, n_labels: int, k: int = 3, max_window: i
     P = int(ptr[S])                                            # the one readback: sizes the views below
     return PointSamples(xy=xy[:P], label=label[:P], inner=inner[:P], obj=obj[:P], ptr=ptr, idx=torch.arange(P, dtype=i32, device=dev),
                         bbox=bbox, round=rnd[:P])
+
+
+# ---- overlap with a ground-truth raster: pair labels and partition scores (csrc/dm_truth.hip; the rule: include/deepmerge_hip.h,
+# DESIGN.md 3.5.3) ----
+@dataclass
+class PartitionScores:
+    """A partition scored against a ground-truth map, over the pixels that carry both a region id and an object id.
+
+    The eight exact integers of the summary: n pixels, sum_cells / sum_regions / sum_objects = the sums of squared cell, region and
+    object pixel counts, sum_owner = sum over regions of the pixels of their best object, sum_cover = sum over objects of the pixels
+    of their best region, n_regions / n_objects = how many are non-empty.  Derived: asa = sum_owner / n (achievable segmentation
+    accuracy; 1 - asa is the under-segmentation), coverage = sum_cover / n (1 - coverage is the over-segmentation), rand and
+    adjusted_rand from the pair counts sum C(x, 2) = (sum x^2 - n) / 2.  NaN where a figure has no pixels (or, Rand, no pair) to
+    speak of."""
+    n: int
+    sum_cells: int
+    sum_regions: int
+    sum_objects: int
+    sum_owner: int
+    sum_cover: int
+    n_regions: int
+    n_objects: int
+    asa: float
+    coverage: float
+    rand: float
+    adjusted_rand: float
+
+
+def partition_scores(summary) -> PartitionScores:
+    """PartitionScores from the eight summary integers (Python integer arithmetic until the final divisions)."""
+    n, sq, rows, cols, oc, cv, n_regions, n_objects = (int(v) for v in summary)
+    nan = float("nan")
+    rand = ari = nan
+    if n >= 2:
+        total = n * (n - 1) // 2                                  # pixel pairs
+        both, same_region, same_object = (sq - n) // 2, (rows - n) // 2, (cols - n) // 2
+        rand = (total + 2 * both - same_region - same_object) / total
+        num = 2 * (both * total - same_region * same_object)
+        den = (same_region + same_object) * total - 2 * same_region * same_object
+        ari = num / den if den else 1.0                           # den == 0: both partitions are one block, or both all singletons
+    return PartitionScores(n, sq, rows, cols, oc, cv, n_regions, n_objects, oc / n if n else nan, cv / n if n else nan, rand, ari)
+
+
+def _overlap_facts(keys: torch.Tensor, counts: torch.Tensor, S: int, G: int) -> "Overlap":
+    """dm_overlap_reduce over sorted unique keys int64 [K] with counts int32 [K]."""
+    dev, K = keys.device, keys.numel()
+    keys, counts = keys.contiguous(), counts.contiguous()
+    i32, i64 = torch.int32, torch.int64
+    best, rows, area = (torch.empty(S, dtype=i64, device=dev) for _ in range(3))
+    owner, owner_count = torch.empty(S, dtype=i32, device=dev), torch.empty(S, dtype=i32, device=dev)
+    size, cover = torch.empty(G, dtype=i64, device=dev), torch.empty(G, dtype=i32, device=dev)
+    summary = torch.empty(8, dtype=i64, device=dev)
+    check(_lib.lib().dm_overlap_reduce(keys.data_ptr() if K else None, counts.data_ptr() if K else None, K, S, G, best.data_ptr(),
+                                       rows.data_ptr(), area.data_ptr(), owner.data_ptr(), owner_count.data_ptr(), size.data_ptr(),
+                                       cover.data_ptr(), summary.data_ptr(), _stream()), "dm_overlap_reduce")
+    cells = torch.stack((keys // (G + 1), keys % (G + 1)), 1).to(i32)
+    return Overlap(cells=cells, count=counts, area=area, owner=owner, owner_count=owner_count, size=size, cover=cover, summary=summary,
+                   n_labels=S, n_truth=G)
+
+
+@dataclass
+class Overlap:
+    """What `label_overlap` leaves: the sparse overlap table of a label raster with a ground-truth raster and the facts read off it.
+
+    cells int32 [K,2] = (s, g) sorted by (s, g), g == n_truth is the "unlabelled" column; count int32 [K] > 0: pixels in the cell;
+    area int64 [S]: pixels of every region (all columns); owner int32 [S]: the object holding most of the region's labelled pixels
+    (ties to the smaller id, -1: none), owner_count int32 [S]: how many; size int64 [G]: labelled pixels of every object inside
+    regions 0..S-1, cover int32 [G]: the most any single region holds of it; summary int64 [8]: see PartitionScores."""
+    cells: torch.Tensor
+    count: torch.Tensor
+    area: torch.Tensor
+    owner: torch.Tensor
+    owner_count: torch.Tensor
+    size: torch.Tensor
+    cover: torch.Tensor
+    summary: torch.Tensor
+    n_labels: int
+    n_truth: int
+
+    def coarsen(self, mapping: torch.Tensor) -> "Overlap":
+        """The Overlap of the partition mapping[labels] without rescanning the raster.  mapping int32 [n_labels] -> regions
+        0..C-1 (C = max + 1): the `region_of` of a MergeResult, or `region_of_at(r)`.  Rows are relabelled, equal cells folded
+        (counts added), the facts recomputed by dm_overlap_reduce.  One readback (C)."""
+        _need_cuda(mapping, self.cells)
+        if mapping.dtype != torch.int32 or tuple(mapping.shape) != (self.n_labels,):
+            raise ValueError(f"mapping must be int32 [{self.n_labels}]")
+        lo, hi = (int(v) for v in torch.aminmax(mapping))
+        if lo < 0:
+            raise ValueError("mapping must map every region id to a region id >= 0")
+        G = self.n_truth
+        keys = mapping.long()[self.cells[:, 0].long()] * (G + 1) + self.cells[:, 1].long()
+        uniq, inverse = torch.unique(keys, return_inverse=True)   # sorted
+        counts = torch.zeros(uniq.numel(), dtype=torch.int32, device=keys.device).index_add_(0, inverse, self.count)
+        return _overlap_facts(uniq, counts, hi + 1, G)
+
+    def scores(self) -> PartitionScores:
+        """The partition scored against the truth (one readback: the eight integers)."""
+        return partition_scores(self.summary.tolist())
+
+
+def label_overlap(labels: torch.Tensor, truth: torch.Tensor, n_labels: int, n_truth: int, max_cells: int = 0) -> Overlap:
+    """Overlap table of a label raster (region ids 0..n_labels-1, others ignored) with a ground-truth raster (object ids
+    0..n_truth-1, any other value = unlabelled, counted in column n_truth), and the row / column facts (the rule:
+    include/deepmerge_hip.h).  One pass over both rasters; one readback (number of cells, overflow).  max_cells (default
+    max(1024, 8 n_labels)) bounds the number of non-empty cells; a coarse partition against a fine truth map (n_truth >> n_labels)
+    needs it passed explicitly, and a table that turns out too small raises RuntimeError."""
+    _need_cuda(labels, truth)
+    if labels.dtype != torch.int32 or truth.dtype != torch.int32 or labels.dim() != 2 or labels.shape != truth.shape or labels.numel() < 1:
+        raise ValueError("labels and truth must be int32 [H,W] over the same raster, with at least one pixel")
+    if labels.numel() >= 1 << 31:
+        raise ValueError(f"label_overlap takes rasters of fewer than 2^31 pixels, got {labels.numel()}")
+    S, G = int(n_labels), int(n_truth)
+    if S < 1 or G < 1 or G >= 1 << 31 or S * (G + 1) >= 1 << 62:
+        raise ValueError(f"need n_labels >= 1, 1 <= n_truth < 2^31 and n_labels * (n_truth + 1) < 2^62, got {n_labels}, {n_truth}")
+    labels, truth = labels.contiguous(), truth.contiguous()
+    H, W = labels.shape
+    dev = labels.device
+    max_cells = int(max_cells) or max(1024, 8 * S)                # a region straddles a few objects; 8 S leaves room for ragged truth
+    log2 = max(10, (4 * max_cells - 1).bit_length())             # load factor <= 1/4
+    if log2 > 30:
+        raise ValueError(f"max_cells = {max_cells} needs a table of more than 2^30 slots")
+    tk = torch.empty(1 << log2, dtype=torch.int64, device=dev)
+    tc = torch.empty(1 << log2, dtype=torch.int32, device=dev)
+    ck = torch.empty(max_cells, dtype=torch.int64, device=dev)
+    cc = torch.empty(max_cells, dtype=torch.int32, device=dev)
+    meta = torch.empty(2, dtype=torch.int32, device=dev)
+    check(_lib.lib().dm_label_overlap(labels.data_ptr(), truth.data_ptr(), H, W, S, G, tk.data_ptr(), tc.data_ptr(), log2, ck.data_ptr(),
+                                      cc.data_ptr(), max_cells, meta.data_ptr(), meta[1:].data_ptr(), _stream()), "dm_label_overlap")
+    n, overflow = (int(v) for v in meta.tolist())
+    if overflow or n > max_cells:
+        raise RuntimeError(f"the overlap table has more than max_cells={max_cells} cells (found {n}, table overflow={bool(overflow)}); "
+                           f"pass a larger max_cells")
+    order = torch.argsort(ck[:n])                                 # canonical order; keys are unique
+    return _overlap_facts(ck[:n][order], cc[:n][order], S, G)
+
+
+def pair_flags(edges: torch.Tensor, overlap: Overlap, min_purity: float = 0.6) -> torch.Tensor:
+    """int8 [E] per edge of the region-adjacency graph: 1 = merge (both regions pure and owned by the same object), 0 = do not
+    merge (both pure, different owners), -1 = ambiguous, not a training pair (a region whose best object holds less than
+    min_purity of its area -- unlabelled pixels count against it -- or an endpoint outside [0, n_labels)).  min_purity in [0, 1],
+    rounded to per-mille; the comparison is in integers."""
+    _need_cuda(edges, overlap.area)
+    if edges.dtype != torch.int32 or edges.dim() != 2 or edges.shape[1] != 2:
+        raise ValueError("edges must be int32 [E,2]")
+    if not 0.0 <= float(min_purity) <= 1.0:
+        raise ValueError(f"min_purity must be in [0, 1], got {min_purity}")
+    edges = edges.contiguous()
+    E = edges.shape[0]
+    flags = torch.empty(E, dtype=torch.int8, device=edges.device)
+    check(_lib.lib().dm_pair_flags(edges.data_ptr() if E else None, E, overlap.area.data_ptr(), overlap.owner.data_ptr(),
+                                   overlap.owner_count.data_ptr(), min(overlap.n_labels, (1 << 31) - 1), int(round(float(min_purity) * 1000)),
+                                   flags.data_ptr() if E else None, _stream()), "dm_pair_flags")
+    return flags

@@ -568,6 +568,46 @@ int dm_point_emit(const int32_t *counts, const int32_t *points, const int32_t *p
                   int32_t max_window, int32_t capacity, int32_t *ptr, int32_t *xy, int32_t *label, int32_t *inner, int32_t *obj,
                   int32_t *round, void *stream);
 
+/* ---- overlap of a label raster with a ground-truth raster: pair labels and partition scores (additive in ABI 6;
+ * csrc/dm_truth.hip, DESIGN.md 3.5.3, rag.label_overlap / rag.pair_flags / Overlap.scores) ----------------------------------------
+ * Replaces the `positive` / `negative` polygon-pair lists the reference reads from text files that were made outside the program
+ * by comparing the over-segmentation with a ground-truth map (GenerateTrainPairData.py only counts their lines), and adds what
+ * the reference lacks: a score of a PARTITION against a reference map.  The rule is this build's (restated in numpy in
+ * tests/truth_ref.py).  All arithmetic is on integers; results are bit-exact.
+ * The rule.  labels int32 [H,W]: region ids 0..S-1, ids outside [0,S) are ignored.  truth int32 [H,W]: object ids 0..G-1, any
+ * other value means "unlabelled" and is counted under the pseudo-object G.  H*W < 2^31, G < 2^31, S*(G+1) < 2^62 (S and G are
+ * passed as int64 so that the library, not an integer conversion in the binding, checks the bound).
+ *   overlap table: n[s,g] = number of pixels with labels == s and truth column g, g in 0..G; sparse: keys s*(G+1)+g with int32
+ *     counts, non-zero cells only, in ARBITRARY order (sort by key for a canonical list).
+ *   row facts [S]: area[s] = sum over all G+1 columns (int64); owner[s] = the g < G with the largest n[s,g] >= 1, ties to the
+ *     smallest g, -1 when s has no labelled pixel; owner_count[s] = n[s,owner[s]] or 0.  As the key
+ *     (count << 32) | (0xFFFFFFFF - g) this is one unsigned 64-bit max per row.
+ *   column facts [G]: size[g] = sum of n[s,g] over s (int64); cover[g] = max of n[s,g] over s (int32).
+ *   pair flags: purity_pm in 0..1000; pure(s) iff owner[s] >= 0 and 1000*owner_count[s] >= purity_pm*area[s] (int64).  Edge (a,b):
+ *     1 (merge) iff both pure and owner[a] == owner[b]; 0 iff both pure and the owners differ; -1 (ambiguous, not a training
+ *     pair) otherwise, which includes any edge with an endpoint outside [0,S).
+ *   summary int64 [8], over the labelled columns g < G only: n = sum n[s,g]; sum n[s,g]^2; sum_s r_s^2 with r_s = sum_{g<G} n[s,g];
+ *     sum_g size[g]^2; sum_s owner_count[s]; sum_g cover[g]; number of rows with r_s > 0; number of columns with size > 0.
+ *     Every sum is bounded by n^2 < 2^62.
+ * Every entry point validates before any launch, launches on `stream`, never synchronises and never allocates.
+ *
+ * dm_label_overlap: one pass over both rasters (8 B per pixel).  table_keys / table_counts: scratch of 2^capacity_log2 entries
+ *   (int64 / int32, 8 <= capacity_log2 <= 30); cell_keys / cell_counts: up to max_cells results; n_cells[0] = number found (may
+ *   exceed max_cells: then the output is truncated); overflow[0] = 1 if the table was too small.  All outputs and scratch are
+ *   (re)initialised by the call.
+ * dm_overlap_reduce: row facts, column facts and summary from K cells in any order (K = 0: every fact is that of an empty table).
+ *   Keys must be unique (fold duplicates first); entries with a key outside [0, S*(G+1)) or a count < 1 are skipped.
+ *   Scratch: row_best uint64 [S], row_labelled int64 [S] (= r_s on return).  All outputs are (re)initialised by the call.
+ * dm_pair_flags: flags int8 [E] for edges int32 [E,2] from the row facts. */
+int dm_label_overlap(const int32_t *labels, const int32_t *truth, int32_t H, int32_t W, int64_t S, int64_t G, int64_t *table_keys,
+                     int32_t *table_counts, int32_t capacity_log2, int64_t *cell_keys, int32_t *cell_counts, int32_t max_cells,
+                     int32_t *n_cells, int32_t *overflow, void *stream);
+int dm_overlap_reduce(const int64_t *cell_keys, const int32_t *cell_counts, int32_t K, int64_t S, int64_t G, uint64_t *row_best,
+                      int64_t *row_labelled, int64_t *area, int32_t *owner, int32_t *owner_count, int64_t *size, int32_t *cover,
+                      int64_t *summary, void *stream);
+int dm_pair_flags(const int32_t *edges, int32_t E, const int64_t *area, const int32_t *owner, const int32_t *owner_count, int32_t S,
+                  int32_t purity_pm, int8_t *flags, void *stream);
+
 /* BatchNorm2d (+ ReLU, + Dropout2d mask) of the auxiliary heads (reference nets/ShfitScaleFormer.py:329-368: Conv2d ->
  * BatchNorm2d -> ReLU -> Dropout2d(0.3)) on the channels-last matrix the convolution GEMM produces: x, y fp32 [M, C] with
  * M = samples * rows_per_sample.  training != 0: batch statistics (biased variance, eps inside the sqrt), running_mean /
