@@ -39,7 +39,8 @@ void dm_set_error(const char *fmt, ...);
     }                                                                                \
   } while (0)
 
-static inline bool dm_aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
+static inline bool dm_aligned(const void *p, unsigned bytes) { return (reinterpret_cast<uintptr_t>(p) & (bytes - 1)) == 0; }     // bytes: a power of two
+static inline bool dm_aligned16(const void *p) { return dm_aligned(p, 16); }
 
 // ---- device helpers ------------------------------------------------------------------------
 template <typename T> struct DmTypeInfo;

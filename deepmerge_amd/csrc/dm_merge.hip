@@ -12,20 +12,14 @@
 // the merged components are single regions and pairs, root[b] = a is already the final labelling (no path to compress),
 // and the merged point list of a pair is "segment of a, then segment of b": two block copies to an offset that an exclusive
 // scan of the new counts provides.
-#include <climits>
-
-#include "dm_common.h"
+//
+// The scans run on dm_raster.h's block_exclusive (one looping workgroup).
+#include "dm_raster.h"
 
 namespace {
 
 constexpr unsigned long long NO_BEST = ~0ULL;
 constexpr long long SELF_KEY = LLONG_MAX;                 // relabelled self edge: sorts behind every live key
-constexpr int SCAN_THREADS = 1024, SCAN_ITEMS = 4, SCAN_TILE = SCAN_THREADS * SCAN_ITEMS;
-
-inline int grid_for(long long items, int cap = 2048) {
-  long long g = (items + 255) / 256;
-  return (int)(g < 1 ? 1 : (g > cap ? cap : g));
-}
 
 // ---- best neighbour ----------------------------------------------------------------------------------------------------
 __global__ void best_clear_kernel(unsigned long long *__restrict__ best, int C) {
@@ -96,33 +90,11 @@ __global__ __launch_bounds__(256) void match_kernel(const int *__restrict__ edge
   }
 }
 
-// ---- exclusive scan of three int streams by one looping workgroup -----------------------------------------------------------
+// ---- three int streams scanned together (block_exclusive<I3>) ------------------------------------------------------------------
 struct I3 { int x, y, z; };
 __device__ __forceinline__ I3 operator+(I3 a, I3 b) { return {a.x + b.x, a.y + b.y, a.z + b.z}; }
-__device__ __forceinline__ I3 shfl_up3(I3 v, int o) { return {__shfl_up(v.x, o, 64), __shfl_up(v.y, o, 64), __shfl_up(v.z, o, 64)}; }
-
-// Exclusive prefix of `v` over the workgroup's threads (thread order) and the workgroup total.  lds: SCAN_THREADS / 64 entries.
-__device__ __forceinline__ I3 block_exclusive3(I3 v, I3 *lds, I3 &total) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  I3 inc = v;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const I3 up = shfl_up3(inc, o);
-    if (lane >= o) inc = inc + up;
-  }
-  __syncthreads();                                     // the previous tile's readers of lds are done
-  if (lane == 63) lds[wave] = inc;
-  __syncthreads();
-  I3 before = {0, 0, 0}, all = {0, 0, 0};
-#pragma unroll
-  for (int w = 0; w < SCAN_THREADS / 64; ++w) {
-    const I3 t = lds[w];
-    if (w < wave) before = before + t;
-    all = all + t;
-  }
-  total = all;
-  return {before.x + inc.x - v.x, before.y + inc.y - v.y, before.z + inc.z - v.z};
-}
+__device__ __forceinline__ I3 operator-(I3 a, I3 b) { return {a.x - b.x, a.y - b.y, a.z - b.z}; }
+__device__ __forceinline__ I3 shfl_up(I3 v, int o) { return {shfl_up(v.x, o), shfl_up(v.y, o), shfl_up(v.z, o)}; }
 
 // ---- fold regions ------------------------------------------------------------------------------------------------------
 // One workgroup walks the C regions in tiles: new dense id of every root (= rank among the roots, so ids stay in order of
@@ -155,7 +127,7 @@ __global__ __launch_bounds__(SCAN_THREADS) void fold_scan_kernel(const int *__re
       sum = sum + v;
     }
     I3 total;
-    I3 run = carry + block_exclusive3(sum, lds, total);
+    I3 run = carry + block_exclusive(sum, lds, total);
 #pragma unroll
     for (int j = 0; j < SCAN_ITEMS; ++j) {
       const long long r = base + (long long)threadIdx.x * SCAN_ITEMS + j;
@@ -251,7 +223,7 @@ __global__ __launch_bounds__(256) void edge_keys_kernel(const int *__restrict__ 
 __global__ __launch_bounds__(SCAN_THREADS) void fold_edges_kernel(const long long *__restrict__ keys, const long long *__restrict__ order,
                                                                   const int *__restrict__ weights, int E, int *__restrict__ new_edges,
                                                                   int *__restrict__ new_weights, int *__restrict__ n_edges) {
-  __shared__ I3 lds[SCAN_THREADS / 64];
+  __shared__ int lds[SCAN_THREADS / 64];
   int carry = 0;
   for (long long base = 0; base < E; base += SCAN_TILE) {
     int head[SCAN_ITEMS], sum = 0;
@@ -265,8 +237,8 @@ __global__ __launch_bounds__(SCAN_THREADS) void fold_edges_kernel(const long lon
       }
       sum += head[j];
     }
-    I3 total;
-    int run = carry + block_exclusive3({sum, 0, 0}, lds, total).x;
+    int total;
+    int run = carry + block_exclusive(sum, lds, total);
 #pragma unroll
     for (int j = 0; j < SCAN_ITEMS; ++j) {
       const long long i = base + (long long)threadIdx.x * SCAN_ITEMS + j;
@@ -285,7 +257,7 @@ __global__ __launch_bounds__(SCAN_THREADS) void fold_edges_kernel(const long lon
       }
       run += head[j];
     }
-    carry += total.x;
+    carry += total;
   }
   if (threadIdx.x == 0) *n_edges = carry;
 }

@@ -16,22 +16,16 @@
 //   3. column_clearance_kernel  c - 1 = min over y' of max(|y - y'|, g(y', x)): rows are visited outwards until |y - y'|
 //                             reaches the best value so far, i.e. c rows up and c rows down per pixel (4 pixels per thread)
 // Selection round j: one pass over the raster, key = (score << 32) | (0xFFFFFFFF - linear index), one 64-bit max per
-// superpixel.  As in dm_rag.hip a workgroup owns a 64x64-pixel tile, a thread a 16-pixel strip of one row; the tile's labels
-// get a slot in an LDS table, the strip's runs are folded there with 64-bit LDS max, and each label of the tile then costs
-// ONE global 64-bit atomicMax.  Round 0 carries the bounding box in the same table.
-#include <climits>
-
-#include "dm_common.h"
+// superpixel, on dm_raster.h's tile walk: the tile's labels get a slot in an LDS table, the strip's runs are folded there
+// with 64-bit LDS max, and each label of the tile then costs ONE global 64-bit atomicMax.  Round 0 carries the bounding box in
+// the same table.
+#include "dm_raster.h"
 
 namespace {
 
-typedef unsigned long long u64;
-
-constexpr int STRIP = 16;
 constexpr int TSLOTS_LOG2 = 6, TSLOTS = 1 << TSLOTS_LOG2;      // labels per 64x64 tile kept in LDS (more: global atomics)
 constexpr int KMAX = 16;                                       // points per superpixel
 constexpr int ROW_THREADS = 256;
-constexpr int SCAN_THREADS = 1024, SCAN_ITEMS = 4, SCAN_TILE = SCAN_THREADS * SCAN_ITEMS;
 
 // ---- clearance -----------------------------------------------------------------------------------------------------------
 // A workgroup covers 256 consecutive pixels of one row: four waves, one 64-bit word each.
@@ -140,7 +134,7 @@ __global__ void select_init_kernel(u64 *__restrict__ best, int *__restrict__ cnt
   if (s >= S) return;
   best[s] = 0;
   cnt[s] = 0;
-  bbox[4 * s + 0] = INT_MAX; bbox[4 * s + 1] = INT_MAX; bbox[4 * s + 2] = -1; bbox[4 * s + 3] = -1;
+  box_init(bbox + 4 * s);
 }
 
 // Round j over the raster.  FIRST (j == 0): no earlier points, and the bounding box rides along.
@@ -155,23 +149,15 @@ __global__ __launch_bounds__(256) void point_select_kernel(const int *__restrict
   __shared__ int t_pt[TSLOTS][KMAX][2];
   for (int i = threadIdx.x; i < TSLOTS; i += blockDim.x) {
     t_key[i] = -1; t_best[i] = 0; t_np[i] = 0;
-    t_box[i][0] = INT_MAX; t_box[i][1] = INT_MAX; t_box[i][2] = -1; t_box[i][3] = -1;
+    box_init(t_box[i]);
   }
   __syncthreads();
-  const int tiles_x = (W + 63) / 64;
-  const int ty = blockIdx.x / tiles_x, tx = blockIdx.x - ty * tiles_x;
-  const int y = ty * 64 + (threadIdx.x >> 2), x0 = tx * 64 + (threadIdx.x & 3) * STRIP;
-  const bool live = y < H && x0 < W;
-  const int n = live ? min(STRIP, W - x0) : 0;
-  const long long base = (long long)(live ? y : 0) * W + (live ? x0 : 0);
+  const Strip g = strip_of(H, W);
+  const int y = g.y, x0 = g.x0, n = g.n;
+  const long long base = g.base;
   int lab[STRIP], c[STRIP];
+  load_strip<VEC>(labels, base, n, -1, lab);
   if (VEC && n == STRIP) {
-#pragma unroll
-    for (int v = 0; v < STRIP / 4; ++v) {
-      const i32x4 a = *reinterpret_cast<const i32x4 *>(labels + base + 4 * v);
-#pragma unroll
-      for (int e = 0; e < 4; ++e) lab[4 * v + e] = a[e];
-    }
 #pragma unroll
     for (int v = 0; v < STRIP / 8; ++v) {
       const u32x4 q = *reinterpret_cast<const u32x4 *>(clr + base + 8 * v);
@@ -180,21 +166,8 @@ __global__ __launch_bounds__(256) void point_select_kernel(const int *__restrict
     }
   } else {
 #pragma unroll
-    for (int i = 0; i < STRIP; ++i) {
-      lab[i] = (i < n) ? labels[base + i] : -1;
-      c[i] = (i < n) ? (int)clr[base + i] : 0;
-    }
+    for (int i = 0; i < STRIP; ++i) c[i] = (i < n) ? (int)clr[base + i] : 0;
   }
-  // slot of a label in the tile's table (open addressing); -1 when the table is full: that label goes to global memory
-  auto slot_of = [&](int l) -> int {
-    unsigned slot = ((unsigned)l * 2654435761u) >> (32 - TSLOTS_LOG2);
-    for (int probe = 0; probe < TSLOTS; ++probe) {
-      const int seen = atomicCAS(&t_key[slot], -1, l);
-      if (seen == -1 || seen == l) return (int)slot;
-      slot = (slot + 1) & (TSLOTS - 1);
-    }
-    return -1;
-  };
   if (!FIRST) {
     // claim the strip's labels, then load every claimed label's earlier points once for the whole tile
     int cur = -1;
@@ -204,7 +177,7 @@ __global__ __launch_bounds__(256) void point_select_kernel(const int *__restrict
       const int l = lab[i];
       if (l != cur) {
         cur = l;
-        if ((unsigned)l < (unsigned)S) slot_of(l);
+        if ((unsigned)l < (unsigned)S) claim_label_slot<TSLOTS_LOG2>(t_key, l);
       }
     }
     __syncthreads();
@@ -229,17 +202,11 @@ __global__ __launch_bounds__(256) void point_select_kernel(const int *__restrict
       if (!valid) return;
       if (slot >= 0) {
         if (run_best) atomicMax(&t_best[slot], run_best);
-        if (FIRST) {
-          atomicMin(&t_box[slot][0], run_x0); atomicMin(&t_box[slot][1], y);
-          atomicMax(&t_box[slot][2], xend); atomicMax(&t_box[slot][3], y);
-        }
+        if (FIRST) box_fold(t_box[slot], run_x0, y, xend, y);
         return;
       }
       if (run_best) atomicMax(best + cur, run_best);
-      if (FIRST) {
-        atomicMin(bbox + 4 * cur + 0, run_x0); atomicMin(bbox + 4 * cur + 1, y);
-        atomicMax(bbox + 4 * cur + 2, xend); atomicMax(bbox + 4 * cur + 3, y);
-      }
+      if (FIRST) box_fold(bbox + 4 * cur, run_x0, y, xend, y);
     };
 #pragma unroll
     for (int i = 0; i < STRIP; ++i) {
@@ -250,7 +217,7 @@ __global__ __launch_bounds__(256) void point_select_kernel(const int *__restrict
         flush(x - 1);
         cur = l; run_x0 = x; run_best = 0;
         valid = (unsigned)l < (unsigned)S;
-        slot = valid ? slot_of(l) : -1;
+        slot = valid ? claim_label_slot<TSLOTS_LOG2>(t_key, l) : -1;    // -1: table full, the label goes to global memory
         np = 0;
         if (!FIRST && valid) np = slot >= 0 ? t_np[slot] : min(min(j, k), cnt[l]);
       }
@@ -268,17 +235,14 @@ __global__ __launch_bounds__(256) void point_select_kernel(const int *__restrict
         run_best = key > run_best ? key : run_best;
       }
     }
-    if (live) flush(x0 + n - 1);
+    if (g.live) flush(x0 + n - 1);
   }
   __syncthreads();
   for (int i = threadIdx.x; i < TSLOTS; i += blockDim.x) {      // one global max (and one box) per label of the tile
     const int l = t_key[i];
     if (l < 0) continue;
     if (t_best[i]) atomicMax(best + l, t_best[i]);
-    if (FIRST && t_box[i][2] >= 0) {
-      atomicMin(bbox + 4 * l + 0, t_box[i][0]); atomicMin(bbox + 4 * l + 1, t_box[i][1]);
-      atomicMax(bbox + 4 * l + 2, t_box[i][2]); atomicMax(bbox + 4 * l + 3, t_box[i][3]);
-    }
+    if (FIRST && t_box[i][2] >= 0) box_fold(bbox + 4 * l, t_box[i][0], t_box[i][1], t_box[i][2], t_box[i][3]);
   }
 }
 
@@ -303,7 +267,6 @@ __global__ void point_commit_kernel(u64 *__restrict__ best, const unsigned short
 // Exclusive scan of the counts by one looping workgroup (S is tens of thousands: a few tiles of 4096).
 __global__ __launch_bounds__(SCAN_THREADS) void count_scan_kernel(const int *__restrict__ cnt, int S, int k, int *__restrict__ ptr) {
   __shared__ int lds[SCAN_THREADS / 64];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   int carry = 0;
   for (long long base = 0; base < S; base += SCAN_TILE) {
     int item[SCAN_ITEMS], sum = 0;
@@ -313,23 +276,8 @@ __global__ __launch_bounds__(SCAN_THREADS) void count_scan_kernel(const int *__r
       item[i] = s < S ? min(max(cnt[s], 0), k) : 0;
       sum += item[i];
     }
-    int inc = sum;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-      const int up = __shfl_up(inc, o, 64);
-      if (lane >= o) inc += up;
-    }
-    __syncthreads();                                          // the previous tile's readers of lds are done
-    if (lane == 63) lds[wave] = inc;
-    __syncthreads();
-    int before = 0, total = 0;
-#pragma unroll
-    for (int w = 0; w < SCAN_THREADS / 64; ++w) {
-      const int t = lds[w];
-      if (w < wave) before += t;
-      total += t;
-    }
-    int run = carry + before + inc - sum;
+    int total;
+    int run = carry + block_exclusive(sum, lds, total);
 #pragma unroll
     for (int i = 0; i < SCAN_ITEMS; ++i) {
       const long long s = base + (long long)threadIdx.x * SCAN_ITEMS + i;
@@ -361,8 +309,6 @@ __global__ __launch_bounds__(256) void point_emit_kernel(const int *__restrict__
   round[row] = q;
 }
 
-inline bool aligned(const void *p, unsigned a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
-
 }  // namespace
 
 extern "C" int dm_label_clearance(const int32_t *labels, int32_t H, int32_t W, int32_t max_window, uint64_t *bits, uint8_t *row_dist,
@@ -378,7 +324,7 @@ extern "C" int dm_label_clearance(const int32_t *labels, int32_t H, int32_t W, i
   hipLaunchKernelGGL(row_distance_kernel, dim3((unsigned)((long long)H * gb)), dim3(ROW_THREADS), 0, s, (const u64 *)bits, H, W, WW, gb, capm1,
                      row_dist);
   const int gc = (W + 4 * ROW_THREADS - 1) / (4 * ROW_THREADS);
-  if (W % 4 == 0 && aligned(row_dist, 4) && aligned(clearance, 8))
+  if (W % 4 == 0 && dm_aligned(row_dist, 4) && dm_aligned(clearance, 8))
     hipLaunchKernelGGL(column_clearance_kernel<true>, dim3((unsigned)((long long)H * gc)), dim3(ROW_THREADS), 0, s, row_dist, H, W, gc, clearance);
   else
     hipLaunchKernelGGL(column_clearance_kernel<false>, dim3((unsigned)((long long)H * gc)), dim3(ROW_THREADS), 0, s, row_dist, H, W, gc, clearance);
@@ -395,7 +341,7 @@ extern "C" int dm_point_select_round(const int32_t *labels, const uint16_t *clea
   DM_REQUIRE(k >= 1 && k <= KMAX, DM_ERR_BAD_SHAPE, "dm_point_select_round: k = %d outside 1..16", k);
   DM_REQUIRE(round >= 0 && round < k, DM_ERR_BAD_SHAPE, "dm_point_select_round: round = %d outside 0..k-1 (k = %d)", round, k);
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  const dim3 grid((unsigned)(((W + 63) / 64) * ((H + 63) / 64)));      // one workgroup per 64x64-pixel tile
+  const dim3 grid = tile_grid(H, W);
   const bool vec = (W % STRIP == 0) && dm_aligned16(labels) && dm_aligned16(clearance);
   if (round == 0) {
     hipLaunchKernelGGL(select_init_kernel, dim3((S + 255) / 256), dim3(256), 0, s, (u64 *)best, counts, bbox, S);

@@ -5,31 +5,23 @@
 // the build's own (oracle/rag.py states them; every quantity is an exact integer or a fixed double-precision formula
 // of exact integers, so the GPU and the oracle agree bit for bit).
 //
-// HBM-bound integer work: one pass over the raster per kernel.  A thread walks a 16-pixel strip of one row (one 16-byte
-// load per band, 64 bytes of labels), run-length merges what it finds and flushes once per run, so the number of atomics
-// is ~10x below one per pixel; all atomics are on integers (exact, order-independent => deterministic).
-#include <climits>
-
-#include "dm_common.h"
-#include "dm_table.h"
+// HBM-bound integer work: one pass over the raster per kernel, on dm_raster.h's tile walk.  A thread run-length merges its
+// strip (one 16-byte load per band, 64 bytes of labels) and flushes once per run into the tile's LDS tables, so the number
+// of atomics is ~10x below one per pixel; all atomics are on integers (exact, order-independent => deterministic).
+#include "dm_raster.h"
 
 namespace {
 
-constexpr int STRIP = 16;
 constexpr int TSLOTS_LOG2 = 6, TSLOTS = 1 << TSLOTS_LOG2;      // labels per 64x64 tile kept in LDS (more: global atomics)
-constexpr int ESLOTS_LOG2 = 7, ESLOTS = 1 << ESLOTS_LOG2;      // label pairs per tile kept in LDS
+constexpr int ESLOTS_LOG2 = 7;                                 // 128 label pairs per tile kept in LDS
 
 __global__ void rag_init_kernel(long long *count, long long *sum, long long *sumsq, int *bbox, long long *peri, int S, int bands3) {
   const int s = blockIdx.x * blockDim.x + threadIdx.x;
   if (s >= S) return;
   count[s] = 0;
   for (int b = 0; b < bands3; ++b) { sum[(long long)s * bands3 + b] = 0; sumsq[(long long)s * bands3 + b] = 0; }
-  bbox[4 * s + 0] = INT_MAX; bbox[4 * s + 1] = INT_MAX; bbox[4 * s + 2] = -1; bbox[4 * s + 3] = -1;
+  box_init(bbox + 4 * s);
   peri[2 * s + 0] = 0; peri[2 * s + 1] = 0;
-}
-
-__device__ __forceinline__ void atomic_add64(long long *p, long long v) {
-  atomicAdd(reinterpret_cast<unsigned long long *>(p), (unsigned long long)v);
 }
 
 // Per label: pixel count, per-band sum and sum of squares (first NB <= 3 bands), bounding box, perimeter in pixel edges
@@ -39,38 +31,29 @@ __global__ __launch_bounds__(256) void label_stats_kernel(const int *__restrict_
                                                           int H, int W, int S, long long *__restrict__ count,
                                                           long long *__restrict__ sum, long long *__restrict__ sumsq,
                                                           int *__restrict__ bbox, long long *__restrict__ peri) {
-  // A workgroup owns a 64x64-pixel tile (thread = one 16-pixel strip of one row).  A tile meets only a handful of superpixels,
-  // so the per-run statistics are first folded in an LDS-private table (integer LDS atomics) and every label of the tile then
-  // costs ONE set of global atomics: ~25x fewer global atomics than flushing every run.
+  // A tile meets only a handful of superpixels, so the per-run statistics are first folded in an LDS-private table (integer LDS
+  // atomics) and every label of the tile then costs ONE set of global atomics: ~25x fewer global atomics than flushing every run.
   __shared__ int t_key[TSLOTS];
   __shared__ unsigned t_cnt[TSLOTS], t_sum[TSLOTS][NB], t_sq[TSLOTS][NB], t_per[TSLOTS][2];
   __shared__ int t_box[TSLOTS][4];
   for (int i = threadIdx.x; i < TSLOTS; i += blockDim.x) {
     t_key[i] = -1; t_cnt[i] = 0; t_per[i][0] = 0; t_per[i][1] = 0;
-    t_box[i][0] = INT_MAX; t_box[i][1] = INT_MAX; t_box[i][2] = -1; t_box[i][3] = -1;
+    box_init(t_box[i]);
 #pragma unroll
     for (int b = 0; b < NB; ++b) { t_sum[i][b] = 0; t_sq[i][b] = 0; }
   }
   __syncthreads();
-  const int tiles_x = (W + 63) / 64;
-  const int ty = blockIdx.x / tiles_x, tx = blockIdx.x - ty * tiles_x;
   {
-    const int y = ty * 64 + (threadIdx.x >> 2), x0 = tx * 64 + (threadIdx.x & 3) * STRIP;
-    const bool live = y < H && x0 < W;
-    const int n = live ? min(STRIP, W - x0) : 0;
-    const int *row = labels + (long long)(live ? y : 0) * W;
+    const Strip g = strip_of(H, W);
+    const int y = g.y, x0 = g.x0, n = g.n;
+    const bool live = g.live;
     // strip registers: this row's labels with one neighbour on each side, the rows above / below, the bands' bytes
     int lab[STRIP + 2], up[STRIP], dn[STRIP];
     unsigned char px[NB][STRIP];
+    load_strip<VEC>(labels, g.base, n, -2, lab + 1);             // -2 = outside the raster
+    load_strip<VEC>(labels, g.base - W, n, -2, up, y > 0);
+    load_strip<VEC>(labels, g.base + W, n, -2, dn, y + 1 < H);
     if (VEC && n == STRIP) {
-#pragma unroll
-      for (int v = 0; v < STRIP / 4; ++v) {
-        const i32x4 a = *reinterpret_cast<const i32x4 *>(row + x0 + 4 * v);
-        const i32x4 u = (y > 0) ? *reinterpret_cast<const i32x4 *>(row - W + x0 + 4 * v) : (i32x4){-2, -2, -2, -2};
-        const i32x4 d = (y + 1 < H) ? *reinterpret_cast<const i32x4 *>(row + W + x0 + 4 * v) : (i32x4){-2, -2, -2, -2};
-#pragma unroll
-        for (int e = 0; e < 4; ++e) { lab[1 + 4 * v + e] = a[e]; up[4 * v + e] = u[e]; dn[4 * v + e] = d[e]; }
-      }
 #pragma unroll
       for (int b = 0; b < NB; ++b) {
         const u32x4 q = *reinterpret_cast<const u32x4 *>(tile + ((long long)b * H + y) * W + x0);
@@ -79,38 +62,25 @@ __global__ __launch_bounds__(256) void label_stats_kernel(const int *__restrict_
       }
     } else {
 #pragma unroll
-      for (int i = 0; i < STRIP; ++i) {
-        const bool in = i < n;
-        lab[1 + i] = in ? row[x0 + i] : -2;
-        up[i] = (in && y > 0) ? row[x0 + i - W] : -2;
-        dn[i] = (in && y + 1 < H) ? row[x0 + i + W] : -2;
+      for (int i = 0; i < STRIP; ++i)
 #pragma unroll
-        for (int b = 0; b < NB; ++b) px[b][i] = in ? tile[((long long)b * H + y) * W + x0 + i] : 0;
-      }
+        for (int b = 0; b < NB; ++b) px[b][i] = (i < n) ? tile[((long long)b * H + y) * W + x0 + i] : 0;
     }
-    lab[0] = (live && x0 > 0) ? row[x0 - 1] : -2;             // -2 = outside the raster
-    lab[STRIP + 1] = (live && x0 + STRIP < W) ? row[x0 + STRIP] : -2;
-    if (n < STRIP) lab[1 + n] = (live && x0 + n < W) ? row[x0 + n] : -2;
+    lab[0] = (live && x0 > 0) ? labels[g.base - 1] : -2;
+    lab[STRIP + 1] = (live && x0 + STRIP < W) ? labels[g.base + STRIP] : -2;
+    if (n < STRIP) lab[1 + n] = (live && x0 + n < W) ? labels[g.base + n] : -2;
     int cur = -1, run_x0 = 0;
     long long c = 0, sm[NB], sq[NB], pin = 0, pbd = 0;
 #pragma unroll
     for (int b = 0; b < NB; ++b) { sm[b] = 0; sq[b] = 0; }
     auto flush = [&](int xend) {
       if (cur < 0 || cur >= S || c == 0) return;
-      // slot of this label in the tile's table (open addressing); a full table falls back to global atomics
-      unsigned slot = ((unsigned)cur * 2654435761u) >> (32 - TSLOTS_LOG2);
-      bool found = false;
-      for (int probe = 0; probe < TSLOTS; ++probe) {
-        const int seen = atomicCAS(&t_key[slot], -1, cur);
-        if (seen == -1 || seen == cur) { found = true; break; }
-        slot = (slot + 1) & (TSLOTS - 1);
-      }
-      if (found) {
+      const int slot = claim_label_slot<TSLOTS_LOG2>(t_key, cur);      // a full table falls back to global atomics
+      if (slot >= 0) {
         atomicAdd(&t_cnt[slot], (unsigned)c);
 #pragma unroll
         for (int b = 0; b < NB; ++b) { atomicAdd(&t_sum[slot][b], (unsigned)sm[b]); atomicAdd(&t_sq[slot][b], (unsigned)sq[b]); }
-        atomicMin(&t_box[slot][0], run_x0); atomicMin(&t_box[slot][1], y);
-        atomicMax(&t_box[slot][2], xend); atomicMax(&t_box[slot][3], y);
+        box_fold(t_box[slot], run_x0, y, xend, y);
         if (pin) atomicAdd(&t_per[slot][0], (unsigned)pin);
         if (pbd) atomicAdd(&t_per[slot][1], (unsigned)pbd);
         return;
@@ -118,8 +88,7 @@ __global__ __launch_bounds__(256) void label_stats_kernel(const int *__restrict_
       atomic_add64(count + cur, c);
 #pragma unroll
       for (int b = 0; b < NB; ++b) { atomic_add64(sum + (long long)cur * NB + b, sm[b]); atomic_add64(sumsq + (long long)cur * NB + b, sq[b]); }
-      atomicMin(bbox + 4 * cur + 0, run_x0); atomicMin(bbox + 4 * cur + 1, y);
-      atomicMax(bbox + 4 * cur + 2, xend); atomicMax(bbox + 4 * cur + 3, y);
+      box_fold(bbox + 4 * cur, run_x0, y, xend, y);
       if (pin) atomic_add64(peri + 2 * cur, pin);
       if (pbd) atomic_add64(peri + 2 * cur + 1, pbd);
     };
@@ -159,8 +128,7 @@ __global__ __launch_bounds__(256) void label_stats_kernel(const int *__restrict_
       atomic_add64(sum + (long long)l * NB + b, (long long)t_sum[i][b]);
       atomic_add64(sumsq + (long long)l * NB + b, (long long)t_sq[i][b]);
     }
-    atomicMin(bbox + 4 * l + 0, t_box[i][0]); atomicMin(bbox + 4 * l + 1, t_box[i][1]);
-    atomicMax(bbox + 4 * l + 2, t_box[i][2]); atomicMax(bbox + 4 * l + 3, t_box[i][3]);
+    box_fold(bbox + 4 * l, t_box[i][0], t_box[i][1], t_box[i][2], t_box[i][3]);
     if (t_per[i][0]) atomic_add64(peri + 2 * l, (long long)t_per[i][0]);
     if (t_per[i][1]) atomic_add64(peri + 2 * l + 1, (long long)t_per[i][1]);
   }
@@ -202,58 +170,27 @@ __global__ void label_features_kernel(const long long *__restrict__ count, const
 }
 
 // ---- adjacency: open-addressing table keyed by a * S + b (a < b), value = number of shared pixel edges --------------------
-// (the table itself: dm_table.h)
+// (the table itself, the tile's LDS table in front of it and the launch sequence: dm_raster.h)
 template <bool VEC>
 __global__ __launch_bounds__(256) void rag_edges_kernel(const int *__restrict__ labels, int H, int W, int S, long long *__restrict__ keys,
                                                         int *__restrict__ cnt, unsigned mask, int *__restrict__ overflow) {
-  // same 64x64 tiling as label_stats_kernel: pairs are first counted in an LDS-private table, then every distinct pair of the
-  // tile is added to the global table once
-  __shared__ long long e_key[ESLOTS];
-  __shared__ int e_cnt[ESLOTS];
-  for (int i = threadIdx.x; i < ESLOTS; i += blockDim.x) { e_key[i] = EMPTY_KEY; e_cnt[i] = 0; }
-  __syncthreads();
-  const int tiles_x = (W + 63) / 64;
-  const int ty = blockIdx.x / tiles_x, tx = blockIdx.x - ty * tiles_x;
-  auto tile_add = [&](long long key, int c) {
-    unsigned slot = (unsigned)mix64((unsigned long long)key) & (ESLOTS - 1);
-    for (int probe = 0; probe < ESLOTS; ++probe) {
-      const long long seen = (long long)atomicCAS(reinterpret_cast<unsigned long long *>(&e_key[slot]), (unsigned long long)EMPTY_KEY,
-                                                  (unsigned long long)key);
-      if (seen == EMPTY_KEY || seen == key) { atomicAdd(&e_cnt[slot], c); return; }
-      slot = (slot + 1) & (ESLOTS - 1);
-    }
-    table_add(keys, cnt, mask, key, c, overflow);            // tile table full: straight to the global table
-  };
+  __shared__ TileTable<ESLOTS_LOG2> pairs;                       // the tile's pairs, each added to the global table once
+  pairs.clear();
   {
-    const int y = ty * 64 + (threadIdx.x >> 2), x0 = tx * 64 + (threadIdx.x & 3) * STRIP;
-    const bool live = y < H && x0 < W;
-    const int n = live ? min(STRIP, W - x0) : 0;
-    const int *row = labels + (long long)(live ? y : 0) * W;
+    const Strip g = strip_of(H, W);
+    const int n = g.n;
     int lab[STRIP + 1], dn[STRIP];
-    if (VEC && n == STRIP) {
-#pragma unroll
-      for (int v = 0; v < STRIP / 4; ++v) {
-        const i32x4 a = *reinterpret_cast<const i32x4 *>(row + x0 + 4 * v);
-        const i32x4 d = (y + 1 < H) ? *reinterpret_cast<const i32x4 *>(row + W + x0 + 4 * v) : (i32x4){-2, -2, -2, -2};
-#pragma unroll
-        for (int e = 0; e < 4; ++e) { lab[4 * v + e] = a[e]; dn[4 * v + e] = d[e]; }
-      }
-    } else {
-#pragma unroll
-      for (int i = 0; i < STRIP; ++i) {
-        lab[i] = (i < n) ? row[x0 + i] : -2;
-        dn[i] = (i < n && y + 1 < H) ? row[x0 + i + W] : -2;
-      }
-    }
-    lab[STRIP] = (live && x0 + STRIP < W) ? row[x0 + STRIP] : -2;
-    if (n < STRIP) lab[n] = (live && x0 + n < W) ? row[x0 + n] : -2;
+    load_strip<VEC>(labels, g.base, n, -2, lab);                 // -2 = outside the raster
+    load_strip<VEC>(labels, g.base + W, n, -2, dn, g.y + 1 < H);
+    lab[STRIP] = (g.live && g.x0 + STRIP < W) ? labels[g.base + STRIP] : -2;
+    if (n < STRIP) lab[n] = (g.live && g.x0 + n < W) ? labels[g.base + n] : -2;
     long long run_key = EMPTY_KEY;
     int run_cnt = 0;
     auto emit = [&](int a, int b) {
       if (a == b || a < 0 || b < 0 || a >= S || b >= S) return;
       const long long key = (long long)min(a, b) * S + max(a, b);
       if (key == run_key) { ++run_cnt; return; }
-      if (run_cnt) tile_add(run_key, run_cnt);
+      if (run_cnt) pairs.add(run_key, run_cnt, keys, cnt, mask, overflow);
       run_key = key; run_cnt = 1;
     };
 #pragma unroll
@@ -262,11 +199,9 @@ __global__ __launch_bounds__(256) void rag_edges_kernel(const int *__restrict__ 
 #pragma unroll
     for (int i = 0; i < STRIP; ++i)
       if (i < n) emit(lab[i], lab[i + 1]);           // (ids < 0, incl. the -2 "outside" marker, are dropped by emit)
-    if (run_cnt) tile_add(run_key, run_cnt);
+    if (run_cnt) pairs.add(run_key, run_cnt, keys, cnt, mask, overflow);
   }
-  __syncthreads();
-  for (int i = threadIdx.x; i < ESLOTS; i += blockDim.x)
-    if (e_key[i] != EMPTY_KEY) table_add(keys, cnt, mask, e_key[i], e_cnt[i], overflow);
+  pairs.flush(keys, cnt, mask, overflow);
 }
 
 }  // namespace
@@ -279,7 +214,7 @@ extern "C" int dm_label_stats(const int32_t *labels, const uint8_t *tile, int32_
   const int nb = bands < 3 ? bands : 3;
   hipLaunchKernelGGL(rag_init_kernel, dim3((S + 255) / 256), dim3(256), 0, s, (long long *)count, (long long *)sum, (long long *)sumsq, bbox,
                      (long long *)peri, S, nb);
-  const dim3 grid((unsigned)(((W + 63) / 64) * ((H + 63) / 64)));     // one workgroup per 64x64-pixel tile
+  const dim3 grid = tile_grid(H, W);
   // 16-byte strip loads need W % 16 == 0 and 16-byte aligned rasters
   const bool vec = (W % STRIP == 0) && dm_aligned16(labels) && dm_aligned16(tile);
 #define DM_STATS(NB_)                                                                                                                      \
@@ -314,18 +249,8 @@ extern "C" int dm_rag_edges(const int32_t *labels, int32_t H, int32_t W, int32_t
   DM_REQUIRE(labels && table_keys && table_counts && edge_keys && edge_counts && n_edges && overflow, DM_ERR_BAD_SHAPE, "dm_rag_edges: null pointer");
   DM_REQUIRE(H > 0 && W > 0 && S > 0 && capacity_log2 >= 8 && capacity_log2 <= 30 && max_edges > 0, DM_ERR_BAD_SHAPE,
              "dm_rag_edges: bad sizes (H=%d W=%d S=%d capacity_log2=%d)", H, W, S, capacity_log2);
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  const long long cap = 1LL << capacity_log2;
-  hipLaunchKernelGGL(table_clear_kernel, dim3(grid_for(cap, 2048)), dim3(256), 0, s, (long long *)table_keys, table_counts, cap, overflow, n_edges);
-  const dim3 tgrid((unsigned)(((W + 63) / 64) * ((H + 63) / 64)));
-  if (W % STRIP == 0 && dm_aligned16(labels))
-    hipLaunchKernelGGL(rag_edges_kernel<true>, tgrid, dim3(256), 0, s, labels, H, W, S, (long long *)table_keys, table_counts,
-                       (unsigned)(cap - 1), overflow);
-  else
-    hipLaunchKernelGGL(rag_edges_kernel<false>, tgrid, dim3(256), 0, s, labels, H, W, S, (long long *)table_keys, table_counts,
-                       (unsigned)(cap - 1), overflow);
-  hipLaunchKernelGGL(table_compact_kernel, dim3(grid_for(cap, 2048)), dim3(256), 0, s, (const long long *)table_keys, table_counts, cap,
-                     (long long *)edge_keys, edge_counts, n_edges, max_edges);
+  run_tile_table(rag_edges_kernel<true>, rag_edges_kernel<false>, W % STRIP == 0 && dm_aligned16(labels), reinterpret_cast<hipStream_t>(stream), H, W,
+                 table_keys, table_counts, capacity_log2, edge_keys, edge_counts, max_edges, n_edges, overflow, labels, H, W, S);
   DM_LAUNCH_CHECK("dm_rag_edges");
   return DM_OK;
 }
@@ -370,7 +295,7 @@ extern "C" int dm_merge_round(const int32_t *edges, const uint8_t *merge, int32_
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   if (init) hipLaunchKernelGGL(uf_init_kernel, dim3((S + 255) / 256), dim3(256), 0, s, parent, S);
   hipMemsetAsync(changed, 0, sizeof(int32_t), s);
-  if (E > 0) hipLaunchKernelGGL(uf_hook_kernel, dim3(grid_for(E, 2048)), dim3(256), 0, s, edges, merge, E, S, parent, changed);
+  if (E > 0) hipLaunchKernelGGL(uf_hook_kernel, dim3(grid_for(E)), dim3(256), 0, s, edges, merge, E, S, parent, changed);
   hipLaunchKernelGGL(uf_compress_kernel, dim3((S + 255) / 256), dim3(256), 0, s, parent, S);
   DM_LAUNCH_CHECK("dm_merge_round");
   return DM_OK;

@@ -7,59 +7,26 @@
 // Every quantity is an integer and every reduction an integer add / max, so the result does not depend on the order in which
 // threads arrive: the GPU and the numpy spec agree bit for bit.  No floating point anywhere in this file.
 //
-// dm_label_overlap has dm_rag.hip's structure: a workgroup owns a 64x64-pixel tile, a thread a 16-pixel strip of one row of BOTH
-// rasters (16-byte loads: 64 B of labels + 64 B of truth), run-length merged; the tile's cells are counted in an LDS-private
-// table (integer LDS atomics) and each distinct cell of the tile then costs ONE add into the global table (dm_table.h).
-#include "dm_common.h"
-#include "dm_table.h"
+// dm_label_overlap is a pass on dm_raster.h's tile walk over BOTH rasters (64 B of labels + 64 B of truth per strip), run-length
+// merged; the tile's cells are counted in its TileTable and from there in the global table.
+#include "dm_raster.h"
 
 namespace {
 
-typedef unsigned long long u64;
-
-constexpr int STRIP = 16;
-constexpr int CSLOTS_LOG2 = 7, CSLOTS = 1 << CSLOTS_LOG2;      // cells per 64x64 tile kept in LDS (more: global table directly)
+constexpr int CSLOTS_LOG2 = 7;                                 // 128 cells per 64x64 tile kept in LDS (more: global table directly)
 
 template <bool VEC>
 __global__ __launch_bounds__(256) void label_overlap_kernel(const int *__restrict__ labels, const int *__restrict__ truth, int H, int W, long long S,
                                                             long long G, long long *__restrict__ keys, int *__restrict__ cnt, unsigned mask,
                                                             int *__restrict__ overflow) {
-  __shared__ long long c_key[CSLOTS];
-  __shared__ int c_cnt[CSLOTS];
-  for (int i = threadIdx.x; i < CSLOTS; i += blockDim.x) { c_key[i] = EMPTY_KEY; c_cnt[i] = 0; }
-  __syncthreads();
-  const int tiles_x = (W + 63) / 64;
-  const int ty = blockIdx.x / tiles_x, tx = blockIdx.x - ty * tiles_x;
-  auto tile_add = [&](long long key, int c) {
-    unsigned slot = (unsigned)mix64((u64)key) & (CSLOTS - 1);
-    for (int probe = 0; probe < CSLOTS; ++probe) {
-      const long long seen = (long long)atomicCAS(reinterpret_cast<u64 *>(&c_key[slot]), (u64)EMPTY_KEY, (u64)key);
-      if (seen == EMPTY_KEY || seen == key) { atomicAdd(&c_cnt[slot], c); return; }
-      slot = (slot + 1) & (CSLOTS - 1);
-    }
-    table_add(keys, cnt, mask, key, c, overflow);              // tile table full: straight to the global table
-  };
+  __shared__ TileTable<CSLOTS_LOG2> cells;
+  cells.clear();
   {
-    const int y = ty * 64 + (threadIdx.x >> 2), x0 = tx * 64 + (threadIdx.x & 3) * STRIP;
-    const bool live = y < H && x0 < W;
-    const int n = live ? min(STRIP, W - x0) : 0;
-    const long long base = (long long)(live ? y : 0) * W + (live ? x0 : 0);
+    const Strip g = strip_of(H, W);
+    const int n = g.n;
     int lab[STRIP], tru[STRIP];
-    if (VEC && n == STRIP) {
-#pragma unroll
-      for (int v = 0; v < STRIP / 4; ++v) {
-        const i32x4 a = *reinterpret_cast<const i32x4 *>(labels + base + 4 * v);
-        const i32x4 t = *reinterpret_cast<const i32x4 *>(truth + base + 4 * v);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) { lab[4 * v + e] = a[e]; tru[4 * v + e] = t[e]; }
-      }
-    } else {
-#pragma unroll
-      for (int i = 0; i < STRIP; ++i) {
-        lab[i] = (i < n) ? labels[base + i] : -1;
-        tru[i] = (i < n) ? truth[base + i] : -1;
-      }
-    }
+    load_strip<VEC>(labels, g.base, n, -1, lab);
+    load_strip<VEC>(truth, g.base, n, -1, tru);
     const long long cols = G + 1;
     long long run_key = EMPTY_KEY;
     int run_cnt = 0;
@@ -70,14 +37,12 @@ __global__ __launch_bounds__(256) void label_overlap_kernel(const int *__restric
       // ids outside [0,S) are ignored; any truth value outside [0,G) is the "unlabelled" column G
       const long long key = (l >= 0 && l < S) ? (long long)l * cols + ((t >= 0 && t < G) ? (long long)t : G) : EMPTY_KEY;
       if (key == run_key) { ++run_cnt; continue; }
-      if (run_key != EMPTY_KEY) tile_add(run_key, run_cnt);
+      if (run_key != EMPTY_KEY) cells.add(run_key, run_cnt, keys, cnt, mask, overflow);
       run_key = key; run_cnt = 1;
     }
-    if (run_key != EMPTY_KEY) tile_add(run_key, run_cnt);
+    if (run_key != EMPTY_KEY) cells.add(run_key, run_cnt, keys, cnt, mask, overflow);
   }
-  __syncthreads();
-  for (int i = threadIdx.x; i < CSLOTS; i += blockDim.x)        // one global add per distinct cell of the tile
-    if (c_key[i] != EMPTY_KEY) table_add(keys, cnt, mask, c_key[i], c_cnt[i], overflow);
+  cells.flush(keys, cnt, mask, overflow);
 }
 
 // ---- row / column facts and the summary from the compacted cells -----------------------------------------------------------
@@ -91,13 +56,11 @@ __global__ void reduce_init_kernel(u64 *__restrict__ row_best, long long *__rest
   }
 }
 
-__device__ __forceinline__ void add64(long long *p, long long v) { atomicAdd(reinterpret_cast<u64 *>(p), (u64)v); }
-
 // Sum over the wave, then one atomic per wave (lane 0).
 __device__ __forceinline__ void wave_add64(long long *p, long long v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  if ((threadIdx.x & 63) == 0 && v) add64(p, v);
+  if ((threadIdx.x & 63) == 0 && v) atomic_add64(p, v);
 }
 
 __global__ __launch_bounds__(256) void overlap_cells_kernel(const long long *__restrict__ keys, const int *__restrict__ counts, int K, long long S, long long G,
@@ -113,11 +76,11 @@ __global__ __launch_bounds__(256) void overlap_cells_kernel(const long long *__r
     const long long s = key / cols;
     const long long g = key - s * cols;
     if (s >= S) continue;
-    add64(area + s, c);
+    atomic_add64(area + s, c);
     if (g < G) {
-      add64(row_labelled + s, c);
+      atomic_add64(row_labelled + s, c);
       atomicMax(row_best + s, ((u64)c << 32) | (u64)(0xFFFFFFFFu - (unsigned)g));
-      add64(size + g, c);
+      atomic_add64(size + g, c);
       atomicMax(cover + g, (int)c);
       n += c; sq += c * c;
     }
@@ -184,19 +147,10 @@ extern "C" int dm_label_overlap(const int32_t *labels, const int32_t *truth, int
              (long long)S, (long long)G, capacity_log2, max_cells);
   DM_REQUIRE(key_bound_ok(S, G), DM_ERR_BAD_SHAPE, "dm_label_overlap: key bound exceeded (S=%lld G=%lld; need S*(G+1) < 2^62)", (long long)S,
              (long long)G);
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  const long long cap = 1LL << capacity_log2;
-  hipLaunchKernelGGL(table_clear_kernel, dim3(grid_for(cap, 2048)), dim3(256), 0, s, (long long *)table_keys, table_counts, cap, overflow, n_cells);
-  const dim3 tgrid((unsigned)(((W + 63) / 64) * ((H + 63) / 64)));     // one workgroup per 64x64-pixel tile
   // 16-byte strip loads need W % 16 == 0 and 16-byte aligned rasters
-  if (W % STRIP == 0 && dm_aligned16(labels) && dm_aligned16(truth))
-    hipLaunchKernelGGL(label_overlap_kernel<true>, tgrid, dim3(256), 0, s, labels, truth, H, W, (long long)S, (long long)G, (long long *)table_keys, table_counts,
-                       (unsigned)(cap - 1), overflow);
-  else
-    hipLaunchKernelGGL(label_overlap_kernel<false>, tgrid, dim3(256), 0, s, labels, truth, H, W, (long long)S, (long long)G, (long long *)table_keys, table_counts,
-                       (unsigned)(cap - 1), overflow);
-  hipLaunchKernelGGL(table_compact_kernel, dim3(grid_for(cap, 2048)), dim3(256), 0, s, (const long long *)table_keys, table_counts, cap,
-                     (long long *)cell_keys, cell_counts, n_cells, max_cells);
+  const bool vec = W % STRIP == 0 && dm_aligned16(labels) && dm_aligned16(truth);
+  run_tile_table(label_overlap_kernel<true>, label_overlap_kernel<false>, vec, reinterpret_cast<hipStream_t>(stream), H, W, table_keys, table_counts,
+                 capacity_log2, cell_keys, cell_counts, max_cells, n_cells, overflow, labels, truth, H, W, (long long)S, (long long)G);
   DM_LAUNCH_CHECK("dm_label_overlap");
   return DM_OK;
 }
@@ -211,11 +165,11 @@ extern "C" int dm_overlap_reduce(const int64_t *cell_keys, const int32_t *cell_c
   DM_REQUIRE(key_bound_ok(S, G), DM_ERR_BAD_SHAPE, "dm_overlap_reduce: key bound exceeded (S=%lld G=%lld; need S*(G+1) < 2^62)", (long long)S,
              (long long)G);
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  const dim3 rgrid(grid_for(S > G ? S : G, 2048));
+  const dim3 rgrid(grid_for(S > G ? S : G));
   hipLaunchKernelGGL(reduce_init_kernel, rgrid, dim3(256), 0, s, (u64 *)row_best, (long long *)row_labelled, (long long *)area, (long long *)size,
                      cover, (long long *)summary, (long long)S, (long long)G);
   if (K > 0)
-    hipLaunchKernelGGL(overlap_cells_kernel, dim3(grid_for(K, 2048)), dim3(256), 0, s, (const long long *)cell_keys, cell_counts, K, (long long)S, (long long)G,
+    hipLaunchKernelGGL(overlap_cells_kernel, dim3(grid_for(K)), dim3(256), 0, s, (const long long *)cell_keys, cell_counts, K, (long long)S, (long long)G,
                        (u64 *)row_best, (long long *)row_labelled, (long long *)area, (long long *)size, cover, (long long *)summary);
   hipLaunchKernelGGL(overlap_finish_kernel, rgrid, dim3(256), 0, s, (const u64 *)row_best, (const long long *)row_labelled, (const long long *)size,
                      cover, (long long)S, (long long)G, owner, owner_count, (long long *)summary);
@@ -229,7 +183,7 @@ extern "C" int dm_pair_flags(const int32_t *edges, int32_t E, const int64_t *are
   DM_REQUIRE(E >= 0 && S > 0, DM_ERR_BAD_SHAPE, "dm_pair_flags: bad sizes (E=%d S=%d)", E, S);
   DM_REQUIRE(purity_pm >= 0 && purity_pm <= 1000, DM_ERR_BAD_SHAPE, "dm_pair_flags: purity_pm = %d outside 0..1000", purity_pm);
   if (E == 0) return DM_OK;
-  hipLaunchKernelGGL(pair_flags_kernel, dim3(grid_for(E, 2048)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), edges, E,
+  hipLaunchKernelGGL(pair_flags_kernel, dim3(grid_for(E)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), edges, E,
                      (const long long *)area, owner, owner_count, S, purity_pm, (signed char *)flags);
   DM_LAUNCH_CHECK("dm_pair_flags");
   return DM_OK;

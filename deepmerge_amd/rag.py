@@ -55,30 +55,41 @@ def designed_features(stats: Dict[str, torch.Tensor]) -> torch.Tensor:
     return feat
 
 
+def _count_keys(dev, n_labels: int, max_out: int, what: str, noun: str, call) -> Tuple[torch.Tensor, torch.Tensor]:
+    """One pass that counts 64-bit keys in a device hash table (csrc/dm_raster.h): sizes the table for at most max_out distinct
+    keys (0: max(1024, 8 n_labels)), runs call(table keys, table counts, log2 of the slots, out keys, out counts, max_out, n,
+    overflow) -- the eight arguments dm_rag_edges and dm_label_overlap share, as data pointers and ints -- and returns (keys int64
+    [n], counts int32 [n]) sorted by key.  One readback (n, overflow)."""
+    max_out = int(max_out) or max(1024, 8 * n_labels)
+    log2 = max(10, (4 * max_out - 1).bit_length())               # load factor <= 1/4
+    if log2 > 30:
+        raise ValueError(f"max_{noun} = {max_out} needs a table of more than 2^30 slots")
+    tk = torch.empty(1 << log2, dtype=torch.int64, device=dev)
+    tc = torch.empty(1 << log2, dtype=torch.int32, device=dev)
+    ok = torch.empty(max_out, dtype=torch.int64, device=dev)
+    oc = torch.empty(max_out, dtype=torch.int32, device=dev)
+    meta = torch.empty(2, dtype=torch.int32, device=dev)
+    call(tk.data_ptr(), tc.data_ptr(), log2, ok.data_ptr(), oc.data_ptr(), max_out, meta.data_ptr(), meta[1:].data_ptr())
+    n, overflow = (int(v) for v in meta.tolist())
+    if overflow or n > max_out:
+        raise RuntimeError(f"{what} has more than max_{noun}={max_out} {noun} (found {n}, table overflow={bool(overflow)}); "
+                           f"pass a larger max_{noun}")
+    order = torch.argsort(ok[:n])                                # canonical order; keys are unique
+    return ok[:n][order], oc[:n][order]
+
+
 def rag_edges(labels: torch.Tensor, n_labels: int, max_edges: int = 0) -> Tuple[torch.Tensor, torch.Tensor]:
-    """(edges int32 [E,2] with a < b, sorted by (a, b); shared boundary length int32 [E] in pixel edges)."""
+    """(edges int32 [E,2] with a < b, sorted by (a, b); shared boundary length int32 [E] in pixel edges).  max_edges (default
+    max(1024, 8 n_labels): a planar graph has E <= 3 S - 6, and 8 S leaves room for raster artefacts) bounds the number of edges."""
     _need_cuda(labels)
     if labels.dtype != torch.int32 or labels.dim() != 2:
         raise ValueError("labels must be int32 [H,W]")
     labels = labels.contiguous()
     H, W = labels.shape
-    dev = labels.device
-    max_edges = max_edges or max(1024, 8 * n_labels)          # planar graph: E <= 3 S - 6; 8 S leaves room for raster artefacts
-    log2 = max(10, (4 * max_edges - 1).bit_length())          # load factor <= 1/4
-    keys = torch.empty(1 << log2, dtype=torch.int64, device=dev)
-    cnts = torch.empty(1 << log2, dtype=torch.int32, device=dev)
-    ek = torch.empty(max_edges, dtype=torch.int64, device=dev)
-    ec = torch.empty(max_edges, dtype=torch.int32, device=dev)
-    meta = torch.empty(2, dtype=torch.int32, device=dev)
-    check(_lib.lib().dm_rag_edges(labels.data_ptr(), H, W, n_labels, keys.data_ptr(), cnts.data_ptr(), log2, ek.data_ptr(), ec.data_ptr(),
-                                  max_edges, meta.data_ptr(), meta[1:].data_ptr(), _stream()), "dm_rag_edges")
-    n, overflow = (int(v) for v in meta.tolist())
-    if overflow or n > max_edges:
-        raise RuntimeError(f"RAG has more than max_edges={max_edges} edges (found {n}, table overflow={bool(overflow)}); pass a larger max_edges")
-    order = torch.argsort(ek[:n])                             # canonical order; keys are unique
-    k = ek[:n][order]
+    k, w = _count_keys(labels.device, n_labels, max_edges, "RAG", "edges", lambda *table: check(
+        _lib.lib().dm_rag_edges(labels.data_ptr(), H, W, n_labels, *table, _stream()), "dm_rag_edges"))
     edges = torch.stack((k // n_labels, k % n_labels), 1).to(torch.int32)
-    return edges, ec[:n][order]
+    return edges, w
 
 
 def points_to_csr(labels: torch.Tensor, xy: torch.Tensor, n_labels: int) -> Tuple[torch.Tensor, torch.Tensor]:
@@ -559,24 +570,10 @@ def label_overlap(labels: torch.Tensor, truth: torch.Tensor, n_labels: int, n_tr
         raise ValueError(f"need n_labels >= 1, 1 <= n_truth < 2^31 and n_labels * (n_truth + 1) < 2^62, got {n_labels}, {n_truth}")
     labels, truth = labels.contiguous(), truth.contiguous()
     H, W = labels.shape
-    dev = labels.device
-    max_cells = int(max_cells) or max(1024, 8 * S)                # a region straddles a few objects; 8 S leaves room for ragged truth
-    log2 = max(10, (4 * max_cells - 1).bit_length())             # load factor <= 1/4
-    if log2 > 30:
-        raise ValueError(f"max_cells = {max_cells} needs a table of more than 2^30 slots")
-    tk = torch.empty(1 << log2, dtype=torch.int64, device=dev)
-    tc = torch.empty(1 << log2, dtype=torch.int32, device=dev)
-    ck = torch.empty(max_cells, dtype=torch.int64, device=dev)
-    cc = torch.empty(max_cells, dtype=torch.int32, device=dev)
-    meta = torch.empty(2, dtype=torch.int32, device=dev)
-    check(_lib.lib().dm_label_overlap(labels.data_ptr(), truth.data_ptr(), H, W, S, G, tk.data_ptr(), tc.data_ptr(), log2, ck.data_ptr(),
-                                      cc.data_ptr(), max_cells, meta.data_ptr(), meta[1:].data_ptr(), _stream()), "dm_label_overlap")
-    n, overflow = (int(v) for v in meta.tolist())
-    if overflow or n > max_cells:
-        raise RuntimeError(f"the overlap table has more than max_cells={max_cells} cells (found {n}, table overflow={bool(overflow)}); "
-                           f"pass a larger max_cells")
-    order = torch.argsort(ck[:n])                                 # canonical order; keys are unique
-    return _overlap_facts(ck[:n][order], cc[:n][order], S, G)
+    # default max_cells: a region straddles a few objects; 8 S leaves room for ragged truth
+    keys, counts = _count_keys(labels.device, S, max_cells, "the overlap table", "cells", lambda *table: check(
+        _lib.lib().dm_label_overlap(labels.data_ptr(), truth.data_ptr(), H, W, S, G, *table, _stream()), "dm_label_overlap"))
+    return _overlap_facts(keys, counts, S, G)
 
 
 def pair_flags(edges: torch.Tensor, overlap: Overlap, min_purity: float = 0.6) -> torch.Tensor:

@@ -93,6 +93,16 @@ def test_unaligned_raster_and_more_labels_than_table_slots():
             assert_equals_spec(rag.sample_points(view, 3000, k=k), R.sample_points(lab, 3000, k))
 
 
+def test_more_labels_than_one_scan_tile():
+    """5000 labels: the emit's exclusive scan walks two tiles of 4096 counts, the second one partly filled, and carries the first
+    tile's total into it."""
+    from deepmerge_amd import rag
+    lab = np.random.default_rng(5).integers(0, 5000, (96, 128)).astype(np.int32)
+    ref = R.sample_points(lab, 5000, 3)
+    assert ref["ptr"][4096] == 8457 and ref["ptr"][5000] == 10289
+    assert_equals_spec(rag.sample_points(dev(lab), 5000, k=3), ref)
+
+
 def test_two_runs_are_identical_and_a_side_stream_works():
     from deepmerge_amd import rag
     lab, S = raster(300, 420, 17, 5, holes=True)

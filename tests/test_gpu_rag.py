@@ -27,16 +27,33 @@ def superpixels(H, W, cell, seed):
     return lab, gy * gx
 
 
-@pytest.mark.parametrize("H,W,cell,bands", [(64, 80, 9, 3), (257, 301, 13, 4), (1024, 1024, 29, 1), (33, 17, 40, 2)])
+def offset_view(a, off):
+    """A device copy of `a` that starts `off` elements into a larger buffer: contiguous, 16-byte aligned only if off says so."""
+    buf = torch.zeros(a.size + 16, dtype=torch.from_numpy(a).dtype, device=DEV)
+    v = buf[off:off + a.size].view(*a.shape)
+    v.copy_(torch.from_numpy(a).to(DEV))
+    assert v.data_ptr() % 16 == (a.itemsize * off) % 16 and v.is_contiguous()
+    return v
+
+
+@pytest.mark.parametrize("H,W,cell,bands", [(64, 80, 9, 3), (257, 301, 13, 4), (1024, 1024, 29, 1), (33, 17, 40, 2),
+                                            (64, 64, 0, 3)])         # cell 0: per-pixel noise labels, see below
 def test_rag_and_features_match_oracle(H, W, cell, bands):
     from deepmerge_amd import rag
-    lab, S = superpixels(H, W, cell, H + W)
-    S += 3                                                   # a few ids that never occur
     rng = np.random.default_rng(1)
+    if cell:
+        lab, S = superpixels(H, W, cell, H + W)
+        S += 3                                               # a few ids that never occur
+    else:
+        # 2567 labels and 8045 distinct pairs in ONE 64x64 tile: both LDS tables (64 labels, 128 pairs) run full, so nearly
+        # every add takes the fall-through to global memory; the pairs still fit the default max_edges = 8 S
+        lab, S = np.random.default_rng(4).integers(0, 4096, (H, W)).astype(np.int32), 4096
     tile = rng.integers(0, 256, (bands, H, W), dtype=np.uint8)
     want_e, want_w = OR.rag_edges(lab, S)
     want_st = OR.label_stats(lab, tile, S)
     want_f = OR.designed_features(want_st)
+    if not cell:
+        assert len(want_e) > 3000 and (want_st["count"] > 0).sum() > 64
     tl, tt = torch.from_numpy(lab).to(DEV), torch.from_numpy(tile).to(DEV)
     edges, w = rag.rag_edges(tl, S)
     assert np.array_equal(edges.cpu().numpy(), want_e) and np.array_equal(w.cpu().numpy(), want_w)
@@ -47,6 +64,23 @@ def test_rag_and_features_match_oracle(H, W, cell, bands):
     assert np.array_equal(f, want_f)
     edges2, w2 = rag.rag_edges(tl, S)                        # insertion order varies; the result must not
     assert torch.equal(edges, edges2) and torch.equal(w, w2)
+
+
+def test_unaligned_rasters_take_the_scalar_loads():
+    """W % 16 == 0, so only the alignment of the label raster and of the image tile decides between the 16-byte strip loads
+    (offset 0 of both) and the scalar ones (every other case)."""
+    from deepmerge_amd import rag
+    lab, S = superpixels(96, 128, 9, 30)
+    tile = np.random.default_rng(2).integers(0, 256, (3, 96, 128), dtype=np.uint8)
+    want_e, want_w = OR.rag_edges(lab, S)
+    want_st = OR.label_stats(lab, tile, S)
+    for off_l, off_t in ((0, 0), (1, 0), (3, 0), (0, 1), (0, 3)):
+        tl, tt = offset_view(lab, off_l), offset_view(tile, off_t)
+        edges, w = rag.rag_edges(tl, S)
+        assert np.array_equal(edges.cpu().numpy(), want_e) and np.array_equal(w.cpu().numpy(), want_w), (off_l, off_t)
+        st = rag.label_stats(tl, tt, S)
+        for k in ("count", "sum", "sumsq", "bbox", "peri"):
+            assert np.array_equal(st[k].cpu().numpy(), want_st[k]), (k, off_l, off_t)
 
 
 def test_rag_rejects_small_capacity_and_bad_input():
