@@ -101,6 +101,17 @@ class FeatureIO:
         return result, pts
 
     @torch.no_grad()
+    def segment_tile(self, tile: torch.Tensor, cell: int = 29, compactness: int = 10, iters: int = 10, min_size: Optional[int] = None,
+                     **merge_tile_kwargs):
+        """From an image tile alone to the merged partition: rag.slic(tile, cell, compactness, iters, min_size) followed by
+        merge_tile(tile, labels, n_labels, **merge_tile_kwargs).  Returns (MergeResult, PointSamples, labels, n_labels), where
+        labels / n_labels are the SLIC superpixels the merge started from."""
+        from . import rag
+        labels, n_labels = rag.slic(tile, cell=cell, compactness=compactness, iters=iters, min_size=min_size)
+        result, pts = self.merge_tile(tile, labels, n_labels, **merge_tile_kwargs)
+        return result, pts, labels, n_labels
+
+    @torch.no_grad()
     def _extract_local(self, tile, points_xy, inner, obj, region_features, batch_size):
         from .patches import point_batch_cols
         P = points_xy.shape[0]

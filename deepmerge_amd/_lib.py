@@ -162,6 +162,10 @@ SIGNATURES = {
     "dm_label_overlap": (_I, [_P, _P, _I, _I, _L, _L, _P, _P, _I, _P, _P, _I, _P, _P, _P]),
     "dm_overlap_reduce": (_I, [_P, _P, _I, _L, _L, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "dm_pair_flags": (_I, [_P, _I, _P, _P, _P, _I, _I, _P, _P]),
+    "dm_slic_iterate": (_I, [_P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P]),
+    "dm_connected_labels": (_I, [_P, _I, _I, _I, _I, _P, _P, _P, _P, _P]),
+    "dm_label_area": (_I, [_P, _I, _I, _I, _P, _P]),
+    "dm_slic_absorb_pick": (_I, [_P, _P, _I, _P, _I, _I, _P, _P, _P, _P]),
     "dm_gru_cell_fwd": (_I, [_P, _L, _P, _P, _P, _P, _I, _I, _P]),
     "dm_gru_cell_bwd": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _P]),
     "dm_prof_enable": (_I, [_I]),

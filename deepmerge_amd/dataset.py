@@ -241,7 +241,8 @@ class PairDataset:
         """A dataset from tiles, their over-segmentations and ground-truth maps alone -- no pair lists, no shapefiles.
         images: one dict per training image:
           tile            uint8 [bands, H, W]
-          labels, n_labels   int32 [H, W] superpixel ids 0..n_labels-1 (others ignored)
+          labels, n_labels   int32 [H, W] superpixel ids 0..n_labels-1 (others ignored); without a `labels` key the tile is
+                             segmented with rag.slic(tile, **im.get("slic", {})) (slic: a dict of its keyword arguments)
           truth, n_truth     int32 [H, W] object ids 0..n_truth-1 (any other value: unlabelled)
         (arrays or tensors).  Per image, on the device: rag.label_stats -> designed_features -> rag_edges -> sample_points(k,
         max_window) -> label_overlap -> pair_flags(min_purity); the points become xy / inner / obj / polygon_points, the designed
@@ -257,7 +258,11 @@ class PairDataset:
         train, val = [], []
         with torch.cuda.device(dev):
             for t, im in enumerate(images):
-                tile, labels, truth, S = up(im["tile"]), up(im["labels"]), up(im["truth"]), int(im["n_labels"])
+                tile, truth = up(im["tile"]), up(im["truth"])
+                if "labels" in im:
+                    labels, S = up(im["labels"]), int(im["n_labels"])
+                else:
+                    labels, S = rag.slic(tile, **im.get("slic", {}))
                 designed = rag.designed_features(rag.label_stats(labels, tile, S))
                 edges, _ = rag.rag_edges(labels, S)
                 pts = rag.sample_points(labels, S, k=k, max_window=max_window)

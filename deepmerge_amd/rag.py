@@ -593,3 +593,119 @@ def pair_flags(edges: torch.Tensor, overlap: Overlap, min_purity: float = 0.6) -
                                    overlap.owner_count.data_ptr(), min(overlap.n_labels, (1 << 31) - 1), int(round(float(min_purity) * 1000)),
                                    flags.data_ptr() if E else None, _stream()), "dm_pair_flags")
     return flags
+
+
+# ---- SLIC superpixels and 4-connected components (csrc/dm_slic.hip; the rule: include/deepmerge_hip.h) ---------
+def connected_labels(raster: torch.Tensor, background: Optional[int] = None) -> Tuple[torch.Tensor, int]:
+    """(labels int32 [H,W], n): the 4-connected components of equal values of an int32 raster, numbered 0..n-1 in the order of
+    their first pixel in raster-scan order.  Pixels equal to `background` get -1 and belong to no component (a class raster's
+    "no object" value).  The input is not modified.  One readback (n)."""
+    _need_cuda(raster)
+    if raster.dtype != torch.int32 or raster.dim() != 2 or raster.numel() < 1:
+        raise ValueError("raster must be int32 [H,W] with at least one pixel")
+    if raster.numel() >= 1 << 31:
+        raise ValueError(f"connected_labels takes rasters of fewer than 2^31 pixels, got {raster.numel()}")
+    if background is not None and not -(1 << 31) <= int(background) < 1 << 31:
+        raise ValueError(f"background must be an int32 value or None, got {background}")
+    raster = raster.contiguous()
+    H, W = raster.shape
+    dev, i32 = raster.device, torch.int32
+    parent = torch.empty(H * W, dtype=i32, device=dev)
+    chunks = torch.empty((H * W + 4095) // 4096 + 1, dtype=i32, device=dev)
+    labels = torch.empty((H, W), dtype=i32, device=dev)
+    n = torch.empty(1, dtype=i32, device=dev)
+    check(_lib.lib().dm_connected_labels(raster.data_ptr(), H, W, int(background is not None), int(background or 0), parent.data_ptr(),
+                                         chunks.data_ptr(), labels.data_ptr(), n.data_ptr(), _stream()), "dm_connected_labels")
+    return labels, int(n)
+
+
+def _check_slic(tile: torch.Tensor, cell: int, compactness: int, iters: int, min_size: Optional[int]) -> int:
+    _need_cuda(tile)
+    if tile.dtype != torch.uint8 or tile.dim() != 3 or tile.numel() < 1:
+        raise ValueError("tile must be uint8 [bands,H,W] with at least one band and one pixel")
+    if tile.shape[1] * tile.shape[2] >= 1 << 31:
+        raise ValueError(f"slic takes rasters of fewer than 2^31 pixels, got {tile.shape[1] * tile.shape[2]}")
+    if not 4 <= int(cell) <= 256:
+        raise ValueError(f"cell must be in 4..256, got {cell}")
+    if not 0 <= int(compactness) <= 255:
+        raise ValueError(f"compactness must be in 0..255, got {compactness}")
+    if int(iters) < 0:
+        raise ValueError(f"iters must be >= 0, got {iters}")
+    min_size = max(1, int(cell) * int(cell) // 4) if min_size is None else int(min_size)
+    if min_size < 1:
+        raise ValueError(f"min_size must be >= 1, got {min_size}")
+    return min_size
+
+
+def slic_assign(tile: torch.Tensor, cell: int = 29, compactness: int = 10, iters: int = 10) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Steps 1-3 of the SLIC rule: (centre id of every pixel int32 [H,W], final centres int32 [K,6] = y, x, band 0..3).  One call,
+    no readback: assignment, then `iters` times (update, assignment)."""
+    _check_slic(tile, cell, compactness, iters, None)
+    tile = tile.contiguous()
+    bands, H, W = tile.shape
+    K = ((H + cell - 1) // cell) * ((W + cell - 1) // cell)
+    dev = tile.device
+    centres = torch.empty((K, 6), dtype=torch.int32, device=dev)
+    sums = torch.empty((K, 7), dtype=torch.int64, device=dev)
+    labels = torch.empty((H, W), dtype=torch.int32, device=dev)
+    check(_lib.lib().dm_slic_iterate(tile.data_ptr(), bands, H, W, int(cell), int(compactness), int(iters), centres.data_ptr(),
+                                     sums.data_ptr(), labels.data_ptr(), _stream()), "dm_slic_iterate")
+    return labels, centres
+
+
+def label_area(labels: torch.Tensor, n_labels: int) -> torch.Tensor:
+    """int32 [n_labels]: pixels of every id 0..n_labels-1 (other ids are ignored)."""
+    _need_cuda(labels)
+    if labels.dtype != torch.int32 or labels.dim() != 2 or labels.numel() < 1 or labels.numel() >= 1 << 31 or n_labels < 1:
+        raise ValueError("labels must be int32 [H,W] with 1 <= H*W < 2^31 pixels, and n_labels >= 1")
+    labels = labels.contiguous()
+    area = torch.empty(int(n_labels), dtype=torch.int32, device=labels.device)
+    check(_lib.lib().dm_label_area(labels.data_ptr(), labels.shape[0], labels.shape[1], int(n_labels), area.data_ptr(), _stream()),
+          "dm_label_area")
+    return area
+
+
+def absorb_small(labels: torch.Tensor, n_labels: int, min_size: int, on_round=None) -> Tuple[torch.Tensor, int, int]:
+    """Step 5 of the SLIC rule on a raster of connected regions 0..n_labels-1 numbered by first pixel: (labels, n, rounds).
+    Per round: rag_edges, one 64-bit max per small region (dm_slic_absorb_pick), merge_components over the picked edges,
+    relabel_raster; the areas are folded, not recounted.  A few small readbacks per round, as merge_regions has them.
+    on_round(round): called before every round (tools/mb_slic.py times the rounds with it)."""
+    n, rounds, dev, lib = int(n_labels), 0, labels.device, _lib.lib()
+    area = label_area(labels, n)
+    while n > 1:
+        if on_round is not None:
+            on_round(rounds)
+        edges, weights = rag_edges(labels, n)
+        E = edges.shape[0]
+        if E == 0:
+            break
+        best = torch.empty(n, dtype=torch.int64, device=dev)
+        merge = torch.empty(E, dtype=torch.uint8, device=dev)
+        picked = torch.empty(1, dtype=torch.int32, device=dev)
+        check(lib.dm_slic_absorb_pick(edges.data_ptr(), weights.data_ptr(), E, area.data_ptr(), n, int(min_size), best.data_ptr(),
+                                      merge.data_ptr(), picked.data_ptr(), _stream()), "dm_slic_absorb_pick")
+        if int(picked) == 0:
+            break
+        root = merge_components(edges, merge, n).long()
+        is_root = root == torch.arange(n, device=dev)
+        dense = torch.cumsum(is_root.to(torch.int64), 0) - 1      # a united region's first pixel is that of its smallest member
+        mapping = dense[root]
+        n_new = int(dense[-1]) + 1
+        area = torch.zeros(n_new, dtype=torch.int32, device=dev).index_add_(0, mapping, area)
+        labels = relabel_raster(labels, mapping.to(torch.int32))
+        n, rounds = n_new, rounds + 1
+    return labels, n, rounds
+
+
+def slic(tile: torch.Tensor, cell: int = 29, compactness: int = 10, iters: int = 10, min_size: Optional[int] = None) -> Tuple[torch.Tensor, int]:
+    """SLIC superpixels of an image tile (uint8 [bands,H,W], the first four bands are used): (labels int32 [H,W], n_labels), the
+    label raster every other call of this module starts from.  cell: the grid step, about the side of a superpixel (4..256);
+    compactness 0..255 weighs position against colour; iters: update rounds; min_size (default max(1, cell*cell // 4)): connected
+    regions smaller than this are absorbed into the neighbour they share the longest boundary with.  Regions are 4-connected and
+    numbered by first pixel.  Integer arithmetic throughout: the same input gives the same raster on every run (the rule:
+    include/deepmerge_hip.h, restated in numpy in tests/slic_ref.py)."""
+    min_size = _check_slic(tile, cell, compactness, iters, min_size)
+    assigned, _ = slic_assign(tile, cell, compactness, iters)
+    labels, n = connected_labels(assigned)
+    labels, n, _ = absorb_small(labels, n, min_size)
+    return labels, n

@@ -608,6 +608,49 @@ int dm_overlap_reduce(const int64_t *cell_keys, const int32_t *cell_counts, int3
 int dm_pair_flags(const int32_t *edges, int32_t E, const int64_t *area, const int32_t *owner, const int32_t *owner_count, int32_t S,
                   int32_t purity_pm, int8_t *flags, void *stream);
 
+/* ---- SLIC superpixels from an image tile, 4-connected component labelling (additive in ABI 6; csrc/dm_slic.hip, DESIGN.md 3.5.4,
+ * rag.slic / rag.connected_labels) ------------------------------------------------------------------------------------------------
+ * Produces, on the device, the over-segmentation the reference reads from shapefiles written by external GIS software.  The
+ * reference never defines it; the rule is this build's (restated in numpy in tests/slic_ref.py).  All arithmetic is on integers;
+ * nothing depends on the order in which threads arrive; results are bit-exact.
+ * The rule.  tile uint8 [bands,H,W], the first nb = min(bands, 4) bands are used; H*W < 2^31; 4 <= cell <= 256;
+ * 0 <= compactness <= 255; iters >= 0; min_size >= 1.
+ *   1. centres: gy = ceil(H / cell), gx = ceil(W / cell), K = gy*gx.  Centre c = j*gx + i starts at y = min(H-1, j*cell + cell/2),
+ *      x = min(W-1, i*cell + cell/2) with the colour of the pixel there.  Positions and colours are integers.
+ *   2. assignment: pixel (y, x) of grid cell (j, i) = (y / cell, x / cell) considers the up to 9 centres of the grid cells
+ *      (j+dj, i+di), dj, di in -1..1, inside the grid, and takes the one with the smallest
+ *        D = cell^2 * sum_b (p_b - c_b)^2 + compactness^2 * ((y - c_y)^2 + (x - c_x)^2);  ties go to the smaller centre id.
+ *      A centre of cell J owns pixels of the cells J-1..J+1 only, so a pixel and a candidate are less than 3 cell apart on either
+ *      axis and D <= cell^2 (nb 255^2 + 18 compactness^2): 32-bit arithmetic where that is below 2^32, 64-bit otherwise.
+ *   3. update: a centre with n >= 1 pixels becomes the rounded mean (2 sum + n) / (2 n) of their y, x and every band; a centre
+ *      without pixels stays.  The sequence is: assignment, then iters times (update, assignment).
+ *   4. components: the assignment is split into 4-connected components of equal label, numbered 0..n-1 in the order of their
+ *      first pixel in raster-scan order.
+ *   5. absorption, in rounds: with areas and shared boundary lengths (pixel edges, as dm_rag_edges counts them) as they are at the
+ *      start of the round, every region with area < min_size that has a neighbour picks the neighbour with the longest shared
+ *      boundary, ties to the smaller id: one unsigned 64-bit max of (weight << 32) | (0xFFFFFFFF - neighbour) per region.  The
+ *      picks are united (regions = connected components of the pick graph) and the regions renumbered by first pixel.  Rounds
+ *      repeat until none picks.  The number of small regions at least halves per round.
+ *   6. result: labels int32 [H,W] with ids 0..n-1, and n.
+ * Every entry point validates before any launch, launches on `stream`, never synchronises and never allocates.
+ *
+ * dm_slic_iterate: steps 1-3, the whole loop without a readback.  centres int32 [K,6] = y, x, band 0..3 (the final centres on
+ *   return), sums int64 [K,7] scratch, labels int32 [H,W] = the centre id of every pixel after the last assignment.
+ * dm_connected_labels: step 4 for any int32 raster.  use_background != 0: pixels equal to `background` belong to no component
+ *   and get -1.  Scratch: parent int32 [H*W], chunk_counts int32 [ceil(H*W / 4096) + 1].  labels int32 [H,W] (not the raster
+ *   itself), n_labels[0] = the number of components.
+ * dm_label_area: area int32 [S] = pixels of every id in [0,S) (cleared by the call); other ids are ignored.
+ * dm_slic_absorb_pick: the picks of one round of step 5 over E >= 1 edges (a < b, as dm_rag_edges yields them): best uint64 [S]
+ *   scratch, merge uint8 [E] = 1 iff one end of the edge picked the other, n_picked[0] = number of such edges.  All
+ *   (re)initialised by the call.  dm_merge_round over `merge` unites the picks; dm_relabel_raster applies them. */
+int dm_slic_iterate(const uint8_t *tile, int32_t bands, int32_t H, int32_t W, int32_t cell, int32_t compactness, int32_t iters,
+                    int32_t *centres, int64_t *sums, int32_t *labels, void *stream);
+int dm_connected_labels(const int32_t *raster, int32_t H, int32_t W, int32_t use_background, int32_t background, int32_t *parent,
+                        int32_t *chunk_counts, int32_t *labels, int32_t *n_labels, void *stream);
+int dm_label_area(const int32_t *labels, int32_t H, int32_t W, int32_t S, int32_t *area, void *stream);
+int dm_slic_absorb_pick(const int32_t *edges, const int32_t *weights, int32_t E, const int32_t *area, int32_t S, int32_t min_size,
+                        uint64_t *best, uint8_t *merge, int32_t *n_picked, void *stream);
+
 /* BatchNorm2d (+ ReLU, + Dropout2d mask) of the auxiliary heads (reference nets/ShfitScaleFormer.py:329-368: Conv2d ->
  * BatchNorm2d -> ReLU -> Dropout2d(0.3)) on the channels-last matrix the convolution GEMM produces: x, y fp32 [M, C] with
  * M = samples * rows_per_sample.  training != 0: batch statistics (biased variance, eps inside the sqrt), running_mean /
