@@ -142,6 +142,43 @@ class FeatureIO:
                 w.append(F[s:s + batch_size].float().cpu().numpy())
         return int(F.shape[0])
 
+    # -- the shapefiles the reference's loaders read (MyUtils1.py:60-114, MyUtils2.py:155-193), without GDAL: deepmerge_amd/shpstore.py --
+    @staticmethod
+    def save_shapefiles(folder: str, labels: torch.Tensor, n_labels: int, pts, designed: torch.Tensor, edges: Optional[torch.Tensor] = None,
+                        simi: Optional[torch.Tensor] = None, geotransform=None):
+        """Write a label raster as the three layers the reference reads: `polygons.shp` (one record per label: the 15 FEATURE_NAMES
+        fields from `designed` [n_labels,15] and `PointID`, the space-separated point indices of pts.ptr / pts.idx), `lines.shp` (one
+        record per boundary arc: LEFT_FID, RIGHT_FID, -1 = outside the raster, and `simi` when given: the value of the arc's row in
+        `edges`, 0.0 for LEFT_FID == -1) and `PointsGCS.shp` (one record per sample point of `pts`: inner, object).  FIDs are label,
+        arc and point indices.  Returns the three paths."""
+        import os
+        from . import rag, shpstore
+        if simi is not None and edges is None:
+            raise ValueError("simi needs edges: an arc finds its value through its row in `edges`")
+        if designed.dim() != 2 or tuple(designed.shape) != (n_labels, len(rag.FEATURE_NAMES)):
+            raise ValueError(f"designed must be [{n_labels},{len(rag.FEATURE_NAMES)}] (as designed_features returns it)")
+        if pts.ptr.numel() != n_labels + 1:
+            raise ValueError(f"pts.ptr must have n_labels + 1 = {n_labels + 1} entries")
+        polys, arcs = rag._trace(labels, n_labels)
+        os.makedirs(folder, exist_ok=True)
+        ptr, idx = pts.ptr.cpu().tolist(), pts.idx.cpu().tolist()
+        point_id = [" ".join(str(i) for i in idx[ptr[l]:ptr[l + 1]]) for l in range(n_labels)]
+        feats = designed.float().cpu().numpy()
+        fields = [(name, feats[:, i]) for i, name in enumerate(rag.FEATURE_NAMES)] + [("PointID", point_id)]
+        paths = [shpstore.write_polygons(os.path.join(folder, "polygons.shp"), polys, fields, geotransform)]
+        line_fields = [("LEFT_FID", arcs.left.cpu().numpy()), ("RIGHT_FID", arcs.right.cpu().numpy())]
+        if simi is not None:
+            if simi.numel() != edges.shape[0]:
+                raise ValueError(f"simi has {simi.numel()} values for {edges.shape[0]} edges")
+            row = rag._attach_edges(arcs, n_labels, edges).edge.long()
+            values = torch.where(row >= 0, simi.float()[row.clamp(min=0)], torch.zeros((), dtype=torch.float32, device=row.device)) \
+                if simi.numel() else torch.zeros(row.numel(), dtype=torch.float32)
+            line_fields.append(("simi", values.cpu().numpy()))
+        paths.append(shpstore.write_lines(os.path.join(folder, "lines.shp"), arcs, line_fields, geotransform))
+        paths.append(shpstore.write_points(os.path.join(folder, "PointsGCS.shp"), pts.xy.cpu().numpy(),
+                                           [("inner", pts.inner.cpu().numpy()), ("object", pts.obj.cpu().numpy())], geotransform))
+        return tuple(paths)
+
     def ReadFeatures(self, h5_file_path: str):
         """Open a feature store for GetFeaturesByID (ExtractFeatures.py:103-107)."""
         from .h5store import H5FeatureReader

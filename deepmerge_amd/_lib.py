@@ -79,6 +79,15 @@ class DmMergeFold(C.Structure):
                 ("hist_base", C.c_int32), ("hist_cap", C.c_int32)]
 
 
+class DmVectorTrace(C.Structure):
+    _fields_ = [("dart", C.c_void_p), ("next", C.c_void_p), ("lab", C.c_void_p), ("other", C.c_void_p), ("flags", C.c_void_p),
+                ("key", C.c_void_p), ("sum", C.c_void_p), ("ring_of_slot", C.c_void_p), ("ring_ptr", C.c_void_p),
+                ("arc_base", C.c_void_p), ("xy", C.c_void_p), ("area2", C.c_void_p),
+                ("arc_first", C.c_void_p), ("arc_left", C.c_void_p), ("arc_right", C.c_void_p), ("arc_vstart", C.c_void_p),
+                ("arc_count", C.c_void_p), ("arc_pos", C.c_void_p), ("arc_ptr", C.c_void_p), ("arc_xy", C.c_void_p),
+                ("W", C.c_int32), ("D", C.c_int32), ("R", C.c_int32), ("n_arcs", C.c_int32)]
+
+
 class DmProfRow(C.Structure):
     _fields_ = [("name", C.c_char * 64), ("launches", C.c_int64), ("total_ms", C.c_double),
                 ("total_flops", C.c_double), ("total_bytes", C.c_double)]
@@ -166,6 +175,14 @@ SIGNATURES = {
     "dm_connected_labels": (_I, [_P, _I, _I, _I, _I, _P, _P, _P, _P, _P]),
     "dm_label_area": (_I, [_P, _I, _I, _I, _P, _P]),
     "dm_slic_absorb_pick": (_I, [_P, _P, _I, _P, _I, _I, _P, _P, _P, _P]),
+    "dm_vector_count": (_I, [_P, _I, _I, _P, _P, _P, _P]),
+    "dm_vector_emit": (_I, [_P, _P, _I, _I, _P, _P, _P]),
+    "dm_vector_link": (_I, [_P, _P, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P, _P]),
+    "dm_vector_head_round": (_I, [_P, _P, _P, _P, _I, _P, _P]),
+    "dm_vector_rank_init": (_I, [_P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _I, _P]),
+    "dm_vector_rank_round": (_I, [_P, _P, _P, _P, _I, _P, _P]),
+    "dm_vector_ring_emit": (_I, [C.POINTER(DmVectorTrace), _P]),
+    "dm_vector_arc_emit": (_I, [C.POINTER(DmVectorTrace), _P]),
     "dm_gru_cell_fwd": (_I, [_P, _L, _P, _P, _P, _P, _I, _I, _P]),
     "dm_gru_cell_bwd": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _P]),
     "dm_prof_enable": (_I, [_I]),

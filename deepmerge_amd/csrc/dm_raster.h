@@ -1,4 +1,4 @@
-// What the passes over a label raster share (dm_rag.hip, dm_truth.hip, dm_points.hip, dm_merge.hip), each piece once:
+// What the passes over a label raster share (dm_rag.hip, dm_truth.hip, dm_points.hip, dm_merge.hip, dm_vector.hip), each piece once:
 //   - the tile walk: a workgroup of 256 threads owns a 64x64-pixel tile, a thread a 16-pixel strip of one row (Strip, load_strip);
 //   - the tile's LDS tables: 64-bit keys with counts in front of the global table (TileTable), label -> slot (claim_label_slot),
 //     bounding boxes (box_init / box_fold, on LDS and on global boxes alike);
@@ -176,9 +176,10 @@ constexpr int SCAN_THREADS = 1024, SCAN_ITEMS = 4, SCAN_TILE = SCAN_THREADS * SC
 
 __device__ __forceinline__ int shfl_up(int v, int o) { return __shfl_up(v, o, 64); }
 
-// Exclusive prefix of `v` over the workgroup's SCAN_THREADS threads (thread order) and the workgroup total.  T: int, or a struct
-// of ints with +, - and shfl_up.  lds: SCAN_THREADS / 64 entries; the first barrier lets the previous tile's readers finish.
-template <typename T>
+// Exclusive prefix of `v` over the workgroup's THREADS threads (thread order) and the workgroup total.  T: int, or a struct
+// of ints with +, - and shfl_up.  lds: THREADS / 64 entries; the first barrier lets the previous tile's readers finish.
+// THREADS = 256 scans the strips of a tile inside a tile kernel (dm_vector.hip).
+template <typename T, int THREADS = SCAN_THREADS>
 __device__ __forceinline__ T block_exclusive(T v, T *lds, T &total) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   T inc = v;
@@ -192,7 +193,7 @@ __device__ __forceinline__ T block_exclusive(T v, T *lds, T &total) {
   __syncthreads();
   T before{}, all{};
 #pragma unroll
-  for (int w = 0; w < SCAN_THREADS / 64; ++w) {
+  for (int w = 0; w < THREADS / 64; ++w) {
     const T t = lds[w];
     if (w < wave) before = before + t;
     all = all + t;

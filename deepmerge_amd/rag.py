@@ -8,6 +8,8 @@ The sample points, their `inner` / `object` window fields and point lists, which
 come from the label raster as well (csrc/dm_points.hip: `clearance`, `sample_points`; spec tests/points_ref.py).
 Against a ground-truth raster, `label_overlap` counts the overlap table once; `pair_flags` labels the RAG edges for training and
 `Overlap.coarsen(...).scores()` scores any merged partition (csrc/dm_truth.hip; spec tests/truth_ref.py).
+`polygons` and `boundary_arcs` trace a label raster into closed rings and boundary arcs, the geometry of the reference's polygon
+layer and `lines.shp` (csrc/dm_vector.hip; spec tests/vector_ref.py); deepmerge_amd/shpstore.py writes them as shapefiles.
 """
 from __future__ import annotations
 
@@ -200,6 +202,14 @@ class MergeResult:
                 parent = parent[parent]
         dense = torch.cumsum((parent == torch.arange(S0, device=parent.device)).to(torch.int64), 0) - 1
         return dense[parent].to(torch.int32)
+
+    def polygons(self, raster: torch.Tensor) -> "Polygons":
+        """The merged regions as polygon rings: `polygons(self.labels(raster), number of merged regions)`."""
+        return polygons(self.labels(raster), self.rep.numel())
+
+    def boundary_arcs(self, raster: torch.Tensor) -> "Arcs":
+        """The boundaries between the merged regions, `edge` = row of `self.edges`: `boundary_arcs(self.labels(raster), ...)`."""
+        return boundary_arcs(self.labels(raster), self.rep.numel(), edges=self.edges)
 
     def scores(self, overlap: "Overlap", round: Optional[int] = None) -> "PartitionScores":
         """The partition scored against a ground-truth map: `overlap` = label_overlap(superpixel raster, truth, S0, G), coarsened by
@@ -709,3 +719,195 @@ def slic(tile: torch.Tensor, cell: int = 29, compactness: int = 10, iters: int =
     labels, n = connected_labels(assigned)
     labels, n, _ = absorb_small(labels, n, min_size)
     return labels, n
+
+
+# ---- polygon rings and boundary arcs (csrc/dm_vector.hip; the rule: include/deepmerge_hip.h) ---------------------
+MAX_TRACE_PIXELS = 1 << 28        # dart ids 4 (y W + x) + side and the packed 64-bit keys stay below 2^30
+
+
+@dataclass
+class Polygons:
+    """What `polygons` leaves: the closed rings of every label, rings sorted by (label, smallest dart id).
+
+    region_ptr int32 [n_labels+1]: the rings of each label (an empty range for an absent id); ring_ptr int64 [R+1] into xy;
+    xy int32 [V,2]: corners (x, y), y down, a ring is not closed by repeating its first vertex; ring_label int32 [R];
+    ring_area2 int64 [R]: the shoelace sum, positive for an outer ring and negative for a hole."""
+    region_ptr: torch.Tensor
+    ring_ptr: torch.Tensor
+    xy: torch.Tensor
+    ring_label: torch.Tensor
+    ring_area2: torch.Tensor
+
+
+@dataclass
+class Arcs:
+    """What `boundary_arcs` leaves: one polyline per stretch of boundary between two labels, sorted by (right, left, first dart).
+
+    arc_ptr int64 [A+1] into xy; xy int32 [Va,2] (a closed arc repeats its first vertex at the end); right int32 [A]: the label on
+    the arc's right, left int32 [A]: the label on its left, greater than `right`, or -1 for the outside of the raster; edge int32
+    [A] or None: the row of (right, left) in the `edges` given (as rag_edges returns them), -1 for left == -1."""
+    arc_ptr: torch.Tensor
+    xy: torch.Tensor
+    left: torch.Tensor
+    right: torch.Tensor
+    edge: Optional[torch.Tensor] = None
+
+
+def _jump(call, bufs, D: int, changed: torch.Tensor, what: str, max_rounds: int = 32):
+    """Pointer-jumping rounds between two buffer sets (read one, write the other) until the device flag stays 0, as
+    merge_components repeats its rounds.  Returns (the set that holds the result, rounds run)."""
+    for r in range(max_rounds):
+        src, dst = bufs[r & 1], bufs[1 - (r & 1)]
+        check(call(src[0].data_ptr(), src[1].data_ptr(), dst[0].data_ptr(), dst[1].data_ptr(), D, changed.data_ptr(), _stream()), what)
+        if int(changed.item()) == 0:
+            return dst, r + 1
+    raise RuntimeError(f"{what} did not converge in {max_rounds} rounds")
+
+
+def _trace(labels: torch.Tensor, n_labels: int, stats: Optional[dict] = None) -> Tuple[Polygons, Arcs]:
+    """One tracing run for both results.  Readbacks: the label range, the number of darts D (it sizes everything that follows, so
+    there is no max_ parameter), one flag per jumping round, the numbers of rings, vertices and arcs.  stats: a dict that receives
+    D, the rounds, the time per stage and the bytes of the passes (tools/mb_vector.py)."""
+    _need_cuda(labels)
+    if labels.dtype != torch.int32 or labels.dim() != 2 or labels.numel() < 1:
+        raise ValueError("labels must be int32 [H,W] with at least one pixel")
+    if labels.numel() > MAX_TRACE_PIXELS:
+        raise ValueError(f"polygons / boundary_arcs take rasters of at most 2^28 pixels, got {labels.numel()}")
+    S = int(n_labels)
+    if not 1 <= S < 1 << 31:
+        raise ValueError(f"n_labels must be in 1..2^31-1, got {n_labels}")
+    labels = labels.contiguous()
+    lo, hi = (int(v) for v in torch.aminmax(labels))
+    if lo < 0 or hi >= S:
+        raise ValueError(f"labels must be in 0..n_labels-1 = 0..{S - 1}, found {lo}..{hi}")
+    H, W = labels.shape
+    dev, lib, i32, i64 = labels.device, _lib.lib(), torch.int32, torch.int64
+    new = lambda n, dt: torch.empty(n, dtype=dt, device=dev)
+    marks = []
+
+    def mark(stage):                                             # stage boundaries for tools/mb_vector.py; nothing when stats is None
+        if stats is not None:
+            e = torch.cuda.Event(enable_timing=True)
+            e.record()
+            marks.append((stage, e))
+    mark("start")
+    tiles = ((H + 63) // 64) * ((W + 63) // 64)
+    mask, tile_off, meta = new(H * W, torch.uint8), new(tiles + 1, i32), new(2, i32)
+    check(lib.dm_vector_count(labels.data_ptr(), H, W, mask.data_ptr(), tile_off.data_ptr(), meta.data_ptr(), _stream()), "dm_vector_count")
+    D = int(meta[0])
+    mark("count + scan + readback of D")
+    first_slot, dart = new(H * W, i32), new(D, i32)
+    check(lib.dm_vector_emit(mask.data_ptr(), tile_off.data_ptr(), H, W, first_slot.data_ptr(), dart.data_ptr(), _stream()), "dm_vector_emit")
+    nxt0, lab, other, flags = new(D, i32), new(D, i32), new(D, i32), new(D, torch.uint8)
+    keys, jumps = (new(D, i64), new(D, i64)), (nxt0, new(D, i32), new(D, i32))
+    check(lib.dm_vector_link(labels.data_ptr(), mask.data_ptr(), first_slot.data_ptr(), dart.data_ptr(), H, W, D, nxt0.data_ptr(),
+                             lab.data_ptr(), other.data_ptr(), flags.data_ptr(), keys[0].data_ptr(), _stream()), "dm_vector_link")
+    mark("emit + link")
+    # heads: round 0 reads (keys[0], next) and writes (keys[1], jumps[1]); `next` itself is never written again
+    changed = meta[1:]
+    check(lib.dm_vector_head_round(keys[0].data_ptr(), nxt0.data_ptr(), keys[1].data_ptr(), jumps[1].data_ptr(), D, changed.data_ptr(),
+                                   _stream()), "dm_vector_head_round")
+    key, head_rounds = keys[1], 1
+    if int(changed.item()):
+        (key, _), more = _jump(lib.dm_vector_head_round, [(keys[1], jumps[1]), (keys[0], jumps[2])], D, changed, "dm_vector_head_round")
+        head_rounds += more
+    del jumps
+    mark("head rounds")
+    # ranks
+    max_rings = D // 4 + 1
+    sums, nxts = (new(D, i64), new(D, i64)), (new(D, i32), new(D, i32))
+    ring_key, ring_slot, n_rings = new(max_rings, i64), new(max_rings, i32), new(1, i32)
+    check(lib.dm_vector_rank_init(key.data_ptr(), nxt0.data_ptr(), flags.data_ptr(), lab.data_ptr(), D, sums[0].data_ptr(), nxts[0].data_ptr(),
+                                  ring_key.data_ptr(), ring_slot.data_ptr(), n_rings.data_ptr(), max_rings, _stream()), "dm_vector_rank_init")
+    (total, _), rank_rounds = _jump(lib.dm_vector_rank_round, [(sums[0], nxts[0]), (sums[1], nxts[1])], D, changed, "dm_vector_rank_round")
+    R = int(n_rings)
+    mark("rank rounds")
+    # rings in (label, head) order; the tables over rings and arcs are small next to the darts
+    ring_key, order = torch.sort(ring_key[:R])
+    ring_slot = ring_slot[:R][order].long()
+    ring_of_slot = new(D, i32)
+    ring_of_slot[ring_slot] = torch.arange(R, dtype=i32, device=dev)
+    ring_total = total[ring_slot]
+    ring_ptr = torch.zeros(R + 1, dtype=i64, device=dev)
+    ring_ptr[1:] = torch.cumsum(ring_total >> 32, 0)
+    arc_base = torch.zeros(R + 1, dtype=i64, device=dev)
+    arc_base[1:] = torch.cumsum(torch.clamp(ring_total & 0xffffffff, min=1), 0)
+    V, n_arcs = (int(v) for v in torch.stack((ring_ptr[-1], arc_base[-1])).tolist())
+    arc_base = arc_base.to(i32)
+    xy, area2 = new((V, 2), i32), new(R, i64)
+    arc_first, arc_left, arc_right, arc_vstart, arc_count = (new(n_arcs, i32) for _ in range(5))
+    t = _lib.DmVectorTrace()
+    for name, tensor in (("dart", dart), ("next", nxt0), ("lab", lab), ("other", other), ("flags", flags), ("key", key), ("sum", total),
+                         ("ring_of_slot", ring_of_slot), ("ring_ptr", ring_ptr), ("arc_base", arc_base), ("xy", xy), ("area2", area2),
+                         ("arc_first", arc_first), ("arc_left", arc_left), ("arc_right", arc_right), ("arc_vstart", arc_vstart),
+                         ("arc_count", arc_count)):
+        setattr(t, name, tensor.data_ptr())
+    t.W, t.D, t.R, t.n_arcs = W, D, R, n_arcs
+    check(lib.dm_vector_ring_emit(ctypes.byref(t), _stream()), "dm_vector_ring_emit")
+    ring_label = (ring_key >> 32).to(i32)
+    region_ptr = torch.zeros(S + 1, dtype=i64, device=dev)
+    region_ptr[1:] = torch.cumsum(torch.bincount(ring_label.long(), minlength=S), 0)
+    polys = Polygons(region_ptr=region_ptr.to(i32), ring_ptr=ring_ptr, xy=xy, ring_label=ring_label, ring_area2=area2)
+    mark("ring tables (sort, scans) + ring_emit")
+    # arcs: keep one side of every boundary, order by (right, left, first dart) in two stable passes
+    kept = torch.nonzero((arc_left < 0) | (arc_left > arc_right)).squeeze(1)
+    low = ((arc_left[kept].long() + 1) << 30) | arc_first[kept].long()            # left + 1 < 2^31, dart ids < 2^30
+    by_low = torch.argsort(low)
+    by_right = torch.argsort(arc_right[kept][by_low], stable=True)
+    kept = kept[by_low][by_right]
+    A = kept.numel()
+    arc_pos = torch.full((n_arcs,), -1, dtype=i32, device=dev)
+    arc_pos[kept] = torch.arange(A, dtype=i32, device=dev)
+    arc_ptr = torch.zeros(A + 1, dtype=i64, device=dev)
+    arc_ptr[1:] = torch.cumsum(arc_count[kept].long(), 0)
+    arc_xy = new((int(arc_ptr[-1]), 2), i32)
+    t.arc_pos, t.arc_ptr, t.arc_xy = arc_pos.data_ptr(), arc_ptr.data_ptr(), arc_xy.data_ptr()
+    check(lib.dm_vector_arc_emit(ctypes.byref(t), _stream()), "dm_vector_arc_emit")
+    arcs = Arcs(arc_ptr=arc_ptr, xy=arc_xy, left=arc_left[kept], right=arc_right[kept])
+    mark("arc tables (two sorts, scan) + arc_emit")
+    if stats is not None:
+        torch.cuda.synchronize()
+        stats["stage_ms"] = [(b[0], a[1].elapsed_time(b[1])) for a, b in zip(marks[:-1], marks[1:])]
+        # bytes read + written by the passes over the raster and over the darts (the ring and arc tables are small beside them)
+        raster = H * W * (4 + 3 * 4 + 1) + H * W * (1 + 4) + 4 * D
+        link = D * (17 + 25)
+        rounds = (head_rounds + rank_rounds) * D * (24 + 12)
+        emit = D * (33 + 30) + 8 * (V + arc_xy.shape[0])
+        stats.update(D=D, rings=R, arcs=A, vertices=V, arc_vertices=int(arc_xy.shape[0]), head_rounds=head_rounds, rank_rounds=rank_rounds,
+                     bytes=raster + link + rounds + emit)
+    return polys, arcs
+
+
+def polygons(labels: torch.Tensor, n_labels: int) -> Polygons:
+    """The closed rings of every label of an int32 raster with ids 0..n_labels-1 (a label need not be connected, an id may be
+    absent; any other value raises).  H*W <= 2^28.  The rule: include/deepmerge_hip.h, restated in numpy in tests/vector_ref.py; every
+    array is bit-equal to it.  The input is not modified."""
+    return _trace(labels, n_labels)[0]
+
+
+def _attach_edges(arcs: Arcs, n_labels: int, edges: torch.Tensor) -> Arcs:
+    """Arcs.edge: the row of every arc's (right, left) pair in `edges`, -1 for left == -1."""
+    _need_cuda(edges)
+    if edges.dtype != torch.int32 or edges.dim() != 2 or edges.shape[1] != 2:
+        raise ValueError("edges must be int32 [E,2]")
+    S, inner = int(n_labels), arcs.left >= 0
+    edge = torch.full_like(arcs.left, -1)
+    if bool(inner.any()):
+        if edges.shape[0] == 0:
+            raise ValueError("boundary_arcs: the raster has boundaries between labels, but `edges` is empty")
+        ekeys = edges[:, 0].long() * S + edges[:, 1].long()
+        akeys = arcs.right.long()[inner] * S + arcs.left.long()[inner]
+        row = torch.searchsorted(ekeys, akeys).clamp(max=ekeys.numel() - 1)
+        if not bool((ekeys[row] == akeys).all()):
+            raise ValueError("boundary_arcs: an arc's (right, left) pair is not a row of `edges` (pass rag_edges of the same raster)")
+        edge[inner] = row.to(torch.int32)
+    arcs.edge = edge
+    return arcs
+
+
+def boundary_arcs(labels: torch.Tensor, n_labels: int, edges: Optional[torch.Tensor] = None) -> Arcs:
+    """The boundary arcs of the same tracing run: every unit boundary lies in exactly one arc.  edges int32 [E,2], sorted by (a, b)
+    (rag_edges of the same raster): `Arcs.edge` gets the row of every arc's (right, left) pair; a pair that is not in `edges`
+    raises."""
+    arcs = _trace(labels, n_labels)[1]
+    return arcs if edges is None else _attach_edges(arcs, n_labels, edges)

@@ -651,6 +651,77 @@ int dm_label_area(const int32_t *labels, int32_t H, int32_t W, int32_t S, int32_
 int dm_slic_absorb_pick(const int32_t *edges, const int32_t *weights, int32_t E, const int32_t *area, int32_t S, int32_t min_size,
                         uint64_t *best, uint8_t *merge, int32_t *n_picked, void *stream);
 
+/* ---- polygon rings and boundary arcs from a label raster (additive in ABI 6; csrc/dm_vector.hip, DESIGN.md 3.5.5,
+ * rag.polygons / rag.boundary_arcs) ----------------------------------------------------------------------------------------------
+ * Produces, on the device, the geometry the reference reads from shapefiles written by external GIS software (the polygon layer,
+ * MyUtils1.py:79-114; one polyline per shared boundary with LEFT_FID / RIGHT_FID, MyUtils2.py:155-193).  The reference never
+ * defines it; the rule is this build's (restated in numpy in tests/vector_ref.py).  All arithmetic is on integers; nothing depends
+ * on the order in which threads arrive; results are bit-exact.
+ * The rule.  labels int32 [H,W] with ids 0..S-1 (a label need not be connected; the caller checks the range), H*W <= 2^28.
+ *   Pixel (x, y) covers [x, x+1] x [y, y+1]; corners are (x, y), 0 <= x <= W, 0 <= y <= H, y down.
+ *   1. darts: a pixel has a dart on every side whose neighbour has another label or lies outside the raster; `other` is that
+ *      label, -1 outside.  Side 0 (top) runs east from (x, y), 1 (right) south from (x+1, y), 2 (bottom) west from (x+1, y+1),
+ *      3 (left) north from (x, y+1): the pixel lies on the dart's right.  dart id = 4 (y W + x) + side.
+ *   2. successor of a dart of label l that ends at corner c, with the two pixels ahead of c seen along the dart: ahead-right is
+ *      not l: side (side+1)&3 of the same pixel; else ahead-left is not l: the same side of the ahead-right pixel; else side
+ *      (side+3)&3 of the ahead-left pixel.  Right turns first: labels that touch diagonally are not joined (4-connectivity).
+ *      The successor map is a permutation of the darts.
+ *   3. rings: a ring is a cycle, its head the smallest dart id, its label l.  A vertex dart is one whose predecessor has another
+ *      side (the head is one).  The ring's vertices are the start corners of its vertex darts in cycle order from the head (not
+ *      closed).  area2 = the shoelace sum over the ring, int64: positive for an outer ring, negative for a hole.  Rings are
+ *      ordered by (label, head).
+ *   4. arcs: a break dart is one whose predecessor has another `other`.  A ring without one is one closed arc from its head;
+ *      otherwise an arc runs from a break dart to the last dart before the next.  Vertices: the start corner of the first dart,
+ *      the start corners of the later vertex darts, the end corner of the last dart.  Kept iff other == -1 or other > l, with
+ *      right = l, left = other; ordered by (right, left, id of the first dart).
+ * Slots: darts are stored compacted, D of them, in tile order.  Every entry point validates before any launch, launches on
+ * `stream`, never synchronises and never allocates; the caller reads back D, the round flags and the ring / arc counts, and sorts
+ * and scans the ring and arc tables between the calls (rag._trace).
+ *
+ * dm_vector_count: mask uint8 [H,W] = the 4-bit side mask of every pixel; tile_off int32 [tiles+1] (tiles = ceil(H/64) ceil(W/64)) =
+ *   exclusive scan of the darts per 64x64 tile, tile_off[tiles] = n_darts[0] = D.
+ * dm_vector_emit: first_slot int32 [H,W]: slot(dart) = first_slot[pixel] + popcount(mask & ((1 << side) - 1)); dart int32 [D].
+ * dm_vector_link: per slot next (successor slot), lab, other, flags uint8 (1 vertex dart, 2 break dart), key int64 = dart id << 32 | slot.
+ * dm_vector_head_round: key_out[i] = min(key_in[i], key_in[jump_in[i]]), jump_out[i] = jump_in[jump_in[i]]; changed[0] = 1 iff a
+ *   key changed (cleared by the call).  Start with jump_in = next; when changed stays 0, key & 0xffffffff is the slot of the ring's
+ *   head.  The buffers of a round are distinct.
+ * dm_vector_rank_init: sum int64 [D] = vertex flag << 32 | break flag, nxt int32 [D] = next, -1 in front of the head; the heads'
+ *   ring_key int64 = label << 32 | head dart id and ring_slot, in arrival order (the caller sorts them), n_rings[0] = R <= D / 4.
+ * dm_vector_rank_round: sum_out[i] = sum_in[i] + sum_in[nxt_in[i]], nxt_out[i] = nxt_in[nxt_in[i]]; changed[0] = 1 iff a nxt_out is
+ *   not -1.  When it stays 0, sum is the count of vertex / break darts from the dart to the end of its cut cycle.
+ * dm_vector_ring_emit: with ring_of_slot (ring index at every head slot), ring_ptr int64 [R+1] (scan of the rings' vertex counts,
+ *   sum[head] >> 32) and arc_base int32 [R+1] (scan of max(1, break darts of the ring)): xy int32 [V,2], area2 int64 [R], and per arc
+ *   of the unsorted arc table [n_arcs]: arc_first (dart id), arc_left, arc_right, arc_vstart (scratch), arc_count (vertices).
+ * dm_vector_arc_emit: with arc_pos int32 [n_arcs] (row of the arc among the kept, sorted arcs, -1 = dropped) and arc_ptr int64 [A+1]:
+ *   arc_xy int32 [Va,2]. */
+typedef struct DmVectorTrace {
+  const int32_t *dart, *next, *lab, *other;
+  const uint8_t *flags;
+  const int64_t *key, *sum;
+  const int32_t *ring_of_slot;
+  const int64_t *ring_ptr;
+  const int32_t *arc_base;
+  int32_t *xy;
+  int64_t *area2;
+  int32_t *arc_first, *arc_left, *arc_right, *arc_vstart, *arc_count;
+  const int32_t *arc_pos;
+  const int64_t *arc_ptr;
+  int32_t *arc_xy;
+  int32_t W, D, R, n_arcs;
+} DmVectorTrace;
+int dm_vector_count(const int32_t *labels, int32_t H, int32_t W, uint8_t *mask, int32_t *tile_off, int32_t *n_darts, void *stream);
+int dm_vector_emit(const uint8_t *mask, const int32_t *tile_off, int32_t H, int32_t W, int32_t *first_slot, int32_t *dart, void *stream);
+int dm_vector_link(const int32_t *labels, const uint8_t *mask, const int32_t *first_slot, const int32_t *dart, int32_t H, int32_t W,
+                   int32_t D, int32_t *next, int32_t *lab, int32_t *other, uint8_t *flags, int64_t *key, void *stream);
+int dm_vector_head_round(const int64_t *key_in, const int32_t *jump_in, int64_t *key_out, int32_t *jump_out, int32_t D, int32_t *changed,
+                         void *stream);
+int dm_vector_rank_init(const int64_t *key, const int32_t *next, const uint8_t *flags, const int32_t *lab, int32_t D, int64_t *sum,
+                        int32_t *nxt, int64_t *ring_key, int32_t *ring_slot, int32_t *n_rings, int32_t max_rings, void *stream);
+int dm_vector_rank_round(const int64_t *sum_in, const int32_t *nxt_in, int64_t *sum_out, int32_t *nxt_out, int32_t D, int32_t *changed,
+                         void *stream);
+int dm_vector_ring_emit(const DmVectorTrace *t, void *stream);
+int dm_vector_arc_emit(const DmVectorTrace *t, void *stream);
+
 /* BatchNorm2d (+ ReLU, + Dropout2d mask) of the auxiliary heads (reference nets/ShfitScaleFormer.py:329-368: Conv2d ->
  * BatchNorm2d -> ReLU -> Dropout2d(0.3)) on the channels-last matrix the convolution GEMM produces: x, y fp32 [M, C] with
  * M = samples * rows_per_sample.  training != 0: batch statistics (biased variance, eps inside the sqrt), running_mean /
