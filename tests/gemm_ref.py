@@ -1,0 +1,467 @@
+"""CPU side of the GEMM epilogue tests: the float64 spec of dm_gemm's fused epilogue, the data, the error bounds and the case table.
+
+Shared by tests/test_gemm_host.py (no GPU: pins the spec, the exactness of the data and the constants of the bounds) and
+tests/test_gpu_gemm_epilogues.py (every kernel family's epilogue against the spec).  numpy / torch float64 only.
+
+Spec (the order of dm_gemm_emit, deepmerge_amd/csrc/dm_gemm_common.h): v = acc + bias; GELU (the pre-activation v is saved first), GELU_GRAD (gelu'(v)
+is saved), DGELU (v *= gelu'(aux)) or MUL (v *= aux); + residual; + old C; rounding to c_dtype (DM_BF16_PAIR: hi = bf16(v),
+lo = bf16(v - hi)).  Row m of C / residual / aux lives at (m / rows_per_group) * group_stride + (m % rows_per_group) * ld (dm_gemm_row).
+
+Two classes of check.  EXACT: every configuration without a transcendental, and the saved pre-activation of GELU -- the data is built
+so that every intermediate is a float32 whatever the order of the additions and with or without fused multiply-add, so the kernel's
+result is compared bit for bit.  BOUNDED: GELU output, saved GELU' and DGELU, inside a bound derived below.
+"""
+import math
+
+import numpy as np
+import torch
+
+from rows_ref import C_BF16, U, UB, worst  # noqa: F401  (the rounding model and err / tol reduction of the row-kernel tests)
+
+F32, BF16, PAIR = "f32", "bf16", "pair"
+PAD_ROWS = 256          # rows of sentinel below M in every allocation
+VIEW_OFFSET = 8         # every view starts this many elements into its allocation
+GROUP_ROWS = 41         # rows_per_group of the grouped configurations: divides no tile, no 16-row MFMA tile, no 8-row item
+E_AS = 1.5e-7           # |erf error| of Abramowitz-Stegun 7.1.26 (the comment of dm_gelu_parts_fast, deepmerge_amd/csrc/dm_common.h)
+
+# ---- configurations --------------------------------------------------------------------------------------------------------------
+# aux: None (no operand), "null" (GELU without a saved operand: inference), or (dtype, "save" | "read")
+CONFIGS = (
+    dict(id=1, name="none_f32", epi="none", bias=False, res=False, aux=None, c=F32, acc=False, grouped=False),              # lean key 0,0,1,0
+    dict(id=2, name="none_bf16", epi="none", bias=False, res=False, aux=None, c=BF16, acc=False, grouped=False),            # 0,0,0,0
+    dict(id=3, name="bias_res_f32", epi="none", bias=True, res=True, aux=None, c=F32, acc=False, grouped=False),            # 1,0,1,0
+    dict(id=4, name="acc_f32", epi="none", bias=False, res=False, aux=None, c=F32, acc=True, grouped=False),                # 0,1,1,0
+    dict(id=5, name="bias_res_acc_f32", epi="none", bias=True, res=True, aux=None, c=F32, acc=True, grouped=False),         # run-time lean form
+    dict(id=6, name="gelu_bf16_nosave", epi="gelu", bias=True, res=False, aux="null", c=BF16, acc=False, grouped=False),    # 0,0,0,0 + GELU
+    dict(id=7, name="gelu_save_bf16", epi="gelu", bias=True, res=False, aux=(BF16, "save"), c=BF16, acc=False, grouped=False),          # 0,0,0,1
+    dict(id=8, name="gelugrad_save_bf16", epi="gelu_grad", bias=True, res=False, aux=(BF16, "save"), c=BF16, acc=False, grouped=False),  # 0,0,0,1
+    dict(id=9, name="gelu_save_f32", epi="gelu", bias=True, res=False, aux=(F32, "save"), c=F32, acc=False, grouped=False),  # run-time lean form
+    dict(id=10, name="mul_bf16", epi="mul", bias=False, res=False, aux=(BF16, "read"), c=BF16, acc=False, grouped=False),    # 0,2,0,0
+    dict(id=11, name="dgelu_f32_res", epi="dgelu", bias=False, res=True, aux=(F32, "read"), c=F32, acc=False, grouped=False),  # run-time lean form
+    dict(id=12, name="pair_gelu", epi="gelu", bias=True, res=False, aux=(BF16, "save"), c=PAIR, acc=False, grouped=False),   # run-time lean form
+    dict(id=13, name="grouped41", epi="none", bias=True, res=True, aux=None, c=F32, acc=False, grouped=True),                # lean form refused
+    dict(id=14, name="grouped41_gelugrad", epi="gelu_grad", bias=False, res=False, aux=(BF16, "save"), c=BF16, acc=False, grouped=True),
+)
+CONFIG = {c["name"]: c for c in CONFIGS}
+ALL = tuple(c["name"] for c in CONFIGS)
+
+
+def lean_key(cfg):
+    """dm_epi_lean_key restated: RES | YL << 1 | C32 << 3 | XS << 4, -1 for grouped rows, 1 << 8 for plane pairs."""
+    if cfg["grouped"]:
+        return -1
+    if cfg["c"] == PAIR:
+        return 1 << 8
+    aux = cfg["aux"] if isinstance(cfg["aux"], tuple) else None
+    c32 = cfg["c"] == F32
+    yl = 1 if (c32 and cfg["acc"]) else ((3 if aux[0] == F32 else 2) if aux and aux[1] == "read" else 0)
+    xs = (2 if aux[0] == F32 else 1) if aux and aux[1] == "save" else 0
+    return int(cfg["res"]) | (yl << 1) | (int(c32) << 3) | (xs << 4)
+
+
+SPECIALISED_KEYS = (0, 1 | (1 << 3), 1 << 3, (1 << 1) | (1 << 3), 1 << 4, 2 << 1)      # dm_epi_key_specialised
+
+# ---- families --------------------------------------------------------------------------------------------------------------------
+# The proposed shape is M, N, K = 328, 200, 192: 328 = 8 * 41 = 2 * 128 + 72 = 256 + 72 = 5 * 64 + 8, 200 = 128 + 72 = 192 + 8, three K steps
+# of 64.  Every family needs two tiles in M and in N, a last row of tiles with a partially filled wave block AND a wave block that starts
+# past M, an N tail (N % 8 == 0) that ends inside a wave's columns, and two or three K steps; where the proposal cannot give that, the
+# nearest shape that does is taken and the reason stands next to it.  `wave` = (rows, columns) of a wave's block, `tile` = (rows, columns)
+# of the workgroup's tile, `bk` = the K step.  `env`: the switches read_switches (deepmerge_amd/csrc/dm_gemm.hip) reads on every call; a key set to
+# None is removed from the environment.  `codes`: the `_t<code>` of the family's profiler row (prof_family_code), () = no row at all.
+_OFF = {"DM_GEMM_W4": "0", "DM_GEMM_Q4": "0", "DM_GEMM_RING": "0", "DM_GEMM_256": "0", "DM_GEMM_FORCE_TILE": "0", "DM_GEMM_RING_WM": None, "DM_GEMM_256P": None}
+_Q4_SKIPS = {
+    "bias_res_acc_f32": "dm_gemm_q4.hip dm_gemm_q4_plan: `if (!dm_epi_key_specialised(dm_epi_lean_key(p, 64))) return false` (residual + accumulate has no straight-line instance)",
+    "gelu_save_f32": "dm_gemm_q4.hip dm_gemm_q4_plan: `if (!dm_epi_key_specialised(...)) return false` (fp32 aux written)",
+    "dgelu_f32_res": "dm_gemm_q4.hip dm_gemm_q4_plan: `if (!dm_epi_key_specialised(...)) return false` (fp32 aux read + residual)",
+    "pair_gelu": "dm_gemm_q4.hip dm_gemm_q4_plan: `... || p.c_dtype == DM_BF16_PAIR) return false`",
+    "grouped41": "dm_gemm_q4.hip dm_gemm_q4_plan: `if (!dm_epi_key_specialised(...)) return false` (grouped rows: dm_epi_lean_key is -1)",
+    "grouped41_gelugrad": "dm_gemm_q4.hip dm_gemm_q4_plan: `if (!dm_epi_key_specialised(...)) return false` (grouped rows: dm_epi_lean_key is -1)",
+}
+_P256P_SKIPS = {name: "dm_gemm256.hip dm_gemm256_launch: `... && rows_ok && dm_epi_key_specialised(dm_epi_lean_key(p, 128))` (else the launch falls to gemm256_kernel, "
+                      "the p256 family; plane pairs: `p.c_dtype != DM_BF16_PAIR`)" for name in _Q4_SKIPS}
+_PAIR_F32 = {"pair_gelu": "dm_gemm.hip gemm_prepare: `a plane-pair result needs an NT / NN bf16 product ...` (ab_dtype == DM_BF16)"}
+_GENERIC_SKIPS = {name: "dm_gemm.hip gemm_generic: `a->ab_dtype == DM_F32 && a->c_dtype == DM_F32 && (a->aux == nullptr || a->aux_dtype == DM_F32)` (the generic path is fp32-only)"
+                  for name in ("none_bf16", "gelu_bf16_nosave", "gelu_save_bf16", "gelugrad_save_bf16", "mul_bf16", "pair_gelu", "grouped41_gelugrad")}
+_GENERIC_SKIPS["grouped41"] = "dm_gemm.hip gemm_generic: `DM_REQUIRE(a->rows_per_group == 0, ...)` (grouped rows need the MFMA path)"
+
+FAMILIES = {
+    # 64 x 64 tiles, a wave owns 32 x 32: rows 320 .. 351 are partially filled (8 rows), 352 .. 383 start past M
+    "t64": dict(ab=BF16, shape=(328, 200, 192), layouts=("NT", "NN"), tile=(64, 64), wave=(32, 32), bk=64, codes=(64,), fast=True,
+                env=dict(_OFF, DM_GEMM_FORCE_TILE="64"), skips={}),
+    # 128 x 128 tiles, a wave owns 64 x 64.  M = 328 leaves rows 256 .. 319 full and 320 .. 383 partial: no wave block starts past M.
+    # M = 296 = 2 * 128 + 40 = 7 * 41 + 9 is the nearest M (in steps of 8, towards fewer rows) whose last tile has both: 256 .. 319 partial, 320 .. 383 past M
+    "t128": dict(ab=BF16, shape=(296, 200, 192), layouts=("NT", "NN"), tile=(128, 128), wave=(64, 64), bk=64, codes=(128,), fast=True,
+                 env=dict(_OFF, DM_GEMM_FORCE_TILE="128"), skips={}),
+    # fp32 operands (exact erff GELU, dm_gemm_emit / the strips with FAST = false).  gemm_prepare sends fp32 products with fewer than 16 tiles
+    # of 128 x 128 to the generic path (`((M + BM - 1) / BM) * ((N + BN - 1) / BN) < 16`): N = 712 = 5 * 128 + 72 = 11 * 64 + 8 gives 18 and keeps
+    # the same N tail; the K step of the fp32 tiles is 32, so K = 96 is three steps
+    "f32_t64": dict(ab=F32, shape=(328, 712, 96), layouts=("NT", "NN"), tile=(64, 64), wave=(32, 32), bk=32, codes=(64,), fast=False,
+                    env=dict(_OFF, DM_GEMM_FORCE_TILE="64"), skips=_PAIR_F32),
+    "f32_t128": dict(ab=F32, shape=(296, 712, 96), layouts=("NT", "NN"), tile=(128, 128), wave=(64, 64), bk=32, codes=(128,), fast=False,
+                     env=dict(_OFF, DM_GEMM_FORCE_TILE="128"), skips=_PAIR_F32),     # M = 296: as for t128
+    # ring kernel (NT only), WM 8: 256 x 128 tiles, a wave owns 128 x 64: rows 256 .. 383 partial, 384 .. 511 past M
+    "ring8": dict(ab=BF16, shape=(328, 200, 192), layouts=("NT",), tile=(256, 128), wave=(128, 64), bk=64, codes=(2568,), fast=True,
+                  env=dict(_OFF, DM_GEMM_RING="2", DM_GEMM_RING_WM="8"), skips={}),
+    # WM 4: 128 x 128 tiles, a wave owns 64 x 64: M = 296 as for t128
+    "ring4": dict(ab=BF16, shape=(296, 200, 192), layouts=("NT",), tile=(128, 128), wave=(64, 64), bk=64, codes=(1288,), fast=True,
+                  env=dict(_OFF, DM_GEMM_RING="2", DM_GEMM_RING_WM="4"), skips={}),
+    # four workgroups per CU, 128 x 128 tiles, a wave owns 64 x 64; dm_gemm_q4_plan: `if (p.M % 64 != 0) return false` -> M = 320: rows 256 .. 319
+    # full, 320 .. 383 past M; only the straight-line epilogues
+    "q4": dict(ab=BF16, shape=(320, 200, 192), layouts=("NT", "NN"), tile=(128, 128), wave=(64, 64), bk=64, codes=(1284,), fast=True,
+               env=dict(_OFF, DM_GEMM_Q4="2"), skips=_Q4_SKIPS),
+    # 4-wave persistent kernel, 256 x 192 tiles, a wave pair owns 128 rows x 192 columns.  dm_gemm_w4_plan: `k_eff % (2 * bk_eff) != 0 || p.N % TN != 0`
+    # return 0 -> N = 384 (two tiles, no N tail exists for this family), K = 256 (four K steps, the smallest even count above two)
+    "w4": dict(ab=BF16, shape=(328, 384, 256), layouts=("NT", "NN"), tile=(256, 192), wave=(128, 192), bk=64, codes=(1924,), fast=True,
+               env=dict(_OFF, DM_GEMM_W4="2"), skips={}),
+    # 256 x 256 pipeline (one tile per workgroup), a wave owns 128 x 64: N = 200 is one tile, N = 328 = 256 + 72 is two with the same tail
+    "p256": dict(ab=BF16, shape=(328, 328, 192), layouts=("NT", "NN"), tile=(256, 256), wave=(128, 64), bk=64, codes=(256,), fast=True,
+                 env=dict(_OFF, DM_GEMM_256="2"), skips={}),
+    # the persistent form of the pipeline (DM_GEMM_256P = 2: every legal launch; read per call).  dm_gemm256_launch takes it only with
+    # `p.N % 256 == 0` -> N = 512 (two tiles, no N tail exists for this form) and `dm_epi_key_specialised(dm_epi_lean_key(p, 128))`; any other
+    # launch runs the one-tile-per-workgroup kernel above under the same code 256, which the row cannot tell apart, so those
+    # configurations are left to p256
+    "p256p": dict(ab=BF16, shape=(328, 512, 192), layouts=("NT", "NN"), tile=(256, 256), wave=(128, 64), bk=64, codes=(256,), fast=True,
+                  env=dict(_OFF, DM_GEMM_256="2", DM_GEMM_256P="2"), skips=_P256P_SKIPS),
+    # forward / dgrad K slices.  plan_fwd_split(M = 328, N = 200, K = 1536): N % 8 == 0 and K >= 1536; 3 * 2 = 6 tiles of 128 x 128 < 256; split = 4 gives
+    # K / 4 = 384 < 8 * 64, split = 2 gives 768 >= 512; 6 * 2 < 512 -> two slices on 64 x 64 tiles, summed and emitted by splitk_epilogue_kernel (dm_gemm_emit8).
+    # DM_GEMM_FORCE_TILE must be absent (`!sw.force_tile_set`); the row carries the tile, 64 -- the same code as unsplit 64 x 64 tiles, so the
+    # GPU test also prefills the call's split-K slab (workspace slot "gemm") with NaN and requires both slices of it to have been written
+    "kslices": dict(ab=BF16, shape=(328, 200, 1536), layouts=("NT", "NN"), tile=(64, 64), wave=(32, 32), bk=64, codes=(64,), fast=True,
+                    env=dict(_OFF, DM_GEMM_FORCE_TILE=None), skips={}),
+    # generic fp32 path by shape (K = 19: K % 4 != 0): 16 x 16 outputs per workgroup, one output per thread, no profiler row
+    "generic": dict(ab=F32, shape=(328, 200, 19), layouts=("NT", "NN"), tile=(16, 16), wave=(16, 16), bk=32, codes=(), fast=False,
+                    env=dict(_OFF), skips=_GENERIC_SKIPS),
+}
+
+
+# A finding of these tests, recorded rather than hidden: the 64 x 64 strips (dm_gemm_strip_load / dm_gemm_strip_store) add a ZERO vector for an
+# absent residual, so MUL's -0 (a zero accumulator times a negative aux) is stored as +0; every other form adds nothing and keeps -0, as the
+# spec does.  Numerically equal; only for these (family, configuration) pairs the bit comparison maps -0 to +0 first.  Everywhere else it
+# is strict.
+STRIP_ZERO_SIGN = (("t64", "mul_bf16"), ("f32_t64", "mul_bf16"))
+
+
+def plan_fwd_split(M, N, K):
+    """deepmerge_amd/csrc/dm_gemm.hip plan_fwd_split restated for NT / NN: (slices, tile)."""
+    if N % 8 != 0 or K < 1536:
+        return 1, 0
+    t128 = ((M + 127) // 128) * ((N + 127) // 128)
+    if t128 >= 256:
+        return 1, 0
+    split = 4
+    while split > 1 and K // split < 8 * 64:
+        split >>= 1
+    if split <= 1 or t128 * split >= 512:
+        return 1, 0
+    return split, 64
+
+
+def family_configs(family):
+    return tuple(n for n in ALL if n not in FAMILIES[family]["skips"])
+
+
+# ---- addressing and buffers --------------------------------------------------------------------------------------------------------
+def row_offsets(M, ld, rows_per_group=0, group_stride=0):
+    """dm_gemm_row restated: element offset of every output row."""
+    m = np.arange(M, dtype=np.int64)
+    if rows_per_group > 0:
+        return (m // rows_per_group) * group_stride + (m % rows_per_group) * ld
+    return m * ld
+
+
+def buffers(cfg, M, N):
+    """The allocation of every operand a configuration has: {"c" | "aux" | "res": dict(dtype, ld, elems, idx, written)} plus the grouped-row
+    arguments.  idx [M, N] = flat element index of output (m, n) inside the allocation (plane pairs: idx of the hi plane, "plane" = the lo
+    plane's distance).  Plain rows: ldc = N + 8, ldaux = N + 16, ldr = N + 24 (plane pairs: ldc = N, as gemm_prepare demands).  Grouped rows:
+    one leading dimension N + 8 for all three, because dm_gemm_row gives them one group_stride = 41 * ld + 64."""
+    out = {"rows_per_group": 0, "group_stride": 0}
+    if cfg["grouped"]:
+        ld = N + 8
+        rpg, gs = GROUP_ROWS, GROUP_ROWS * ld + 64
+        out.update(rows_per_group=rpg, group_stride=gs)
+        lds = {"c": ld, "aux": ld, "res": ld}
+        extent = ((M + rpg - 1) // rpg) * gs
+    else:
+        rpg = gs = 0
+        lds = {"c": N if cfg["c"] == PAIR else N + 8, "aux": N + 16, "res": N + 24}
+        extent = None
+    cols = np.arange(N, dtype=np.int64)[None, :]
+
+    def one(dtype, ld, written, pair=False):
+        ro = row_offsets(M, ld, rpg, gs)
+        if pair:
+            elems = VIEW_OFFSET + 2 * M * N + PAD_ROWS * ld
+        else:
+            elems = VIEW_OFFSET + (extent if extent is not None else M * ld) + PAD_ROWS * ld
+        d = dict(dtype=dtype, ld=ld, elems=int(elems), idx=VIEW_OFFSET + ro[:, None] + cols, written=written)
+        if pair:
+            d["plane"] = M * N
+        return d
+
+    out["c"] = one(BF16 if cfg["c"] == PAIR else cfg["c"], lds["c"], True, pair=cfg["c"] == PAIR)
+    if isinstance(cfg["aux"], tuple):
+        out["aux"] = one(cfg["aux"][0], lds["aux"], cfg["aux"][1] == "save")
+    if cfg["res"]:
+        out["res"] = one(F32, lds["res"], False)
+    return out
+
+
+# ---- data --------------------------------------------------------------------------------------------------------------------------
+def k_shift(K):
+    """Operands are integers in [-2, 2] (variance 2 each); A is scaled by 2^-shift so that the accumulator's spread is between 1 and 2."""
+    return max(0, math.ceil(math.log2(math.sqrt(4.0 * K) / 2.0)))
+
+
+_PLANT = (0.0, 6.0, -6.0, 5.5, -5.5, 0.015625, -0.015625, 1.0)      # bias of the first and the last eight columns
+
+
+def operands(M, N, K):
+    """Everything a case reads, as float64 numpy arrays (all exactly representable in bf16 resp. fp32; cached per shape):
+    a [M, K], b [N, K] small integers (a times 2^-shift), acc = a b^T; bias, res, old_c, aux_mul on the 2^-6 grid with |.| <= 2;
+    aux_dgelu on the 2^-6 grid over [-6.5, 6.5].  Rows 0 and M - 1 of a are zero, so those rows of the pre-activation are the bias, which
+    carries exact zeros, both signs and +-5.5 / +-6 (erf saturated in fp32) in its first and last eight columns."""
+    key = (M, N, K)
+    if key in _OPERANDS:
+        return _OPERANDS[key]
+    rng = np.random.default_rng(1000003 * M + 1009 * N + K)
+    a = rng.integers(-2, 3, size=(M, K)).astype(np.float64) * 2.0 ** -k_shift(K)
+    b = rng.integers(-2, 3, size=(N, K)).astype(np.float64)
+    a[0] = 0.0
+    a[M - 1] = 0.0
+    grid = lambda shape, lim: rng.integers(-lim, lim + 1, size=shape).astype(np.float64) / 64.0
+    bias = grid((N,), 128)
+    bias[:8] = _PLANT
+    bias[N - 8:] = _PLANT[::-1]
+    d = dict(a=a, b=b, acc=a @ b.T, bias=bias, res=grid((M, N), 128), old_c=grid((M, N), 128), aux_mul=grid((M, N), 128),
+             aux_dgelu=grid((M, N), 416))
+    d["aux_dgelu"][0, :8] = _PLANT
+    d["aux_dgelu"][M - 1, N - 8:] = _PLANT
+    for v in d.values():
+        v.setflags(write=False)
+    _OPERANDS[key] = d
+    return d
+
+
+_OPERANDS = {}
+
+
+def case(cfg, M, N, K):
+    """A configuration with the operand values it reads (the argument of epilogue_ref)."""
+    d = operands(M, N, K)
+    c = dict(cfg)
+    c["bias_v"] = d["bias"] if cfg["bias"] else None
+    c["res_v"] = d["res"] if cfg["res"] else None
+    c["old_c"] = d["old_c"] if cfg["acc"] else None
+    c["aux_v"] = None
+    if isinstance(cfg["aux"], tuple) and cfg["aux"][1] == "read":
+        c["aux_v"] = d["aux_mul"] if cfg["epi"] == "mul" else d["aux_dgelu"]
+    return c
+
+
+# ---- the spec ------------------------------------------------------------------------------------------------------------------------
+def gelu64(x):
+    x = np.asarray(x, dtype=np.float64)
+    return 0.5 * x * (1.0 + torch.special.erf(torch.from_numpy(x / math.sqrt(2.0))).numpy())
+
+
+def dgelu64(x):
+    x = np.asarray(x, dtype=np.float64)
+    cdf = 0.5 * (1.0 + torch.special.erf(torch.from_numpy(x / math.sqrt(2.0))).numpy())
+    return cdf + x * np.exp(-0.5 * x * x) / math.sqrt(2.0 * math.pi)
+
+
+def round_bf16(x):
+    """float64 -> nearest bf16 (ties to even), returned as float64.  Exact for the EXACT class, whose values are float32 already."""
+    return torch.from_numpy(np.ascontiguousarray(x, dtype=np.float64)).to(torch.float32).to(torch.bfloat16).to(torch.float64).numpy()
+
+
+def round_to(x, dtype):
+    if dtype == BF16:
+        return round_bf16(x)
+    return np.asarray(x, dtype=np.float64).astype(np.float32).astype(np.float64)
+
+
+def epilogue_ref(acc, cfg):
+    """What dm_gemm leaves in C and in aux for accumulator `acc` (float64) under `cfg` (see case()).  Returns a dict:
+    v     the unrounded result, float64                          c     v rounded to c_dtype (plane pairs: the hi plane)
+    c_lo  plane pairs: bf16(v - hi)                              pre   the pre-activation acc + bias (GELU-type epilogues)
+    aux_v the unrounded saved operand (saving epilogues)         aux   aux_v rounded to the aux dtype"""
+    v = np.array(acc, dtype=np.float64)
+    out = {}
+    if cfg["bias_v"] is not None:
+        v = v + cfg["bias_v"][None, :]
+    epi = cfg["epi"]
+    if epi == "gelu":
+        out["pre"] = v
+        if isinstance(cfg["aux"], tuple):
+            out["aux_v"] = v
+        v = gelu64(v)
+    elif epi == "gelu_grad":
+        out["pre"] = v
+        out["aux_v"] = dgelu64(v)
+        v = gelu64(v)
+    elif epi == "dgelu":
+        v = v * dgelu64(cfg["aux_v"])
+    elif epi == "mul":
+        v = v * cfg["aux_v"]
+    if cfg["res_v"] is not None:
+        v = v + cfg["res_v"]
+    if cfg["old_c"] is not None:
+        v = v + cfg["old_c"]
+    out["v"] = v
+    if cfg["c"] == PAIR:
+        out["c"] = round_bf16(v)
+        out["c_lo"] = round_bf16(v - out["c"])
+    else:
+        out["c"] = round_to(v, cfg["c"])
+    if "aux_v" in out:
+        out["aux"] = round_to(out["aux_v"], cfg["aux"][0])
+    return out
+
+
+def is_exact(cfg):
+    """(C exact, saved aux exact): compared bit for bit."""
+    return cfg["epi"] in ("none", "mul"), cfg["epi"] == "gelu"
+
+
+# ---- float32 restatements of the kernels' arithmetic ---------------------------------------------------------------------------------
+f32 = np.float32
+
+
+def _fma(a, b, c):
+    """fl32(a * b + c) with one rounding: the product of two float32 is exact in float64; the sum's float64 rounding is far below a float32 ulp."""
+    return (np.asarray(a, dtype=np.float64) * np.asarray(b, dtype=np.float64) + np.asarray(c, dtype=np.float64)).astype(f32)
+
+
+def gelu_parts_fast32(x):
+    """dm_gelu_parts_fast (deepmerge_amd/csrc/dm_common.h) operation by operation in float32; a correctly rounded exp2 and 1 / x stand in for v_exp_f32 and
+    v_rcp_f32 (__expf(x) is exp2(x * log2 e))."""
+    x = np.asarray(x, dtype=f32)
+    z = np.abs(x) * f32(0.70710678118654752440)
+    arg = (-(z * z)) * f32(1.4426950408889634)
+    e = np.exp2(arg.astype(np.float64)).astype(f32)
+    t = (1.0 / _fma(f32(0.3275911), z, f32(1.0)).astype(np.float64)).astype(f32)
+    poly = _fma(t, f32(1.061405429), f32(-1.453152027))
+    poly = _fma(t, poly, f32(1.421413741))
+    poly = _fma(t, poly, f32(-0.284496736))
+    poly = _fma(t, poly, f32(0.254829592))
+    poly = t * poly
+    erf_abs = _fma(-poly, e, f32(1.0))
+    cdf = f32(0.5) * (f32(1.0) + np.copysign(erf_abs, x))
+    pdf = f32(0.39894228040143267794) * e
+    return cdf, pdf
+
+
+def _erf32(x):
+    """A correctly rounded erff."""
+    return torch.special.erf(torch.from_numpy(np.asarray(x, dtype=f32).astype(np.float64))).numpy().astype(f32)
+
+
+def gelu32(x, fast):
+    x = np.asarray(x, dtype=f32)
+    if fast:
+        return x * gelu_parts_fast32(x)[0]                                            # dm_gelu_fast
+    return (f32(0.5) * x) * (f32(1.0) + _erf32(x * f32(0.70710678118654752440)))      # dm_gelu
+
+
+def dgelu32(x, fast):
+    x = np.asarray(x, dtype=f32)
+    if fast:
+        cdf, pdf = gelu_parts_fast32(x)
+        return _fma(x, pdf, cdf)                                                      # dm_dgelu_fast
+    cdf = f32(0.5) * (f32(1.0) + _erf32(x * f32(0.70710678118654752440)))
+    pdf = f32(0.39894228040143267794) * np.exp(((f32(-0.5) * x) * x).astype(np.float64)).astype(f32)
+    return cdf + x * pdf                                                              # dm_dgelu
+
+
+def restate32(acc, cfg, fast, order="left", fma=False):
+    """The epilogue in float32, operation by operation (unrounded-to-c_dtype result `v`, saved operand `aux_v`, both float32).
+    order = "left": ((acc + bias) ... + residual) + old C, the kernels' order; "right": the additive operands are summed first and joined
+    to the accumulator last (bias + (residual + old C) where no multiply stands between them).  fma: multiply-adds fused (one rounding)."""
+    v = np.asarray(acc, dtype=np.float64).astype(f32)
+    assert np.array_equal(v.astype(np.float64), acc), "the accumulator must be a float32"
+    g = lambda k: None if cfg[k] is None else np.asarray(cfg[k], dtype=np.float64).astype(f32)
+    bias, res, old, aux = g("bias_v"), g("res_v"), g("old_c"), g("aux_v")
+    out = {}
+    epi = cfg["epi"]
+    tail = [t for t in (res, old) if t is not None]
+    if epi == "none" and order == "right":
+        adds = ([np.broadcast_to(bias[None, :], v.shape)] if bias is not None else []) + tail
+        if adds:
+            s = adds[-1]
+            for t in adds[-2::-1]:
+                s = t + s
+            v = v + s
+        out["v"] = v
+        return out
+    if bias is not None:
+        v = v + bias[None, :]
+    if epi == "gelu":
+        out["aux_v"] = v
+        v = gelu32(v, fast)
+    elif epi == "gelu_grad":
+        out["aux_v"] = dgelu32(v, fast)
+        v = gelu32(v, fast)
+    mult = None
+    if epi == "dgelu":
+        mult = dgelu32(aux, fast)
+    elif epi == "mul":
+        mult = aux
+    if order == "right" and len(tail) == 2:
+        tail = [tail[0] + tail[1]]
+    if mult is not None:
+        if fma and tail:
+            v = _fma(v, mult, tail[0])
+            tail = tail[1:]
+        else:
+            v = v * mult
+    for t in tail:
+        v = v + t
+    out["v"] = v
+    return out
+
+
+# ---- bounds --------------------------------------------------------------------------------------------------------------------------
+# GELU, its derivative and DGELU are the only inexact steps.  With the fast parts (bf16-operand kernels) the error of the CDF is E_AS / 2 from
+# the polynomial plus about one U of rounding (the last fma and the halving are the only roundings at unit scale: t, the polynomial and
+# exp(-x^2 / 2) carry relative errors of a few U into a product poly * e <= 1); with erff (fp32 operands) it is the roundings alone.
+#     gelu(x)  = x cdf                      |error| <= C_G  D |x|                  D = E_AS / 2 + U  (fast)   or   U  (erff)
+#     gelu'(x) = cdf + x pdf                |error| <= C_D  D                      (|x pdf| <= 0.25 and its relative error (1 + x^2) U stay inside D)
+#     acc gelu'(aux) + res                  |error| <= C_DG (D |acc| + U |result|) (the factor's error scaled by |acc|; product and sum rounded once each)
+# A bf16 destination adds one rounding to 8 bits: tol + C_BF16 2^-8 (|value| + tol), the form of rows_ref.  Each constant is the smallest integer
+# for which the float32 restatement above stays at or below HALF the bound on the data of every case (tests/test_gemm_host.py asserts both
+# directions), so a correct kernel has a factor 2 to spare for the 1-ulp v_exp_f32 / v_rcp_f32 and the library's erff / expf.
+C = {(True, "gelu"): 3, (True, "dgelu"): 1, (True, "muld"): 4,           # fast parts: C_G, C_D, C_DG
+     (False, "gelu"): 3, (False, "dgelu"): 1, (False, "muld"): 5}        # erff / expf
+# (C_D: the derivative is only ever SAVED as bf16 in these configurations, so the rounding to 8 bits dominates its bound)
+
+
+def unit(fast):
+    return E_AS / 2 + U if fast else U
+
+
+def with_bf16(tol, value, dtype):
+    return tol + C_BF16 * UB * (np.abs(value) + tol) if dtype == BF16 else tol
+
+
+def bounds(cfg, ref, acc, fast, consts=None):
+    """{"c": tol or None, "aux": tol or None}: None where the class is EXACT (or nothing is stored)."""
+    k = dict(C) if consts is None else consts
+    D = unit(fast)
+    out = {"c": None, "aux": None}
+    epi = cfg["epi"]
+    cdt = BF16 if cfg["c"] == PAIR else cfg["c"]
+    if epi in ("gelu", "gelu_grad"):
+        tol = k[(fast, "gelu")] * D * np.abs(ref["pre"])
+        # plane pairs: hi + lo restores the fp32 result to 2^-16 relative (two roundings to 8 bits); the GPU test compares the SUM of the planes
+        out["c"] = tol + UB * UB * np.abs(ref["v"]) if cfg["c"] == PAIR else with_bf16(tol, ref["v"], cdt)
+        if epi == "gelu_grad":
+            out["aux"] = with_bf16(k[(fast, "dgelu")] * D * np.ones_like(ref["v"]), ref["aux_v"], cfg["aux"][0])
+    elif epi == "dgelu":
+        out["c"] = with_bf16(k[(fast, "muld")] * (D * np.abs(acc) + U * np.abs(ref["v"])), ref["v"], cdt)
+    return out
+
+
+def family_cases(family):
+    """(layout, config name) of everything a family runs."""
+    return [(lay, n) for lay in FAMILIES[family]["layouts"] for n in family_configs(family)]

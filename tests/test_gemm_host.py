@@ -1,0 +1,260 @@
+"""No GPU: the spec, the data, the bounds and the case table of the GEMM epilogue tests (tests/gemm_ref.py) are pinned here.
+
+  * epilogue_ref equals the same thing built from torch float64 operators (F.gelu, autograd for GELU');
+  * every EXACT configuration is exact on these inputs: the float32 restatement equals the float64 spec bit for bit in both association
+    orders and with or without fused multiply-add;
+  * every BOUNDED configuration's float32 restatement stays at or below half its bound, and no constant is larger than that needs;
+  * the case table is well formed: the extents each family needs, 16-byte aligned views, >= 256 rows and >= 8 columns of sentinel, the
+    grouped cube inside its allocation, every skip documented.
+
+Worst err / tol of the restatements is printed ("[gemm_host] ..."; run with -s); the table is at the top of tests/test_gpu_gemm_epilogues.py.
+"""
+import numpy as np
+import pytest
+import torch
+
+import gemm_ref as G
+
+SHAPES = sorted({f["shape"] for f in G.FAMILIES.values()})
+# the (shape, fast) pairs that occur: fast parts with bf16 operands, erff with fp32 operands
+SHAPE_FAST = sorted({(f["shape"], f["fast"]) for f in G.FAMILIES.values()})
+
+
+def _torch_ref(acc, cfg):
+    """The epilogue from torch float64 operators."""
+    v = torch.from_numpy(np.array(acc))
+    if cfg["bias_v"] is not None:
+        v = v + torch.from_numpy(np.array(cfg["bias_v"]))[None, :]
+    out = {}
+    gelu = torch.nn.functional.gelu
+
+    def grad(x):
+        x = x.clone().requires_grad_(True)
+        gelu(x).sum().backward()
+        return x.grad
+
+    if cfg["epi"] == "gelu":
+        out["aux_v"] = v
+        v = gelu(v)
+    elif cfg["epi"] == "gelu_grad":
+        out["aux_v"] = grad(v)
+        v = gelu(v)
+    elif cfg["epi"] == "dgelu":
+        v = v * grad(torch.from_numpy(np.array(cfg["aux_v"])))
+    elif cfg["epi"] == "mul":
+        v = v * torch.from_numpy(np.array(cfg["aux_v"]))
+    if cfg["res_v"] is not None:
+        v = v + torch.from_numpy(np.array(cfg["res_v"]))
+    if cfg["old_c"] is not None:
+        v = v + torch.from_numpy(np.array(cfg["old_c"]))
+    out["v"] = v
+    return out
+
+
+@pytest.mark.parametrize("shape", SHAPES)
+def test_epilogue_ref_equals_torch_float64(shape):
+    M, N, K = shape
+    acc = G.operands(M, N, K)["acc"]
+    for cfg in G.CONFIGS:
+        c = G.case(cfg, M, N, K)
+        ref, want = G.epilogue_ref(acc, c), _torch_ref(acc, c)
+        # float64 on both sides: the two differ by the rounding of erf / exp and of x / sqrt(2), a few 2^-53 of the magnitudes involved
+        scale = 1.0 + np.abs(acc).max()
+        assert np.abs(ref["v"] - want["v"].numpy()).max() <= 8 * 2.0 ** -53 * scale, cfg["name"]
+        if "aux_v" in ref:
+            assert np.abs(ref["aux_v"] - want["aux_v"].numpy()).max() <= 8 * 2.0 ** -53 * scale, cfg["name"]
+        if cfg["epi"] in ("none", "mul"):
+            assert np.array_equal(ref["v"], want["v"].numpy()), cfg["name"]
+        # the rounding of c_dtype, against torch's casts
+        if cfg["c"] == G.PAIR:
+            hi = torch.from_numpy(ref["v"]).float().bfloat16()
+            lo = (torch.from_numpy(ref["v"]) - hi.double()).float().bfloat16()      # (the spec is float64: v - hi is not rounded to fp32 first)
+            assert np.array_equal(ref["c"], hi.double().numpy()) and np.array_equal(ref["c_lo"], lo.double().numpy())
+        else:
+            dt = torch.float32 if cfg["c"] == G.F32 else torch.bfloat16
+            assert np.array_equal(ref["c"], torch.from_numpy(ref["v"]).float().to(dt).double().numpy()), cfg["name"]
+
+
+def test_grouped_rows_restate_dm_gemm_row():
+    """(m / rows_per_group) * group_stride + (m % rows_per_group) * ld, spelled out row by row; a group ends inside a 16-row MFMA tile and
+    inside an 8-row item."""
+    ld, gs = 208, 41 * 208 + 64
+    ro = G.row_offsets(328, ld, 41, gs)
+    assert [int(ro[m]) for m in (0, 1, 40, 41, 42, 327)] == [0, ld, 40 * ld, gs, gs + ld, 7 * gs + 40 * ld]
+    assert np.array_equal(G.row_offsets(5, 7), np.arange(5) * 7)
+    assert G.GROUP_ROWS % 8 != 0 and G.GROUP_ROWS % 16 != 0 and all(t % G.GROUP_ROWS for t in (64, 128, 256))
+
+
+@pytest.mark.parametrize("shape", SHAPES)
+def test_data_is_exact_and_spans_the_gelu_range(shape):
+    M, N, K = shape
+    d = G.operands(M, N, K)
+    bf = lambda x: torch.from_numpy(np.array(x)).float().bfloat16().double().numpy()
+    assert np.array_equal(bf(d["a"]), d["a"]) and np.array_equal(bf(d["b"]), d["b"])                 # operands exact in bf16
+    assert np.array_equal(d["acc"].astype(np.float32).astype(np.float64), d["acc"])                  # the accumulator is a float32
+    assert np.array_equal(bf(d["aux_mul"]), d["aux_mul"])                                             # the bf16 aux that is read
+    for k in ("bias", "res", "old_c", "aux_mul", "aux_dgelu"):
+        assert np.array_equal(np.round(d[k] * 64) / 64, d[k]), k                                      # the 2^-6 grid
+    # every partial sum of integer products fits: |sum| <= 4 K 2^-shift needs log2(4 K) bits
+    assert 4 * K < 2 ** 24
+    pre = d["acc"] + d["bias"][None, :]
+    for x in (pre, d["aux_dgelu"]):
+        assert (x == 0).any() and (x >= 5.5).any() and (x <= -5.5).any() and ((x > 0) & (x < 0.02)).any() and ((x < 0) & (x > -0.02)).any()
+    assert 1.0 <= d["acc"].std() <= 2.5 and np.abs(pre).max() < 16
+    # saturated tails: erf(6 / sqrt 2) is 1 in float32, erf(5.5 / sqrt 2) its neighbour below
+    sat = lambda x: np.float32(torch.special.erf(torch.tensor(x / np.sqrt(2.0), dtype=torch.float64)).item())
+    assert sat(6.0) == np.float32(1.0) and sat(5.5) == np.nextafter(np.float32(1.0), np.float32(0.0))
+    assert (pre == 6.0).any() and (pre == -6.0).any()
+
+
+@pytest.mark.parametrize("shape", SHAPES)
+def test_exact_configurations_are_exact_in_float32(shape):
+    M, N, K = shape
+    acc = G.operands(M, N, K)["acc"]
+    for cfg in G.CONFIGS:
+        c = G.case(cfg, M, N, K)
+        c_exact, aux_exact = G.is_exact(cfg)
+        ref = G.epilogue_ref(acc, c)
+        for order in ("left", "right"):
+            for fma in (False, True):
+                for fast in (True, False):
+                    r = G.restate32(acc, c, fast, order, fma)
+                    if c_exact:
+                        assert np.array_equal(r["v"].astype(np.float64), ref["v"]), (cfg["name"], order, fma)
+                        assert np.array_equal(np.signbit(r["v"]), np.signbit(ref["v"])), cfg["name"]
+                    if aux_exact and "aux_v" in ref:
+                        assert np.array_equal(r["aux_v"].astype(np.float64), ref["aux_v"]), (cfg["name"], order, fma)
+    # the exact class covers what the issue lists
+    assert [c["name"] for c in G.CONFIGS if G.is_exact(c)[0]] == ["none_f32", "none_bf16", "bias_res_f32", "acc_f32", "bias_res_acc_f32", "mul_bf16", "grouped41"]
+
+
+def _worst_ratios(consts):
+    """Worst err / tol of the float32 restatement per (fast, kind) over every shape and bounded configuration; bf16 destinations included."""
+    worst = {}
+    for shape, fast in SHAPE_FAST:
+        M, N, K = shape
+        acc = G.operands(M, N, K)["acc"]
+        for cfg in G.CONFIGS:
+            if all(G.is_exact(cfg)) or (cfg["c"] == G.PAIR and not fast):
+                continue
+            c = G.case(cfg, M, N, K)
+            ref = G.epilogue_ref(acc, c)
+            tol = G.bounds(cfg, ref, acc, fast, consts)
+            for fma in (False, True):
+                r = G.restate32(acc, c, fast, "left", fma)
+                if tol["c"] is not None:
+                    cdt = G.BF16 if cfg["c"] == G.PAIR else cfg["c"]
+                    if cfg["c"] == G.PAIR:
+                        hi = G.round_bf16(r["v"].astype(np.float64))
+                        got = hi + G.round_bf16(r["v"].astype(np.float64) - hi)
+                    else:
+                        got = G.round_to(r["v"].astype(np.float64), cdt)
+                    kind = "muld" if cfg["epi"] == "dgelu" else "gelu"
+                    key = (fast, kind, cdt if cfg["c"] != G.PAIR else G.PAIR)
+                    worst[key] = max(worst.get(key, 0.0), G.worst(np.abs(got - ref["v"]), tol["c"]))
+                if tol["aux"] is not None:
+                    got = G.round_to(r["aux_v"].astype(np.float64), cfg["aux"][0])
+                    key = (fast, "dgelu", cfg["aux"][0])
+                    worst[key] = max(worst.get(key, 0.0), G.worst(np.abs(got - ref["aux_v"]), tol["aux"]))
+    return worst
+
+
+def test_bounded_restatements_stay_below_half_their_bounds_with_the_smallest_constants():
+    worst = _worst_ratios(None)
+    for key, r in sorted(worst.items(), key=str):
+        print(f"  [gemm_host] {'fast' if key[0] else 'erff'} {key[1]:<6s} -> {key[2]:<5s} err/tol = {r:.3f}")
+        assert r <= 0.5, (key, r)
+    # no constant can be one smaller: some destination of its kind then exceeds half the bound
+    for ck, cv in G.C.items():
+        assert cv >= 1
+        if cv == 1:
+            continue
+        less = dict(G.C)
+        less[ck] = cv - 1
+        w = _worst_ratios(less)
+        assert max(r for key, r in w.items() if key[:2] == ck) > 0.5, (ck, cv)
+    # every kind the GPU test checks has been measured here
+    assert {k[:2] for k in worst} == set(G.C)
+
+
+def test_case_table_is_well_formed():
+    assert [c["id"] for c in G.CONFIGS] == list(range(1, 15)) and len(G.CONFIG) == 14
+    # lean keys as the issue's table names them
+    keys = {c["name"]: G.lean_key(c) for c in G.CONFIGS}
+    assert keys["none_f32"] == 8 and keys["none_bf16"] == 0 and keys["bias_res_f32"] == 9 and keys["acc_f32"] == 10
+    assert keys["gelu_save_bf16"] == 16 == keys["gelugrad_save_bf16"] and keys["mul_bf16"] == 4 and keys["gelu_bf16_nosave"] == 0
+    for name in ("bias_res_acc_f32", "gelu_save_f32", "dgelu_f32_res"):                     # the run-time lean form
+        assert keys[name] >= 0 and keys[name] not in G.SPECIALISED_KEYS
+    assert all(f in G.FAMILIES and G.FAMILIES[f]["tile"] == (64, 64) and n == "mul_bf16" for f, n in G.STRIP_ZERO_SIGN)
+    assert keys["pair_gelu"] == 1 << 8 and keys["grouped41"] == -1 == keys["grouped41_gelugrad"]
+    assert set(G.FAMILIES) == {"t64", "t128", "f32_t64", "f32_t128", "ring8", "ring4", "q4", "w4", "p256", "p256p", "kslices", "generic"}
+
+    for fam, f in G.FAMILIES.items():
+        M, N, K = f["shape"]
+        tm, tn = f["tile"]
+        wm, wn = f["wave"]
+        assert (M + tm - 1) // tm >= 2 and (N + tn - 1) // tn >= 2, fam                     # two tiles each way
+        assert M % tm != 0, fam                                                             # ragged M
+        last = (M // tm) * tm
+        blocks = range(last, last + tm, wm)
+        if fam != "generic":                                                                # (16 x 16 outputs, one per thread: no wave block)
+            assert any(b >= M for b in blocks), fam                                         # a wave block that starts past M
+            if fam != "q4":                                                                 # (q4 takes M % 64 == 0: its guard)
+                assert any(b < M < b + wm for b in blocks), fam                             # a partially filled wave block
+                assert M % 16 != 0, fam                                                     # ... that ends inside a 16-row MFMA tile
+        assert N % 8 == 0
+        if fam == "w4":
+            assert N % 192 == 0 and K % 128 == 0                                            # dm_gemm_w4_plan
+        elif fam == "p256p":
+            assert N % 256 == 0                                                             # dm_gemm256_launch
+            assert set(G.family_configs(fam)) == {c["name"] for c in G.CONFIGS if G.lean_key(c) in G.SPECIALISED_KEYS}
+        else:
+            assert N % tn != 0 and (N % wn) == 8, fam                                       # an N tail that ends inside a wave's columns
+        steps = (K + f["bk"] - 1) // f["bk"]
+        assert fam in ("kslices", "generic") or 2 <= steps <= (4 if fam == "w4" else 3), fam
+        if f["ab"] == G.F32 and fam != "generic":
+            assert ((M + 127) // 128) * ((N + 127) // 128) >= 16 and K % 4 == 0              # stays off the generic path (gemm_prepare)
+        if fam == "generic":
+            assert K % 4 != 0
+        if fam == "q4":
+            assert M % 64 == 0
+            assert set(G.family_configs(fam)) == {c["name"] for c in G.CONFIGS if G.lean_key(c) in G.SPECIALISED_KEYS}
+        if fam == "kslices":
+            assert G.plan_fwd_split(M, N, K) == (2, 64) and "DM_GEMM_FORCE_TILE" in f["env"] and f["env"]["DM_GEMM_FORCE_TILE"] is None
+        else:
+            assert G.plan_fwd_split(M, N, K) == (1, 0), fam
+        if f["ab"] == G.BF16:
+            assert K % 8 == 0
+        # documented skips only, each with the refusing line
+        assert set(f["skips"]) <= set(G.ALL) and all(".hip" in why and "`" in why for why in f["skips"].values()), fam
+        assert len(G.family_cases(fam)) == len(f["layouts"]) * (14 - len(f["skips"]))
+        if fam in ("t64", "t128", "ring8", "ring4", "w4", "p256", "kslices"):
+            assert not f["skips"], fam
+
+        for cfg in G.CONFIGS:
+            b = G.buffers(cfg, M, N)
+            lds = []
+            for op in ("c", "aux", "res"):
+                if op not in b:
+                    continue
+                o = b[op]
+                size = 4 if o["dtype"] == G.F32 else 2
+                idx = o["idx"]
+                assert idx.shape == (M, N) and idx.min() == G.VIEW_OFFSET == 8
+                assert (G.VIEW_OFFSET * size) % 16 == 0 and (o["ld"] * size) % 16 == 0      # 16-byte aligned view and rows
+                assert (b["group_stride"] * size) % 16 == 0
+                assert len(np.unique(idx)) == M * N                                         # no two outputs share an element
+                top = int(idx.max()) + (o.get("plane", 0))
+                assert o["elems"] - 1 - top >= G.PAD_ROWS * o["ld"] >= 256 * N          # >= 256 rows of sentinel below the last row
+                if cfg["c"] == G.PAIR and op == "c":
+                    assert o["ld"] == N and o["plane"] == M * N and o["plane"] % 8 == 0
+                else:
+                    assert o["ld"] - N >= 8                                                 # >= 8 columns of sentinel right of N
+                    lds.append(o["ld"])
+            if cfg["grouped"]:
+                assert b["rows_per_group"] == 41 and b["group_stride"] == 41 * (N + 8) + 64 and set(lds) == {N + 8}
+                groups = (M + 40) // 41
+                assert b["c"]["elems"] >= G.VIEW_OFFSET + groups * b["group_stride"] + 256 * (N + 8)      # the cube fits
+            else:
+                assert len(set(lds)) == len(lds)                                            # all leading dimensions differ
+                assert b["rows_per_group"] == 0
