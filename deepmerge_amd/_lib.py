@@ -183,6 +183,9 @@ SIGNATURES = {
     "dm_vector_rank_round": (_I, [_P, _P, _P, _P, _I, _P, _P]),
     "dm_vector_ring_emit": (_I, [C.POINTER(DmVectorTrace), _P]),
     "dm_vector_arc_emit": (_I, [C.POINTER(DmVectorTrace), _P]),
+    "dm_rasterize_count": (_I, [_P, _P, _P, _I, _I, _I, _I, _P, _P]),
+    "dm_rasterize_emit": (_I, [_P, _P, _P, _P, _P, _I, _I, _L, _I, _I, _L, _P, _P]),
+    "dm_rasterize_fill": (_I, [_P, _L, _I, _I, _I, _P, _P, _P]),
     "dm_gru_cell_fwd": (_I, [_P, _L, _P, _P, _P, _P, _I, _I, _P]),
     "dm_gru_cell_bwd": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _P]),
     "dm_prof_enable": (_I, [_I]),

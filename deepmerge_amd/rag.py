@@ -10,6 +10,8 @@ Against a ground-truth raster, `label_overlap` counts the overlap table once; `p
 `Overlap.coarsen(...).scores()` scores any merged partition (csrc/dm_truth.hip; spec tests/truth_ref.py).
 `polygons` and `boundary_arcs` trace a label raster into closed rings and boundary arcs, the geometry of the reference's polygon
 layer and `lines.shp` (csrc/dm_vector.hip; spec tests/vector_ref.py); deepmerge_amd/shpstore.py writes them as shapefiles.
+`rasterize` is the way back, for any polygon: rings to a label raster (csrc/dm_rasterize.hip; spec tests/rasterize_ref.py), and
+`labels_from_shapefile` reads the rings from a polygon shapefile, the form the reference's users have their data in.
 """
 from __future__ import annotations
 
@@ -911,3 +913,121 @@ def boundary_arcs(labels: torch.Tensor, n_labels: int, edges: Optional[torch.Ten
     raises."""
     arcs = _trace(labels, n_labels)[1]
     return arcs if edges is None else _attach_edges(arcs, n_labels, edges)
+
+
+# ---- polygon rings to a label raster (csrc/dm_rasterize.hip; the rule: include/deepmerge_hip.h, DESIGN.md 3.5.6) ----------------------
+SUBPIXEL = 256                    # DM_RASTERIZE_SUBPIXEL: fixed-point units per pixel
+MAX_COORDINATE = 1 << 20          # |coordinate| in pixels
+MAX_EVENTS = 1 << 30
+
+
+@dataclass
+class Rings:
+    """Closed polygon rings in pixel-corner space (x right, y down), as `rasterize` takes them.
+
+    ring_ptr int64 [R+1] into xy; xy float64 [V,2]; ring_label int32 [R] in 0 .. 2^31 - 2.  The rings of one label need not be
+    adjacent; a ring may repeat its first vertex at its end, need not lie inside the raster, and may be empty."""
+    ring_ptr: torch.Tensor
+    xy: torch.Tensor
+    ring_label: torch.Tensor
+
+
+def rasterize(rings, H: int, W: int, fill: int = -1, stats: Optional[dict] = None) -> torch.Tensor:
+    """int32 [H,W]: the label raster of polygon rings, the exact inverse of `polygons`.  rings: a `Rings` (float64 coordinates,
+    quantised to 1/256 pixel: q = floor(256 v + 0.5)) or a `Polygons` (int32 corners, multiplied by 256 with no float step).
+
+    A pixel belongs to a label iff its centre is inside that label's rings by the even-odd rule (holes need no flag), with the
+    half-open tie rules of include/deepmerge_hip.h: polygons that share an edge partition the pixels along it.  A pixel inside
+    several labels gets the greatest, a pixel inside none gets `fill` < 0.  Integer arithmetic throughout, bit-equal to
+    tests/rasterize_ref.py.  The inputs are not modified.  Readbacks: the range check, the number of events N (it sizes the keys),
+    the error flag.  stats: a dict that receives N, the time per stage and the bytes of the passes (tools/mb_rasterize.py)."""
+    ring_ptr, xy, ring_label = rings.ring_ptr, rings.xy, rings.ring_label
+    _need_cuda(ring_ptr, xy, ring_label)
+    if ring_ptr.dtype != torch.int64 or ring_ptr.dim() != 1 or ring_ptr.numel() < 1:
+        raise ValueError("ring_ptr must be int64 [R+1]")
+    R = ring_ptr.numel() - 1
+    if ring_label.dtype != torch.int32 or tuple(ring_label.shape) != (R,):
+        raise ValueError(f"ring_label must be int32 [R] with R = {R}")
+    if xy.dtype not in (torch.float64, torch.int32) or xy.dim() != 2 or xy.shape[1] != 2:
+        raise ValueError("xy must be float64 [V,2] (or int32 [V,2] corners, as Polygons.xy)")
+    H, W, fill = int(H), int(W), int(fill)
+    if H < 1 or W < 1 or H * W >= 1 << 31:
+        raise ValueError(f"need H, W >= 1 and H * W < 2^31, got {H} x {W}")
+    if not -(1 << 31) <= fill < 0:
+        raise ValueError(f"fill must be a negative int32, got {fill}")
+    V = xy.shape[0]
+    if V > MAX_EVENTS:
+        raise ValueError(f"rasterize takes at most 2^30 vertices, got {V}")
+    dev, lib, i32, i64 = xy.device, _lib.lib(), torch.int32, torch.int64
+    ring_ptr, xy, ring_label = ring_ptr.contiguous(), xy.contiguous(), ring_label.contiguous()
+    marks = []
+
+    def mark(stage):                                             # stage boundaries for tools/mb_rasterize.py; nothing when stats is None
+        if stats is not None:
+            e = torch.cuda.Event(enable_timing=True)
+            e.record()
+            marks.append((stage, e))
+    mark("start")
+    # the range check: one readback of (coordinates out of range or not finite, ring_ptr not 0 .. V non-decreasing, label range)
+    bad_xy = ~((xy >= -MAX_COORDINATE) & (xy <= MAX_COORDINATE))            # NaN compares false: refused
+    bad_ptr = (ring_ptr[0] != 0) | (ring_ptr[-1] != V)
+    if R:
+        bad_ptr = bad_ptr | (ring_ptr[1:] < ring_ptr[:-1]).any()
+        lo, hi = torch.aminmax(ring_label)
+    else:
+        lo = hi = torch.zeros((), dtype=i32, device=dev)
+    any_bad = bad_xy.any() if V else torch.zeros((), dtype=torch.bool, device=dev)
+    bad_xy_, bad_ptr_, lo, hi = torch.stack((any_bad.to(i64), bad_ptr.to(i64), lo.to(i64), hi.to(i64))).tolist()
+    if bad_ptr_:
+        raise ValueError(f"ring_ptr must start at 0, be non-decreasing and end at V = {V}")
+    if bad_xy_:
+        raise ValueError("coordinates must be finite and within +-2^20 pixels")
+    if lo < 0 or hi > (1 << 31) - 2:
+        raise ValueError(f"ring labels must be in 0 .. 2^31 - 2, found {lo} .. {hi}")
+    n_labels = hi + 1
+    if n_labels * H * (W + 1) >= 1 << 63:
+        raise ValueError(f"(largest label + 1) * H * (W + 1) must be below 2^63, got {n_labels} * {H} * {W + 1}")
+    N = 0
+    if R and V:
+        q = torch.floor(xy * SUBPIXEL + 0.5).to(i32) if xy.dtype == torch.float64 else xy * SUBPIXEL
+        vert_ring = (torch.searchsorted(ring_ptr, torch.arange(V, dtype=i64, device=dev), right=True) - 1).to(i32)
+        count = torch.empty(V, dtype=i32, device=dev)
+        check(lib.dm_rasterize_count(q.data_ptr(), ring_ptr.data_ptr(), vert_ring.data_ptr(), V, R, H, W, count.data_ptr(), _stream()),
+              "dm_rasterize_count")
+        scan = torch.zeros(V + 1, dtype=i64, device=dev)
+        torch.cumsum(count, 0, dtype=i64, out=scan[1:])
+        N = int(scan[-1])
+        mark("quantise + count + scan + readback of N")
+        if N > MAX_EVENTS:
+            raise ValueError(f"the rings cross {N} pixel-row centres; rasterize takes at most 2^30")
+    if N == 0:
+        return torch.full((H, W), fill, dtype=i32, device=dev)
+    keys = torch.empty(N, dtype=i64, device=dev)
+    check(lib.dm_rasterize_emit(q.data_ptr(), ring_ptr.data_ptr(), vert_ring.data_ptr(), ring_label.data_ptr(), scan.data_ptr(), V, R, N, H, W,
+                                n_labels, keys.data_ptr(), _stream()), "dm_rasterize_emit")
+    mark("emit")
+    keys = torch.sort(keys).values
+    mark("sort")
+    out = torch.empty((H, W), dtype=i32, device=dev)
+    error = torch.empty(1, dtype=i32, device=dev)
+    check(lib.dm_rasterize_fill(keys.data_ptr(), N, H, W, fill, out.data_ptr(), error.data_ptr(), _stream()), "dm_rasterize_fill")
+    if int(error):
+        raise RuntimeError("rasterize: a pair of sorted events disagrees in (label, row): the rings are not closed (an odd number of "
+                           "crossings in a row)")
+    mark("pre-set + fill + readback of the error flag")
+    if stats is not None:
+        torch.cuda.synchronize()
+        stats["stage_ms"] = [(b[0], a[1].elapsed_time(b[1])) for a, b in zip(marks[:-1], marks[1:])]
+        stats.update(N=N, vertices=V, rings=R)
+    return out
+
+
+def labels_from_shapefile(path: str, H: int, W: int, geotransform=None, label_field: Optional[str] = None, fill: int = -1,
+                          device="cuda:0") -> Tuple[torch.Tensor, int]:
+    """(labels int32 [H,W], n_labels) from a polygon shapefile: `shpstore.read_rings` followed by `rasterize`.  Record i is label i
+    (the FID; n_labels = the record count), or the value of the integer field `label_field` (n_labels = the largest + 1).
+    geotransform: the six GDAL terms of the raster the labels are for (None: X = x, Y = -y)."""
+    from . import shpstore
+    ring_ptr, xy, ring_label, n_labels = shpstore._read_rings(path, geotransform, label_field)
+    rings = Rings(*(torch.from_numpy(a).to(device) for a in (ring_ptr, xy, ring_label)))
+    return rasterize(rings, H, W, fill), n_labels

@@ -43,6 +43,20 @@ def corner_to_geo(gt: Optional[Sequence[float]], xy: np.ndarray) -> np.ndarray:
     return np.stack((gt[0] + x * gt[1] + y * gt[2], gt[3] + x * gt[4] + y * gt[5]), 1)
 
 
+def geo_to_corner(gt: Optional[Sequence[float]], XY: np.ndarray) -> np.ndarray:
+    """float64 [N,2]: the inverse of `corner_to_geo`, the corner position (x, y) of every (X, Y).  Solves the general 2x2, so the
+    rotation terms gt[2], gt[4] may be non-zero; a singular transform raises."""
+    gt = DEFAULT_GEOTRANSFORM if gt is None else tuple(float(v) for v in gt)
+    if len(gt) != 6:
+        raise ValueError("geotransform must have six entries")
+    det = gt[1] * gt[5] - gt[2] * gt[4]
+    if det == 0.0 or not np.isfinite(det):
+        raise ValueError(f"geotransform {gt} is singular: gt[1] gt[5] - gt[2] gt[4] = {det}")
+    XY = np.asarray(XY, np.float64).reshape(-1, 2)
+    dX, dY = XY[:, 0] - gt[0], XY[:, 1] - gt[3]
+    return np.stack(((gt[5] * dX - gt[2] * dY) / det, (gt[1] * dY - gt[4] * dX) / det), 1)
+
+
 def pixel_to_geo(gt: Optional[Sequence[float]], xy: np.ndarray) -> np.ndarray:
     """The position of pixel (x, y) for which `patches.geo_to_pixel` (the reference's conversion, int(|offset / size| + 1)) returns
     (x, y): half a pixel in front of corner (x, y).  That conversion never returns 0, so a pixel of column or row 0 reads back as 1."""
@@ -220,3 +234,44 @@ class ShapeReader:
 
     def __len__(self) -> int:
         return len(self.shapes)
+
+
+def read_rings(path: str, geotransform=None, label_field: Optional[str] = None) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """(ring_ptr int64 [R+1], xy float64 [V,2] in pixel-corner space, ring_label int32 [R]) of a polygon shapefile, the arrays of
+    `rag.Rings`.  All parts of record i are rings of label i (the FID), or of the value of the integer field `label_field`; null
+    shapes are skipped.  A ring keeps its repeated closing vertex (a zero-length edge to `rag.rasterize`).  A file that is not of
+    polygon type, a field that is missing, not integer, negative or >= 2^31 - 1, and a part of fewer than 2 vertices raise
+    ValueError naming the record."""
+    return _read_rings(path, geotransform, label_field)[:3]
+
+
+def _read_rings(path: str, geotransform, label_field: Optional[str]):
+    """read_rings and n_labels: the record count when the label is the FID, the field's largest value + 1 otherwise."""
+    shp = ShapeReader(path)
+    if shp.shape_type != POLYGON:
+        raise ValueError(f"{path}: shape type {shp.shape_type} is not polygon ({POLYGON})")
+    values = None
+    if label_field is not None:
+        if label_field not in shp.fields:
+            raise ValueError(f"{path}: no field {label_field!r} (fields: {sorted(shp.fields)})")
+        values = shp.fields[label_field]
+        if isinstance(values, list) or values.dtype.kind not in "iu":
+            raise ValueError(f"{path}: field {label_field!r} is not an integer field")
+        if len(values) != len(shp):
+            raise ValueError(f"{path}: field {label_field!r} has {len(values)} values for {len(shp)} records")
+    ring_ptr, parts, labels, n_labels = [0], [], [], 0
+    for i, shape in enumerate(shp.shapes):
+        label = i if values is None else int(values[i])
+        if not 0 <= label < (1 << 31) - 1:
+            raise ValueError(f"{path}: record {i + 1}: label {label} of field {label_field!r} is outside 0 .. 2^31 - 2")
+        n_labels = max(n_labels, label + 1)
+        if shape is None:
+            continue
+        for p, part in enumerate(shape):
+            if part.shape[0] < 2:
+                raise ValueError(f"{path}: record {i + 1}: part {p} has {part.shape[0]} vertices; a ring needs at least 2")
+            parts.append(part)
+            ring_ptr.append(ring_ptr[-1] + part.shape[0])
+            labels.append(label)
+    xy = geo_to_corner(geotransform, np.concatenate(parts)) if parts else np.zeros((0, 2), np.float64)
+    return np.asarray(ring_ptr, np.int64), xy, np.asarray(labels, np.int32), n_labels

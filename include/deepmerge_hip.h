@@ -722,6 +722,50 @@ int dm_vector_rank_round(const int64_t *sum_in, const int32_t *nxt_in, int64_t *
 int dm_vector_ring_emit(const DmVectorTrace *t, void *stream);
 int dm_vector_arc_emit(const DmVectorTrace *t, void *stream);
 
+/* ---- polygon rings rasterised into a label raster (additive in ABI 6; csrc/dm_rasterize.hip, DESIGN.md 3.5.6, rag.rasterize /
+ * rag.labels_from_shapefile) ------------------------------------------------------------------------------------------------------
+ * The inverse of the tracing above, for ANY polygon: the step from the polygon layer the reference's users have (superpixels
+ * written by external GIS software, digitised ground truth) to the label raster every raster pass here starts from.  The rule is
+ * this build's (restated in numpy in tests/rasterize_ref.py).  All arithmetic is on integers; nothing depends on the order in which
+ * threads arrive; results are bit-exact.
+ * The rule.
+ *   coordinates: pixel-corner space as DmVectorTrace.xy uses it, x right, y down; pixel (c, r) covers [c, c+1] x [r, r+1], its
+ *     centre is (c + 1/2, r + 1/2).
+ *   quantisation: a float64 coordinate v becomes the int32 q = floor(v * DM_RASTERIZE_SUBPIXEL + 0.5): 8 sub-pixel bits.
+ *     |v| <= 2^20 pixels (NaN and inf are refused), so |q| <= 2^28 and every product below stays under 2^60.  An integer corner x is
+ *     256 x exactly.  The entry points take the quantised int32 coordinates.
+ *   rings: a ring is always closed, the last vertex joins the first.  A repeated closing vertex (as shapefiles store it) is a
+ *     zero-length edge that contributes nothing.  A ring that encloses nothing (fewer than 3 vertices, collinear vertices, zero
+ *     area) contributes nothing, by the parity rule itself, and is not an error.  Vertices may lie outside the raster.
+ *   crossings: an edge with ends (x0, y0), (x1, y1); y0 == y1 contributes nothing.  Otherwise the ends are swapped so that y0 < y1,
+ *     dy = y1 - y0.  The edge crosses pixel row r iff y0 <= 256 r + 128 < y1 (half-open: a vertex on a centre row counts once).
+ *     There, with Yc = 256 r + 128, num = x0 dy + (Yc - y0) (x1 - x0); the crossing is at X = num / dy.  Column c is right of it
+ *     iff 256 c + 128 >= X, i.e. (256 c + 128) dy >= num: the event's column is cx = ceil((num - 128 dy) / (256 dy)), exact
+ *     integer ceiling division, clamped to [0, W].  Rows outside [0, H) give no event.
+ *   inside: pixel (c, r) belongs to label l iff the number of events of ALL rings of l in row r with cx <= c is odd (even-odd: holes
+ *     need no flag, the doubly covered part of a self-intersecting ring is left out).  Polygons that share an edge partition the
+ *     pixels along it: no gap, no double claim.
+ *   output: int32 [H,W]; a pixel inside no label holds `fill` < 0; labels are 0 .. 2^31 - 2; a pixel inside several labels gets the
+ *     greatest (integer max into a raster pre-set to `fill`).
+ * Closed rings give every (label, row) an even number of events, so in the sorted keys events 2j and 2j+1 share (label, row) and
+ * bound one span of the label's pixels.  Every entry point validates before any launch, launches on `stream`, never synchronises
+ * and never allocates; the caller scans the counts, reads back N and sorts the keys between the calls (rag.rasterize).
+ *
+ * dm_rasterize_count: xy int32 [V,2] quantised, ring_ptr int64 [R+1] non-decreasing from 0 to V, vert_ring int32 [V] = the ring of
+ *   every vertex.  Edge v runs from vertex v to its successor within its ring.  count int32 [V] = the events of edge v.
+ * dm_rasterize_emit: scan int64 [V+1] = exclusive scan of count, N = scan[V] <= 2^30.  One thread per event: keys int64 [N],
+ *   key = (label H + row) (W + 1) + cx with label = ring_label[ring] in [0, n_labels); n_labels H (W + 1) < 2^63.  An event whose
+ *   edge the tables do not hold gets key -1.
+ * dm_rasterize_fill: keys int64 [N] SORTED, N even (N = 0: keys may be NULL).  out int32 [H,W] is pre-set to fill < 0, then every
+ *   pair (2j, 2j+1) writes max(label) over columns [cx of 2j, cx of 2j+1) of its row.  error[0] = 1 iff a pair's keys disagree in
+ *   (label, row), a key is negative or a label exceeds 2^31 - 2 (cleared by the call); such a pair writes nothing. */
+#define DM_RASTERIZE_SUBPIXEL 256
+int dm_rasterize_count(const int32_t *xy, const int64_t *ring_ptr, const int32_t *vert_ring, int32_t V, int32_t R, int32_t H, int32_t W,
+                       int32_t *count, void *stream);
+int dm_rasterize_emit(const int32_t *xy, const int64_t *ring_ptr, const int32_t *vert_ring, const int32_t *ring_label, const int64_t *scan,
+                      int32_t V, int32_t R, int64_t N, int32_t H, int32_t W, int64_t n_labels, int64_t *keys, void *stream);
+int dm_rasterize_fill(const int64_t *keys, int64_t N, int32_t H, int32_t W, int32_t fill, int32_t *out, int32_t *error, void *stream);
+
 /* BatchNorm2d (+ ReLU, + Dropout2d mask) of the auxiliary heads (reference nets/ShfitScaleFormer.py:329-368: Conv2d ->
  * BatchNorm2d -> ReLU -> Dropout2d(0.3)) on the channels-last matrix the convolution GEMM produces: x, y fp32 [M, C] with
  * M = samples * rows_per_sample.  training != 0: batch statistics (biased variance, eps inside the sqrt), running_mean /
