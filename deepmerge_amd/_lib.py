@@ -186,6 +186,12 @@ SIGNATURES = {
     "dm_rasterize_count": (_I, [_P, _P, _P, _I, _I, _I, _I, _P, _P]),
     "dm_rasterize_emit": (_I, [_P, _P, _P, _P, _P, _I, _I, _L, _I, _I, _L, _P, _P]),
     "dm_rasterize_fill": (_I, [_P, _L, _I, _I, _I, _P, _P, _P]),
+    "dm_simplify_nodes": (_I, [_P, _I, _I, _P, _P]),
+    "dm_simplify_chains": (_I, [_P, _P, _I, _L, _I, _I, _I, _P, _P, _P]),
+    "dm_simplify_arc_count": (_I, [_P, _P, _I, _L, _I, _I, _P, _P, _P]),
+    "dm_simplify_arc_emit": (_I, [_P, _P, _P, _I, _L, _L, _I, _I, _P, _P, _P]),
+    "dm_simplify_ring_count": (_I, [_P, _P, _P, _I, _I, _I, _I, _P, _P, _P]),
+    "dm_simplify_ring_emit": (_I, [_P, _P, _P, _P, _P, _I, _I, _L, _I, _I, _P, _P, _P, _P]),
     "dm_gru_cell_fwd": (_I, [_P, _L, _P, _P, _P, _P, _I, _I, _P]),
     "dm_gru_cell_bwd": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _P]),
     "dm_prof_enable": (_I, [_I]),

@@ -12,10 +12,13 @@ Against a ground-truth raster, `label_overlap` counts the overlap table once; `p
 layer and `lines.shp` (csrc/dm_vector.hip; spec tests/vector_ref.py); deepmerge_amd/shpstore.py writes them as shapefiles.
 `rasterize` is the way back, for any polygon: rings to a label raster (csrc/dm_rasterize.hip; spec tests/rasterize_ref.py), and
 `labels_from_shapefile` reads the rings from a polygon shapefile, the form the reference's users have their data in.
+`simplify` is Douglas-Peucker on the traced geometry, once per shared boundary, so neighbours keep sharing every vertex
+(csrc/dm_simplify.hip; spec tests/simplify_ref.py).
 """
 from __future__ import annotations
 
 import ctypes
+import math
 from dataclasses import dataclass, field
 from typing import Dict, List, Optional, Tuple
 
@@ -212,6 +215,11 @@ class MergeResult:
     def boundary_arcs(self, raster: torch.Tensor) -> "Arcs":
         """The boundaries between the merged regions, `edge` = row of `self.edges`: `boundary_arcs(self.labels(raster), ...)`."""
         return boundary_arcs(self.labels(raster), self.rep.numel(), edges=self.edges)
+
+    def simplified(self, raster: torch.Tensor, tolerance: float) -> Tuple["Polygons", "Arcs"]:
+        """The merged regions' rings and boundary arcs simplified to `tolerance` pixels, `Arcs.edge` = row of `self.edges`:
+        `simplify(self.labels(raster), number of merged regions, tolerance, edges=self.edges)`."""
+        return simplify(self.labels(raster), self.rep.numel(), tolerance, edges=self.edges)
 
     def scores(self, overlap: "Overlap", round: Optional[int] = None) -> "PartitionScores":
         """The partition scored against a ground-truth map: `overlap` = label_overlap(superpixel raster, truth, S0, G), coarsened by
@@ -913,6 +921,94 @@ def boundary_arcs(labels: torch.Tensor, n_labels: int, edges: Optional[torch.Ten
     raises."""
     arcs = _trace(labels, n_labels)[1]
     return arcs if edges is None else _attach_edges(arcs, n_labels, edges)
+
+
+# ---- shared-boundary Douglas-Peucker (csrc/dm_simplify.hip; the rule: include/deepmerge_hip.h, DESIGN.md 3.5.7) ----------------------
+MAX_SIMPLIFY_SIDE = 1 << 15       # DM_SIMPLIFY_MAX_SIDE: every cross product of two corner differences stays below 2^31
+MAX_SIMPLIFY_Q = 1 << 20          # DM_SIMPLIFY_MAX_Q: the tolerance in 1/256 pixel
+
+
+def _simplify(labels: torch.Tensor, n_labels: int, tolerance: float, stats: Optional[dict] = None) -> Tuple[Polygons, Arcs, torch.Tensor]:
+    """`simplify` and the keep flags uint8 [(H+1)(W+1)] (2 node, 1 kept chain vertex, 0 otherwise) it decided by."""
+    _need_cuda(labels)
+    if labels.dtype != torch.int32 or labels.dim() != 2 or labels.numel() < 1:
+        raise ValueError("labels must be int32 [H,W] with at least one pixel")
+    H, W = labels.shape
+    if H > MAX_SIMPLIFY_SIDE or W > MAX_SIMPLIFY_SIDE:
+        raise ValueError(f"simplify takes rasters of at most 32768 x 32768 pixels, got {H} x {W}")
+    t = float(tolerance)
+    if not math.isfinite(t) or t < 0:
+        raise ValueError(f"tolerance must be finite and >= 0, got {tolerance}")
+    q = int(math.floor(t * SUBPIXEL + 0.5))
+    if q > MAX_SIMPLIFY_Q:
+        raise ValueError(f"tolerance must be at most {MAX_SIMPLIFY_Q // SUBPIXEL} pixels, got {tolerance}")
+    trace_stats = None if stats is None else {}
+    polys, arcs = _trace(labels, n_labels, trace_stats)
+    labels = labels.contiguous()
+    dev, lib, i32, i64 = labels.device, _lib.lib(), torch.int32, torch.int64
+    new = lambda n, dt: torch.empty(n, dtype=dt, device=dev)
+    marks = []
+
+    def mark(stage):                                             # stage boundaries for tools/mb_simplify.py; nothing when stats is None
+        if stats is not None:
+            e = torch.cuda.Event(enable_timing=True)
+            e.record()
+            marks.append((stage, e))
+    mark("start")
+    A, Va = arcs.left.numel(), arcs.xy.shape[0]
+    R, V = polys.ring_label.numel(), polys.xy.shape[0]
+    keep = new((H + 1) * (W + 1), torch.uint8)
+    check(lib.dm_simplify_nodes(labels.data_ptr(), H, W, keep.data_ptr(), _stream()), "dm_simplify_nodes")
+    mark("nodes")
+    stack = new(Va, i64)                                         # one entry per arc vertex: the bound of the depth-first walk
+    check(lib.dm_simplify_chains(arcs.xy.data_ptr(), arcs.arc_ptr.data_ptr(), A, Va, H, W, q, keep.data_ptr(), stack.data_ptr(), _stream()),
+          "dm_simplify_chains")
+    del stack
+    mark("chains")
+    arc_count, ring_count = new(A, i32), new(V, i32)
+    check(lib.dm_simplify_arc_count(arcs.xy.data_ptr(), arcs.arc_ptr.data_ptr(), A, Va, H, W, keep.data_ptr(), arc_count.data_ptr(), _stream()),
+          "dm_simplify_arc_count")
+    vert_ring = (torch.searchsorted(polys.ring_ptr, torch.arange(V, dtype=i64, device=dev), right=True) - 1).to(i32)
+    check(lib.dm_simplify_ring_count(polys.xy.data_ptr(), polys.ring_ptr.data_ptr(), vert_ring.data_ptr(), V, R, H, W, keep.data_ptr(),
+                                     ring_count.data_ptr(), _stream()), "dm_simplify_ring_count")
+    arc_ptr, scan = torch.zeros(A + 1, dtype=i64, device=dev), torch.zeros(V + 1, dtype=i64, device=dev)
+    torch.cumsum(arc_count, 0, dtype=i64, out=arc_ptr[1:])
+    torch.cumsum(ring_count, 0, dtype=i64, out=scan[1:])
+    ring_ptr = scan[polys.ring_ptr]
+    Van, Vn = (int(v) for v in torch.stack((arc_ptr[-1], scan[-1])).tolist())            # the one readback: the vertex totals
+    mark("arc_count + ring_count + scans + readback of the totals")
+    arc_xy, xy, area2 = new((Van, 2), i32), new((Vn, 2), i32), new(R, i64)
+    check(lib.dm_simplify_arc_emit(arcs.xy.data_ptr(), arcs.arc_ptr.data_ptr(), arc_ptr.data_ptr(), A, Va, Van, H, W, keep.data_ptr(),
+                                   arc_xy.data_ptr(), _stream()), "dm_simplify_arc_emit")
+    check(lib.dm_simplify_ring_emit(polys.xy.data_ptr(), polys.ring_ptr.data_ptr(), vert_ring.data_ptr(), scan.data_ptr(), ring_ptr.data_ptr(), V, R,
+                                    Vn, H, W, keep.data_ptr(), xy.data_ptr(), area2.data_ptr(), _stream()), "dm_simplify_ring_emit")
+    mark("arc_emit + ring_emit + area")
+    out_polys = Polygons(region_ptr=polys.region_ptr, ring_ptr=ring_ptr, xy=xy, ring_label=polys.ring_label, ring_area2=area2)
+    out_arcs = Arcs(arc_ptr=arc_ptr, xy=arc_xy, left=arcs.left, right=arcs.right)
+    if stats is not None:
+        torch.cuda.synchronize()
+        stats["stage_ms"] = [(b[0], a[1].elapsed_time(b[1])) for a, b in zip(marks[:-1], marks[1:])]
+        stats.update(trace=trace_stats, q=q, arcs=A, rings=R, arc_vertices=Va, vertices=V, kept_arc_vertices=Van, kept_vertices=Vn,
+                     longest_arc=int((arcs.arc_ptr[1:] - arcs.arc_ptr[:-1]).max()))
+    return out_polys, out_arcs, keep
+
+
+def simplify(labels: torch.Tensor, n_labels: int, tolerance: float, stats: Optional[dict] = None,
+             edges: Optional[torch.Tensor] = None) -> Tuple[Polygons, Arcs]:
+    """The rings and boundary arcs of `polygons` / `boundary_arcs`, simplified by Douglas-Peucker to `tolerance` pixels (quantised to
+    1/256 pixel as `rasterize` quantises coordinates; at most 4096), once per stretch of shared boundary: the two neighbours of a
+    boundary get the same vertices, so the simplified polygons still tile the raster without slivers or overlaps, and `lines.shp`
+    and `polygons.shp` written from the two results share every vertex.  Corners where three or more boundaries meet, and the four
+    raster corners, stay put.  H, W <= 32768.
+
+    Same rings and arcs, in the same order, as the tracing gives (`Arcs.edge` from `edges`, as `boundary_arcs` takes them); a ring
+    that collapses stays, with ring_area2 == 0.  At tolerance 0 only the pixel corners inside straight runs are absent, as they are
+    from the tracing, and `rasterize` of the rings is the input raster.  Two different boundaries may cross at a large tolerance, as
+    with any plain Douglas-Peucker.  The rule: include/deepmerge_hip.h, restated in tests/simplify_ref.py; every array is bit-equal
+    to it.  One tracing run plus the passes of csrc/dm_simplify.hip; the input is not modified; the only added readback is the pair
+    of vertex totals.  stats: a dict that receives the time per stage and the sizes (tools/mb_simplify.py)."""
+    polys, arcs, _ = _simplify(labels, n_labels, tolerance, stats)
+    return polys, (arcs if edges is None else _attach_edges(arcs, n_labels, edges))
 
 
 # ---- polygon rings to a label raster (csrc/dm_rasterize.hip; the rule: include/deepmerge_hip.h, DESIGN.md 3.5.6) ----------------------

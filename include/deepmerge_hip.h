@@ -766,6 +766,65 @@ int dm_rasterize_emit(const int32_t *xy, const int64_t *ring_ptr, const int32_t 
                       int32_t V, int32_t R, int64_t N, int32_t H, int32_t W, int64_t n_labels, int64_t *keys, void *stream);
 int dm_rasterize_fill(const int64_t *keys, int64_t N, int32_t H, int32_t W, int32_t fill, int32_t *out, int32_t *error, void *stream);
 
+/* ---- shared-boundary Douglas-Peucker on the traced rings and arcs (additive in ABI 6; csrc/dm_simplify.hip, DESIGN.md 3.5.7,
+ * rag.simplify) ----------------------------------------------------------------------------------------------------------------
+ * The tracing above leaves a pixel staircase.  Simplified per polygon, two neighbours would treat their common boundary
+ * differently and leave slivers and overlaps; here every stretch of boundary is simplified once, as the arc that stores it, and
+ * both neighbours see the result.  The rule is this build's (restated in numpy / Python ints in tests/simplify_ref.py).  All
+ * arithmetic is on integers; nothing depends on the order in which threads arrive or segments are split; results are bit-exact.
+ * The rule.  labels int32 [H,W], 1 <= H, W <= DM_SIMPLIFY_MAX_SIDE (so every |cross| below is under 2^31); corners as above.
+ *   nodes: a corner (x, y), 0 <= x <= W, 0 <= y <= H, is a node iff at least three of its four unit grid edges are boundary
+ *     edges (two different labels across; the outside of the raster counts as label -1), or it is one of the four raster corners.
+ *     Nodes are never removed.  Every other corner on a boundary has exactly two boundary edges, so exactly one chain passes
+ *     through it, once: a keep flag per corner is single-valued.
+ *   chains: an arc of the tracing is cut at every vertex that is a node; an open arc also at its two ends (they are nodes: an arc
+ *     ends where the label across changes).  The kept arc of a pair comes from the smaller label's ring and can run through a
+ *     corner with four boundary edges unbroken: it is cut there.  A closed arc (first vertex == last) is the cyclic sequence of
+ *     its vertices without the repeated end, and without its stored start when that is no node and lies inside a straight run (a
+ *     hole's head dart need not be a vertex dart).  With no node among them the arc has no natural ends: its one chain begins and
+ *     ends at the vertex smallest in (y, x), which is kept.
+ *   Douglas-Peucker on a chain v[0..n-1]; the two ends are kept.  For a segment (i, j) with j > i + 1: d_k =
+ *     |cross(v[j] - v[i], v[k] - v[i])| if v[i] != v[j], else |v[k] - v[i]|^2 (a closed chain's first split); k* = the arg-max of
+ *     d_k over i < k < j, ties to the smallest k.  The tolerance t in pixels is quantised as rasterize quantises coordinates:
+ *     q = floor(256 t + 0.5), 0 <= q <= DM_SIMPLIFY_MAX_Q.  k* is kept, and both halves (i, k*), (k*, j) are split further, iff
+ *     65536 d^2 > q^2 |v[j] - v[i]|^2 (distinct ends) or 65536 d > q^2 (coinciding ends): both exact in 128 bits.
+ *   keep uint8 [(H+1)(W+1)], corner (x, y) at y (W+1) + x: 2 for a node, 1 for a kept chain vertex, 0 otherwise.
+ *   arcs out: the same arcs in the same order, each with its kept vertices in stored order; a closed arc begins at its first kept
+ *     vertex (a stored start that is not kept is rotated away) and repeats that vertex at its end.
+ *   rings out: the same rings in the same order; a ring becomes the kept corners met when walking from each of its vertices to
+ *     the next, one unit step at a time.  The walk inserts the nodes that sit on a straight run of the ring (T-junctions, where a
+ *     neighbour's chain ends): without them the neighbours would no longer share vertices.  area2 is the shoelace sum again; a
+ *     ring left with fewer than three vertices or zero area is still there, with area2 == 0.
+ * Shared boundaries stay shared and nodes stay put.  Two different chains may cross at a large tolerance, as with any plain
+ * Douglas-Peucker; this is not detected.  Every entry point validates before any launch, launches on `stream`, never synchronises
+ * and never allocates; the caller scans the counts and reads back the vertex totals between count and emit (rag.simplify).
+ *
+ * dm_simplify_nodes: keep = 2 at the nodes, 0 elsewhere (every entry is written).
+ * dm_simplify_chains: arc_xy int32 [Va,2], arc_ptr int64 [A+1] as DmVectorTrace leaves them, q as above; keep from
+ *   dm_simplify_nodes gets its 1s.  One wavefront per arc; stack int64 [Va] is its workspace, laid out by arc_ptr: a depth-first
+ *   walk that pushes one half of every split never holds more entries than the chain has interior vertices.  An arc with a vertex
+ *   outside the raster is left alone.
+ * dm_simplify_arc_count: count int32 [A] = the kept vertices of every arc (with the repeated end of a closed arc).
+ * dm_simplify_arc_emit: new_ptr int64 [A+1] = the exclusive scan of count, Vn = new_ptr[A]; out_xy int32 [Vn,2].
+ * dm_simplify_ring_count: xy int32 [V,2], ring_ptr int64 [R+1], vert_ring int32 [V] = the ring of every vertex; count int32 [V] =
+ *   the kept corners on the unit steps from vertex v (included) to its successor within its ring (excluded).
+ * dm_simplify_ring_emit: scan int64 [V+1] = the exclusive scan of count, Vn = scan[V], new_ring_ptr int64 [R+1] = scan at
+ *   ring_ptr; out_xy int32 [Vn,2], area2 int64 [R] (cleared, then summed with integer atomics). */
+#define DM_SIMPLIFY_MAX_SIDE 32768
+#define DM_SIMPLIFY_MAX_Q (1 << 20)
+int dm_simplify_nodes(const int32_t *labels, int32_t H, int32_t W, uint8_t *keep, void *stream);
+int dm_simplify_chains(const int32_t *arc_xy, const int64_t *arc_ptr, int32_t A, int64_t Va, int32_t H, int32_t W, int32_t q, uint8_t *keep,
+                       int64_t *stack, void *stream);
+int dm_simplify_arc_count(const int32_t *arc_xy, const int64_t *arc_ptr, int32_t A, int64_t Va, int32_t H, int32_t W, const uint8_t *keep,
+                          int32_t *count, void *stream);
+int dm_simplify_arc_emit(const int32_t *arc_xy, const int64_t *arc_ptr, const int64_t *new_ptr, int32_t A, int64_t Va, int64_t Vn, int32_t H,
+                         int32_t W, const uint8_t *keep, int32_t *out_xy, void *stream);
+int dm_simplify_ring_count(const int32_t *xy, const int64_t *ring_ptr, const int32_t *vert_ring, int32_t V, int32_t R, int32_t H, int32_t W,
+                           const uint8_t *keep, int32_t *count, void *stream);
+int dm_simplify_ring_emit(const int32_t *xy, const int64_t *ring_ptr, const int32_t *vert_ring, const int64_t *scan, const int64_t *new_ring_ptr,
+                          int32_t V, int32_t R, int64_t Vn, int32_t H, int32_t W, const uint8_t *keep, int32_t *out_xy, int64_t *area2,
+                          void *stream);
+
 /* BatchNorm2d (+ ReLU, + Dropout2d mask) of the auxiliary heads (reference nets/ShfitScaleFormer.py:329-368: Conv2d ->
  * BatchNorm2d -> ReLU -> Dropout2d(0.3)) on the channels-last matrix the convolution GEMM produces: x, y fp32 [M, C] with
  * M = samples * rows_per_sample.  training != 0: batch statistics (biased variance, eps inside the sqrt), running_mean /
