@@ -524,7 +524,9 @@ _DEFER_REDUCTIONS = os.environ.get("DM_DEFER_REDUCTIONS", "1") != "0"      # A/B
 
 
 def relpos_bias_gather(table: torch.Tensor, index32: torch.Tensor, N: int, transposed: bool = False):
-    """Dense bias [H,N,N]; with transposed=True also its per-head transpose -> (bias, bias_t)."""
+    """Dense bias [H,N,N]; with transposed=True also its per-head transpose -> (bias, bias_t).
+    Index entries outside [0, n_bins) are CLAMPED to the nearest bin, whereas relpos_index_csr drops them, so gather and
+    relpos_bias_scatter are adjoint only on in-range indices (the model's index tables never leave the range)."""
     _need_cuda(table, index32)
     n_bins, H = table.shape
     bias = torch.empty((H, N, N), dtype=torch.float32, device=table.device)
@@ -650,7 +652,8 @@ def attention_bwd_split(hi, lo, table, cube, out, dout, lse, B, N, H, D, scale, 
 def relpos_index_csr(index32: torch.Tensor, n_bins: int):
     """CSR inverse of a relative_position_index: (positions int32 [<= N*N], offsets int32 [n_bins+1]) with
     positions[offsets[b]:offsets[b+1]] = the flat entries i*N+j whose index is b, ascending.  Entries outside
-    [0, n_bins) are dropped.  Cached ON the index tensor (the int32 copy of the module's buffer lives as long as the module; a
+    [0, n_bins) are DROPPED (relpos_bias_gather clamps them instead: the two are not adjoint there; the model never
+    produces such entries).  Cached ON the index tensor (the int32 copy of the module's buffer lives as long as the module; a
     process-wide cache with eviction could drop an entry between a trainer's warm-up steps and its graph capture, and the
     rebuild below synchronises -- illegal while a stream is capturing)."""
     key = (index32._version, n_bins)
@@ -694,7 +697,10 @@ def attention_bwd(qkv, bias, out, dout, lse, B, N, H, D, scale, index32=None, n_
 
 
 def relpos_bias_scatter(slab, dtable, B, H, info, n_bins, accumulate=False):
-    """Fold the dense bias-gradient slab of attention_bwd into d(relative_position_bias_table) [n_bins, H]."""
+    """Fold the dense bias-gradient slab of attention_bwd into d(relative_position_bias_table) [n_bins, H].
+    The slab is CONSUMED: with more than one chunk (and H*N*N % 4 == 0, 16-byte aligned) chunk 0 is overwritten by the sum of
+    the chunks before the bins are gathered; pass a clone to keep it.  accumulate=False overwrites every bin (empty ones with
+    0), accumulate=True adds to dtable."""
     _need_cuda(slab, dtable)
     chunks, N, (positions, offsets) = info
     check(_lib.lib().dm_relpos_bias_reduce(slab.data_ptr(), positions.data_ptr(), offsets.data_ptr(), dtable.data_ptr(), chunks, H, N,
