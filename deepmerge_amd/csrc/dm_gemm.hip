@@ -46,8 +46,8 @@ bool dm_gemm_q4_plan(GemmParams &p, const GemmSwitches &sw, int layout, int ab_d
 void dm_gemm_q4_launch(const GemmParams &p, int layout, hipStream_t s);
 int dm_gemm_w4_plan(GemmParams &p, const GemmSwitches &sw, int layout, int ab_dtype, bool aligned8, bool can_split, long long workspace_bytes);   // dm_gemm_w4.hip (grid size, 0 = not taken)
 void dm_gemm_w4_launch(const GemmParams &p, int layout, int grid, hipStream_t s);
-int dm_gemm_w4_grouped(GemmParams *ps, int n, hipStream_t s, bool launch, const DmGroupedExtra &x);      // dm_gemm_w4.hip: n weight gradients in one launch (0 = not taken, 1 = one K slice per tile, 2 = stream-K)
-long long dm_gemm_w4_grouped_ws_bytes();
+bool dm_gemm_w4_grouped_plan(GroupPlan &pl, int mode, const DmGroupedExtra &x);      // dm_gemm_w4.hip: n weight gradients in one launch (false = not taken)
+bool dm_gemm_w4_grouped_launch(const GroupPlan &pl, hipStream_t s);
 
 namespace {
 
@@ -695,6 +695,7 @@ inline GemmSwitches read_switches() {
   if (const char *e = getenv("DM_GEMM_Q4")) sw.q4 = atoi(e);
   if (const char *e = getenv("DM_GEMM_RING")) sw.ring = atoi(e);
   if (const char *e = getenv("DM_GEMM_256")) sw.p256 = atoi(e);
+  if (const char *e = getenv("DM_GEMM_GROUPED")) { const int m = atoi(e); sw.grouped = (m == 0 || m == 2 || m == 4) ? m : 1; }
   if (const char *e = getenv("DM_GEMM_FORCE_TILE")) { sw.force_tile = atoi(e); sw.force_tile_set = true; }
   return sw;
 }
@@ -702,14 +703,14 @@ inline GemmSwitches read_switches() {
 // A/B aid (tools/routing_check.py finds candidates in a cold microbenchmark; the decision is taken INSIDE the step): DM_GEMM_ROUTE names a
 // kernel family for single products, e.g. "NT:16384x2304x768=ring,NN:16384x3072x768=256" (families: w4, ring, 256, 128, 64, q4).  For a named
 // product the call's own copy of the switches is replaced: the named family "whenever legal", every other family off, a forced tile only
-// for 128 / 64.  The environment is not touched.  Never set in production.
-inline void apply_route(GemmSwitches &sw, int layout, int M, int N, int K) {
+// for 128 / 64.  The environment is not touched.  Never set in production.  Returns whether the product was named.
+inline bool apply_route(GemmSwitches &sw, int layout, int M, int N, int K) {
   static const char *const e = getenv("DM_GEMM_ROUTE");      // read once: unset (the product's case) costs nothing per call
-  if (!e || !*e) return;
+  if (!e || !*e) return false;
   char want[64];
   snprintf(want, sizeof(want), "%s:%dx%dx%d=", layout == DM_NT ? "NT" : layout == DM_NN ? "NN" : "TN", M, N, K);
   const char *hit = strstr(e, want);
-  if (!hit) return;
+  if (!hit) return false;
   const char *fam = hit + strlen(want);
   GemmSwitches r;
   r.w4 = r.w4_tn = r.q4 = r.ring = r.p256 = 0;
@@ -719,8 +720,9 @@ inline void apply_route(GemmSwitches &sw, int layout, int M, int N, int K) {
   else if (!strncmp(fam, "128", 3)) { r.force_tile = 128; r.force_tile_set = true; }
   else if (!strncmp(fam, "64", 2)) { r.force_tile = 64; r.force_tile_set = true; }
   else if (!strncmp(fam, "q4", 2)) r.q4 = 2;
-  else return;
+  else return false;
   sw = r;
+  return true;
 }
 
 // 64x64 tiles when the product has too few 128x128 tiles to give every CU its share
@@ -1170,34 +1172,26 @@ extern "C" int dm_gemm(const DmGemmArgs *a, void *stream) {
 }
 
 // n independent products, results as n dm_gemm calls in order would give them (weight gradients: up to the order of the fp32 additions
-// over K).  The products must not overlap in their outputs and none may read another's output.  Fast path: 1 .. 8 bf16 weight gradients
+// over K).  The products must not overlap in their outputs and none may read another's output.  Fast path: 2 .. 8 bf16 weight gradients
 // (DM_TN, plain operands or plane pairs, fp32 C, no epilogue operands, whole 256 x 192 tiles, automatic slice count) in ONE launch of the
-// 4-wave kernel (dm_gemm_w4_grouped: one K slice per tile for short contractions, stream-K + one fix-up launch for long ones; the column sums
-// of A from the same launches).  Anything else: the calls one after the other.
-extern "C" int64_t dm_gemm_grouped_workspace_bytes(const DmGemmArgs *args, int32_t n) {
-  if (args == nullptr || n < 1 || n > 8) return 0;
-  const char *menv = getenv("DM_GEMM_GROUPED");      // only the stream-K form (never chosen by the default rule) takes a group workspace
-  if (!menv || atoi(menv) != 3) return 0;
-  for (int i = 0; i < n; ++i)
-    if (args[i].layout != DM_TN || args[i].ab_dtype != DM_BF16 || args[i].M % 256 != 0 || args[i].N % 192 != 0) return 0;
-  return dm_gemm_w4_grouped_ws_bytes();
-}
-
-extern "C" int dm_gemm_grouped(const DmGemmArgs *args, int32_t n, void *workspace, int64_t workspace_bytes, void *stream) {
+// 4-wave kernel (dm_gemm_w4_grouped_plan: one K slice per tile for short contractions, shared K slices for long ones; the column sums of A
+// from the same launch).  Anything else: the calls one after the other -- also when the 4-wave family is switched off (DM_GEMM_W4=0 /
+// DM_GEMM_W4_TN=0) or DM_GEMM_ROUTE names a member, so that A/B runs measure the route they asked for.
+extern "C" int dm_gemm_grouped(const DmGemmArgs *args, int32_t n, void *stream) {
   DM_REQUIRE(args != nullptr && n >= 1, DM_ERR_BAD_SHAPE, "dm_gemm_grouped: null args / n < 1");
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  bool fast = n <= 8;
-  GemmParams ps[8];
-  float *cs_rows[8] = {nullptr};       // form 1, per product: the row the launch writes when the sums must be ADDED to colsum_a afterwards
+  const GemmSwitches sw = read_switches();
+  bool fast = n <= 8 && sw.w4 != 0 && sw.w4_tn != 0;
+  GroupPlan pl{};
+  float *cs_rows[8] = {nullptr};       // one-slice form, per product: the row the launch writes when the sums must be ADDED to colsum_a afterwards
   DmGroupedExtra x{};
-  x.ws = (workspace && dm_aligned16(workspace)) ? workspace : nullptr;
-  x.ws_bytes = x.ws ? workspace_bytes : 0;
   for (int i = 0; fast && i < n; ++i) {
     const DmGemmArgs &a = args[i];
+    GemmSwitches routed = sw;
     fast = a.layout == DM_TN && a.ab_dtype == DM_BF16 && a.c_dtype == DM_F32 && a.epilogue == DM_EPI_NONE && a.split_k == 0 && a.k_fold >= 0 &&
            a.A && a.B && a.C && !a.bias && !a.residual && !a.aux && a.rows_per_group == 0 && a.M > 0 && a.N > 0 && a.K > 0 &&
            a.M % 8 == 0 && a.N % 8 == 0 && a.lda % 8 == 0 && a.ldb % 8 == 0 && a.ldc % 4 == 0 && a.lda >= a.M && a.ldb >= a.N && a.ldc >= a.N &&
-           dm_aligned16(a.A) && dm_aligned16(a.B) && dm_aligned16(a.C);
+           dm_aligned16(a.A) && dm_aligned16(a.B) && dm_aligned16(a.C) && !apply_route(routed, a.layout, a.M, a.N, a.K);
     if (!fast) break;
     GemmParams p{};
     p.A = a.A; p.B = a.B; p.C = a.C;
@@ -1215,23 +1209,22 @@ extern "C" int dm_gemm_grouped(const DmGemmArgs *args, int32_t n, void *workspac
       p.k_fold = a.k_fold;
     }
     x.cs_out[i] = a.colsum_a;
-    x.cs_acc[i] = a.colsum_accumulate ? 1 : 0;
     // the product's own workspace, cut as dm_gemm cuts it: split-K slab, then the column-sum rows (the sliced form of the group)
     x.slab_bytes[i] = cut_workspace(a.workspace, a.workspace ? a.workspace_bytes : 0, a.M, a.colsum_a != nullptr, x.cs_region[i]);
     x.slab[i] = x.slab_bytes[i] > 0 ? reinterpret_cast<float *>(a.workspace) : nullptr;
     if (a.colsum_a) {
       if (!a.colsum_accumulate) {
-        p.colsum_slab = a.colsum_a;                      // form 1, first write of the step: the launch stores the sums where they belong
+        p.colsum_slab = a.colsum_a;                      // one-slice form, first write of the step: the launch stores the sums where they belong
       } else {
         fast = x.cs_region[i] != nullptr;                // (the workspace holds the column-sum region)
         if (!fast) break;
         p.colsum_slab = cs_rows[i] = x.cs_region[i];
       }
     }
-    ps[i] = p;
+    pl.grp.p[i] = p;
   }
-  const int form = fast ? dm_gemm_w4_grouped(ps, n, s, false, x) : 0;
-  if (form != 0) {
+  pl.grp.n = n;
+  if (fast && dm_gemm_w4_grouped_plan(pl, sw.grouped, x)) {
     double flops = 0, bytes = 0;
     for (int i = 0; i < n; ++i) {
       flops += 2.0 * args[i].M * args[i].N * args[i].K;
@@ -1240,27 +1233,27 @@ extern "C" int dm_gemm_grouped(const DmGemmArgs *args, int32_t n, void *workspac
     char shaped[64];
     const char *pname = "gemm_bf16_TN";
     if (prof_by_shape()) {
-      snprintf(shaped, sizeof(shaped), "gemm_bf16_TN_grouped%d_K%d_%s", n, args[0].K, form == 2 ? "streamk" : form == 3 ? "sliced" : "1slice");
+      snprintf(shaped, sizeof(shaped), "gemm_bf16_TN_grouped%d_K%d_%s", n, args[0].K, pl.form == GroupForm::sliced ? "sliced" : "1slice");
       pname = shaped;
     }
     {
-      DmProfScope prof(pname, s, flops, bytes);      // (stream-K: the fix-up launch is inside the scope, like the reductions of sliced products are not)
-      dm_gemm_w4_grouped(ps, n, s, true, x);
+      DmProfScope prof(pname, s, flops, bytes);      // (the reductions of the sliced form are outside the scope, like those of sliced products)
+      DM_REQUIRE(dm_gemm_w4_grouped_launch(pl, s), DM_ERR_HIP, "dm_gemm_grouped: the grouped kernel's LDS limit could not be set");
     }
-    if (form == 1)
+    if (pl.form == GroupForm::one_slice)
       for (int i = 0; i < n; ++i)
         if (cs_rows[i])
           hipLaunchKernelGGL(colsum_rows_reduce_kernel, dim3((args[i].M + 63) / 64), dim3(64), 0, s, cs_rows[i], args[i].colsum_a, args[i].M, 1, 1);
-    if (form == 3)      // every product's slices summed in slice order, its column-sum rows folded in the same launch (as dm_gemm does)
+    if (pl.form == GroupForm::sliced)      // every product's slices summed in slice order, its column-sum rows folded in the same launch (as dm_gemm does)
       for (int i = 0; i < n; ++i) {
         const DmGemmArgs &a = args[i];
-        const int split = ps[i].split_k;
+        const GemmParams &p = pl.grp.p[i];
         const long long want = ((long long)a.M * a.N / 4 + 255) / 256;
         const int rgrid = (int)(want < 2048 ? want : 2048);
         const bool fold_cs = a.colsum_a != nullptr;
         const int cs_blocks = fold_cs ? (a.M + 255) / 256 : 0;
-        hipLaunchKernelGGL(splitk_reduce_kernel, dim3(rgrid + cs_blocks), dim3(256), 0, s, ps[i].workspace, reinterpret_cast<float *>(a.C), (long long)a.ldc,
-                           a.M, a.N, split, a.accumulate, rgrid, fold_cs ? x.cs_region[i] : nullptr, fold_cs ? a.colsum_a : nullptr, a.M, split,
+        hipLaunchKernelGGL(splitk_reduce_kernel, dim3(rgrid + cs_blocks), dim3(256), 0, s, p.workspace, reinterpret_cast<float *>(a.C), (long long)a.ldc,
+                           a.M, a.N, p.split_k, a.accumulate, rgrid, fold_cs ? x.cs_region[i] : nullptr, fold_cs ? a.colsum_a : nullptr, a.M, p.split_k,
                            a.colsum_accumulate);
       }
     DM_LAUNCH_CHECK("dm_gemm_grouped");

@@ -32,9 +32,10 @@ constexpr int DM_DBG_NO_EPILOGUE = 0x800;    // DM_GEMM_NOEPI=1 (ablation builds
 
 // The per-call modes of the kernel families (0 = off, 1 = routing rules, 2 = whenever legal; the 4-wave kernel knows more: dm_gemm_w4_plan)
 // and the forced tile.  dm_gemm reads them from the environment once per call (DM_GEMM_W4, DM_GEMM_W4_TN, DM_GEMM_Q4, DM_GEMM_RING,
-// DM_GEMM_256, DM_GEMM_FORCE_TILE), lets DM_GEMM_ROUTE edit its copy, and hands it to the plans.
+// DM_GEMM_256, DM_GEMM_GROUPED, DM_GEMM_FORCE_TILE), lets DM_GEMM_ROUTE edit its copy, and hands it to the plans.
 struct GemmSwitches {
   int w4 = 1, w4_tn = 1, q4 = 1, ring = 1, p256 = 1;
+  int grouped = 1;                 // dm_gemm_grouped's one launch: 0 = off, 1 = rule, 2 = one K slice per tile whenever legal, 4 = sliced whenever legal
   int force_tile = 0;              // 64 / 128 force that tile of the register-staged kernel (tuning / A-B aid); anything else does not,
   bool force_tile_set = false;     // but the variable's mere presence turns the forward K slices of that kernel off
 };
@@ -42,10 +43,28 @@ struct GemmSwitches {
 // CUs the one-workgroup-per-CU grids are planned for (dm_gemm.hip)
 int dm_gemm_cu_count();
 
-// dm_gemm_grouped -> dm_gemm_w4_grouped: where the column sums of A go (stream-K form) and the group's workspace
+// dm_gemm_grouped (dm_gemm.hip) -> dm_gemm_w4_grouped_plan / _launch (dm_gemm_w4.hip): n independent weight gradients in one launch.
+namespace dmw4 {
+constexpr int GROUP_MAX = 8;
+struct GemmGroup {                 // the kernel argument: workgroups first[i] .. first[i + 1] - 1 belong to product i
+  GemmParams p[GROUP_MAX];
+  int first[GROUP_MAX + 1];
+  int n;
+};
+}  // namespace dmw4
+// What the sliced form reads per product: whether column sums of A are wanted (cs_out), and the product's own split-K slab / column-sum
+// rows (its dm_gemm workspace, cut as dm_gemm cuts it)
 struct DmGroupedExtra {
-  float *cs_out[8]; int cs_acc[8]; void *ws; long long ws_bytes;
-  float *slab[8]; long long slab_bytes[8]; float *cs_region[8];      // the sliced form: every product's own split-K slab / column-sum rows (its dm_gemm workspace)
+  float *cs_out[8];
+  float *slab[8]; long long slab_bytes[8]; float *cs_region[8];
+};
+enum class GroupForm { none, one_slice, sliced };      // none: the separate calls
+struct GroupPlan {
+  GroupForm form = GroupForm::none;
+  dmw4::GemmGroup grp;             // in: p[0 .. n - 1] and n; out: tiles / slices / slabs of every product, first[]
+  int grid = 0;
+  int ek = 9;                      // lean epilogue instance: 9 = fp32 C written, 11 = accumulated in place
+  bool fold = false, any_cs = false;
 };
 
 // The result strip as a hi / lo plane pair (c_dtype == DM_BF16_PAIR): hi = bf16(v), lo = bf16(v - hi) -- the split of dm_split_bf16.

@@ -379,9 +379,7 @@ def gemm_grouped(calls) -> None:
                             kw.get("epilogue", DM_EPI_NONE), kw.get("aux"), kw.get("ldaux"), kw.get("accumulate", False), kw.get("split_k", 0),
                             kw.get("rows_per_group", 0), kw.get("group_stride", 0), kw.get("colsum_out"), kw.get("colsum_accumulate", False),
                             f"{kw.get('ws_slot', 'gemm')}.g{i}", None, fold, min_slabs=16 if layout == DM_TN else 0)
-    ws_bytes = _lib.lib().dm_gemm_grouped_workspace_bytes(arr, len(calls))
-    ws = workspace(ws_bytes, calls[0][0][1].t.device if isinstance(calls[0][0][1], Planes) else calls[0][0][1].device, "gemm_grouped") if ws_bytes > 0 else None
-    check(_lib.lib().dm_gemm_grouped(arr, len(calls), None if ws is None else ws.data_ptr(), 0 if ws is None else ws.numel(), _stream()), "dm_gemm_grouped")
+    check(_lib.lib().dm_gemm_grouped(arr, len(calls), _stream()), "dm_gemm_grouped")
 
 
 def cast(src: torch.Tensor, dtype: torch.dtype) -> torch.Tensor:
@@ -1709,7 +1707,7 @@ class BlockFn(torch.autograd.Function):
 
         pending = [] if (side is None and (lp or planes) and 0 < M <= _WGRAD_GROUP_TOKENS) else None
         # larger blocks: every product fills the chip with its own K slices, except the small proj gradient (12 tiles: 16 short slices) --
-        # it waits for the qkv gradient and the two share one sliced launch (dm_gemm_grouped's third form)
+        # it waits for the qkv gradient and the two share one sliced launch (dm_gemm_grouped's sliced form)
         late = [] if (pending is None and side is None and (lp or planes) and _WGRAD_PAIR) else None
 
         def wgrad(*a, pair=False, **kw):

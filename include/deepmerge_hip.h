@@ -45,6 +45,7 @@ typedef enum {
 /* ---- library ------------------------------------------------------------------------- */
 int dm_abi_version(void);   /* 2: dm_patch_pyramid / dm_patch_pyramid_cols take a resize rule; 3: table-reading and split-bf16 attention entry points, dm_split_bf16_colsum (round 3);
                              * 4: DmGemmArgs.k_fold / a_fold / b_fold, dm_split_bf16_planes (round 4); 5: dm_pair_batch_gather (round 5); 6: dm_gemm_grouped (round 5);
+                             * 7: dm_gemm_grouped(args, n, stream) without a group workspace, its workspace query removed;
                              * additive in 6: dm_pairwise_distance, dm_pair_epoch_draw, dm_contrastive_terms, dm_pair_eval_summary */
 const char *dm_last_error(void);
 /* Name of the code object architecture the library was built for ("gfx950"). */
@@ -124,25 +125,21 @@ typedef struct {
 int dm_gemm(const DmGemmArgs *args, void *stream);
 /* Bytes of workspace dm_gemm may use for these dimensions (upper bound over split_k choices). */
 int64_t dm_gemm_workspace_bytes(int32_t layout, int32_t M, int32_t N, int32_t K);
-/* ABI 6: n INDEPENDENT products (no output overlaps another product's operands or output), results as n dm_gemm calls in order --
- * weight gradients up to the order of the fp32 additions over K.  The four weight gradients of a transformer block (dW = dy^T x for
- * qkv / proj / fc1 / fc2: nets/ShfitScaleFormer.py:35, :119, :134 and vit_model.py:112-135, :160-176 under autograd) feed nothing else
- * in the block's backward pass.  Alone each has 12 .. 48 output tiles of 256 x 192: it either leaves most CUs idle or pays up to 16 K
- * slices, a slab round trip of as many partial gradients and a reduction launch.  Fast path: 1 .. 8 bf16 DM_TN products (plain operands
- * or hi / lo plane pairs through k_fold; fp32 C, no epilogue operands, split_k == 0, M % 256 == N % 192 == 0, K % 128 == 0) in ONE launch:
- *   contraction <= 12288, 2+ products, all tiles within one round of the CUs: one K slice per tile, the gradient stored / accumulated
- *   in place (the form the training step uses: -3.0 % on the headline step);
- *   contraction > 12288, the same for all products, tiles x slices >= 0.85 of the CUs: the SAME K slices for every product, (product,
+/* ABI 6, three arguments since ABI 7: n INDEPENDENT products (no output overlaps another product's operands or output), results as n dm_gemm
+ * calls in order -- weight gradients up to the order of the fp32 additions over K.  The four weight gradients of a transformer block (dW = dy^T x
+ * for qkv / proj / fc1 / fc2: nets/ShfitScaleFormer.py:35, :119, :134 and vit_model.py:112-135, :160-176 under autograd) feed nothing else in the
+ * block's backward pass.  Alone each has 12 .. 48 output tiles of 256 x 192: it either leaves most CUs idle or pays up to 16 K slices, a slab
+ * round trip of as many partial gradients and a reduction launch.  Fast path: 2 .. 8 bf16 DM_TN products (plain operands or hi / lo plane pairs
+ * through k_fold; fp32 C, no epilogue operands, split_k == 0, M % 256 == N % 192 == 0, K % 128 == 0) in ONE launch, in one of two forms:
+ *   one-slice: contraction <= 12288, all tiles within one round of the CUs, the same `accumulate` for all: one K slice per tile, the gradient
+ *   stored / accumulated in place (the form the training step uses: -3.0 % on the headline step);
+ *   sliced: contraction > 12288, the same for all products, tiles x slices >= 0.85 of the CUs: the SAME K slices for every product, (product,
  *   tile, slice) per workgroup, partial tiles to each product's own workspace slab and its own reduction behind (the 12-tile proj gradient
- *   next to the qkv gradient: 5 slices on 240 workgroups instead of 16 + 7 on two launches; -1.1 % on the headline step);
- *   DM_GEMM_GROUPED=3, with `workspace` (dm_gemm_grouped_workspace_bytes): "stream-K" -- every workgroup takes the same number of
- *   consecutive K steps of its product's tile-major step space, a tile is left as 2-3 partial pieces and ONE fix-up launch sums them in
- *   workgroup order (deterministic).  Exact, tested, and slower than the separate launches (no operand panel is shared between
- *   workgroups that sit at different K offsets: csrc/dm_gemm_w4.hip); never chosen by the default rule.
- * colsum_a is produced by the same launches.  Every other group: the calls one after the other (same errors as dm_gemm).  Each args[i]
- * carries its own workspace, as for dm_gemm; `workspace` (16-byte aligned, may be NULL) belongs to the group. */
-int64_t dm_gemm_grouped_workspace_bytes(const DmGemmArgs *args, int32_t n);
-int dm_gemm_grouped(const DmGemmArgs *args, int32_t n, void *workspace, int64_t workspace_bytes, void *stream);
+ *   next to the qkv gradient: 5 slices on 240 workgroups instead of 16 + 7 on two launches; -1.1 % on the headline step).
+ * colsum_a is produced by the same launch.  Every other group: the calls one after the other (same errors as dm_gemm) -- also when
+ * DM_GEMM_GROUPED=0, DM_GEMM_W4=0 or DM_GEMM_W4_TN=0 is set or DM_GEMM_ROUTE names a member (A/B runs; DM_GEMM_GROUPED=2 / 4: the one-slice /
+ * sliced form whenever legal).  Each args[i] carries its own workspace, as for dm_gemm; the group has none. */
+int dm_gemm_grouped(const DmGemmArgs *args, int32_t n, void *stream);
 
 /* ---- fused attention with 3-D relative-position bias -------------------------------------
  * Replaces nets/ShfitScaleFormer.py:119-133 (reshape/permute, q*scale, q@k^T, bias add, softmax,

@@ -98,3 +98,65 @@ def test_gemm_route_overrides_per_product_and_leaves_the_environment(force_tile)
     assert p["exact"], p
     # the process environment is what the child was started with
     assert got["env"] == plain
+
+
+# ---- dm_gemm_grouped: the one launch honours the family switches and DM_GEMM_ROUTE ----------------------------------------------------
+# The smallest legal group: two bf16 DM_TN products of one 256 x 192 tile and two K steps each, both with column sums.  The rule leaves
+# so small a group to the separate calls; DM_GEMM_GROUPED=2 takes the one-slice form whenever it is legal.
+GROUP_SPEC = ("TN", 256, 192, 128)
+
+GROUP_CHILD = r"""
+import json, sys
+sys.path.insert(0, sys.argv[1])
+import torch
+from deepmerge_amd import _lib, ops
+from deepmerge_amd._lib import DM_TN
+
+dev, lib = "cuda:0", _lib.lib()
+_, M, N, K = json.loads(sys.argv[2])
+g = torch.Generator(device=dev); g.manual_seed(M + N + K)
+calls, want = [], []
+for i in range(2):
+    dy = torch.randint(-1, 2, (K, M), device=dev, generator=g).to(torch.bfloat16)
+    x = torch.randint(-1, 2, (K, N), device=dev, generator=g).to(torch.bfloat16)
+    dw = torch.full((M, N), float("nan"), device=dev)
+    db = torch.full((M,), float("nan"), device=dev)
+    calls.append(((DM_TN, dy, x, dw, M, N, K), dict(lda=M, ldb=N, ldc=N, colsum_out=db)))
+    want.append((dy.float().T @ x.float(), dy.float().sum(0), dw, db))
+lib.dm_prof_enable(1)
+ops.gemm_grouped(calls)
+torch.cuda.synchronize()
+lib.dm_prof_enable(0)
+rows = (_lib.DmProfRow * 64)()
+n = lib.dm_prof_collect(rows, 64)
+# dm_prof_collect sums the launches of one name into one row: one entry per launch here
+names = [rows[i].name.decode() for i in range(n) for _ in range(rows[i].launches)]
+print("RESULT " + json.dumps({"rows": names, "exact": [bool(torch.equal(dw, w_dw) and torch.equal(db, w_db)) for w_dw, w_db, dw, db in want]}))
+"""
+
+
+@pytest.mark.parametrize("extra,n_rows,grouped,codes", [
+    ({}, 1, True, None),                                            # the one-slice form, one launch
+    ({"DM_GEMM_W4_TN": "0"}, 2, False, "not1924"),                  # the 4-wave weight-gradient form off: the separate calls, elsewhere
+    ({"DM_GEMM_W4": "0"}, 2, False, "not1924"),                     # the 4-wave family off: the same
+    ({"DM_GEMM_ROUTE": "TN:256x192x128=64"}, 2, False, 64),         # a member is routed: the separate calls, each routed by dm_gemm
+], ids=["grouped", "w4_tn_off", "w4_off", "routed"])
+def test_gemm_grouped_honours_family_switches_and_route(extra, n_rows, grouped, codes):
+    """Before ABI 7 the grouped fast path ignored DM_GEMM_W4 / DM_GEMM_W4_TN / DM_GEMM_ROUTE, so an A/B run of the grouped products
+    measured the 4-wave kernel whatever it had asked for.  A "row" is one profiler record (one launch scope)."""
+    env = {k: v for k, v in os.environ.items() if k not in KEYS + ("DM_GEMM_ROUTE", "DM_GEMM_GROUPED")}
+    env.update(DM_GEMM_GROUPED="2", DM_PROF_SHAPES="1", **extra)
+    run = subprocess.run([sys.executable, "-c", GROUP_CHILD, ROOT, json.dumps(GROUP_SPEC)], env=env, cwd=ROOT,
+                         capture_output=True, text=True, timeout=300)
+    assert run.returncode == 0, run.stdout[-2000:] + run.stderr[-4000:]
+    got = json.loads([l for l in run.stdout.splitlines() if l.startswith("RESULT ")][-1][len("RESULT "):])
+    print(json.dumps(got, indent=1))
+    rows = got["rows"]
+    assert len(rows) == n_rows, rows
+    if grouped:
+        assert "grouped2" in rows[0] and "1slice" in rows[0], rows
+    else:
+        assert not any("grouped" in r for r in rows), rows
+        got_codes = [int(r.rsplit("_t", 1)[1]) for r in rows]
+        assert all(c != 1924 for c in got_codes) if codes == "not1924" else got_codes == [codes, codes], rows
+    assert got["exact"] == [True, True], got

@@ -941,14 +941,12 @@ def test_gemm_wgrad_with_fused_column_sums(M, N, K):
 
 
 @pytest.mark.parametrize("T,acc", [(1024, False), (4096, False), (4096, True), (1152, True), (8192, False), (16384, True), (9216, False), (50432, False)])
-def test_gemm_grouped_block_weight_gradients(T, acc, monkeypatch, sk=False):
-    if sk:
-        monkeypatch.setenv("DM_GEMM_GROUPED", "3")
+def test_gemm_grouped_block_weight_gradients(T, acc):
     """dm_gemm_grouped: the four weight gradients of a block (dW = dy^T x for qkv / proj / fc1 / fc2, nets/ShfitScaleFormer.py:35, :119,
     :134 under autograd) in ONE launch of the 4-wave kernel -- 144 tiles, one K slice each, up to 12288 tokens; the separate calls
     beyond (16384 = the headline's stage 0, 50432 = ViT-B/16 at 128 pairs) -- the bias gradients from the same launch.  Exact on integer
     data (so the order of the fp32 additions does not matter): equal to the separate dm_gemm calls bit for bit, with `accumulate` /
-    `colsum_accumulate` honoured.  (test_gemm_grouped_stream_k_*: the same groups through the stream-K form.)"""
+    `colsum_accumulate` honoured."""
     ops = _ops()
     from deepmerge_amd._lib import DM_TN
     g = torch.Generator(device=DEV); g.manual_seed(T + int(acc))
@@ -968,12 +966,11 @@ def test_gemm_grouped_block_weight_gradients(T, acc, monkeypatch, sk=False):
         assert torch.equal(db, w_db), f"product {k}: bias gradient"
 
 
-@pytest.mark.parametrize("T,acc,sk", [(1024, False, False), (4096, True, False), (8192, False, True)])
-def test_gemm_grouped_plane_pair_weight_gradients(T, acc, sk, monkeypatch):
+@pytest.mark.parametrize("T,acc", [(1024, False), (4096, True), (8192, False)])
+def test_gemm_grouped_plane_pair_weight_gradients(T, acc):
     """The grouped launch on hi / lo plane pairs (the "bf16x3" products of the tolerance mode): dW = hi^T hi + hi^T lo + lo^T hi and
-    db = colsum(hi) + colsum(lo), exact on data whose pieces, products and partial sums are exactly representable.  sk: the stream-K form."""
-    if sk:
-        monkeypatch.setenv("DM_GEMM_GROUPED", "3")
+    db = colsum(hi) + colsum(lo), exact on data whose pieces, products and partial sums are exactly representable.  (8192: the one-slice form
+    at the longest plane-pair contraction of the small stages.)"""
     ops = _ops()
     from deepmerge_amd._lib import DM_TN
     g = torch.Generator(device=DEV); g.manual_seed(3 * T + int(acc))
@@ -998,21 +995,13 @@ def test_gemm_grouped_plane_pair_weight_gradients(T, acc, sk, monkeypatch):
         assert torch.equal(db, w_db), f"product {k}: bias gradient"
 
 
-@pytest.mark.parametrize("T,acc", [(4096, False), (8192, False), (16384, True), (50432, False)])
-def test_gemm_grouped_stream_k_block_weight_gradients(T, acc, monkeypatch):
-    """The block's four weight gradients through the stream-K form (DM_GEMM_GROUPED=3: equal runs of K steps per workgroup across tile
-    boundaries, partial pieces summed in workgroup order by one fix-up launch): exact."""
-    test_gemm_grouped_block_weight_gradients(T, acc, monkeypatch, sk=True)
-
-
 @pytest.mark.parametrize("shapes,T", [([(768, 768)], 16384), ([(768, 768), (2304, 768)], 9216), ([(256, 192), (3072, 768), (768, 3072)], 12288),
                                       ([(3072, 3072), (768, 768)], 8192)])
-def test_gemm_grouped_stream_k_uneven_groups(shapes, T, monkeypatch):
-    """The stream-K form on groups whose products differ in tile count (1 .. 192 tiles: the workgroups are dealt in proportion to the K
-    steps), a single product, and a product with more tiles than its share of workgroups (pieces longer than a tile: three slots)."""
+def test_gemm_grouped_uneven_groups(shapes, T):
+    """dm_gemm_grouped on groups whose products differ in tile count (1 .. 192 tiles), a single product, and a group with more tiles than
+    CUs, through whatever the rule picks for them: the one-slice form, the sliced form or the separate calls."""
     ops = _ops()
     from deepmerge_amd._lib import DM_TN
-    monkeypatch.setenv("DM_GEMM_GROUPED", "3")
     g = torch.Generator(device=DEV); g.manual_seed(T + len(shapes))
     calls, want = [], []
     for (m, n) in shapes:
@@ -1030,7 +1019,7 @@ def test_gemm_grouped_stream_k_uneven_groups(shapes, T, monkeypatch):
 @pytest.mark.parametrize("shapes,T,acc,force", [([(768, 768), (2304, 768)], 16384, False, False), ([(768, 768), (2304, 768)], 50432, True, False),
                                                   ([(768, 3072), (3072, 768), (768, 768), (2304, 768)], 4096, False, True)])
 def test_gemm_grouped_sliced_form(shapes, T, acc, force, monkeypatch):
-    """dm_gemm_grouped's third form: the products of the group share ONE launch with the same K slices -- the proj gradient (12 tiles) next
+    """dm_gemm_grouped's sliced form: the products of the group share ONE launch with the same K slices -- the proj gradient (12 tiles) next
     to the qkv gradient (36) of a 16384-token block: 5 slices on 240 workgroups instead of 16 + 7 on two launches -- partial tiles to each
     product's own slab, summed in slice order by its own reduction.  Exact on integer data; column sums and `accumulate` honoured."""
     ops = _ops()

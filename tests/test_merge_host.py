@@ -136,7 +136,7 @@ def test_folded_graph_and_statistics_equal_those_of_the_relabelled_raster(built,
 def test_merge_entry_points_validate_before_any_launch(built):
     from deepmerge_amd._lib import DmMergeFold
     lib = built.lib()
-    assert lib.dm_abi_version() == 6
+    assert lib.dm_abi_version() == 7
     p = 4096                                                       # any non-null address: validation never dereferences
     cases = [
         (lambda: lib.dm_merge_best(None, p, 4, 4, 1.0, p, None), b"dm_merge_best: null pointer"),

@@ -150,7 +150,7 @@ NEW = ("dm_label_clearance", "dm_point_select_round", "dm_point_emit")
 def test_header_signatures_and_exports_agree_and_abi_is_still_6(built):
     import ctypes
     lib = built.lib()
-    assert lib.dm_abi_version() == 6
+    assert lib.dm_abi_version() == 7
     declared = built.declared_symbols()
     raw = ctypes.CDLL(built.LIB_PATH)
     for name in NEW:

@@ -187,7 +187,7 @@ def test_entries_validate_before_any_launch(built_lib):
     assert lib.dm_rasterize_fill(p, 6, 0, 8, -1, p, p, None) == -1 and b"H=0" in lib.dm_last_error()
     assert lib.dm_rasterize_fill(p, 5, 8, 8, -1, p, p, None) == -1 and b"N even" in lib.dm_last_error()
     assert lib.dm_rasterize_fill(p, 6, 8, 8, 0, p, p, None) == -1 and b"fill < 0" in lib.dm_last_error()
-    assert lib.dm_abi_version() == 6                            # the new symbols are additive
+    assert lib.dm_abi_version() == 7                            # the new symbols are additive
 
 
 def test_rasterize_has_no_cpu_fallback(built_lib):
