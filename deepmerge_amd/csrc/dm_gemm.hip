@@ -373,15 +373,6 @@ __global__ __launch_bounds__(NTHREADS, (TM == 4 ? WG_PER_CU : 4)) void gemm_kern
       }
     }
   }
-#ifdef DM_GEMM_ABLATE
-  if (p.debug & DM_DBG_NO_EPILOGUE) {                 // (ablation builds, DM_GEMM_NOEPI=1: no epilogue at all -- what the K loops alone cost; the asm keeps the MFMAs alive)
-#pragma unroll
-    for (int i = 0; i < TM; ++i)
-#pragma unroll
-      for (int j = 0; j < TM; ++j) asm volatile("" ::"v"(acc[i][j]));
-    return;
-  }
-#endif
   if (p.split_k > 1) {
     float *W = p.workspace + (long long)z * p.M * p.N;
 #pragma unroll
@@ -687,6 +678,34 @@ void launch_mfma(const GemmParams &p, int layout, int grid, hipStream_t s) {
   }
 }
 
+}  // namespace
+
+// The one place the once-per-process part of the environment is read (GemmTuning, dm_gemm_common.h): each value keeps the parse it had
+// where it was used.
+const GemmTuning &dm_gemm_tuning() {
+  static const GemmTuning tuning = [] {
+    GemmTuning t;
+    auto off_char = [](const char *e) { return e && e[0] == '0'; };
+    auto off_int = [](const char *e) { return e && atoi(e) == 0; };
+    if (const char *e = getenv("DM_GEMM_FWD_SPLIT")) t.fwd_split = atoi(e);
+    t.skinny = !off_int(getenv("DM_GEMM_SKINNY"));
+    if (const char *e = getenv("DM_GEMM_GROUP_M")) t.group_m = atoi(e);
+    if (const char *e = getenv("DM_GEMM_256_GROUP_M")) t.p256_group_m = atoi(e);
+    if (const char *e = getenv("DM_GEMM_256_TN_MINK")) t.p256_tn_mink = atoi(e);
+    if (const char *e = getenv("DM_GEMM_256_NT_LONGK")) t.p256_nt_longk = atoi(e);
+    t.fold_routes = !off_int(getenv("DM_GEMM_FOLD_ROUTES"));
+    if (const char *e = getenv("DM_GEMM_CUS_RESERVED")) t.cus_reserved = atoi(e);
+    t.t128_rows_off = off_char(getenv("DM_GEMM_T128_ROWS"));
+    t.t128_touch_off = off_char(getenv("DM_GEMM_T128_TOUCH"));
+    t.epi_lean_off = off_char(getenv("DM_GEMM_EPI_LEAN"));
+    t.route = getenv("DM_GEMM_ROUTE");
+    return t;
+  }();
+  return tuning;
+}
+
+namespace {
+
 // The family switches as the environment has them NOW: read on every call (tests and A/B tools flip them between calls).
 inline GemmSwitches read_switches() {
   GemmSwitches sw;
@@ -694,6 +713,7 @@ inline GemmSwitches read_switches() {
   if (const char *e = getenv("DM_GEMM_W4_TN")) sw.w4_tn = atoi(e);
   if (const char *e = getenv("DM_GEMM_Q4")) sw.q4 = atoi(e);
   if (const char *e = getenv("DM_GEMM_RING")) sw.ring = atoi(e);
+  if (const char *e = getenv("DM_GEMM_RING_WM")) sw.ring_wm = atoi(e);
   if (const char *e = getenv("DM_GEMM_256")) sw.p256 = atoi(e);
   if (const char *e = getenv("DM_GEMM_GROUPED")) { const int m = atoi(e); sw.grouped = (m == 0 || m == 2 || m == 4) ? m : 1; }
   if (const char *e = getenv("DM_GEMM_FORCE_TILE")) { sw.force_tile = atoi(e); sw.force_tile_set = true; }
@@ -705,7 +725,7 @@ inline GemmSwitches read_switches() {
 // product the call's own copy of the switches is replaced: the named family "whenever legal", every other family off, a forced tile only
 // for 128 / 64.  The environment is not touched.  Never set in production.  Returns whether the product was named.
 inline bool apply_route(GemmSwitches &sw, int layout, int M, int N, int K) {
-  static const char *const e = getenv("DM_GEMM_ROUTE");      // read once: unset (the product's case) costs nothing per call
+  const char *const e = dm_gemm_tuning().route;               // read once: unset (the product's case) costs nothing per call
   if (!e || !*e) return false;
   char want[64];
   snprintf(want, sizeof(want), "%s:%dx%dx%d=", layout == DM_NT ? "NT" : layout == DM_NN ? "NN" : "TN", M, N, K);
@@ -751,7 +771,7 @@ int choose_split(int tiles, int K, int bk) {
 // order and passed through the fused epilogue by splitk_epilogue_kernel.  Returns the slice count (1 = no split) and the tile.
 inline int plan_fwd_split(int layout, int M, int N, int K, int &tile) {
   tile = 0;
-  static const int mode = [] { const char *e = getenv("DM_GEMM_FWD_SPLIT"); return e ? atoi(e) : 1; }();      // 0 = off (A/B runs)
+  const int mode = dm_gemm_tuning().fwd_split;      // DM_GEMM_FWD_SPLIT: 0 = off (A/B runs)
   if (mode == 0 || layout == DM_TN || N % 8 != 0 || K < 1536) return 1;
   const long long t128 = (long long)((M + 127) / 128) * ((N + 127) / 128);
   if (t128 >= 256) return 1;                       // enough tiles without slices
@@ -759,7 +779,7 @@ inline int plan_fwd_split(int layout, int M, int N, int K, int &tile) {
   while (split > 1 && K / split < 8 * 64) split >>= 1;      // >= 8 K stages per slice
   if (split <= 1) return 1;
   // (128 x 128 tiles x 4 slices for the M = 4096 products measured no faster than unsplit 64 x 64 tiles -- the slab round trip eats the
-  // gain; those go to the 4-wave kernel's slices, dm_gemm_w4_plan -- so this path serves what is left: M <= 1024)
+  // gain -- so this path serves what is left: M <= 1024)
   if (t128 * split >= 512) return 1;
   tile = 64;
   return split;
@@ -804,8 +824,7 @@ int dm_gemm_cu_count() {
     int dev = 0, cus = 0;
     if (hipGetDevice(&dev) != hipSuccess) return 0;
     if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) return 0;
-    const char *e = getenv("DM_GEMM_CUS_RESERVED");
-    const int r = e ? atoi(e) : 0;
+    const int r = dm_gemm_tuning().cus_reserved;
     return (r > 0 && r < cus) ? cus - r : cus;
   }();
   return n;
@@ -819,7 +838,7 @@ static bool prof_by_shape() {
 
 extern "C" int64_t dm_gemm_workspace_bytes(int32_t layout, int32_t M, int32_t N, int32_t K) {
   if (layout != DM_TN) {
-    // forward / dgrad K slices (plan_fwd_split, dm_gemm_w4_plan): at most 4 partial tiles
+    // forward / dgrad K slices (plan_fwd_split): at most 4 partial tiles
     const long long t128 = (long long)((M + 127) / 128) * ((N + 127) / 128);
     const long long t16 = (long long)((M + 15) / 16) * ((N + 15) / 16);
     const int64_t skinny = (K >= 1024 && t16 <= 128) ? (int64_t)32 * M * N * 4 : 0;      // K slices of the generic fp32 path
@@ -868,20 +887,13 @@ int prof_family_code(const GemmPlan &pl) {
   }
 }
 
-// p.debug of a launch, written here and nowhere else: the ring kernel's ablation code (DM_RING_DEBUG, read per call, ring launches only)
-// with the epilogues' A/B bits on top.  The plans run before this and see p.debug == 0.
+// p.debug of a launch, written here and nowhere else: the epilogues' A/B bits.  The plans run before this and see p.debug == 0.
 int gemm_debug_bits(bool ring) {
+  const GemmTuning &t = dm_gemm_tuning();
   int debug = 0;
-  if (ring) { const char *e = getenv("DM_RING_DEBUG"); debug = e ? atoi(e) : 0; }
-  static const bool rows_off = [] { const char *e = getenv("DM_GEMM_T128_ROWS"); return e && e[0] == '0'; }();   // A/B aid: 4-column epilogue in the 128x128 kernel
-  if (rows_off && !ring) debug |= DM_DBG_ROWS_OFF;
-  static const bool touch_off = [] { const char *e = getenv("DM_GEMM_T128_TOUCH"); return e && e[0] == '0'; }();  // A/B aid: no early touch of the epilogue operands
-  if (touch_off) debug |= DM_DBG_TOUCH_OFF;
-  static const bool lean_off = [] { const char *e = getenv("DM_GEMM_EPI_LEAN"); return e && e[0] == '0'; }();     // A/B aid: the generic whole-line epilogue (dm_gemm_common.h)
-  if (lean_off) debug |= DM_DBG_LEAN_OFF;
-#ifdef DM_GEMM_ABLATE
-  { const char *e = getenv("DM_GEMM_NOEPI"); if (e && e[0] == '1') debug |= DM_DBG_NO_EPILOGUE; }
-#endif
+  if (t.t128_rows_off && !ring) debug |= DM_DBG_ROWS_OFF;      // 4-column epilogue in the 128x128 kernel
+  if (t.t128_touch_off) debug |= DM_DBG_TOUCH_OFF;             // no early touch of the epilogue operands
+  if (t.epi_lean_off) debug |= DM_DBG_LEAN_OFF;                // the generic whole-line epilogue (dm_gemm_common.h)
   return debug;
 }
 
@@ -964,7 +976,7 @@ int gemm_generic(GemmCall &c) {
   dim3 grid((a->N + 15) / 16, (a->M + 15) / 16);
   // skinny products with a long contraction (the head: 64 x 100 over 3840 features = 28 tiles, 36 us on 28 workgroups): K slices
   // over gridDim.z, summed in slice order by a second small launch.  DM_GEMM_SKINNY=0 for A/B runs.
-  static const bool skinny_on = [] { const char *e = getenv("DM_GEMM_SKINNY"); return !(e && atoi(e) == 0); }();
+  const bool skinny_on = dm_gemm_tuning().skinny;
   const long long tiles16 = (long long)grid.x * grid.y;
   int slices = 1;
   if (skinny_on && a->workspace && !a->colsum_a && a->K >= 1024 && tiles16 <= 128) {
@@ -1012,24 +1024,21 @@ int gemm_plan(GemmCall &c, GemmPlan &pl) {
   const bool ring_aligned = (a->ldc % 8 == 0) && (a->aux == nullptr || a->ldaux % 8 == 0) &&
                             (a->rows_per_group == 0 || a->group_stride % 8 == 0) && a->split_k <= 1 && !a->colsum_a;
   const bool w4_ok = (a->layout == DM_TN) ? (a->split_k == 0 && a->ldc % 4 == 0) : ring_aligned;     // wgrad: automatic slice count only
-  // forward / dgrad K slices (w4: (tile, slice) per workgroup; 128 x 128 / 64 x 64: plan_fwd_split): bf16, automatic slice count only, the
+  // forward / dgrad K slices (plan_fwd_split): bf16, automatic slice count only, the
   // 8-column epilogue of splitk_epilogue_kernel must be legal, and the caller's workspace holds the slab
   const bool fwd_slices_ok = a->layout != DM_TN && a->ab_dtype == DM_BF16 && a->split_k == 0 && ring_aligned && a->N % 8 == 0 &&
                              (a->residual == nullptr || a->ldr % 8 == 0) && a->workspace != nullptr && slab_bytes > 0;
   GemmSwitches sw = read_switches();
   apply_route(sw, a->layout, a->M, a->N, a->K);
   p.workspace = reinterpret_cast<float *>(a->workspace);
-  {
-    static const int forced = [] { const char *e = getenv("DM_GEMM_GROUP_M"); return e ? atoi(e) : -1; }();
-    p.group_m = forced >= 0 ? forced : 8;   // measured over the encoder's step: 8 > 4 > 0 (column-fastest) > 16 > 32, within 2 %
-  }
+  p.group_m = dm_gemm_tuning().group_m >= 0 ? dm_gemm_tuning().group_m : 8;   // measured over the encoder's step: 8 > 4 > 0 (column-fastest) > 16 > 32, within 2 %
 
   // the 4-wave register-staged persistent kernel, then the four-workgroups-per-CU 128 x 128 tiles (dm_gemm_q4.hip) for the short-contraction
   // forward / dgrad products, then the ring kernel, then the 256x256 pipeline, then the register-staged tiles.  A plan that takes the
   // product fills p.tiles_m / tiles_n / split_k / k_per_split.
   pl = GemmPlan{};
   pl.family = GemmFamily::TILE;
-  if (w4_ok && (pl.w4_grid = dm_gemm_w4_plan(p, sw, a->layout, a->ab_dtype, true, a->layout == DM_TN ? can_split : fwd_slices_ok, slab_bytes)) != 0)
+  if (w4_ok && (pl.w4_grid = dm_gemm_w4_plan(p, sw, a->layout, a->ab_dtype, true, can_split, slab_bytes)) != 0)
     pl.family = GemmFamily::W4;
   else if (dm_gemm_q4_plan(p, sw, a->layout, a->ab_dtype, ring_aligned))
     pl.family = GemmFamily::Q4;
@@ -1040,7 +1049,6 @@ int gemm_plan(GemmCall &c, GemmPlan &pl) {
 
   if (pl.family != GemmFamily::TILE) {
     pl.split = p.split_k;
-    pl.fwd_split = pl.family == GemmFamily::W4 && a->layout != DM_TN && p.split_k > 1;      // the 4-wave kernel planned slices
   } else {
     pl.tile = pick_tile(sw, a->layout, a->M, a->N, a->K);
     const int bk = (a->ab_dtype == DM_BF16) ? 64 : 32;

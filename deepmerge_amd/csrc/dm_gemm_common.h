@@ -15,7 +15,7 @@ struct GemmParams {
   int tiles_m, tiles_n, split_k, k_per_split;
   int group_m;   // > 0: tiles are walked in bands of group_m row tiles, rows fastest inside a band (L2 reuse)
   float *workspace;
-  int debug;     // ring kernel ablations (-DDM_RING_ABLATE builds, DM_RING_DEBUG: 1 no DMA in the loop, 2 no MFMA, 4 no fragment reads, 8 no stores); 0 in production
+  int debug;     // A/B aids of the epilogues (DM_DBG_* below); 0 in production
   float *colsum_slab;   // TN pipeline: partial column sums of A, [split_k * 4][M] (NULL: not wanted)
   // Folded contraction ("bf16x3" products on hi / lo plane pairs, DmGemmArgs.k_fold): K = 3 * k_fold; K segment s of A starts a_fold[s]
   // elements behind A (b_fold: B) and is addressed inside the segment as a plain operand of contraction length k_fold.  0: plain.
@@ -24,21 +24,39 @@ struct GemmParams {
   long long c_plane;    // c_dtype == DM_BF16_PAIR: element offset of the lo plane behind C (the hi plane)
 };
 
-// p.debug bits above the ring kernel's ablation codes: A/B aids of the epilogues, set by dm_gemm (gemm_debug_bits) and read on the device
+// p.debug bits: A/B aids of the epilogues, set by dm_gemm (gemm_debug_bits) and read on the device
 constexpr int DM_DBG_ROWS_OFF = 0x100;       // DM_GEMM_T128_ROWS=0: 4-column epilogue in the 128x128 kernel
 constexpr int DM_DBG_TOUCH_OFF = 0x200;      // DM_GEMM_T128_TOUCH=0: no early touch of the epilogue operands
 constexpr int DM_DBG_LEAN_OFF = 0x400;       // DM_GEMM_EPI_LEAN=0: the generic whole-line epilogue
-constexpr int DM_DBG_NO_EPILOGUE = 0x800;    // DM_GEMM_NOEPI=1 (ablation builds): no epilogue at all
 
 // The per-call modes of the kernel families (0 = off, 1 = routing rules, 2 = whenever legal; the 4-wave kernel knows more: dm_gemm_w4_plan)
 // and the forced tile.  dm_gemm reads them from the environment once per call (DM_GEMM_W4, DM_GEMM_W4_TN, DM_GEMM_Q4, DM_GEMM_RING,
-// DM_GEMM_256, DM_GEMM_GROUPED, DM_GEMM_FORCE_TILE), lets DM_GEMM_ROUTE edit its copy, and hands it to the plans.
+// DM_GEMM_RING_WM, DM_GEMM_256, DM_GEMM_GROUPED, DM_GEMM_FORCE_TILE), lets DM_GEMM_ROUTE edit its copy, and hands it to the plans.
 struct GemmSwitches {
   int w4 = 1, w4_tn = 1, q4 = 1, ring = 1, p256 = 1;
+  int ring_wm = 0;                 // DM_GEMM_RING_WM: 8 / 4 force that wave height of the ring kernel
   int grouped = 1;                 // dm_gemm_grouped's one launch: 0 = off, 1 = rule, 2 = one K slice per tile whenever legal, 4 = sliced whenever legal
   int force_tile = 0;              // 64 / 128 force that tile of the register-staged kernel (tuning / A-B aid); anything else does not,
   bool force_tile_set = false;     // but the variable's mere presence turns the forward K slices of that kernel off
 };
+
+// What the environment is asked ONCE per process (dm_gemm_tuning, dm_gemm.hip: the first call reads all of it): tuning values and A/B aids
+// of the plans and launches.  Never set in production.
+struct GemmTuning {
+  int fwd_split = 1;               // DM_GEMM_FWD_SPLIT: 0 = no forward / dgrad K slices on 64 x 64 tiles
+  bool skinny = true;              // DM_GEMM_SKINNY=0: no K slices on the generic fp32 path
+  int group_m = -1;                // DM_GEMM_GROUP_M >= 0: GemmParams.group_m of every launch (default 8)
+  int p256_group_m = -1;           // DM_GEMM_256_GROUP_M >= 0: ... of the 256 x 256 pipeline's launches
+  int p256_tn_mink = 8;            // DM_GEMM_256_TN_MINK: K tiles per slice a weight gradient needs on the 256 x 256 pipeline
+  int p256_nt_longk = 1;           // DM_GEMM_256_NT_LONGK=0: the long-K forward products leave the 256 x 256 pipeline
+  bool fold_routes = true;         // DM_GEMM_FOLD_ROUTES=0: the routing rules made for folded products are off
+  int cus_reserved = 0;            // DM_GEMM_CUS_RESERVED: CUs left out of the one-workgroup-per-CU grids
+  bool t128_rows_off = false;      // DM_GEMM_T128_ROWS=0  -> DM_DBG_ROWS_OFF
+  bool t128_touch_off = false;     // DM_GEMM_T128_TOUCH=0 -> DM_DBG_TOUCH_OFF
+  bool epi_lean_off = false;       // DM_GEMM_EPI_LEAN=0   -> DM_DBG_LEAN_OFF
+  const char *route = nullptr;     // DM_GEMM_ROUTE (apply_route)
+};
+const GemmTuning &dm_gemm_tuning();
 
 // CUs the one-workgroup-per-CU grids are planned for (dm_gemm.hip)
 int dm_gemm_cu_count();
@@ -290,16 +308,7 @@ __device__ __forceinline__ void dm_gemm_emit8(const GemmParams &p, f32x4 lo, f32
   }
 }
 
-
-// Staging layout of one wave: rows of PITCH bytes holding 64 fp32 columns.  SWZ = false: padded rows (PITCH = DM_EPI_PITCH = 272),
-// chunk c of a row at c * 16; SWZ = true: exact rows (PITCH = 256, for kernels whose LDS is full), the 16-byte chunk c of row r at
-// slot c ^ (r & 15) -- both patterns (ds_write_b128 of an accumulator tile: 16 rows x 4 chunks; ds_read_b128 of a row's chunk pair by 8
-// lanes x 8 rows) are conflict-free in the bank model of the guide.
-template <int PITCH, bool SWZ> __device__ __forceinline__ int dm_epi_slot(int row, int chunk) {
-  return row * PITCH + ((SWZ ? (chunk ^ (row & 15)) : chunk) << 4);
-}
-
-template <int WM, int ROWS, bool SKIP_STORES = false, int PITCH = DM_EPI_PITCH, bool SWZ = false>
+template <int WM, int ROWS>
 __device__ __forceinline__ void dm_epilogue_rows_generic(const GemmParams &p, f32x4 (&acc)[WM][4], char *mine, int m_wave, int n_wave, int lane) {
   const int g = lane >> 4, li = lane & 15;
   constexpr int PASS_TILES = ROWS / 16;
@@ -309,7 +318,7 @@ __device__ __forceinline__ void dm_epilogue_rows_generic(const GemmParams &p, f3
     for (int ii = 0; ii < PASS_TILES; ++ii)
 #pragma unroll
       for (int j = 0; j < 4; ++j)
-        *reinterpret_cast<f32x4 *>(mine + dm_epi_slot<PITCH, SWZ>(ii * 16 + li, j * 4 + g)) = acc[ps * PASS_TILES + ii][j];
+        *reinterpret_cast<f32x4 *>(mine + ((ii * 16 + li) * DM_EPI_PITCH + ((j * 4 + g) << 4))) = acc[ps * PASS_TILES + ii][j];
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_sched_barrier(0);
     const int n = n_wave + (lane & 7) * 8;
@@ -317,10 +326,9 @@ __device__ __forceinline__ void dm_epilogue_rows_generic(const GemmParams &p, f3
     for (int r = 0; r < ROWS / 8; ++r) {
       const int row = r * 8 + (lane >> 3);
       const int m = m_wave + ps * ROWS + row;
-      const f32x4 lo = *reinterpret_cast<const f32x4 *>(mine + dm_epi_slot<PITCH, SWZ>(row, (lane & 7) * 2));
-      const f32x4 hi = *reinterpret_cast<const f32x4 *>(mine + dm_epi_slot<PITCH, SWZ>(row, (lane & 7) * 2 + 1));
-      if constexpr (SKIP_STORES) { if (lo[0] == 12345.678f && m < p.M) dm_gemm_emit8(p, lo, hi, dm_gemm_row(p, m), n); }
-      else if (m < p.M && n < p.N) dm_gemm_emit8(p, lo, hi, dm_gemm_row(p, m), n);
+      const f32x4 lo = *reinterpret_cast<const f32x4 *>(mine + (row * DM_EPI_PITCH + (((lane & 7) * 2) << 4)));
+      const f32x4 hi = *reinterpret_cast<const f32x4 *>(mine + (row * DM_EPI_PITCH + (((lane & 7) * 2 + 1) << 4)));
+      if (m < p.M && n < p.N) dm_gemm_emit8(p, lo, hi, dm_gemm_row(p, m), n);
     }
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");      // the next pass overwrites the region
     __builtin_amdgcn_sched_barrier(0);
@@ -400,8 +408,7 @@ __device__ __forceinline__ int dm_epi_records(long long bytes) { return (int)(by
 // item -- RES: fp32 residual read; YL: 0 none / 1 old C (accumulate) / 2 aux read, bf16 / 3 aux read, fp32; C32: fp32 C; XS: 0 no aux
 // store / 1 bf16 / 2 fp32 -- is a template argument, so every memory instruction is straight-line code with counted waits; only the
 // arithmetic kind (GELU / GELU' / multiply) stays a run-time branch.  dm_epilogue_rows dispatches the combinations the encoder uses.
-template <int WM, int ROWS, bool SKIP_STORES = false, bool RT = true, bool RES = false, int YL = 0, bool C32 = false, int XS = 0,
-          int PITCH = DM_EPI_PITCH, bool SWZ = false>
+template <int WM, int ROWS, bool RT = true, bool RES = false, int YL = 0, bool C32 = false, int XS = 0>
 __device__ __forceinline__ void dm_epilogue_rows_lean(const GemmParams &p, f32x4 (&acc)[WM][4], char *mine, int m_wave_in, int n_wave_in, int lane) {
   // wave-uniform by construction, but derived from threadIdx in some callers: without the readfirstlane the descriptors below live
   // in VGPRs and every buffer access becomes a waterfall loop
@@ -532,7 +539,7 @@ __device__ __forceinline__ void dm_epilogue_rows_lean(const GemmParams &p, f32x4
     for (int ii = 0; ii < PASS_TILES; ++ii)
 #pragma unroll
       for (int j = 0; j < 4; ++j)
-        *reinterpret_cast<f32x4 *>(mine + dm_epi_slot<PITCH, SWZ>(ii * 16 + li, j * 4 + g)) = acc[ps * PASS_TILES + ii][j];
+        *reinterpret_cast<f32x4 *>(mine + ((ii * 16 + li) * DM_EPI_PITCH + ((j * 4 + g) << 4))) = acc[ps * PASS_TILES + ii][j];
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
@@ -541,10 +548,9 @@ __device__ __forceinline__ void dm_epilogue_rows_lean(const GemmParams &p, f32x4
       if (q + 1 < Q) prefetch(pre[(q + 1) & 1], q + 1);          // (issued before this item's stores: see the header)
       __builtin_amdgcn_sched_barrier(0);
       const int row = r * 8 + rl;
-      const f32x4 lo = *reinterpret_cast<const f32x4 *>(mine + dm_epi_slot<PITCH, SWZ>(row, c8 * 2));
-      const f32x4 hi = *reinterpret_cast<const f32x4 *>(mine + dm_epi_slot<PITCH, SWZ>(row, c8 * 2 + 1));
-      if constexpr (SKIP_STORES) { if (lo[0] == 12345.678f) emit(lo, hi, pre[q & 1], q); }
-      else emit(lo, hi, pre[q & 1], q);
+      const f32x4 lo = *reinterpret_cast<const f32x4 *>(mine + (row * DM_EPI_PITCH + ((c8 * 2) << 4)));
+      const f32x4 hi = *reinterpret_cast<const f32x4 *>(mine + (row * DM_EPI_PITCH + ((c8 * 2 + 1) << 4)));
+      emit(lo, hi, pre[q & 1], q);
       __builtin_amdgcn_sched_barrier(0);
     }
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");      // the next pass overwrites the region
@@ -572,17 +578,17 @@ __host__ __device__ inline bool dm_epi_key_specialised(int key) {
   return key == 0 || key == (1 | (1 << 3)) || key == (1 << 3) || key == ((1 << 1) | (1 << 3)) || key == (1 << 4) || key == (2 << 1);
 }
 
-// LEAN_ONLY: the caller (a kernel whose K loop must not contain the generic form: the persistent LDS-DMA pipeline, where any load the
-// compiler cannot count drains the DMA queue at the loop head) guarantees on the host that dm_epi_key_specialised holds.
-template <int WM, int ROWS, bool SKIP_STORES = false, int PITCH = DM_EPI_PITCH, bool SWZ = false, bool LEAN_ONLY = false>
+// LEAN_ONLY: the caller (a kernel that has no registers for the generic and run-time forms: dm_gemm_q4.hip) guarantees on the host that
+// dm_epi_key_specialised holds.
+template <int WM, int ROWS, bool LEAN_ONLY = false>
 __device__ __forceinline__ void dm_epilogue_rows(const GemmParams &p, f32x4 (&acc)[WM][4], char *mine, int m_wave, int n_wave, int lane) {
   const int key = dm_epi_lean_key(p, 16 * WM);
   if constexpr (!LEAN_ONLY) {
-    if (key < 0) { dm_epilogue_rows_generic<WM, ROWS, SKIP_STORES, PITCH, SWZ>(p, acc, mine, m_wave, n_wave, lane); return; }
+    if (key < 0) { dm_epilogue_rows_generic<WM, ROWS>(p, acc, mine, m_wave, n_wave, lane); return; }
   }
 #define DM_EPI_CASE(RES, YL, C32, XS) \
   case ((RES) | ((YL) << 1) | ((C32) << 3) | ((XS) << 4)): \
-    dm_epilogue_rows_lean<WM, ROWS, SKIP_STORES, false, (RES) != 0, (YL), (C32) != 0, (XS), PITCH, SWZ>(p, acc, mine, m_wave, n_wave, lane); break;
+    dm_epilogue_rows_lean<WM, ROWS, false, (RES) != 0, (YL), (C32) != 0, (XS)>(p, acc, mine, m_wave, n_wave, lane); break;
   switch (key) {
     DM_EPI_CASE(0, 0, 0, 0)      // bf16 C (+ bias / GELU without a saved derivative): qkv forward, the dgrads, inference fc1
     DM_EPI_CASE(1, 0, 1, 0)      // fp32 C + fp32 residual: proj / fc2 forward
@@ -591,7 +597,7 @@ __device__ __forceinline__ void dm_epilogue_rows(const GemmParams &p, f32x4 (&ac
     DM_EPI_CASE(0, 0, 0, 1)      // bf16 C + bf16 aux written: fc1 forward (GELU + saved GELU')
     DM_EPI_CASE(0, 2, 0, 0)      // bf16 C, bf16 aux read: dgrad of fc2 (multiply by the saved GELU')
     default:
-      if constexpr (!LEAN_ONLY) dm_epilogue_rows_lean<WM, ROWS, SKIP_STORES, true, false, 0, false, 0, PITCH, SWZ>(p, acc, mine, m_wave, n_wave, lane);
+      if constexpr (!LEAN_ONLY) dm_epilogue_rows_lean<WM, ROWS, true>(p, acc, mine, m_wave, n_wave, lane);
       break;
   }
 #undef DM_EPI_CASE

@@ -219,7 +219,7 @@ __global__ __launch_bounds__(NTHREADS, 4) void gemm_q4_kernel(const GemmParams p
 #pragma unroll
     for (int j = 0; j < 4; ++j) asm volatile("" : "+a"(acc[i][j]));
   asm volatile("" ::"v"(tv0), "v"(tv1));
-  dm_epilogue_rows<4, 16, false, DM_EPI_PITCH, false, true>(p, acc, smem + wave * (16 * DM_EPI_PITCH), m0 + wm * 64, n0 + wn * 64, lane);
+  dm_epilogue_rows<4, 16, true>(p, acc, smem + wave * (16 * DM_EPI_PITCH), m0 + wm * 64, n0 + wn * 64, lane);
 }
 
 }  // namespace dmq4
@@ -236,11 +236,7 @@ bool dm_gemm_q4_plan(GemmParams &p, const GemmSwitches &sw, int layout, int ab_d
   // in hardware.  With M % 64 == 0 every row of a wave block that starts below M is a row of C, so nothing is written past it.
   if (p.M % 64 != 0) return false;
   // the A/B aids that take the whole-line / lean epilogue away from the 128 x 128 kernel (dm_gemm) keep products off this family
-  static const bool epi_ab = [] {
-    const char *r = getenv("DM_GEMM_T128_ROWS"), *l = getenv("DM_GEMM_EPI_LEAN");
-    return (r && r[0] == '0') || (l && l[0] == '0');
-  }();
-  if (epi_ab) return false;
+  if (dm_gemm_tuning().t128_rows_off || dm_gemm_tuning().epi_lean_off) return false;
   if (p.residual != nullptr && p.ldr % 8 != 0) return false;
   if (!dm_epi_key_specialised(dm_epi_lean_key(p, 64))) return false;      // the kernel instantiates the straight-line epilogues only
   if (128LL * p.lda * 2 >= (1LL << 31) || 128LL * p.ldb * 2 >= (1LL << 31)) return false;

@@ -25,8 +25,6 @@
 //   * epilogue: the wave transposes its accumulators through a private LDS region (rows padded to 272 B) and walks them row
 //     by row, 8 consecutive columns per lane, so that bias / residual / aux reads and the C stores are whole 128-byte lines
 //     (the accumulator layout itself gives 8-byte pieces of 16 different rows per instruction).
-#include <cstdlib>
-
 #include "dm_common.h"
 #include "dm_gemm_common.h"
 #include "dm_mfma.h"
@@ -53,7 +51,7 @@ template <int WM> struct Cfg {
   __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (__attribute__((address_space(3))) void *)(dst), 16, voff, soff, 0, 0)
 
 // FOLD: hi / lo plane pairs, three K segments of p.k_fold (GemmParams.k_fold), as in the other GEMM kernels.
-template <int WM, int DBG = 0, bool FOLD = false>
+template <int WM, bool FOLD = false>
 __global__ __launch_bounds__(256, 2) void gemm_ring_kernel(const GemmParams p) {
   using C = Cfg<WM>;
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -130,37 +128,35 @@ __global__ __launch_bounds__(256, 2) void gemm_ring_kernel(const GemmParams p) {
   // (Tried and dropped: a software L2 prefetch -- every wave touching one dword per 64 bytes of the operand lines two K tiles
   // ahead, left in flight by a counted vmcnt.  The extra 64-byte requests cost more than the latency they hid: 110 us against
   // 96 us on the fc1 product, tools/mb_ring.py.)
-  if constexpr ((DBG & 1) == 0) { stage_b(0); stage_a(0, 0, C::NA); }
+  stage_b(0);
+  stage_a(0, 0, C::NA);
   for (int kt = 0; kt < nk; ++kt) {
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();
     __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
-      fb[0][j] = *reinterpret_cast<const u32x4 *>(smem + ((DBG & 4) ? 0 : offB + j * 2048 + fr0));
-      fb[1][j] = *reinterpret_cast<const u32x4 *>(smem + ((DBG & 4) ? 0 : offB + j * 2048 + fr1));
+      fb[0][j] = *reinterpret_cast<const u32x4 *>(smem + (offB + j * 2048 + fr0));
+      fb[1][j] = *reinterpret_cast<const u32x4 *>(smem + (offB + j * 2048 + fr1));
     }
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_sched_barrier(0);
     __builtin_amdgcn_s_barrier();
     __builtin_amdgcn_sched_barrier(0);
-    const bool more = (kt + 1 < nk) && !(DBG & 1);
+    const bool more = kt + 1 < nk;
     if (more) stage_b(kt + 1);
     const char *img = smem + (kt & 1) * C::A_BYTES + offA;
 #pragma unroll
     for (int ks = 0; ks < 2; ++ks) {
 #pragma unroll
-      for (int i = 0; i < WM; ++i) fa[i] = *reinterpret_cast<const u32x4 *>(img + ((DBG & 4) ? 0 : i * 2048 + (ks ? fr1 : fr0)));
+      for (int i = 0; i < WM; ++i) fa[i] = *reinterpret_cast<const u32x4 *>(img + (i * 2048 + (ks ? fr1 : fr0)));
       if (more) stage_a(kt + 1, ks * (C::NA / 2), (ks + 1) * (C::NA / 2));
       __builtin_amdgcn_sched_barrier(0);
       __builtin_amdgcn_s_setprio(1);
 #pragma unroll
       for (int i = 0; i < WM; ++i)
 #pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          if constexpr ((DBG & 2) != 0) acc[i][j][0] += __builtin_bit_cast(float, fa[i][0] ^ fb[ks][j][1]);
-          else mma<bf16_t>(acc[i][j], fa[i], fb[ks][j]);
-        }
+        for (int j = 0; j < 4; ++j) mma<bf16_t>(acc[i][j], fa[i], fb[ks][j]);
       __builtin_amdgcn_s_setprio(0);
       __builtin_amdgcn_sched_barrier(0);
     }
@@ -169,11 +165,11 @@ __global__ __launch_bounds__(256, 2) void gemm_ring_kernel(const GemmParams p) {
   // ---- epilogue: transpose through a wave-private LDS region, then whole-line row accesses ---------------------
   __builtin_amdgcn_s_barrier();                       // every wave is done with the ring
   char *mine = smem + wave * (C::EPI_ROWS * DM_EPI_PITCH);
-  dm_epilogue_rows<WM, C::EPI_ROWS, (DBG & 8) != 0>(p, acc, mine, m0 + wr * (WM * 16), n0 + wc * 64, lane);
+  dm_epilogue_rows<WM, C::EPI_ROWS>(p, acc, mine, m0 + wr * (WM * 16), n0 + wc * 64, lane);
 }
 
 template <int WM, bool FOLD = false> bool set_lds_limit() {
-  return hipFuncSetAttribute(reinterpret_cast<const void *>(gemm_ring_kernel<WM, 0, FOLD>), hipFuncAttributeMaxDynamicSharedMemorySize, Cfg<WM>::LDS) == hipSuccess;
+  return hipFuncSetAttribute(reinterpret_cast<const void *>(gemm_ring_kernel<WM, FOLD>), hipFuncAttributeMaxDynamicSharedMemorySize, Cfg<WM>::LDS) == hipSuccess;
 }
 
 }  // namespace dmring
@@ -185,8 +181,7 @@ int dm_gemm_ring_plan(GemmParams &p, const GemmSwitches &sw, int layout, int ab_
   if (p.K % dmring::BK != 0 || p.N % 8 != 0) return 0;
   if (p.k_fold > 0 && p.k_fold % dmring::BK != 0) return 0;      // folded contraction: segments of whole K tiles
   if (256LL * p.lda * 2 >= (1LL << 31) || 128LL * p.ldb * 2 >= (1LL << 31)) return 0;
-  const char *fenv = getenv("DM_GEMM_RING_WM");
-  const int force = fenv ? atoi(fenv) : 0;
+  const int force = sw.ring_wm;
   const long long t256 = (long long)((p.M + 255) / 256) * ((p.N + 127) / 128);
   // Measured with cache-cold operands (tools/mb_epi.py, round 2, us per launch: this kernel / best of the other two):
   //   M = 16384: qkv 72 / 83, fc1 + GELU' 119 / 133, proj + residual 53 / 50, fc2 + residual 107 / 102
@@ -203,8 +198,7 @@ int dm_gemm_ring_plan(GemmParams &p, const GemmSwitches &sw, int layout, int ab_
   // 0.330 here (0.335 on the 256 x 256 pipeline); 16384 x 2304 0.235 / 0.235; 4096 x 3072 + GELU' 0.073 / 0.080 -> the widest product is back
   // folded products (tools/mb_fold.py, the qkv forward with a plane-pair result, 16384 x 2304 x 3*768): 192 us here, 199 on the 4-wave kernel,
   // 208 on the 256 x 256 pipeline, 236 on 128 x 128 tiles -- the whole-rounds exception below is a bf16-mode (K = 768) finding
-  static const bool fold_routes = [] { const char *e = getenv("DM_GEMM_FOLD_ROUTES"); return !(e && atoi(e) == 0); }();
-  const bool fold_wide = fold_routes && p.k_fold > 0 && p.N >= 2048 && p.M >= 8192;
+  const bool fold_wide = dm_gemm_tuning().fold_routes && p.k_fold > 0 && p.N >= 2048 && p.M >= 8192;
   if (mode == 1 && !fold_wide && ((long long)((p.M + 127) / 128) * ((p.N + 127) / 128)) % 768 == 0 && !(p.N >= 3072 && p.M >= 8192)) return 0;
   int wm = t256 >= 384 ? 8 : 4;
   if (force == 8 || force == 4) wm = force;
@@ -220,19 +214,9 @@ int dm_gemm_ring_plan(GemmParams &p, const GemmSwitches &sw, int layout, int ab_
 
 void dm_gemm_ring_launch(const GemmParams &p, int wm, hipStream_t s) {
   const dim3 grid((unsigned)(p.tiles_m * p.tiles_n));
-#ifdef DM_RING_ABLATE
-  if (wm == 8 && p.debug) {
-    switch (p.debug) {
-#define DM_ABL(D) case D: { static const bool k = hipFuncSetAttribute(reinterpret_cast<const void *>(dmring::gemm_ring_kernel<8, D>), hipFuncAttributeMaxDynamicSharedMemorySize, dmring::Cfg<8>::LDS) == hipSuccess; (void)k; hipLaunchKernelGGL((dmring::gemm_ring_kernel<8, D>), grid, dim3(256), dmring::Cfg<8>::LDS, s, p); return; }
-      DM_ABL(1) DM_ABL(2) DM_ABL(4) DM_ABL(5) DM_ABL(6) DM_ABL(7) DM_ABL(8) DM_ABL(15)
-#undef DM_ABL
-      default: break;
-    }
-  }
-#endif
   if (p.k_fold > 0) {
-    if (wm == 8) hipLaunchKernelGGL((dmring::gemm_ring_kernel<8, 0, true>), grid, dim3(256), dmring::Cfg<8>::LDS, s, p);
-    else hipLaunchKernelGGL((dmring::gemm_ring_kernel<4, 0, true>), grid, dim3(256), dmring::Cfg<4>::LDS, s, p);
+    if (wm == 8) hipLaunchKernelGGL((dmring::gemm_ring_kernel<8, true>), grid, dim3(256), dmring::Cfg<8>::LDS, s, p);
+    else hipLaunchKernelGGL((dmring::gemm_ring_kernel<4, true>), grid, dim3(256), dmring::Cfg<4>::LDS, s, p);
     return;
   }
   if (wm == 8) hipLaunchKernelGGL(dmring::gemm_ring_kernel<8>, grid, dim3(256), dmring::Cfg<8>::LDS, s, p);

@@ -17,29 +17,11 @@
 //     the 256 CUs;
 //   * fused epilogue through a per-wave LDS staging region that is not shared with the K-step buffers.
 // Loads past the end of the sequence use a null buffer descriptor (zero-filled, no traffic): no tail special cases.
-#include <cstdlib>
 #include <type_traits>
 
 #include "dm_common.h"
 #include "dm_gemm_common.h"
 #include "dm_mfma.h"
-
-// -DDM_W4_STAMP (diagnostic build, tools/w4_stamps.py): wave 0 of the first 64 workgroups stamps s_memtime at six points of its K steps
-// 8 .. 23 of the folded form's three-set step into a __device__ array
-#ifdef DM_W4_STAMP
-__device__ unsigned long long dmw4_stamps[64 * 16 * 8];
-#define DMW4_T(i) do { if (wave == 0 && lane == 0 && blockIdx.x < 64 && sstep >= 8 && sstep < 24) dmw4_stamps[(blockIdx.x * 16 + (sstep - 8)) * 8 + (i)] = __builtin_amdgcn_s_memtime(); } while (0)
-extern "C" int dm_debug_w4_stamps(unsigned long long *out) { return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(dmw4_stamps), sizeof(dmw4_stamps)); }
-// ... and every workgroup's wave 0 stamps the phases of its FIRST tile: 0 kernel entry, 1 addresses set up (first global load next), 2 prologue
-// done (two K steps staged, first fragments read), 3 K loop done, 4 epilogue issued
-__device__ unsigned long long dmw4_kstamps[512 * 8];
-#define DMW4_K(i) do { if (wave == 0 && lane == 0 && blockIdx.x < 512) { dmw4_kstamps[blockIdx.x * 8 + (i)] = __builtin_amdgcn_s_memtime(); \
-    if ((i) == 0 || (i) == 4) dmw4_kstamps[blockIdx.x * 8 + ((i) == 0 ? 5 : 6)] = __builtin_amdgcn_s_memrealtime(); } } while (0)     /* (slots 5 / 6: the chip-wide 100 MHz clock at entry / end) */
-extern "C" int dm_debug_w4_kstamps(unsigned long long *out) { return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(dmw4_kstamps), sizeof(dmw4_kstamps)); }
-#else
-#define DMW4_T(i) do { } while (0)
-#define DMW4_K(i) do { } while (0)
-#endif
 
 namespace dmw4 {
 
@@ -64,7 +46,6 @@ __device__ __forceinline__ void mma_pinned(f32x4 &acc, const u32x4 &a, const u32
   asm volatile("s_nop 0\n\tv_mfma_f32_16x16x32_bf16 %0, %1, %2, %0" : "+a"(acc) : "v"(b), "v"(a));
 }
 
-// DBG (ablation builds only, -DDM_W4_ABLATE): 1 no epilogue, 4 no global loads, 8 no LDS writes, 16 no fragment reads, 32 no MFMAs
 // EK: 0 = the generic fused epilogue (any operand combination, grouped rows); k > 0 = the lean epilogue with item structure key
 // k - 1 = RES | YL << 1 | C32 << 3 | XS << 4 (dm_gemm_common.h).  ONE epilogue per kernel instance: with two in one kernel the
 // accumulators meet in phi nodes behind them and the register allocator spills all 48 tiles around every tile end (tried).
@@ -76,9 +57,8 @@ __device__ __forceinline__ void mma_pinned(f32x4 &acc, const u32x4 &a, const u32
 // needs 3 steps: the staging / fragment traffic that bounds this kernel's step drops by a third.
 // The kernel body: workgroup L of G (XCD-remapped ids) of the launch described by p.  gemm_w4_kernel runs it for one product;
 // gemm_w4_grouped_kernel for one of several independent weight gradients sharing a launch (dm_gemm_grouped).
-template <int LAYOUT, int DBG, int EK, bool FOLD, bool CS>
+template <int LAYOUT, int EK, bool FOLD, bool CS>
 __device__ __forceinline__ void gemm_w4_body(const GemmParams &p, const int G, const int L) {
-  constexpr int EPIU = 0;
   constexpr bool AMM = (LAYOUT == DM_TN);      // A m-contiguous [K][M] (wgrad) or k-contiguous [M][K]
   constexpr bool BMM = (LAYOUT != DM_NT);      // B m-contiguous [K][N] (dgrad, wgrad) or k-contiguous [N][K] (forward)
   constexpr int NB = 6;                        // global loads of B per thread and K step
@@ -88,23 +68,14 @@ __device__ __forceinline__ void gemm_w4_body(const GemmParams &p, const int G, c
   const int wm = wave & 1, wn = wave >> 1;
   const int g = lane >> 4, li = lane & 15;
 
-  DMW4_K(0);
   const int tiles = p.tiles_m * p.tiles_n;
-  {
-    // Experiment (DM_W4_STAGGER = n, off by default): the workgroups of every other XCD start n x 1024 cycles late, so that half of the
-    // chip stores its tiles while the other half is in its K loop (all 256 workgroups otherwise reach every epilogue together and
-    // the stores run at the memory system's burst rate with the matrix pipes idle).
-    const int stag = (p.debug >> 16) & 0x7fff;
-    if (stag && (blockIdx.x & 1)) {
-      const long long t0 = __builtin_amdgcn_s_memtime();
-      while (__builtin_amdgcn_s_memtime() - t0 < (long long)stag * 1024) __builtin_amdgcn_s_sleep(32);
-    }
-  }
   // wgrad (TN): one (tile, K slice) per workgroup, slices of k_per_split (the last one may be shorter); the partial tile goes to
   // slab z of the split-K workspace.  Forward / dgrad: whole K, tiles L, L + G, ...
-  // (round 4: forward / dgrad products with few tiles and a long contraction are sliced the same way -- p.split_k > 1, partial
-  // tiles to the slab, dm_gemm's splitk_epilogue_kernel applies the fused epilogue)
-  const bool sliced = AMM || p.split_k > 1;
+  // (Forward / dgrad K slices were built, measured and removed: p.split_k is 1 for NT / NN.  ONE instance -- NN, folded, generic epilogue --
+  // keeps their run-time shape, here and in epilogue_generic: without it the register allocator gives that instance 456 registers
+  // instead of 448 and moves staging registers through AGPRs inside its K loop.  For every other instance `sliced` is the constant AMM.)
+  constexpr bool SLICE_SHAPE = LAYOUT == DM_NN && FOLD && EK == 0;
+  const bool sliced = AMM || (SLICE_SHAPE && p.split_k > 1);
   const int zslice = sliced ? L / tiles : 0;
   constexpr int BKR = FOLD ? 32 : BK;                  // contraction positions per K step
   const int k_total = FOLD ? p.k_fold : p.K;
@@ -197,7 +168,7 @@ __device__ __forceinline__ void gemm_w4_body(const GemmParams &p, const int G, c
   // ---- tile cursors (uniform) -------------------------------------------------------------------------------------------------------
   const bf16_t *Ab = reinterpret_cast<const bf16_t *>(p.A), *Bb = reinterpret_cast<const bf16_t *>(p.B);
   auto tile_mn = [&](int r, int &m0, int &n0) __attribute__((always_inline)) {
-    const int tid = (DBG & 64) ? (L & 7) : sliced ? L - zslice * tiles : L + r * G;        // (ablation 64: every workgroup reads the same few L2-resident tiles)
+    const int tid = sliced ? L - zslice * tiles : L + r * G;
     // (A BLOCKED order -- column blocks of 8 tiles walked row by row, an XCD keeping its own chunk over the rounds, so that its 32
     // workgroups share 4 panels of A and 8 of B instead of 2 and 16 -- was measured in round 4: 16384 x 3072 x 768 on 4 rounds 103 -> 97 us,
     // x 2304 on 3 rounds 80 -> 77 us, the sliced weight gradients unchanged; the multi-round products still lose to the kernels with 2-3
@@ -270,15 +241,8 @@ __device__ __forceinline__ void gemm_w4_body(const GemmParams &p, const int G, c
   asm volatile("v_mov_b32 %0, 0" : "=v"(vzero[0]));
   vzero[1] = vzero[2] = vzero[3] = vzero[0];
   asm volatile("s_nop 7" ::: "memory");
-  if constexpr (DBG & 4) {
-#pragma unroll
-    for (int u = 0; u < 8; ++u) ga[0][u] = ga[1][u] = vzero;
-#pragma unroll
-    for (int u = 0; u < NB; ++u) gb[0][u] = gb[1][u] = vzero;
-  }
   // fetch piece q of the group cursor's K step into register set `set`
   auto gload = [&](auto set_tag, auto grp_tag, int q) __attribute__((always_inline)) {
-    if constexpr (DBG & 4) return;
     constexpr int set = decltype(set_tag)::value;
     constexpr bool GX = decltype(grp_tag)::value == 0;
     const int k = GX ? cx.k : cy.k;
@@ -292,7 +256,6 @@ __device__ __forceinline__ void gemm_w4_body(const GemmParams &p, const int G, c
   };
   // piece q: register set -> LDS buffer
   auto lwrite = [&](auto set_tag, auto buf_tag, int q) __attribute__((always_inline)) {
-    if constexpr (DBG & 8) return;
     constexpr int set = decltype(set_tag)::value;
     char *a = smem + decltype(buf_tag)::value * BUF_BYTES;
     if (q < 8) {
@@ -329,16 +292,9 @@ __device__ __forceinline__ void gemm_w4_body(const GemmParams &p, const int G, c
   // Fragments: B double-buffered (the next k-step's six tiles load while this one's are in use); A rotates in place (row tile i's
   // fragment is dead after its six MFMAs and is reloaded for the next k-step at once) -- the arch-VGPR budget is 256.
   u32x4 fa[8], fb[2][6];
-  if constexpr (DBG & 16) {
-#pragma unroll
-    for (int i = 0; i < 8; ++i) fa[i] = vzero;
-#pragma unroll
-    for (int j = 0; j < 6; ++j) fb[0][j] = fb[1][j] = vzero;
-  }
 
   auto read_a = [&](int i, auto ks_tag, auto buf_tag) __attribute__((always_inline)) {
     constexpr int ks = decltype(ks_tag)::value;
-    if constexpr (DBG & 16) return fa[i];
     const char *a = smem + decltype(buf_tag)::value * BUF_BYTES;
     if constexpr (!AMM) {
       return *reinterpret_cast<const u32x4 *>(a + i * 2048 + (ks ? offA1 : offA0));
@@ -351,7 +307,6 @@ __device__ __forceinline__ void gemm_w4_body(const GemmParams &p, const int G, c
   // B fragment of column tile j, k-step ks of LDS buffer buf, into fragment set dst
   auto load_bx = [&](int j, auto ks_tag, auto buf_tag, auto dst_tag) __attribute__((always_inline)) {
     constexpr int ks = decltype(ks_tag)::value, dst = decltype(dst_tag)::value;
-    if constexpr (DBG & 16) return;
     const char *b = smem + decltype(buf_tag)::value * BUF_BYTES + A_BYTES;
     if constexpr (!BMM) {
       fb[dst][j] = *reinterpret_cast<const u32x4 *>(b + j * 2048 + offB[ks]);
@@ -368,9 +323,7 @@ __device__ __forceinline__ void gemm_w4_body(const GemmParams &p, const int G, c
   //   after MFMA 2: staging piece i of this phase's group (GRP: 0 = X, 1 = Y): register set SSET -> LDS buffer SBUF
   //   after MFMA 3: the freed set entry is refilled from global memory
   //   after MFMA 5: B fragment i of the next k-step (rows 0..5)
-  auto mm = [&](f32x4 &c, const u32x4 &a, const u32x4 &b) __attribute__((always_inline)) {
-    if constexpr (!(DBG & 32)) mma_pinned(c, a, b);
-  };
+  auto mm = [&](f32x4 &c, const u32x4 &a, const u32x4 &b) __attribute__((always_inline)) { mma_pinned(c, a, b); };
   auto mfmas = [&](auto ks_tag, auto nks_tag, auto nbuf_tag, auto grp_tag, auto sset_tag, auto sbuf_tag) __attribute__((always_inline)) {
     constexpr int ks = decltype(ks_tag)::value;
     constexpr int q0 = decltype(grp_tag)::value == 0 ? 0 : PH;
@@ -475,10 +428,10 @@ __device__ __forceinline__ void gemm_w4_body(const GemmParams &p, const int G, c
     int lane = lane_outer;
     asm volatile("" : "+v"(lane) : "v"(tv[0]), "v"(tv[1]), "v"(tv[2]), "v"(tv[3]), "v"(tv[4]), "v"(tv[5]));
     const int g = lane >> 4, li = lane & 15;
-    const bool split = p.split_k > 1;
-    const bool c32 = (AMM || split) ? true : (RT ? (p.c_dtype == DM_F32) : C32);
+    const bool split = AMM && p.split_k > 1;               // weight gradients only: the partial tile of a K slice goes to the slab
+    const bool c32 = AMM ? true : (RT ? (p.c_dtype == DM_F32) : C32);
     const bool x32 = RT ? (p.aux_dtype == DM_F32) : (YL == 3 || XS == 2);
-    const bool plain = AMM || split;                       // no fused epilogue: partial tile / weight gradient
+    constexpr bool plain = AMM;                            // no fused epilogue: weight gradient
     const bool has_res = !plain && (RT ? (p.residual != nullptr) : RES);
     const bool has_acc = !split && (RT ? (c32 && p.accumulate) : (YL == 1));
     const bool aux_load = !plain && (RT ? (p.aux && (p.epilogue == DM_EPI_DGELU || p.epilogue == DM_EPI_MUL)) : (YL >= 2));
@@ -654,16 +607,16 @@ __device__ __forceinline__ void gemm_w4_body(const GemmParams &p, const int G, c
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
       __builtin_amdgcn_s_barrier();
       __builtin_amdgcn_sched_barrier(0);
-      auto pass = [&](int q3) __attribute__((always_inline)) {               // (unrolled: the three bodies' residual / aux loads are in flight together)
+      auto pass = [&](int q3) __attribute__((always_inline)) {
         const int item = q3 * 64 + lane;             // 8 rows x 24 groups of 8 columns
         const int rr = item / 24, cg = item - rr * 24;
         const int row = wn * 8 + rr;
         const f32x4 lo = *reinterpret_cast<const f32x4 *>(slab + row * 768 + (((2 * cg) ^ (row & 7)) << 4));
         const f32x4 hi = *reinterpret_cast<const f32x4 *>(slab + row * 768 + (((2 * cg + 1) ^ (row & 7)) << 4));
-        int m = m_pair + i * 16 + row;
-        if (AMM || p.split_k > 1) {
+        const int m = m_pair + i * 16 + row;
+        if (AMM || (SLICE_SHAPE && p.split_k > 1)) {
           // wgrad: fp32 partial tile into slab z of the split-K workspace (summed in slice order by splitk_reduce_kernel), or,
-          // unsplit, straight into the gradient (a sliced forward / dgrad product always writes the slab)
+          // unsplit, straight into the gradient
           if (m < p.M) {
             const int n = n_cur + cg * 8;
             if (p.split_k > 1) {
@@ -678,18 +631,12 @@ __device__ __forceinline__ void gemm_w4_body(const GemmParams &p, const int G, c
               dm_store4(d + 4, h2);
             }
           }
-        } else {
-        if constexpr (DBG & 256) m = wm * 128 + i * 16 + row;         // (ablation: every workgroup stores to the same 256 rows)
-        if constexpr (DBG & 128) { if (lo[0] == 12345.678f) dm_gemm_emit8(p, lo, hi, dm_gemm_row(p, m), n_cur + cg * 8); }
-        else if (m < p.M) dm_gemm_emit8(p, lo, hi, dm_gemm_row(p, m), (DBG & 256) ? cg * 8 : n_cur + cg * 8);
+        } else if (m < p.M) {
+          dm_gemm_emit8(p, lo, hi, dm_gemm_row(p, m), n_cur + cg * 8);
         }
       };
-      if constexpr (EPIU) {        // unrolled: the three bodies' residual / aux loads are in flight together
-        pass(0); pass(1); pass(2);
-      } else {
 #pragma nounroll
-        for (int q3 = 0; q3 < 3; ++q3) pass(q3);
-      }
+      for (int q3 = 0; q3 < 3; ++q3) pass(q3);
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");      // the next row tile overwrites the slab
       __builtin_amdgcn_s_barrier();
       __builtin_amdgcn_sched_barrier(0);
@@ -725,7 +672,7 @@ __device__ __forceinline__ void gemm_w4_body(const GemmParams &p, const int G, c
   // holds its B hi piece (the lo piece sits in set 1 - PAR: the roles alternate, so the next step's hi fragments can load while this
   // step's are still in use).  hi.hi [B lo fragments; group Y of step s + 1 -> buffer 1 - PAR] | hi.lo [A lo fragments] | barrier |
   // lo.hi [fragments of step s + 1; group X of step s + 2 -> buffer PAR].
-  // s_memtime stamps of the three sets (tools/w4_stamps.py, -DDM_W4_STAMP; weight gradient 768 x 3072 x 3*16384, cycles per set for 768
+  // s_memtime stamps of the three sets (a diagnostic build since removed; weight gradient 768 x 3072 x 3*16384, cycles per set for 768
   // cycles of MFMAs): 1780 / 972 / 1492, + 330 for the wait and the barrier; with BOTH staging groups in front of the barrier (buffer
   // 1 - PAR is free from the previous barrier on) 1440 / 1452 / 1244: a staging group costs ~500-700 cycles wherever it sits, the 14
   // transposed fragment reads of the next step ~450 -- moving the pieces does not shorten the step.  It is not the LDS array either
@@ -735,22 +682,14 @@ __device__ __forceinline__ void gemm_w4_body(const GemmParams &p, const int G, c
   // fabric at less than half the L2's rate per CU (MI355X_MICROARCH.md 'Indexed rows': 33 vs 70 GB/s per CU).
   auto body3 = [&](auto par_tag) __attribute__((always_inline)) {
     constexpr int PAR = decltype(par_tag)::value;
-    [[maybe_unused]] const int sstep = kt + PAR;
-    DMW4_T(0);
     mfmas3(IC<PAR>{}, IC<0>{}, IC<0>{}, IC<0>{}, IC<1>{}, IC<1 - PAR>{}, IC<1 - PAR>{}, IC<1>{}, IC<1>{}, IC<PAR>{}, IC<1 - PAR>{}, IC<0>{});
-    DMW4_T(1);
     mfmas3(IC<1 - PAR>{}, IC<1>{}, IC<1>{}, IC<PAR>{}, IC<-1>{}, IC<0>{}, IC<0>{}, IC<0>{}, IC<0>{}, IC<0>{}, IC<0>{}, IC<-1>{});
-    DMW4_T(2);
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    DMW4_T(3);
     __builtin_amdgcn_s_barrier();
-    DMW4_T(4);
     mfmas3(IC<PAR>{}, IC<1>{}, IC<0>{}, IC<1 - PAR>{}, IC<0>{}, IC<PAR>{}, IC<PAR>{}, IC<1>{}, IC<0>{}, IC<1 - PAR>{}, IC<1 - PAR>{}, IC<1>{});
-    DMW4_T(5);
   };
 
   // ---- prologue: the state the schedule above expects at step 0 (buffer 0 complete, X(1) in buffer 1, Y(1) / X(2) / Y(2) / X(3) in flight) ----
-  DMW4_K(1);
 #pragma unroll
   for (int q = 0; q < PH; ++q) gload(IC<0>{}, IC<0>{}, q);                 // X(0) -> set 0
   advance_x();
@@ -779,19 +718,15 @@ __device__ __forceinline__ void gemm_w4_body(const GemmParams &p, const int G, c
 #pragma unroll
   for (int i = 0; i < 8; ++i) fa[i] = read_a(i, IC<0>{}, IC<0>{});
 
-  DMW4_K(2);
   // K % 128 == 0 (plan): a tile is an even number of K steps, so tiles end after an odd step only
   for (int step = 0; step < total; step += 2) {
-    if constexpr (!AMM) { if (kt + 2 == ntile && p.split_k <= 1) touch_epilogue_operands(); }
+    if constexpr (!AMM) { if (kt + 2 == ntile) touch_epilogue_operands(); }
     if constexpr (FOLD) { body3(IC<0>{}); body3(IC<1>{}); }
     else { body(IC<0>{}); body(IC<1>{}); }
     kt += 2;
     if (kt == ntile) {
-      if (r == 0) DMW4_K(3);
-      if constexpr (DBG & 1) { kt = 0; ++r; if (r < n_my) tile_mn(r, m_cur, n_cur); } else
       if constexpr (EK == 0) epilogue_generic();
       else epilogue_lean(IC<0>{}, IC<(EK - 1) & 1>{}, IC<((EK - 1) >> 1) & 3>{}, IC<((EK - 1) >> 3) & 1>{}, IC<((EK - 1) >> 4) & 3>{});
-      if (r == 1) DMW4_K(4);
       // The next step's k-step-0 fragments were prefetched during the last MFMAs; holding their 56 registers across the epilogue
       // (on top of the 88 staging registers in flight) overflows the register file, so they are read again here instead.
 #pragma unroll
@@ -802,9 +737,9 @@ __device__ __forceinline__ void gemm_w4_body(const GemmParams &p, const int G, c
   }
 }
 
-template <int LAYOUT, int DBG = 0, int EK = 0, bool FOLD = false, bool CS = true>
+template <int LAYOUT, int EK = 0, bool FOLD = false, bool CS = true>
 __global__ __launch_bounds__(256) void gemm_w4_kernel(const GemmParams p) {
-  gemm_w4_body<LAYOUT, DBG, EK, FOLD, CS>(p, (int)gridDim.x, dm_xcd_remap(blockIdx.x, gridDim.x));
+  gemm_w4_body<LAYOUT, EK, FOLD, CS>(p, (int)gridDim.x, dm_xcd_remap(blockIdx.x, gridDim.x));
 }
 
 // Several independent weight gradients (DM_TN, one K slice each) in ONE launch: workgroups first[i] .. first[i + 1] - 1 (after the XCD
@@ -820,20 +755,21 @@ __global__ __launch_bounds__(256) void gemm_w4_grouped_kernel(const GemmGroup gr
     if (k < grp.n && L >= grp.first[k]) i = k;
   i = __builtin_amdgcn_readfirstlane(i);
   const int tiles = grp.first[i + 1] - grp.first[i];
-  gemm_w4_body<DM_TN, 0, EK, FOLD, CS>(grp.p[i], tiles, L - grp.first[i]);
+  gemm_w4_body<DM_TN, EK, FOLD, CS>(grp.p[i], tiles, L - grp.first[i]);
 }
 
 }  // namespace dmw4
 
 namespace {
-template <int LAYOUT, int DBG = 0, int EK = 0, bool FOLD = false, bool CS = true> bool w4_set_lds_limit() {
-  return hipFuncSetAttribute(reinterpret_cast<const void *>(dmw4::gemm_w4_kernel<LAYOUT, DBG, EK, FOLD, CS>), hipFuncAttributeMaxDynamicSharedMemorySize,
+template <int LAYOUT, int EK = 0, bool FOLD = false, bool CS = true> bool w4_set_lds_limit() {
+  return hipFuncSetAttribute(reinterpret_cast<const void *>(dmw4::gemm_w4_kernel<LAYOUT, EK, FOLD, CS>), hipFuncAttributeMaxDynamicSharedMemorySize,
                              dmw4::LDS_BYTES) == hipSuccess;
 }
 }  // namespace
 
 // Decides whether the 4-wave persistent kernel runs this product (bf16 NT / NN); fills p.tiles_m / tiles_n and returns the grid
-// size (0 = not taken).  `aligned8`: the 8-column epilogue (dm_gemm_emit8) is legal for C / aux / grouped rows.
+// size (0 = not taken).  `aligned8`: the 8-column epilogue (dm_gemm_emit8) is legal for C / aux / grouped rows.  `can_split` and
+// `workspace_bytes` matter for DM_TN only: whether K slices are allowed, and the slab they must fit.
 int dm_gemm_w4_plan(GemmParams &p, const GemmSwitches &sw, int layout, int ab_dtype, bool aligned8, bool can_split, long long workspace_bytes) {
   using namespace dmw4;
   const int mode = sw.w4;         // DM_GEMM_W4: 0 = off, 1 = routing rule, 2 = every legal product, 3 = every whole-round shape
@@ -846,9 +782,9 @@ int dm_gemm_w4_plan(GemmParams &p, const GemmSwitches &sw, int layout, int ab_dt
     if (p.k_fold % (2 * bk_eff) != 0) return 0;
     if (p.a_fold[0] != 0 || p.a_fold[1] != 0 || p.a_fold[2] <= 0 || p.b_fold[0] != 0 || p.b_fold[2] != 0 || p.b_fold[1] <= 0) return 0;
     if (p.a_fold[2] * 2 >= (1LL << 30) || p.b_fold[1] * 2 >= (1LL << 30)) return 0;      // (byte offsets live in 32-bit lane offsets)
-    static const bool attr_fold = w4_set_lds_limit<DM_TN, 0, 0, true>() && w4_set_lds_limit<DM_TN, 0, 9, true>() && w4_set_lds_limit<DM_TN, 0, 11, true>() &&
-                                  w4_set_lds_limit<DM_TN, 0, 0, true, false>() && w4_set_lds_limit<DM_TN, 0, 9, true, false>() && w4_set_lds_limit<DM_TN, 0, 11, true, false>() &&
-                                  w4_set_lds_limit<DM_NT, 0, 0, true>() && w4_set_lds_limit<DM_NT, 0, 10, true>() && w4_set_lds_limit<DM_NN, 0, 0, true>();
+    static const bool attr_fold = w4_set_lds_limit<DM_TN, 0, true>() && w4_set_lds_limit<DM_TN, 9, true>() && w4_set_lds_limit<DM_TN, 11, true>() &&
+                                  w4_set_lds_limit<DM_TN, 0, true, false>() && w4_set_lds_limit<DM_TN, 9, true, false>() && w4_set_lds_limit<DM_TN, 11, true, false>() &&
+                                  w4_set_lds_limit<DM_NT, 0, true>() && w4_set_lds_limit<DM_NT, 10, true>() && w4_set_lds_limit<DM_NN, 0, true>();
     if (!attr_fold) return 0;
   }
   if (layout == DM_TN) {
@@ -877,8 +813,8 @@ int dm_gemm_w4_plan(GemmParams &p, const GemmSwitches &sw, int layout, int ab_dt
     // (round 5, tools/routing_check.py: 2304 x 768 x 4096 -- 36 tiles x 4 slices = 0.56 of the CUs -- 36.0 us here against 41.1 on the 256 x 256
     // pipeline: the fill bound is 0.55 for >= 24 tiles)
     if (tmode == 1 && ((double)(tiles * split) / cus < (tiles >= 24 ? 0.55 : 0.7) || tiles < 12 || (tiles < 24 && k_eff < 8192))) return 0;
-    static const bool attr_tn = w4_set_lds_limit<DM_TN>() && w4_set_lds_limit<DM_TN, 0, 9>() && w4_set_lds_limit<DM_TN, 0, 11>() &&
-                                w4_set_lds_limit<DM_TN, 0, 0, false, false>() && w4_set_lds_limit<DM_TN, 0, 9, false, false>() && w4_set_lds_limit<DM_TN, 0, 11, false, false>();
+    static const bool attr_tn = w4_set_lds_limit<DM_TN>() && w4_set_lds_limit<DM_TN, 9>() && w4_set_lds_limit<DM_TN, 11>() &&
+                                w4_set_lds_limit<DM_TN, 0, false, false>() && w4_set_lds_limit<DM_TN, 9, false, false>() && w4_set_lds_limit<DM_TN, 11, false, false>();
     if (!attr_tn) return 0;
     p.tiles_m = p.M / TM;
     p.tiles_n = p.N / TN;
@@ -895,40 +831,9 @@ int dm_gemm_w4_plan(GemmParams &p, const GemmSwitches &sw, int layout, int ab_dt
   const long long tiles = (long long)tiles_m * tiles_n;
   const int cus = dm_gemm_cu_count();
   if (cus <= 0) return 0;
-  {
-    // Round 4: few tiles and a long contraction (the 4096-token stage's fc2 forward, fc1 / qkv dgrad: 64 tiles, K = 2304 .. 4096):
-    // one (tile, K slice) per workgroup as for the weight gradients, <= 4 slices of an even number (>= 8) of K steps; dm_gemm sums
-    // the slab and applies the fused epilogue (splitk_epilogue_kernel).  `can_split`: the caller allows it (automatic slice count,
-    // 8-column epilogue legal, workspace present).
-    // Measured in the step (tools/prof_shapes.py, same box): 4096 x 768 x 3072 54 us sliced against 47 us on unsplit 64 x 64 tiles (fc1
-    // dgrad 51 / 44, qkv dgrad 42 / 35): 256 workgroups x 12 K steps pay the kernel's fill and a 192 KiB fp32 slab each, then the 63 MB
-    // reduction -- OFF by default (DM_GEMM_W4_SLICES=1 for A/B runs); the M <= 1024 products gain from slices on 64 x 64 tiles instead.
-    static const bool slices_on = [] { const char *e = getenv("DM_GEMM_W4_SLICES"); return e && atoi(e) == 1; }();
-    constexpr long long LIM = (1LL << 31) / (128LL * 4);
-    // (no test of DM_DBG_LEAN_OFF here: dm_gemm sets the p.debug bits after the plans, so this rule has never seen the bit set)
-    if (slices_on && p.k_fold == 0 && can_split && mode != 0 && tiles * 2 <= cus && p.K >= 1536 && p.N < LIM) {
-      const int steps = p.K / BK;
-      int split = (int)(cus / tiles);
-      if (split > 4) split = 4;
-      int per = (steps + split - 1) / split;
-      per += per & 1;
-      if (per < 8) per = 8;
-      split = (steps + per - 1) / per;
-      if (split > 1 && (long long)split * p.M * p.N * 4 <= workspace_bytes && (double)(tiles * split) / cus >= 0.7) {
-        static const bool attr_sl = w4_set_lds_limit<DM_NT, 0, 9>() && w4_set_lds_limit<DM_NN, 0, 9>();
-        if (attr_sl) {
-          p.tiles_m = tiles_m;
-          p.tiles_n = tiles_n;
-          p.split_k = split;
-          p.k_per_split = per * BK;
-          return (int)(tiles * split);
-        }
-      }
-    }
-  }
   if (mode == 1 || mode == 4 || mode == 5) {
     // One workgroup per CU, all of them in lockstep: a tile's stores (25 MB per round of the chip) are not hidden by anybody's MFMAs,
-    // ~10 us per round (tools/mb_w4_loop.py).  With ONE tile per workgroup that is paid once and the deep operand pipeline wins
+    // ~10 us per round (measured with an ablation build).  With ONE tile per workgroup that is paid once and the deep operand pipeline wins
     // (dgrads into N = 768: -13 .. -15 %, fc2 forward: -3 %); with 3-4 tiles per workgroup the older kernels, whose 2-3 workgroups
     // per CU overlap each other's epilogues, stay ahead (+14 .. +19 %).  mode 3 = every whole-round shape (for measurements).
     // Round 5 (tools/routing_check.py at token counts the routing had not been tuned on, profiles/r05_routing_check.txt): the data
@@ -954,8 +859,8 @@ int dm_gemm_w4_plan(GemmParams &p, const GemmSwitches &sw, int layout, int ab_dt
     const long long rounds = (tiles + cus - 1) / cus;
     if ((double)tiles / (double)(rounds * cus) < 0.85) return 0;
   }
-  static const bool attr_ok = w4_set_lds_limit<DM_NT>() && w4_set_lds_limit<DM_NN>() && w4_set_lds_limit<DM_NT, 0, 1>() && w4_set_lds_limit<DM_NT, 0, 10>() &&
-                              w4_set_lds_limit<DM_NT, 0, 17>() && w4_set_lds_limit<DM_NN, 0, 1>() && w4_set_lds_limit<DM_NN, 0, 5>();
+  static const bool attr_ok = w4_set_lds_limit<DM_NT>() && w4_set_lds_limit<DM_NN>() && w4_set_lds_limit<DM_NT, 1>() && w4_set_lds_limit<DM_NT, 10>() &&
+                              w4_set_lds_limit<DM_NT, 17>() && w4_set_lds_limit<DM_NN, 1>() && w4_set_lds_limit<DM_NN, 5>();
   if (!attr_ok) return 0;
   p.tiles_m = tiles_m;
   p.tiles_n = tiles_n;
@@ -965,16 +870,6 @@ int dm_gemm_w4_plan(GemmParams &p, const GemmSwitches &sw, int layout, int ab_dt
 }
 
 void dm_gemm_w4_launch(const GemmParams &p, int layout, int grid, hipStream_t s) {
-#ifdef DM_W4_ABLATE
-  if (layout == DM_NT) {
-    const char *denv = getenv("DM_W4_DEBUG");
-    const int dbg = denv ? atoi(denv) : 0;
-#define W4_CASE(D) case D: { static const bool ok = w4_set_lds_limit<DM_NT, D>(); (void)ok; \
-      hipLaunchKernelGGL((dmw4::gemm_w4_kernel<DM_NT, D>), dim3(grid), dim3(256), dmw4::LDS_BYTES, s, p); return; }
-    switch (dbg) { W4_CASE(1) W4_CASE(5) W4_CASE(13) W4_CASE(29) W4_CASE(33) W4_CASE(17) W4_CASE(9) W4_CASE(61) W4_CASE(45) W4_CASE(65) W4_CASE(73) W4_CASE(3) W4_CASE(128) W4_CASE(256) W4_CASE(320) W4_CASE(64) default: break; }
-#undef W4_CASE
-  }
-#endif
   // Which epilogue: the lean form (dm_gemm_common.h) where its preconditions hold -- plain rows, 32-bit offsets inside a wave pair's
   // 128 rows -- and the item structure is one of the instantiated ones; the generic form otherwise (and with DM_GEMM_EPI_LEAN=0).
   constexpr long long LIM = (1LL << 31) / (128LL * 4);
@@ -985,17 +880,11 @@ void dm_gemm_w4_launch(const GemmParams &p, int layout, int grid, hipStream_t s)
   const int yl = (c32 && p.accumulate && p.split_k <= 1) ? 1 : aux_read ? (x32 ? 3 : 2) : 0;
   const int xs = aux_write ? (x32 ? 2 : 1) : 0;
   const int key = (p.residual ? 1 : 0) | (yl << 1) | ((c32 ? 1 : 0) << 3) | (xs << 4);
-  GemmParams q = p;
-  {
-    const char *senv = getenv("DM_W4_STAGGER");
-    const int stag = senv ? atoi(senv) : 0;
-    if (stag > 0 && layout != DM_TN && q.tiles_m * q.tiles_n > grid) q.debug |= (stag & 0x7fff) << 16;      // multi-tile forward / dgrad launches only
-  }
-#define W4_GO(LAY, EKV) hipLaunchKernelGGL((dmw4::gemm_w4_kernel<LAY, 0, EKV>), dim3(grid), dim3(256), dmw4::LDS_BYTES, s, q)
-#define W4_GOF(LAY, EKV) hipLaunchKernelGGL((dmw4::gemm_w4_kernel<LAY, 0, EKV, true>), dim3(grid), dim3(256), dmw4::LDS_BYTES, s, q)
+#define W4_GO(LAY, EKV) hipLaunchKernelGGL((dmw4::gemm_w4_kernel<LAY, EKV>), dim3(grid), dim3(256), dmw4::LDS_BYTES, s, p)
+#define W4_GOF(LAY, EKV) hipLaunchKernelGGL((dmw4::gemm_w4_kernel<LAY, EKV, true>), dim3(grid), dim3(256), dmw4::LDS_BYTES, s, p)
 // weight gradients: the instance with the column-sum MFMAs only when the launch wants column sums
-#define W4_GOT(EKV, FOLDV) do { if (q.colsum_slab) hipLaunchKernelGGL((dmw4::gemm_w4_kernel<DM_TN, 0, EKV, FOLDV, true>), dim3(grid), dim3(256), dmw4::LDS_BYTES, s, q); \
-    else hipLaunchKernelGGL((dmw4::gemm_w4_kernel<DM_TN, 0, EKV, FOLDV, false>), dim3(grid), dim3(256), dmw4::LDS_BYTES, s, q); } while (0)
+#define W4_GOT(EKV, FOLDV) do { if (p.colsum_slab) hipLaunchKernelGGL((dmw4::gemm_w4_kernel<DM_TN, EKV, FOLDV, true>), dim3(grid), dim3(256), dmw4::LDS_BYTES, s, p); \
+    else hipLaunchKernelGGL((dmw4::gemm_w4_kernel<DM_TN, EKV, FOLDV, false>), dim3(grid), dim3(256), dmw4::LDS_BYTES, s, p); } while (0)
   if (p.k_fold > 0) {                                      // hi / lo plane pairs ("bf16x3"): fp32 outputs
     if (layout == DM_TN) {
       if (lean_ok && key == 8) W4_GOT(9, true);
@@ -1013,8 +902,6 @@ void dm_gemm_w4_launch(const GemmParams &p, int layout, int grid, hipStream_t s)
     if (lean_ok && key == 8) W4_GOT(9, false);            // fp32 slab / gradient written
     else if (lean_ok && key == 10) W4_GOT(11, false);     // fp32 gradient accumulated in place
     else W4_GOT(0, false);
-  } else if (p.split_k > 1) {                             // sliced forward / dgrad: fp32 partial tile into the slab
-    if (layout == DM_NT) W4_GO(DM_NT, 9); else W4_GO(DM_NN, 9);
   } else if (layout == DM_NT) {
     if (lean_ok && key == 0) W4_GO(DM_NT, 1);             // bf16 C
     else if (lean_ok && key == 9) W4_GO(DM_NT, 10);       // fp32 C + fp32 residual: fc2 / proj forward

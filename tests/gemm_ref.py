@@ -68,7 +68,7 @@ SPECIALISED_KEYS = (0, 1 | (1 << 3), 1 << 3, (1 << 1) | (1 << 3), 1 << 4, 2 << 1
 # nearest shape that does is taken and the reason stands next to it.  `wave` = (rows, columns) of a wave's block, `tile` = (rows, columns)
 # of the workgroup's tile, `bk` = the K step.  `env`: the switches read_switches (deepmerge_amd/csrc/dm_gemm.hip) reads on every call; a key set to
 # None is removed from the environment.  `codes`: the `_t<code>` of the family's profiler row (prof_family_code), () = no row at all.
-_OFF = {"DM_GEMM_W4": "0", "DM_GEMM_Q4": "0", "DM_GEMM_RING": "0", "DM_GEMM_256": "0", "DM_GEMM_FORCE_TILE": "0", "DM_GEMM_RING_WM": None, "DM_GEMM_256P": None}
+_OFF = {"DM_GEMM_W4": "0", "DM_GEMM_Q4": "0", "DM_GEMM_RING": "0", "DM_GEMM_256": "0", "DM_GEMM_FORCE_TILE": "0", "DM_GEMM_RING_WM": None}
 _Q4_SKIPS = {
     "bias_res_acc_f32": "dm_gemm_q4.hip dm_gemm_q4_plan: `if (!dm_epi_key_specialised(dm_epi_lean_key(p, 64))) return false` (residual + accumulate has no straight-line instance)",
     "gelu_save_f32": "dm_gemm_q4.hip dm_gemm_q4_plan: `if (!dm_epi_key_specialised(...)) return false` (fp32 aux written)",
@@ -77,8 +77,6 @@ _Q4_SKIPS = {
     "grouped41": "dm_gemm_q4.hip dm_gemm_q4_plan: `if (!dm_epi_key_specialised(...)) return false` (grouped rows: dm_epi_lean_key is -1)",
     "grouped41_gelugrad": "dm_gemm_q4.hip dm_gemm_q4_plan: `if (!dm_epi_key_specialised(...)) return false` (grouped rows: dm_epi_lean_key is -1)",
 }
-_P256P_SKIPS = {name: "dm_gemm256.hip dm_gemm256_launch: `... && rows_ok && dm_epi_key_specialised(dm_epi_lean_key(p, 128))` (else the launch falls to gemm256_kernel, "
-                      "the p256 family; plane pairs: `p.c_dtype != DM_BF16_PAIR`)" for name in _Q4_SKIPS}
 _PAIR_F32 = {"pair_gelu": "dm_gemm.hip gemm_prepare: `a plane-pair result needs an NT / NN bf16 product ...` (ab_dtype == DM_BF16)"}
 _GENERIC_SKIPS = {name: "dm_gemm.hip gemm_generic: `a->ab_dtype == DM_F32 && a->c_dtype == DM_F32 && (a->aux == nullptr || a->aux_dtype == DM_F32)` (the generic path is fp32-only)"
                   for name in ("none_bf16", "gelu_bf16_nosave", "gelu_save_bf16", "gelugrad_save_bf16", "mul_bf16", "pair_gelu", "grouped41_gelugrad")}
@@ -116,12 +114,6 @@ FAMILIES = {
     # 256 x 256 pipeline (one tile per workgroup), a wave owns 128 x 64: N = 200 is one tile, N = 328 = 256 + 72 is two with the same tail
     "p256": dict(ab=BF16, shape=(328, 328, 192), layouts=("NT", "NN"), tile=(256, 256), wave=(128, 64), bk=64, codes=(256,), fast=True,
                  env=dict(_OFF, DM_GEMM_256="2"), skips={}),
-    # the persistent form of the pipeline (DM_GEMM_256P = 2: every legal launch; read per call).  dm_gemm256_launch takes it only with
-    # `p.N % 256 == 0` -> N = 512 (two tiles, no N tail exists for this form) and `dm_epi_key_specialised(dm_epi_lean_key(p, 128))`; any other
-    # launch runs the one-tile-per-workgroup kernel above under the same code 256, which the row cannot tell apart, so those
-    # configurations are left to p256
-    "p256p": dict(ab=BF16, shape=(328, 512, 192), layouts=("NT", "NN"), tile=(256, 256), wave=(128, 64), bk=64, codes=(256,), fast=True,
-                  env=dict(_OFF, DM_GEMM_256="2", DM_GEMM_256P="2"), skips=_P256P_SKIPS),
     # forward / dgrad K slices.  plan_fwd_split(M = 328, N = 200, K = 1536): N % 8 == 0 and K >= 1536; 3 * 2 = 6 tiles of 128 x 128 < 256; split = 4 gives
     # K / 4 = 384 < 8 * 64, split = 2 gives 768 >= 512; 6 * 2 < 512 -> two slices on 64 x 64 tiles, summed and emitted by splitk_epilogue_kernel (dm_gemm_emit8).
     # DM_GEMM_FORCE_TILE must be absent (`!sw.force_tile_set`); the row carries the tile, 64 -- the same code as unsplit 64 x 64 tiles, so the

@@ -5,10 +5,15 @@
     orders and with or without fused multiply-add;
   * every BOUNDED configuration's float32 restatement stays at or below half its bound, and no constant is larger than that needs;
   * the case table is well formed: the extents each family needs, 16-byte aligned views, >= 256 rows and >= 8 columns of sentinel, the
-    grouped cube inside its allocation, every skip documented.
+    grouped cube inside its allocation, every skip documented;
+  * the DM_GEMM_* switches the GPU test clears for its children are exactly the ones the library reads.
 
 Worst err / tol of the restatements is printed ("[gemm_host] ..."; run with -s); the table is at the top of tests/test_gpu_gemm_epilogues.py.
 """
+import glob
+import os
+import re
+
 import numpy as np
 import pytest
 import torch
@@ -187,7 +192,7 @@ def test_case_table_is_well_formed():
         assert keys[name] >= 0 and keys[name] not in G.SPECIALISED_KEYS
     assert all(f in G.FAMILIES and G.FAMILIES[f]["tile"] == (64, 64) and n == "mul_bf16" for f, n in G.STRIP_ZERO_SIGN)
     assert keys["pair_gelu"] == 1 << 8 and keys["grouped41"] == -1 == keys["grouped41_gelugrad"]
-    assert set(G.FAMILIES) == {"t64", "t128", "f32_t64", "f32_t128", "ring8", "ring4", "q4", "w4", "p256", "p256p", "kslices", "generic"}
+    assert set(G.FAMILIES) == {"t64", "t128", "f32_t64", "f32_t128", "ring8", "ring4", "q4", "w4", "p256", "kslices", "generic"}
 
     for fam, f in G.FAMILIES.items():
         M, N, K = f["shape"]
@@ -205,9 +210,6 @@ def test_case_table_is_well_formed():
         assert N % 8 == 0
         if fam == "w4":
             assert N % 192 == 0 and K % 128 == 0                                            # dm_gemm_w4_plan
-        elif fam == "p256p":
-            assert N % 256 == 0                                                             # dm_gemm256_launch
-            assert set(G.family_configs(fam)) == {c["name"] for c in G.CONFIGS if G.lean_key(c) in G.SPECIALISED_KEYS}
         else:
             assert N % tn != 0 and (N % wn) == 8, fam                                       # an N tail that ends inside a wave's columns
         steps = (K + f["bk"] - 1) // f["bk"]
@@ -258,3 +260,26 @@ def test_case_table_is_well_formed():
             else:
                 assert len(set(lds)) == len(lds)                                            # all leading dimensions differ
                 assert b["rows_per_group"] == 0
+
+
+def test_switch_list_is_what_the_library_reads():
+    """The DM_GEMM_* names the library hands to getenv are, as a set, ONCE_PER_PROCESS of tests/test_gpu_gemm_epilogues.py plus the names
+    read_switches() reads on every call; each name is read in exactly one place, and that place is dm_gemm.hip."""
+    from test_gpu_gemm_epilogues import ONCE_PER_PROCESS
+    csrc = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "deepmerge_amd", "csrc")
+    pattern = re.compile(r'getenv\(\s*"(DM_GEMM_\w+)"')
+    read = {}
+    for path in sorted(glob.glob(os.path.join(csrc, "*"))):
+        if os.path.isfile(path):
+            with open(path, errors="replace") as f:
+                read[os.path.basename(path)] = pattern.findall(f.read())
+    names = [n for found in read.values() for n in found]
+    assert names and sorted(names) == sorted(set(names)), sorted(n for n in set(names) if names.count(n) > 1)
+    assert {f for f, found in read.items() if found} == {"dm_gemm.hip"}
+    with open(os.path.join(csrc, "dm_gemm.hip")) as f:
+        src = f.read()
+    body = src[src.index("GemmSwitches read_switches()"):]
+    per_call = pattern.findall(body[:body.index("\n}\n")])
+    assert "DM_GEMM_RING_WM" in per_call and "DM_GEMM_FORCE_TILE" in per_call
+    assert len(set(ONCE_PER_PROCESS)) == len(ONCE_PER_PROCESS)
+    assert set(names) == set(ONCE_PER_PROCESS) | set(per_call), set(names) ^ (set(ONCE_PER_PROCESS) | set(per_call))
