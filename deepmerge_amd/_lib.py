@@ -164,6 +164,8 @@ SIGNATURES = {
     "dm_merge_edge_keys": (_I, [_P, _P, _P, _I, _I, _P, _P]),
     "dm_merge_fold_edges": (_I, [_P, _P, _P, _I, _P, _P, _P, _P]),
     "dm_relabel_raster": (_I, [_P, _P, _P, _L, _I, _P]),
+    "dm_region_merge_cost": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _D, _D, _D, _D, _D, _P, _P]),
+    "dm_pixel_regions": (_I, [_P, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P]),
     "dm_label_clearance": (_I, [_P, _I, _I, _I, _P, _P, _P, _P]),
     "dm_point_select_round": (_I, [_P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P]),
     "dm_point_emit": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P]),

@@ -14,6 +14,9 @@ layer and `lines.shp` (csrc/dm_vector.hip; spec tests/vector_ref.py); deepmerge_
 `labels_from_shapefile` reads the rings from a polygon shapefile, the form the reference's users have their data in.
 `simplify` is Douglas-Peucker on the traced geometry, once per shared boundary, so neighbours keep sharing every vertex
 (csrc/dm_simplify.hip; spec tests/simplify_ref.py).
+`mrs` is multiresolution segmentation, the classical baseline of the learned merge and a second source of superpixels: the rounds of
+`merge_regions` scored by the colour / shape heterogeneity cost of the regions' statistics, from single pixels or from a label raster
+(csrc/dm_mrs.hip; spec tests/mrs_ref.py).
 """
 from __future__ import annotations
 
@@ -307,6 +310,27 @@ def merge_regions(features: torch.Tensor, ptr: torch.Tensor, idx: torch.Tensor, 
             raise ValueError("stats['bands'] must be 1..3")
     features, ptr, idx, edges = features.contiguous(), ptr.contiguous(), idx.contiguous(), edges.contiguous()
     _check_merge_inputs(features, ptr, idx, edges, S0)
+    lib = _lib.lib()
+    pooled = torch.empty((S0, D), dtype=torch.float32, device=ptr.device)
+
+    def score(cur, C, E, simi, stream):                          # segment mean + edge similarity: the sweep's kernels
+        check(lib.dm_segment_mean(features.data_ptr(), cur["ptr"].data_ptr(), cur["idx"].data_ptr(), pooled.data_ptr(), C, D, stream),
+              "dm_segment_mean")
+        if E:
+            check(lib.dm_edge_similarity(pooled.data_ptr(), cur["edges"].data_ptr(), simi.data_ptr(), None, E, D, margin, stream),
+                  "dm_edge_similarity")
+
+    return _merge_loop(score, margin, pooled, ptr, idx, edges, weights, stats, nb, max_rounds, min_regions)
+
+
+def _merge_loop(score, margin: float, pooled: torch.Tensor, ptr: torch.Tensor, idx: torch.Tensor, edges: torch.Tensor,
+                weights: Optional[torch.Tensor], stats: Optional[Dict[str, torch.Tensor]], nb: int, max_rounds: Optional[int],
+                min_regions: int) -> MergeResult:
+    """The rounds of the mutual-best merge (include/deepmerge_hip.h) around a pluggable score step, for `merge_regions` and `mrs`.
+    score(cur, C, E, simi, stream) writes simi[:E] for the partition `cur` (the dict of its device arrays) and whatever it keeps of
+    its own (`pooled [S0,D]`, whose first C rows go into the result); an edge is a candidate iff simi < margin.  The inputs are
+    checked and contiguous.  P = len(idx) may be 0: then no point list is read or written."""
+    S0, P, E0 = ptr.numel() - 1, idx.numel(), edges.shape[0]
     dev, lib, i32 = ptr.device, _lib.lib(), torch.int32
 
     def new_state():
@@ -324,7 +348,6 @@ def merge_regions(features: torch.Tensor, ptr: torch.Tensor, idx: torch.Tensor, 
     if stats is not None:
         cur.update({k: stats[k].contiguous() for k in _STAT_KEYS})
     spare = [new_state(), new_state()] if E0 else []
-    pooled = torch.empty((S0, D), dtype=torch.float32, device=dev)
     simi = torch.empty(E0, dtype=torch.float32, device=dev)
     best = torch.empty(S0, dtype=torch.int64, device=dev)
     picked = torch.empty(E0, dtype=torch.uint8, device=dev)
@@ -333,17 +356,13 @@ def merge_regions(features: torch.Tensor, ptr: torch.Tensor, idx: torch.Tensor, 
     meta = torch.zeros(3, dtype=i32, device=dev)                 # picked edges, new C, new E: the round's one readback
     history = torch.empty((S0, 3), dtype=i32, device=dev)
     history_simi = torch.empty(S0, dtype=torch.float32, device=dev)
-    ptr_of = lambda t: None if t is None else t.data_ptr()
+    ptr_of = lambda t: (t.data_ptr() or None) if t is not None else None      # an empty tensor (no points) has no address
 
     C, E, rounds, n_hist = S0, E0, 0, 0
     regions, merges = [S0], []
     while True:
         stream = _stream()
-        check(lib.dm_segment_mean(features.data_ptr(), cur["ptr"].data_ptr(), cur["idx"].data_ptr(), pooled.data_ptr(), C, D, stream),
-              "dm_segment_mean")
-        if E:
-            check(lib.dm_edge_similarity(pooled.data_ptr(), cur["edges"].data_ptr(), simi.data_ptr(), None, E, D, margin, stream),
-                  "dm_edge_similarity")
+        score(cur, C, E, simi, stream)
         if E == 0 or C <= max(min_regions, 1) or (max_rounds is not None and rounds >= max_rounds):
             break
         nxt = spare[rounds & 1]
@@ -381,6 +400,159 @@ def merge_regions(features: torch.Tensor, ptr: torch.Tensor, idx: torch.Tensor, 
                        weights=None if weights is None else cur["weights"].clone(), stats=out_stats, pooled=pooled[:C].clone(),
                        simi=simi[:E].clone(), rep=cur["rep"].clone(), rounds=rounds, history=history[:n_hist].clone(),
                        history_simi=history_simi[:n_hist].clone(), regions_per_round=regions, merges_per_round=merges)
+
+
+# ---- multiresolution region merging (csrc/dm_mrs.hip; the rule: include/deepmerge_hip.h; spec tests/mrs_ref.py) ----
+MAX_REGIONS = 1 << 24     # what a merge takes (dm_merge_best's key keeps the neighbour id beside the score)
+
+
+def _on_device(*ts):
+    """`_need_cuda` for the entry points below, whose bad arguments are all ValueErrors."""
+    try:
+        _need_cuda(*ts)
+    except RuntimeError as e:
+        raise ValueError(str(e)) from None
+
+
+def _mrs_params(nb: int, shape: float, compactness: float, band_weights) -> Tuple[float, float, List[float]]:
+    shape, compactness = float(shape), float(compactness)
+    if not 0.0 <= shape < 1.0:
+        raise ValueError(f"shape must be in [0, 1), got {shape}")
+    if not 0.0 <= compactness <= 1.0:
+        raise ValueError(f"compactness must be in [0, 1], got {compactness}")
+    bw = [1.0] * nb if band_weights is None else [float(v) for v in band_weights]
+    if len(bw) != nb:
+        raise ValueError(f"band_weights must have {nb} values (one per band that counts), got {len(bw)}")
+    if not all(math.isfinite(v) and v >= 0.0 for v in bw):
+        raise ValueError(f"band_weights must be finite and >= 0, got {bw}")
+    return shape, compactness, bw + [1.0] * (3 - nb)
+
+
+def _check_stats(stats: Dict[str, torch.Tensor], C: int) -> int:
+    nb = int(stats["bands"])
+    if not 1 <= nb <= 3:
+        raise ValueError("stats['bands'] must be 1..3")
+    want = {"count": (torch.int64, (C,)), "sum": (torch.int64, (C, nb)), "sumsq": (torch.int64, (C, nb)),
+            "bbox": (torch.int32, (C, 4)), "peri": (torch.int64, (C, 2))}
+    for k, (dt, shape) in want.items():
+        if stats[k].dtype != dt or tuple(stats[k].shape) != shape:
+            raise ValueError(f"stats[{k!r}] must be {dt} {list(shape)} (as label_stats returns it)")
+    return nb
+
+
+def _launch_merge_cost(lib, st, edges, weights, E: int, C: int, nb: int, bw, shape: float, compactness: float, cost, stream):
+    check(lib.dm_region_merge_cost(st["count"].data_ptr(), st["sum"].data_ptr(), st["sumsq"].data_ptr(), st["bbox"].data_ptr(),
+                                   st["peri"].data_ptr(), edges.data_ptr(), weights.data_ptr(), E, C, nb, bw[0], bw[1], bw[2], shape,
+                                   compactness, cost.data_ptr(), stream), "dm_region_merge_cost")
+
+
+def region_merge_cost(stats: Dict[str, torch.Tensor], edges: torch.Tensor, weights: torch.Tensor, shape: float = 0.1,
+                      compactness: float = 0.5, band_weights=None) -> torch.Tensor:
+    """float32 [E]: the multiresolution-segmentation cost of merging the two regions of every edge -- the increase of the
+    Baatz-Schaepe colour heterogeneity (n sigma per band, weighted by band_weights) and shape heterogeneity (compactness
+    n l / sqrt(n) and smoothness n l / b, mixed by `compactness`), mixed by `shape`, clamped at 0 -- from `label_stats`' exact
+    statistics and `rag_edges`' boundary lengths.  Every region of an edge must have count > 0 (else its cost is NaN)."""
+    _on_device(edges, weights, *(stats[k] for k in _STAT_KEYS))
+    if edges.dtype != torch.int32 or edges.dim() != 2 or edges.shape[1] != 2:
+        raise ValueError("edges must be int32 [E,2]")
+    E, C = edges.shape[0], stats["count"].numel()
+    if weights.dtype != torch.int32 or tuple(weights.shape) != (E,):
+        raise ValueError("weights must be int32 [E]")
+    nb = _check_stats(stats, C)
+    if not 1 <= C <= MAX_REGIONS:
+        raise ValueError(f"region_merge_cost takes 1 to 2^24 regions, got {C}")
+    shape, compactness, bw = _mrs_params(nb, shape, compactness, band_weights)
+    cost = torch.empty(E, dtype=torch.float32, device=edges.device)
+    if E:
+        _launch_merge_cost(_lib.lib(), {k: stats[k].contiguous() for k in _STAT_KEYS}, edges.contiguous(), weights.contiguous(), E, C, nb,
+                           bw, shape, compactness, cost, _stream())
+    return cost
+
+
+def _check_tile(tile: torch.Tensor):
+    _on_device(tile)
+    if tile.dtype != torch.uint8 or tile.dim() != 3 or tile.shape[0] < 1 or tile.shape[1] < 1 or tile.shape[2] < 1:
+        raise ValueError("tile must be uint8 [bands,H,W] with bands, H, W >= 1")
+
+
+def pixel_regions(tile: torch.Tensor) -> Tuple[Dict[str, torch.Tensor], torch.Tensor, torch.Tensor]:
+    """(stats, edges, weights) of the partition in which pixel (y, x) is region y * W + x: what `label_stats` and `rag_edges` give
+    for an `arange` raster, bit for bit, written in closed form (no hash table).  H * W <= 2^24."""
+    _check_tile(tile)
+    bands, H, W = tile.shape
+    if H * W > MAX_REGIONS:
+        raise ValueError(f"a pixel start takes at most 2^24 pixels, got {H} x {W} = {H * W}")
+    tile = tile.contiguous()
+    n, nb, dev, E = H * W, min(bands, 3), tile.device, H * (W - 1) + (H - 1) * W
+    stats = {"count": torch.empty(n, dtype=torch.int64, device=dev), "sum": torch.empty((n, nb), dtype=torch.int64, device=dev),
+             "sumsq": torch.empty((n, nb), dtype=torch.int64, device=dev), "bbox": torch.empty((n, 4), dtype=torch.int32, device=dev),
+             "peri": torch.empty((n, 2), dtype=torch.int64, device=dev)}
+    edges = torch.empty((E, 2), dtype=torch.int32, device=dev)
+    weights = torch.empty(E, dtype=torch.int32, device=dev)
+    check(_lib.lib().dm_pixel_regions(tile.data_ptr(), bands, H, W, stats["count"].data_ptr(), stats["sum"].data_ptr(),
+                                      stats["sumsq"].data_ptr(), stats["bbox"].data_ptr(), stats["peri"].data_ptr(),
+                                      edges.data_ptr() or None, weights.data_ptr() or None, _stream()), "dm_pixel_regions")
+    stats["bands"] = nb
+    return stats, edges, weights
+
+
+def mrs(tile: torch.Tensor, scale: float, shape: float = 0.1, compactness: float = 0.5, band_weights=None,
+        labels: Optional[torch.Tensor] = None, n_labels: Optional[int] = None, max_rounds: Optional[int] = None,
+        min_regions: int = 0) -> MergeResult:
+    """Multiresolution segmentation: mutual-best region merging by `region_merge_cost`, the classical baseline of the learned
+    merge and a second source of superpixels.
+
+    tile uint8 [bands,H,W] (the first three bands count).  Per round every region chooses its cheapest neighbour among the edges
+    with cost < scale^2 (ties: smallest id), mutual choices merge, and statistics, edges and boundary lengths are folded -- the
+    rounds of `merge_regions`, with the cost in place of the learned similarity and no point lists.  Starts from single pixels
+    (labels None: S0 = H * W <= 2^24 and `result.region_of.view(H, W)` is the label raster) or from a label raster (labels int32
+    [H,W] with every id in [0, n_labels) present: `result.labels(labels)` is the raster).  The result has pooled [C,0], ptr zeros,
+    idx empty, simi = the cost of the final partition's edges; `labels()`, `polygons()`, `simplified()`, `scores()` and
+    `region_of_at()` work as on any MergeResult.  Stops as `merge_regions` does.  The inputs are not modified; one small readback per
+    round."""
+    _check_tile(tile)
+    scale = float(scale)
+    if not (math.isfinite(scale) and scale > 0.0):
+        raise ValueError(f"scale must be finite and > 0, got {scale}")
+    bands, H, W = tile.shape
+    shape, compactness, bw = _mrs_params(min(bands, 3), shape, compactness, band_weights)
+    if max_rounds is not None and max_rounds < 0:
+        raise ValueError("max_rounds must be >= 0 or None")
+    if labels is None:
+        if n_labels is not None:
+            raise ValueError("n_labels goes with labels")
+        stats, edges, weights = pixel_regions(tile)
+        S0 = H * W
+    else:
+        _on_device(labels)
+        if labels.dtype != torch.int32 or tuple(labels.shape) != (H, W):
+            raise ValueError("labels must be int32 [H,W] over the tile's raster")
+        if n_labels is None or not 1 <= int(n_labels) <= MAX_REGIONS:
+            raise ValueError(f"n_labels must be given with labels, 1 to 2^24, got {n_labels}")
+        S0 = int(n_labels)
+        stats = label_stats(labels, tile, S0)
+        if bool((stats["count"] == 0).any()):                    # (the one readback before round 1)
+            raise ValueError("mrs: every id in [0, n_labels) must occur in labels (a region without pixels has no cost)")
+        edges, weights = rag_edges(labels, S0)
+        edges, weights = edges.contiguous(), weights.contiguous()
+    nb, dev, lib = stats["bands"], tile.device, _lib.lib()
+
+    def score(cur, C, E, simi, stream):
+        if E:
+            _launch_merge_cost(lib, cur, cur["edges"], cur["weights"], E, C, nb, bw, shape, compactness, simi, stream)
+
+    return _merge_loop(score, scale * scale, torch.empty((S0, 0), dtype=torch.float32, device=dev),
+                       torch.zeros(S0 + 1, dtype=torch.int32, device=dev), torch.empty(0, dtype=torch.int32, device=dev), edges, weights,
+                       stats, nb, max_rounds, min_regions)
+
+
+def mrs_segment(tile: torch.Tensor, scale: float, **kw) -> Tuple[torch.Tensor, int]:
+    """(labels int32 [H,W] with dense ids 0..n-1, n): `mrs` as a segmenter, the pair `slic` returns, so that
+    `FeatureIO.merge_tile(tile, *mrs_segment(tile, scale))` is the pipeline on multiresolution superpixels."""
+    res = mrs(tile, scale, **kw)
+    start = kw.get("labels")
+    raster = res.region_of.view(tile.shape[1], tile.shape[2]).clone() if start is None else res.labels(start)
+    return raster, res.rep.numel()
 
 
 # ---- sample points and window sides from the label raster (csrc/dm_points.hip; the rule: include/deepmerge_hip.h, DESIGN.md 3.5.2) ----

@@ -46,7 +46,8 @@ typedef enum {
 int dm_abi_version(void);   /* 2: dm_patch_pyramid / dm_patch_pyramid_cols take a resize rule; 3: table-reading and split-bf16 attention entry points, dm_split_bf16_colsum (round 3);
                              * 4: DmGemmArgs.k_fold / a_fold / b_fold, dm_split_bf16_planes (round 4); 5: dm_pair_batch_gather (round 5); 6: dm_gemm_grouped (round 5);
                              * 7: dm_gemm_grouped(args, n, stream) without a group workspace, its workspace query removed;
-                             * additive in 6: dm_pairwise_distance, dm_pair_epoch_draw, dm_contrastive_terms, dm_pair_eval_summary */
+                             * additive in 6: dm_pairwise_distance, dm_pair_epoch_draw, dm_contrastive_terms, dm_pair_eval_summary;
+                             * additive in 7: dm_region_merge_cost, dm_pixel_regions */
 const char *dm_last_error(void);
 /* Name of the code object architecture the library was built for ("gfx950"). */
 const char *dm_arch(void);
@@ -528,6 +529,43 @@ int dm_merge_edge_keys(const int32_t *edges, const int32_t *root, const int32_t 
 int dm_merge_fold_edges(const int64_t *sorted_keys, const int64_t *order, const int32_t *weights, int32_t E, int32_t *new_edges,
                         int32_t *new_weights, int32_t *n_edges, void *stream);
 int dm_relabel_raster(const int32_t *labels, const int32_t *map, int32_t *out, int64_t n, int32_t S, void *stream);
+
+/* ---- multiresolution region merging (additive in ABI 7; csrc/dm_mrs.hip, DESIGN.md 3.5.8, rag.mrs) --------------------------
+ * The classical baseline of a learned merge: the Baatz-Schaepe colour / shape heterogeneity criterion, driven by the mutual-best
+ * merge above.  The rule.  State of a round: the state above without point lists (ptr all zeros, P = 0): C regions, edges,
+ * weights = shared boundary length, and the five statistics of dm_label_stats for nb = min(bands, 3) bands.  Exact integers:
+ *   region r:        n_r = count[r];  l_r = peri[r,0] + peri[r,1];  b_r = 2 ((x1 - x0 + 1) + (y1 - y0 + 1)) from bbox[r];
+ *                    V_r,c = n_r sumsq[r,c] - sum[r,c]^2  (= (n sigma)^2, never negative)
+ *   union m of edge (a, b, w):  n_m = n_a + n_b;  sum, sumsq added;  l_m = l_a + l_b - 2 w;  b_m from the union of the boxes.
+ * V needs up to 78 bits (count up to 2^31): it is formed in 128-bit integers and converted to double with ONE rounding to
+ * nearest-even (hi = V >> 32 < 2^46 and lo = V & 0xffffffff convert exactly, double(hi) * 2^32 is exact, the add rounds).
+ * n, l, b are converted to double one by one.  Then, in IEEE double operations, no FMA contraction, in exactly this association:
+ *   hc  = 0.0;  for c in 0..nb-1:  hc = hc + bw[c] * ((sqrt(V_m,c) - sqrt(V_a,c)) - sqrt(V_b,c))
+ *   hcm = (l_m * sqrt(n_m) - l_a * sqrt(n_a)) - l_b * sqrt(n_b)                 compactness: n * l / sqrt(n)
+ *   hsm = ((n_m * l_m) / b_m - (n_a * l_a) / b_a) - (n_b * l_b) / b_b           smoothness:  n * l / b
+ *   hs  = compactness * hcm + (1.0 - compactness) * hsm
+ *   f   = (1.0 - shape) * hc + shape * hs
+ *   cost = float32(f > 0.0 ? f : 0.0)
+ * The clamp to +0.0 is part of the rule: a merge that shortens the outline makes the shape term negative, and dm_merge_best
+ * orders candidates by the bit pattern of a non-negative float.  All non-positive costs are equally best; ties go to the smaller
+ * neighbour id.  An edge is a candidate iff cost < float32(scale * scale) (float compare); steps 2 to 5 above follow unchanged,
+ * with simi = cost in the history.  shape in [0, 1), compactness in [0, 1], band weights finite and >= 0, none normalised.
+ *
+ * dm_region_merge_cost: cost float32 [E] of the E >= 1 edges, one thread per edge; 1 <= C <= 2^24, bands in 1..3 (= nb; bw of a
+ *   band >= nb is checked and not used).  An edge with an endpoint outside [0, C) or with an empty region (count <= 0: it has no
+ *   cost) gets NaN, which is never a candidate.
+ * dm_pixel_regions: the start state in which pixel (y, x) of tile uint8 [bands,H,W] is region y W + x, in closed form: count 1,
+ *   sum = p, sumsq = p^2 for the first nb bands, bbox = the pixel, peri = (4-neighbours inside the raster, 4 minus that).  Pixel a
+ *   owns the edges (a, a + 1) if x + 1 < W, then (a, a + W) if y + 1 < H; its first edge is row y (2W - 1) + 2x of the list for
+ *   y + 1 < H and row y (2W - 1) + x on the last row, so edges int32 [E,2] comes out sorted and unique, E = H (W - 1) + (H - 1) W,
+ *   weights int32 [E] all 1.  1 <= H W <= 2^24; edges / weights may be NULL only for a 1 x 1 raster.  The result equals
+ *   dm_label_stats and dm_rag_edges (sorted) of the raster labels[y,x] = y W + x bit for bit.
+ * Both validate before any launch, launch on `stream`, never synchronise and never allocate. */
+int dm_region_merge_cost(const int64_t *count, const int64_t *sum, const int64_t *sumsq, const int32_t *bbox, const int64_t *peri,
+                         const int32_t *edges, const int32_t *weights, int32_t E, int32_t C, int32_t bands, double bw0, double bw1,
+                         double bw2, double shape, double compactness, float *cost, void *stream);
+int dm_pixel_regions(const uint8_t *tile, int32_t bands, int32_t H, int32_t W, int64_t *count, int64_t *sum, int64_t *sumsq,
+                     int32_t *bbox, int64_t *peri, int32_t *edges, int32_t *weights, void *stream);
 
 /* ---- sample points and window sides from a label raster (additive in ABI 6; csrc/dm_points.hip, DESIGN.md 3.5.2,
  * rag.clearance / rag.sample_points) ------------------------------------------------------------------------------------------
