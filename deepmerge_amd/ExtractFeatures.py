@@ -112,6 +112,13 @@ class FeatureIO:
         return result, pts, labels, n_labels
 
     @torch.no_grad()
+    def segment_scene(self, source, **kw):
+        """From a scene larger than one tile (anything with `.shape == (bands, H, W)` and `.read(y0, y1, x0, x1)`, or a host array
+        / memmap) to the merged partition: `scene.segment_scene(self, source, **kw)`.  Returns a `scene.SceneResult`."""
+        from . import scene
+        return scene.segment_scene(self, source, **kw)
+
+    @torch.no_grad()
     def _extract_local(self, tile, points_xy, inner, obj, region_features, batch_size):
         from .patches import point_batch_cols
         P = points_xy.shape[0]

@@ -157,6 +157,7 @@ SIGNATURES = {
     "dm_label_stats": (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P]),
     "dm_label_features": (_I, [_P, _P, _P, _P, _P, _I, _I, _P, _P]),
     "dm_rag_edges": (_I, [_P, _I, _I, _I, _P, _P, _I, _P, _P, _I, _P, _P, _P]),
+    "dm_seam_stitch": (_I, [_P, _P, _L, _L, _P, _P, _P, _I, _P, _P, _I, _P, _P, _P]),
     "dm_merge_round": (_I, [_P, _P, _I, _I, _P, _P, _I, _P]),
     "dm_merge_best": (_I, [_P, _P, _I, _I, _F, _P, _P]),
     "dm_merge_match": (_I, [_P, _P, _I, _I, _P, _P, _P, _P, _P]),

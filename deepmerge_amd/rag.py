@@ -102,6 +102,35 @@ def rag_edges(labels: torch.Tensor, n_labels: int, max_edges: int = 0) -> Tuple[
     return edges, w
 
 
+def seam_stitch(a: torch.Tensor, b: torch.Tensor, n_labels: int, peri: torch.Tensor, max_edges: int = 0) -> Tuple[torch.Tensor, torch.Tensor]:
+    """What lies between the tiles of a scene (csrc/dm_scene.hip; the rule: include/deepmerge_hip.h).
+
+    a, b int32 [n]: the scene-wide superpixel ids of the two pixels that face each other across every seam position, all seams
+    concatenated; peri int64 [n_labels,2]: `label_stats`' "peri" of every tile, concatenated.  Returns (edges int32 [E,2] with
+    a < b, sorted by (a, b); shared boundary length int32 [E]) of the pairs that face each other across a seam, as `rag_edges`
+    returns those inside a raster (max_edges as there), and UPDATES `peri` IN PLACE: every seam pixel edge leaves the "raster
+    border" column for the column `label_stats` on the assembled scene puts it in.  n == 0 (a scene of one tile) returns empty
+    tensors without a launch.  One readback, as `rag_edges`."""
+    _need_cuda(a, b, peri)
+    if a.dtype != torch.int32 or b.dtype != torch.int32 or a.dim() != 1 or a.shape != b.shape:
+        raise ValueError("a and b must be int32 [n], one entry per seam position")
+    S = int(n_labels)
+    if not 1 <= S <= MAX_REGIONS:
+        raise ValueError(f"n_labels must be in 1..2^24, got {n_labels}")
+    if peri.dtype != torch.int64 or tuple(peri.shape) != (S, 2) or not peri.is_contiguous():
+        raise ValueError(f"peri must be contiguous int64 [{S},2] (label_stats' 'peri' of every tile, concatenated)")
+    if a.device != b.device or a.device != peri.device:
+        raise ValueError("a, b and peri must be on one device")
+    n = a.numel()
+    if n == 0:
+        return torch.empty((0, 2), dtype=torch.int32, device=a.device), torch.empty(0, dtype=torch.int32, device=a.device)
+    a, b = a.contiguous(), b.contiguous()
+    k, w = _count_keys(a.device, S, max_edges, "the seam graph", "edges", lambda *table: check(
+        _lib.lib().dm_seam_stitch(a.data_ptr(), b.data_ptr(), n, S, peri.data_ptr(), *table, _stream()), "dm_seam_stitch"))
+    edges = torch.stack((k // S, k % S), 1).to(torch.int32)
+    return edges, w
+
+
 def points_to_csr(labels: torch.Tensor, xy: torch.Tensor, n_labels: int) -> Tuple[torch.Tensor, torch.Tensor]:
     """CSR membership (ptr int32 [S+1], idx int32 [P]) of sample points (x, y) in superpixels, the form
     rag_similarity_sweep consumes (the reference's space-separated `PointID` strings, ExtractFeatures.py:175-179).

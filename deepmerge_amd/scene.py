@@ -1,0 +1,314 @@
+"""Scenes larger than one tile: tile stream, seam stitch, one merge.
+
+Everything from image to merged partition elsewhere in this package works on one tile resident in HBM.  A real scene has 10^9 to
+10^10 pixels: it fits neither the raster kernels' index range (2^31 pixels) nor, with its intermediates, the device.  This
+module streams the scene through the device tile by tile and runs ONE merge over the scene's graph.
+
+The definition.  Superpixels are made per tile and never cross a seam.  Everything after that is, bit for bit, what the one-tile
+pipeline (`FeatureIO.merge_tile`) computes on the whole scene given the assembled seam-cut label raster with scene-wide ids:
+statistics, designed features, edges and boundary lengths, sample points and window fields, the crops the encoder sees, the
+merge.  What the per-tile passes cannot see -- the RAG edges whose two pixels lie in different tiles, and the pixel edges a tile
+counted as "raster border" although another label faces them -- is added by one `rag.seam_stitch` launch over all seams
+(csrc/dm_scene.hip).  The encoder's crops reach across seams: every tile is read with a halo of (max_window + 1) // 2 pixels.
+(The encoder's rows are bit-equal to the whole-scene call's as far as the encoder itself does not depend on which points share
+a batch: the batches of a scene break at tile boundaries.)
+
+Known consequence: where the learned merge does not join two superpixels across a seam, a straight boundary stays on the seam
+line.  Out of scope: superpixels that cross seams; a user label raster whose regions cross seams; rings and arcs across tiles
+(trace `SceneResult.merged_tile(i)` per tile); `rag.mrs` on a scene graph; overlapping the copy of the next tile with compute.
+
+Memory.  The scene's pixels are never on the device as a whole: one halo window at a time.  What is resident for the whole scene
+is per superpixel and per sample point: the statistics, the graph, the points and the [P,100] feature rows.  The scene-wide
+label raster lives on the host (`labels_out`, a numpy array or a memmap).  Every tile is read twice: once for the graph, once
+for the encode, because the designed features the encoder takes need the statistics of ALL tiles' seams first; the alternative
+(encode in the first pass once a tile's four neighbours are known) saves the second read at the price of per-tile bookkeeping.
+"""
+from __future__ import annotations
+
+import time
+from dataclasses import dataclass
+from typing import Callable, Dict, List, Optional, Tuple
+
+import numpy as np
+import torch
+
+from . import rag
+
+Core = Tuple[int, int, int, int]          # y0, y1, x0, x1
+
+
+class ArraySource:
+    """A scene held in a numpy array, an `np.memmap` or a CPU tensor ([bands,H,W] uint8 for an image, [H,W] int32 for a truth
+    raster): `.shape` and `.read(y0, y1, x0, x1)`, the two things `segment_scene` asks of a source."""
+
+    def __init__(self, array):
+        if isinstance(array, torch.Tensor):
+            if array.is_cuda:
+                raise ValueError("ArraySource wraps host memory (the scene is never on the device as a whole)")
+            array = array.numpy()
+        if not isinstance(array, np.ndarray) or array.ndim not in (2, 3):
+            raise ValueError("ArraySource takes a numpy array, an np.memmap or a CPU tensor of 2 or 3 dimensions")
+        self.array = array
+        self.shape = tuple(int(v) for v in array.shape)
+
+    def read(self, y0: int, y1: int, x0: int, x1: int) -> np.ndarray:
+        return np.ascontiguousarray(self.array[..., y0:y1, x0:x1])
+
+
+def tile_grid(H: int, W: int, tile) -> List[Core]:
+    """The row-major list of (y0, y1, x0, x1) cores that cover an H x W scene in tiles of `tile` (an int or (th, tw)); the last
+    row and column are ragged, down to 1 pixel."""
+    th, tw = (tile, tile) if isinstance(tile, int) else tuple(tile)
+    th, tw, H, W = int(th), int(tw), int(H), int(W)
+    if th < 1 or tw < 1:
+        raise ValueError(f"tile must be >= 1, got {tile}")
+    if H < 1 or W < 1:
+        raise ValueError(f"the scene must have at least one pixel, got {H} x {W}")
+    return [(y, min(H, y + th), x, min(W, x + tw)) for y in range(0, H, th) for x in range(0, W, tw)]
+
+
+def halo_of(max_window: int) -> int:
+    """Pixels a tile's window is grown by on every side: the crop of a window of side L <= max_window around (mx, my) starts at
+    (2 mx - L) / 2 >= mx - (max_window + 1) // 2 and ends before mx + L / 2 + 1."""
+    return (int(max_window) + 1) // 2
+
+
+def window_of(core: Core, H: int, W: int, halo: int) -> Core:
+    """The core grown by `halo` on every side, clipped to the scene."""
+    y0, y1, x0, x1 = core
+    return max(0, y0 - halo), min(H, y1 + halo), max(0, x0 - halo), min(W, x1 + halo)
+
+
+def _as_source(source):
+    return source if hasattr(source, "read") and hasattr(source, "shape") else ArraySource(source)
+
+
+def _read(source, box: Core, dtype: torch.dtype, ndim: int, device) -> torch.Tensor:
+    y0, y1, x0, x1 = box
+    got = source.read(y0, y1, x0, x1)
+    t = got if isinstance(got, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(got))
+    if t.dtype != dtype or t.dim() != ndim or tuple(t.shape[-2:]) != (y1 - y0, x1 - x0):
+        raise ValueError(f"source.read({y0}, {y1}, {x0}, {x1}) must return {dtype} with trailing shape [{y1 - y0},{x1 - x0}] and "
+                         f"{ndim} dimensions, got {t.dtype} {list(t.shape)}")
+    return t.to(device)
+
+
+class _Clock:
+    """Seconds per stage into a dict (tools/mb_scene.py); synchronises at every stage boundary, so only when asked for."""
+
+    def __init__(self, into: Optional[dict], device):
+        self.into, self.device = into, device
+        self.t = self._now()
+
+    def _now(self):
+        if self.into is None:
+            return 0.0
+        torch.cuda.synchronize(self.device)
+        return time.perf_counter()
+
+    def lap(self, stage: str):
+        if self.into is not None:
+            now = self._now()
+            self.into[stage] = self.into.get(stage, 0.0) + now - self.t
+            self.t = now
+
+
+def _check_scene(source, tile, max_window: int, labels_out):
+    shape = tuple(source.shape)
+    if len(shape) != 3 or min(shape) < 1:
+        raise ValueError(f"source.shape must be (bands, H, W) with bands, H, W >= 1, got {shape}")
+    bands, H, W = (int(v) for v in shape)
+    if not 1 <= int(max_window) <= rag.MAX_WINDOW:
+        raise ValueError(f"max_window must be in 1..{rag.MAX_WINDOW}, got {max_window}")
+    tiles = tile_grid(H, W, tile)
+    halo = halo_of(max_window)
+    # a window's height depends on its tile row only, its width on its tile column only
+    side_y = max(min(H, y1 + halo) - max(0, y0 - halo) for y0, y1 in {c[:2] for c in tiles})
+    side_x = max(min(W, x1 + halo) - max(0, x0 - halo) for x0, x1 in {c[2:] for c in tiles})
+    if side_y * side_x >= 1 << 31:
+        raise ValueError(f"a tile's window (core + halo of {halo}) must have fewer than 2^31 pixels, got {side_y} x {side_x}")
+    if labels_out is None:
+        labels_out = np.empty((H, W), dtype=np.int32)
+    elif not isinstance(labels_out, np.ndarray) or labels_out.dtype != np.int32 or labels_out.shape != (H, W) or not labels_out.flags.writeable:
+        raise ValueError(f"labels_out must be a writable int32 [{H},{W}] numpy array or memmap")
+    return bands, H, W, tiles, halo, labels_out
+
+
+def _scene_graph(source, tile=4096, segmenter: Optional[Callable] = None, k: int = 3, max_window: int = rag.MAX_WINDOW,
+                 labels_out=None, device="cuda:0", stage_times: Optional[dict] = None) -> dict:
+    """The first pass of `segment_scene`, everything but the encoder and the merge: per tile segment, statistics, edges, points;
+    then the seam stitch, the edge sort and the designed features.  Returns the fields of a SceneResult that do not need a net."""
+    source = _as_source(source)
+    bands, H, W, tiles, halo, labels_out = _check_scene(source, tile, max_window, labels_out)
+    segmenter = rag.slic if segmenter is None else segmenter
+    dev, i32 = torch.device(device), torch.int32
+    nx = sum(1 for t in tiles if t[0] == 0)
+    ny = len(tiles) // nx
+    clock = _Clock(stage_times, dev)
+    offsets, point_offsets = [0], [0]
+    stats_parts: Dict[str, list] = {key: [] for key in rag._STAT_KEYS}
+    edge_parts, weight_parts, strips = [], [], []
+    pt_parts: Dict[str, list] = {f: [] for f in ("xy", "label", "inner", "obj", "ptr", "bbox", "round")}
+    nb = min(bands, 3)
+    for i, core in enumerate(tiles):
+        y0, y1, x0, x1 = core
+        # (the first pass needs the core only; the halo is what the encoder's crops reach into, in the second pass)
+        core_tile = _read(source, core, torch.uint8, 3, dev)
+        clock.lap("read + copy")
+        labels, n = segmenter(core_tile)
+        n = int(n)
+        if labels.dtype != i32 or tuple(labels.shape) != (y1 - y0, x1 - x0) or n < 1:
+            raise ValueError(f"segmenter must return (labels int32 [{y1 - y0},{x1 - x0}], n >= 1) for tile {i}, got "
+                             f"{labels.dtype} {list(labels.shape)}, n = {n}")
+        off = offsets[-1]
+        if off + n > rag.MAX_REGIONS:
+            raise ValueError(f"the scene has more than 2^24 superpixels ({off + n} after tile {i} of {len(tiles)}): one merge takes "
+                             f"at most {rag.MAX_REGIONS} regions; use larger superpixels")
+        inside = (labels >= 0) & (labels < n)
+        local = torch.where(inside, labels, torch.full_like(labels, -1)).contiguous()      # ids outside [0, n): "no superpixel"
+        clock.lap("segment")
+        st = rag.label_stats(local, core_tile, n)
+        e, w = rag.rag_edges(local, n)
+        pts = rag.sample_points(local, n, k=k, max_window=max_window)
+        # tile ids / positions -> scene ids / positions
+        shift = torch.tensor([x0, y0, x0, y0], dtype=i32, device=dev)
+        for key in rag._STAT_KEYS:
+            stats_parts[key].append(st[key] if key != "bbox" else torch.where(st["bbox"][:, 2:3] >= 0, st["bbox"] + shift, st["bbox"]))
+        edge_parts.append(e + off)
+        weight_parts.append(w)
+        pt_parts["xy"].append(pts.xy + shift[:2])
+        pt_parts["label"].append(pts.label + off)
+        pt_parts["inner"].append(pts.inner)
+        pt_parts["obj"].append(pts.obj)
+        pt_parts["round"].append(pts.round)
+        pt_parts["ptr"].append(pts.ptr[:-1] + point_offsets[-1])
+        pt_parts["bbox"].append(torch.where(pts.bbox[:, 2:3] >= 0, pts.bbox + shift, pts.bbox))
+        glob = torch.where(inside, local + off, local)
+        strips.append((glob[0].clone(), glob[-1].clone(), glob[:, 0].clone(), glob[:, -1].clone()))      # top, bottom, left, right
+        offsets.append(off + n)
+        point_offsets.append(point_offsets[-1] + pts.xy.shape[0])
+        clock.lap("graph")
+        labels_out[y0:y1, x0:x1] = glob.cpu().numpy()
+        clock.lap("write")
+    S, P = offsets[-1], point_offsets[-1]
+    stats = {key: torch.cat(stats_parts[key]).contiguous() for key in rag._STAT_KEYS}
+    stats["bands"] = nb
+    # all seams of the scene, concatenated: the pixels left / right of every vertical seam, above / below every horizontal one
+    sa, sb = [], []
+    for r in range(ny):
+        for c in range(nx):
+            top, bottom, left, right = strips[r * nx + c]
+            if c + 1 < nx:
+                sa.append(right); sb.append(strips[r * nx + c + 1][2])
+            if r + 1 < ny:
+                sa.append(bottom); sb.append(strips[(r + 1) * nx + c][0])
+    empty = torch.empty(0, dtype=i32, device=dev)
+    a, b = (torch.cat(sa), torch.cat(sb)) if sa else (empty, empty)
+    # (a seam position adds at most one distinct pair: the table is sized for the seams, not for the scene)
+    seam_edges, seam_weights = rag.seam_stitch(a, b, S, stats["peri"], max_edges=max(1024, min(8 * S, int(a.numel()))))
+    clock.lap("stitch")
+    edges, weights = torch.cat(edge_parts + [seam_edges]), torch.cat(weight_parts + [seam_weights])
+    order = torch.argsort(edges[:, 0].long() * S + edges[:, 1].long())       # the two sets are disjoint: one sort, nothing to fold
+    edges, weights = edges[order].contiguous(), weights[order].contiguous()
+    designed = rag.designed_features(stats)                      # only now: `peri` and `border` need the seam fix
+    ptr = torch.cat(pt_parts["ptr"] + [torch.tensor([P], dtype=i32, device=dev)])
+    points = rag.PointSamples(xy=torch.cat(pt_parts["xy"]), label=torch.cat(pt_parts["label"]), inner=torch.cat(pt_parts["inner"]),
+                              obj=torch.cat(pt_parts["obj"]), ptr=ptr, idx=torch.arange(P, dtype=i32, device=dev),
+                              bbox=torch.cat(pt_parts["bbox"]), round=torch.cat(pt_parts["round"]))
+    clock.lap("graph")
+    return dict(n_labels=S, tiles=tiles, offsets=offsets, point_offsets=point_offsets, stats=stats, designed=designed, edges=edges,
+                weights=weights, points=points, labels=labels_out, halo=halo, n_seam=int(a.numel()), n_seam_edges=int(seam_edges.shape[0]),
+                source=source, device=dev)
+
+
+@dataclass
+class SceneResult:
+    """What `segment_scene` leaves.  result: the MergeResult of the one merge over the scene; n_labels: superpixels of the scene;
+    tiles: the cores (y0, y1, x0, x1), row-major; offsets [T+1]: tile i owns the scene-wide ids offsets[i] .. offsets[i+1]-1;
+    stats / designed / edges / weights: `label_stats`, `designed_features` and `rag_edges` of the scene; points: a PointSamples in
+    scene coordinates; features [P,100]: the encoder's rows; labels: the scene-wide superpixel raster (`labels_out`, on the host)."""
+    result: "rag.MergeResult"
+    n_labels: int
+    tiles: List[Core]
+    offsets: List[int]
+    stats: Dict[str, torch.Tensor]
+    designed: torch.Tensor
+    edges: torch.Tensor
+    weights: torch.Tensor
+    points: "rag.PointSamples"
+    features: torch.Tensor
+    labels: np.ndarray
+
+    def _tile_labels(self, i: int) -> torch.Tensor:
+        y0, y1, x0, x1 = self.tiles[i]
+        return torch.from_numpy(np.ascontiguousarray(self.labels[y0:y1, x0:x1])).to(self.edges.device)
+
+    def merged_tile(self, i: int) -> torch.Tensor:
+        """int32 [th,tw] on the device: tile i of the merged raster, `relabel_raster` of its superpixels with `result.region_of`."""
+        return rag.relabel_raster(self._tile_labels(i), self.result.region_of)
+
+    def write_merged(self, out=None) -> np.ndarray:
+        """Streams every tile of the merged raster into `out`, a writable int32 [H,W] numpy array or memmap (allocated if None)."""
+        H, W = self.labels.shape
+        if out is None:
+            out = np.empty((H, W), dtype=np.int32)
+        elif not isinstance(out, np.ndarray) or out.dtype != np.int32 or out.shape != (H, W) or not out.flags.writeable:
+            raise ValueError(f"out must be a writable int32 [{H},{W}] numpy array or memmap")
+        for i, (y0, y1, x0, x1) in enumerate(self.tiles):
+            out[y0:y1, x0:x1] = self.merged_tile(i).cpu().numpy()
+        return out
+
+    def overlap(self, truth_source, n_truth: int) -> "rag.Overlap":
+        """The `Overlap` of the scene's superpixels with a ground-truth raster (int32 [H,W]: an array, a memmap, a CPU tensor, or
+        anything with `.read(y0, y1, x0, x1)` returning int32 [y1-y0, x1-x0]), for `result.scores(...)`: per tile one
+        `rag.label_overlap` with tile-local ids (so that every table is sized for one tile), keys shifted to scene-wide ids and
+        concatenated, then the facts of the whole table.  Equals `rag.label_overlap` on the assembled rasters field by field."""
+        truth_source = _as_source(truth_source)
+        G, dev = int(n_truth), self.edges.device
+        keys, counts = [], []
+        for i, core in enumerate(self.tiles):
+            off, n = self.offsets[i], self.offsets[i + 1] - self.offsets[i]
+            truth = _read(truth_source, core, torch.int32, 2, dev)
+            glob = self._tile_labels(i)
+            local = torch.where(glob >= 0, glob - off, glob)
+            ov = rag.label_overlap(local, truth, n, G)
+            keys.append((ov.cells[:, 0].long() + off) * (G + 1) + ov.cells[:, 1].long())
+            counts.append(ov.count)
+        return rag._overlap_facts(torch.cat(keys), torch.cat(counts), self.n_labels, G)        # sorted: offsets ascend
+
+
+def segment_scene(fio, source, tile=4096, segmenter: Optional[Callable] = None, k: int = 3, margin: float = 1.0,
+                  max_window: int = rag.MAX_WINDOW, batch_size: int = 2000, labels_out=None, stage_times: Optional[dict] = None,
+                  **merge_kwargs) -> SceneResult:
+    """From a scene of any size to its merged partition (the module docstring states the definition).
+
+    fio: a FeatureIO; source: `.shape == (bands, H, W)` and `.read(y0, y1, x0, x1) -> uint8 [bands, y1-y0, x1-x0]` (a numpy
+    array or a CPU tensor), or an array / memmap / CPU tensor, which is wrapped in an ArraySource; tile: core side, an int or
+    (th, tw); segmenter(core_tile uint8 [bands,th,tw] on the device) -> (labels int32 [th,tw], n), default `rag.slic` with its
+    defaults (ids outside [0, n) are written as -1, "no superpixel"); k, max_window: as `rag.sample_points` takes them; margin,
+    merge_kwargs: as `rag.merge_regions` takes them; labels_out: a writable int32 [H,W] numpy array or memmap for the scene-wide
+    superpixel raster, allocated if None; stage_times: a dict that receives seconds per stage (synchronises at stage boundaries).
+    Limits: at most 2^24 superpixels in the scene, every window (core + halo) below 2^31 pixels."""
+    g = _scene_graph(source, tile, segmenter, k, max_window, labels_out, device=fio.device, stage_times=stage_times)
+    dev, pts, H, W = g["device"], g["points"], g["labels"].shape[0], g["labels"].shape[1]
+    clock = _Clock(stage_times, dev)
+    P = pts.xy.shape[0]
+    if P < 1:
+        raise ValueError("the scene has no sample point (no pixel carries a superpixel id)")
+    features = torch.empty((P, 100), dtype=torch.float32, device=dev)
+    for i, core in enumerate(g["tiles"]):
+        lo, hi = g["point_offsets"][i], g["point_offsets"][i + 1]
+        if hi == lo:
+            continue
+        wy0, wy1, wx0, wx1 = box = window_of(core, H, W, g["halo"])
+        window = _read(g["source"], box, torch.uint8, 3, dev)
+        clock.lap("read + copy")
+        origin = torch.tensor([wx0, wy0], dtype=torch.int32, device=dev)
+        features[lo:hi] = fio.extract_features_from_tile(window, pts.xy[lo:hi] - origin, pts.inner[lo:hi], pts.obj[lo:hi],
+                                                         g["designed"][pts.label[lo:hi].long()], batch_size=batch_size)
+        clock.lap("encode")
+    fio.features = features
+    result = rag.merge_regions(features, pts.ptr, pts.idx, g["edges"], margin=margin, weights=g["weights"], stats=g["stats"], **merge_kwargs)
+    clock.lap("merge")
+    return SceneResult(result=result, n_labels=g["n_labels"], tiles=g["tiles"], offsets=g["offsets"], stats=g["stats"], designed=g["designed"],
+                       edges=g["edges"], weights=g["weights"], points=pts, features=features, labels=g["labels"])

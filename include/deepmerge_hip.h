@@ -469,6 +469,29 @@ int dm_rag_edges(const int32_t *labels, int32_t H, int32_t W, int32_t S, int64_t
                  int32_t capacity_log2, int64_t *edge_keys, int32_t *edge_counts, int32_t max_edges, int32_t *n_edges,
                  int32_t *overflow, void *stream);
 
+/* ---- seam stitch: the graph and the perimeters between the tiles of a scene (additive in ABI 7; csrc/dm_scene.hip, DESIGN.md
+ * 3.5.9, rag.seam_stitch / deepmerge_amd/scene.py) ------------------------------------------------------------------------------
+ * A scene larger than one raster is segmented tile by tile; superpixels never cross a seam and carry scene-wide ids 0..S-1.
+ * dm_label_stats and dm_rag_edges run per tile, so they miss what lies between tiles.  This call adds it, so that the
+ * concatenated per-tile results equal what the two calls give on the assembled scene raster, bit for bit.
+ * The rule.  a, b int32 [n]: a[i] and b[i] are the scene-wide ids of the two pixels that face each other across seam position
+ * i; all seams of the scene are concatenated, in any order.  1 <= n, 1 <= S <= 2^24.
+ *   edges: every position with both ids in [0,S) and a[i] != b[i] adds 1 to key min*S + max: dm_rag_edges' key and count for a
+ *     4-neighbour pair, through the same table.  The pairs are disjoint from every tile's own (a tile's pairs lie inside it).
+ *   perimeter: peri int64 [S,2] holds dm_label_stats' peri of every tile, concatenated.  The tile counted the pixel edge of
+ *     a[i] that faces b[i] in column 1 (raster border); dm_label_stats on the scene would see the neighbour b[i].  So, for the
+ *     side l = a[i] facing f = b[i], and likewise for l = b[i] facing f = a[i], when l is in [0,S):
+ *       f == -2 (dm_label_stats' marker for "outside the raster"): nothing moves;
+ *       f == l: column 1 loses the edge (inside a raster, equal neighbours share no perimeter);
+ *       any other f, ids outside [0,S) such as -1 included: the edge moves from column 1 to column 0 ("another label").
+ *     A side whose own id is outside [0,S) has no row in peri and moves nothing.
+ * Integer adds only: nothing depends on arrival order.  table_* / edge_* / n_edges / overflow: as dm_rag_edges takes them
+ * (8 <= capacity_log2 <= 30, results in ARBITRARY order, n_edges may exceed max_edges: then the output is truncated); they are
+ * (re)initialised by the call, peri is updated in place.  Validates before any launch, never synchronises, never allocates. */
+int dm_seam_stitch(const int32_t *a, const int32_t *b, int64_t n, int64_t S, int64_t *peri, int64_t *table_keys,
+                   int32_t *table_counts, int32_t capacity_log2, int64_t *edge_keys, int32_t *edge_counts, int32_t max_edges,
+                   int32_t *n_edges, int32_t *overflow, void *stream);
+
 /* One round of the merge step that follows the sweep (optional; the reference leaves merging to external
  * GIS tooling): union-find over the edges with merge[e] != 0.  parent int32 [S] (init != 0: reset to the identity first);
  * after the call parent[s] is a root candidate and changed[0] tells whether any root was hooked -- repeat with init = 0
