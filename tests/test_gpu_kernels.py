@@ -319,15 +319,7 @@ def test_gemm_rejects_bad_arguments():
 
 
 # ---------------------------------------------------------------------------------------------
-def _attn_ref(qkv, bias, scale):
-    """fp64 reference of the fused core on CPU.  qkv [B,N,3,H,D] double; bias [H,N,N] or None."""
-    q, k, v = qkv[:, :, 0].permute(0, 2, 1, 3), qkv[:, :, 1].permute(0, 2, 1, 3), qkv[:, :, 2].permute(0, 2, 1, 3)
-    s = (q * scale) @ k.transpose(-1, -2)
-    if bias is not None:
-        s = s + bias[None]
-    p = torch.softmax(s, -1)
-    o = (p @ v).permute(0, 2, 1, 3).reshape(qkv.shape[0], qkv.shape[1], -1)
-    return o, torch.logsumexp(s, -1)
+from attn_frame import attn_ref as _attn_ref      # the fp64 reference of the fused core (shared with test_gpu_attention_edges.py)
 
 
 @pytest.mark.parametrize("N,with_bias", [(256, True), (192, True), (128, False), (197, False), (198, False), (193, True), (160, True)])
