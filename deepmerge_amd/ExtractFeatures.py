@@ -119,6 +119,14 @@ class FeatureIO:
         return scene.segment_scene(self, source, **kw)
 
     @torch.no_grad()
+    def trace_scene(self, source, n_labels: int, **kw):
+        """A scene's label raster (int32 [H, W] on the host, ids 0..n_labels-1, or anything with `.shape` and `.read`) traced
+        into rings and arcs across its tiles: `scene.trace_labels(source, n_labels, device=self.device, **kw)`.  Returns
+        (rag.Polygons, rag.Arcs) in scene coordinates."""
+        from . import scene
+        return scene.trace_labels(source, n_labels, device=self.device, **kw)
+
+    @torch.no_grad()
     def _extract_local(self, tile, points_xy, inner, obj, region_features, batch_size):
         from .patches import point_batch_cols
         P = points_xy.shape[0]
@@ -168,21 +176,7 @@ class FeatureIO:
         if pts.ptr.numel() != n_labels + 1:
             raise ValueError(f"pts.ptr must have n_labels + 1 = {n_labels + 1} entries")
         polys, arcs = rag._trace(labels, n_labels) if tolerance is None else rag.simplify(labels, n_labels, tolerance)
-        os.makedirs(folder, exist_ok=True)
-        ptr, idx = pts.ptr.cpu().tolist(), pts.idx.cpu().tolist()
-        point_id = [" ".join(str(i) for i in idx[ptr[l]:ptr[l + 1]]) for l in range(n_labels)]
-        feats = designed.float().cpu().numpy()
-        fields = [(name, feats[:, i]) for i, name in enumerate(rag.FEATURE_NAMES)] + [("PointID", point_id)]
-        paths = [shpstore.write_polygons(os.path.join(folder, "polygons.shp"), polys, fields, geotransform)]
-        line_fields = [("LEFT_FID", arcs.left.cpu().numpy()), ("RIGHT_FID", arcs.right.cpu().numpy())]
-        if simi is not None:
-            if simi.numel() != edges.shape[0]:
-                raise ValueError(f"simi has {simi.numel()} values for {edges.shape[0]} edges")
-            row = rag._attach_edges(arcs, n_labels, edges).edge.long()
-            values = torch.where(row >= 0, simi.float()[row.clamp(min=0)], torch.zeros((), dtype=torch.float32, device=row.device)) \
-                if simi.numel() else torch.zeros(row.numel(), dtype=torch.float32)
-            line_fields.append(("simi", values.cpu().numpy()))
-        paths.append(shpstore.write_lines(os.path.join(folder, "lines.shp"), arcs, line_fields, geotransform))
+        paths = write_polygon_and_line_layers(folder, polys, arcs, n_labels, pts.ptr, pts.idx, designed, edges, simi, geotransform)
         paths.append(shpstore.write_points(os.path.join(folder, "PointsGCS.shp"), pts.xy.cpu().numpy(),
                                            [("inner", pts.inner.cpu().numpy()), ("object", pts.obj.cpu().numpy())], geotransform))
         return tuple(paths)
@@ -209,6 +203,33 @@ class FeatureIO:
         if self.features is None or idx >= self.features.shape[0]:
             raise IndexError("index error!")
         return self.features[idx]
+
+
+def write_polygon_and_line_layers(folder: str, polys, arcs, n_labels: int, ptr: torch.Tensor, idx: torch.Tensor, designed: torch.Tensor,
+                                  edges: Optional[torch.Tensor] = None, simi: Optional[torch.Tensor] = None, geotransform=None) -> list:
+    """`polygons.shp` and `lines.shp` of traced rings and arcs, as `FeatureIO.save_shapefiles` describes them: the writer both
+    `FeatureIO.save_shapefiles` (one raster) and `scene.SceneResult.save_shapefiles` (a scene, traced across its tiles) go through.
+    ptr / idx: the point lists behind `PointID`.  Returns the two paths."""
+    import os
+    from . import rag, shpstore
+    if simi is not None and edges is None:
+        raise ValueError("simi needs edges: an arc finds its value through its row in `edges`")
+    os.makedirs(folder, exist_ok=True)
+    ptr, idx = ptr.cpu().tolist(), idx.cpu().tolist()
+    point_id = [" ".join(str(i) for i in idx[ptr[l]:ptr[l + 1]]) for l in range(n_labels)]
+    feats = designed.float().cpu().numpy()
+    fields = [(name, feats[:, i]) for i, name in enumerate(rag.FEATURE_NAMES)] + [("PointID", point_id)]
+    paths = [shpstore.write_polygons(os.path.join(folder, "polygons.shp"), polys, fields, geotransform)]
+    line_fields = [("LEFT_FID", arcs.left.cpu().numpy()), ("RIGHT_FID", arcs.right.cpu().numpy())]
+    if simi is not None:
+        if simi.numel() != edges.shape[0]:
+            raise ValueError(f"simi has {simi.numel()} values for {edges.shape[0]} edges")
+        row = rag._attach_edges(arcs, n_labels, edges).edge.long()
+        values = torch.where(row >= 0, simi.float()[row.clamp(min=0)], torch.zeros((), dtype=torch.float32, device=row.device)) \
+            if simi.numel() else torch.zeros(row.numel(), dtype=torch.float32)
+        line_fields.append(("simi", values.cpu().numpy()))
+    paths.append(shpstore.write_lines(os.path.join(folder, "lines.shp"), arcs, line_fields, geotransform))
+    return paths
 
 
 def rag_similarity_sweep(features: torch.Tensor, ptr: torch.Tensor, idx: torch.Tensor, edges: torch.Tensor,

@@ -88,6 +88,15 @@ class DmVectorTrace(C.Structure):
                 ("W", C.c_int32), ("D", C.c_int32), ("R", C.c_int32), ("n_arcs", C.c_int32)]
 
 
+class DmSceneVectorTrace(C.Structure):
+    _fields_ = [("dart", C.c_void_p), ("next", C.c_void_p), ("lab", C.c_void_p), ("other", C.c_void_p), ("flags", C.c_void_p),
+                ("key", C.c_void_p), ("sum", C.c_void_p), ("ring_of_slot", C.c_void_p), ("ring_ptr", C.c_void_p),
+                ("arc_base", C.c_void_p), ("xy", C.c_void_p), ("area2", C.c_void_p),
+                ("arc_first", C.c_void_p), ("arc_left", C.c_void_p), ("arc_right", C.c_void_p), ("arc_vstart", C.c_void_p),
+                ("arc_count", C.c_void_p), ("arc_pos", C.c_void_p), ("arc_ptr", C.c_void_p), ("arc_xy", C.c_void_p),
+                ("W", C.c_int64), ("D", C.c_int32), ("R", C.c_int32), ("n_arcs", C.c_int32)]
+
+
 class DmProfRow(C.Structure):
     _fields_ = [("name", C.c_char * 64), ("launches", C.c_int64), ("total_ms", C.c_double),
                 ("total_flops", C.c_double), ("total_bytes", C.c_double)]
@@ -185,6 +194,10 @@ SIGNATURES = {
     "dm_vector_rank_round": (_I, [_P, _P, _P, _P, _I, _P, _P]),
     "dm_vector_ring_emit": (_I, [C.POINTER(DmVectorTrace), _P]),
     "dm_vector_arc_emit": (_I, [C.POINTER(DmVectorTrace), _P]),
+    "dm_scene_vector_count": (_I, [_P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P]),
+    "dm_scene_vector_link": (_I, [_P, _P, _P, _I, _I, _I, _L, _L, _L, _L, _P, _P, _P, _P, _P, _P]),
+    "dm_scene_vector_ring_emit": (_I, [C.POINTER(DmSceneVectorTrace), _P]),
+    "dm_scene_vector_arc_emit": (_I, [C.POINTER(DmSceneVectorTrace), _P]),
     "dm_rasterize_count": (_I, [_P, _P, _P, _I, _I, _I, _I, _P, _P]),
     "dm_rasterize_emit": (_I, [_P, _P, _P, _P, _P, _I, _I, _L, _I, _I, _L, _P, _P]),
     "dm_rasterize_fill": (_I, [_P, _L, _I, _I, _I, _P, _P, _P]),

@@ -15,75 +15,10 @@
 //   arc_emit   vertices of the kept arcs at arc_ptr[arc] + rank inside the arc; the last dart writes the arc's end corner
 // The sorts and the scans over rings and arcs between the stages are the caller's (rag._trace: torch.sort, as rag_edges).
 // Every slot is written by exactly one thread; all atomics are integer adds: no result depends on the order of arrival.
-#include "dm_raster.h"
+// count, the scan, the successor rule and the two emit kernels live in dm_vector.h, shared with dm_scene_vector.hip.
+#include "dm_vector.h"
 
 namespace {
-
-constexpr int BRK = 2, VTX = 1;                                // flags[slot]
-
-__device__ __forceinline__ int popc4(int m) { return __popc((unsigned)m); }
-
-// ---- count: side masks and darts per tile ----------------------------------------------------------------------------------
-// mask bit s: the neighbour across side s (0 top, 1 right, 2 bottom, 3 left) has another label or lies outside.
-template <bool VEC>
-__global__ __launch_bounds__(256) void vec_count_kernel(const int *__restrict__ labels, int H, int W, unsigned char *__restrict__ mask,
-                                                        int *__restrict__ tile_count) {
-  __shared__ int total;
-  if (threadIdx.x == 0) total = 0;
-  __syncthreads();
-  const Strip g = strip_of(H, W);
-  const int n = g.n;
-  int lab[STRIP + 2], up[STRIP], dn[STRIP];
-  load_strip<VEC>(labels, g.base, n, -2, lab + 1);              // -2 = outside the raster
-  load_strip<VEC>(labels, g.base - W, n, -2, up, g.y > 0);
-  load_strip<VEC>(labels, g.base + W, n, -2, dn, g.y + 1 < H);
-  lab[0] = (g.live && g.x0 > 0) ? labels[g.base - 1] : -2;
-  lab[STRIP + 1] = (g.live && g.x0 + STRIP < W) ? labels[g.base + STRIP] : -2;
-  unsigned packed[STRIP / 4] = {0, 0, 0, 0};
-  int c = 0;
-#pragma unroll
-  for (int i = 0; i < STRIP; ++i) {
-    const int l = lab[1 + i];
-    const int m = (i < n) ? ((up[i] != l) | ((lab[2 + i] != l) << 1) | ((dn[i] != l) << 2) | ((lab[i] != l) << 3)) : 0;
-    c += popc4(m);
-    packed[i >> 2] |= (unsigned)m << (8 * (i & 3));
-  }
-  if (VEC && n == STRIP) {
-    *reinterpret_cast<u32x4 *>(mask + g.base) = (u32x4){packed[0], packed[1], packed[2], packed[3]};
-  } else {
-#pragma unroll
-    for (int i = 0; i < STRIP; ++i)
-      if (i < n) mask[g.base + i] = (unsigned char)(packed[i >> 2] >> (8 * (i & 3)));
-  }
-  if (c) atomicAdd(&total, c);
-  __syncthreads();
-  if (threadIdx.x == 0) tile_count[blockIdx.x] = total;
-}
-
-// Exclusive scan of the tile counts in place, by one looping workgroup; counts[n_tiles] = n_out[0] = the number of darts.
-__global__ __launch_bounds__(SCAN_THREADS) void vec_scan_kernel(int *__restrict__ counts, int n_tiles, int *__restrict__ n_out) {
-  __shared__ int lds[SCAN_THREADS / 64];
-  int carry = 0;
-  for (int base = 0; base < n_tiles; base += SCAN_TILE) {
-    int item[SCAN_ITEMS], sum = 0;
-#pragma unroll
-    for (int j = 0; j < SCAN_ITEMS; ++j) {
-      const int i = base + threadIdx.x * SCAN_ITEMS + j;
-      item[j] = i < n_tiles ? counts[i] : 0;
-      sum += item[j];
-    }
-    int total;
-    int run = carry + block_exclusive(sum, lds, total);
-#pragma unroll
-    for (int j = 0; j < SCAN_ITEMS; ++j) {
-      const int i = base + threadIdx.x * SCAN_ITEMS + j;
-      if (i < n_tiles) counts[i] = run;
-      run += item[j];
-    }
-    carry += total;
-  }
-  if (threadIdx.x == 0) { counts[n_tiles] = carry; *n_out = carry; }
-}
 
 // ---- emit: first slot per pixel, dart id per slot ----------------------------------------------------------------------------
 // Slots run in tile order, inside a tile in strip order, inside a strip by pixel and side: slot(dart) = first_slot[pixel] +
@@ -133,31 +68,14 @@ __global__ __launch_bounds__(256) void vec_emit_kernel(const unsigned char *__re
 }
 
 // ---- link: successor, labels, flags -----------------------------------------------------------------------------------------------
-__device__ __forceinline__ int dir_x(int s) { return s == 0 ? 1 : (s == 2 ? -1 : 0); }
-__device__ __forceinline__ int dir_y(int s) { return s == 1 ? 1 : (s == 3 ? -1 : 0); }
-
-// Label across side s of pixel (x, y): to the dart's left; -1 outside the raster.
-__device__ __forceinline__ int label_across(const int *__restrict__ labels, int H, int W, int x, int y, int s) {
-  const int ax = x + dir_y(s), ay = y - dir_x(s);
-  return (ax >= 0 && ax < W && ay >= 0 && ay < H) ? labels[(long long)ay * W + ax] : -1;
-}
-
 __global__ void vec_link_kernel(const int *__restrict__ labels, const unsigned char *__restrict__ mask, const int *__restrict__ first_slot,
                                 const int *__restrict__ dart, int H, int W, int D, int *__restrict__ next, int *__restrict__ lab,
                                 int *__restrict__ other, unsigned char *__restrict__ flags, long long *__restrict__ key) {
   for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < D; i += gridDim.x * blockDim.x) {
     const int id = dart[i], pix = id >> 2, s = id & 3;
     const int y = pix / W, x = pix - y * W;
-    const int m = mask[pix];
-    // the successor from the masks alone: ahead-right differs <=> this pixel has a dart on side s + 1; ahead-left differs (given
-    // that ahead-right is the same label) <=> the ahead-right pixel has a dart on side s
-    int qx = x, qy = y, t = (s + 1) & 3;                          // turn right
-    if (!(m >> t & 1)) {
-      qx = x + dir_x(s); qy = y + dir_y(s); t = s;                // straight: the ahead-right pixel is inside (it has this label)
-      if (!(mask[qy * W + qx] >> s & 1)) {
-        qx += dir_y(s); qy -= dir_x(s); t = (s + 3) & 3;          // turn left: the ahead-left pixel has this label as well
-      }
-    }
+    int qx = x, qy = y;
+    const int t = successor_of(mask, W, qx, qy, s);
     const int q = qy * W + qx;
     const int succ = first_slot[q] + popc4(mask[q] & ((1 << t) - 1));
     const int o = label_across(labels, H, W, x, y, s);
@@ -214,85 +132,6 @@ __global__ void vec_rank_kernel(const long long *__restrict__ sum_in, const int 
   }
 }
 
-// ---- rings and arcs -------------------------------------------------------------------------------------------------------------
-struct DartPlace {                                               // where a dart sits in its ring and its arc
-  int head, ring, vertices, breaks;                              // head slot, ring index, the ring's vertex and break darts
-  int vrank;                                                     // vertex darts in [head, dart)
-  int binc;                                                      // break darts in [head, dart]
-  int arc;                                                       // index of its arc before the arcs are sorted
-  bool first;                                                    // the arc's first dart
-};
-
-__device__ __forceinline__ DartPlace place_of(const DmVectorTrace &t, int i, int f) {
-  DartPlace p;
-  p.head = (int)(t.key[i] & 0xffffffffLL);
-  p.ring = t.ring_of_slot[p.head];
-  const long long all = t.sum[p.head], mine = t.sum[i];
-  p.vertices = (int)(all >> 32);
-  p.breaks = (int)(all & 0xffffffffLL);
-  p.vrank = p.vertices - (int)(mine >> 32);
-  p.binc = p.breaks - (int)(mine & 0xffffffffLL) + ((f & BRK) >> 1);
-  const int ordinal = p.breaks == 0 ? 0 : (p.binc == 0 ? p.breaks : p.binc) - 1;     // the darts in front of the first break dart
-  p.arc = t.arc_base[p.ring] + ordinal;                                               // belong to the ring's last arc
-  p.first = p.breaks == 0 ? i == p.head : (f & BRK) != 0;
-  return p;
-}
-
-__device__ __forceinline__ void store_corner(int *__restrict__ xy, long long at, int W, int id, bool end) {
-  const int pix = id >> 2, s = id & 3;
-  const int y = pix / W, x = pix - y * W;
-  int cx = x + (s == 1 || s == 2), cy = y + (s >= 2);             // the dart's start corner
-  if (end) { cx += dir_x(s); cy += dir_y(s); }
-  xy[2 * at] = cx;
-  xy[2 * at + 1] = cy;
-}
-
-__global__ void vec_ring_init_kernel(long long *__restrict__ area2, int R, int *__restrict__ arc_count, int n_arcs) {
-  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < max(R, n_arcs); i += gridDim.x * blockDim.x) {
-    if (i < R) area2[i] = 0;
-    if (i < n_arcs) arc_count[i] = 2;                            // the first dart's start corner and the last dart's end corner
-  }
-}
-
-__global__ void vec_ring_emit_kernel(DmVectorTrace t) {
-  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < t.D; i += gridDim.x * blockDim.x) {
-    const int f = t.flags[i], id = t.dart[i];
-    const DartPlace p = place_of(t, i, f);
-    if (f & VTX) store_corner(t.xy, t.ring_ptr[p.ring] + p.vrank, t.W, id, false);
-    // the shoelace term of a unit dart: -y east, +x south, +y west, -x north, at the dart's own line
-    const int pix = id >> 2, s = id & 3, y = pix / t.W, x = pix - y * t.W;
-    const long long term = s == 0 ? -(long long)y : s == 1 ? (long long)(x + 1) : s == 2 ? (long long)(y + 1) : -(long long)x;
-    if (term) atomic_add64((long long *)t.area2 + p.ring, term);
-    if (p.first) {
-      t.arc_first[p.arc] = id;
-      t.arc_right[p.arc] = t.lab[i];
-      t.arc_left[p.arc] = t.other[i];
-      t.arc_vstart[p.arc] = p.vrank + (f & VTX);                 // vertex darts in [head, first dart]
-    } else if (f & VTX) {
-      atomicAdd(t.arc_count + p.arc, 1);
-    }
-  }
-}
-
-__global__ void vec_arc_emit_kernel(DmVectorTrace t) {
-  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < t.D; i += gridDim.x * blockDim.x) {
-    const int f = t.flags[i], id = t.dart[i];
-    const DartPlace p = place_of(t, i, f);
-    const int pos = t.arc_pos[p.arc];
-    if (pos < 0) continue;                                       // the arc is kept from its other side
-    const long long base = t.arc_ptr[pos];
-    if (p.first) {
-      store_corner(t.arc_xy, base, t.W, id, false);
-    } else if (f & VTX) {
-      const int start = t.arc_vstart[p.arc];
-      const bool wrapped = p.breaks != 0 && p.binc == 0;         // in front of the ring's first break dart: the arc began behind
-      store_corner(t.arc_xy, base + 1 + (wrapped ? p.vertices - start + p.vrank : p.vrank - start), t.W, id, false);
-    }
-    const int j = t.next[i];
-    if (p.breaks == 0 ? j == p.head : (t.flags[j] & BRK) != 0) store_corner(t.arc_xy, t.arc_ptr[pos + 1] - 1, t.W, id, true);
-  }
-}
-
 }  // namespace
 
 extern "C" int dm_vector_count(const int32_t *labels, int32_t H, int32_t W, uint8_t *mask, int32_t *tile_off, int32_t *n_darts, void *stream) {
@@ -301,8 +140,9 @@ extern "C" int dm_vector_count(const int32_t *labels, int32_t H, int32_t W, uint
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   const dim3 grid = tile_grid(H, W);
   const bool vec = W % STRIP == 0 && dm_aligned16(labels) && dm_aligned16(mask);
-  if (vec) hipLaunchKernelGGL(vec_count_kernel<true>, grid, dim3(256), 0, s, labels, H, W, mask, tile_off);
-  else hipLaunchKernelGGL(vec_count_kernel<false>, grid, dim3(256), 0, s, labels, H, W, mask, tile_off);
+  unsigned char *none = nullptr;
+  if (vec) hipLaunchKernelGGL((vec_count_kernel<true, false>), grid, dim3(256), 0, s, labels, H, W, mask, tile_off, none, 0, 0, 0, 0);
+  else hipLaunchKernelGGL((vec_count_kernel<false, false>), grid, dim3(256), 0, s, labels, H, W, mask, tile_off, none, 0, 0, 0, 0);
   hipLaunchKernelGGL(vec_scan_kernel, dim3(1), dim3(SCAN_THREADS), 0, s, tile_off, (int)grid.x, n_darts);
   DM_LAUNCH_CHECK("dm_vector_count");
   return DM_OK;
@@ -367,29 +207,18 @@ extern "C" int dm_vector_rank_round(const int64_t *sum_in, const int32_t *nxt_in
   return DM_OK;
 }
 
-static int vector_trace_ok(const DmVectorTrace *t, const char *what, bool arcs) {
-  DM_REQUIRE(t && t->dart && t->next && t->lab && t->other && t->flags && t->key && t->sum && t->ring_of_slot && t->arc_base && t->arc_vstart,
-             DM_ERR_BAD_SHAPE, "%s: null pointer", what);
-  DM_REQUIRE(t->W > 0 && t->D >= 4 && t->R >= 1 && t->n_arcs >= t->R, DM_ERR_BAD_SHAPE, "%s: bad sizes (W=%d D=%d R=%d n_arcs=%d)", what, t->W,
-             t->D, t->R, t->n_arcs);
-  if (arcs) DM_REQUIRE(t->arc_pos && t->arc_ptr && t->arc_xy, DM_ERR_BAD_SHAPE, "%s: null pointer", what);
-  else DM_REQUIRE(t->ring_ptr && t->xy && t->area2 && t->arc_first && t->arc_left && t->arc_right && t->arc_count, DM_ERR_BAD_SHAPE,
-                  "%s: null pointer", what);
-  return DM_OK;
-}
-
 extern "C" int dm_vector_ring_emit(const DmVectorTrace *t, void *stream) {
   if (int rc = vector_trace_ok(t, "dm_vector_ring_emit", false)) return rc;
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   hipLaunchKernelGGL(vec_ring_init_kernel, dim3(grid_for(t->n_arcs)), dim3(256), 0, s, (long long *)t->area2, t->R, t->arc_count, t->n_arcs);
-  hipLaunchKernelGGL(vec_ring_emit_kernel, dim3(grid_for(t->D)), dim3(256), 0, s, *t);
+  hipLaunchKernelGGL((vec_ring_emit_kernel<DmVectorTrace, int, false>), dim3(grid_for(t->D)), dim3(256), 0, s, *t);
   DM_LAUNCH_CHECK("dm_vector_ring_emit");
   return DM_OK;
 }
 
 extern "C" int dm_vector_arc_emit(const DmVectorTrace *t, void *stream) {
   if (int rc = vector_trace_ok(t, "dm_vector_arc_emit", true)) return rc;
-  hipLaunchKernelGGL(vec_arc_emit_kernel, dim3(grid_for(t->D)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), *t);
+  hipLaunchKernelGGL((vec_arc_emit_kernel<DmVectorTrace, int>), dim3(grid_for(t->D)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), *t);
   DM_LAUNCH_CHECK("dm_vector_arc_emit");
   return DM_OK;
 }

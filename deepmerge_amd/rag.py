@@ -975,6 +975,82 @@ def _jump(call, bufs, D: int, changed: torch.Tensor, what: str, max_rounds: int 
     raise RuntimeError(f"{what} did not converge in {max_rounds} rounds")
 
 
+def _trace_table(dart: torch.Tensor, nxt0: torch.Tensor, lab: torch.Tensor, other: torch.Tensor, flags: torch.Tensor, key0: torch.Tensor,
+                 W: int, S: int, mark=lambda stage: None, wide: bool = False) -> Tuple[Polygons, Arcs, dict]:
+    """From a linked dart table (dart ids, successor slots, labels, flags, key = head candidate << 32 | slot) to both results: the
+    jumping rounds, the ring and arc tables, the two emits.  wide: the table of a scene (scene.trace_labels) -- dart int64 in
+    ascending order, key = slot << 32 | slot, W up to 2^31 - 2; the emits are the 64-bit ones and an arc's first dart is known by
+    its slot.  Returns (Polygons, Arcs, counts for the callers' stats)."""
+    lib, dev, i32, i64, D = _lib.lib(), dart.device, torch.int32, torch.int64, int(dart.numel())
+    new = lambda n, dt: torch.empty(n, dtype=dt, device=dev)
+    keys, jumps = (key0, new(D, i64)), (nxt0, new(D, i32), new(D, i32))
+    changed = new(1, i32)
+    # heads: round 0 reads (keys[0], next) and writes (keys[1], jumps[1]); `next` itself is never written again
+    check(lib.dm_vector_head_round(keys[0].data_ptr(), nxt0.data_ptr(), keys[1].data_ptr(), jumps[1].data_ptr(), D, changed.data_ptr(),
+                                   _stream()), "dm_vector_head_round")
+    key, head_rounds = keys[1], 1
+    if int(changed.item()):
+        (key, _), more = _jump(lib.dm_vector_head_round, [(keys[1], jumps[1]), (keys[0], jumps[2])], D, changed, "dm_vector_head_round")
+        head_rounds += more
+    del jumps
+    mark("head rounds")
+    # ranks
+    max_rings = D // 4 + 1
+    sums, nxts = (new(D, i64), new(D, i64)), (new(D, i32), new(D, i32))
+    ring_key, ring_slot, n_rings = new(max_rings, i64), new(max_rings, i32), new(1, i32)
+    check(lib.dm_vector_rank_init(key.data_ptr(), nxt0.data_ptr(), flags.data_ptr(), lab.data_ptr(), D, sums[0].data_ptr(), nxts[0].data_ptr(),
+                                  ring_key.data_ptr(), ring_slot.data_ptr(), n_rings.data_ptr(), max_rings, _stream()), "dm_vector_rank_init")
+    (total, _), rank_rounds = _jump(lib.dm_vector_rank_round, [(sums[0], nxts[0]), (sums[1], nxts[1])], D, changed, "dm_vector_rank_round")
+    R = int(n_rings)
+    mark("rank rounds")
+    # rings in (label, head) order; the tables over rings and arcs are small next to the darts
+    ring_key, order = torch.sort(ring_key[:R])
+    ring_slot = ring_slot[:R][order].long()
+    ring_of_slot = new(D, i32)
+    ring_of_slot[ring_slot] = torch.arange(R, dtype=i32, device=dev)
+    ring_total = total[ring_slot]
+    ring_ptr = torch.zeros(R + 1, dtype=i64, device=dev)
+    ring_ptr[1:] = torch.cumsum(ring_total >> 32, 0)
+    arc_base = torch.zeros(R + 1, dtype=i64, device=dev)
+    arc_base[1:] = torch.cumsum(torch.clamp(ring_total & 0xffffffff, min=1), 0)
+    V, n_arcs = (int(v) for v in torch.stack((ring_ptr[-1], arc_base[-1])).tolist())
+    arc_base = arc_base.to(i32)
+    xy, area2 = new((V, 2), i32), new(R, i64)
+    arc_first, arc_left, arc_right, arc_vstart, arc_count = (new(n_arcs, i32) for _ in range(5))
+    t = _lib.DmSceneVectorTrace() if wide else _lib.DmVectorTrace()
+    ring_name, arc_name = ("dm_scene_vector_ring_emit", "dm_scene_vector_arc_emit") if wide else ("dm_vector_ring_emit", "dm_vector_arc_emit")
+    for name, tensor in (("dart", dart), ("next", nxt0), ("lab", lab), ("other", other), ("flags", flags), ("key", key), ("sum", total),
+                         ("ring_of_slot", ring_of_slot), ("ring_ptr", ring_ptr), ("arc_base", arc_base), ("xy", xy), ("area2", area2),
+                         ("arc_first", arc_first), ("arc_left", arc_left), ("arc_right", arc_right), ("arc_vstart", arc_vstart),
+                         ("arc_count", arc_count)):
+        setattr(t, name, tensor.data_ptr())
+    t.W, t.D, t.R, t.n_arcs = W, D, R, n_arcs
+    check(getattr(lib, ring_name)(ctypes.byref(t), _stream()), ring_name)
+    ring_label = (ring_key >> 32).to(i32)
+    region_ptr = torch.zeros(S + 1, dtype=i64, device=dev)
+    region_ptr[1:] = torch.cumsum(torch.bincount(ring_label.long(), minlength=S), 0)
+    polys = Polygons(region_ptr=region_ptr.to(i32), ring_ptr=ring_ptr, xy=xy, ring_label=ring_label, ring_area2=area2)
+    mark("ring tables (sort, scans) + ring_emit")
+    # arcs: keep one side of every boundary, order by (right, left, first dart) in two stable passes
+    kept = torch.nonzero((arc_left < 0) | (arc_left > arc_right)).squeeze(1)
+    # left + 1 < 2^31; one raster: dart ids < 2^30; a scene: arc_first is the slot, < 2^31, and slot order is dart-id order
+    low = ((arc_left[kept].long() + 1) << (31 if wide else 30)) | arc_first[kept].long()
+    by_low = torch.argsort(low)
+    by_right = torch.argsort(arc_right[kept][by_low], stable=True)
+    kept = kept[by_low][by_right]
+    A = kept.numel()
+    arc_pos = torch.full((n_arcs,), -1, dtype=i32, device=dev)
+    arc_pos[kept] = torch.arange(A, dtype=i32, device=dev)
+    arc_ptr = torch.zeros(A + 1, dtype=i64, device=dev)
+    arc_ptr[1:] = torch.cumsum(arc_count[kept].long(), 0)
+    arc_xy = new((int(arc_ptr[-1]), 2), i32)
+    t.arc_pos, t.arc_ptr, t.arc_xy = arc_pos.data_ptr(), arc_ptr.data_ptr(), arc_xy.data_ptr()
+    check(getattr(lib, arc_name)(ctypes.byref(t), _stream()), arc_name)
+    arcs = Arcs(arc_ptr=arc_ptr, xy=arc_xy, left=arc_left[kept], right=arc_right[kept])
+    mark("arc tables (two sorts, scan) + arc_emit")
+    return polys, arcs, dict(D=D, R=R, A=A, V=V, head_rounds=head_rounds, rank_rounds=rank_rounds, arc_xy=arc_xy)
+
+
 def _trace(labels: torch.Tensor, n_labels: int, stats: Optional[dict] = None) -> Tuple[Polygons, Arcs]:
     """One tracing run for both results.  Readbacks: the label range, the number of darts D (it sizes everything that follows, so
     there is no max_ parameter), one flag per jumping round, the numbers of rings, vertices and arcs.  stats: a dict that receives
@@ -1010,72 +1086,12 @@ def _trace(labels: torch.Tensor, n_labels: int, stats: Optional[dict] = None) ->
     first_slot, dart = new(H * W, i32), new(D, i32)
     check(lib.dm_vector_emit(mask.data_ptr(), tile_off.data_ptr(), H, W, first_slot.data_ptr(), dart.data_ptr(), _stream()), "dm_vector_emit")
     nxt0, lab, other, flags = new(D, i32), new(D, i32), new(D, i32), new(D, torch.uint8)
-    keys, jumps = (new(D, i64), new(D, i64)), (nxt0, new(D, i32), new(D, i32))
+    key0 = new(D, i64)
     check(lib.dm_vector_link(labels.data_ptr(), mask.data_ptr(), first_slot.data_ptr(), dart.data_ptr(), H, W, D, nxt0.data_ptr(),
-                             lab.data_ptr(), other.data_ptr(), flags.data_ptr(), keys[0].data_ptr(), _stream()), "dm_vector_link")
+                             lab.data_ptr(), other.data_ptr(), flags.data_ptr(), key0.data_ptr(), _stream()), "dm_vector_link")
     mark("emit + link")
-    # heads: round 0 reads (keys[0], next) and writes (keys[1], jumps[1]); `next` itself is never written again
-    changed = meta[1:]
-    check(lib.dm_vector_head_round(keys[0].data_ptr(), nxt0.data_ptr(), keys[1].data_ptr(), jumps[1].data_ptr(), D, changed.data_ptr(),
-                                   _stream()), "dm_vector_head_round")
-    key, head_rounds = keys[1], 1
-    if int(changed.item()):
-        (key, _), more = _jump(lib.dm_vector_head_round, [(keys[1], jumps[1]), (keys[0], jumps[2])], D, changed, "dm_vector_head_round")
-        head_rounds += more
-    del jumps
-    mark("head rounds")
-    # ranks
-    max_rings = D // 4 + 1
-    sums, nxts = (new(D, i64), new(D, i64)), (new(D, i32), new(D, i32))
-    ring_key, ring_slot, n_rings = new(max_rings, i64), new(max_rings, i32), new(1, i32)
-    check(lib.dm_vector_rank_init(key.data_ptr(), nxt0.data_ptr(), flags.data_ptr(), lab.data_ptr(), D, sums[0].data_ptr(), nxts[0].data_ptr(),
-                                  ring_key.data_ptr(), ring_slot.data_ptr(), n_rings.data_ptr(), max_rings, _stream()), "dm_vector_rank_init")
-    (total, _), rank_rounds = _jump(lib.dm_vector_rank_round, [(sums[0], nxts[0]), (sums[1], nxts[1])], D, changed, "dm_vector_rank_round")
-    R = int(n_rings)
-    mark("rank rounds")
-    # rings in (label, head) order; the tables over rings and arcs are small next to the darts
-    ring_key, order = torch.sort(ring_key[:R])
-    ring_slot = ring_slot[:R][order].long()
-    ring_of_slot = new(D, i32)
-    ring_of_slot[ring_slot] = torch.arange(R, dtype=i32, device=dev)
-    ring_total = total[ring_slot]
-    ring_ptr = torch.zeros(R + 1, dtype=i64, device=dev)
-    ring_ptr[1:] = torch.cumsum(ring_total >> 32, 0)
-    arc_base = torch.zeros(R + 1, dtype=i64, device=dev)
-    arc_base[1:] = torch.cumsum(torch.clamp(ring_total & 0xffffffff, min=1), 0)
-    V, n_arcs = (int(v) for v in torch.stack((ring_ptr[-1], arc_base[-1])).tolist())
-    arc_base = arc_base.to(i32)
-    xy, area2 = new((V, 2), i32), new(R, i64)
-    arc_first, arc_left, arc_right, arc_vstart, arc_count = (new(n_arcs, i32) for _ in range(5))
-    t = _lib.DmVectorTrace()
-    for name, tensor in (("dart", dart), ("next", nxt0), ("lab", lab), ("other", other), ("flags", flags), ("key", key), ("sum", total),
-                         ("ring_of_slot", ring_of_slot), ("ring_ptr", ring_ptr), ("arc_base", arc_base), ("xy", xy), ("area2", area2),
-                         ("arc_first", arc_first), ("arc_left", arc_left), ("arc_right", arc_right), ("arc_vstart", arc_vstart),
-                         ("arc_count", arc_count)):
-        setattr(t, name, tensor.data_ptr())
-    t.W, t.D, t.R, t.n_arcs = W, D, R, n_arcs
-    check(lib.dm_vector_ring_emit(ctypes.byref(t), _stream()), "dm_vector_ring_emit")
-    ring_label = (ring_key >> 32).to(i32)
-    region_ptr = torch.zeros(S + 1, dtype=i64, device=dev)
-    region_ptr[1:] = torch.cumsum(torch.bincount(ring_label.long(), minlength=S), 0)
-    polys = Polygons(region_ptr=region_ptr.to(i32), ring_ptr=ring_ptr, xy=xy, ring_label=ring_label, ring_area2=area2)
-    mark("ring tables (sort, scans) + ring_emit")
-    # arcs: keep one side of every boundary, order by (right, left, first dart) in two stable passes
-    kept = torch.nonzero((arc_left < 0) | (arc_left > arc_right)).squeeze(1)
-    low = ((arc_left[kept].long() + 1) << 30) | arc_first[kept].long()            # left + 1 < 2^31, dart ids < 2^30
-    by_low = torch.argsort(low)
-    by_right = torch.argsort(arc_right[kept][by_low], stable=True)
-    kept = kept[by_low][by_right]
-    A = kept.numel()
-    arc_pos = torch.full((n_arcs,), -1, dtype=i32, device=dev)
-    arc_pos[kept] = torch.arange(A, dtype=i32, device=dev)
-    arc_ptr = torch.zeros(A + 1, dtype=i64, device=dev)
-    arc_ptr[1:] = torch.cumsum(arc_count[kept].long(), 0)
-    arc_xy = new((int(arc_ptr[-1]), 2), i32)
-    t.arc_pos, t.arc_ptr, t.arc_xy = arc_pos.data_ptr(), arc_ptr.data_ptr(), arc_xy.data_ptr()
-    check(lib.dm_vector_arc_emit(ctypes.byref(t), _stream()), "dm_vector_arc_emit")
-    arcs = Arcs(arc_ptr=arc_ptr, xy=arc_xy, left=arc_left[kept], right=arc_right[kept])
-    mark("arc tables (two sorts, scan) + arc_emit")
+    polys, arcs, info = _trace_table(dart, nxt0, lab, other, flags, key0, W, S, mark)
+    D, R, A, V, head_rounds, rank_rounds, arc_xy = (info[k] for k in ("D", "R", "A", "V", "head_rounds", "rank_rounds", "arc_xy"))
     if stats is not None:
         torch.cuda.synchronize()
         stats["stage_ms"] = [(b[0], a[1].elapsed_time(b[1])) for a, b in zip(marks[:-1], marks[1:])]

@@ -14,8 +14,15 @@ counted as "raster border" although another label faces them -- is added by one 
 a batch: the batches of a scene break at tile boundaries.)
 
 Known consequence: where the learned merge does not join two superpixels across a seam, a straight boundary stays on the seam
-line.  Out of scope: superpixels that cross seams; a user label raster whose regions cross seams; rings and arcs across tiles
-(trace `SceneResult.merged_tile(i)` per tile); `rag.mrs` on a scene graph; overlapping the copy of the next tile with compute.
+line.  Out of scope: superpixels that cross seams; a user label raster whose regions cross seams; `rag.mrs` on a scene graph;
+overlapping the copy of the next tile with compute.
+
+Rings and arcs.  `trace_labels` traces a scene's label raster -- the merged raster through
+`SceneResult.trace` -- into the rings and arcs `rag._trace` gives on the whole raster, array for array and bit for bit, whatever
+the tile size: every tile is read with one pixel of its neighbours' labels, its core's darts get scene-wide 64-bit ids
+(csrc/dm_scene_vector.hip), the tiles' tables are joined by one sort, and the jumping rounds run once over the scene's table.
+`SceneResult.save_shapefiles` writes them as `polygons.shp` and `lines.shp`.  Out of scope: `rag.simplify` on a scene;
+`PointsGCS.shp` for a scene; overlapping the next tile's read with compute.
 
 Memory.  The scene's pixels are never on the device as a whole: one halo window at a time.  What is resident for the whole scene
 is per superpixel and per sample point: the statistics, the graph, the points and the [P,100] feature rows.  The scene-wide
@@ -32,7 +39,8 @@ from typing import Callable, Dict, List, Optional, Tuple
 import numpy as np
 import torch
 
-from . import rag
+from . import _lib, rag
+from .ops import _stream, check
 
 Core = Tuple[int, int, int, int]          # y0, y1, x0, x1
 
@@ -258,6 +266,37 @@ class SceneResult:
             out[y0:y1, x0:x1] = self.merged_tile(i).cpu().numpy()
         return out
 
+    def _tile(self) -> Tuple[int, int]:
+        y0, y1, x0, x1 = self.tiles[0]
+        return y1 - y0, x1 - x0
+
+    def trace(self, merged=None, tile=None, stats: Optional[dict] = None) -> Tuple["rag.Polygons", "rag.Arcs"]:
+        """The merged regions as polygon rings and boundary arcs in scene coordinates, regions that cross seams in one piece:
+        `trace_labels` of the merged raster.  merged: the host raster as `write_merged` returns it (computed if None); tile: the
+        tracing tile, default the scene's own.  `Arcs.edge` is the row of (right, left) in `result.edges`.  Equals
+        `MergeResult.polygons / boundary_arcs` on the assembled raster."""
+        merged = self.write_merged() if merged is None else merged
+        C = int(self.result.rep.numel())
+        polys, arcs = trace_labels(merged, C, tile=self._tile() if tile is None else tile, stats=stats, device=self.edges.device)
+        return polys, rag._attach_edges(arcs, C, self.result.edges)
+
+    def polygons(self, merged=None, tile=None) -> "rag.Polygons":
+        return self.trace(merged, tile)[0]
+
+    def boundary_arcs(self, merged=None, tile=None) -> "rag.Arcs":
+        return self.trace(merged, tile)[1]
+
+    def save_shapefiles(self, folder: str, geotransform=None, merged=None, tile=None) -> Tuple[str, str]:
+        """Write the merged regions as the two layers of `FeatureIO.save_shapefiles` that a scene has: `polygons.shp` (one record
+        per merged region: the 15 designed fields of `designed_features(result.stats)` and `PointID` from `result.ptr / idx`) and
+        `lines.shp` (one record per boundary arc: LEFT_FID, RIGHT_FID, simi = `result.simi` of the arc's edge, 0.0 on the scene's
+        frame), through the same writer.  No `PointsGCS.shp`: out of scope for a scene.  Returns the two paths."""
+        from .ExtractFeatures import write_polygon_and_line_layers
+        polys, arcs = self.trace(merged, tile)
+        r = self.result
+        return tuple(write_polygon_and_line_layers(folder, polys, arcs, int(r.rep.numel()), r.ptr, r.idx, rag.designed_features(r.stats),
+                                                   edges=r.edges, simi=r.simi, geotransform=geotransform))
+
     def overlap(self, truth_source, n_truth: int) -> "rag.Overlap":
         """The `Overlap` of the scene's superpixels with a ground-truth raster (int32 [H,W]: an array, a memmap, a CPU tensor, or
         anything with `.read(y0, y1, x0, x1)` returning int32 [y1-y0, x1-x0]), for `result.scores(...)`: per tile one
@@ -312,3 +351,127 @@ def segment_scene(fio, source, tile=4096, segmenter: Optional[Callable] = None, 
     clock.lap("merge")
     return SceneResult(result=result, n_labels=g["n_labels"], tiles=g["tiles"], offsets=g["offsets"], stats=g["stats"], designed=g["designed"],
                        edges=g["edges"], weights=g["weights"], points=pts, features=features, labels=g["labels"])
+
+
+# ---- rings and arcs across tile seams (csrc/dm_scene_vector.hip) ---------------------------------------------------
+MAX_TRACE_SIDE = (1 << 31) - 1        # DM_SCENE_VECTOR_MAX_SIDE: H, W below it, so every corner fits int32
+MAX_TRACE_SCENE = 1 << 60             # DM_SCENE_VECTOR_MAX_PIXELS: dart ids 4 (y W + x) + side stay below 2^62
+MAX_DARTS = 1 << 31                   # slots are int32
+
+
+def _check_trace(source, n_labels, tile) -> Tuple[int, int, int, List[Core]]:
+    shape = tuple(source.shape)
+    if len(shape) != 2 or min(shape) < 1:
+        raise ValueError(f"source.shape must be (H, W) with H, W >= 1, got {shape}")
+    H, W = (int(v) for v in shape)
+    if H >= MAX_TRACE_SIDE or W >= MAX_TRACE_SIDE:
+        raise ValueError(f"H and W must be below 2^31 - 1, got {H} x {W}")
+    if H * W > MAX_TRACE_SCENE:
+        raise ValueError(f"the scene must have at most 2^60 pixels (64-bit dart ids), got {H} x {W}")
+    S = int(n_labels)
+    if not 1 <= S < 1 << 31:
+        raise ValueError(f"n_labels must be in 1..2^31-1, got {n_labels}")
+    th, tw = (tile, tile) if isinstance(tile, int) else tuple(tile)
+    if int(th) < 1 or int(tw) < 1:
+        raise ValueError(f"tile must be >= 1, got {tile}")
+    # a window's height depends on its tile row only, its width on its column only, and neither grows behind the second
+    side = lambda n, t: max(min(n, y + t + 1) - max(0, y - 1) for y in range(0, min(n, 2 * t), t))
+    side_y, side_x = side(H, int(th)), side(W, int(tw))
+    if side_y * side_x > rag.MAX_TRACE_PIXELS:
+        raise ValueError(f"a tile's window (core + 1 pixel on every side) must have at most 2^28 pixels, got {side_y} x {side_x}")
+    return H, W, S, tile_grid(H, W, tile)
+
+
+def _check_darts(total: int, i: int, n_tiles: int):
+    if total >= MAX_DARTS:
+        raise ValueError(f"the scene has 2^31 darts or more ({total} after tile {i} of {n_tiles}): slots are 32-bit; trace a coarser "
+                         f"partition or the scene in parts")
+
+
+def _tile_darts(window: torch.Tensor, box: Core, origin: Tuple[int, int], H: int, W: int):
+    """The dart records of one tile (dm_scene_vector_count, dm_vector_emit, dm_scene_vector_link).  window int32 [wh,ww] on the
+    device: the core `box` = (cy0, cy1, cx0, cx1) in window coordinates and its apron; origin (oy, ox): the window's first pixel in
+    the H x W scene.  Returns (id int64, succ int64, lab, other, succ_flags uint8), each [D], in the tile's slot order; None when
+    the core has no dart."""
+    rag._need_cuda(window)
+    lib, dev, i32 = _lib.lib(), window.device, torch.int32
+    window = window.contiguous()
+    wh, ww = window.shape
+    cy0, cy1, cx0, cx1 = box
+    new = lambda n, dt: torch.empty(n, dtype=dt, device=dev)
+    n_tiles = ((wh + 63) // 64) * ((ww + 63) // 64)
+    mask, core_mask, tile_off, meta = new(wh * ww, torch.uint8), new(wh * ww, torch.uint8), new(n_tiles + 1, i32), new(1, i32)
+    check(lib.dm_scene_vector_count(window.data_ptr(), wh, ww, cy0, cy1, cx0, cx1, mask.data_ptr(), core_mask.data_ptr(), tile_off.data_ptr(),
+                                    meta.data_ptr(), _stream()), "dm_scene_vector_count")
+    D = int(meta[0])
+    if D == 0:
+        return None
+    first_slot, dart = new(wh * ww, i32), new(D, i32)
+    check(lib.dm_vector_emit(core_mask.data_ptr(), tile_off.data_ptr(), wh, ww, first_slot.data_ptr(), dart.data_ptr(), _stream()),
+          "dm_vector_emit")
+    ids, succ = new(D, torch.int64), new(D, torch.int64)
+    lab, other, sflags = new(D, i32), new(D, i32), new(D, torch.uint8)
+    check(lib.dm_scene_vector_link(window.data_ptr(), mask.data_ptr(), dart.data_ptr(), wh, ww, D, int(origin[0]), int(origin[1]), H, W,
+                                   ids.data_ptr(), succ.data_ptr(), lab.data_ptr(), other.data_ptr(), sflags.data_ptr(), _stream()),
+          "dm_scene_vector_link")
+    return ids, succ, lab, other, sflags
+
+
+def _join(ids: torch.Tensor, succ: torch.Tensor, lab: torch.Tensor, other: torch.Tensor, succ_flags: torch.Tensor):
+    """The tiles' concatenated records as one linked table: one sort by scene dart id (slot order = id order), next = the slot of
+    every successor, the returned flags scattered to it (the successor map is a permutation: nothing collides), key = slot << 32 |
+    slot.  Returns (dart int64, next int32, lab, other, flags uint8, key int64).  Table arithmetic in torch, as rag._trace does its
+    own between the kernels."""
+    D = int(ids.numel())
+    dart, order = torch.sort(ids)
+    succ = succ[order]
+    nxt = torch.searchsorted(dart, succ)
+    if not bool((dart[nxt.clamp(max=D - 1)] == succ).all()):
+        raise RuntimeError("a dart's successor is not a dart of the scene: the tiles' records do not cover one label raster")
+    flags = torch.empty(D, dtype=torch.uint8, device=ids.device)
+    flags[nxt] = succ_flags[order]
+    slot = torch.arange(D, dtype=torch.int64, device=ids.device)
+    return dart, nxt.to(torch.int32), lab[order], other[order], flags, (slot << 32) | slot
+
+
+def trace_labels(source, n_labels: int, tile=4096, stats: Optional[dict] = None, device="cuda:0") -> Tuple["rag.Polygons", "rag.Arcs"]:
+    """A scene's label raster traced into polygon rings and boundary arcs across tile seams: array for array and bit for bit what
+    `rag._trace(L, n_labels)` returns on the whole raster L, in scene coordinates, whatever the tile size.
+
+    source: int32 [H, W] with ids 0..n_labels-1 -- a numpy array, an `np.memmap`, a CPU tensor, or anything with `.shape == (H, W)`
+    and `.read(y0, y1, x0, x1) -> int32 [y1-y0, x1-x0]`; it is read window by window and never modified.  tile: core side, an int
+    or (th, tw).  stats: a dict that receives the darts, rings, arcs, rounds and seconds per stage (synchronises at stage
+    boundaries).  Limits, each a ValueError: H, W < 2^31 - 1 and H W <= 2^60; every window (core + 1 pixel) at most 2^28 pixels;
+    ids outside 0..n_labels-1 (-1 included) name their tile; fewer than 2^31 darts in the scene.
+    Memory: one window's rasters at a time; 25 bytes per dart of the scene while the tiles stream."""
+    source = _as_source(source)
+    H, W, S, tiles = _check_trace(source, n_labels, tile)
+    dev = torch.device(device)
+    clock = _Clock(None if stats is None else stats.setdefault("stage_s", {}), dev)
+    parts, total = [], 0
+    for i, core in enumerate(tiles):
+        y0, y1, x0, x1 = core
+        wy0, wy1, wx0, wx1 = box = window_of(core, H, W, 1)
+        window = _read(source, box, torch.int32, 2, dev)
+        clock.lap("read + copy")
+        lo, hi = (int(v) for v in torch.aminmax(window))
+        if lo < 0 or hi >= S:
+            raise ValueError(f"labels must be in 0..n_labels-1 = 0..{S - 1}: the window of tile {i} (rows {wy0}..{wy1 - 1}, columns "
+                             f"{wx0}..{wx1 - 1}) holds {lo}..{hi}")
+        got = _tile_darts(window, (y0 - wy0, y1 - wy0, x0 - wx0, x1 - wx0), (wy0, wx0), H, W)
+        if got is not None:
+            total += int(got[0].numel())
+            _check_darts(total, i, len(tiles))
+            parts.append(got)
+        clock.lap("per-tile passes")
+    ids, succ, lab, other, sflags = (torch.cat([p[k] for p in parts]) for k in range(5))
+    del parts
+    table = _join(ids, succ, lab, other, sflags)
+    del ids, succ, lab, other, sflags
+    clock.lap("sort + join")
+    stage_of = {"head rounds": "rounds", "rank rounds": "rounds"}
+    polys, arcs, info = rag._trace_table(*table, W, S, mark=lambda stage: clock.lap(stage_of.get(stage, "emit")), wide=True)
+    if stats is not None:
+        stats.update(D=info["D"], rings=info["R"], arcs=info["A"], vertices=info["V"], arc_vertices=int(info["arc_xy"].shape[0]),
+                     head_rounds=info["head_rounds"], rank_rounds=info["rank_rounds"], tiles=len(tiles))
+    return polys, arcs

@@ -780,6 +780,61 @@ int dm_vector_rank_round(const int64_t *sum_in, const int32_t *nxt_in, int64_t *
 int dm_vector_ring_emit(const DmVectorTrace *t, void *stream);
 int dm_vector_arc_emit(const DmVectorTrace *t, void *stream);
 
+/* ---- a scene's label raster traced across tile seams (additive in ABI 7; csrc/dm_scene_vector.hip, DESIGN.md 3.5.10,
+ * scene.trace_labels / SceneResult.trace) ---------------------------------------------------------------------------------------
+ * The rule above, unchanged, for a raster L [scene_h, scene_w] that is read tile by tile and never resident: the result is,
+ * array for array and bit for bit, what the one-raster calls give on the whole of L, whatever the tile size.  No new geometry
+ * rule: rings are ordered by (label, smallest scene dart id), arcs by (right, left, first dart).
+ * A tile is a core box of the scene and its window: the core grown by one pixel on every side and clipped to the scene (an apron
+ * of the neighbours' labels).  Only the core's pixels own darts.  scene dart id = 4 ((y + oy) scene_w + (x + ox)) + side for the
+ * window pixel (x, y) of a window whose first pixel is the scene's (ox, oy): int64.
+ * Why the apron is enough: a core dart consults its own pixel, the ahead-right and the ahead-left pixel and the pixel across its
+ * successor's side, all 8-neighbours of the core pixel; a window edge that is not a scene edge is never consulted for a core
+ * dart, and one that is a scene edge is the raster's outside.
+ *
+ * dm_scene_vector_count: labels int32 [H,W] = the window (1 <= H*W <= 2^28), the core = [cy0,cy1) x [cx0,cx1) in window
+ *   coordinates, at most one pixel from every window edge.  mask uint8 [H,W] = dm_vector_count's mask of the window; core_mask = the
+ *   same inside the core, 0 outside; tile_off int32 [tiles+1] = exclusive scan of the CORE's darts per 64x64 tile of the window,
+ *   tile_off[tiles] = n_darts[0] = D.  dm_vector_emit on (core_mask, tile_off) then leaves the core's window-local dart ids.
+ * dm_scene_vector_link: for the D darts `dart` (window-local ids, as dm_vector_emit leaves them): id int64 = the scene dart id,
+ *   succ int64 = the successor's scene dart id (its pixel may be an apron pixel: another tile's dart), lab, other, and succ_flags
+ *   uint8 = the flags (1 vertex dart, 2 break dart) OF THE SUCCESSOR, which the caller scatters once it knows the successor's slot.
+ *   1 <= D; the window lies in the scene; scene_h, scene_w < DM_SCENE_VECTOR_MAX_SIDE, scene_h * scene_w <=
+ *   DM_SCENE_VECTOR_MAX_PIXELS (ids stay below 2^62).
+ * The join is the caller's: concatenate the tiles' records, sort by id (slot order = id order), next = position of succ among the
+ * sorted ids, flags[next] = succ_flags, key = slot << 32 | slot.  dm_vector_head_round / rank_init / rank_round then run
+ * unchanged; rank_init's ring_key becomes label << 32 | head slot, which sorts as (label, smallest dart id).
+ * dm_scene_vector_ring_emit / dm_scene_vector_arc_emit: dm_vector_ring_emit / dm_vector_arc_emit with dart int64 [D] (scene ids)
+ *   and W int64 = scene_w; arc_first receives the first dart's SLOT (the caller's arc sort key: (left + 1) << 31 | slot).  Corners
+ *   are int32, area2 the int64 integer atomic add.
+ * Every entry point validates before any launch, launches on `stream`, never synchronises and never allocates. */
+#define DM_SCENE_VECTOR_MAX_SIDE 2147483647LL        /* scene_h, scene_w < 2^31 - 1: every corner fits int32 */
+#define DM_SCENE_VECTOR_MAX_PIXELS (1LL << 60)
+typedef struct DmSceneVectorTrace {
+  const int64_t *dart;
+  const int32_t *next, *lab, *other;
+  const uint8_t *flags;
+  const int64_t *key, *sum;
+  const int32_t *ring_of_slot;
+  const int64_t *ring_ptr;
+  const int32_t *arc_base;
+  int32_t *xy;
+  int64_t *area2;
+  int32_t *arc_first, *arc_left, *arc_right, *arc_vstart, *arc_count;
+  const int32_t *arc_pos;
+  const int64_t *arc_ptr;
+  int32_t *arc_xy;
+  int64_t W;
+  int32_t D, R, n_arcs;
+} DmSceneVectorTrace;
+int dm_scene_vector_count(const int32_t *labels, int32_t H, int32_t W, int32_t cy0, int32_t cy1, int32_t cx0, int32_t cx1, uint8_t *mask,
+                          uint8_t *core_mask, int32_t *tile_off, int32_t *n_darts, void *stream);
+int dm_scene_vector_link(const int32_t *labels, const uint8_t *mask, const int32_t *dart, int32_t H, int32_t W, int32_t D, int64_t oy,
+                         int64_t ox, int64_t scene_h, int64_t scene_w, int64_t *id, int64_t *succ, int32_t *lab, int32_t *other,
+                         uint8_t *succ_flags, void *stream);
+int dm_scene_vector_ring_emit(const DmSceneVectorTrace *t, void *stream);
+int dm_scene_vector_arc_emit(const DmSceneVectorTrace *t, void *stream);
+
 /* ---- polygon rings rasterised into a label raster (additive in ABI 6; csrc/dm_rasterize.hip, DESIGN.md 3.5.6, rag.rasterize /
  * rag.labels_from_shapefile) ------------------------------------------------------------------------------------------------------
  * The inverse of the tracing above, for ANY polygon: the step from the polygon layer the reference's users have (superpixels
