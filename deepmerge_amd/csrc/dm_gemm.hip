@@ -44,6 +44,8 @@ int dm_gemm_ring_plan(GemmParams &p, const GemmSwitches &sw, int layout, int ab_
 void dm_gemm_ring_launch(const GemmParams &p, int wm, hipStream_t s);
 bool dm_gemm_q4_plan(GemmParams &p, const GemmSwitches &sw, int layout, int ab_dtype, bool aligned8);      // dm_gemm_q4.hip
 void dm_gemm_q4_launch(const GemmParams &p, int layout, hipStream_t s);
+bool dm_gemm_t96_plan(GemmParams &p, const GemmSwitches &sw, int layout, int ab_dtype, bool aligned8);     // dm_gemm_t96.hip
+void dm_gemm_t96_launch(const GemmParams &p, int layout, hipStream_t s);
 int dm_gemm_w4_plan(GemmParams &p, const GemmSwitches &sw, int layout, int ab_dtype, bool aligned8, bool can_split, long long workspace_bytes);   // dm_gemm_w4.hip (grid size, 0 = not taken)
 void dm_gemm_w4_launch(const GemmParams &p, int layout, int grid, hipStream_t s);
 bool dm_gemm_w4_grouped_plan(GroupPlan &pl, int mode, const DmGroupedExtra &x);      // dm_gemm_w4.hip: n weight gradients in one launch (false = not taken)
@@ -712,6 +714,7 @@ inline GemmSwitches read_switches() {
   if (const char *e = getenv("DM_GEMM_W4")) sw.w4 = atoi(e);
   if (const char *e = getenv("DM_GEMM_W4_TN")) sw.w4_tn = atoi(e);
   if (const char *e = getenv("DM_GEMM_Q4")) sw.q4 = atoi(e);
+  if (const char *e = getenv("DM_GEMM_T96")) sw.t96 = atoi(e);
   if (const char *e = getenv("DM_GEMM_RING")) sw.ring = atoi(e);
   if (const char *e = getenv("DM_GEMM_RING_WM")) sw.ring_wm = atoi(e);
   if (const char *e = getenv("DM_GEMM_256")) sw.p256 = atoi(e);
@@ -721,7 +724,7 @@ inline GemmSwitches read_switches() {
 }
 
 // A/B aid (tools/routing_check.py finds candidates in a cold microbenchmark; the decision is taken INSIDE the step): DM_GEMM_ROUTE names a
-// kernel family for single products, e.g. "NT:16384x2304x768=ring,NN:16384x3072x768=256" (families: w4, ring, 256, 128, 64, q4).  For a named
+// kernel family for single products, e.g. "NT:16384x2304x768=ring,NN:16384x3072x768=256" (families: w4, ring, 256, 128, 64, q4, t96).  For a named
 // product the call's own copy of the switches is replaced: the named family "whenever legal", every other family off, a forced tile only
 // for 128 / 64.  The environment is not touched.  Never set in production.  Returns whether the product was named.
 inline bool apply_route(GemmSwitches &sw, int layout, int M, int N, int K) {
@@ -733,13 +736,14 @@ inline bool apply_route(GemmSwitches &sw, int layout, int M, int N, int K) {
   if (!hit) return false;
   const char *fam = hit + strlen(want);
   GemmSwitches r;
-  r.w4 = r.w4_tn = r.q4 = r.ring = r.p256 = 0;
+  r.w4 = r.w4_tn = r.q4 = r.t96 = r.ring = r.p256 = 0;
   if (!strncmp(fam, "w4", 2)) r.w4 = r.w4_tn = 2;
   else if (!strncmp(fam, "ring", 4)) r.ring = 2;
   else if (!strncmp(fam, "256", 3)) r.p256 = 2;
   else if (!strncmp(fam, "128", 3)) { r.force_tile = 128; r.force_tile_set = true; }
   else if (!strncmp(fam, "64", 2)) { r.force_tile = 64; r.force_tile_set = true; }
   else if (!strncmp(fam, "q4", 2)) r.q4 = 2;
+  else if (!strncmp(fam, "t96", 3)) r.t96 = 2;
   else return false;
   sw = r;
   return true;
@@ -862,7 +866,7 @@ struct GemmCall {
   float *cs_region;
 };
 
-enum class GemmFamily { W4, Q4, RING, P256, TILE };      // in the order of precedence; TILE = the register-staged 128x128 / 64x64 kernel
+enum class GemmFamily { W4, Q4, T96, RING, P256, TILE };      // in the order of precedence; TILE = the register-staged 128x128 / 64x64 kernel
 
 // What dm_gemm decided for one product on the MFMA path (the grid geometry itself is in GemmParams: tiles_m / tiles_n / split_k / k_per_split).
 struct GemmPlan {
@@ -881,6 +885,7 @@ int prof_family_code(const GemmPlan &pl) {
   switch (pl.family) {
     case GemmFamily::W4: return 1924;
     case GemmFamily::Q4: return 1284;
+    case GemmFamily::T96: return 12896;
     case GemmFamily::RING: return pl.ring_wm == 8 ? 2568 : 1288;
     case GemmFamily::P256: return 256;
     default: return pl.tile;
@@ -1034,7 +1039,7 @@ int gemm_plan(GemmCall &c, GemmPlan &pl) {
   p.group_m = dm_gemm_tuning().group_m >= 0 ? dm_gemm_tuning().group_m : 8;   // measured over the encoder's step: 8 > 4 > 0 (column-fastest) > 16 > 32, within 2 %
 
   // the 4-wave register-staged persistent kernel, then the four-workgroups-per-CU 128 x 128 tiles (dm_gemm_q4.hip) for the short-contraction
-  // forward / dgrad products, then the ring kernel, then the 256x256 pipeline, then the register-staged tiles.  A plan that takes the
+  // forward / dgrad products, then the one-round 128 x 96 DMA-ring tiles (dm_gemm_t96.hip) for the long-contraction 768-wide ones, then the ring kernel, then the 256x256 pipeline, then the register-staged tiles.  A plan that takes the
   // product fills p.tiles_m / tiles_n / split_k / k_per_split.
   pl = GemmPlan{};
   pl.family = GemmFamily::TILE;
@@ -1042,6 +1047,8 @@ int gemm_plan(GemmCall &c, GemmPlan &pl) {
     pl.family = GemmFamily::W4;
   else if (dm_gemm_q4_plan(p, sw, a->layout, a->ab_dtype, ring_aligned))
     pl.family = GemmFamily::Q4;
+  else if (dm_gemm_t96_plan(p, sw, a->layout, a->ab_dtype, ring_aligned))
+    pl.family = GemmFamily::T96;
   else if ((pl.ring_wm = dm_gemm_ring_plan(p, sw, a->layout, a->ab_dtype, ring_aligned)) != 0)
     pl.family = GemmFamily::RING;
   else if (dm_gemm256_plan(p, sw, a->layout, a->ab_dtype, can_split, slab_bytes, a->split_k))
@@ -1103,6 +1110,7 @@ int gemm_launch(const GemmCall &c, const GemmPlan &pl) {
     switch (pl.family) {
       case GemmFamily::W4: dm_gemm_w4_launch(p, a->layout, pl.w4_grid, s); break;
       case GemmFamily::Q4: dm_gemm_q4_launch(p, a->layout, s); break;
+      case GemmFamily::T96: dm_gemm_t96_launch(p, a->layout, s); break;
       case GemmFamily::RING: dm_gemm_ring_launch(p, pl.ring_wm, s); break;
       case GemmFamily::P256: dm_gemm256_launch(p, a->layout, s); break;
       case GemmFamily::TILE: {

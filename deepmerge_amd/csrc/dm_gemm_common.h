@@ -30,10 +30,10 @@ constexpr int DM_DBG_TOUCH_OFF = 0x200;      // DM_GEMM_T128_TOUCH=0: no early t
 constexpr int DM_DBG_LEAN_OFF = 0x400;       // DM_GEMM_EPI_LEAN=0: the generic whole-line epilogue
 
 // The per-call modes of the kernel families (0 = off, 1 = routing rules, 2 = whenever legal; the 4-wave kernel knows more: dm_gemm_w4_plan)
-// and the forced tile.  dm_gemm reads them from the environment once per call (DM_GEMM_W4, DM_GEMM_W4_TN, DM_GEMM_Q4, DM_GEMM_RING,
+// and the forced tile.  dm_gemm reads them from the environment once per call (DM_GEMM_W4, DM_GEMM_W4_TN, DM_GEMM_Q4, DM_GEMM_T96, DM_GEMM_RING,
 // DM_GEMM_RING_WM, DM_GEMM_256, DM_GEMM_GROUPED, DM_GEMM_FORCE_TILE), lets DM_GEMM_ROUTE edit its copy, and hands it to the plans.
 struct GemmSwitches {
-  int w4 = 1, w4_tn = 1, q4 = 1, ring = 1, p256 = 1;
+  int w4 = 1, w4_tn = 1, q4 = 1, t96 = 1, ring = 1, p256 = 1;
   int ring_wm = 0;                 // DM_GEMM_RING_WM: 8 / 4 force that wave height of the ring kernel
   int grouped = 1;                 // dm_gemm_grouped's one launch: 0 = off, 1 = rule, 2 = one K slice per tile whenever legal, 4 = sliced whenever legal
   int force_tile = 0;              // 64 / 128 force that tile of the register-staged kernel (tuning / A-B aid); anything else does not,
@@ -408,15 +408,17 @@ __device__ __forceinline__ int dm_epi_records(long long bytes) { return (int)(by
 // item -- RES: fp32 residual read; YL: 0 none / 1 old C (accumulate) / 2 aux read, bf16 / 3 aux read, fp32; C32: fp32 C; XS: 0 no aux
 // store / 1 bf16 / 2 fp32 -- is a template argument, so every memory instruction is straight-line code with counted waits; only the
 // arithmetic kind (GELU / GELU' / multiply) stays a run-time branch.  dm_epilogue_rows dispatches the combinations the encoder uses.
-template <int WM, int ROWS, bool RT = true, bool RES = false, int YL = 0, bool C32 = false, int XS = 0>
-__device__ __forceinline__ void dm_epilogue_rows_lean(const GemmParams &p, f32x4 (&acc)[WM][4], char *mine, int m_wave_in, int n_wave_in, int lane) {
+// NJ: 16-column accumulator tiles per wave block (4; 3 = the 48-column block of dm_gemm_t96.hip: the lanes of column groups 6 and 7 of a
+// row are killed like columns past N).
+template <int WM, int ROWS, bool RT = true, bool RES = false, int YL = 0, bool C32 = false, int XS = 0, int NJ = 4>
+__device__ __forceinline__ void dm_epilogue_rows_lean(const GemmParams &p, f32x4 (&acc)[WM][NJ], char *mine, int m_wave_in, int n_wave_in, int lane) {
   // wave-uniform by construction, but derived from threadIdx in some callers: without the readfirstlane the descriptors below live
   // in VGPRs and every buffer access becomes a waterfall loop
   const int m_wave = __builtin_amdgcn_readfirstlane(m_wave_in), n_wave = __builtin_amdgcn_readfirstlane(n_wave_in);
   constexpr int PASS_TILES = ROWS / 16, NPASS = WM / PASS_TILES, R = ROWS / 8, Q = NPASS * R;
   const int g = lane >> 4, li = lane & 15, c8 = lane & 7, rl = lane >> 3;
   const int n = n_wave + c8 * 8;
-  const unsigned kill = (n < p.N) ? 0u : 0x80000000u;              // columns past N (N % 8 == 0: whole groups)
+  const unsigned kill = (n < p.N && (NJ == 4 || c8 * 8 < NJ * 16)) ? 0u : 0x80000000u;      // columns past N (N % 8 == 0: whole groups)
   const bool c32 = RT ? (p.c_dtype == DM_F32) : C32;
   const bool x32 = RT ? (p.aux_dtype == DM_F32) : (YL == 3 || XS == 2);
   const int csz = c32 ? 4 : 2, xsz = x32 ? 4 : 2;
@@ -538,7 +540,7 @@ __device__ __forceinline__ void dm_epilogue_rows_lean(const GemmParams &p, f32x4
 #pragma unroll
     for (int ii = 0; ii < PASS_TILES; ++ii)
 #pragma unroll
-      for (int j = 0; j < 4; ++j)
+      for (int j = 0; j < NJ; ++j)
         *reinterpret_cast<f32x4 *>(mine + ((ii * 16 + li) * DM_EPI_PITCH + ((j * 4 + g) << 4))) = acc[ps * PASS_TILES + ii][j];
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_sched_barrier(0);
@@ -580,15 +582,16 @@ __host__ __device__ inline bool dm_epi_key_specialised(int key) {
 
 // LEAN_ONLY: the caller (a kernel that has no registers for the generic and run-time forms: dm_gemm_q4.hip) guarantees on the host that
 // dm_epi_key_specialised holds.
-template <int WM, int ROWS, bool LEAN_ONLY = false>
-__device__ __forceinline__ void dm_epilogue_rows(const GemmParams &p, f32x4 (&acc)[WM][4], char *mine, int m_wave, int n_wave, int lane) {
+template <int WM, int ROWS, bool LEAN_ONLY = false, int NJ = 4>
+__device__ __forceinline__ void dm_epilogue_rows(const GemmParams &p, f32x4 (&acc)[WM][NJ], char *mine, int m_wave, int n_wave, int lane) {
+  static_assert(NJ == 4 || LEAN_ONLY, "narrower wave blocks exist in the straight-line forms only");
   const int key = dm_epi_lean_key(p, 16 * WM);
   if constexpr (!LEAN_ONLY) {
     if (key < 0) { dm_epilogue_rows_generic<WM, ROWS>(p, acc, mine, m_wave, n_wave, lane); return; }
   }
 #define DM_EPI_CASE(RES, YL, C32, XS) \
   case ((RES) | ((YL) << 1) | ((C32) << 3) | ((XS) << 4)): \
-    dm_epilogue_rows_lean<WM, ROWS, false, (RES) != 0, (YL), (C32) != 0, (XS)>(p, acc, mine, m_wave, n_wave, lane); break;
+    dm_epilogue_rows_lean<WM, ROWS, false, (RES) != 0, (YL), (C32) != 0, (XS), NJ>(p, acc, mine, m_wave, n_wave, lane); break;
   switch (key) {
     DM_EPI_CASE(0, 0, 0, 0)      // bf16 C (+ bias / GELU without a saved derivative): qkv forward, the dgrads, inference fc1
     DM_EPI_CASE(1, 0, 1, 0)      // fp32 C + fp32 residual: proj / fc2 forward
@@ -597,7 +600,7 @@ __device__ __forceinline__ void dm_epilogue_rows(const GemmParams &p, f32x4 (&ac
     DM_EPI_CASE(0, 0, 0, 1)      // bf16 C + bf16 aux written: fc1 forward (GELU + saved GELU')
     DM_EPI_CASE(0, 2, 0, 0)      // bf16 C, bf16 aux read: dgrad of fc2 (multiply by the saved GELU')
     default:
-      if constexpr (!LEAN_ONLY) dm_epilogue_rows_lean<WM, ROWS, true>(p, acc, mine, m_wave, n_wave, lane);
+      if constexpr (!LEAN_ONLY) dm_epilogue_rows_lean<WM, ROWS, true>(p, acc, mine, m_wave, n_wave, lane);      // (NJ == 4)
       break;
   }
 #undef DM_EPI_CASE

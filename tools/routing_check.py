@@ -16,14 +16,15 @@ from deepmerge_amd._lib import DM_EPI_GELU_GRAD, DM_EPI_MUL, DM_EPI_NONE, DM_NN,
 
 DEV = "cuda:0"
 g = torch.Generator(device=DEV); g.manual_seed(1)
-KEYS = ("DM_GEMM_FORCE_TILE", "DM_GEMM_256", "DM_GEMM_W4", "DM_GEMM_W4_TN", "DM_GEMM_RING", "DM_GEMM_FWD_SPLIT")
-OFF = {"DM_GEMM_256": "0", "DM_GEMM_W4": "0", "DM_GEMM_W4_TN": "0", "DM_GEMM_RING": "0"}
+KEYS = ("DM_GEMM_FORCE_TILE", "DM_GEMM_256", "DM_GEMM_W4", "DM_GEMM_W4_TN", "DM_GEMM_RING", "DM_GEMM_T96", "DM_GEMM_FWD_SPLIT")
+OFF = {"DM_GEMM_256": "0", "DM_GEMM_W4": "0", "DM_GEMM_W4_TN": "0", "DM_GEMM_RING": "0", "DM_GEMM_T96": "0"}
 FAMILIES = {          # name -> (environment, layouts it applies to)
     "128x128": ({**OFF, "DM_GEMM_FORCE_TILE": "128"}, (DM_NT, DM_NN, DM_TN)),
     "64x64": ({**OFF, "DM_GEMM_FORCE_TILE": "64"}, (DM_NT, DM_NN, DM_TN)),
     "256x256": ({**OFF, "DM_GEMM_256": "2"}, (DM_NT, DM_NN, DM_TN)),
     "ring": ({**OFF, "DM_GEMM_RING": "2"}, (DM_NT,)),
     "w4": ({**OFF, "DM_GEMM_W4": "2", "DM_GEMM_W4_TN": "2"}, (DM_NT, DM_NN, DM_TN)),
+    "t96": ({**OFF, "DM_GEMM_T96": "2"}, (DM_NT, DM_NN)),        # refuses fused epilogues other than bias / fp32 residual: those rows fall through
 }
 
 
