@@ -127,6 +127,14 @@ class FeatureIO:
         return scene.trace_labels(source, n_labels, device=self.device, **kw)
 
     @torch.no_grad()
+    def simplify_scene(self, source, n_labels: int, tolerance: float, **kw):
+        """The rings and arcs of `trace_scene`, simplified to `tolerance` pixels once per stretch of shared boundary, across the
+        scene's tiles: `scene.simplify_labels(source, n_labels, tolerance, device=self.device, **kw)`.  Returns (rag.Polygons,
+        rag.Arcs) in scene coordinates, bit for bit `rag.simplify` of the whole raster."""
+        from . import scene
+        return scene.simplify_labels(source, n_labels, tolerance, device=self.device, **kw)
+
+    @torch.no_grad()
     def _extract_local(self, tile, points_xy, inner, obj, region_features, batch_size):
         from .patches import point_batch_cols
         P = points_xy.shape[0]

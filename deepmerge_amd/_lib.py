@@ -97,6 +97,13 @@ class DmSceneVectorTrace(C.Structure):
                 ("W", C.c_int64), ("D", C.c_int32), ("R", C.c_int32), ("n_arcs", C.c_int32)]
 
 
+class DmSceneSimplifyRings(C.Structure):
+    _fields_ = [("xy", C.c_void_p), ("ring_ptr", C.c_void_p), ("vert_ring", C.c_void_p), ("node_row", C.c_void_p), ("node_col", C.c_void_p),
+                ("kept_row", C.c_void_p), ("status", C.c_void_p),
+                ("n_nodes", C.c_int64), ("n_kept", C.c_int64), ("scene_h", C.c_int64), ("scene_w", C.c_int64),
+                ("V", C.c_int32), ("R", C.c_int32)]
+
+
 class DmProfRow(C.Structure):
     _fields_ = [("name", C.c_char * 64), ("launches", C.c_int64), ("total_ms", C.c_double),
                 ("total_flops", C.c_double), ("total_bytes", C.c_double)]
@@ -207,6 +214,13 @@ SIGNATURES = {
     "dm_simplify_arc_emit": (_I, [_P, _P, _P, _I, _L, _L, _I, _I, _P, _P, _P]),
     "dm_simplify_ring_count": (_I, [_P, _P, _P, _I, _I, _I, _I, _P, _P, _P]),
     "dm_simplify_ring_emit": (_I, [_P, _P, _P, _P, _P, _I, _I, _L, _I, _I, _P, _P, _P, _P]),
+    "dm_scene_simplify_node_count": (_I, [_P, _I, _I, _I, _I, _I, _I, _L, _L, _L, _L, _P, _P, _P]),
+    "dm_scene_simplify_node_emit": (_I, [_P, _I, _I, _I, _I, _I, _I, _L, _L, _L, _L, _P, _I, _P, _P]),
+    "dm_scene_simplify_chains": (_I, [_P, _P, _I, _L, _L, _L, _I, _P, _P, _P]),
+    "dm_scene_simplify_arc_count": (_I, [_P, _P, _I, _L, _L, _L, _P, _P, _P]),
+    "dm_scene_simplify_arc_emit": (_I, [_P, _P, _P, _I, _L, _L, _L, _L, _P, _P, _P]),
+    "dm_scene_simplify_ring_count": (_I, [C.POINTER(DmSceneSimplifyRings), _P, _P]),
+    "dm_scene_simplify_ring_emit": (_I, [C.POINTER(DmSceneSimplifyRings), _P, _P, _L, _P, _P, _P]),
     "dm_gru_cell_fwd": (_I, [_P, _L, _P, _P, _P, _P, _I, _I, _P]),
     "dm_gru_cell_bwd": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _P]),
     "dm_prof_enable": (_I, [_I]),

@@ -12,30 +12,9 @@
 //   ring_count  per ring vertex: the kept corners on the unit steps from it to its successor (this inserts the nodes on a
 //               straight run)                                      ring_emit  the same walk, writing them; then area2 per new vertex
 // The scans between count and emit are the caller's (rag.simplify: torch.cumsum, as rag._trace and rag.rasterize do it).
-#include "dm_raster.h"
-#include "dm_simplify.h"
+#include "dm_simplify_arcs.h"                                     // an arc, the chains and arc kernels, the area: shared with dm_scene_simplify.hip
 
 namespace {
-
-constexpr int MAX_SIDE = DM_SIMPLIFY_MAX_SIDE;
-constexpr int WAVES = 4;                                         // wavefronts per workgroup of 256
-
-__device__ __forceinline__ u64 wave_max(u64 v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const u64 w = __shfl_xor(v, o, 64);
-    v = w > v ? w : v;
-  }
-  return v;
-}
-__device__ __forceinline__ u64 wave_min(u64 v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const u64 w = __shfl_xor(v, o, 64);
-    v = w < v ? w : v;
-  }
-  return v;
-}
 
 // ---- nodes ------------------------------------------------------------------------------------------------------------------
 // The strip of the tile walk is 16 corners of one corner row y: they look at pixels x0 - 1 .. x0 + n - 1 of pixel rows y - 1 and y.
@@ -57,215 +36,6 @@ __global__ __launch_bounds__(256) void simplify_nodes_kernel(const int *__restri
       const int x = g.x0 + i;
       const bool corner = (x == 0 || x == W) && (g.y == 0 || g.y == H);
       keep[g.base + i] = (degree >= 3 || corner) ? 2 : 0;
-    }
-  }
-}
-
-// ---- an arc as its wavefront sees it ---------------------------------------------------------------------------------------------
-// Stored vertices xy[first .. first + n).  A closed arc (first vertex == last) is the cyclic sequence of its first n - 1 vertices,
-// without the stored start when `skip`: logical position p in [0, 2 len) is stored vertex skip + (p mod len).
-struct Arc {
-  const int *xy;
-  long long first;
-  int n, len, skip;
-  bool closed;
-};
-
-__device__ __forceinline__ void vertex(const Arc &c, int p, int &x, int &y) {
-  const long long at = c.first + c.skip + (p >= c.len ? p - c.len : p);
-  x = c.xy[2 * at];
-  y = c.xy[2 * at + 1];
-}
-
-// Index of corner (x, y) in keep; -1 outside the raster.
-__device__ __forceinline__ int corner_index(int x, int y, int H, int W) {
-  return (x >= 0 && x <= W && y >= 0 && y <= H) ? y * (W + 1) + x : -1;      // (H+1)(W+1) <= 32769^2 < 2^31
-}
-
-// False for an arc the tables do not hold.  Wave-uniform.
-__device__ __forceinline__ bool arc_of(const int *__restrict__ xy, const long long *__restrict__ arc_ptr, int a, long long Va, Arc &c) {
-  const long long first = arc_ptr[a], end = arc_ptr[a + 1];
-  if (first < 0 || end > Va || end - first < 2 || end - first > INT_MAX) return false;
-  c.xy = xy;
-  c.first = first;
-  c.n = (int)(end - first);
-  c.closed = c.n >= 3 && xy[2 * first] == xy[2 * (end - 1)] && xy[2 * first + 1] == xy[2 * (end - 1) + 1];
-  c.len = c.closed ? c.n - 1 : c.n;
-  c.skip = 0;
-  return true;
-}
-
-// ---- chains -------------------------------------------------------------------------------------------------------------------------
-// Douglas-Peucker on the chain of logical positions [s, e] of arc c, by the whole wavefront.  The walk is depth first: the left
-// half of a split is taken at once, the right half is pushed.  Every entry on the stack is a segment with at least one interior
-// vertex, and the interiors of the entries and of the segment in hand are disjoint parts of the chain's interior, so the stack never
-// holds more entries than the chain has interior vertices: fewer than the arc has vertices, which is what `cap` is (the arc's
-// share of the workspace, one int64 per stored vertex).  Lane 0 alone reads and writes the stack; the others get it by a shuffle.
-__device__ __forceinline__ void split_chain(const Arc &c, int s, int e, int H, int W, u64 q2, unsigned char *__restrict__ keep,
-                                            long long *__restrict__ stack, int cap, int lane) {
-  int i = s, j = e, sp = 0;
-  bool have = e - s > 1;
-  while (have) {
-    int xi, yi, xj, yj;
-    vertex(c, i, xi, yi);
-    vertex(c, j, xj, yj);
-    const long long dx = xj - xi, dy = yj - yi;
-    const u64 len2 = (u64)(dx * dx + dy * dy);
-    u64 best = 0;                                                // d << 32 | ~(k - i): the greatest d, then the smallest k
-    for (int k = i + 1 + lane; k < j; k += 64) {
-      int x, y;
-      vertex(c, k, x, y);
-      const long long rx = x - xi, ry = y - yi;
-      const long long cr = dx * ry - dy * rx;
-      const u64 d = len2 == 0 ? (u64)(rx * rx + ry * ry) : (u64)(cr < 0 ? -cr : cr);
-      const u64 key = (d << 32) | (u64)(0xffffffffu - (unsigned)(k - i));
-      best = key > best ? key : best;
-    }
-    best = wave_max(best);
-    const int k = i + (int)(0xffffffffu - (unsigned)(best & 0xffffffffu));
-    bool left = false, right = false;
-    if (dm_simplify_exceeds(best >> 32, len2, q2)) {                          // wave-uniform; d = 0 never exceeds
-      if (lane == 0) {
-        int x, y;
-        vertex(c, k, x, y);
-        const int at = corner_index(x, y, H, W);
-        if (at >= 0) keep[at] = 1;
-      }
-      left = k - i > 1;
-      right = j - k > 1;
-    }
-    if (left && right) {
-      if (sp < cap) {
-        if (lane == 0) stack[sp] = ((long long)k << 32) | (long long)j;
-        ++sp;
-      }
-      j = k;
-    } else if (left) {
-      j = k;
-    } else if (right) {
-      i = k;
-    } else if (sp > 0) {
-      --sp;
-      long long top = lane == 0 ? stack[sp] : 0;
-      top = __shfl(top, 0, 64);
-      i = (int)(top >> 32);
-      j = (int)(top & 0xffffffffLL);
-    } else {
-      have = false;
-    }
-  }
-}
-
-__global__ __launch_bounds__(256) void simplify_chains_kernel(const int *__restrict__ xy, const long long *__restrict__ arc_ptr, int A, long long Va,
-                                                              int H, int W, u64 q2, unsigned char *__restrict__ keep, long long *__restrict__ stack) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  for (int a = blockIdx.x * WAVES + wave; a < A; a += gridDim.x * WAVES) {
-    Arc c;
-    if (!arc_of(xy, arc_ptr, a, Va, c)) continue;
-    if (c.closed) {                                              // a stored start inside a straight run is no vertex of the cyclic sequence
-      int x0, y0, x1, y1, x2, y2;
-      vertex(c, c.len - 1, x0, y0);
-      vertex(c, 0, x1, y1);
-      vertex(c, 1, x2, y2);
-      const int at = corner_index(x1, y1, H, W);
-      const bool node = at >= 0 && keep[at] == 2;
-      if (!node && (long long)(x1 - x0) * (y2 - y1) == (long long)(y1 - y0) * (x2 - x1)) { c.skip = 1; c.len -= 1; }
-    }
-    if (c.len < 2) continue;
-    // the node scan: the first cut, or the anchor (the vertex smallest in (y, x), which is its corner index); a vertex outside the
-    // raster refuses the arc.  The scan ends before the first write; the writes store 1 where keep was 0 and a cut is keep == 2,
-    // so the later searches for the next cut see the same nodes.
-    u64 first_node = ~0ULL, smallest = ~0ULL;
-    bool bad = false;
-    for (int p = lane; p < c.len; p += 64) {
-      int x, y;
-      vertex(c, p, x, y);
-      const int at = corner_index(x, y, H, W);
-      if (at < 0) { bad = true; continue; }
-      if (keep[at] == 2 && first_node == ~0ULL) first_node = (u64)p;
-      const u64 key = ((u64)at << 32) | (u64)p;
-      smallest = key < smallest ? key : smallest;
-    }
-    if (__any(bad)) continue;
-    first_node = wave_min(first_node);
-    int s = 0, end = c.len - 1;                                  // an open arc is cut at its two ends, which are nodes
-    if (c.closed) {
-      if (first_node != ~0ULL) {
-        s = (int)first_node;
-      } else {
-        smallest = wave_min(smallest);
-        s = (int)(smallest & 0xffffffffULL);
-        if (lane == 0) keep[(int)(smallest >> 32)] = 1;          // no node: the anchor is kept
-      }
-      end = s + c.len;
-    }
-    long long *const stk = stack + c.first;
-    while (s < end) {
-      int e = end;                                               // the next cut behind s
-      for (int base = s + 1; base < end; base += 64) {
-        const int p = base + lane;
-        bool node = false;
-        if (p < end) {
-          int x, y;
-          vertex(c, p, x, y);
-          node = keep[corner_index(x, y, H, W)] == 2;            // inside the raster: the scan above saw every vertex
-        }
-        const u64 m = __ballot(node);
-        if (m) { e = base + __ffsll((unsigned long long)m) - 1; break; }
-      }
-      split_chain(c, s, e, H, W, q2, keep, stk, c.n, lane);
-      s = e;
-    }
-  }
-}
-
-// ---- arcs out -----------------------------------------------------------------------------------------------------------------------
-// Kept vertices of an arc in stored order; a closed arc is walked without its repeated end and gets its first kept vertex again
-// at its end, which rotates away a stored start that is not kept.  OUT: write them at out[new_ptr[a] ..); else count[a].
-template <bool OUT>
-__global__ __launch_bounds__(256) void simplify_arc_kernel(const int *__restrict__ xy, const long long *__restrict__ arc_ptr, int A, long long Va, int H,
-                                                           int W, const unsigned char *__restrict__ keep, int *__restrict__ count,
-                                                           const long long *__restrict__ new_ptr, long long Vn, int *__restrict__ out) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  for (int a = blockIdx.x * WAVES + wave; a < A; a += gridDim.x * WAVES) {
-    Arc c;
-    if (!arc_of(xy, arc_ptr, a, Va, c)) {
-      if (!OUT && lane == 0) count[a] = 0;
-      continue;
-    }
-    long long to = 0, room = 0;
-    if (OUT) {
-      to = new_ptr[a];
-      room = new_ptr[a + 1] - to;
-      if (to < 0 || room < 0 || to + room > Vn) continue;
-    }
-    int total = 0, fx = 0, fy = 0;
-    for (int base = 0; base < c.len; base += 64) {
-      const int p = base + lane;
-      int x = 0, y = 0;
-      bool kept = false;
-      if (p < c.len) {
-        vertex(c, p, x, y);
-        const int at = corner_index(x, y, H, W);
-        kept = at >= 0 && keep[at] != 0;
-      }
-      const u64 m = __ballot(kept);
-      if (OUT) {
-        const int rank = total + __popcll(m & ((1ULL << lane) - 1));
-        if (kept && rank < room) { out[2 * (to + rank)] = x; out[2 * (to + rank) + 1] = y; }
-        if (total == 0 && m) {                                    // the first kept vertex, for the closing repeat
-          const int src = __ffsll((unsigned long long)m) - 1;
-          fx = __shfl(x, src, 64);
-          fy = __shfl(y, src, 64);
-        }
-      }
-      total += __popcll(m);
-    }
-    const bool repeat = c.closed && total > 0;
-    if (OUT) {
-      if (repeat && lane == 0 && total < room) { out[2 * (to + total)] = fx; out[2 * (to + total) + 1] = fy; }
-    } else if (lane == 0) {
-      count[a] = total + repeat;
     }
   }
 }
@@ -319,30 +89,9 @@ __global__ void simplify_ring_kernel(const int *__restrict__ xy, const long long
   }
 }
 
-__global__ void simplify_area_init_kernel(long long *__restrict__ area2, int R) {
-  for (int r = blockIdx.x * blockDim.x + threadIdx.x; r < R; r += gridDim.x * blockDim.x) area2[r] = 0;
-}
-
-// The shoelace term of every new vertex and its successor within its ring (found by an upper-bound search in new_ring_ptr), added
-// with integer atomics: the sum does not depend on the order of arrival.
-__global__ void simplify_area_kernel(const int *__restrict__ out, const long long *__restrict__ new_ring_ptr, int R, long long Vn,
-                                     long long *__restrict__ area2) {
-  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < Vn; i += (long long)gridDim.x * blockDim.x) {
-    int lo = 0, hi = R;                                          // the last r with new_ring_ptr[r] <= i
-    while (hi - lo > 1) {
-      const int mid = lo + ((hi - lo) >> 1);
-      if (new_ring_ptr[mid] <= i) lo = mid; else hi = mid;
-    }
-    const long long first = new_ring_ptr[lo], end = new_ring_ptr[lo + 1];
-    if (i < first || i >= end || end > Vn) continue;
-    const long long n = i + 1 == end ? first : i + 1;
-    const long long term = (long long)out[2 * i] * out[2 * n + 1] - (long long)out[2 * n] * out[2 * i + 1];
-    if (term) atomic_add64(area2 + lo, term);
-  }
-}
+typedef CornerKeep<const unsigned char> DenseRead;
 
 inline bool side_ok(int H, int W) { return H > 0 && W > 0 && H <= MAX_SIDE && W <= MAX_SIDE; }
-inline int wave_grid(int items) { return grid_for((long long)items * 64); }
 
 }  // namespace
 
@@ -362,8 +111,8 @@ extern "C" int dm_simplify_chains(const int32_t *arc_xy, const int64_t *arc_ptr,
   DM_REQUIRE(side_ok(H, W) && A > 0 && Va >= 2 && Va <= (1LL << 30), DM_ERR_BAD_SHAPE,
              "dm_simplify_chains: bad sizes (H=%d W=%d A=%d Va=%lld; " SIDES ", A >= 1, 2 <= Va <= 2^30)", H, W, A, (long long)Va);
   DM_REQUIRE(q >= 0 && q <= DM_SIMPLIFY_MAX_Q, DM_ERR_BAD_SHAPE, "dm_simplify_chains: bad tolerance (q=%d; need 0 <= q <= 2^20)", q);
-  hipLaunchKernelGGL(simplify_chains_kernel, dim3(wave_grid(A)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), arc_xy,
-                     (const long long *)arc_ptr, A, (long long)Va, H, W, (u64)q * (u64)q, keep, (long long *)stack);
+  hipLaunchKernelGGL(simplify_chains_kernel<CornerKeep<unsigned char>>, dim3(wave_grid(A)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), arc_xy,
+                     (const long long *)arc_ptr, A, (long long)Va, CornerKeep<unsigned char>{keep, H, W}, (u64)q * (u64)q, (long long *)stack);
   DM_LAUNCH_CHECK("dm_simplify_chains");
   return DM_OK;
 }
@@ -378,8 +127,8 @@ static int simplify_arcs_ok(const char *what, const void *a, const void *b, cons
 extern "C" int dm_simplify_arc_count(const int32_t *arc_xy, const int64_t *arc_ptr, int32_t A, int64_t Va, int32_t H, int32_t W, const uint8_t *keep,
                                      int32_t *count, void *stream) {
   if (int rc = simplify_arcs_ok("dm_simplify_arc_count", arc_xy, arc_ptr, keep, count, A, Va, H, W)) return rc;
-  hipLaunchKernelGGL(simplify_arc_kernel<false>, dim3(wave_grid(A)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), arc_xy,
-                     (const long long *)arc_ptr, A, (long long)Va, H, W, keep, count, (const long long *)nullptr, 0LL, (int *)nullptr);
+  hipLaunchKernelGGL((simplify_arc_kernel<false, DenseRead>), dim3(wave_grid(A)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), arc_xy,
+                     (const long long *)arc_ptr, A, (long long)Va, DenseRead{keep, H, W}, count, (const long long *)nullptr, 0LL, (int *)nullptr);
   DM_LAUNCH_CHECK("dm_simplify_arc_count");
   return DM_OK;
 }
@@ -390,8 +139,8 @@ extern "C" int dm_simplify_arc_emit(const int32_t *arc_xy, const int64_t *arc_pt
   DM_REQUIRE(new_ptr, DM_ERR_BAD_SHAPE, "dm_simplify_arc_emit: null pointer");
   DM_REQUIRE(Vn >= 1 && Vn <= Va, DM_ERR_BAD_SHAPE, "dm_simplify_arc_emit: bad sizes (Vn=%lld Va=%lld; need 1 <= Vn <= Va)", (long long)Vn,
              (long long)Va);
-  hipLaunchKernelGGL(simplify_arc_kernel<true>, dim3(wave_grid(A)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), arc_xy,
-                     (const long long *)arc_ptr, A, (long long)Va, H, W, keep, (int *)nullptr, (const long long *)new_ptr, (long long)Vn, out_xy);
+  hipLaunchKernelGGL((simplify_arc_kernel<true, DenseRead>), dim3(wave_grid(A)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), arc_xy,
+                     (const long long *)arc_ptr, A, (long long)Va, DenseRead{keep, H, W}, (int *)nullptr, (const long long *)new_ptr, (long long)Vn, out_xy);
   DM_LAUNCH_CHECK("dm_simplify_arc_emit");
   return DM_OK;
 }

@@ -1145,6 +1145,17 @@ MAX_SIMPLIFY_SIDE = 1 << 15       # DM_SIMPLIFY_MAX_SIDE: every cross product of
 MAX_SIMPLIFY_Q = 1 << 20          # DM_SIMPLIFY_MAX_Q: the tolerance in 1/256 pixel
 
 
+def _quantise_tolerance(tolerance: float) -> int:
+    """q = floor(256 t + 0.5) of a tolerance in pixels: finite, >= 0, at most 4096 (rag.simplify, scene.simplify_labels)."""
+    t = float(tolerance)
+    if not math.isfinite(t) or t < 0:
+        raise ValueError(f"tolerance must be finite and >= 0, got {tolerance}")
+    q = int(math.floor(t * SUBPIXEL + 0.5))
+    if q > MAX_SIMPLIFY_Q:
+        raise ValueError(f"tolerance must be at most {MAX_SIMPLIFY_Q // SUBPIXEL} pixels, got {tolerance}")
+    return q
+
+
 def _simplify(labels: torch.Tensor, n_labels: int, tolerance: float, stats: Optional[dict] = None) -> Tuple[Polygons, Arcs, torch.Tensor]:
     """`simplify` and the keep flags uint8 [(H+1)(W+1)] (2 node, 1 kept chain vertex, 0 otherwise) it decided by."""
     _need_cuda(labels)
@@ -1153,12 +1164,7 @@ def _simplify(labels: torch.Tensor, n_labels: int, tolerance: float, stats: Opti
     H, W = labels.shape
     if H > MAX_SIMPLIFY_SIDE or W > MAX_SIMPLIFY_SIDE:
         raise ValueError(f"simplify takes rasters of at most 32768 x 32768 pixels, got {H} x {W}")
-    t = float(tolerance)
-    if not math.isfinite(t) or t < 0:
-        raise ValueError(f"tolerance must be finite and >= 0, got {tolerance}")
-    q = int(math.floor(t * SUBPIXEL + 0.5))
-    if q > MAX_SIMPLIFY_Q:
-        raise ValueError(f"tolerance must be at most {MAX_SIMPLIFY_Q // SUBPIXEL} pixels, got {tolerance}")
+    q = _quantise_tolerance(tolerance)
     trace_stats = None if stats is None else {}
     polys, arcs = _trace(labels, n_labels, trace_stats)
     labels = labels.contiguous()

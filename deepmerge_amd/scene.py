@@ -21,8 +21,12 @@ Rings and arcs.  `trace_labels` traces a scene's label raster
 `SceneResult.trace` -- into the rings and arcs `rag._trace` gives on the whole raster, array for array and bit for bit, whatever
 the tile size: every tile is read with one pixel of its neighbours' labels, its core's darts get scene-wide 64-bit ids
 (csrc/dm_scene_vector.hip), the tiles' tables are joined by one sort, and the jumping rounds run once over the scene's table.
-`SceneResult.save_shapefiles` writes them as `polygons.shp` and `lines.shp`.  Out of scope: `rag.simplify` on a scene;
-`PointsGCS.shp` for a scene; overlapping the next tile's read with compute.
+`SceneResult.save_shapefiles` writes them as `polygons.shp` and `lines.shp`.
+
+Simplified rings and arcs.  `simplify_labels` is `rag.simplify` on a scene, bit for bit: the same tile stream
+also yields the scene's nodes (csrc/dm_scene_simplify.hip), and the keep flag per pixel corner becomes two sorted node lists, one
+byte per stored arc vertex and the sorted kept set.  `SceneResult.simplified` and `save_shapefiles(..., tolerance=)` go through it.
+Out of scope: `PointsGCS.shp` for a scene; overlapping the next tile's read with compute; detecting chains that cross.
 
 Memory.  The scene's pixels are never on the device as a whole: one halo window at a time.  What is resident for the whole scene
 is per superpixel and per sample point: the statistics, the graph, the points and the [P,100] feature rows.  The scene-wide
@@ -32,6 +36,7 @@ for the encode, because the designed features the encoder takes need the statist
 """
 from __future__ import annotations
 
+import ctypes
 import time
 from dataclasses import dataclass
 from typing import Callable, Dict, List, Optional, Tuple
@@ -286,13 +291,24 @@ class SceneResult:
     def boundary_arcs(self, merged=None, tile=None) -> "rag.Arcs":
         return self.trace(merged, tile)[1]
 
-    def save_shapefiles(self, folder: str, geotransform=None, merged=None, tile=None) -> Tuple[str, str]:
+    def simplified(self, tolerance: float, merged=None, tile=None, stats: Optional[dict] = None) -> Tuple["rag.Polygons", "rag.Arcs"]:
+        """The rings and arcs of `trace`, simplified to `tolerance` pixels once per stretch of shared boundary:
+        `simplify_labels` of the merged raster, `Arcs.edge` attached as `trace` does.  Equals `MergeResult.simplified` on the
+        assembled raster."""
+        merged = self.write_merged() if merged is None else merged
+        C = int(self.result.rep.numel())
+        polys, arcs = simplify_labels(merged, C, tolerance, tile=self._tile() if tile is None else tile, stats=stats, device=self.edges.device)
+        return polys, rag._attach_edges(arcs, C, self.result.edges)
+
+    def save_shapefiles(self, folder: str, geotransform=None, merged=None, tile=None, tolerance: Optional[float] = None) -> Tuple[str, str]:
         """Write the merged regions as the two layers of `FeatureIO.save_shapefiles` that a scene has: `polygons.shp` (one record
         per merged region: the 15 designed fields of `designed_features(result.stats)` and `PointID` from `result.ptr / idx`) and
         `lines.shp` (one record per boundary arc: LEFT_FID, RIGHT_FID, simi = `result.simi` of the arc's edge, 0.0 on the scene's
-        frame), through the same writer.  No `PointsGCS.shp`: out of scope for a scene.  Returns the two paths."""
+        frame), through the same writer.  tolerance: None writes the traced pixel staircase; a number writes the rings and arcs of
+        `simplified(tolerance)`, so the two layers share every vertex.  No `PointsGCS.shp`: out of scope for a scene.  Returns the
+        two paths."""
         from .ExtractFeatures import write_polygon_and_line_layers
-        polys, arcs = self.trace(merged, tile)
+        polys, arcs = self.trace(merged, tile) if tolerance is None else self.simplified(tolerance, merged, tile)
         r = self.result
         return tuple(write_polygon_and_line_layers(folder, polys, arcs, int(r.rep.numel()), r.ptr, r.idx, rag.designed_features(r.stats),
                                                    edges=r.edges, simi=r.simi, geotransform=geotransform))
@@ -434,6 +450,50 @@ def _join(ids: torch.Tensor, succ: torch.Tensor, lab: torch.Tensor, other: torch
     return dart, nxt.to(torch.int32), lab[order], other[order], flags, (slot << 32) | slot
 
 
+def _windows(source, H: int, W: int, S: int, tiles: List[Core], dev, clock: _Clock):
+    """The tile stream of `trace_labels` and `simplify_labels`: per tile (i, window int32 on the device, the core's box in window
+    coordinates, the window's origin (oy, ox) in the scene), the window being the core and one pixel of apron, clipped to the scene,
+    with its ids checked."""
+    for i, core in enumerate(tiles):
+        y0, y1, x0, x1 = core
+        wy0, wy1, wx0, wx1 = box = window_of(core, H, W, 1)
+        window = _read(source, box, torch.int32, 2, dev)
+        clock.lap("read + copy")
+        lo, hi = (int(v) for v in torch.aminmax(window))
+        if lo < 0 or hi >= S:
+            raise ValueError(f"labels must be in 0..n_labels-1 = 0..{S - 1}: the window of tile {i} (rows {wy0}..{wy1 - 1}, columns "
+                             f"{wx0}..{wx1 - 1}) holds {lo}..{hi}")
+        yield i, window, (y0 - wy0, y1 - wy0, x0 - wx0, x1 - wx0), (wy0, wx0)
+
+
+def _scene_table(source, H: int, W: int, S: int, tiles: List[Core], dev, clock: _Clock, nodes: Optional[list] = None):
+    """One stream of the scene's windows into the joined dart table `rag._trace_table` takes.  nodes: a list that receives every
+    tile's node records (`_tile_nodes`) from the same windows, so that the scene is read once."""
+    parts, total, n_nodes = [], 0, 0
+    for i, window, box, origin in _windows(source, H, W, S, tiles, dev, clock):
+        got = _tile_darts(window, box, origin, H, W)
+        if got is not None:
+            total += int(got[0].numel())
+            _check_darts(total, i, len(tiles))
+            parts.append(got)
+        if nodes is not None:
+            own = _tile_nodes(window, box, origin, H, W)
+            if own is not None:
+                n_nodes += int(own.numel())
+                _check_nodes(n_nodes, i, len(tiles))
+                nodes.append(own)
+        clock.lap("per-tile passes")
+    ids, succ, lab, other, sflags = (torch.cat([p[k] for p in parts]) for k in range(5))
+    del parts
+    table = _join(ids, succ, lab, other, sflags)
+    del ids, succ, lab, other, sflags
+    clock.lap("sort + join")
+    return table
+
+
+_TRACE_STAGE = {"head rounds": "rounds", "rank rounds": "rounds"}
+
+
 def trace_labels(source, n_labels: int, tile=4096, stats: Optional[dict] = None, device="cuda:0") -> Tuple["rag.Polygons", "rag.Arcs"]:
     """A scene's label raster traced into polygon rings and boundary arcs across tile seams: array for array and bit for bit what
     `rag._trace(L, n_labels)` returns on the whole raster L, in scene coordinates, whatever the tile size.
@@ -448,30 +508,148 @@ def trace_labels(source, n_labels: int, tile=4096, stats: Optional[dict] = None,
     H, W, S, tiles = _check_trace(source, n_labels, tile)
     dev = torch.device(device)
     clock = _Clock(None if stats is None else stats.setdefault("stage_s", {}), dev)
-    parts, total = [], 0
-    for i, core in enumerate(tiles):
-        y0, y1, x0, x1 = core
-        wy0, wy1, wx0, wx1 = box = window_of(core, H, W, 1)
-        window = _read(source, box, torch.int32, 2, dev)
-        clock.lap("read + copy")
-        lo, hi = (int(v) for v in torch.aminmax(window))
-        if lo < 0 or hi >= S:
-            raise ValueError(f"labels must be in 0..n_labels-1 = 0..{S - 1}: the window of tile {i} (rows {wy0}..{wy1 - 1}, columns "
-                             f"{wx0}..{wx1 - 1}) holds {lo}..{hi}")
-        got = _tile_darts(window, (y0 - wy0, y1 - wy0, x0 - wx0, x1 - wx0), (wy0, wx0), H, W)
-        if got is not None:
-            total += int(got[0].numel())
-            _check_darts(total, i, len(tiles))
-            parts.append(got)
-        clock.lap("per-tile passes")
-    ids, succ, lab, other, sflags = (torch.cat([p[k] for p in parts]) for k in range(5))
-    del parts
-    table = _join(ids, succ, lab, other, sflags)
-    del ids, succ, lab, other, sflags
-    clock.lap("sort + join")
-    stage_of = {"head rounds": "rounds", "rank rounds": "rounds"}
-    polys, arcs, info = rag._trace_table(*table, W, S, mark=lambda stage: clock.lap(stage_of.get(stage, "emit")), wide=True)
+    table = _scene_table(source, H, W, S, tiles, dev, clock)
+    polys, arcs, info = rag._trace_table(*table, W, S, mark=lambda stage: clock.lap(_TRACE_STAGE.get(stage, "emit")), wide=True)
     if stats is not None:
         stats.update(D=info["D"], rings=info["R"], arcs=info["A"], vertices=info["V"], arc_vertices=int(info["arc_xy"].shape[0]),
                      head_rounds=info["head_rounds"], rank_rounds=info["rank_rounds"], tiles=len(tiles))
     return polys, arcs
+
+
+# ---- shared-boundary Douglas-Peucker across tile seams (csrc/dm_scene_simplify.hip) -------------------------------
+MAX_NODES = 1 << 31                   # positions in the sorted node lists are counted in int32 ranges per run
+MAX_ARC_EXTENT = rag.MAX_SIMPLIFY_SIDE        # DM_SIMPLIFY_MAX_SIDE: an arc's bounding box, so that every |cross| stays below 2^31
+
+
+def _check_nodes(total: int, i: int, n_tiles: int):
+    if total >= MAX_NODES:
+        raise ValueError(f"the scene has 2^31 nodes or more ({total} after tile {i} of {n_tiles}): simplify a coarser partition or the "
+                         f"scene in parts")
+
+
+def _tile_nodes(window: torch.Tensor, box: Core, origin: Tuple[int, int], H: int, W: int) -> Optional[torch.Tensor]:
+    """The node records of one tile (dm_scene_simplify_node_count / node_emit): int64 [N], the scene corner ids y (W + 1) + x of the
+    nodes among the corners the core owns, in no particular order; None when it owns none.  Arguments as `_tile_darts` takes them."""
+    rag._need_cuda(window)
+    lib, dev, i32 = _lib.lib(), window.device, torch.int32
+    window = window.contiguous()
+    wh, ww = window.shape
+    blocks = ((wh + 64) // 64) * ((ww + 64) // 64)                # 64 x 64 blocks of the (wh + 1) x (ww + 1) corners
+    tile_off, meta = torch.empty(blocks + 1, dtype=i32, device=dev), torch.empty(1, dtype=i32, device=dev)
+    place = (window.data_ptr(), wh, ww, *box, int(origin[0]), int(origin[1]), H, W)
+    check(lib.dm_scene_simplify_node_count(*place, tile_off.data_ptr(), meta.data_ptr(), _stream()), "dm_scene_simplify_node_count")
+    N = int(meta[0])
+    if N == 0:
+        return None
+    node = torch.empty(N, dtype=torch.int64, device=dev)
+    check(lib.dm_scene_simplify_node_emit(*place, tile_off.data_ptr(), N, node.data_ptr(), _stream()), "dm_scene_simplify_node_emit")
+    return node
+
+
+def _check_arc_extents(arcs: "rag.Arcs"):
+    """Every arc's bounding box at most 32768 on each side (one reduction, one readback): within a chain the rule's cross products
+    are taken from the chain's first vertex and must stay below 2^31, which `rag.simplify` gets from H, W <= 32768."""
+    A, Va, dev = arcs.left.numel(), arcs.xy.shape[0], arcs.xy.device
+    arc_of = (torch.searchsorted(arcs.arc_ptr, torch.arange(Va, dtype=torch.int64, device=dev), right=True) - 1).clamp(0, A - 1)
+    index = arc_of[:, None].expand(-1, 2)
+    lo = torch.full((A, 2), (1 << 31) - 1, dtype=torch.int32, device=dev).scatter_reduce_(0, index, arcs.xy, "amin")
+    hi = torch.full((A, 2), -(1 << 31), dtype=torch.int32, device=dev).scatter_reduce_(0, index, arcs.xy, "amax")
+    extent = hi.long() - lo.long()
+    worst = torch.argmax(extent.amax(1))
+    w, h, left, right, a = torch.stack((extent[worst, 0], extent[worst, 1], arcs.left[worst].long(), arcs.right[worst].long(), worst)).tolist()
+    if max(w, h) > MAX_ARC_EXTENT:
+        raise ValueError(f"arc {a} between (left, right) = ({left}, {right}) spans {w} x {h} pixels: an arc's bounding box must be at most "
+                         f"{MAX_ARC_EXTENT} on each side (the rule's cross products stay below 2^31); simplify the scene in parts")
+
+
+def _simplify_tables(polys: "rag.Polygons", arcs: "rag.Arcs", node_row: torch.Tensor, H: int, W: int, q: int, mark=lambda stage: None,
+                     stats: Optional[dict] = None) -> Tuple["rag.Polygons", "rag.Arcs", torch.Tensor]:
+    """From a scene's traced rings and arcs and its nodes (node_row int64, the corner ids y (W + 1) + x, ascending) to the simplified
+    rings and arcs and `arc_keep`: the sparse form of `rag._simplify`.  Table arithmetic in torch between the
+    kernels: node_col, arc_keep's 2s, the kept set, the scans.  Readbacks: the arc extents, the kept set's size, the totals."""
+    lib, dev, i32, i64 = _lib.lib(), arcs.xy.device, torch.int32, torch.int64
+    rag._need_cuda(arcs.xy)
+    new = lambda n, dt: torch.empty(n, dtype=dt, device=dev)
+    A, Va = arcs.left.numel(), arcs.xy.shape[0]
+    R, V = polys.ring_label.numel(), polys.xy.shape[0]
+    Nn = int(node_row.numel())
+    if max(H, W) > MAX_ARC_EXTENT:                               # within 32768 x 32768 no arc can be wider
+        _check_arc_extents(arcs)
+    ny = torch.div(node_row, W + 1, rounding_mode="floor")
+    node_col = torch.sort((node_row - ny * (W + 1)) * (H + 1) + ny).values
+    ids = arcs.xy[:, 1].long() * (W + 1) + arcs.xy[:, 0].long()
+    at = torch.searchsorted(node_row, ids).clamp(max=Nn - 1)
+    arc_keep = ((node_row[at] == ids).to(torch.uint8) * 2).contiguous()
+    del at, ny
+    mark("node lists + arc_keep")
+    stack = new(Va, i64)                                         # one entry per arc vertex: the bound of the depth-first walk
+    check(lib.dm_scene_simplify_chains(arcs.xy.data_ptr(), arcs.arc_ptr.data_ptr(), A, Va, H, W, q, arc_keep.data_ptr(), stack.data_ptr(), _stream()),
+          "dm_scene_simplify_chains")
+    del stack
+    mark("chains")
+    kept_row = torch.sort(torch.cat((node_row, ids[arc_keep == 1]))).values
+    del ids
+    mark("kept set")
+    arc_count, ring_count, status = new(A, i32), new(V, i32), new(1, i32)
+    check(lib.dm_scene_simplify_arc_count(arcs.xy.data_ptr(), arcs.arc_ptr.data_ptr(), A, Va, H, W, arc_keep.data_ptr(), arc_count.data_ptr(),
+                                          _stream()), "dm_scene_simplify_arc_count")
+    mark("arc_count")
+    vert_ring = (torch.searchsorted(polys.ring_ptr, torch.arange(V, dtype=i64, device=dev), right=True) - 1).to(i32)
+    t = _lib.DmSceneSimplifyRings()
+    for name, tensor in (("xy", polys.xy), ("ring_ptr", polys.ring_ptr), ("vert_ring", vert_ring), ("node_row", node_row), ("node_col", node_col),
+                         ("kept_row", kept_row), ("status", status)):
+        setattr(t, name, tensor.data_ptr())
+    t.n_nodes, t.n_kept, t.scene_h, t.scene_w, t.V, t.R = Nn, int(kept_row.numel()), H, W, V, R
+    check(lib.dm_scene_simplify_ring_count(ctypes.byref(t), ring_count.data_ptr(), _stream()), "dm_scene_simplify_ring_count")
+    mark("ring_count")
+    arc_ptr, scan = torch.zeros(A + 1, dtype=i64, device=dev), torch.zeros(V + 1, dtype=i64, device=dev)
+    torch.cumsum(arc_count, 0, dtype=i64, out=arc_ptr[1:])
+    torch.cumsum(ring_count, 0, dtype=i64, out=scan[1:])
+    ring_ptr = scan[polys.ring_ptr]
+    Van, Vn, unsorted = (int(v) for v in torch.stack((arc_ptr[-1], scan[-1], status[0].long())).tolist())       # the vertex totals
+    if unsorted:
+        raise RuntimeError("dm_scene_simplify_ring_count: the node lists are not sorted")
+    mark("scans + readback of the totals")
+    arc_xy, xy, area2 = new((Van, 2), i32), new((Vn, 2), i32), new(R, i64)
+    check(lib.dm_scene_simplify_arc_emit(arcs.xy.data_ptr(), arcs.arc_ptr.data_ptr(), arc_ptr.data_ptr(), A, Va, Van, H, W, arc_keep.data_ptr(),
+                                         arc_xy.data_ptr(), _stream()), "dm_scene_simplify_arc_emit")
+    mark("arc_emit")
+    check(lib.dm_scene_simplify_ring_emit(ctypes.byref(t), scan.data_ptr(), ring_ptr.data_ptr(), Vn, xy.data_ptr(), area2.data_ptr(), _stream()),
+          "dm_scene_simplify_ring_emit")
+    mark("ring_emit + area")
+    out_polys = rag.Polygons(region_ptr=polys.region_ptr, ring_ptr=ring_ptr, xy=xy, ring_label=polys.ring_label, ring_area2=area2)
+    out_arcs = rag.Arcs(arc_ptr=arc_ptr, xy=arc_xy, left=arcs.left, right=arcs.right)
+    if stats is not None:
+        stats.update(q=q, nodes=Nn, kept=int(kept_row.numel()), arcs=A, rings=R, arc_vertices=Va, vertices=V, kept_arc_vertices=Van,
+                     kept_vertices=Vn, longest_arc=int((arcs.arc_ptr[1:] - arcs.arc_ptr[:-1]).max()))
+    return out_polys, out_arcs, arc_keep
+
+
+def simplify_labels(source, n_labels: int, tolerance: float, tile=4096, stats: Optional[dict] = None,
+                    device="cuda:0") -> Tuple["rag.Polygons", "rag.Arcs"]:
+    """A scene's label raster traced and simplified across tile seams: array for array and bit for bit what
+    `rag.simplify(L, n_labels, tolerance)` returns on the whole raster L (where `rag.simplify` takes it), in scene coordinates,
+    whatever the tile size.  Shared boundaries stay shared and nodes stay put, across seams as within a tile.
+
+    source, n_labels, tile, device: as `trace_labels` takes them; the scene is read once, the same windows yield the darts and the
+    nodes.  tolerance: pixels, finite, >= 0, at most 4096, quantised to 1/256 pixel.  stats: a dict that receives the sizes and the
+    seconds per stage (synchronises at stage boundaries).  Limits, each a ValueError: every limit of `trace_labels`; the tolerance
+    (checked before any device work); fewer than 2^31 nodes; every arc's bounding box at most 32768 on each side.
+    Memory: what `trace_labels` holds, plus 8 bytes per node twice, 9 bytes per arc vertex (keep byte, depth-first stack) and 8 bytes
+    per kept vertex; no raster of corners."""
+    q = rag._quantise_tolerance(tolerance)
+    source = _as_source(source)
+    H, W, S, tiles = _check_trace(source, n_labels, tile)
+    dev = torch.device(device)
+    clock = _Clock(None if stats is None else stats.setdefault("stage_s", {}), dev)
+    nodes: List[torch.Tensor] = []
+    table = _scene_table(source, H, W, S, tiles, dev, clock, nodes)
+    polys, arcs, info = rag._trace_table(*table, W, S, mark=lambda stage: clock.lap(_TRACE_STAGE.get(stage, "emit")), wide=True)
+    del table
+    node_row = torch.sort(torch.cat(nodes)).values
+    del nodes
+    sizes = None if stats is None else {}
+    out_polys, out_arcs, _ = _simplify_tables(polys, arcs, node_row, H, W, q, mark=lambda stage: clock.lap("simplify: " + stage), stats=sizes)
+    if stats is not None:
+        stats.update(sizes, D=info["D"], head_rounds=info["head_rounds"], rank_rounds=info["rank_rounds"], tiles=len(tiles))
+    return out_polys, out_arcs

@@ -938,6 +938,71 @@ int dm_simplify_ring_emit(const int32_t *xy, const int64_t *ring_ptr, const int3
                           int32_t V, int32_t R, int64_t Vn, int32_t H, int32_t W, const uint8_t *keep, int32_t *out_xy, int64_t *area2,
                           void *stream);
 
+/* ---- shared-boundary Douglas-Peucker on a scene's rings and arcs across tile seams (additive in ABI 7;
+ * csrc/dm_scene_simplify.hip, DESIGN.md 3.5.11, scene.simplify_labels / SceneResult.simplified) -----------------------------------
+ * The rule above, unchanged, for a raster L [scene_h, scene_w] that is read tile by tile and never resident: the result is, array
+ * for array and bit for bit, what the one-raster calls give on the whole of L, whatever the tile size.  No new geometry rule, only
+ * a sparse form of `keep`, which as a raster would take (scene_h + 1)(scene_w + 1) bytes and 64-bit corner ids.  It rests on three
+ * facts about the rule (asserted in tests/test_scene_simplify_host.py):
+ *   1. a corner with keep == 1 is a stored vertex of exactly one arc, and occurs there once among the arc's positions below len;
+ *   2. a node that lies on an arc is a stored vertex of that arc: the chain pass needs keep only at arc vertices;
+ *   3. on the straight run of a ring from vertex v to its successor the kept corners are v itself, if kept, and exactly the nodes
+ *      strictly inside the run (the T-junctions).
+ * The sparse form: scene corner id = y (scene_w + 1) + x, int64.
+ *   node_row int64 [n_nodes]: the ids of the scene's nodes, ascending; node_col int64 [n_nodes]: x (scene_h + 1) + y of the same
+ *     nodes, ascending.  A scene has at least its four corners and fewer than 2^31 nodes.
+ *   arc_keep uint8 [Va]: one byte per stored arc vertex, 2 where the vertex's corner is in node_row, else 0 (the caller's); the
+ *     chain pass writes its 1s by position, arc_keep[first + skip + p mod len].
+ *   kept_row int64 [n_kept]: ascending, the ids of the nodes and of the arc vertices with arc_keep == 1.  A ring vertex is kept iff
+ *     it is found there; the nodes inside a run are one range of node_row (horizontal run) or node_col (vertical run).
+ * Arithmetic limit: the rule's products need |cross| < 2^31 within a chain.  Differences are taken from v[i], so this is a limit
+ * per arc: its bounding box at most DM_SIMPLIFY_MAX_SIDE on each side.  An arc beyond it is left alone by the chain pass, as is an
+ * arc with a vertex outside the scene; the caller checks the extents and raises (scene.simplify_labels).
+ * Every entry point validates before any launch, launches on `stream`, never synchronises and never allocates.
+ *
+ * dm_scene_simplify_node_count / node_emit: labels int32 [H,W] = the window dm_scene_vector_count reads, the core = [cy0,cy1) x
+ *   [cx0,cx1) in window coordinates, the window's first pixel at (ox, oy) of the scene.  The core may touch a window edge only where
+ *   that is the scene's edge.  Scene corner (X, Y), 0 <= X <= scene_w, 0 <= Y <= scene_h, belongs to the core that holds pixel
+ *   (min(X, scene_w - 1), min(Y, scene_h - 1)).  The node rule is dm_simplify_nodes's: at least three of the four unit edges are
+ *   boundary edges, or a scene corner; outside the SCENE is -1.  tile_off int32 [blocks+1], blocks = ceil((H+1)/64) ceil((W+1)/64):
+ *   the exclusive scan of the owned nodes per 64x64 block of window corners, tile_off[blocks] = n_nodes[0] = N.  node_emit writes
+ *   node int64 [N], the scene corner ids, in no particular order (the caller concatenates the tiles and sorts).
+ * dm_scene_simplify_chains / arc_count / arc_emit: dm_simplify_chains / arc_count / arc_emit with arc_keep in the place of keep;
+ *   2 <= Va < 2^31.  The anchor of a closed arc without a node is the vertex smallest in (y, x), by a wave minimum of the 64-bit
+ *   corner id and then of the position among the lanes that hold it.
+ * dm_scene_simplify_ring_count: one thread per ring vertex; count int32 [V] = (v kept) + the nodes strictly inside the run to its
+ *   successor: three binary searches, O(log n_nodes) whatever the run's length.  status int32 [1] is cleared, then set to 1 where a
+ *   list shows itself unsorted (a range that ends before it begins or holds more nodes than the run has inner corners).  No index
+ *   is followed unchecked: every search stays inside its list, sorted or not.  The detection is best effort, not a test of
+ *   sortedness: the host cannot see a device list without a synchronisation, so the entry returns DM_OK and a swap that leaves
+ *   every searched range consistent goes unseen.  The caller sorts the lists (scene.simplify_labels does).
+ * dm_scene_simplify_ring_emit: scan / new_ring_ptr / Vn / out_xy / area2 as dm_simplify_ring_emit takes them; the nodes of a run
+ *   are emitted in the walk's direction; an entry outside its run's id range sets status (never cleared here) and ends the run.
+ *   scene.simplify_labels reads status once, after ring_count; what ring_emit adds is for a direct caller of the entries to read.
+ *   A shoelace term is below 2^63 and area2 at most 2 scene_h scene_w <= 2^61. */
+typedef struct DmSceneSimplifyRings {
+  const int32_t *xy;              /* [V,2] ring vertices in scene coordinates */
+  const int64_t *ring_ptr;        /* [R+1] */
+  const int32_t *vert_ring;       /* [V] */
+  const int64_t *node_row, *node_col, *kept_row;
+  int32_t *status;                /* [1] */
+  int64_t n_nodes, n_kept, scene_h, scene_w;
+  int32_t V, R;
+} DmSceneSimplifyRings;
+int dm_scene_simplify_node_count(const int32_t *labels, int32_t H, int32_t W, int32_t cy0, int32_t cy1, int32_t cx0, int32_t cx1, int64_t oy,
+                                 int64_t ox, int64_t scene_h, int64_t scene_w, int32_t *tile_off, int32_t *n_nodes, void *stream);
+int dm_scene_simplify_node_emit(const int32_t *labels, int32_t H, int32_t W, int32_t cy0, int32_t cy1, int32_t cx0, int32_t cx1, int64_t oy,
+                                int64_t ox, int64_t scene_h, int64_t scene_w, const int32_t *tile_off, int32_t N, int64_t *node, void *stream);
+int dm_scene_simplify_chains(const int32_t *arc_xy, const int64_t *arc_ptr, int32_t A, int64_t Va, int64_t scene_h, int64_t scene_w, int32_t q,
+                             uint8_t *arc_keep, int64_t *stack, void *stream);
+int dm_scene_simplify_arc_count(const int32_t *arc_xy, const int64_t *arc_ptr, int32_t A, int64_t Va, int64_t scene_h, int64_t scene_w,
+                                const uint8_t *arc_keep, int32_t *count, void *stream);
+int dm_scene_simplify_arc_emit(const int32_t *arc_xy, const int64_t *arc_ptr, const int64_t *new_ptr, int32_t A, int64_t Va, int64_t Vn,
+                               int64_t scene_h, int64_t scene_w, const uint8_t *arc_keep, int32_t *out_xy, void *stream);
+int dm_scene_simplify_ring_count(const DmSceneSimplifyRings *t, int32_t *count, void *stream);
+int dm_scene_simplify_ring_emit(const DmSceneSimplifyRings *t, const int64_t *scan, const int64_t *new_ring_ptr, int64_t Vn, int32_t *out_xy,
+                                int64_t *area2, void *stream);
+
 /* BatchNorm2d (+ ReLU, + Dropout2d mask) of the auxiliary heads (reference nets/ShfitScaleFormer.py:329-368: Conv2d ->
  * BatchNorm2d -> ReLU -> Dropout2d(0.3)) on the channels-last matrix the convolution GEMM produces: x, y fp32 [M, C] with
  * M = samples * rows_per_sample.  training != 0: batch statistics (biased variance, eps inside the sqrt), running_mean /
