@@ -1521,12 +1521,17 @@ def pair_weight(weight: torch.Tensor, w2d: torch.Tensor) -> Planes:
     return split_planes(w2d)
 
 
-def _operand_grad(dy: torch.Tensor, dtype: torch.dtype) -> torch.Tensor:
-    """The incoming fp32 gradient as an MFMA operand; reuses the bf16 copy the previous LayerNorm
-    backward already wrote, if there is one."""
+def _grad_tag(g: torch.Tensor):
+    """What a copy that rides on a gradient tensor (`_dm_lp_copy`, `_dm_planes`) is valid for: these very bytes.  The autograd engine may
+    sum a second contribution into the tensor in place (same object, same storage, `_version` bumped); the copy is then stale."""
+    return (g.data_ptr(), g._version)
+
+
+def _operand_grad(dy: torch.Tensor, dtype: torch.dtype, lp: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The incoming fp32 gradient as an MFMA operand; `lp`: the bf16 copy the previous LayerNorm backward already wrote next to it
+    (BlockFn.backward takes it off the tensor and checks that it is still current), reused if it fits."""
     if dy.dtype == dtype and dy.is_contiguous():
         return dy
-    lp = getattr(dy, "_dm_lp_copy", None)      # attached by the BlockFn.backward that produced this very tensor object
     if lp is not None and lp.dtype == dtype and lp.numel() == dy.numel():
         return lp.reshape(dy.shape)
     return _as_operand(dy, dtype)
@@ -1688,16 +1693,15 @@ class BlockFn(torch.autograd.Function):
         M = B * N
         dtype, dev = (torch.float32 if planes else y1.dtype), x.device
         lp = dtype != torch.float32
+        # the bf16 copy / the plane pair the LayerNorm backward of the NEXT block wrote next to this very tensor: one rule for both --
+        # (copy, _grad_tag at the time it was attached); a tag that no longer matches means the engine summed another contribution
+        # into the tensor in place, and the copy is stale
         lp_copy = getattr(dx2, "_dm_lp_copy", None)
-        dy_pair = getattr(dx2, "_dm_planes", None)   # the plane pair the LayerNorm backward of the NEXT block wrote next to this very tensor
-        if dy_pair is not None and dy_pair[1] != (dx2.data_ptr(), dx2._version):
-            dy_pair = None                           # (the engine summed another contribution into the tensor in place: the pair is stale)
-        elif dy_pair is not None:
-            dy_pair = dy_pair[0]
+        dy_pair = getattr(dx2, "_dm_planes", None)
+        lp_copy = lp_copy[0] if (lp_copy is not None and lp_copy[1] == _grad_tag(dx2)) else None
+        dy_pair = dy_pair[0] if (dy_pair is not None and dy_pair[1] == _grad_tag(dx2)) else None
         dx2 = dx2.contiguous().view(M, Cc)
-        if lp_copy is not None:
-            dx2._dm_lp_copy = lp_copy                # (.contiguous() is the same storage; the attribute rides along)
-        dy = _operand_grad(dx2, dtype)
+        dy = _operand_grad(dx2, dtype, lp_copy)
         if planes and isinstance(dy_pair, Planes) and (dy_pair.rows, dy_pair.cols) == (M, Cc):
             dy = dy_pair
         # ---- MLP ---------------------------------------------------------------------------
@@ -1799,10 +1803,10 @@ class BlockFn(torch.autograd.Function):
         dx = r[0].view(B, N, Cc)
         if lp:
             # The bf16 copy the LayerNorm backward wrote rides on the tensor object autograd hands to the next node (the
-            # engine preserves the Python object); a consumer that gets some other tensor simply casts.
-            dx._dm_lp_copy = r[1]
+            # engine preserves the Python object); a consumer that gets some other tensor, or this one after an in-place sum, simply casts.
+            dx._dm_lp_copy = (r[1], _grad_tag(dx))
         if planes:
-            dx._dm_planes = (r[1], (dx.data_ptr(), dx._version))      # likewise the plane pair ("bf16x3"); a consumer that gets another tensor splits
+            dx._dm_planes = (r[1], _grad_tag(dx))      # likewise the plane pair ("bf16x3"); a consumer that gets another tensor splits
         return (dx, _grad_done(P_n1w, dg1, k_n1), _grad_done(P_n1b, dbt1, k_n1b),
                 _grad_done(P_table, dtable, k_t) if want_table else None, None,
                 _grad_done(P_qkv_w, dwq, k_wq), _grad_done(P_qkv_b, dbq, k_bq),
