@@ -2,6 +2,8 @@
 
 Shared by tests/test_gemm_host.py (no GPU: pins the spec, the exactness of the data and the constants of the bounds) and
 tests/test_gpu_gemm_epilogues.py (every kernel family's epilogue against the spec).  numpy / torch float64 only.
+The weight gradient (DM_TN) has its own section below FAMILIES: families and shapes, the library's split rules restated, data, spec and
+frames of tests/test_gpu_gemm_wgrad.py.
 
 Spec (the order of dm_gemm_emit, deepmerge_amd/csrc/dm_gemm_common.h): v = acc + bias; GELU (the pre-activation v is saved first), GELU_GRAD (gelu'(v)
 is saved), DGELU (v *= gelu'(aux)) or MUL (v *= aux); + residual; + old C; rounding to c_dtype (DM_BF16_PAIR: hi = bf16(v),
@@ -150,6 +152,357 @@ def plan_fwd_split(M, N, K):
 
 def family_configs(family):
     return tuple(n for n in ALL if n not in FAMILIES[family]["skips"])
+
+
+# The operand side of NT / NN: in the 14 configurations above A and B are dense (lda = K) and unguarded.  Every family also runs none_f32
+# once more per layout with A and B as views VIEW_OFFSET elements into NaN allocations: lda = K + 8, ldb = K + 8 (NT: B is [N, K]) or N + 8
+# (NN: B is [K, N]), OPERAND_PAD_ROWS rows of NaN below the last row.  A read outside the window poisons the result.
+FRAMED_AB = "none_f32+framed_ab"
+OPERAND_PAD_ROWS = 64
+
+
+def family_framed_cases(family):
+    return [(lay, FRAMED_AB) for lay in FAMILIES[family]["layouts"]]
+
+
+def framed_operand(rows, cols):
+    """A read-only operand [rows, cols] as a framed view: (elements of the allocation, leading dimension, idx [rows, cols])."""
+    ld = cols + 8
+    idx = VIEW_OFFSET + np.arange(rows, dtype=np.int64)[:, None] * ld + np.arange(cols, dtype=np.int64)[None, :]
+    return VIEW_OFFSET + (rows + OPERAND_PAD_ROWS) * ld, ld, idx
+
+
+# ---- the weight gradient (DM_TN): families, plans, data, frames ------------------------------------------------------------------------
+# dW [M, N] = dy^T x (+ old dW), db [M] = column sums of dy (+ old db); dy [K, M] and x [K, N] are row-per-k.  tests/test_gpu_gemm_wgrad.py
+# runs every family at the smallest shape with two tiles in M and in N, a partly filled wave block and one that starts past M, an N tail,
+# and at least two K slices whose last is shorter and ends in a partial K step -- where the family has them.  The split rules of the library
+# are restated below, each with its source line; tests/test_gemm_host.py pins the slice structure of every shape, the GPU test checks it
+# against the split-K slab.
+CUS = 256                # compute units of the MI355X (dm_gemm_cu_count)
+WG_PER_CU = 3            # dm_gemm.hip: `constexpr int WG_PER_CU = (LDS_STAGES == 1) ? 3 : 2` with DM_GEMM_LDS_STAGES 1
+CS_MAX_SLICES = 64       # dm_rows.hip
+
+
+def choose_split(tiles, K, bk):
+    """dm_gemm.hip choose_split: `while (tiles * s < 256 * WG_PER_CU && s < 32 && K / (s * 2) >= 8 * bk) s *= 2`."""
+    s = 1
+    while tiles * s < 256 * WG_PER_CU and s < 32 and K // (s * 2) >= 8 * bk:
+        s *= 2
+    return s
+
+
+def pick_tile_tn(M, N, K, force_tile):
+    """dm_gemm.hip pick_tile for DM_TN."""
+    if force_tile in (64, 128):
+        return force_tile
+    t128 = ((M + 127) // 128) * ((N + 127) // 128)
+    if t128 >= 256:
+        return 128
+    return 128 if (K > 4096 and t128 >= 64) else 64
+
+
+def colsum_region_floats(M):
+    """dm_gemm.hip colsum_region_floats: `(fused > alone ? fused : alone) + 64`, fused = 128 M, alone = dm_colsum_partial_floats(M) = 64 M."""
+    return max(128 * M, CS_MAX_SLICES * M) + 64
+
+
+def tn_workspace_bytes(M, N, K, force_tile=0):
+    """dm_gemm.hip dm_gemm_workspace_bytes for DM_TN: `(s > 1 ? s * M * N * 4 : 0) + colsum_region_floats(M) * 4`, s = choose_split(tiles, K, 32)."""
+    tile = pick_tile_tn(M, N, K, force_tile)
+    s = choose_split(((M + tile - 1) // tile) * ((N + tile - 1) // tile), K, 32)
+    return (s * M * N * 4 if s > 1 else 0) + colsum_region_floats(M) * 4
+
+
+def cut_workspace(nbytes, M, colsum):
+    """dm_gemm.hip cut_workspace: (bytes of the split-K slab, byte offset of the column-sum region or None)."""
+    if not colsum:
+        return nbytes, None
+    need = colsum_region_floats(M) * 4
+    assert nbytes >= need
+    slab = (nbytes - need) & ~15
+    return slab, slab
+
+
+def _slices(K, split, bk):
+    """`kps = ((K + split - 1) / split + bk - 1) / bk * bk; split = (K + kps - 1) / kps` (gemm_plan, dm_gemm256_plan)."""
+    kps = ((K + split - 1) // split + bk - 1) // bk * bk
+    return (K + kps - 1) // kps, kps
+
+
+def plan_tile_tn(M, N, K, tile, bk, slab_bytes):
+    """dm_gemm.hip gemm_plan, the TILE branch for a weight gradient without a caller's split_k: `split = can_split ? choose_split(tiles_m *
+    tiles_n, K, bk) : 1; while (split > 1 && split * M * N * 4 > slab_bytes) split >>= 1`.  Returns (slices, k_per_split)."""
+    split = choose_split(((M + tile - 1) // tile) * ((N + tile - 1) // tile), K, bk) if slab_bytes > 0 else 1
+    while split > 1 and split * M * N * 4 > slab_bytes:
+        split >>= 1
+    return _slices(K, split, bk)
+
+
+def plan_p256_tn(M, N, K, slab_bytes):
+    """dm_gemm256.hip dm_gemm256_plan, the slice loop: `for (sp = 1; sp <= 32; ++sp) { if (sp > 1 && (K / sp < 8 * BK256 || sp * M * N * 4 >
+    workspace_bytes)) break; eff = wg / (((wg + 255) / 256) * 256); if (eff > best + 0.04) { best = eff; split = sp; } }`."""
+    tiles = ((M + 255) // 256) * ((N + 255) // 256)
+    split, best = 1, 0.0
+    if slab_bytes > 0:
+        for sp in range(1, 33):
+            if sp > 1 and (K // sp < 8 * 64 or sp * M * N * 4 > slab_bytes):
+                break
+            wg = tiles * sp
+            eff = wg / (((wg + 255) // 256) * 256)
+            if eff > best + 0.04:
+                best, split = eff, sp
+    return _slices(K, split, 64)
+
+
+def plan_w4_tn(M, N, k_eff, bk_eff, slab_bytes, cus=CUS):
+    """dm_gemm_w4.hip dm_gemm_w4_plan, DM_TN: `split = cus / tiles; if (split > 16) split = 16; per = (steps + split - 1) / split; per += per & 1;
+    if (per < 16) per = 16; split = (steps + per - 1) / per; while (split > 1 && split * M * N * 4 > workspace_bytes) { per += 2; ... }`.
+    k_eff, bk_eff: K and 64, or for plane pairs k_fold and 32 (slices in contraction positions of ONE piece)."""
+    assert M % 256 == 0 and N % 192 == 0 and k_eff % (2 * bk_eff) == 0
+    tiles = (M // 256) * (N // 192)
+    steps = k_eff // bk_eff
+    split = min(cus // tiles, 16)
+    per = (steps + split - 1) // split
+    per += per & 1
+    per = max(per, 16)
+    split = (steps + per - 1) // per
+    while split > 1 and split * M * N * 4 > slab_bytes:
+        per += 2
+        split = (steps + per - 1) // per
+    return split, per * bk_eff
+
+
+def plan_generic_tn(M, N, K, slab_bytes, colsum, skinny_on=True):
+    """dm_gemm.hip gemm_generic, the skinny rule: `if (skinny_on && a->workspace && !a->colsum_a && a->K >= 1024 && tiles16 <= 128) { slices =
+    512 / tiles16; if (slices > K / 128) slices = K / 128; if (slices > 32) slices = 32; while (slices > 1 && slices * M * N * 4 > slab_bytes)
+    slices >>= 1; }` and `k_per_split = ((K + slices - 1) / slices + 31) / 32 * 32`."""
+    tiles16 = ((N + 15) // 16) * ((M + 15) // 16)
+    slices = 1
+    if skinny_on and slab_bytes > 0 and not colsum and K >= 1024 and tiles16 <= 128:
+        slices = min(512 // tiles16, K // 128, 32)
+        while slices > 1 and slices * M * N * 4 > slab_bytes:
+            slices >>= 1
+    if slices > 1:
+        return _slices(K, slices, 32)
+    return 1, K
+
+
+def plan_grouped(shapes, k_eff, bk_eff, mode, cus=CUS):
+    """dm_gemm_w4.hip dm_gemm_w4_grouped_plan for products of one contraction length: ("one_slice", 1, k_eff), ("sliced", S, k_per_split) or
+    None.  one_slice: `n >= 2 && same_acc && tiles <= cus && (mode == 2 || (tiles / cus >= 0.4 && k_max <= 12288))`; sliced: `S = cus / tiles;
+    if (S > 16) S = 16; per = (steps + S - 1) / S; per += per & 1; if (per < 16) per = 16; S = (steps + per - 1) / per` with `S >= 2 && mode != 2`
+    and `mode == 4 || (k_max > 12288 && tiles * S / cus >= 0.85)` (the slabs fit: ops.gemm_grouped asks for 16 slices of room)."""
+    tiles = sum((M // 256) * (N // 192) for M, N in shapes)
+    steps = k_eff // bk_eff
+    if len(shapes) >= 2 and tiles <= cus and (mode == 2 or (tiles / cus >= 0.4 and k_eff <= 12288)):
+        return "one_slice", 1, k_eff
+    S = min(cus // tiles, 16)
+    per = (steps + S - 1) // S
+    per += per & 1
+    per = max(per, 16)
+    S = (steps + per - 1) // per
+    if len(shapes) >= 2 and S >= 2 and mode != 2 and (mode == 4 or (k_eff > 12288 and tiles * S / cus >= 0.85)):
+        return "sliced", S, per * bk_eff
+    return None
+
+
+def colsum_rows_alone(K, M, lda):
+    """dm_rows.hip dm_colsum on dy [K, M]: the rows [M] it leaves in its scratch.  `slices = (M + 255) / 256` (M there = K here), capped at 64,
+    evened out; one slice in the vector form (`(N % 4 == 0) && (ldx % 4 == 0)`, 16-byte aligned) goes straight to the destination."""
+    slices = min((K + 255) // 256, CS_MAX_SLICES)
+    rps = (K + slices - 1) // slices
+    slices = (K + rps - 1) // rps
+    vec = M % 4 == 0 and lda % 4 == 0
+    return 0 if (slices == 1 and vec) else slices
+
+
+def k_slices(K, split, kps):
+    return [(z * kps, min(K, (z + 1) * kps)) for z in range(split)]
+
+
+# env: as for FAMILIES (read_switches reads it on every call).  shapes: (M, N, K of the sliced cases, K of the unsplit short case).  fold:
+# (M, N, k_fold) of the plane-pair case.  cs: how the column sums of dy come about -- "fused" (rows [M] per K slice from the product's own
+# kernel: gemm_plan `pl.cs_fused`, `cs_rows_per_slice`) or "alone" (dm_colsum).  The shapes are the proposal's except where noted.
+_WOFF = dict(_OFF, DM_GEMM_T96="0", DM_GEMM_W4_TN=None, DM_GEMM_GROUPED=None)
+WG_FAMILIES = {
+    # 64 x 64 tiles (a wave owns 32 x 32): 328 = 5 * 64 + 8, 200 = 3 * 64 + 8.  choose_split(24 tiles, 1100, 64) = 2 -> slices of 576 and 524 = 8 * 64 + 12
+    "t64": dict(ab=BF16, codes=(64,), env=dict(_WOFF, DM_GEMM_FORCE_TILE="64"), kind="tile", tile=64, bk=64, cs="fused", cs_rows=1,
+                shapes=((328, 200, 1100, 76),), fold=(328, 200, 384)),
+    # 128 x 128 tiles (a wave owns 64 x 64): M = 296 as in FAMILIES.  The column sums come from dm_colsum (cs_t64 needs tile == 64)
+    "t128": dict(ab=BF16, codes=(128,), env=dict(_WOFF, DM_GEMM_FORCE_TILE="128"), kind="tile", tile=128, bk=64, cs="alone", cs_rows=0,
+                 shapes=((296, 200, 1100, 76),), fold=None),
+    # fp32 operands, K step 32 (for DM_TN gemm_prepare's "fewer than 16 tiles" rule does not apply): choose_split(.., 1100, 32) = 4 -> 288, 288, 288, 236 = 7 * 32 + 12
+    "f32_t64": dict(ab=F32, codes=(64,), env=dict(_WOFF, DM_GEMM_FORCE_TILE="64"), kind="tile", tile=64, bk=32, cs="alone", cs_rows=0,
+                    shapes=((328, 200, 1100, 44),), fold=None),
+    "f32_t128": dict(ab=F32, codes=(128,), env=dict(_WOFF, DM_GEMM_FORCE_TILE="128"), kind="tile", tile=128, bk=32, cs="alone", cs_rows=0,
+                     shapes=((296, 200, 1100, 44),), fold=None),
+    # 256 x 256 pipeline.  The proposal expected 4 slices of 576 for K = 2056; the slice loop of dm_gemm256_plan takes a slice count only when it
+    # fills the 256 CUs better by MORE than 0.04 (`eff > best + 0.04`): 4 tiles x 3 slices = 12 / 256 = 0.047 is taken, x 4 = 0.0625 is not.  So
+    # K = 2056 gives 3 slices of 704, 704 and 648 = 10 * 64 + 8: two slices or more, the last shorter and ending in a partial K step -- the
+    # structure asked for, so the shape stays.  The plane-pair case (k_fold = 704, K = 2112) has one slice per K segment.
+    "p256": dict(ab=BF16, codes=(256,), env=dict(_WOFF, DM_GEMM_256="2"), kind="p256", tile=256, bk=64, cs="fused", cs_rows=4,
+                 shapes=((328, 328, 2056, 72),), fold=(328, 328, 704)),
+    # 4-wave kernel: whole 256 x 192 tiles and K % 128 == 0 only, so the edges are the strides, the rows behind K and the short last slice:
+    # 34 K steps -> per = 16 -> slices of 1024, 1024 and 128.  Plane pairs: 34 steps of 32 -> 512, 512, 64 positions of each piece
+    "w4": dict(ab=BF16, codes=(1924,), env=dict(_WOFF, DM_GEMM_W4="2", DM_GEMM_W4_TN="2"), kind="w4", tile=(256, 192), bk=64, cs="fused", cs_rows=1,
+               shapes=((256, 192, 2176, 1024), (512, 384, 2176, 1024)), fold=(256, 192, 1088)),
+    # generic fp32 path (M % 4 != 0): no profiler row.  28 tiles of 16 x 16 -> 16 slices by the rule, 8 inside the slab dm_gemm_workspace_bytes
+    # declares: 7 of 288 and one of 34 (wave 0 gets 32 of it, wave 1 two, the others none), then sgemm_small_reduce_kernel.  With column sums
+    # wanted the rule leaves the product unsliced (`!a->colsum_a`)
+    "generic": dict(ab=F32, codes=(), env=dict(_WOFF), kind="generic", tile=16, bk=32, cs="alone", cs_rows=0,
+                    shapes=((102, 50, 2050, 19),), fold=None),
+}
+# dm_gemm_grouped: two products in one launch of the 4-wave kernel.  DM_GEMM_GROUPED = 4: the sliced form (3 slices, as w4 alone), = 2: the
+# one-slice form; the rule itself leaves so small a group (3 tiles) to the separate calls, which here is a failure.
+WG_GROUP = dict(ab=BF16, env=dict(_WOFF, DM_GEMM_W4="2", DM_GEMM_W4_TN="2"), shapes=((256, 192), (512, 192)), cs_rows=1,
+                cases=(dict(name="sliced", K=2176, mode=4, fold=False, acc=False, cs="store"),
+                       dict(name="sliced_acc", K=2176, mode=4, fold=False, acc=True, cs="add"),
+                       dict(name="one_slice", K=1024, mode=2, fold=False, acc=False, cs="store"),
+                       dict(name="one_slice_acc", K=1024, mode=2, fold=False, acc=True, cs="add"),
+                       dict(name="fold_sliced", K=1088, mode=4, fold=True, acc=True, cs="store"),
+                       dict(name="fold_one_slice", K=512, mode=2, fold=True, acc=False, cs="add")))
+WG_ALL = tuple(WG_FAMILIES) + ("grouped",)
+GROUP_MIN_SLABS = 16     # deepmerge_amd/ops.py gemm_grouped: `min_slabs=16 if layout == DM_TN else 0`
+
+
+def wg_cases(family):
+    """The products a weight-gradient family runs: dict(name, M, N, K, fold, acc, cs) with cs = None | "store" | "add" (colsum_accumulate).
+    Per shape: the sliced contraction plain, with accumulate + column sums, and with added column sums; the unsplit short contraction with
+    accumulate on (straight to C), without and with column sums.  Plane pairs (K = k_fold): accumulate and column sums."""
+    f = WG_FAMILIES[family]
+    out = []
+    for si, (M, N, K, Ks) in enumerate(f["shapes"]):
+        tag = "" if len(f["shapes"]) == 1 else f"@{M}x{N}"
+        for name, k, acc, cs in (("split", K, False, None), ("split_acc_cs", K, True, "store"), ("split_csadd", K, False, "add"),
+                                 ("short_acc", Ks, True, None), ("short_acc_csadd", Ks, True, "add")):
+            out.append(dict(name=name + tag, M=M, N=N, K=k, fold=False, acc=acc, cs=cs))
+    if f["fold"]:
+        M, N, kf = f["fold"]
+        out.append(dict(name="fold_acc_cs", M=M, N=N, K=kf, fold=True, acc=True, cs="store"))
+    return out
+
+
+def wg_plan(family, case, ws_bytes=None):
+    """What the library does with a case: dict(split, kps, ws_bytes (the workspace the call declares), cs ("fused" | "alone" | None), cs_rows
+    (rows [M] written to the column-sum region), writes = [(first float, floats)] of the workspace that are written)."""
+    f = WG_FAMILIES[family]
+    M, N, K = case["M"], case["N"], case["K"]
+    k_all = 3 * K if case["fold"] else K
+    force = int(f["env"].get("DM_GEMM_FORCE_TILE") or 0)
+    if ws_bytes is None:
+        ws_bytes = tn_workspace_bytes(M, N, k_all, force)
+    slab, cs_off = cut_workspace(ws_bytes, M, case["cs"] is not None)
+    if f["kind"] == "tile":
+        split, kps = plan_tile_tn(M, N, k_all, f["tile"], f["bk"], slab)
+    elif f["kind"] == "p256":
+        split, kps = plan_p256_tn(M, N, k_all, slab)
+    elif f["kind"] == "w4":
+        split, kps = plan_w4_tn(M, N, K, 32 if case["fold"] else 64, slab)
+    else:
+        split, kps = plan_generic_tn(M, N, K, slab, case["cs"] is not None)
+    cs, rows = None, 0
+    if case["cs"] is not None:
+        cs = f["cs"]
+        rows = split * f["cs_rows"] if cs == "fused" else colsum_rows_alone(K, M, M if case["fold"] else M + 8)
+        if cs == "alone" and case["fold"]:
+            raise AssertionError("no family sums the planes of a pair with dm_colsum in these cases")
+    writes = [(0, split * M * N)] if split > 1 else []
+    if rows:
+        writes.append((cs_off // 4, rows * M))
+    return dict(split=split, kps=kps, ws_bytes=ws_bytes, cs=cs, cs_rows=rows, writes=writes)
+
+
+def wg_group_plan(case, numels=None):
+    """The grouped launch of a case: dict(form, split, kps, per product: ws_bytes, writes).  numels: the sizes of the products' workspace
+    buffers where they are known (ops.gemm_grouped declares the whole buffer of slot "gemm.g<i>", which only grows)."""
+    g = WG_GROUP
+    bk = 32 if case["fold"] else 64
+    form, S, kps = plan_grouped(g["shapes"], case["K"], bk, case["mode"])
+    k_all = 3 * case["K"] if case["fold"] else case["K"]
+    prods = []
+    for i, (M, N) in enumerate(g["shapes"]):
+        nbytes = max(tn_workspace_bytes(M, N, k_all) + GROUP_MIN_SLABS * M * N * 4, 1 << 20)      # ops._gemm_args / ops.workspace
+        if numels is not None:
+            assert numels[i] >= nbytes
+            nbytes = numels[i]
+        slab, cs_off = cut_workspace(nbytes, M, True)
+        writes = []
+        if form == "sliced":
+            writes = [(0, S * M * N), (cs_off // 4, S * M)]
+        elif case["cs"] == "add":           # dm_gemm_grouped: one row for the reduction that ADDS it to colsum_a; a first write goes straight there
+            writes = [(cs_off // 4, M)]
+        prods.append(dict(M=M, N=N, ws_bytes=nbytes, writes=writes))
+    return dict(form=form, split=S, kps=kps, products=prods)
+
+
+def wg_data(M, N, K, fold=False):
+    """float64 arrays, all exact in bf16 and in fp32 (cached per shape).  Plain: dy [K, M] integers in [-2, 2], x [K, N] on the 2^-6 grid with
+    |x| <= 2: every product is a multiple of 2^-6 and |sum| <= 4 K, so for K <= 2304 every partial sum in any order and slicing is a float32.
+    Plane pairs: +-(i + j / 1024), i in {1, 2}, j in 0 .. 3 -> hi = +-i, lo = +-j / 1024 (dy_hi, dy_lo, x_hi, x_lo): multiples of 2^-10 with
+    |sum| < 4.02 K.  old_c [M, N] and old_db [M] on the 2^-6 grid."""
+    key = (M, N, K, fold)
+    if key in _WG_DATA:
+        return _WG_DATA[key]
+    rng = np.random.default_rng(7 + 1000003 * M + 1009 * N + 2 * K + int(fold))
+    grid = lambda shape, lim: rng.integers(-lim, lim + 1, size=shape).astype(np.float64) / 64.0
+    d = {}
+    if fold:
+        for nm, cols in (("dy", M), ("x", N)):
+            sign = rng.integers(0, 2, size=(K, cols)).astype(np.float64) * 2 - 1
+            d[nm + "_hi"] = sign * rng.integers(1, 3, size=(K, cols)).astype(np.float64)
+            d[nm + "_lo"] = sign * rng.integers(0, 4, size=(K, cols)).astype(np.float64) / 1024.0
+    else:
+        d["dy"] = rng.integers(-2, 3, size=(K, M)).astype(np.float64)
+        d["x"] = grid((K, N), 128)
+    d["old_c"] = grid((M, N), 128)
+    d["old_db"] = grid((M,), 128)
+    for v in d.values():
+        v.setflags(write=False)
+    _WG_DATA[key] = d
+    return d
+
+
+_WG_DATA = {}
+
+
+def wg_ref(d, acc, cs, fold=False, k0=0, k1=None):
+    """The float64 spec over contraction rows [k0, k1): (dW, db).  Plane pairs: dW = hi^T hi + hi^T lo + lo^T hi, db = colsum(hi) + colsum(lo)."""
+    sl = slice(k0, k1)
+    if fold:
+        ah, al, bh, bl = d["dy_hi"][sl], d["dy_lo"][sl], d["x_hi"][sl], d["x_lo"][sl]
+        dw = ah.T @ bh + ah.T @ bl + al.T @ bh
+        db = ah.sum(0) + al.sum(0)
+    else:
+        dw = d["dy"][sl].T @ d["x"][sl]
+        db = d["dy"][sl].sum(0)
+    if acc:
+        dw = dw + d["old_c"]
+    if cs == "add":
+        db = db + d["old_db"]
+    return dw, db
+
+
+def wg_frames(M, N, K, kps, fold=False):
+    """The allocations of a weight-gradient product, every view VIEW_OFFSET elements in: {"dy" | "x" | "c" | "db": dict(elems, ld, idx)}.
+    dy: lda = M + 8, x: ldb = N + 16, and below row K at least one whole k_per_split of rows, so that a slice that forgets its
+    `min(K, ...)` still reads inside the allocation.  Plane pairs are dense [2, K, cols] blocks (ops.gemm: lda = M), framed as a whole: idx is
+    [2, K, cols].  C: ldc = N + 8 and PAD_ROWS rows below M; db: M floats and 64 behind them."""
+    rows_below = max(kps, 64)
+    out = {}
+    for nm, cols, pad in (("dy", M, 8), ("x", N, 16)):
+        k = np.arange(K, dtype=np.int64)[:, None]
+        c = np.arange(cols, dtype=np.int64)[None, :]
+        if fold:
+            idx = VIEW_OFFSET + np.stack([k * cols + c, K * cols + k * cols + c])
+            out[nm] = dict(elems=VIEW_OFFSET + (2 * K + rows_below) * cols, ld=cols, idx=idx, plane=K * cols)
+        else:
+            ld = cols + pad
+            out[nm] = dict(elems=VIEW_OFFSET + (K + rows_below) * ld, ld=ld, idx=VIEW_OFFSET + k * ld + c)
+    ldc = N + 8
+    out["c"] = dict(elems=VIEW_OFFSET + (M + PAD_ROWS) * ldc, ld=ldc,
+                    idx=VIEW_OFFSET + np.arange(M, dtype=np.int64)[:, None] * ldc + np.arange(N, dtype=np.int64)[None, :])
+    out["db"] = dict(elems=VIEW_OFFSET + M + 64, ld=M, idx=VIEW_OFFSET + np.arange(M, dtype=np.int64))
+    return out
 
 
 # ---- addressing and buffers --------------------------------------------------------------------------------------------------------

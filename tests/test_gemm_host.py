@@ -7,6 +7,8 @@
   * the case table is well formed: the extents each family needs, 16-byte aligned views, >= 256 rows and >= 8 columns of sentinel, the
     grouped cube inside its allocation, every skip documented;
   * the DM_GEMM_* switches the GPU test clears for its children are exactly the ones the library reads.
+  * the weight-gradient tests (tests/test_gpu_gemm_wgrad.py): the restated split rules give the slice structure of every shape, the data
+    sums exactly in float32 in adversarial orders and needs more than 8 significand bits, the frames guard every operand.
 
 Worst err / tol of the restatements is printed ("[gemm_host] ..."; run with -s); the table is at the top of tests/test_gpu_gemm_epilogues.py.
 """
@@ -283,3 +285,176 @@ def test_switch_list_is_what_the_library_reads():
     assert "DM_GEMM_RING_WM" in per_call and "DM_GEMM_FORCE_TILE" in per_call
     assert len(set(ONCE_PER_PROCESS)) == len(ONCE_PER_PROCESS)
     assert set(names) == set(ONCE_PER_PROCESS) | set(per_call), set(names) ^ (set(ONCE_PER_PROCESS) | set(per_call))
+
+
+# ---- the weight gradient (DM_TN): tests/test_gpu_gemm_wgrad.py -------------------------------------------------------------------------
+def _wg_all_cases():
+    """(family, case, plan) of every product the GPU module runs, the grouped products as cases of their own."""
+    out = [(fam, c, G.wg_plan(fam, c)) for fam in G.WG_FAMILIES for c in G.wg_cases(fam)]
+    for c in G.WG_GROUP["cases"]:
+        gp = G.wg_group_plan(c)
+        for M, N in G.WG_GROUP["shapes"]:
+            out.append(("grouped", dict(c, name=f"{c['name']}@{M}x{N}", M=M, N=N), dict(split=gp["split"], kps=gp["kps"])))
+    return out
+
+
+def test_wgrad_slice_structure_of_every_shape():
+    """The restated split rules give the slice structure the case table claims; printed per product (run with -s)."""
+    got = {}
+    for fam, c, plan in _wg_all_cases():
+        sl = G.k_slices(c["K"] if fam in ("w4", "grouped") or not c["fold"] else 3 * c["K"], plan["split"], plan["kps"])
+        got[(fam, c["name"])] = [b - a for a, b in sl]
+        print(f"  [gemm_host] wgrad {fam:<8s} {c['name']:<24s} M={c['M']} N={c['N']} K={c['K']}{' x3' if c['fold'] else ''} slices={got[(fam, c['name'])]} "
+              f"cs={plan.get('cs')} rows={plan.get('cs_rows')}")
+    for fam, tile in (("t64", 64), ("t128", 128)):
+        for name in ("split", "split_acc_cs", "split_csadd"):
+            assert got[(fam, name)] == [576, 524] and 524 % 64 == 12                       # the last step has 12 rows
+            assert got[("f32_" + fam, name)] == [288, 288, 288, 236] and 236 % 32 == 12     # bk = 32
+        for name in ("short_acc", "short_acc_csadd"):
+            assert got[(fam, name)] == [76] and got[("f32_" + fam, name)] == [44]
+    assert got[("t64", "fold_acc_cs")] == [576, 576]                                        # K = 3 * 384: the slices straddle the segments
+    # the proposal expected 4 x 576 for the pipeline; `eff > best + 0.04` takes 3 slices (gemm_ref.WG_FAMILIES["p256"])
+    assert got[("p256", "split")] == got[("p256", "split_acc_cs")] == got[("p256", "split_csadd")] == [704, 704, 648] and 648 % 64 == 8
+    assert got[("p256", "short_acc")] == [72] and got[("p256", "fold_acc_cs")] == [704, 704, 704]
+    for tag in ("@256x192", "@512x384"):
+        for name in ("split", "split_acc_cs", "split_csadd"):
+            assert got[("w4", name + tag)] == [1024, 1024, 128]
+        assert got[("w4", "short_acc" + tag)] == [1024]
+    assert got[("w4", "fold_acc_cs")] == [512, 512, 64]                                     # positions of each piece: 34 steps of 32
+    assert got[("generic", "split")] == [288] * 7 + [34]                                    # 8 z-slices; the last: 32 + 2 + 0 + 0 over the four waves
+    assert got[("generic", "split_acc_cs")] == [2050] == got[("generic", "split_csadd")]    # `!a->colsum_a`: unsliced
+    assert got[("generic", "short_acc")] == [19]
+    for tag in ("@256x192", "@512x192"):
+        assert got[("grouped", "sliced" + tag)] == got[("grouped", "sliced_acc" + tag)] == [1024, 1024, 128]
+        assert got[("grouped", "one_slice" + tag)] == [1024] and got[("grouped", "fold_sliced" + tag)] == [512, 512, 64]
+        assert got[("grouped", "fold_one_slice" + tag)] == [512]
+    assert [G.wg_group_plan(c)["form"] for c in G.WG_GROUP["cases"]] == ["sliced", "sliced", "one_slice", "one_slice", "sliced", "one_slice"]
+    # the rule itself would leave the group to the separate calls: the forms have to be forced
+    assert all(G.plan_grouped(G.WG_GROUP["shapes"], c["K"], 32 if c["fold"] else 64, 1) is None for c in G.WG_GROUP["cases"])
+    # column sums: fused rows per slice on t64 (1), the pipeline (4) and the 4-wave kernel (1); dm_colsum elsewhere (5 scratch rows for K = 1100,
+    # none for one slice in the vector form, always some in the scalar form of the generic family)
+    rows = {(fam, c["name"]): (p.get("cs"), p.get("cs_rows")) for fam, c, p in _wg_all_cases() if fam != "grouped" and c["cs"]}
+    assert rows[("t64", "split_acc_cs")] == ("fused", 2) and rows[("p256", "split_acc_cs")] == ("fused", 12) and rows[("p256", "short_acc_csadd")] == ("fused", 4)
+    assert rows[("w4", "split_csadd@512x384")] == ("fused", 3) and rows[("t128", "split_acc_cs")] == ("alone", 5) == rows[("f32_t64", "split_csadd")]
+    assert rows[("t128", "short_acc_csadd")] == ("alone", 0) and rows[("generic", "split_acc_cs")] == ("alone", 9) and rows[("generic", "short_acc_csadd")] == ("alone", 1)
+    # every family has what it can have: two tiles each way, the ragged last tile, the N tail, >= 2 slices with a shorter, partial last one
+    for fam, f in G.WG_FAMILIES.items():
+        for M, N, K, Ks in f["shapes"]:
+            tm, tn = f["tile"] if isinstance(f["tile"], tuple) else (f["tile"], f["tile"])
+            sl = got[(fam, "split" + ("" if len(f["shapes"]) == 1 else f"@{M}x{N}"))]
+            assert len(sl) >= 2 and sl[-1] < sl[0] and K <= 2304, fam
+            if fam == "w4":
+                assert M % tm == 0 and N % tn == 0 and K % 128 == 0 and sl[-1] % 128 == 0 and (M // tm) * (N // tn) in (1, 4)
+                continue
+            assert (M + tm - 1) // tm >= 2 and (N + tn - 1) // tn >= 2 and M % tm != 0 and N % tn != 0, fam
+            assert sl[-1] % f["bk"] != 0 and Ks % f["bk"] != 0 and Ks < 8 * f["bk"], fam          # a partial last K step; the short case cannot split
+            if fam != "generic":
+                wm = tm // 2 if f["kind"] == "tile" else 128
+                blocks = range((M // tm) * tm, (M // tm) * tm + tm, wm)
+                assert any(b >= M for b in blocks) and any(b < M < b + wm for b in blocks) and M % 16 != 0, fam
+                assert M % 8 == 0 and N % 8 == 0
+            else:
+                assert M % 4 != 0                                                           # gemm_prepare: off the MFMA path
+
+
+def test_wgrad_data_is_exact_in_any_order_and_needs_more_than_8_bits():
+    bf = lambda x: torch.from_numpy(np.array(x)).float().bfloat16().double().numpy()
+    seen = set()
+    for fam, c, plan in _wg_all_cases():
+        M, N, K, fold = c["M"], c["N"], c["K"], c["fold"]
+        d = G.wg_data(M, N, K, fold)
+        # the proof: products on a grid, the sum of their magnitudes below 2^24 grid steps
+        if fold:
+            assert 4.02 * K * 1024 < 2 ** 24
+            parts = [("dy_hi", "x_hi"), ("dy_hi", "x_lo"), ("dy_lo", "x_hi")]
+            for k in ("dy_hi", "dy_lo", "x_hi", "x_lo"):
+                assert np.array_equal(bf(d[k]), d[k]) and np.array_equal(np.round(d[k] * 1024) / 1024, d[k])
+            assert np.abs(d["dy_hi"]).max() == 2 and np.abs(d["dy_lo"]).max() == 3 / 1024
+        else:
+            assert K <= 2304 and 4 * K * 64 < 2 ** 24
+            parts = [("dy", "x")]
+            assert np.array_equal(bf(d["dy"]), d["dy"]) and np.array_equal(bf(d["x"]), d["x"])
+            assert np.array_equal(np.round(d["dy"]), d["dy"]) and np.abs(d["dy"]).max() == 2
+            assert np.array_equal(np.round(d["x"] * 64) / 64, d["x"]) and np.abs(d["x"]).max() == 2
+        for k in ("old_c", "old_db"):
+            assert np.array_equal(np.round(d[k] * 64) / 64, d[k]) and np.abs(d[k]).max() <= 2
+        dw, db = G.wg_ref(d, c["acc"], c["cs"], fold)
+        assert np.array_equal(dw.astype(np.float32).astype(np.float64), dw) and np.array_equal(db.astype(np.float32).astype(np.float64), db)
+        # some output, and some element of every slice's partial tile, needs more than 8 significand bits: a slab kept in bf16 would be seen
+        assert (bf(dw) != dw).any(), (fam, c["name"])
+        for k0, k1 in G.k_slices(K, plan["split"], plan["kps"]) if not (fold and fam in ("t64", "p256")) else [(0, K)]:
+            part = G.wg_ref(d, False, None, fold, k0, k1)[0]
+            assert (bf(part) != part).any(), (fam, c["name"], k0, k1)
+        # the demonstration, once per data set: float32 sums over a block of outputs that holds the first and the last rows and columns, in
+        # adversarial orders -- k ascending, descending, all negative products first (the largest intermediate magnitude), all positive first,
+        # pairwise (numpy), and slice by slice with the partials added last
+        if (M, N, K, fold) in seen:
+            continue
+        seen.add((M, N, K, fold))
+        mi = np.r_[0:8, M - 8:M]
+        ni = np.r_[0:8, N - 8:N]
+        prod = np.concatenate([d[a][:, mi, None] * d[b][:, None, ni] for a, b in parts]).astype(np.float32)      # [K or 3K, 16, 16]
+        assert np.array_equal(prod.astype(np.float64), np.concatenate([d[a][:, mi, None] * d[b][:, None, ni] for a, b in parts]))
+        want = G.wg_ref(d, False, None, fold)[0][np.ix_(mi, ni)]
+        seq = lambda p: np.cumsum(p, axis=0, dtype=np.float32)[-1]
+        srt = np.sort(prod, axis=0)
+        orders = {"ascending k": seq(prod), "descending k": seq(prod[::-1]), "negatives first": seq(srt), "positives first": seq(srt[::-1]),
+                  "pairwise": prod.sum(axis=0, dtype=np.float32)}
+        step = max(1, prod.shape[0] // 7)
+        orders["slices"] = seq(np.stack([seq(prod[i:i + step]) for i in range(0, prod.shape[0], step)]))
+        for name, v in orders.items():
+            assert v.dtype == np.float32 and np.array_equal(v.astype(np.float64), want), (fam, c["name"], name)
+        assert np.abs(np.cumsum(srt, axis=0, dtype=np.float32)).max() > np.abs(want).max()      # the sorted order does reach further out than the result
+
+
+def test_wgrad_frames_are_guarded():
+    """16-byte but not 256-byte aligned views, padded leading dimensions, a whole k_per_split of rows below K, sentinel around C and db."""
+    for fam, c, plan in _wg_all_cases():
+        M, N, K, fold = c["M"], c["N"], c["K"], c["fold"]
+        esz = 4 if (G.WG_GROUP if fam == "grouped" else G.WG_FAMILIES[fam])["ab"] == G.F32 else 2
+        fr = G.wg_frames(M, N, K, plan["kps"], fold)
+        for nm, cols in (("dy", M), ("x", N)):
+            o = fr[nm]
+            assert o["idx"].min() == G.VIEW_OFFSET and (G.VIEW_OFFSET * esz) % 16 == 0 and (G.VIEW_OFFSET * esz) % 256 != 0
+            assert len(np.unique(o["idx"])) == o["idx"].size == (2 if fold else 1) * K * cols
+            # a slice that starts anywhere below K and runs for a whole k_per_split stays inside the allocation, all its columns included
+            assert o["elems"] - 1 - int(o["idx"].max()) >= plan["kps"] * o["ld"] - (o["ld"] - cols), (fam, c["name"], nm)
+            if fold:
+                assert o["ld"] == cols and o["plane"] == K * cols and np.array_equal(o["idx"][1] - o["idx"][0], np.full((K, cols), K * cols))
+            else:
+                assert o["ld"] - cols >= 8 and (fam == "generic" or ((o["ld"] * esz) % 16 == 0 and o["ld"] % 8 == 0))      # (generic: M % 4 != 0, any alignment)
+                assert o["idx"].shape == (K, cols) and o["idx"][1, 0] - o["idx"][0, 0] == o["ld"]
+        assert fr["dy"]["ld"] != fr["x"]["ld"] or fold
+        o = fr["c"]
+        assert o["ld"] == N + 8 and o["idx"].shape == (M, N) and o["idx"].min() == G.VIEW_OFFSET and len(np.unique(o["idx"])) == M * N
+        assert o["elems"] - 1 - int(o["idx"].max()) >= G.PAD_ROWS * o["ld"]
+        assert fr["db"]["idx"].shape == (M,) and fr["db"]["elems"] - 1 - int(fr["db"]["idx"].max()) >= 64
+        # the workspace: the planned writes lie inside the declared bytes, slab and column-sum rows apart
+        if fam != "grouped":
+            writes = sorted(plan["writes"])
+            assert all(a + n <= plan["ws_bytes"] // 4 for a, n in writes) and all(a + n <= b for (a, n), (b, _) in zip(writes, writes[1:]))
+            assert plan["ws_bytes"] == G.tn_workspace_bytes(M, N, 3 * K if fold else K, int(G.WG_FAMILIES[fam]["env"].get("DM_GEMM_FORCE_TILE") or 0))
+    for c in G.WG_GROUP["cases"]:
+        for p in G.wg_group_plan(c)["products"]:
+            writes = sorted(p["writes"])
+            assert all(a + n <= p["ws_bytes"] // 4 for a, n in writes) and all(a + n <= b for (a, n), (b, _) in zip(writes, writes[1:]))
+
+
+def test_wgrad_switches_are_read_by_the_library():
+    """Every switch a weight-gradient family sets is a name read_switches reads on every call."""
+    with open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "deepmerge_amd", "csrc", "dm_gemm.hip")) as f:
+        src = f.read()
+    body = src[src.index("GemmSwitches read_switches()"):]
+    per_call = set(re.findall(r'getenv\(\s*"(DM_GEMM_\w+)"', body[:body.index("\n}\n")]))
+    for f in list(G.WG_FAMILIES.values()) + [G.WG_GROUP]:
+        assert set(f["env"]) <= per_call, set(f["env"]) - per_call
+    assert "DM_GEMM_GROUPED" in per_call
+    assert set(G.WG_ALL) == {"t64", "t128", "f32_t64", "f32_t128", "p256", "w4", "generic", "grouped"}
+
+
+def test_framed_operand_cases_of_the_epilogue_families():
+    for fam, f in G.FAMILIES.items():
+        assert G.family_framed_cases(fam) == [(lay, G.FRAMED_AB) for lay in f["layouts"]] and "none_f32" in G.family_configs(fam)
+    elems, ld, idx = G.framed_operand(328, 192)
+    assert ld == 200 and idx.shape == (328, 192) and idx.min() == G.VIEW_OFFSET and idx[1, 0] - idx[0, 0] == ld
+    assert elems - 1 - int(idx.max()) >= G.OPERAND_PAD_ROWS * ld and len(np.unique(idx)) == idx.size

@@ -1,7 +1,7 @@
 """GPU: the fused epilogue of dm_gemm on every kernel family at ragged edges, against the float64 spec of tests/gemm_ref.py.
 
 Every family (forced by the switches read_switches reads on every call) runs the 14 operand configurations of gemm_ref.CONFIGS, in NT and
-NN where it has both, at the smallest shape whose last row of tiles holds a partially filled wave block and one that starts past M, with an
+NN where it has both (and none_f32 once more per layout with A and B as framed views too: gemm_ref.FRAMED_AB, lda = K + 8, NaN pads and pad rows), at the smallest shape whose last row of tiles holds a partially filled wave block and one that starts past M, with an
 N tail inside a wave's columns.  C, aux and residual are views 8 elements into larger allocations with leading dimensions N + 8 / N + 16 /
 N + 24 and 256 rows below M; everything outside the M x N windows is NaN (also in the operands that are only read, so that a read outside
 the window poisons the result), and after the call every byte outside the written windows must still be the prefill.
@@ -111,8 +111,16 @@ def same_bits(got, want64, dtype, zero_sign_apart):
 
 HIP_WORDS = ("hip", "illegal", "launch failed", "memory access", "out of memory")
 
-for layout, name in G.family_cases(family):
-    cfg = G.CONFIG[name]
+def framed(values, rows, cols):
+    # a read-only operand as a view VIEW_OFFSET elements into a NaN allocation with a padded leading dimension (gemm_ref.framed_operand)
+    elems, ld, idx = G.framed_operand(rows, cols)
+    flat = torch.full((elems,), float("nan"), dtype=ab)
+    flat[torch.from_numpy(idx)] = values.cpu()
+    return flat, ld
+
+
+for layout, name in G.family_cases(family) + G.family_framed_cases(family):
+    cfg = G.CONFIG["none_f32" if name == G.FRAMED_AB else name]
     c = G.case(cfg, M, N, K)
     ref = G.epilogue_ref(d["acc"], c)
     b = G.buffers(cfg, M, N)
@@ -127,7 +135,13 @@ for layout, name in G.family_cases(family):
         c_arg, ldc = ops.Planes(on["c"][off:off + 2 * M * N].view(2, M, N)), None
     else:
         c_arg, ldc = on["c"][off:], b["c"]["ld"]
-    kw = dict(lda=K, ldb=K if layout == "NT" else N, ldc=ldc, bias=bias if cfg["bias"] else None, epilogue=EPI[cfg["epi"]],
+    a_arg, b_arg, lda, ldb = A, B[layout], K, K if layout == "NT" else N
+    if name == G.FRAMED_AB:
+        host["a"], lda = framed(A, M, K)
+        host["b"], ldb = framed(B[layout], *((N, K) if layout == "NT" else (K, N)))
+        on["a"], on["b"] = host["a"].clone().to(dev), host["b"].clone().to(dev)
+        a_arg, b_arg = on["a"][off:], on["b"][off:]
+    kw = dict(lda=lda, ldb=ldb, ldc=ldc, bias=bias if cfg["bias"] else None, epilogue=EPI[cfg["epi"]],
               accumulate=cfg["acc"], rows_per_group=b["rows_per_group"], group_stride=b["group_stride"])
     if "aux" in b:
         kw.update(aux=on["aux"][off:], ldaux=b["aux"]["ld"])
@@ -145,7 +159,7 @@ for layout, name in G.family_cases(family):
         slab.view(torch.float32).fill_(float("nan"))
     lib.dm_prof_enable(1)
     try:
-        ops.gemm(DM_NT if layout == "NT" else DM_NN, A, B[layout], c_arg, M, N, K, **kw)
+        ops.gemm(DM_NT if layout == "NT" else DM_NN, a_arg, b_arg, c_arg, M, N, K, **kw)
     except Exception as e:
         # exit status 3 = dm_gemm refused the arguments before any launch; anything that names the runtime, and anything raised later
         # (the synchronize below is outside this block), ends the child with another status, after which the parent starts nothing more
@@ -162,6 +176,7 @@ for layout, name in G.family_cases(family):
     line["rows"] = [rows[i].name.decode() for i in range(n)]
     after = {k: v.cpu() for k, v in on.items()}
     line["sentinel"] = {k: changed_bytes(host[k], after[k], b[k], b[k]["written"]) for k in ("c", "aux", "res") if k in b}
+    line["sentinel"].update({k: changed_bytes(host[k], after[k], None, False) for k in ("a", "b") if k in host})
 
     c_exact, aux_exact = G.is_exact(cfg)
     apart = (family, name) in G.STRIP_ZERO_SIGN
@@ -225,10 +240,10 @@ def test_gemm_epilogue_family(family):
     assert run.returncode == 0 and run.stdout.rstrip().endswith("DONE"), (run.returncode, run.stdout[-1500:], run.stderr[-3000:])
 
     # exactly the documented cases ran
-    assert [(l["layout"], l["config"]) for l in lines] == G.family_cases(family)
+    assert [(l["layout"], l["config"]) for l in lines] == G.family_cases(family) + G.family_framed_cases(family)
     bad = []
     for l in lines:
-        cfg = G.CONFIG[l["config"]]
+        cfg = G.CONFIG["none_f32" if l["config"] == G.FRAMED_AB else l["config"]]
         tag = (l["layout"], l["config"])
         # the family: the code of the one profiler row; the generic path leaves none
         if fam["codes"]:
@@ -255,6 +270,8 @@ def test_gemm_epilogue_family(family):
             if not r <= 1.0:
                 bad.append((tag, f"{op}: {r:.3f} of the bound"))
         want_ops = {"c"} | ({"aux"} if isinstance(cfg["aux"], tuple) else set()) | ({"res"} if cfg["res"] else set())
+        if l["config"] == G.FRAMED_AB:
+            want_ops |= {"a", "b"}
         if set(l["sentinel"]) != want_ops:
             bad.append((tag, "sentinel counts missing", l["sentinel"]))
         for op, nbytes in l["sentinel"].items():

@@ -1020,7 +1020,10 @@ def test_gemm_grouped_falls_back_to_separate_calls():
 def test_gemm_skinny_fp32_k_slices(layout, M, N, K, monkeypatch):
     """The generic fp32 path cuts the contraction of skinny products (the 100-wide head over 3840 pooled features,
     nets/ShfitScaleFormer.py:958-975: 28 output tiles) into K slices over gridDim.z and sums them in slice order in a second launch:
-    exact on integer data, every epilogue, ragged K, and the same bits as the unsliced kernel on such data."""
+    exact on integer data, every epilogue, ragged K, and the same bits as the unsliced kernel on such data.
+    The TN case was never generic: 100 and 52 are multiples of 4 and gemm_prepare's "fewer than 16 tiles" rule excludes DM_TN, so it runs on
+    64 x 64 MFMA tiles (profiler code 64, read by tests/test_gpu_gemm_wgrad.py, whose `generic` family reaches sgemm_small_kernel<DM_TN> with
+    K slices at M = 102); it stays here as an MFMA case with a ragged K."""
     ops = _ops()
     from deepmerge_amd._lib import DM_EPI_GELU, DM_EPI_NONE, DM_NN, DM_NT, DM_TN
     lay = {"NT": DM_NT, "NN": DM_NN, "TN": DM_TN}[layout]
