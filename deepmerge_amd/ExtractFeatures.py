@@ -168,13 +168,16 @@ class FeatureIO:
     # -- the shapefiles the reference's loaders read (MyUtils1.py:60-114, MyUtils2.py:155-193), without GDAL: deepmerge_amd/shpstore.py --
     @staticmethod
     def save_shapefiles(folder: str, labels: torch.Tensor, n_labels: int, pts, designed: torch.Tensor, edges: Optional[torch.Tensor] = None,
-                        simi: Optional[torch.Tensor] = None, geotransform=None, tolerance: Optional[float] = None):
+                        simi: Optional[torch.Tensor] = None, geotransform=None, tolerance: Optional[float] = None,
+                        topology: bool = False):
         """Write a label raster as the three layers the reference reads: `polygons.shp` (one record per label: the 15 FEATURE_NAMES
         fields from `designed` [n_labels,15] and `PointID`, the space-separated point indices of pts.ptr / pts.idx), `lines.shp` (one
         record per boundary arc: LEFT_FID, RIGHT_FID, -1 = outside the raster, and `simi` when given: the value of the arc's row in
         `edges`, 0.0 for LEFT_FID == -1) and `PointsGCS.shp` (one record per sample point of `pts`: inner, object).  FIDs are label,
         arc and point indices.  tolerance: None writes the traced pixel staircase; a number writes the rings and arcs of
-        `rag.simplify(labels, n_labels, tolerance)`, so `polygons.shp` and `lines.shp` share every vertex.  Returns the three paths."""
+        `rag.simplify(labels, n_labels, tolerance, topology=topology)`, so `polygons.shp` and `lines.shp` share every vertex;
+        topology=True also repairs what plain simplification breaks (collapsed islands, boundaries that cross), so a GIS takes the
+        layer as it is.  Returns the three paths."""
         import os
         from . import rag, shpstore
         if simi is not None and edges is None:
@@ -183,7 +186,7 @@ class FeatureIO:
             raise ValueError(f"designed must be [{n_labels},{len(rag.FEATURE_NAMES)}] (as designed_features returns it)")
         if pts.ptr.numel() != n_labels + 1:
             raise ValueError(f"pts.ptr must have n_labels + 1 = {n_labels + 1} entries")
-        polys, arcs = rag._trace(labels, n_labels) if tolerance is None else rag.simplify(labels, n_labels, tolerance)
+        polys, arcs = rag._trace(labels, n_labels) if tolerance is None else rag.simplify(labels, n_labels, tolerance, topology=topology)
         paths = write_polygon_and_line_layers(folder, polys, arcs, n_labels, pts.ptr, pts.idx, designed, edges, simi, geotransform)
         paths.append(shpstore.write_points(os.path.join(folder, "PointsGCS.shp"), pts.xy.cpu().numpy(),
                                            [("inner", pts.inner.cpu().numpy()), ("object", pts.obj.cpu().numpy())], geotransform))

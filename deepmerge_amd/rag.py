@@ -13,7 +13,8 @@ layer and `lines.shp` (csrc/dm_vector.hip; spec tests/vector_ref.py); deepmerge_
 `rasterize` is the way back, for any polygon: rings to a label raster (csrc/dm_rasterize.hip; spec tests/rasterize_ref.py), and
 `labels_from_shapefile` reads the rings from a polygon shapefile, the form the reference's users have their data in.
 `simplify` is Douglas-Peucker on the traced geometry, once per shared boundary, so neighbours keep sharing every vertex
-(csrc/dm_simplify.hip; spec tests/simplify_ref.py).
+(csrc/dm_simplify.hip; spec tests/simplify_ref.py); `simplify_conflicts` finds where that breaks a polygon and `simplify(topology=True)`
+repairs it (csrc/dm_simplify_topology.hip; spec tests/simplify_topology_ref.py).
 `mrs` is multiresolution segmentation, the classical baseline of the learned merge and a second source of superpixels: the rounds of
 `merge_regions` scored by the colour / shape heterogeneity cost of the regions' statistics, from single pixels or from a label raster
 (csrc/dm_mrs.hip; spec tests/mrs_ref.py).
@@ -248,10 +249,10 @@ class MergeResult:
         """The boundaries between the merged regions, `edge` = row of `self.edges`: `boundary_arcs(self.labels(raster), ...)`."""
         return boundary_arcs(self.labels(raster), self.rep.numel(), edges=self.edges)
 
-    def simplified(self, raster: torch.Tensor, tolerance: float) -> Tuple["Polygons", "Arcs"]:
+    def simplified(self, raster: torch.Tensor, tolerance: float, topology: bool = False) -> Tuple["Polygons", "Arcs"]:
         """The merged regions' rings and boundary arcs simplified to `tolerance` pixels, `Arcs.edge` = row of `self.edges`:
-        `simplify(self.labels(raster), number of merged regions, tolerance, edges=self.edges)`."""
-        return simplify(self.labels(raster), self.rep.numel(), tolerance, edges=self.edges)
+        `simplify(self.labels(raster), number of merged regions, tolerance, edges=self.edges, topology=topology)`."""
+        return simplify(self.labels(raster), self.rep.numel(), tolerance, edges=self.edges, topology=topology)
 
     def scores(self, overlap: "Overlap", round: Optional[int] = None) -> "PartitionScores":
         """The partition scored against a ground-truth map: `overlap` = label_overlap(superpixel raster, truth, S0, G), coarsened by
@@ -1156,8 +1157,11 @@ def _quantise_tolerance(tolerance: float) -> int:
     return q
 
 
-def _simplify(labels: torch.Tensor, n_labels: int, tolerance: float, stats: Optional[dict] = None) -> Tuple[Polygons, Arcs, torch.Tensor]:
-    """`simplify` and the keep flags uint8 [(H+1)(W+1)] (2 node, 1 kept chain vertex, 0 otherwise) it decided by."""
+def _simplify(labels: torch.Tensor, n_labels: int, tolerance: float, stats: Optional[dict] = None, topology: bool = False,
+              max_rounds: int = 64, conflicts_only: bool = False):
+    """`simplify` and the keep flags uint8 [(H+1)(W+1)] (2 node, 1 kept chain vertex, 0 otherwise) it decided by.  topology: the
+    repair rounds of `_TopologyRounds` run between the chain pass and the count.  conflicts_only: the `Conflicts` of the plain
+    keep flags instead."""
     _need_cuda(labels)
     if labels.dtype != torch.int32 or labels.dim() != 2 or labels.numel() < 1:
         raise ValueError("labels must be int32 [H,W] with at least one pixel")
@@ -1188,6 +1192,12 @@ def _simplify(labels: torch.Tensor, n_labels: int, tolerance: float, stats: Opti
           "dm_simplify_chains")
     del stack
     mark("chains")
+    if conflicts_only:
+        return _TopologyRounds(arcs, keep, H, W, q).conflicts()
+    if topology:
+        rounds = _TopologyRounds(arcs, keep, H, W, q)
+        flagged = rounds.repair(max_rounds, stats is not None)
+        mark("topology rounds")
     arc_count, ring_count = new(A, i32), new(V, i32)
     check(lib.dm_simplify_arc_count(arcs.xy.data_ptr(), arcs.arc_ptr.data_ptr(), A, Va, H, W, keep.data_ptr(), arc_count.data_ptr(), _stream()),
           "dm_simplify_arc_count")
@@ -1213,11 +1223,121 @@ def _simplify(labels: torch.Tensor, n_labels: int, tolerance: float, stats: Opti
         stats["stage_ms"] = [(b[0], a[1].elapsed_time(b[1])) for a, b in zip(marks[:-1], marks[1:])]
         stats.update(trace=trace_stats, q=q, arcs=A, rings=R, arc_vertices=Va, vertices=V, kept_arc_vertices=Van, kept_vertices=Vn,
                      longest_arc=int((arcs.arc_ptr[1:] - arcs.arc_ptr[:-1]).max()))
+        if topology:
+            stats.update(topology_rounds=len(flagged) - 1, topology_flagged=flagged, topology_stage_ms=rounds.stage_ms,
+                         topology_segments=rounds.n_segments, topology_cell_entries=rounds.cell_entries)
     return out_polys, out_arcs, keep
 
 
+@dataclass
+class Conflicts:
+    """The segments of a plain `simplify` that the topology rule flags, sorted by arc, then along the arc.
+
+    arc int32 [n] (the arc of `boundary_arcs` / `simplify`); xy int32 [n,4] = the two ends (x0, y0, x1, y1) in arc order; kind
+    uint8 [n]: bit 1 the segment meets another one or is degenerate, bit 2 it jumped over a fixed point; n_segments: all segments
+    of the simplified scene, flagged or not."""
+    arc: torch.Tensor
+    xy: torch.Tensor
+    kind: torch.Tensor
+    n_segments: int
+
+
+class _TopologyRounds:
+    """The detection and repair rounds of csrc/dm_simplify_topology.hip on the keep flags of one `_simplify` call: the arrays, the
+    struct the entries take, and the table arithmetic between them (the scans are torch.cumsum, as everywhere in this file)."""
+    STAGES = ("segment table", "binning", "pair tests", "jump tests", "refine")
+
+    def __init__(self, arcs: Arcs, keep: torch.Tensor, H: int, W: int, q: int):
+        dev, i32, i64 = keep.device, torch.int32, torch.int64
+        self.lib, self.arcs, self.keep = _lib.lib(), arcs, keep
+        self.A, self.Va, self.H, self.W = arcs.left.numel(), arcs.xy.shape[0], H, W
+        cells = ((H >> 5) + 1) * ((W >> 5) + 1)                    # DM_SIMPLIFY_TOPOLOGY_CELL_LOG2
+        new = lambda n, dt: torch.empty(n, dtype=dt, device=dev)
+        self.count, self.new_ptr = new(self.A, i32), torch.zeros(self.A + 1, dtype=i64, device=dev)
+        self.point_count, self.point_fill, self.point_ptr = new(cells, i32), new(cells, i32), torch.zeros(cells + 1, dtype=i64, device=dev)
+        self.point_xy = new((self.Va, 2), i32)
+        self.seg, self.kind = torch.full((self.Va, 4), -1, dtype=i32, device=dev), new(self.Va, i32)
+        self.cell_count, self.cell_fill, self.cell_ptr = new(cells, i32), new(cells, i32), torch.zeros(cells + 1, dtype=i64, device=dev)
+        self.cell_seg = new(max(2 * self.Va, 1024), i32)         # grows when a round needs more (status[2])
+        self.stack, self.status = None, new(4, i32)
+        self.t = _lib.DmSimplifyTopology(arc_xy=arcs.xy.data_ptr(), arc_ptr=arcs.arc_ptr.data_ptr(), new_ptr=self.new_ptr.data_ptr(),
+                                         keep=keep.data_ptr(), point_count=self.point_count.data_ptr(), point_fill=self.point_fill.data_ptr(),
+                                         point_ptr=self.point_ptr.data_ptr(), point_xy=self.point_xy.data_ptr(), seg=self.seg.data_ptr(),
+                                         kind=self.kind.data_ptr(), cell_count=self.cell_count.data_ptr(), cell_fill=self.cell_fill.data_ptr(),
+                                         cell_ptr=self.cell_ptr.data_ptr(), cell_seg=self.cell_seg.data_ptr(), stack=None,
+                                         status=self.status.data_ptr(), Va=self.Va, cap=self.cell_seg.numel(), A=self.A, H=H, W=W, q=q)
+        self.stage_ms, self.n_segments, self.cell_entries = [], 0, 0
+        self._call("point_count")
+        torch.cumsum(self.point_count, 0, dtype=i64, out=self.point_ptr[1:])
+        self._call("point_fill")
+
+    def _call(self, name, *args):
+        check(getattr(self.lib, "dm_simplify_topology_" + name)(ctypes.byref(self.t), *args, _stream()), "dm_simplify_topology_" + name)
+
+    def _round(self, apply: bool, timed: bool):
+        """One round on the current keep: (flagged, flagged with interior vertices).  One readback: the status words."""
+        a = self.arcs
+        while True:
+            marks = []
+
+            def mark():
+                if timed:
+                    e = torch.cuda.Event(enable_timing=True)
+                    e.record()
+                    marks.append(e)
+            mark()
+            check(self.lib.dm_simplify_arc_count(a.xy.data_ptr(), a.arc_ptr.data_ptr(), self.A, self.Va, self.H, self.W, self.keep.data_ptr(),
+                                                 self.count.data_ptr(), _stream()), "dm_simplify_arc_count")
+            torch.cumsum(self.count, 0, dtype=torch.int64, out=self.new_ptr[1:])
+            self._call("segments")
+            mark()
+            self._call("bin_count")
+            torch.cumsum(self.cell_count, 0, dtype=torch.int64, out=self.cell_ptr[1:])
+            self._call("bin_fill")
+            mark()
+            self._call("pairs")
+            mark()
+            self._call("jumps")
+            mark()
+            self._call("refine", 1 if apply else 0)
+            mark()
+            flagged, inner, need, _ = self.status.tolist()
+            if need <= self.t.cap:
+                break
+            self.cell_seg = torch.empty(need, dtype=torch.int32, device=self.keep.device)       # nothing was kept: the round again
+            self.t.cell_seg, self.t.cap = self.cell_seg.data_ptr(), need
+        if timed:                                                  # per round: stage -> ms (the readback above has synchronised)
+            self.stage_ms.append({stage: e0.elapsed_time(e1) for stage, e0, e1 in zip(self.STAGES, marks[:-1], marks[1:])})
+        self.cell_entries = need
+        return flagged, inner
+
+    def repair(self, max_rounds: int, timed: bool = False):
+        """Rounds until no segment is flagged: the flagged-segment count of every round (the last is 0)."""
+        self.stack = torch.empty(2 * self.Va, dtype=torch.int64, device=self.keep.device)
+        self.t.stack = self.stack.data_ptr()
+        counts = []
+        while True:
+            flagged, inner = self._round(True, timed)
+            counts.append(flagged)
+            if flagged == 0:
+                self.n_segments = int(self.new_ptr[-1]) - self.A if timed else 0
+                return counts
+            if inner == 0:
+                raise RuntimeError(f"simplify: {flagged} conflicting segments have no vertex left to restore (round {len(counts)})")
+            if len(counts) > max_rounds:
+                raise RuntimeError(f"simplify: conflicts remain after {max_rounds} repair rounds ({flagged} segments)")
+
+    def conflicts(self) -> Conflicts:
+        self._round(False, False)
+        Vn = int(self.new_ptr[-1])
+        hit = torch.nonzero(self.kind[:Vn]).reshape(-1)
+        seg = self.seg[:Vn + 1]
+        return Conflicts(arc=(seg[hit, 0] >> 1), xy=torch.cat((seg[hit, 2:4], seg[hit + 1, 2:4]), 1), kind=self.kind[hit].to(torch.uint8),
+                         n_segments=Vn - self.A)
+
+
 def simplify(labels: torch.Tensor, n_labels: int, tolerance: float, stats: Optional[dict] = None,
-             edges: Optional[torch.Tensor] = None) -> Tuple[Polygons, Arcs]:
+             edges: Optional[torch.Tensor] = None, topology: bool = False, max_rounds: int = 64) -> Tuple[Polygons, Arcs]:
     """The rings and boundary arcs of `polygons` / `boundary_arcs`, simplified by Douglas-Peucker to `tolerance` pixels (quantised to
     1/256 pixel as `rasterize` quantises coordinates; at most 4096), once per stretch of shared boundary: the two neighbours of a
     boundary get the same vertices, so the simplified polygons still tile the raster without slivers or overlaps, and `lines.shp`
@@ -1226,12 +1346,29 @@ def simplify(labels: torch.Tensor, n_labels: int, tolerance: float, stats: Optio
 
     Same rings and arcs, in the same order, as the tracing gives (`Arcs.edge` from `edges`, as `boundary_arcs` takes them); a ring
     that collapses stays, with ring_area2 == 0.  At tolerance 0 only the pixel corners inside straight runs are absent, as they are
-    from the tracing, and `rasterize` of the rings is the input raster.  Two different boundaries may cross at a large tolerance, as
-    with any plain Douglas-Peucker.  The rule: include/deepmerge_hip.h, restated in tests/simplify_ref.py; every array is bit-equal
-    to it.  One tracing run plus the passes of csrc/dm_simplify.hip; the input is not modified; the only added readback is the pair
-    of vertex totals.  stats: a dict that receives the time per stage and the sizes (tools/mb_simplify.py)."""
-    polys, arcs, _ = _simplify(labels, n_labels, tolerance, stats)
+    from the tracing, and `rasterize` of the rings is the input raster.  With topology=False two different boundaries may cross,
+    land on each other or swing over a neighbour's corner, and an island may collapse, at any tolerance above 0, as with any plain
+    Douglas-Peucker: `simplify_conflicts` lists where.  The rule: include/deepmerge_hip.h, restated in tests/simplify_ref.py; every
+    array is bit-equal to it.  One tracing run plus the passes of csrc/dm_simplify.hip; the input is not modified; the only added
+    readback is the pair of vertex totals.  stats: a dict that receives the time per stage and the sizes (tools/mb_simplify.py).
+
+    topology=True repairs those conflicts (csrc/dm_simplify_topology.hip; spec tests/simplify_topology_ref.py): in
+    rounds, every segment that meets another one or jumped over a node gets back the vertex farthest from it, and its halves are
+    simplified again, until none is flagged.  Only dropped vertices come back, so shared boundaries stay shared, every removed
+    vertex stays within the tolerance, and every ring keeps a non-zero area of its traced sign.  Without a conflict the result is
+    bit for bit the plain one after one detection round.  One readback per round; RuntimeError past `max_rounds`.  stats also
+    receives `topology_rounds`, `topology_flagged` (the flagged segments of every round; the last is 0) and `topology_stage_ms`
+    (per round: stage -> ms)."""
+    if max_rounds < 1:
+        raise ValueError(f"max_rounds must be at least 1, got {max_rounds}")
+    polys, arcs, _ = _simplify(labels, n_labels, tolerance, stats, topology=bool(topology), max_rounds=int(max_rounds))
     return polys, (arcs if edges is None else _attach_edges(arcs, n_labels, edges))
+
+
+def simplify_conflicts(labels: torch.Tensor, n_labels: int, tolerance: float) -> Conflicts:
+    """The segments of `simplify(labels, n_labels, tolerance)` that break the layer's topology: a `Conflicts`, bit-equal to
+    tests/simplify_topology_ref.py.  Empty means the plain result is safe and `topology=True` would return it unchanged."""
+    return _simplify(labels, n_labels, tolerance, conflicts_only=True)
 
 
 # ---- polygon rings to a label raster (csrc/dm_rasterize.hip; the rule: include/deepmerge_hip.h, DESIGN.md 3.5.6) ----------------------

@@ -908,8 +908,8 @@ int dm_rasterize_fill(const int64_t *keys, int64_t N, int32_t H, int32_t W, int3
  *     the next, one unit step at a time.  The walk inserts the nodes that sit on a straight run of the ring (T-junctions, where a
  *     neighbour's chain ends): without them the neighbours would no longer share vertices.  area2 is the shoelace sum again; a
  *     ring left with fewer than three vertices or zero area is still there, with area2 == 0.
- * Shared boundaries stay shared and nodes stay put.  Two different chains may cross at a large tolerance, as with any plain
- * Douglas-Peucker; this is not detected.  Every entry point validates before any launch, launches on `stream`, never synchronises
+ * Shared boundaries stay shared and nodes stay put.  Two different chains may cross, at any tolerance above 0, as with any plain
+ * Douglas-Peucker; the entries below (dm_simplify_topology_*) detect and repair it.  Every entry point validates before any launch, launches on `stream`, never synchronises
  * and never allocates; the caller scans the counts and reads back the vertex totals between count and emit (rag.simplify).
  *
  * dm_simplify_nodes: keep = 2 at the nodes, 0 elsewhere (every entry is written).
@@ -937,6 +937,76 @@ int dm_simplify_ring_count(const int32_t *xy, const int64_t *ring_ptr, const int
 int dm_simplify_ring_emit(const int32_t *xy, const int64_t *ring_ptr, const int32_t *vert_ring, const int64_t *scan, const int64_t *new_ring_ptr,
                           int32_t V, int32_t R, int64_t Vn, int32_t H, int32_t W, const uint8_t *keep, int32_t *out_xy, int64_t *area2,
                           void *stream);
+
+/* ---- topology-safe simplification: find and repair boundary conflicts (additive in ABI 7; csrc/dm_simplify_topology.hip,
+ * DESIGN.md 3.5.12, rag.simplify(topology=True) / rag.simplify_conflicts) ---------------------------------------------------------
+ * Plain Douglas-Peucker moves every chain on its own: islands collapse to a point, two boundaries land on each other, a boundary
+ * swings over a neighbour's corner.  The arcs are stored once per shared boundary and every vertex is an integer, so the damage is
+ * found exactly and repaired for both neighbours at once, only by keeping vertices the rule above had dropped.  Restated in numpy /
+ * Python ints in tests/simplify_topology_ref.py; integers only; nothing depends on the order in which anything is tested.
+ * The rule.  orient(a, b, c) = (b.x - a.x)(c.y - a.y) - (b.y - a.y)(c.x - a.x): coordinates are at most 32768, below 2^31.
+ *   segments: for the current keep, every chain is the sequence of its kept vertices; a segment is two consecutive kept vertices
+ *     (v[i], v[j]) of one chain, its interior vertices are v[i+1 .. j-1] of the traced chain.  The frame arcs (left == -1) are
+ *     segments like any other.  Order: by arc, then along the arc as dm_simplify_arc_emit writes it (segment s of an arc joins
+ *     vertices s and s + 1 of the simplified arc).
+ *   fixed points: every node (keep == 2) and the anchor of every closed arc without a node.  They never move.
+ *   kind, a bit set per segment.
+ *     bit 1, meets: the segment is degenerate (v[i] == v[j]: a closed chain collapsed to its start), or it shares with another
+ *       segment of the scene a point that is not an end of both.  Between two non-degenerate segments (A, B), (C, D): {A, B} ==
+ *       {C, D}; or a proper crossing (orient(A,B,C), orient(A,B,D) of strictly opposite signs and so orient(C,D,A),
+ *       orient(C,D,B)); or an end of one on the other (orient == 0, inside the bounding box) that is not also an end of that
+ *       other.  Both segments of a meeting pair are flagged; degenerate segments take no part in pair tests.
+ *     bit 2, jumps: the segment has interior vertices and some fixed point p other than v[i], v[j] is inside the polygon v[i],
+ *       v[i+1], .., v[j] closed by the segment, by the even-odd rule, half-open in y: the edges (u, w) with (u.y <= p.y) !=
+ *       (w.y <= p.y) and (w.y > u.y and orient(u,w,p) > 0, or w.y < u.y and orient(u,w,p) < 0) are odd in number.
+ *   repair, in rounds: a round computes the kinds of all segments of the current keep; every flagged segment with interior
+ *     vertices has its arg-max k* kept (d_k and the ties as above) and both halves (i, k*), (k*, j) simplified by the ordinary
+ *     rule at the same q; flagged segments without interior vertices are left alone.  Rounds repeat until no segment is flagged;
+ *     then count and emit run once on the final keep.  The traced arcs are conflict-free and every round keeps at least one more
+ *     vertex, so this ends; the caller gives up past its round limit.
+ * The search structure: a uniform grid of cells of 2^DM_SIMPLIFY_TOPOLOGY_CELL_LOG2 corners a side, (H >> log2) + 1 rows of
+ * (W >> log2) + 1; a point is in the cell of its coordinates >> log2, a segment in every cell one of its points is in (walked
+ * along the segment, not over its box).  Per-cell lists by count, the caller's scan, fill.
+ *
+ * One struct for all entries; every entry validates before any launch, launches on `stream`, never synchronises, never allocates.
+ *   point_count: clears point_count / point_fill, then point_count[cell] = the fixed points of the cell, one per arc vertex that
+ *     is a node (a node is counted once for every arc that passes through or ends at it) or anchor.  keep after dm_simplify_chains.
+ *   point_fill: point_ptr = the exclusive scan of point_count (at most Va in all); point_xy gets the points by cell.
+ *   segments: clears cell_count / cell_fill / status; new_ptr = the exclusive scan of dm_simplify_arc_count on the current keep;
+ *     seg slot e = (2 arc + skip, position in the arc as dm_simplify_chains sees it, x, y) of simplified vertex e.
+ *   bin_count: kind[e] = 1 for a degenerate segment, else 0; cell_count[cell] = the other segments passing through the cell.
+ *   bin_fill: cell_ptr = the exclusive scan of cell_count; cell_seg [cap] gets the slots by cell; status[2] = the entries needed
+ *     (when above cap the lists are cut short: repeat the round with a larger cap; refine then keeps nothing).
+ *   pairs: kind |= 1.   jumps: kind |= 2.
+ *   refine: status[0] = flagged segments, status[1] = those with interior vertices; apply != 0: every one of those is split as
+ *     the rule says.  stack int64 [2 Va]: segment (i, j) of an arc owns the j - i entries from 2 arc_ptr[arc] + i. */
+#define DM_SIMPLIFY_TOPOLOGY_CELL_LOG2 5
+typedef struct DmSimplifyTopology {
+  const int32_t *arc_xy;          /* [Va,2] the traced arcs */
+  const int64_t *arc_ptr;         /* [A+1] */
+  const int64_t *new_ptr;         /* [A+1] */
+  uint8_t *keep;                  /* [(H+1)(W+1)] */
+  int32_t *point_count, *point_fill; /* [cells] */
+  const int64_t *point_ptr;       /* [cells+1] */
+  int32_t *point_xy;              /* [Va,2] */
+  int32_t *seg;                   /* [Va,4], 16-byte aligned */
+  int32_t *kind;                  /* [Va] */
+  int32_t *cell_count, *cell_fill; /* [cells] */
+  const int64_t *cell_ptr;        /* [cells+1] */
+  int32_t *cell_seg;              /* [cap] */
+  int64_t *stack;                 /* [2 Va] */
+  int32_t *status;                /* [4] */
+  int64_t Va, cap;
+  int32_t A, H, W, q;
+} DmSimplifyTopology;
+int dm_simplify_topology_point_count(const DmSimplifyTopology *t, void *stream);
+int dm_simplify_topology_point_fill(const DmSimplifyTopology *t, void *stream);
+int dm_simplify_topology_segments(const DmSimplifyTopology *t, void *stream);
+int dm_simplify_topology_bin_count(const DmSimplifyTopology *t, void *stream);
+int dm_simplify_topology_bin_fill(const DmSimplifyTopology *t, void *stream);
+int dm_simplify_topology_pairs(const DmSimplifyTopology *t, void *stream);
+int dm_simplify_topology_jumps(const DmSimplifyTopology *t, void *stream);
+int dm_simplify_topology_refine(const DmSimplifyTopology *t, int32_t apply, void *stream);
 
 /* ---- shared-boundary Douglas-Peucker on a scene's rings and arcs across tile seams (additive in ABI 7;
  * csrc/dm_scene_simplify.hip, DESIGN.md 3.5.11, scene.simplify_labels / SceneResult.simplified) -----------------------------------
