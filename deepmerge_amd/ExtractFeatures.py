@@ -127,12 +127,15 @@ class FeatureIO:
         return scene.trace_labels(source, n_labels, device=self.device, **kw)
 
     @torch.no_grad()
-    def simplify_scene(self, source, n_labels: int, tolerance: float, **kw):
+    def simplify_scene(self, source, n_labels: int, tolerance: float, topology: bool = False, **kw):
         """The rings and arcs of `trace_scene`, simplified to `tolerance` pixels once per stretch of shared boundary, across the
         scene's tiles: `scene.simplify_labels(source, n_labels, tolerance, device=self.device, **kw)`.  Returns (rag.Polygons,
-        rag.Arcs) in scene coordinates, bit for bit `rag.simplify` of the whole raster."""
+        rag.Arcs) in scene coordinates, bit for bit `rag.simplify` of the whole raster.  topology=True also repairs what plain
+        simplification breaks: `scene.simplify_labels_topology` with the same arguments (and max_rounds), bit for bit
+        `rag.simplify(..., topology=True)` of the whole raster."""
         from . import scene
-        return scene.simplify_labels(source, n_labels, tolerance, device=self.device, **kw)
+        call = scene.simplify_labels_topology if topology else scene.simplify_labels
+        return call(source, n_labels, tolerance, device=self.device, **kw)
 
     @torch.no_grad()
     def _extract_local(self, tile, points_xy, inner, obj, region_features, batch_size):

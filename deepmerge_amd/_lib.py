@@ -112,6 +112,15 @@ class DmSimplifyTopology(C.Structure):
                 ("Va", C.c_int64), ("cap", C.c_int64), ("A", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("q", C.c_int32)]
 
 
+class DmSceneSimplifyTopology(C.Structure):
+    _fields_ = [("arc_xy", C.c_void_p), ("arc_ptr", C.c_void_p), ("new_ptr", C.c_void_p), ("arc_keep", C.c_void_p),
+                ("point_count", C.c_void_p), ("point_fill", C.c_void_p), ("point_ptr", C.c_void_p), ("point_xy", C.c_void_p),
+                ("seg", C.c_void_p), ("kind", C.c_void_p), ("cell_count", C.c_void_p), ("cell_fill", C.c_void_p),
+                ("cell_ptr", C.c_void_p), ("cell_seg", C.c_void_p), ("stack", C.c_void_p), ("status", C.c_void_p),
+                ("Va", C.c_int64), ("cap", C.c_int64), ("A", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("q", C.c_int32),
+                ("cell_log2", C.c_int32)]
+
+
 class DmProfRow(C.Structure):
     _fields_ = [("name", C.c_char * 64), ("launches", C.c_int64), ("total_ms", C.c_double),
                 ("total_flops", C.c_double), ("total_bytes", C.c_double)]
@@ -237,6 +246,14 @@ SIGNATURES = {
     "dm_scene_simplify_arc_emit": (_I, [_P, _P, _P, _I, _L, _L, _L, _L, _P, _P, _P]),
     "dm_scene_simplify_ring_count": (_I, [C.POINTER(DmSceneSimplifyRings), _P, _P]),
     "dm_scene_simplify_ring_emit": (_I, [C.POINTER(DmSceneSimplifyRings), _P, _P, _L, _P, _P, _P]),
+    "dm_scene_simplify_topology_point_count": (_I, [C.POINTER(DmSceneSimplifyTopology), _P]),
+    "dm_scene_simplify_topology_point_fill": (_I, [C.POINTER(DmSceneSimplifyTopology), _P]),
+    "dm_scene_simplify_topology_segments": (_I, [C.POINTER(DmSceneSimplifyTopology), _P]),
+    "dm_scene_simplify_topology_bin_count": (_I, [C.POINTER(DmSceneSimplifyTopology), _P]),
+    "dm_scene_simplify_topology_bin_fill": (_I, [C.POINTER(DmSceneSimplifyTopology), _P]),
+    "dm_scene_simplify_topology_pairs": (_I, [C.POINTER(DmSceneSimplifyTopology), _P]),
+    "dm_scene_simplify_topology_jumps": (_I, [C.POINTER(DmSceneSimplifyTopology), _P]),
+    "dm_scene_simplify_topology_refine": (_I, [C.POINTER(DmSceneSimplifyTopology), _I, _P]),
     "dm_gru_cell_fwd": (_I, [_P, _L, _P, _P, _P, _P, _I, _I, _P]),
     "dm_gru_cell_bwd": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _P]),
     "dm_prof_enable": (_I, [_I]),

@@ -1,6 +1,11 @@
-// The integer predicates and the cell walk of dm_simplify_topology.hip, shared with the host check
-// tools/simplify_topology_host_check.cpp.  The rule: include/deepmerge_hip.h; tests/simplify_topology_ref.py
-// restates it.  Coordinates are 0 .. 32768, so every product below is at most 2^31 and every sum fits 64 bits with room to spare.
+// The integer predicates and the cell walk of dm_simplify_topology_kernels.h, shared with the host checks
+// tools/simplify_topology_host_check.cpp and tools/scene_simplify_topology_host_check.cpp.  The rule: include/deepmerge_hip.h,
+// DESIGN.md 3.5.12; tests/simplify_topology_ref.py restates it.
+// Arithmetic.  Coordinates are int32 in [0, 2^31 - 2] (one raster: 0 .. 32768), so every difference of two fits an int, every
+// product of two differences is below 2^62 and every difference of two such products below 2^63: nothing below overflows 64 bits.
+// What is actually met is far smaller: two segments that share a cell, or a fixed point inside a sub-chain's box, have a segment or
+// chain extent of at most 32768 (DM_SIMPLIFY_MAX_SIDE, the arc-extent limit) as one factor of each product and a difference below
+// 2^32 as the other, so every orient term is below 2^48.
 #pragma once
 #include "dm_simplify.h"
 
@@ -50,6 +55,7 @@ DM_HD static inline void dm_topo_walk_cells(int x0, int y0, int x1, int y1, int 
       lo = y0 < y1 ? y0 : y1;
       hi = y0 < y1 ? y1 : y0;
     } else {
+      // cx <= x1 >> log2, so cx << log2 <= x1 < 2^31 fits the int it is formed in, at any log2; dy xa and dy xb are below 2^62
       const long long left = cx << log2, right = left + (1LL << log2);
       const long long xa = (left > x0 ? left : x0) - x0, xb = (right < x1 ? right : x1) - x0;
       const int ya = y0 + (int)dm_topo_floor_div(dy * xa, dx), yb = y0 + (int)dm_topo_floor_div(dy * xb, dx);

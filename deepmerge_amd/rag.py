@@ -1244,39 +1244,49 @@ class Conflicts:
 
 class _TopologyRounds:
     """The detection and repair rounds of csrc/dm_simplify_topology.hip on the keep flags of one `_simplify` call: the arrays, the
-    struct the entries take, and the table arithmetic between them (the scans are torch.cumsum, as everywhere in this file)."""
+    struct the entries take, and the table arithmetic between them (the scans are torch.cumsum, as everywhere in this file).
+    scene._SceneTopologyRounds binds the same rounds to the scene form of the entries: what differs is named here, once."""
     STAGES = ("segment table", "binning", "pair tests", "jump tests", "refine")
+    STRUCT, PREFIX, KEEP = _lib.DmSimplifyTopology, "dm_simplify_topology_", "keep"        # the struct, its entries, its keep field
 
-    def __init__(self, arcs: Arcs, keep: torch.Tensor, H: int, W: int, q: int):
+    def __init__(self, arcs: Arcs, keep: torch.Tensor, H: int, W: int, q: int, cap: Optional[int] = None, **fields):
         dev, i32, i64 = keep.device, torch.int32, torch.int64
         self.lib, self.arcs, self.keep = _lib.lib(), arcs, keep
         self.A, self.Va, self.H, self.W = arcs.left.numel(), arcs.xy.shape[0], H, W
-        cells = ((H >> 5) + 1) * ((W >> 5) + 1)                    # DM_SIMPLIFY_TOPOLOGY_CELL_LOG2
+        cells = self._cells(**fields)
         new = lambda n, dt: torch.empty(n, dtype=dt, device=dev)
         self.count, self.new_ptr = new(self.A, i32), torch.zeros(self.A + 1, dtype=i64, device=dev)
         self.point_count, self.point_fill, self.point_ptr = new(cells, i32), new(cells, i32), torch.zeros(cells + 1, dtype=i64, device=dev)
         self.point_xy = new((self.Va, 2), i32)
         self.seg, self.kind = torch.full((self.Va, 4), -1, dtype=i32, device=dev), new(self.Va, i32)
         self.cell_count, self.cell_fill, self.cell_ptr = new(cells, i32), new(cells, i32), torch.zeros(cells + 1, dtype=i64, device=dev)
-        self.cell_seg = new(max(2 * self.Va, 1024), i32)         # grows when a round needs more (status[2])
+        self.cell_seg = new(max(2 * self.Va, 1024) if cap is None else int(cap), i32)         # grows when a round needs more (status[2])
         self.stack, self.status = None, new(4, i32)
-        self.t = _lib.DmSimplifyTopology(arc_xy=arcs.xy.data_ptr(), arc_ptr=arcs.arc_ptr.data_ptr(), new_ptr=self.new_ptr.data_ptr(),
-                                         keep=keep.data_ptr(), point_count=self.point_count.data_ptr(), point_fill=self.point_fill.data_ptr(),
-                                         point_ptr=self.point_ptr.data_ptr(), point_xy=self.point_xy.data_ptr(), seg=self.seg.data_ptr(),
-                                         kind=self.kind.data_ptr(), cell_count=self.cell_count.data_ptr(), cell_fill=self.cell_fill.data_ptr(),
-                                         cell_ptr=self.cell_ptr.data_ptr(), cell_seg=self.cell_seg.data_ptr(), stack=None,
-                                         status=self.status.data_ptr(), Va=self.Va, cap=self.cell_seg.numel(), A=self.A, H=H, W=W, q=q)
+        self.t = self.STRUCT(arc_xy=arcs.xy.data_ptr(), arc_ptr=arcs.arc_ptr.data_ptr(), new_ptr=self.new_ptr.data_ptr(),
+                             point_count=self.point_count.data_ptr(), point_fill=self.point_fill.data_ptr(),
+                             point_ptr=self.point_ptr.data_ptr(), point_xy=self.point_xy.data_ptr(), seg=self.seg.data_ptr(),
+                             kind=self.kind.data_ptr(), cell_count=self.cell_count.data_ptr(), cell_fill=self.cell_fill.data_ptr(),
+                             cell_ptr=self.cell_ptr.data_ptr(), cell_seg=self.cell_seg.data_ptr(), stack=None,
+                             status=self.status.data_ptr(), Va=self.Va, cap=self.cell_seg.numel(), A=self.A, H=H, W=W, q=q,
+                             **{self.KEEP: keep.data_ptr()}, **fields)
         self.stage_ms, self.n_segments, self.cell_entries = [], 0, 0
         self._call("point_count")
         torch.cumsum(self.point_count, 0, dtype=i64, out=self.point_ptr[1:])
         self._call("point_fill")
 
+    def _cells(self) -> int:
+        return ((self.H >> 5) + 1) * ((self.W >> 5) + 1)          # DM_SIMPLIFY_TOPOLOGY_CELL_LOG2
+
+    def _arc_count(self):
+        a = self.arcs
+        check(self.lib.dm_simplify_arc_count(a.xy.data_ptr(), a.arc_ptr.data_ptr(), self.A, self.Va, self.H, self.W, self.keep.data_ptr(),
+                                             self.count.data_ptr(), _stream()), "dm_simplify_arc_count")
+
     def _call(self, name, *args):
-        check(getattr(self.lib, "dm_simplify_topology_" + name)(ctypes.byref(self.t), *args, _stream()), "dm_simplify_topology_" + name)
+        check(getattr(self.lib, self.PREFIX + name)(ctypes.byref(self.t), *args, _stream()), self.PREFIX + name)
 
     def _round(self, apply: bool, timed: bool):
         """One round on the current keep: (flagged, flagged with interior vertices).  One readback: the status words."""
-        a = self.arcs
         while True:
             marks = []
 
@@ -1286,8 +1296,7 @@ class _TopologyRounds:
                     e.record()
                     marks.append(e)
             mark()
-            check(self.lib.dm_simplify_arc_count(a.xy.data_ptr(), a.arc_ptr.data_ptr(), self.A, self.Va, self.H, self.W, self.keep.data_ptr(),
-                                                 self.count.data_ptr(), _stream()), "dm_simplify_arc_count")
+            self._arc_count()
             torch.cumsum(self.count, 0, dtype=torch.int64, out=self.new_ptr[1:])
             self._call("segments")
             mark()

@@ -26,7 +26,11 @@ the tile size: every tile is read with one pixel of its neighbours' labels, its 
 Simplified rings and arcs.  `simplify_labels` is `rag.simplify` on a scene, bit for bit: the same tile stream
 also yields the scene's nodes (csrc/dm_scene_simplify.hip), and the keep flag per pixel corner becomes two sorted node lists, one
 byte per stored arc vertex and the sorted kept set.  `SceneResult.simplified` and `save_shapefiles(..., tolerance=)` go through it.
-Out of scope: `PointsGCS.shp` for a scene; overlapping the next tile's read with compute; detecting chains that cross.
+Out of scope: `PointsGCS.shp` for a scene; overlapping the next tile's read with compute.
+
+Topology-safe simplification.  `simplify_labels_topology` is `rag.simplify(..., topology=True)` on a
+scene, bit for bit: the detection and repair rounds of 3.5.12 run on the byte per stored arc vertex, over a grid whose cell side
+grows with the scene (csrc/dm_scene_simplify_topology.hip); `simplify_conflicts` lists what the plain call breaks.
 
 Memory.  The scene's pixels are never on the device as a whole: one halo window at a time.  What is resident for the whole scene
 is per superpixel and per sample point: the statistics, the graph, the points and the [P,100] feature rows.  The scene-wide
@@ -295,20 +299,33 @@ class SceneResult:
         """The rings and arcs of `trace`, simplified to `tolerance` pixels once per stretch of shared boundary:
         `simplify_labels` of the merged raster, `Arcs.edge` attached as `trace` does.  Equals `MergeResult.simplified` on the
         assembled raster."""
+        return self._simplified(simplify_labels, tolerance, merged, tile, stats=stats)
+
+    def simplified_topology(self, tolerance: float, merged=None, tile=None, stats: Optional[dict] = None,
+                            max_rounds: int = 64) -> Tuple["rag.Polygons", "rag.Arcs"]:
+        """`simplified` with what plain simplification breaks repaired: `simplify_labels_topology` of the merged raster.  Equals
+        `MergeResult.simplified(..., topology=True)` on the assembled raster."""
+        return self._simplified(simplify_labels_topology, tolerance, merged, tile, stats=stats, max_rounds=max_rounds)
+
+    def _simplified(self, call, tolerance, merged, tile, **kw):
         merged = self.write_merged() if merged is None else merged
         C = int(self.result.rep.numel())
-        polys, arcs = simplify_labels(merged, C, tolerance, tile=self._tile() if tile is None else tile, stats=stats, device=self.edges.device)
+        polys, arcs = call(merged, C, tolerance, tile=self._tile() if tile is None else tile, device=self.edges.device, **kw)
         return polys, rag._attach_edges(arcs, C, self.result.edges)
 
-    def save_shapefiles(self, folder: str, geotransform=None, merged=None, tile=None, tolerance: Optional[float] = None) -> Tuple[str, str]:
+    def save_shapefiles(self, folder: str, geotransform=None, merged=None, tile=None, tolerance: Optional[float] = None,
+                        topology: bool = False) -> Tuple[str, str]:
         """Write the merged regions as the two layers of `FeatureIO.save_shapefiles` that a scene has: `polygons.shp` (one record
         per merged region: the 15 designed fields of `designed_features(result.stats)` and `PointID` from `result.ptr / idx`) and
         `lines.shp` (one record per boundary arc: LEFT_FID, RIGHT_FID, simi = `result.simi` of the arc's edge, 0.0 on the scene's
         frame), through the same writer.  tolerance: None writes the traced pixel staircase; a number writes the rings and arcs of
-        `simplified(tolerance)`, so the two layers share every vertex.  No `PointsGCS.shp`: out of scope for a scene.  Returns the
-        two paths."""
+        `simplified(tolerance)`, or of `simplified_topology(tolerance)` with topology=True, so the two layers share every vertex; topology=True also repairs collapsed
+        islands and boundaries that cross, so a GIS takes the layer as it is.  Without a tolerance `topology` has no effect, as in
+        `FeatureIO.save_shapefiles`: the traced staircase has no conflict to repair.  No `PointsGCS.shp`: out of scope for a scene.
+        Returns the two paths."""
         from .ExtractFeatures import write_polygon_and_line_layers
-        polys, arcs = self.trace(merged, tile) if tolerance is None else self.simplified(tolerance, merged, tile)
+        simplified = self.simplified_topology if topology else self.simplified
+        polys, arcs = self.trace(merged, tile) if tolerance is None else simplified(tolerance, merged, tile)
         r = self.result
         return tuple(write_polygon_and_line_layers(folder, polys, arcs, int(r.rep.numel()), r.ptr, r.idx, rag.designed_features(r.stats),
                                                    edges=r.edges, simi=r.simi, geotransform=geotransform))
@@ -562,16 +579,60 @@ def _check_arc_extents(arcs: "rag.Arcs"):
                          f"{MAX_ARC_EXTENT} on each side (the rule's cross products stay below 2^31); simplify the scene in parts")
 
 
-def _simplify_tables(polys: "rag.Polygons", arcs: "rag.Arcs", node_row: torch.Tensor, H: int, W: int, q: int, mark=lambda stage: None,
-                     stats: Optional[dict] = None) -> Tuple["rag.Polygons", "rag.Arcs", torch.Tensor]:
-    """From a scene's traced rings and arcs and its nodes (node_row int64, the corner ids y (W + 1) + x, ascending) to the simplified
-    rings and arcs and `arc_keep`: the sparse form of `rag._simplify` (DESIGN.md 3.5.11).  Table arithmetic in torch between the
-    kernels: node_col, arc_keep's 2s, the kept set, the scans.  Readbacks: the arc extents, the kept set's size, the totals."""
-    lib, dev, i32, i64 = _lib.lib(), arcs.xy.device, torch.int32, torch.int64
-    rag._need_cuda(arcs.xy)
-    new = lambda n, dt: torch.empty(n, dtype=dt, device=dev)
+MAX_TOPOLOGY_CELLS = 1 << 22          # DM_SCENE_SIMPLIFY_TOPOLOGY_MAX_CELLS: 32 bytes of counts and offsets per cell, 128 MB at the cap
+MAX_TOPOLOGY_ARCS = 1 << 30           # the segment table's tag is 2 arc + skip in an int32
+MAX_TOPOLOGY_ARC_VERTICES = 1 << 30   # as rag.simplify(topology=True): the refine stack is 2 Va int64
+
+
+def topology_cells(H: int, W: int, cell_log2: int) -> int:
+    """Cells of the topology grid of an H x W scene at cells of 2^cell_log2 corners: corner coordinates run to H and W included."""
+    return ((int(H) >> cell_log2) + 1) * ((int(W) >> cell_log2) + 1)
+
+
+def topology_cell_log2(H: int, W: int) -> int:
+    """The cell side `simplify_labels_topology` uses, as its log2: the smallest value >= 5 (the one-raster grid's) at which the
+    grid has at most MAX_TOPOLOGY_CELLS cells.  Pure arithmetic: 5 up to 65535 x 65535, 6 up to 131071 x 131071, 20 for the widest scene `trace_labels` takes."""
+    log2 = 5
+    while topology_cells(H, W, log2) > MAX_TOPOLOGY_CELLS:
+        log2 += 1
+    return log2
+
+
+class _SceneTopologyRounds(rag._TopologyRounds):
+    """`rag._TopologyRounds` on the scene form of its entries (csrc/dm_scene_simplify_topology.hip): the keep flags are `arc_keep`,
+    one byte per stored arc vertex, and the grid's cell side is the struct's `cell_log2`.  The rounds are the base class's."""
+    STRUCT, PREFIX, KEEP = _lib.DmSceneSimplifyTopology, "dm_scene_simplify_topology_", "arc_keep"
+
+    def _cells(self, cell_log2: int) -> int:
+        return topology_cells(self.H, self.W, cell_log2)
+
+    def _arc_count(self):
+        a = self.arcs
+        check(self.lib.dm_scene_simplify_arc_count(a.xy.data_ptr(), a.arc_ptr.data_ptr(), self.A, self.Va, self.H, self.W, self.keep.data_ptr(),
+                                                   self.count.data_ptr(), _stream()), "dm_scene_simplify_arc_count")
+
+
+def _check_topology(H: int, W: int, A: int, Va: int, max_rounds: int, cell_log2: Optional[int]) -> int:
+    """The limits `simplify_labels_topology` adds, each a ValueError naming its quantity, before any round; returns the cell side's log2."""
+    if int(max_rounds) < 1:
+        raise ValueError(f"max_rounds must be at least 1, got {max_rounds}")
+    if A >= MAX_TOPOLOGY_ARCS:
+        raise ValueError(f"topology=True takes fewer than 2^30 arcs, got {A}: simplify a coarser partition or the scene in parts")
+    if Va > MAX_TOPOLOGY_ARC_VERTICES:
+        raise ValueError(f"topology=True takes at most 2^30 arc vertices, got {Va}: simplify a coarser partition or the scene in parts")
+    least = topology_cell_log2(H, W)
+    if cell_log2 is None:
+        return least
+    if not least <= int(cell_log2) <= 24:
+        raise ValueError(f"_cell_log2 must be in {least}..24 for a scene of {H} x {W} (at most 2^22 cells), got {cell_log2}")
+    return int(cell_log2)
+
+
+def _chain_flags(arcs: "rag.Arcs", node_row: torch.Tensor, H: int, W: int, q: int, mark=lambda stage: None):
+    """The chain pass of `_simplify_tables`: (node_col, ids, arc_keep) -- the nodes by column, the corner id y (W + 1) + x of every
+    stored arc vertex, and one keep byte per stored arc vertex (2 node, 1 kept by the chain pass, 0 dropped)."""
+    lib, dev = _lib.lib(), arcs.xy.device
     A, Va = arcs.left.numel(), arcs.xy.shape[0]
-    R, V = polys.ring_label.numel(), polys.xy.shape[0]
     Nn = int(node_row.numel())
     if max(H, W) > MAX_ARC_EXTENT:                               # within 32768 x 32768 no arc can be wider
         _check_arc_extents(arcs)
@@ -582,11 +643,36 @@ def _simplify_tables(polys: "rag.Polygons", arcs: "rag.Arcs", node_row: torch.Te
     arc_keep = ((node_row[at] == ids).to(torch.uint8) * 2).contiguous()
     del at, ny
     mark("node lists + arc_keep")
-    stack = new(Va, i64)                                         # one entry per arc vertex: the bound of the depth-first walk
+    stack = torch.empty(Va, dtype=torch.int64, device=dev)       # one entry per arc vertex: the bound of the depth-first walk
     check(lib.dm_scene_simplify_chains(arcs.xy.data_ptr(), arcs.arc_ptr.data_ptr(), A, Va, H, W, q, arc_keep.data_ptr(), stack.data_ptr(), _stream()),
           "dm_scene_simplify_chains")
     del stack
     mark("chains")
+    return node_col, ids, arc_keep
+
+
+def _simplify_tables(polys: "rag.Polygons", arcs: "rag.Arcs", node_row: torch.Tensor, H: int, W: int, q: int, mark=lambda stage: None,
+                     stats: Optional[dict] = None, topology: bool = False, max_rounds: int = 64,
+                     cell_log2: Optional[int] = None) -> Tuple["rag.Polygons", "rag.Arcs", torch.Tensor]:
+    """From a scene's traced rings and arcs and its nodes (node_row int64, the corner ids y (W + 1) + x, ascending) to the simplified
+    rings and arcs and `arc_keep`: the sparse form of `rag._simplify` (DESIGN.md 3.5.11).  Table arithmetic in torch between the
+    kernels: node_col, arc_keep's 2s, the kept set, the scans.  Readbacks: the arc extents, the kept set's size, the totals.
+    topology: the repair rounds of `_SceneTopologyRounds` run on arc_keep between the chain pass and the kept set (DESIGN.md 3.5.13;
+    one readback per round).  A restored vertex is a stored vertex of its arc, so it is a turn of the ring or a node, and the ring
+    pass, which reads only the kept set and the node lists, runs unchanged on the repaired flags."""
+    lib, dev, i32, i64 = _lib.lib(), arcs.xy.device, torch.int32, torch.int64
+    rag._need_cuda(arcs.xy)
+    new = lambda n, dt: torch.empty(n, dtype=dt, device=dev)
+    A, Va = arcs.left.numel(), arcs.xy.shape[0]
+    R, V = polys.ring_label.numel(), polys.xy.shape[0]
+    Nn = int(node_row.numel())
+    if topology:
+        cell_log2 = _check_topology(H, W, A, Va, max_rounds, cell_log2)
+    node_col, ids, arc_keep = _chain_flags(arcs, node_row, H, W, q, mark)
+    if topology:
+        rounds = _SceneTopologyRounds(arcs, arc_keep, H, W, q, cell_log2=cell_log2)
+        flagged = rounds.repair(int(max_rounds), stats is not None)
+        mark("topology rounds")
     kept_row = torch.sort(torch.cat((node_row, ids[arc_keep == 1]))).values
     del ids
     mark("kept set")
@@ -622,22 +708,15 @@ def _simplify_tables(polys: "rag.Polygons", arcs: "rag.Arcs", node_row: torch.Te
     if stats is not None:
         stats.update(q=q, nodes=Nn, kept=int(kept_row.numel()), arcs=A, rings=R, arc_vertices=Va, vertices=V, kept_arc_vertices=Van,
                      kept_vertices=Vn, longest_arc=int((arcs.arc_ptr[1:] - arcs.arc_ptr[:-1]).max()))
+        if topology:
+            stats.update(topology_rounds=len(flagged) - 1, topology_flagged=flagged, topology_stage_ms=rounds.stage_ms,
+                         topology_segments=rounds.n_segments, topology_cell_entries=rounds.cell_entries, topology_cell_log2=cell_log2)
     return out_polys, out_arcs, arc_keep
 
 
-def simplify_labels(source, n_labels: int, tolerance: float, tile=4096, stats: Optional[dict] = None,
-                    device="cuda:0") -> Tuple["rag.Polygons", "rag.Arcs"]:
-    """A scene's label raster traced and simplified across tile seams: array for array and bit for bit what
-    `rag.simplify(L, n_labels, tolerance)` returns on the whole raster L (where `rag.simplify` takes it), in scene coordinates,
-    whatever the tile size.  Shared boundaries stay shared and nodes stay put, across seams as within a tile.
-
-    source, n_labels, tile, device: as `trace_labels` takes them; the scene is read once, the same windows yield the darts and the
-    nodes.  tolerance: pixels, finite, >= 0, at most 4096, quantised to 1/256 pixel.  stats: a dict that receives the sizes and the
-    seconds per stage (synchronises at stage boundaries).  Limits, each a ValueError: every limit of `trace_labels`; the tolerance
-    (checked before any device work); fewer than 2^31 nodes; every arc's bounding box at most 32768 on each side.
-    Memory: what `trace_labels` holds, plus 8 bytes per node twice, 9 bytes per arc vertex (keep byte, depth-first stack) and 8 bytes
-    per kept vertex; no raster of corners (DESIGN.md 3.5.11)."""
-    q = rag._quantise_tolerance(tolerance)
+def _scene_tables(source, n_labels: int, tile, device, stats: Optional[dict]):
+    """What `simplify_labels` and `simplify_conflicts` share: one stream of the scene into its traced rings and arcs and its sorted
+    node list.  Returns (polys, arcs, node_row, H, W, clock, info, number of tiles)."""
     source = _as_source(source)
     H, W, S, tiles = _check_trace(source, n_labels, tile)
     dev = torch.device(device)
@@ -648,8 +727,70 @@ def simplify_labels(source, n_labels: int, tolerance: float, tile=4096, stats: O
     del table
     node_row = torch.sort(torch.cat(nodes)).values
     del nodes
+    return polys, arcs, node_row, H, W, clock, info, len(tiles)
+
+
+def _simplify_scene(source, n_labels: int, tolerance: float, tile, stats: Optional[dict], device, topology: bool, max_rounds: int = 64,
+                    cell_log2: Optional[int] = None) -> Tuple["rag.Polygons", "rag.Arcs"]:
+    """`simplify_labels` (topology=False) and `simplify_labels_topology` (topology=True): one tile stream, one `_simplify_tables`."""
+    q = rag._quantise_tolerance(tolerance)
+    if topology and int(max_rounds) < 1:
+        raise ValueError(f"max_rounds must be at least 1, got {max_rounds}")
+    polys, arcs, node_row, H, W, clock, info, n_tiles = _scene_tables(source, n_labels, tile, device, stats)
     sizes = None if stats is None else {}
-    out_polys, out_arcs, _ = _simplify_tables(polys, arcs, node_row, H, W, q, mark=lambda stage: clock.lap("simplify: " + stage), stats=sizes)
+    out_polys, out_arcs, _ = _simplify_tables(polys, arcs, node_row, H, W, q, mark=lambda stage: clock.lap("simplify: " + stage), stats=sizes,
+                                              topology=topology, max_rounds=max_rounds, cell_log2=cell_log2)
     if stats is not None:
-        stats.update(sizes, D=info["D"], head_rounds=info["head_rounds"], rank_rounds=info["rank_rounds"], tiles=len(tiles))
+        stats.update(sizes, D=info["D"], head_rounds=info["head_rounds"], rank_rounds=info["rank_rounds"], tiles=n_tiles)
     return out_polys, out_arcs
+
+
+def simplify_labels(source, n_labels: int, tolerance: float, tile=4096, stats: Optional[dict] = None,
+                    device="cuda:0") -> Tuple["rag.Polygons", "rag.Arcs"]:
+    """A scene's label raster traced and simplified across tile seams: array for array and bit for bit what
+    `rag.simplify(L, n_labels, tolerance)` returns on the whole raster L (where `rag.simplify` takes it), in scene coordinates,
+    whatever the tile size.  Shared boundaries stay shared and nodes stay put, across seams as within a tile.  Two different
+    boundaries may cross or land on each other and an island may collapse, as with `rag.simplify`: `simplify_conflicts` lists where,
+    `simplify_labels_topology` repairs it.
+
+    source, n_labels, tile, device: as `trace_labels` takes them; the scene is read once, the same windows yield the darts and the
+    nodes.  tolerance: pixels, finite, >= 0, at most 4096, quantised to 1/256 pixel.  stats: a dict that receives the sizes and the
+    seconds per stage (synchronises at stage boundaries).  Limits, each a ValueError: every limit of `trace_labels`; the tolerance
+    (checked before any device work); fewer than 2^31 nodes; every arc's bounding box at most 32768 on each side.
+    Memory: what `trace_labels` holds, plus 8 bytes per node twice, 9 bytes per arc vertex (keep byte, depth-first stack) and 8 bytes
+    per kept vertex; no raster of corners (DESIGN.md 3.5.11)."""
+    return _simplify_scene(source, n_labels, tolerance, tile, stats, device, topology=False)
+
+
+def simplify_labels_topology(source, n_labels: int, tolerance: float, tile=4096, stats: Optional[dict] = None, device="cuda:0",
+                             max_rounds: int = 64, _cell_log2: Optional[int] = None) -> Tuple["rag.Polygons", "rag.Arcs"]:
+    """`simplify_labels` with its conflicts repaired: array for array and bit for bit what `rag.simplify(L, n_labels, tolerance,
+    topology=True)` returns on the whole raster L, whatever the tile size (DESIGN.md 3.5.12, 3.5.13;
+    csrc/dm_scene_simplify_topology.hip; spec tests/simplify_topology_ref.py).  The rule and the rounds are `rag.simplify`'s: only
+    dropped vertices come back, so shared boundaries stay shared and every ring keeps a non-zero area of its traced sign; without a
+    conflict the result is `simplify_labels`'s bit for bit after one detection round.  (A function of its own and not a keyword of
+    `simplify_labels`, whose parameter list is pinned.)
+
+    Arguments and limits as `simplify_labels`.  The rounds work on the byte per stored arc vertex and a grid of cells of 2^cell_log2
+    corners, the smallest side >= 32 at which the grid has at most 2^22 cells (`topology_cell_log2`); the result does not depend on
+    the side (`_cell_log2` forces a coarser one, for tests).  Further limits, each a ValueError before the rounds start: fewer than
+    2^30 arcs, at most 2^30 arc vertices, max_rounds >= 1.  RuntimeError past `max_rounds` and when no flagged segment has a vertex
+    left to restore.  One readback per round.  stats also receives `topology_rounds`, `topology_flagged` (per round; the last is 0),
+    `topology_stage_ms` (per round: stage -> ms), `topology_segments`, `topology_cell_entries`, `topology_cell_log2` and the stage
+    "simplify: topology rounds".  Further memory while the rounds run: per arc vertex 16 bytes of segment table, 4 of kind, 8 of
+    fixed points, 16 of refine stack and 8 of cell list (4 bytes an entry, sized for two entries per arc vertex, growing when a round
+    needs more); per arc 12 bytes of counts and offsets; per grid cell 32 bytes of counts, fill counters and offsets (128 MB at 2^22
+    cells)."""
+    return _simplify_scene(source, n_labels, tolerance, tile, stats, device, topology=True, max_rounds=max_rounds, cell_log2=_cell_log2)
+
+
+def simplify_conflicts(source, n_labels: int, tolerance: float, tile=4096, device="cuda:0") -> "rag.Conflicts":
+    """The segments of `simplify_labels(source, n_labels, tolerance, tile)` that break the layer's topology: a `rag.Conflicts`,
+    bit-equal (`arc`, `xy`, `kind`, `n_segments`) to `rag.simplify_conflicts` on the whole raster and to
+    tests/simplify_topology_ref.py, whatever the tile size.  Empty means the plain result is safe and `topology=True` would return
+    it unchanged.  One detection round on the plain flags; limits as `simplify_labels_topology`."""
+    q = rag._quantise_tolerance(tolerance)
+    polys, arcs, node_row, H, W, _, _, _ = _scene_tables(source, n_labels, tile, device, None)
+    cell_log2 = _check_topology(H, W, arcs.left.numel(), arcs.xy.shape[0], 1, None)
+    _, _, arc_keep = _chain_flags(arcs, node_row, H, W, q)
+    return _SceneTopologyRounds(arcs, arc_keep, H, W, q, cell_log2=cell_log2).conflicts()

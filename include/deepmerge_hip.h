@@ -1073,6 +1073,60 @@ int dm_scene_simplify_ring_count(const DmSceneSimplifyRings *t, int32_t *count, 
 int dm_scene_simplify_ring_emit(const DmSceneSimplifyRings *t, const int64_t *scan, const int64_t *new_ring_ptr, int64_t Vn, int32_t *out_xy,
                                 int64_t *area2, void *stream);
 
+/* ---- topology-safe simplification of a scene (additive in ABI 7; csrc/dm_scene_simplify_topology.hip, DESIGN.md 3.5.13,
+ * scene.simplify_labels_topology / scene.simplify_conflicts) --------------------------------------------------------------
+ * The rule and the repair rounds of dm_simplify_topology_* above, unchanged, on a scene's arcs: the result is, array for array and
+ * bit for bit, what the one-raster entries give on the whole raster.  The same kernels (csrc/dm_simplify_topology_kernels.h) in a
+ * second form; the struct is DmSimplifyTopology with three differences:
+ *   arc_keep uint8 [Va] in the place of keep: one byte per stored arc vertex as dm_scene_simplify_chains leaves it (2 node, 1 kept,
+ *     0 dropped); a vertex's flag is found by its position in its arc, and refine writes its 1s there.  The caller builds kept_row
+ *     from it after the last round.
+ *   H, W are the scene's sides, 1 <= H, W < 2^31 - 1.
+ *   cell_log2: the grid has cells of 2^cell_log2 corners a side, (H >> cell_log2) + 1 rows of (W >> cell_log2) + 1, and must have at
+ *     most DM_SCENE_SIMPLIFY_TOPOLOGY_MAX_CELLS of them (the product is formed in 64 bits); 5 <= cell_log2 <= 24.  The flags are
+ *     ORs over all pairs that share a cell, and a segment is in the cell of every one of its points, so two segments that share a
+ *     point share a cell at any cell side: the result does not depend on cell_log2.  Cell ids are int.
+ * Arithmetic.  Coordinates are int32 in [0, 2^31 - 2]: every difference of two fits an int, every product of two differences is
+ * below 2^62 and every orient below 2^63, so no entry overflows whatever the tables hold.  Within a chain the rule needs
+ * |cross| < 2^31 (refine's arg-max key is d << 32 | ~(k - i)): the arc-extent limit of dm_scene_simplify_chains, a bounding box of
+ * at most DM_SIMPLIFY_MAX_SIDE on each side.  An arc beyond it, or with a vertex outside the scene, has no fixed points; a
+ * sub-chain beyond it is not tested for jumps and not refined: what the chain pass refuses stays refused, and the caller raises
+ * before any of it (scene.simplify_labels).  Between two segments that share a cell, or a fixed point inside a sub-chain's box, one
+ * factor of each product is such an extent and the other a difference below 2^32: every orient term met is below 2^48.
+ * Sizes: 1 <= A < 2^30 (the table's tag is 2 arc + skip in an int), 2 <= Va <= 2^30, 0 <= q <= 2^20, 1 <= cap < 2^31.  Every entry
+ * validates before any launch (DM_ERR_BAD_SHAPE), launches on `stream`, never synchronises, never allocates; every slot, arc,
+ * position, cell range and point range is checked before it is followed.  The entries do what their namesakes above do;
+ * `segments` takes new_ptr = the exclusive scan of dm_scene_simplify_arc_count on the current arc_keep. */
+#define DM_SCENE_SIMPLIFY_TOPOLOGY_MIN_CELL_LOG2 5
+#define DM_SCENE_SIMPLIFY_TOPOLOGY_MAX_CELL_LOG2 24
+#define DM_SCENE_SIMPLIFY_TOPOLOGY_MAX_CELLS (1LL << 22)
+typedef struct DmSceneSimplifyTopology {
+  const int32_t *arc_xy;          /* [Va,2] the traced arcs, scene coordinates */
+  const int64_t *arc_ptr;         /* [A+1] */
+  const int64_t *new_ptr;         /* [A+1] */
+  uint8_t *arc_keep;              /* [Va] */
+  int32_t *point_count, *point_fill; /* [cells] */
+  const int64_t *point_ptr;       /* [cells+1] */
+  int32_t *point_xy;              /* [Va,2] */
+  int32_t *seg;                   /* [Va,4], 16-byte aligned */
+  int32_t *kind;                  /* [Va] */
+  int32_t *cell_count, *cell_fill; /* [cells] */
+  const int64_t *cell_ptr;        /* [cells+1] */
+  int32_t *cell_seg;              /* [cap] */
+  int64_t *stack;                 /* [2 Va] */
+  int32_t *status;                /* [4] */
+  int64_t Va, cap;
+  int32_t A, H, W, q, cell_log2;
+} DmSceneSimplifyTopology;
+int dm_scene_simplify_topology_point_count(const DmSceneSimplifyTopology *t, void *stream);
+int dm_scene_simplify_topology_point_fill(const DmSceneSimplifyTopology *t, void *stream);
+int dm_scene_simplify_topology_segments(const DmSceneSimplifyTopology *t, void *stream);
+int dm_scene_simplify_topology_bin_count(const DmSceneSimplifyTopology *t, void *stream);
+int dm_scene_simplify_topology_bin_fill(const DmSceneSimplifyTopology *t, void *stream);
+int dm_scene_simplify_topology_pairs(const DmSceneSimplifyTopology *t, void *stream);
+int dm_scene_simplify_topology_jumps(const DmSceneSimplifyTopology *t, void *stream);
+int dm_scene_simplify_topology_refine(const DmSceneSimplifyTopology *t, int32_t apply, void *stream);
+
 /* BatchNorm2d (+ ReLU, + Dropout2d mask) of the auxiliary heads (reference nets/ShfitScaleFormer.py:329-368: Conv2d ->
  * BatchNorm2d -> ReLU -> Dropout2d(0.3)) on the channels-last matrix the convolution GEMM produces: x, y fp32 [M, C] with
  * M = samples * rows_per_sample.  training != 0: batch statistics (biased variance, eps inside the sqrt), running_mean /
