@@ -36,6 +36,7 @@
 // LDS images (bank model of MI355X_MICROARCH.md, both conflict-free for the access patterns used here):
 //   K [keys][128 B], 16-byte chunk index XOR ((key >> 1) & 7)   (ds_read_b128 of 32 consecutive rows, same chunk)
 //   V [keys][128 B], 64-byte half index XOR ((key >> 1) & 1)    (ds_read_b64_tr_b16 of 4 rows x 64 B per half-wave)
+// Tests: tests/test_gpu_attention_spikes.py drives `tile_max` / `rescale_o` (which rows, tiles and lane halves rescale; data: tests/attn_spike.py).
 #include "dm_attention_q32.h"
 
 // Timing ablations (tools/gpu_q32_abl.sh builds with EXTRA=-DDMQ_ABL=<bits>; results are then wrong by design):

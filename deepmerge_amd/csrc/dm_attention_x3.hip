@@ -10,6 +10,7 @@
 // Scores, softmax statistics and the output are fp32 throughout; the bias enters as the scores' C operand from the head's table in
 // LDS (token cubes (3 | 4, 8, 8)) or is absent (ViT); other bias forms stay on the generic fp32 kernels.
 // One wave per SIMD (4 waves x 32 query rows): 28 MFMAs per 32-key tile with the tile's VALU work in their gaps.
+// Tests: tests/test_gpu_attention_spikes.py drives the forward's `tile_max` / `rescale_o` (this file's copy of the deferred maximum).
 #include "dm_attention_q32.h"
 #include "dm_attention_x3.h"
 

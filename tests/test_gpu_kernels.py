@@ -361,6 +361,17 @@ def test_attention_q32_deferred_maximum(N, with_bias):
     np.testing.assert_allclose(lse.cpu().numpy(), lse_ref.numpy(), rtol=2e-2, atol=2e-2)
     err = (out.float().cpu().double() - o_ref).abs().max().item()
     assert err < 3e-2, f"forward max err {err}"
+    # backward on the same data, from the lse of the rescale path (dense rows without an index: no slab); the dqkv bound of
+    # test_attention_forward_backward.  tests/test_gpu_attention_spikes.py controls which rows, tiles and lane halves rescale.
+    dout = torch.from_numpy(rng.normal(size=(B, N, H * D)).astype(np.float32)).to(torch.bfloat16)
+    q64 = qkv.double().requires_grad_(True)
+    o64, _ = _attn_ref(q64, None if bias is None else bias.double(), 0.125)
+    o64.backward(dout.double())
+    dqkv, _, _ = ops.attention_bwd(qkv.to(DEV), None if bias is None else bias.to(DEV), out, dout.to(DEV), lse, B, N, H, D, 0.125)
+    assert torch.isfinite(dqkv.float()).all()
+    gq = q64.grad
+    err = (dqkv.float().cpu().double() - gq).abs().max().item()
+    assert err < 4e-2 * max(1.0, gq.abs().max().item()), f"dqkv max err {err} (scale {gq.abs().max().item()})"
 
 
 @pytest.mark.parametrize("scales,B,H", [(4, 8, 12), (3, 10, 12), (4, 33, 3), (4, 50, 12), (3, 43, 7)])
