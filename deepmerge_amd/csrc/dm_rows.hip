@@ -25,34 +25,57 @@ static int ln_max_wg() {           // workgroups of the LayerNorm backward (each
 }
 constexpr int CS_MAX_SLICES = 64;
 
+// four elements as they lie in memory, for a load whose conversion to fp32 comes later (dm_load4 converts on the spot)
+template <typename T> struct Raw4;
+template <> struct Raw4<float> { typedef f32x4 type; };
+template <> struct Raw4<bf16_t> { typedef bf16x4 type; };
+template <typename T>
+__device__ __forceinline__ typename Raw4<T>::type dm_load_raw4(const T *p) { return *reinterpret_cast<const typename Raw4<T>::type *>(p); }
+__device__ __forceinline__ f32x4 dm_widen4(f32x4 v) { return v; }
+__device__ __forceinline__ f32x4 dm_widen4(bf16x4 v) { return (f32x4){(float)v[0], (float)v[1], (float)v[2], (float)v[3]}; }
+
 // ---------------------------------------------------------------------------------------------
 // LayerNorm forward: one wave per row.
 // ---------------------------------------------------------------------------------------------
 // PAIR (TY = bf16): y is the hi / lo plane pair [2, rows, cols] of the normalised rows (the operand format of the folded "bf16x3"
 // products: no fp32 y, no split pass).
-template <typename TY, bool PAIR = false>
+// CH = float4 chunks per lane per row (cols <= 256 CH); FULL: cols == 256 CH, every lane live in every chunk -- no lane predicate, so
+// no skip branches in the row loop and the waits in it are counted exactly (the encoder's 768 columns: CH = 3).
+template <typename TY, bool PAIR, int CH, bool FULL>
 __global__ __launch_bounds__(256) void layernorm_fwd_kernel(const float *__restrict__ x, const float *__restrict__ gamma,
                                                             const float *__restrict__ beta, TY *__restrict__ y,
                                                             float *__restrict__ mean_out, float *__restrict__ rstd_out,
                                                             int rows, int cols, float eps) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  // gamma and beta wait in LDS: read from there they count on the LDS counter, and a wait for them cannot drain the next row's loads
+  __shared__ f32x4 gb[2][CH * 64];
+  const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);      // the row index stays scalar: branches on it are jumps
   const int nch = cols >> 2;
-  for (int row = blockIdx.x * 4 + wave; row < rows; row += gridDim.x * 4) {
-    const float *xr = x + (long long)row * cols;
-    f32x4 v[MAXCH];
+  for (int c = threadIdx.x; c < nch; c += 256) {
+    gb[0][c] = dm_load4(gamma + 4 * c);
+    gb[1][c] = dm_load4(beta + 4 * c);
+  }
+  __syncthreads();
+  const int stride = gridDim.x * 4;
+  int row = blockIdx.x * 4 + wave;
+  if (row >= rows) return;
+  auto request = [&](int r, f32x4(&dst)[CH]) __attribute__((always_inline)) {
+    const float *xr = x + (long long)r * cols;
+#pragma unroll
+    for (int i = 0; i < CH; ++i) {
+      const int c = lane + 64 * i;
+      dst[i] = (FULL || c < nch) ? dm_load4(xr + 4 * c) : (f32x4){0.f, 0.f, 0.f, 0.f};
+    }
+  };
+  auto finish = [&](int row, const f32x4(&v)[CH]) __attribute__((always_inline)) {
     float s = 0.f;
 #pragma unroll
-    for (int i = 0; i < MAXCH; ++i) {
-      const int c = lane + 64 * i;
-      v[i] = (c < nch) ? dm_load4(xr + 4 * c) : (f32x4){0.f, 0.f, 0.f, 0.f};
-      s += (v[i][0] + v[i][1]) + (v[i][2] + v[i][3]);
-    }
+    for (int i = 0; i < CH; ++i) s += (v[i][0] + v[i][1]) + (v[i][2] + v[i][3]);
     const float mean = dm_wave_sum(s) / (float)cols;
     float q = 0.f;
 #pragma unroll
-    for (int i = 0; i < MAXCH; ++i) {
+    for (int i = 0; i < CH; ++i) {
       const int c = lane + 64 * i;
-      if (c < nch) {
+      if (FULL || c < nch) {
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
           const float d = v[i][e] - mean;
@@ -67,10 +90,12 @@ __global__ __launch_bounds__(256) void layernorm_fwd_kernel(const float *__restr
     }
     TY *yr = y + (long long)row * cols;
 #pragma unroll
-    for (int i = 0; i < MAXCH; ++i) {
+    for (int i = 0; i < CH; ++i) {
       const int c = lane + 64 * i;
-      if (c < nch) {
-        const f32x4 g = dm_load4(gamma + 4 * c), b = dm_load4(beta + 4 * c);
+      if (FULL || c < nch) {
+        int cl = c;
+        asm volatile("" : "+v"(cl));      // an index the compiler cannot call loop-invariant: hoisted, the 2 CH reads cost 8 CH registers, and with them the eighth wave per SIMD that the grid counts on
+        const f32x4 g = gb[0][cl], b = gb[1][cl];
         f32x4 o;
 #pragma unroll
         for (int e = 0; e < 4; ++e) o[e] = (v[i][e] - mean) * rstd * g[e] + b[e];
@@ -88,15 +113,41 @@ __global__ __launch_bounds__(256) void layernorm_fwd_kernel(const float *__restr
         }
       }
     }
+  };
+  // The wave's next row is requested before the current row's first reduction, so its loads are in flight through both reductions, the
+  // arithmetic and the stores.  The first row is peeled: inside the loop the only wait is the one for the row requested an iteration ago,
+  // counted past the stores issued since (a loop that met the first row's request at its head would wait for everything each time round).
+  // Other widths keep the plain loop: with lane predicates every wait in the loop comes out as a wait for everything, and the second
+  // row of registers costs the bf16 instance its eighth wave per SIMD.
+  f32x4 v[CH], nv[CH];
+  if constexpr (!FULL) {
+    for (; row < rows; row += stride) {
+      request(row, v);
+      finish(row, v);
+    }
+    return;
+  }
+  request(row, v);
+  int next = row + stride;
+  if (next < rows) request(next, nv);
+  finish(row, v);
+  while (next < rows) {
+    row = next;
+    next = row + stride;
+#pragma unroll
+    for (int i = 0; i < CH; ++i) v[i] = nv[i];
+    if (next < rows) request(next, nv);
+    finish(row, v);
   }
 }
 
 // LayerNorm backward: dx = dres + rstd*(g - mean(g) - xhat*mean(g*xhat)), g = dy*gamma.
 // Each workgroup keeps per-column partial sums of dy*xhat (dgamma) and dy (dbeta) in registers
 // over its grid-stride rows, combines its 4 waves through LDS and writes one partial row.
-// CH = float4 chunks per lane per row: 3 for rows of up to 768 columns (the encoder's width: 112 registers, 4 workgroups per CU),
-// 4 up to 1024.
-template <typename TDY, int CH>
+// CH = float4 chunks per lane per row: 3 for rows of up to 768 columns, 4 up to 1024.  FULL: cols == 256 CH (the encoder's 768), every
+// lane live in every chunk: no lane predicate, so no skip branches in the row loop and its waits are counted exactly.  Registers
+// (fp32 / bf16 dy): CH = 3 FULL 135 / 126, CH = 3 168 / 162, CH = 4 155 / 148 -- all within the 168 that three workgroups per CU allow.
+template <typename TDY, int CH, bool FULL>
 __global__ __launch_bounds__(256) void layernorm_bwd_kernel(const TDY *__restrict__ dy, const float *__restrict__ x,
                                                             const float *__restrict__ gamma, const float *__restrict__ mean,
                                                             const float *__restrict__ rstd, const float *__restrict__ dres,
@@ -104,33 +155,53 @@ __global__ __launch_bounds__(256) void layernorm_bwd_kernel(const TDY *__restric
                                                             float *__restrict__ partial, int rows, int cols, long long lp_plane) {
   // lp_plane > 0: dx_lp is the hi / lo plane pair of dx (lo plane lp_plane elements behind), not a rounded bf16 copy
   __shared__ float red[4][2][CH * 256];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);      // the row index stays scalar: branches on it are jumps
   const int nch = cols >> 2;
   f32x4 dg[CH], db[CH], gam[CH];
 #pragma unroll
   for (int i = 0; i < CH; ++i) {
     dg[i] = db[i] = (f32x4){0.f, 0.f, 0.f, 0.f};
     const int c = lane + 64 * i;
-    gam[i] = (c < nch) ? dm_load4(gamma + 4 * c) : (f32x4){0.f, 0.f, 0.f, 0.f};
+    gam[i] = (FULL || c < nch) ? dm_load4(gamma + 4 * c) : (f32x4){0.f, 0.f, 0.f, 0.f};
   }
-  for (int row = blockIdx.x * 4 + wave; row < rows; row += gridDim.x * 4) {
+  // A row's operands as they were loaded (dy still in its own type: a conversion would be a use, and a use waits)
+  f32x4 rx[CH], rdr[CH];
+  typename Raw4<TDY>::type rdy[CH];
+  float rmu = 0.f, rrs = 0.f;
+  // every load of a row is issued before anything waits (the residual gradient used to be requested after the two wave
+  // reductions: a second full memory latency per row with only 8 waves per CU to hide it -- 3.4 TB/s at 16384 x 768)
+  auto request = [&](int row) __attribute__((always_inline)) {
     const long long off = (long long)row * cols;
-    const float mu = mean[row], rs = rstd[row];
-    f32x4 xh[CH], g[CH], dr[CH];
-    float s1 = 0.f, s2 = 0.f;
-    // every load of the row is issued before anything waits (the residual gradient used to be requested after the two wave
-    // reductions: a second full memory latency per row with only 8 waves per CU to hide it -- 3.4 TB/s at 16384 x 768)
+    rmu = mean[row];
+    rrs = rstd[row];
 #pragma unroll
     for (int i = 0; i < CH; ++i) {
       const int c = lane + 64 * i;
-      dr[i] = (dres && c < nch) ? dm_load4(dres + off + 4 * c) : (f32x4){0.f, 0.f, 0.f, 0.f};
+      rdr[i] = (dres && (FULL || c < nch)) ? dm_load4(dres + off + 4 * c) : (f32x4){0.f, 0.f, 0.f, 0.f};
     }
 #pragma unroll
     for (int i = 0; i < CH; ++i) {
       const int c = lane + 64 * i;
-      if (c < nch) {
-        const f32x4 xv = dm_load4(x + off + 4 * c);
-        const f32x4 d = dm_load4(dy + off + 4 * c);
+      if (FULL || c < nch) {
+        rx[i] = dm_load4(x + off + 4 * c);
+        rdy[i] = dm_load_raw4(dy + off + 4 * c);
+      }
+    }
+  };
+  f32x4 xh[CH], g[CH], dr[CH];
+  float rs = 0.f, s1 = 0.f, s2 = 0.f;
+  // waits for the requested row and folds it into xhat, g, the two row sums and the column sums; frees the raw registers
+  auto consume = [&]() __attribute__((always_inline)) {
+    const float mu = rmu;
+    rs = rrs;
+    s1 = s2 = 0.f;
+#pragma unroll
+    for (int i = 0; i < CH; ++i) {
+      const int c = lane + 64 * i;
+      dr[i] = rdr[i];
+      if (FULL || c < nch) {
+        const f32x4 xv = rx[i];
+        const f32x4 d = dm_widen4(rdy[i]);
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
           xh[i][e] = (xv[e] - mu) * rs;
@@ -144,11 +215,23 @@ __global__ __launch_bounds__(256) void layernorm_bwd_kernel(const TDY *__restric
         xh[i] = g[i] = (f32x4){0.f, 0.f, 0.f, 0.f};
       }
     }
-    const float c1 = dm_wave_sum(s1) / (float)cols, c2 = dm_wave_sum(s2) / (float)cols;
+  };
+  auto finish = [&](int row) __attribute__((always_inline)) {
+    const long long off = (long long)row * cols;
+    // dm_wave_sum of both row sums, step by step side by side: the two butterflies do not depend on each other, and one after the other
+    // they are twelve cross-lane round trips on the wave's critical path instead of six
+    float t1 = s1, t2 = s2;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+      const float u1 = __shfl_xor(t1, o, 64), u2 = __shfl_xor(t2, o, 64);
+      t1 += u1;
+      t2 += u2;
+    }
+    const float c1 = t1 / (float)cols, c2 = t2 / (float)cols;
 #pragma unroll
     for (int i = 0; i < CH; ++i) {
       const int c = lane + 64 * i;
-      if (c < nch) {
+      if (FULL || c < nch) {
         f32x4 o;
 #pragma unroll
         for (int e = 0; e < 4; ++e) o[e] = rs * (g[i][e] - c1 - xh[i][e] * c2);
@@ -169,6 +252,32 @@ __global__ __launch_bounds__(256) void layernorm_bwd_kernel(const TDY *__restric
           }
         }
       }
+    }
+  };
+  // Software pipeline over the wave's rows, same rows in the same order as a plain grid-stride loop: the next row is requested as soon
+  // as the current one has left the raw registers, before the two wave reductions, so its loads are in flight through the reductions,
+  // the dx arithmetic and the stores.  The first consume() stands outside the loop: at the one inside, what is outstanding is the same
+  // every time round (the requested row, then the stores issued after it), and the wait it gets is counted past those stores.
+  // CH = 4 keeps the plain loop: two rows of raw operands beside four chunks of sums take it past 168 registers (208 / 216), and the
+  // grid's three workgroups per CU no longer fit at once.
+  int row = blockIdx.x * 4 + wave;
+  const int stride = gridDim.x * 4;
+  if constexpr (CH == MAXCH) {
+    for (; row < rows; row += stride) {
+      request(row);
+      consume();
+      finish(row);
+    }
+  } else if (row < rows) {
+    request(row);
+    consume();
+    for (;;) {
+      const int next = row + stride;
+      if (next < rows) request(next);
+      finish(row);
+      if (next >= rows) break;
+      row = next;
+      consume();
     }
   }
 #pragma unroll
@@ -613,12 +722,26 @@ __global__ void relpos_gather_kernel(const float *__restrict__ table, const int 
     }
   }
 }
+// U chunks from chunk c on: all U loads are issued, then added to v in chunk order (a loop of load-and-add pays one memory latency
+// per chunk: a thread has a single position at the model's plane sizes, so nothing else of its own is in flight meanwhile)
+template <int U>
+__device__ __forceinline__ void chunk_add(f32x4 &v, const float *slab, long long plane4, long long i, int c) {
+  f32x4 a[U];
+#pragma unroll
+  for (int u = 0; u < U; ++u) a[u] = dm_load4(slab + ((long long)(c + u) * plane4 + i) * 4);
+#pragma unroll
+  for (int u = 0; u < U; ++u) v += a[u];
+}
 // slab[0][e] = sum_c slab[c][e] in chunk order (coalesced 16-byte accesses); the gather below then works on one plane set
 // that stays L2-resident instead of touching `chunks` scattered cache lines per position.
 __global__ void chunk_sum_kernel(float *__restrict__ slab, long long plane4, int chunks) {
   for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < plane4; i += (long long)gridDim.x * blockDim.x) {
     f32x4 v = dm_load4(slab + 4 * i);
-    for (int c = 1; c < chunks; ++c) v += dm_load4(slab + ((long long)c * plane4 + i) * 4);
+    int c = 1;
+    for (; c + 8 <= chunks; c += 8) chunk_add<8>(v, slab, plane4, i, c);
+    if (c + 4 <= chunks) { chunk_add<4>(v, slab, plane4, i, c); c += 4; }
+    if (c + 2 <= chunks) { chunk_add<2>(v, slab, plane4, i, c); c += 2; }
+    if (c < chunks) chunk_add<1>(v, slab, plane4, i, c);
     dm_store4(slab + 4 * i, v);
   }
 }
@@ -676,13 +799,19 @@ extern "C" int dm_layernorm_fwd(const float *x, const float *gamma, const float 
     return DM_OK;
   }
   const int grid = grid_for((long long)rows, 4, 2048);
-  if (y_dtype == DM_F32)
-    hipLaunchKernelGGL(layernorm_fwd_kernel<float>, dim3(grid), dim3(256), 0, s, x, gamma, beta, (float *)y, mean, rstd, rows, cols, eps);
-  else if (y_dtype == DM_BF16)
-    hipLaunchKernelGGL(layernorm_fwd_kernel<bf16_t>, dim3(grid), dim3(256), 0, s, x, gamma, beta, (bf16_t *)y, mean, rstd, rows, cols, eps);
-  else if (y_dtype == DM_BF16_PAIR)
-    hipLaunchKernelGGL((layernorm_fwd_kernel<bf16_t, true>), dim3(grid), dim3(256), 0, s, x, gamma, beta, (bf16_t *)y, mean, rstd, rows, cols, eps);
+  const bool full3 = cols == 768;      // the encoder's width: three full chunks per lane
+#define DM_LN_FWD(T, PAIR_)                                                                                                                \
+  do {                                                                                                                                     \
+    if (full3)                                                                                                                             \
+      hipLaunchKernelGGL((layernorm_fwd_kernel<T, PAIR_, 3, true>), dim3(grid), dim3(256), 0, s, x, gamma, beta, (T *)y, mean, rstd, rows, cols, eps); \
+    else                                                                                                                                   \
+      hipLaunchKernelGGL((layernorm_fwd_kernel<T, PAIR_, MAXCH, false>), dim3(grid), dim3(256), 0, s, x, gamma, beta, (T *)y, mean, rstd, rows, cols, eps); \
+  } while (0)
+  if (y_dtype == DM_F32) DM_LN_FWD(float, false);
+  else if (y_dtype == DM_BF16) DM_LN_FWD(bf16_t, false);
+  else if (y_dtype == DM_BF16_PAIR) DM_LN_FWD(bf16_t, true);
   else DM_REQUIRE(false, DM_ERR_BAD_DTYPE, "dm_layernorm_fwd: bad y_dtype %d", y_dtype);
+#undef DM_LN_FWD
   DM_LAUNCH_CHECK("dm_layernorm_fwd");
   return DM_OK;
 }
@@ -707,15 +836,21 @@ static int ln_bwd_main(const void *dy, int32_t dy_dtype, const float *x, const f
   }
   const int grid = grid_for((long long)rows, 4, ln_max_wg());
   DM_REQUIRE(dy_dtype == DM_F32 || dy_dtype == DM_BF16, DM_ERR_BAD_DTYPE, "%s: bad dy_dtype %d", who, dy_dtype);
-  const bool narrow = cols <= 768;
-  if (dy_dtype == DM_F32 && narrow)
-    hipLaunchKernelGGL((layernorm_bwd_kernel<float, 3>), dim3(grid), dim3(256), 0, s, (const float *)dy, x, gamma, mean, rstd, dres, dx, (bf16_t *)dx_lp, partial, rows, cols, lp_plane);
-  else if (dy_dtype == DM_F32)
-    hipLaunchKernelGGL((layernorm_bwd_kernel<float, MAXCH>), dim3(grid), dim3(256), 0, s, (const float *)dy, x, gamma, mean, rstd, dres, dx, (bf16_t *)dx_lp, partial, rows, cols, lp_plane);
-  else if (narrow)
-    hipLaunchKernelGGL((layernorm_bwd_kernel<bf16_t, 3>), dim3(grid), dim3(256), 0, s, (const bf16_t *)dy, x, gamma, mean, rstd, dres, dx, (bf16_t *)dx_lp, partial, rows, cols, lp_plane);
-  else
-    hipLaunchKernelGGL((layernorm_bwd_kernel<bf16_t, MAXCH>), dim3(grid), dim3(256), 0, s, (const bf16_t *)dy, x, gamma, mean, rstd, dres, dx, (bf16_t *)dx_lp, partial, rows, cols, lp_plane);
+  // FULL: every lane holds live columns in each of its CH chunks (the encoder's 768 columns): no lane predicate anywhere in the row loop
+  const bool narrow = cols <= 768, full = cols == 768;
+#define DM_LN_BWD(T, CH_, FULL_)                                                                                                      \
+  hipLaunchKernelGGL((layernorm_bwd_kernel<T, CH_, FULL_>), dim3(grid), dim3(256), 0, s, (const T *)dy, x, gamma, mean, rstd, dres, dx, \
+                     (bf16_t *)dx_lp, partial, rows, cols, lp_plane)
+  if (dy_dtype == DM_F32) {
+    if (full) DM_LN_BWD(float, 3, true);
+    else if (narrow) DM_LN_BWD(float, 3, false);
+    else DM_LN_BWD(float, MAXCH, false);
+  } else {
+    if (full) DM_LN_BWD(bf16_t, 3, true);
+    else if (narrow) DM_LN_BWD(bf16_t, 3, false);
+    else DM_LN_BWD(bf16_t, MAXCH, false);
+  }
+#undef DM_LN_BWD
   DM_LAUNCH_CHECK("dm_layernorm_bwd");
   *n_partial = grid;
   return DM_OK;
