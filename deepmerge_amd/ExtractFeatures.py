@@ -114,7 +114,9 @@ class FeatureIO:
     @torch.no_grad()
     def segment_scene(self, source, **kw):
         """From a scene larger than one tile (anything with `.shape == (bands, H, W)` and `.read(y0, y1, x0, x1)`, or a host array
-        / memmap) to the merged partition: `scene.segment_scene(self, source, **kw)`.  Returns a `scene.SceneResult`."""
+        / memmap) to the merged partition: `scene.segment_scene(self, source, **kw)`.  Returns a `scene.SceneResult`.
+        `labels=, n_labels=` bring the scene's superpixels along as a label raster on the host whose regions may cross tile seams
+        (`scene.segment_labels`); they go with no `segmenter`."""
         from . import scene
         return scene.segment_scene(self, source, **kw)
 

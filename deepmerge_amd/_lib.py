@@ -203,6 +203,9 @@ SIGNATURES = {
     "dm_label_clearance": (_I, [_P, _I, _I, _I, _P, _P, _P, _P]),
     "dm_point_select_round": (_I, [_P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P]),
     "dm_point_emit": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P]),
+    "dm_scene_point_init": (_I, [_P, _P, _P, _I, _P]),
+    "dm_scene_point_select": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _L, _L, _L, _L, _I, _I, _I, _P, _P, _P, _P, _P]),
+    "dm_scene_point_commit": (_I, [_P, _L, _L, _I, _I, _P, _P, _P, _P]),
     "dm_label_overlap": (_I, [_P, _P, _I, _I, _L, _L, _P, _P, _I, _P, _P, _I, _P, _P, _P]),
     "dm_overlap_reduce": (_I, [_P, _P, _I, _L, _L, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "dm_pair_flags": (_I, [_P, _I, _P, _P, _P, _I, _I, _P, _P]),

@@ -541,31 +541,59 @@ def mrs(tile: torch.Tensor, scale: float, shape: float = 0.1, compactness: float
     `region_of_at()` work as on any MergeResult.  Stops as `merge_regions` does.  The inputs are not modified; one small readback per
     round."""
     _check_tile(tile)
-    scale = float(scale)
-    if not (math.isfinite(scale) and scale > 0.0):
-        raise ValueError(f"scale must be finite and > 0, got {scale}")
     bands, H, W = tile.shape
-    shape, compactness, bw = _mrs_params(min(bands, 3), shape, compactness, band_weights)
-    if max_rounds is not None and max_rounds < 0:
-        raise ValueError("max_rounds must be >= 0 or None")
+    _mrs_check(scale, min(bands, 3), shape, compactness, band_weights, max_rounds)
     if labels is None:
         if n_labels is not None:
             raise ValueError("n_labels goes with labels")
         stats, edges, weights = pixel_regions(tile)
-        S0 = H * W
     else:
         _on_device(labels)
         if labels.dtype != torch.int32 or tuple(labels.shape) != (H, W):
             raise ValueError("labels must be int32 [H,W] over the tile's raster")
         if n_labels is None or not 1 <= int(n_labels) <= MAX_REGIONS:
             raise ValueError(f"n_labels must be given with labels, 1 to 2^24, got {n_labels}")
-        S0 = int(n_labels)
-        stats = label_stats(labels, tile, S0)
-        if bool((stats["count"] == 0).any()):                    # (the one readback before round 1)
-            raise ValueError("mrs: every id in [0, n_labels) must occur in labels (a region without pixels has no cost)")
-        edges, weights = rag_edges(labels, S0)
-        edges, weights = edges.contiguous(), weights.contiguous()
-    nb, dev, lib = stats["bands"], tile.device, _lib.lib()
+        stats = label_stats(labels, tile, int(n_labels))
+        _check_no_empty_region(stats)                            # (the one readback before round 1)
+        edges, weights = rag_edges(labels, int(n_labels))
+    return mrs_graph(stats, edges, weights, scale, shape, compactness, band_weights, max_rounds, min_regions, _checked=True)
+
+
+def _mrs_check(scale, nb: int, shape, compactness, band_weights, max_rounds) -> Tuple[float, float, float, List[float]]:
+    """The arguments `mrs` and `mrs_graph` share, each a ValueError before any device work."""
+    scale = float(scale)
+    if not (math.isfinite(scale) and scale > 0.0):
+        raise ValueError(f"scale must be finite and > 0, got {scale}")
+    shape, compactness, bw = _mrs_params(nb, shape, compactness, band_weights)
+    if max_rounds is not None and max_rounds < 0:
+        raise ValueError("max_rounds must be >= 0 or None")
+    return scale, shape, compactness, bw
+
+
+def _check_no_empty_region(stats: Dict[str, torch.Tensor]):
+    if bool((stats["count"] == 0).any()):
+        raise ValueError("mrs: every id in [0, n_labels) must occur in labels (a region without pixels has no cost)")
+
+
+def mrs_graph(stats: Dict[str, torch.Tensor], edges: torch.Tensor, weights: torch.Tensor, scale: float, shape: float = 0.1,
+              compactness: float = 0.5, band_weights=None, max_rounds: Optional[int] = None, min_regions: int = 0,
+              _checked: bool = False) -> MergeResult:
+    """The rounds of `mrs` on a graph that is already built: stats as `label_stats` returns them (every region with count > 0,
+    else ValueError), edges int32 [E,2] with a < b, sorted and unique, weights int32 [E] as `rag_edges` returns them.  `mrs` builds
+    its graph from one raster and calls this; `scene.mrs_labels` builds it from a scene's label raster tile by tile.  The inputs
+    are not modified."""
+    _on_device(edges, weights, *(stats[k] for k in _STAT_KEYS))
+    S0 = stats["count"].numel()
+    nb = _check_stats(stats, S0)
+    scale, shape, compactness, bw = _mrs_check(scale, nb, shape, compactness, band_weights, max_rounds)
+    if not 1 <= S0 <= MAX_REGIONS:
+        raise ValueError(f"mrs_graph takes 1 to 2^24 regions, got {S0}")
+    if edges.dtype != torch.int32 or edges.dim() != 2 or edges.shape[1] != 2 or weights.dtype != torch.int32 or tuple(weights.shape) != (edges.shape[0],):
+        raise ValueError("edges must be int32 [E,2] and weights int32 [E]")
+    if not _checked:
+        _check_no_empty_region(stats)
+    edges, weights = edges.contiguous(), weights.contiguous()
+    dev, lib = edges.device, _lib.lib()
 
     def score(cur, C, E, simi, stream):
         if E:

@@ -14,8 +14,15 @@ counted as "raster border" although another label faces them -- is added by one 
 a batch: the batches of a scene break at tile boundaries.)
 
 Known consequence: where the learned merge does not join two superpixels across a seam, a straight boundary stays on the seam
-line.  Out of scope: superpixels that cross seams; a user label raster whose regions cross seams; `rag.mrs` on a scene graph;
-overlapping the copy of the next tile with compute.
+line; superpixels brought along as a label raster avoid it (below).  Out of scope: superpixels MADE HERE that cross seams; a
+pixel-start `rag.mrs` on a scene; overlapping the copy of the next tile with compute.
+
+Superpixels from a label raster.  `segment_labels` (`segment_scene(..., labels=, n_labels=)`) takes the scene's
+superpixels as an int32 raster on the host whose regions know nothing of the tile grid -- those of external GIS software, or an
+earlier merge's result -- and returns what `FeatureIO.merge_tile` returns on the whole scene, bit for bit, whatever the tile size.
+Statistics and edges are folded over the tiles a region lies in (`label_graph`), the seam stitch meets equal ids on both sides of
+a seam, and the sample points are a scene-wide per-region maximum over k passes (`sample_points`, csrc/dm_scene_points.hip).
+`mrs_labels` runs the classical baseline `rag.mrs` on the same graph.
 
 Rings and arcs.  `trace_labels` traces a scene's label raster -- the merged raster through
 `SceneResult.trace` -- into the rings and arcs `rag._trace` gives on the whole raster, array for array and bit for bit, whatever
@@ -241,13 +248,15 @@ def _scene_graph(source, tile=4096, segmenter: Optional[Callable] = None, k: int
 @dataclass
 class SceneResult:
     """What `segment_scene` leaves.  result: the MergeResult of the one merge over the scene; n_labels: superpixels of the scene;
-    tiles: the cores (y0, y1, x0, x1), row-major; offsets [T+1]: tile i owns the scene-wide ids offsets[i] .. offsets[i+1]-1;
+    tiles: the cores (y0, y1, x0, x1), row-major; offsets [T+1]: tile i owns the scene-wide ids offsets[i] .. offsets[i+1]-1, or
+    None when the superpixels come from a label raster whose regions cross seams (`segment_labels`: no tile owns an id);
     stats / designed / edges / weights: `label_stats`, `designed_features` and `rag_edges` of the scene; points: a PointSamples in
-    scene coordinates; features [P,100]: the encoder's rows; labels: the scene-wide superpixel raster (`labels_out`, on the host)."""
+    scene coordinates; features [P,100]: the encoder's rows; labels: the scene-wide superpixel raster on the host (`labels_out`,
+    or what `segment_labels` was given: an array, or anything with `.shape` and `.read`)."""
     result: "rag.MergeResult"
     n_labels: int
     tiles: List[Core]
-    offsets: List[int]
+    offsets: Optional[List[int]]
     stats: Dict[str, torch.Tensor]
     designed: torch.Tensor
     edges: torch.Tensor
@@ -257,8 +266,7 @@ class SceneResult:
     labels: np.ndarray
 
     def _tile_labels(self, i: int) -> torch.Tensor:
-        y0, y1, x0, x1 = self.tiles[i]
-        return torch.from_numpy(np.ascontiguousarray(self.labels[y0:y1, x0:x1])).to(self.edges.device)
+        return _read(_as_source(self.labels), self.tiles[i], torch.int32, 2, self.edges.device)
 
     def merged_tile(self, i: int) -> torch.Tensor:
         """int32 [th,tw] on the device: tile i of the merged raster, `relabel_raster` of its superpixels with `result.region_of`."""
@@ -266,7 +274,7 @@ class SceneResult:
 
     def write_merged(self, out=None) -> np.ndarray:
         """Streams every tile of the merged raster into `out`, a writable int32 [H,W] numpy array or memmap (allocated if None)."""
-        H, W = self.labels.shape
+        H, W = (int(v) for v in self.labels.shape)
         if out is None:
             out = np.empty((H, W), dtype=np.int32)
         elif not isinstance(out, np.ndarray) or out.dtype != np.int32 or out.shape != (H, W) or not out.flags.writeable:
@@ -334,24 +342,38 @@ class SceneResult:
         """The `Overlap` of the scene's superpixels with a ground-truth raster (int32 [H,W]: an array, a memmap, a CPU tensor, or
         anything with `.read(y0, y1, x0, x1)` returning int32 [y1-y0, x1-x0]), for `result.scores(...)`: per tile one
         `rag.label_overlap` with tile-local ids (so that every table is sized for one tile), keys shifted to scene-wide ids and
-        concatenated, then the facts of the whole table.  Equals `rag.label_overlap` on the assembled rasters field by field."""
+        concatenated, then the facts of the whole table.  Equals `rag.label_overlap` on the assembled rasters field by field.
+        Without `offsets` (regions cross seams) the tile-local ids come from compacting the ids present in the tile, and a cell
+        that several tiles hold is folded, counts added."""
         truth_source = _as_source(truth_source)
         G, dev = int(n_truth), self.edges.device
         keys, counts = [], []
         for i, core in enumerate(self.tiles):
-            off, n = self.offsets[i], self.offsets[i + 1] - self.offsets[i]
             truth = _read(truth_source, core, torch.int32, 2, dev)
             glob = self._tile_labels(i)
-            local = torch.where(glob >= 0, glob - off, glob)
-            ov = rag.label_overlap(local, truth, n, G)
-            keys.append((ov.cells[:, 0].long() + off) * (G + 1) + ov.cells[:, 1].long())
+            if self.offsets is None:
+                local, ids = _compact_ids(glob, self.n_labels)
+                if ids.numel() == 0:
+                    continue
+                ov = rag.label_overlap(local, truth, int(ids.numel()), G)
+                keys.append(ids[ov.cells[:, 0].long()] * (G + 1) + ov.cells[:, 1].long())
+            else:
+                off, n = self.offsets[i], self.offsets[i + 1] - self.offsets[i]
+                local = torch.where(glob >= 0, glob - off, glob)
+                ov = rag.label_overlap(local, truth, n, G)
+                keys.append((ov.cells[:, 0].long() + off) * (G + 1) + ov.cells[:, 1].long())
             counts.append(ov.count)
-        return rag._overlap_facts(torch.cat(keys), torch.cat(counts), self.n_labels, G)        # sorted: offsets ascend
+        if self.offsets is not None:
+            return rag._overlap_facts(torch.cat(keys), torch.cat(counts), self.n_labels, G)    # sorted: offsets ascend
+        empty = torch.empty(0, dtype=torch.int64, device=dev)
+        uniq, inverse = torch.unique(torch.cat(keys + [empty]), return_inverse=True)           # sorted
+        folded = torch.zeros(uniq.numel(), dtype=torch.int32, device=dev).index_add_(0, inverse, torch.cat(counts + [empty.to(torch.int32)]))
+        return rag._overlap_facts(uniq, folded, self.n_labels, G)
 
 
 def segment_scene(fio, source, tile=4096, segmenter: Optional[Callable] = None, k: int = 3, margin: float = 1.0,
                   max_window: int = rag.MAX_WINDOW, batch_size: int = 2000, labels_out=None, stage_times: Optional[dict] = None,
-                  **merge_kwargs) -> SceneResult:
+                  labels=None, n_labels: Optional[int] = None, **merge_kwargs) -> SceneResult:
     """From a scene of any size to its merged partition (the module docstring states the definition).
 
     fio: a FeatureIO; source: `.shape == (bands, H, W)` and `.read(y0, y1, x0, x1) -> uint8 [bands, y1-y0, x1-x0]` (a numpy
@@ -360,7 +382,18 @@ def segment_scene(fio, source, tile=4096, segmenter: Optional[Callable] = None, 
     defaults (ids outside [0, n) are written as -1, "no superpixel"); k, max_window: as `rag.sample_points` takes them; margin,
     merge_kwargs: as `rag.merge_regions` takes them; labels_out: a writable int32 [H,W] numpy array or memmap for the scene-wide
     superpixel raster, allocated if None; stage_times: a dict that receives seconds per stage (synchronises at stage boundaries).
+    labels, n_labels: the scene's superpixels brought along as a label raster on the host, whose regions may cross seams: the call
+    is `segment_labels(fio, source, labels, n_labels, ...)` (no segmenter and no labels_out go with it: ValueError).
     Limits: at most 2^24 superpixels in the scene, every window (core + halo) below 2^31 pixels."""
+    if labels is not None:
+        if segmenter is not None or labels_out is not None:
+            raise ValueError("labels= brings the scene's superpixels along: it takes neither a segmenter nor labels_out")
+        if n_labels is None:
+            raise ValueError("n_labels must be given with labels")
+        return segment_labels(fio, source, labels, n_labels, tile=tile, k=k, margin=margin, max_window=max_window, batch_size=batch_size,
+                              stage_times=stage_times, **merge_kwargs)
+    if n_labels is not None:
+        raise ValueError("n_labels goes with labels")
     g = _scene_graph(source, tile, segmenter, k, max_window, labels_out, device=fio.device, stage_times=stage_times)
     dev, pts, H, W = g["device"], g["points"], g["labels"].shape[0], g["labels"].shape[1]
     clock = _Clock(stage_times, dev)
@@ -384,6 +417,227 @@ def segment_scene(fio, source, tile=4096, segmenter: Optional[Callable] = None, 
     clock.lap("merge")
     return SceneResult(result=result, n_labels=g["n_labels"], tiles=g["tiles"], offsets=g["offsets"], stats=g["stats"], designed=g["designed"],
                        edges=g["edges"], weights=g["weights"], points=pts, features=features, labels=g["labels"])
+
+
+# ---- a scene from a label raster whose regions cross tile seams (csrc/dm_scene_points.hip) ------------------------
+MAX_POINT_SCENE = 1 << 48             # DM_SCENE_POINTS_MAX_PIXELS: the key keeps 2^48 - 1 - (y W + x) in 48 bits
+MAX_SCENE_SIDE = (1 << 31) - 1        # points and boxes are int32
+
+
+def _check_labels(labels, n_labels, k, max_window, tile, like: Optional[tuple] = None):
+    """The limits of the calls below, each a ValueError before any device work.  labels: the label source; like: the (H, W) the
+    raster must have (the image's).  Returns (H, W, S, k, tiles, halo)."""
+    shape = tuple(labels.shape)
+    if len(shape) != 2 or min(shape) < 1:
+        raise ValueError(f"labels.shape must be (H, W) with H, W >= 1, got {shape}")
+    H, W = (int(v) for v in shape)
+    if like is not None and (H, W) != tuple(like):
+        raise ValueError(f"labels must cover the scene: labels.shape = ({H}, {W}), the source has {like[0]} x {like[1]} pixels")
+    if H > MAX_SCENE_SIDE or W > MAX_SCENE_SIDE or H * W > MAX_POINT_SCENE:
+        raise ValueError(f"the scene must have H, W < 2^31 and at most 2^48 pixels (the points' 64-bit key), got {H} x {W}")
+    S = int(n_labels)
+    if not 1 <= S <= rag.MAX_REGIONS:
+        raise ValueError(f"n_labels must be in 1..2^24, got {n_labels}")
+    if not 1 <= int(k) <= rag.MAX_POINTS:
+        raise ValueError(f"k must be in 1..{rag.MAX_POINTS}, got {k}")
+    if not 1 <= int(max_window) <= rag.MAX_WINDOW:
+        raise ValueError(f"max_window must be in 1..{rag.MAX_WINDOW}, got {max_window}")
+    th, tw = (tile, tile) if isinstance(tile, int) else tuple(tile)
+    if int(th) < 1 or int(tw) < 1:
+        raise ValueError(f"tile must be >= 1, got {tile}")
+    halo = halo_of(max_window)
+    # a window's height depends on its tile row only, its width on its column only
+    side = lambda n, t: max(min(n, y + int(t) + halo) - max(0, y - halo) for y in range(0, n, int(t)))
+    side_y, side_x = side(H, th), side(W, tw)
+    if side_y * side_x >= 1 << 31:
+        raise ValueError(f"a tile's window (core + halo of {halo}) must have fewer than 2^31 pixels, got {side_y} x {side_x}")
+    return H, W, S, int(k), tile_grid(H, W, tile), halo
+
+
+def point_tiles(xy: torch.Tensor, W: int, tile) -> torch.Tensor:
+    """int64 [P]: the row-major index in `tile_grid(H, W, tile)` of the tile whose core holds every point (x, y) of xy [P,2]."""
+    th, tw = (tile, tile) if isinstance(tile, int) else tuple(tile)
+    nx = (int(W) + int(tw) - 1) // int(tw)
+    return torch.div(xy[:, 1].long(), int(th), rounding_mode="floor") * nx + torch.div(xy[:, 0].long(), int(tw), rounding_mode="floor")
+
+
+def _compact_ids(labels: torch.Tensor, n_labels: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(local int32 like labels, ids int64 [n] ascending): the ids of [0, n_labels) present in `labels` numbered 0..n-1 in
+    ascending order, every other id -1 ("no superpixel"), so that the per-tile tables are sized for the tile, not for the scene."""
+    u, inverse = torch.unique(labels, return_inverse=True)
+    ok = (u >= 0) & (u < n_labels)
+    local_of = torch.where(ok, torch.cumsum(ok, 0) - 1, torch.full_like(u, -1, dtype=torch.int64)).to(torch.int32)
+    return local_of[inverse].contiguous(), u[ok].long()
+
+
+def sample_points(labels, n_labels: int, k: int = 3, max_window: int = rag.MAX_WINDOW, tile=4096, device="cuda:0",
+                  stage_times: Optional[dict] = None) -> "rag.PointSamples":
+    """`rag.sample_points` on a scene's label raster, equal in every field whatever the tile size, although a region's pixels lie in
+    several tiles (csrc/dm_scene_points.hip; the rule: include/deepmerge_hip.h).
+
+    labels: int32 [H, W] on the host -- an array, an `np.memmap`, a CPU tensor, or anything with `.shape == (H, W)` and
+    `.read(y0, y1, x0, x1) -> int32 [y1-y0, x1-x0]`; ids outside [0, n_labels) get no points.  The tables (best, points, counts,
+    boxes: 8 + 12 k + 20 bytes per superpixel) stay on the device; per round every tile's halo window of labels is read, its
+    clearance taken and its core's candidates folded in, then the round's scene-wide winners are committed: k passes over the
+    label raster, because round j + 1 scores against round j's winners.  Limits, each a ValueError before any device work: H, W <
+    2^31 and H W <= 2^48; n_labels in 1..2^24; k in 1..16; max_window in 1..384; every window below 2^31 pixels."""
+    source = _as_source(labels)
+    H, W, S, k, tiles, halo = _check_labels(source, n_labels, k, max_window, tile)
+    dev, lib, i32 = torch.device(device), _lib.lib(), torch.int32
+    clock = _Clock(stage_times, dev)
+    best = torch.empty(S, dtype=torch.int64, device=dev)
+    pts = torch.empty((S, k, 2), dtype=i32, device=dev)
+    pclr = torch.empty((S, k), dtype=i32, device=dev)
+    cnt = torch.empty(S, dtype=i32, device=dev)
+    bbox = torch.empty((S, 4), dtype=i32, device=dev)
+    for j in range(k):
+        for i, core in enumerate(tiles):
+            y0, y1, x0, x1 = core
+            wy0, wy1, wx0, wx1 = box = window_of(core, H, W, halo)
+            window = _read(source, box, i32, 2, dev).contiguous()
+            clock.lap("read + copy")
+            clr = rag.clearance(window, max_window)
+            if i == 0 and j == 0:                                # (behind the first read: a source of the wrong kind fails before any launch)
+                check(lib.dm_scene_point_init(best.data_ptr(), cnt.data_ptr(), bbox.data_ptr(), S, _stream()), "dm_scene_point_init")
+            check(lib.dm_scene_point_select(window.data_ptr(), clr.data_ptr(), wy1 - wy0, wx1 - wx0, y0 - wy0, y1 - wy0, x0 - wx0, x1 - wx0,
+                                            wy0, wx0, H, W, S, k, j, pts.data_ptr(), cnt.data_ptr(), best.data_ptr(), bbox.data_ptr(),
+                                            _stream()), "dm_scene_point_select")
+            clock.lap(f"points round {j}")
+        check(lib.dm_scene_point_commit(best.data_ptr(), H, W, S, k, pts.data_ptr(), pclr.data_ptr(), cnt.data_ptr(), _stream()),
+              "dm_scene_point_commit")
+        clock.lap(f"points round {j}")
+    cap = S * k
+    ptr = torch.empty(S + 1, dtype=i32, device=dev)
+    xy = torch.empty((cap, 2), dtype=i32, device=dev)
+    label, inner, obj, rnd = (torch.empty(cap, dtype=i32, device=dev) for _ in range(4))
+    check(lib.dm_point_emit(cnt.data_ptr(), pts.data_ptr(), pclr.data_ptr(), bbox.data_ptr(), S, k, int(max_window), cap, ptr.data_ptr(),
+                            xy.data_ptr(), label.data_ptr(), inner.data_ptr(), obj.data_ptr(), rnd.data_ptr(), _stream()), "dm_point_emit")
+    P = int(ptr[S])                                            # the one readback: sizes the views below
+    clock.lap("points emit")
+    return rag.PointSamples(xy=xy[:P], label=label[:P], inner=inner[:P], obj=obj[:P], ptr=ptr, idx=torch.arange(P, dtype=i32, device=dev),
+                            bbox=bbox, round=rnd[:P])
+
+
+def label_graph(source, labels, n_labels: int, tile=4096, k: int = 3, max_window: int = rag.MAX_WINDOW, device="cuda:0",
+                stage_times: Optional[dict] = None, points: bool = True) -> dict:
+    """The net-free pass of `segment_labels`: the dict `_scene_graph` returns, with `offsets` and `point_offsets` None, for
+    superpixels that come as a label raster on the host and may cross seams.  Per core the ids present are compacted
+    (`torch.unique`), `label_stats` and `rag_edges` run on the tile-local ids and are folded into the scene's tables (counts, sums
+    and perimeters add, boxes take min / max, the empty box folds to whatever it meets); then one `rag.seam_stitch` over all seams
+    (equal ids facing each other lose the border edge: a region that crosses the seam), one sort of the edge keys with the
+    weights of equal keys added (a pair can occur in several tiles and on seams), the designed features, and `sample_points`
+    (points=False leaves it out: `mrs_labels`).  `n_edge_parts` is the number of edge rows before the fold."""
+    source, lsource = _as_source(source), _as_source(labels)
+    shape = tuple(source.shape)
+    if len(shape) != 3 or min(shape) < 1:
+        raise ValueError(f"source.shape must be (bands, H, W) with bands, H, W >= 1, got {shape}")
+    bands = int(shape[0])
+    H, W, S, k, tiles, halo = _check_labels(lsource, n_labels, k, max_window, tile, like=(int(shape[1]), int(shape[2])))
+    dev, i32, i64 = torch.device(device), torch.int32, torch.int64
+    nx = sum(1 for t in tiles if t[0] == 0)
+    ny = len(tiles) // nx
+    nb = min(bands, 3)
+    clock = _Clock(stage_times, dev)
+    stats = {"count": torch.zeros(S, dtype=i64, device=dev), "sum": torch.zeros((S, nb), dtype=i64, device=dev),
+             "sumsq": torch.zeros((S, nb), dtype=i64, device=dev), "peri": torch.zeros((S, 2), dtype=i64, device=dev),
+             "bbox": torch.tensor([(1 << 31) - 1, (1 << 31) - 1, -1, -1], dtype=i32, device=dev).repeat(S, 1)}
+    key_parts, weight_parts, strips = [], [], []
+    for i, core in enumerate(tiles):
+        y0, y1, x0, x1 = core
+        lab = _read(lsource, core, i32, 2, dev)                  # (the labels first: a source of the wrong kind fails before any copy)
+        core_tile = _read(source, core, torch.uint8, 3, dev)
+        clock.lap("read + copy")
+        local, ids = _compact_ids(lab, S)
+        n = int(ids.numel())
+        glob = torch.where(local >= 0, lab, local)               # ids outside [0, S): "no superpixel"
+        clock.lap("compact")
+        if n:
+            st = rag.label_stats(local, core_tile, n)
+            e, w = rag.rag_edges(local, n)
+            for key in ("count", "sum", "sumsq", "peri"):
+                stats[key].index_add_(0, ids, st[key])
+            box = st["bbox"] + torch.tensor([x0, y0, x0, y0], dtype=i32, device=dev)       # every local id has pixels: no empty box
+            seen = stats["bbox"][ids]
+            stats["bbox"][ids] = torch.cat((torch.minimum(seen[:, :2], box[:, :2]), torch.maximum(seen[:, 2:], box[:, 2:])), 1)
+            key_parts.append(ids[e[:, 0].long()] * S + ids[e[:, 1].long()])               # ids ascend: a < b stays a < b
+            weight_parts.append(w)
+        strips.append((glob[0].clone(), glob[-1].clone(), glob[:, 0].clone(), glob[:, -1].clone()))      # top, bottom, left, right
+        clock.lap("graph")
+    stats["bands"] = nb
+    sa, sb = [], []
+    for r in range(ny):
+        for c in range(nx):
+            top, bottom, left, right = strips[r * nx + c]
+            if c + 1 < nx:
+                sa.append(right); sb.append(strips[r * nx + c + 1][2])
+            if r + 1 < ny:
+                sa.append(bottom); sb.append(strips[(r + 1) * nx + c][0])
+    empty = torch.empty(0, dtype=i32, device=dev)
+    a, b = (torch.cat(sa), torch.cat(sb)) if sa else (empty, empty)
+    seam_edges, seam_weights = rag.seam_stitch(a, b, S, stats["peri"], max_edges=max(1024, min(8 * S, int(a.numel()))))
+    clock.lap("stitch")
+    keys = torch.cat(key_parts + [seam_edges[:, 0].long() * S + seam_edges[:, 1].long()])
+    uniq, inverse = torch.unique(keys, return_inverse=True)      # sorted by (a, b); equal keys of several tiles and seams fold
+    weights = torch.zeros(uniq.numel(), dtype=i32, device=dev).index_add_(0, inverse, torch.cat(weight_parts + [seam_weights]))
+    edges = torch.stack((uniq // S, uniq % S), 1).to(i32).contiguous()
+    designed = rag.designed_features(stats)                      # only now: `peri` and `border` need the seam fix
+    clock.lap("graph")
+    pts = sample_points(lsource, S, k=k, max_window=max_window, tile=tile, device=dev, stage_times=stage_times) if points else None
+    return dict(n_labels=S, tiles=tiles, offsets=None, point_offsets=None, stats=stats, designed=designed, edges=edges, weights=weights,
+                points=pts, labels=labels if isinstance(labels, np.ndarray) else lsource, halo=halo, n_seam=int(a.numel()),
+                n_seam_edges=int(seam_edges.shape[0]), n_edge_parts=int(keys.numel()), source=source, device=dev)
+
+
+def segment_labels(fio, source, labels, n_labels: int, tile=4096, k: int = 3, margin: float = 1.0, max_window: int = rag.MAX_WINDOW,
+                   batch_size: int = 2000, stage_times: Optional[dict] = None, **merge_kwargs) -> SceneResult:
+    """`segment_scene` for superpixels that are brought along: from a scene and its label raster (int32 [H, W] on the host, ids
+    0..n_labels-1, anything else "no superpixel"; regions may cross tile seams, as those of external GIS software or of an earlier
+    merge do) to the merged partition.  Returns, bit for bit and layer by layer, what `FeatureIO.merge_tile(whole scene, whole
+    raster, n_labels, ...)` returns, whatever the tile size (the encoder's rows at equal batch shapes).
+
+    source, tile, k, margin, max_window, batch_size, stage_times, merge_kwargs: as `segment_scene` takes them; labels: as
+    `sample_points` takes it.  A point is encoded with the tile whose core holds it, from that tile's halo window; the rows go back
+    by index, so the points stay sorted by (superpixel, round) scene-wide.  The result's `offsets` is None.  Limits: those of
+    `sample_points`; an id that never occurs has count 0, the empty box and no points."""
+    g = label_graph(source, labels, n_labels, tile=tile, k=k, max_window=max_window, device=fio.device, stage_times=stage_times)
+    dev, pts, tiles = g["device"], g["points"], g["tiles"]
+    H, W = tiles[-1][1], tiles[-1][3]
+    clock = _Clock(stage_times, dev)
+    P = pts.xy.shape[0]
+    if P < 1:
+        raise ValueError("the scene has no sample point (no pixel carries a superpixel id)")
+    tile_of = point_tiles(pts.xy, W, tile)
+    order = torch.argsort(tile_of, stable=True)                  # within a tile the rows keep their (superpixel, round) order
+    ends = torch.cumsum(torch.bincount(tile_of, minlength=len(tiles)), 0).tolist()
+    features = torch.empty((P, 100), dtype=torch.float32, device=dev)
+    for i, core in enumerate(tiles):
+        rows = order[(ends[i - 1] if i else 0):ends[i]]
+        if rows.numel() == 0:
+            continue
+        wy0, wy1, wx0, wx1 = box = window_of(core, H, W, g["halo"])
+        window = _read(g["source"], box, torch.uint8, 3, dev)
+        clock.lap("read + copy")
+        origin = torch.tensor([wx0, wy0], dtype=torch.int32, device=dev)
+        features[rows] = fio.extract_features_from_tile(window, pts.xy[rows] - origin, pts.inner[rows], pts.obj[rows],
+                                                        g["designed"][pts.label[rows].long()], batch_size=batch_size)
+        clock.lap("encode")
+    fio.features = features
+    result = rag.merge_regions(features, pts.ptr, pts.idx, g["edges"], margin=margin, weights=g["weights"], stats=g["stats"], **merge_kwargs)
+    clock.lap("merge")
+    return SceneResult(result=result, n_labels=g["n_labels"], tiles=tiles, offsets=None, stats=g["stats"], designed=g["designed"],
+                       edges=g["edges"], weights=g["weights"], points=pts, features=features, labels=g["labels"])
+
+
+def mrs_labels(source, labels, n_labels: int, scale: float, shape: float = 0.1, compactness: float = 0.5, band_weights=None,
+               max_rounds: Optional[int] = None, min_regions: int = 0, tile=4096, device="cuda:0",
+               stage_times: Optional[dict] = None) -> "rag.MergeResult":
+    """The classical baseline on a scene's graph: `rag.mrs(whole scene, scale, labels=whole raster, n_labels=n_labels, ...)` bit
+    for bit, whatever the tile size -- `label_graph` without points, then `rag.mrs_graph`.  Every id in [0, n_labels) must occur
+    (the same ValueError).  A pixel start on a scene stays out of scope: a merge takes at most 2^24 regions."""
+    shape3 = tuple(_as_source(source).shape)
+    rag._mrs_check(scale, min(int(shape3[0]), 3) if len(shape3) == 3 and shape3[0] >= 1 else 1, shape, compactness, band_weights, max_rounds)
+    g = label_graph(source, labels, n_labels, tile=tile, k=1, device=device, stage_times=stage_times, points=False)
+    return rag.mrs_graph(g["stats"], g["edges"], g["weights"], scale, shape, compactness, band_weights, max_rounds, min_regions)
 
 
 # ---- rings and arcs across tile seams (DESIGN.md 3.5.10; csrc/dm_scene_vector.hip) ---------------------------------------------------

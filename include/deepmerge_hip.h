@@ -477,12 +477,14 @@ int dm_rag_edges(const int32_t *labels, int32_t H, int32_t W, int32_t S, int64_t
  * The rule.  a, b int32 [n]: a[i] and b[i] are the scene-wide ids of the two pixels that face each other across seam position
  * i; all seams of the scene are concatenated, in any order.  1 <= n, 1 <= S <= 2^24.
  *   edges: every position with both ids in [0,S) and a[i] != b[i] adds 1 to key min*S + max: dm_rag_edges' key and count for a
- *     4-neighbour pair, through the same table.  The pairs are disjoint from every tile's own (a tile's pairs lie inside it).
+ *     4-neighbour pair, through the same table.  With per-tile superpixels the pairs are disjoint from every tile's own (a
+ *     tile's pairs lie inside it); with a label raster whose regions cross seams (scene.label_graph) a pair can
+ *     occur in several tiles and on seams, and the caller adds the weights of equal keys.
  *   perimeter: peri int64 [S,2] holds dm_label_stats' peri of every tile, concatenated.  The tile counted the pixel edge of
  *     a[i] that faces b[i] in column 1 (raster border); dm_label_stats on the scene would see the neighbour b[i].  So, for the
  *     side l = a[i] facing f = b[i], and likewise for l = b[i] facing f = a[i], when l is in [0,S):
  *       f == -2 (dm_label_stats' marker for "outside the raster"): nothing moves;
- *       f == l: column 1 loses the edge (inside a raster, equal neighbours share no perimeter);
+ *       f == l: column 1 loses the edge (inside a raster, equal neighbours share no perimeter): a region that crosses the seam;
  *       any other f, ids outside [0,S) such as -1 included: the edge moves from column 1 to column 0 ("another label").
  *     A side whose own id is outside [0,S) has no row in peri and moves nothing.
  * Integer adds only: nothing depends on arrival order.  table_* / edge_* / n_edges / overflow: as dm_rag_edges takes them
@@ -625,6 +627,37 @@ int dm_point_select_round(const int32_t *labels, const uint16_t *clearance, int3
 int dm_point_emit(const int32_t *counts, const int32_t *points, const int32_t *point_clearance, const int32_t *bbox, int32_t S, int32_t k,
                   int32_t max_window, int32_t capacity, int32_t *ptr, int32_t *xy, int32_t *label, int32_t *inner, int32_t *obj,
                   int32_t *round, void *stream);
+
+/* ---- sample points of a scene's label raster across tile seams (additive in ABI 7; csrc/dm_scene_points.hip, DESIGN.md 3.5.14,
+ * scene.sample_points) ---------------------------------------------------------------------------------------------------------
+ * A scene's label raster lives on the host and its regions know nothing of the tile grid: a region's pixels lie in several
+ * tiles.  The rule is the points rule above, word for word, with "linear index" read as the SCENE's y*W + x and every distance
+ * taken in scene coordinates, so the result equals dm_point_select_round / dm_point_emit on the whole raster bit for bit,
+ * whatever the tiles.  Scene: H, W < 2^31 and H*W <= 2^48 (DM_SCENE_POINTS_MAX_PIXELS).
+ *   state, scene-wide, on the device for all rounds: best uint64 [S], points int32 [S,k,2] = (x, y) in scene coordinates,
+ *     point_clearance int32 [S,k], counts int32 [S], bbox int32 [S,4] in scene coordinates (INT_MAX,INT_MAX,-1,-1: never occurs).
+ *   a round j = 0..k-1: dm_scene_point_select once per tile, in any order, then dm_scene_point_commit once.  Round j + 1 reads
+ *     round j's committed points, so a scene costs k passes over its label raster.
+ *   window: labels int32 [wh,ww] and clearance uint16 [wh,ww] = dm_label_clearance of THAT window, wh*ww < 2^31, whose first
+ *     pixel is (oy, ox) of the scene.  Only the core rows cy0..cy1-1, columns cx0..cx1-1 of the window are candidates; the
+ *     cores of a round's calls must partition the scene.  The window must reach (max_window + 1) / 2 pixels beyond the core
+ *     on every side, clipped to the scene: then the window's clearance at a core pixel is the scene's (the cap equals that
+ *     reach, and beyond a clipped side lies the outside of the scene).
+ *   the key: bits 56..63 the score (<= cap <= 192), bits 8..55 2^48 - 1 - linear index, bits 0..7 the pixel's clearance, a
+ *     passenger behind a unique position.  One unsigned 64-bit max per superpixel: largest score, then smallest scene linear
+ *     index.  The commit reads position and clearance out of the key: it needs no raster and no tile resident.
+ * dm_scene_point_init: best and counts to 0, bbox to the empty box; once, before round 0.
+ * dm_scene_point_select: one tile's part of round `round`; round 0 also folds the core's pixels into bbox.
+ * dm_scene_point_commit: every superpixel with a winner gets its next point; best is cleared for the next round.
+ * dm_point_emit then runs unchanged on the scene's tables.  Every entry point validates before any launch, launches on
+ * `stream`, never synchronises and never allocates. */
+#define DM_SCENE_POINTS_MAX_PIXELS (1LL << 48)
+int dm_scene_point_init(uint64_t *best, int32_t *counts, int32_t *bbox, int32_t S, void *stream);
+int dm_scene_point_select(const int32_t *labels, const uint16_t *clearance, int32_t wh, int32_t ww, int32_t cy0, int32_t cy1,
+                          int32_t cx0, int32_t cx1, int64_t oy, int64_t ox, int64_t scene_h, int64_t scene_w, int32_t S, int32_t k,
+                          int32_t round, const int32_t *points, const int32_t *counts, uint64_t *best, int32_t *bbox, void *stream);
+int dm_scene_point_commit(uint64_t *best, int64_t scene_h, int64_t scene_w, int32_t S, int32_t k, int32_t *points,
+                          int32_t *point_clearance, int32_t *counts, void *stream);
 
 /* ---- overlap of a label raster with a ground-truth raster: pair labels and partition scores (additive in ABI 6;
  * csrc/dm_truth.hip, DESIGN.md 3.5.3, rag.label_overlap / rag.pair_flags / Overlap.scores) ----------------------------------------
