@@ -116,7 +116,8 @@ class FeatureIO:
         """From a scene larger than one tile (anything with `.shape == (bands, H, W)` and `.read(y0, y1, x0, x1)`, or a host array
         / memmap) to the merged partition: `scene.segment_scene(self, source, **kw)`.  Returns a `scene.SceneResult`.
         `labels=, n_labels=` bring the scene's superpixels along as a label raster on the host whose regions may cross tile seams
-        (`scene.segment_labels`); they go with no `segmenter`."""
+        (`scene.segment_labels`); they go with no `segmenter`.  `cross_seams=True, slic={...}` makes such superpixels here
+        (`scene.slic_labels`, then `scene.segment_labels`); it goes with neither."""
         from . import scene
         return scene.segment_scene(self, source, **kw)
 

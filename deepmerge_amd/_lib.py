@@ -213,6 +213,9 @@ SIGNATURES = {
     "dm_connected_labels": (_I, [_P, _I, _I, _I, _I, _P, _P, _P, _P, _P]),
     "dm_label_area": (_I, [_P, _I, _I, _I, _P, _P]),
     "dm_slic_absorb_pick": (_I, [_P, _P, _I, _P, _I, _I, _P, _P, _P, _P]),
+    "dm_scene_slic_init": (_I, [_P, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P]),
+    "dm_scene_slic_pass": (_I, [_P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P]),
+    "dm_scene_slic_update": (_I, [_I, _P, _P, _P]),
     "dm_vector_count": (_I, [_P, _I, _I, _P, _P, _P, _P]),
     "dm_vector_emit": (_I, [_P, _P, _I, _I, _P, _P, _P]),
     "dm_vector_link": (_I, [_P, _P, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P, _P]),

@@ -6,7 +6,8 @@
 // which threads arrive: the GPU and the numpy spec agree bit for bit.  No floating point anywhere in this file.
 //
 // The passes run on dm_raster.h's tile walk (a workgroup per 64x64 tile, a thread per 16-pixel strip: one 16-byte load per band):
-//   slic_pass_kernel   assignment: the centres a tile can see are staged in LDS, every pixel takes the nearest of the 9 centres
+//   slic_pass_kernel   (dm_slic_pass.h, shared with the scene form in dm_scene_slic.hip; here at origin zero)
+//                      assignment: the centres a tile can see are staged in LDS, every pixel takes the nearest of the 9 centres
 //                      around its grid cell, the next centres' sums are collected per tile with integer LDS atomics (one group
 //                      per run of equal assignments in a strip) and flushed once per tile with 64-bit global adds; only the
 //                      last pass writes labels.  slic_update_kernel turns sums into centres.  No readback inside the loop.
@@ -14,20 +15,11 @@
 //                      atomicMin: the representative of a component is its smallest linear pixel index whatever the schedule),
 //                      flatten, renumber by first pixel (a scan over "is root" on block_exclusive), apply.
 //   label_area_kernel / absorb_*   what a round of the absorption needs beside rag_edges, merge_components and relabel_raster.
-#include <type_traits>
-
-#include "dm_raster.h"
+#include "dm_slic_pass.h"
 
 namespace {
 
-// ---- SLIC assignment pass ------------------------------------------------------------------------------------------------
-// A centre of grid cell J only ever owns pixels of the cells J-1 .. J+1, so its rounded mean stays inside them: a pixel and a
-// candidate centre are less than 3 cell apart on either axis, and a 64-row tile sees the centres of at most 64 / cell + 3 grid
-// rows (cell >= 4: 19).
-constexpr int SLIC_SIDE = 19, SLIC_SLOTS = SLIC_SIDE * SLIC_SIDE;
-constexpr int CENTRE_INTS = 6;                                  // y, x, band 0..3
-constexpr int SUM_INTS = 7;                                     // n, sum y, sum x, sum band 0..3
-
+// ---- SLIC assignment pass: dm_slic_pass.h, here at origin zero --------------------------------------------------------------
 __global__ void slic_init_kernel(const uint8_t *__restrict__ tile, long long plane, int H, int W, int nb, int cell, int gx, int K,
                                  int *__restrict__ centres, long long *__restrict__ sums) {
   const int c = blockIdx.x * blockDim.x + threadIdx.x;
@@ -38,205 +30,6 @@ __global__ void slic_init_kernel(const uint8_t *__restrict__ tile, long long pla
   centres[c * CENTRE_INTS + 1] = x;
   for (int b = 0; b < 4; ++b) centres[c * CENTRE_INTS + 2 + b] = b < nb ? (int)tile[b * plane + (long long)y * W + x] : 0;
   for (int k = 0; k < SUM_INTS; ++k) sums[(long long)c * SUM_INTS + k] = 0;
-}
-
-// Rounded mean (2 sum + n) / (2 n) of every centre that owns a pixel; the sums are cleared for the next pass.
-__global__ void slic_update_kernel(int K, int *__restrict__ centres, long long *__restrict__ sums) {
-  const int c = blockIdx.x * blockDim.x + threadIdx.x;
-  if (c >= K) return;
-  long long *s = sums + (long long)c * SUM_INTS;
-  const long long n = s[0];
-  if (n > 0)
-    for (int k = 0; k < CENTRE_INTS; ++k) centres[c * CENTRE_INTS + k] = (int)((2 * s[1 + k] + n) / (2 * n));
-  for (int k = 0; k < SUM_INTS; ++k) s[k] = 0;
-}
-
-// The strip's pixels, band b in byte b of pix[i] (bands >= NB stay 0).
-template <int NB, bool VEC>
-__device__ __forceinline__ void load_pixels(const uint8_t *__restrict__ tile, long long plane, long long base, int n, unsigned *pix) {
-#pragma unroll
-  for (int i = 0; i < STRIP; ++i) pix[i] = 0;
-#pragma unroll
-  for (int b = 0; b < NB; ++b) {
-    const uint8_t *p = tile + b * plane + base;
-    if (VEC && n == STRIP) {
-      const u32x4 v = *reinterpret_cast<const u32x4 *>(p);
-#pragma unroll
-      for (int i = 0; i < STRIP; ++i) pix[i] |= ((v[i >> 2] >> (8 * (i & 3))) & 0xffu) << (8 * b);
-    } else {
-#pragma unroll
-      for (int i = 0; i < STRIP; ++i)
-        if (i < n) pix[i] |= (unsigned)p[i] << (8 * b);
-    }
-  }
-}
-
-// D: unsigned 32-bit where the host proved cell^2 (NB 255^2 + 18 compactness^2) < 2^32, else 64-bit.
-template <int NB, bool WIDE, bool VEC>
-__global__ __launch_bounds__(256) void slic_pass_kernel(const uint8_t *__restrict__ tile, long long plane, int H, int W, int cell, int gy, int gx,
-                                                        unsigned cell2, unsigned comp2, const int *__restrict__ centres,
-                                                        long long *__restrict__ sums, int *__restrict__ labels) {
-  typedef typename std::conditional<WIDE, u64, unsigned>::type dist_t;
-  __shared__ int c_y[SLIC_SLOTS], c_x[SLIC_SLOTS];
-  __shared__ unsigned c_col[SLIC_SLOTS];
-  __shared__ int acc[SLIC_SLOTS * SUM_INTS];
-  const int tiles_x = (W + 63) / 64;
-  const int ty = blockIdx.x / tiles_x, tx = blockIdx.x - ty * tiles_x;
-  const int Y0 = ty * 64, X0 = tx * 64;
-  const int j0 = max(0, Y0 / cell - 1), j1 = min(gy - 1, min(H - 1, Y0 + 63) / cell + 1);
-  const int i0 = max(0, X0 / cell - 1), i1 = min(gx - 1, min(W - 1, X0 + 63) / cell + 1);
-  const int nj = j1 - j0 + 1, ni = i1 - i0 + 1;                  // <= SLIC_SIDE each
-  for (int s = threadIdx.x; s < nj * ni; s += blockDim.x) {
-    const int jj = s / ni, ii = s - jj * ni;
-    const int *c = centres + ((long long)(j0 + jj) * gx + i0 + ii) * CENTRE_INTS;
-    c_y[s] = c[0];
-    c_x[s] = c[1];
-    c_col[s] = (unsigned)c[2] | (unsigned)c[3] << 8 | (unsigned)c[4] << 16 | (unsigned)c[5] << 24;
-    for (int k = 0; k < SUM_INTS; ++k) acc[s * SUM_INTS + k] = 0;
-  }
-  __syncthreads();
-
-  const Strip g = strip_of(H, W);
-  if (g.live) {
-    unsigned pix[STRIP];
-    load_pixels<NB, VEC>(tile, plane, g.base, g.n, pix);
-    const int j = g.y / cell;
-    int i = g.x0 / cell, rem = g.x0 - i * cell;
-    // the 9 candidates of grid cell (j, i), in ascending centre id; slot < 0: outside the grid
-    int k_slot[9], k_y[9], k_x[9];
-    unsigned k_col[9];
-    dist_t k_dy[9];
-    auto reload = [&]() {
-#pragma unroll
-      for (int dj = -1; dj <= 1; ++dj)
-#pragma unroll
-        for (int di = -1; di <= 1; ++di) {
-          const int k = (dj + 1) * 3 + di + 1, cj = j + dj, ci = i + di;
-          const bool in = cj >= 0 && cj < gy && ci >= 0 && ci < gx;
-          const int s = in ? (cj - j0) * ni + (ci - i0) : -1;
-          k_slot[k] = s;
-          k_y[k] = in ? c_y[s] : 0;
-          k_x[k] = in ? c_x[s] : 0;
-          k_col[k] = in ? c_col[s] : 0;
-          const int dy = g.y - k_y[k];
-          k_dy[k] = (dist_t)comp2 * (dist_t)(unsigned)(dy * dy);
-        }
-    };
-    reload();
-    int out[STRIP];
-    int run_slot = -1, run_n = 0, run_x = 0, run_b[NB];
-#pragma unroll
-    for (int b = 0; b < NB; ++b) run_b[b] = 0;
-    auto flush = [&]() {
-      if (run_n == 0) return;
-      int *a = acc + run_slot * SUM_INTS;
-      atomicAdd(a + 0, run_n);
-      atomicAdd(a + 1, run_n * (g.y - Y0));
-      atomicAdd(a + 2, run_x);
-#pragma unroll
-      for (int b = 0; b < NB; ++b) atomicAdd(a + 3 + b, run_b[b]);
-    };
-#pragma unroll
-    for (int p = 0; p < STRIP; ++p) {
-      if (p < g.n) {
-        const int x = g.x0 + p;
-        dist_t best = 0;
-        int best_k = -1;
-#pragma unroll
-        for (int k = 0; k < 9; ++k) {
-          unsigned dc = 0;
-#pragma unroll
-          for (int b = 0; b < NB; ++b) {
-            const int d = (int)((pix[p] >> (8 * b)) & 0xffu) - (int)((k_col[k] >> (8 * b)) & 0xffu);
-            dc += (unsigned)(d * d);
-          }
-          const int dx = x - k_x[k];
-          const dist_t D = (dist_t)cell2 * (dist_t)dc + k_dy[k] + (dist_t)comp2 * (dist_t)(unsigned)(dx * dx);
-          const bool better = (k_slot[k] >= 0) & ((best_k < 0) | (D < best));      // selects, no branches: the grid's edge is rare
-          best = better ? D : best;
-          best_k = better ? k : best_k;
-        }
-        int slot = 0;
-#pragma unroll
-        for (int k = 0; k < 9; ++k)
-          if (k == best_k) slot = k_slot[k];
-        const int sj = slot / ni;
-        out[p] = (j0 + sj) * gx + i0 + (slot - sj * ni);
-        if (sums) {
-          if (slot != run_slot) {
-            flush();
-            run_slot = slot; run_n = 0; run_x = 0;
-#pragma unroll
-            for (int b = 0; b < NB; ++b) run_b[b] = 0;
-          }
-          ++run_n;
-          run_x += x - X0;
-#pragma unroll
-          for (int b = 0; b < NB; ++b) run_b[b] += (int)((pix[p] >> (8 * b)) & 0xffu);
-        }
-        if (++rem == cell) {
-          rem = 0; ++i;
-          if (p + 1 < g.n) reload();                               // the next pixel is in the tile: its candidates are staged
-        }
-      } else {
-        out[p] = 0;
-      }
-    }
-    if (sums) flush();
-    if (labels) {
-      if (VEC && g.n == STRIP) {
-#pragma unroll
-        for (int v = 0; v < STRIP / 4; ++v)
-          *reinterpret_cast<i32x4 *>(labels + g.base + 4 * v) = (i32x4){out[4 * v], out[4 * v + 1], out[4 * v + 2], out[4 * v + 3]};
-      } else {
-#pragma unroll
-        for (int p = 0; p < STRIP; ++p)
-          if (p < g.n) labels[g.base + p] = out[p];
-      }
-    }
-  }
-  if (!sums) return;
-  __syncthreads();
-  for (int s = threadIdx.x; s < nj * ni; s += blockDim.x) {
-    const int n = acc[s * SUM_INTS];
-    if (n == 0) continue;
-    const int jj = s / ni, ii = s - jj * ni;
-    long long *dst = sums + ((long long)(j0 + jj) * gx + i0 + ii) * SUM_INTS;
-    atomic_add64(dst + 0, n);
-    atomic_add64(dst + 1, (long long)acc[s * SUM_INTS + 1] + (long long)n * Y0);     // tile-relative sums fit 32 bits: 4096 * 63
-    atomic_add64(dst + 2, (long long)acc[s * SUM_INTS + 2] + (long long)n * X0);
-#pragma unroll
-    for (int b = 0; b < NB; ++b) atomic_add64(dst + 3 + b, acc[s * SUM_INTS + 3 + b]);
-  }
-}
-
-template <int NB, bool WIDE>
-void launch_pass(bool vec, hipStream_t s, const uint8_t *tile, int H, int W, int cell, int gy, int gx, unsigned comp2, const int *centres,
-                 long long *sums, int *labels) {
-  const long long plane = (long long)H * W;
-  const unsigned cell2 = (unsigned)(cell * cell);
-  if (vec)
-    hipLaunchKernelGGL((slic_pass_kernel<NB, WIDE, true>), tile_grid(H, W), dim3(256), 0, s, tile, plane, H, W, cell, gy, gx, cell2, comp2, centres,
-                       sums, labels);
-  else
-    hipLaunchKernelGGL((slic_pass_kernel<NB, WIDE, false>), tile_grid(H, W), dim3(256), 0, s, tile, plane, H, W, cell, gy, gx, cell2, comp2, centres,
-                       sums, labels);
-}
-
-void slic_pass(int nb, bool wide, bool vec, hipStream_t s, const uint8_t *tile, int H, int W, int cell, int gy, int gx, unsigned comp2,
-               const int *centres, long long *sums, int *labels) {
-#define DM_PASS(NB_)                                                                                          \
-  do {                                                                                                        \
-    if (wide) launch_pass<NB_, true>(vec, s, tile, H, W, cell, gy, gx, comp2, centres, sums, labels);         \
-    else launch_pass<NB_, false>(vec, s, tile, H, W, cell, gy, gx, comp2, centres, sums, labels);             \
-  } while (0)
-  switch (nb) {
-    case 1: DM_PASS(1); break;
-    case 2: DM_PASS(2); break;
-    case 3: DM_PASS(3); break;
-    default: DM_PASS(4); break;
-  }
-#undef DM_PASS
 }
 
 // ---- 4-connected components ---------------------------------------------------------------------------------------------
@@ -457,17 +250,16 @@ extern "C" int dm_slic_iterate(const uint8_t *tile, int32_t bands, int32_t H, in
   const int nb = bands < 4 ? bands : 4;
   const int gy = (H + cell - 1) / cell, gx = (W + cell - 1) / cell, K = gy * gx;
   const unsigned comp2 = (unsigned)(compactness * compactness);
-  // D <= cell^2 (nb 255^2 + 2 * 3^2 compactness^2): a pixel and a candidate centre are less than 3 cell apart on either axis
-  const bool wide = (u64)cell * cell * ((u64)nb * 65025 + 18ULL * comp2) >= (1ULL << 32);
   // 16-byte strip loads / stores need W % 16 == 0 (then every band plane keeps the alignment) and 16-byte aligned rasters
   const bool vec = W % STRIP == 0 && dm_aligned16(tile) && dm_aligned16(labels);
+  const SlicPass pass = {nb, slic_wide(cell, nb, comp2), vec, H, W, 0, 0, H, W, cell, gy, gx, comp2};
   const long long plane = (long long)H * W;
   hipLaunchKernelGGL(slic_init_kernel, dim3((K + 255) / 256), dim3(256), 0, s, tile, plane, H, W, nb, cell, gx, K, centres, (long long *)sums);
   for (int it = 0; it < iters; ++it) {
-    slic_pass(nb, wide, vec, s, tile, H, W, cell, gy, gx, comp2, centres, (long long *)sums, nullptr);
+    slic_pass<false>(pass, s, tile, centres, (long long *)sums, nullptr);
     hipLaunchKernelGGL(slic_update_kernel, dim3((K + 255) / 256), dim3(256), 0, s, K, centres, (long long *)sums);
   }
-  slic_pass(nb, wide, vec, s, tile, H, W, cell, gy, gx, comp2, centres, nullptr, labels);
+  slic_pass<false>(pass, s, tile, centres, nullptr, labels);
   DM_LAUNCH_CHECK("dm_slic_iterate");
   return DM_OK;
 }

@@ -14,8 +14,9 @@ counted as "raster border" although another label faces them -- is added by one 
 a batch: the batches of a scene break at tile boundaries.)
 
 Known consequence: where the learned merge does not join two superpixels across a seam, a straight boundary stays on the seam
-line; superpixels brought along as a label raster avoid it (below).  Out of scope: superpixels MADE HERE that cross seams; a
-pixel-start `rag.mrs` on a scene; overlapping the copy of the next tile with compute.
+line; superpixels that cross seams avoid it: brought along as a label raster, or made here by `slic_labels` (both below;
+`segment_scene(..., cross_seams=True)`).  Out of scope: a pixel-start `rag.mrs` on a scene; overlapping the copy of the next tile
+with compute.
 
 Superpixels from a label raster.  `segment_labels` (`segment_scene(..., labels=, n_labels=)`) takes the scene's
 superpixels as an int32 raster on the host whose regions know nothing of the tile grid -- those of external GIS software, or an
@@ -23,6 +24,10 @@ earlier merge's result -- and returns what `FeatureIO.merge_tile` returns on the
 Statistics and edges are folded over the tiles a region lies in (`label_graph`), the seam stitch meets equal ids on both sides of
 a seam, and the sample points are a scene-wide per-region maximum over k passes (`sample_points`, csrc/dm_scene_points.hip).
 `mrs_labels` runs the classical baseline `rag.mrs` on the same graph.
+
+Superpixels that cross seams, made here.  `slic_labels` is `rag.slic` on a scene, bit for bit, whatever the tile
+size: one scene-wide table of centres, the assignment passes streamed core by core (csrc/dm_scene_slic.hip), components and
+absorption finished on the component graph.  `slic_assign` is its steps 1-3.
 
 Rings and arcs.  `trace_labels` traces a scene's label raster -- the merged raster through
 `SceneResult.trace` -- into the rings and arcs `rag._trace` gives on the whole raster, array for array and bit for bit, whatever
@@ -373,7 +378,8 @@ class SceneResult:
 
 def segment_scene(fio, source, tile=4096, segmenter: Optional[Callable] = None, k: int = 3, margin: float = 1.0,
                   max_window: int = rag.MAX_WINDOW, batch_size: int = 2000, labels_out=None, stage_times: Optional[dict] = None,
-                  labels=None, n_labels: Optional[int] = None, **merge_kwargs) -> SceneResult:
+                  labels=None, n_labels: Optional[int] = None, cross_seams: bool = False, slic: Optional[dict] = None,
+                  **merge_kwargs) -> SceneResult:
     """From a scene of any size to its merged partition (the module docstring states the definition).
 
     fio: a FeatureIO; source: `.shape == (bands, H, W)` and `.read(y0, y1, x0, x1) -> uint8 [bands, y1-y0, x1-x0]` (a numpy
@@ -384,7 +390,18 @@ def segment_scene(fio, source, tile=4096, segmenter: Optional[Callable] = None, 
     superpixel raster, allocated if None; stage_times: a dict that receives seconds per stage (synchronises at stage boundaries).
     labels, n_labels: the scene's superpixels brought along as a label raster on the host, whose regions may cross seams: the call
     is `segment_labels(fio, source, labels, n_labels, ...)` (no segmenter and no labels_out go with it: ValueError).
+    cross_seams=True makes the superpixels here and lets them cross the seams: `slic_labels(source, tile, **(slic or {}),
+    labels_out=labels_out)`, then `segment_labels` on that raster; slic: its keywords (cell, compactness, iters, min_size,
+    resident_bytes).  It takes no segmenter and no labels= (ValueError); the default, False, is the per-tile path above.
     Limits: at most 2^24 superpixels in the scene, every window (core + halo) below 2^31 pixels."""
+    if cross_seams:
+        if segmenter is not None or labels is not None or n_labels is not None:
+            raise ValueError("cross_seams=True makes the scene's superpixels itself (slic_labels): it takes neither a segmenter nor labels=")
+        made, n_made = slic_labels(source, tile, **(slic or {}), labels_out=labels_out, device=fio.device, stage_times=stage_times)
+        return segment_labels(fio, source, made, n_made, tile=tile, k=k, margin=margin, max_window=max_window, batch_size=batch_size,
+                              stage_times=stage_times, **merge_kwargs)
+    if slic is not None:
+        raise ValueError("slic= holds the keywords of slic_labels: it goes with cross_seams=True")
     if labels is not None:
         if segmenter is not None or labels_out is not None:
             raise ValueError("labels= brings the scene's superpixels along: it takes neither a segmenter nor labels_out")
@@ -1048,3 +1065,270 @@ def simplify_conflicts(source, n_labels: int, tolerance: float, tile=4096, devic
     cell_log2 = _check_topology(H, W, arcs.left.numel(), arcs.xy.shape[0], 1, None)
     _, _, arc_keep = _chain_flags(arcs, node_row, H, W, q)
     return _SceneTopologyRounds(arcs, arc_keep, H, W, q, cell_log2=cell_log2).conflicts()
+
+
+# ---- SLIC superpixels across tile seams (csrc/dm_scene_slic.hip, csrc/dm_slic_pass.h) -----------------------------
+MAX_SLIC_SIDE = (1 << 31) - 1         # H, W are int32 (the centres' positions too)
+MAX_SLIC_CENTRES = 1 << 31            # centre ids are int32
+MAX_SLIC_COMPONENTS = (1 << 31) - 1   # provisional ids are int32 in the raster, in dm_merge_round and in dm_slic_absorb_pick
+MAX_SLIC_EDGES = (1 << 31) - 1        # dm_slic_absorb_pick's and dm_merge_round's E
+MAX_SLIC_WEIGHT = 1 << 31             # a shared boundary's length is int32 in dm_slic_absorb_pick
+
+
+def _check_scene_slic(source, tile, cell, compactness, iters, min_size, out, out_name: str, resident_bytes):
+    """The limits of `slic_assign` / `slic_labels`, each a ValueError before any device work.  Returns (bands, H, W, K, min_size,
+    tiles, out)."""
+    shape = tuple(source.shape)
+    if len(shape) != 3 or min(shape) < 1:
+        raise ValueError(f"source.shape must be (bands, H, W) with bands, H, W >= 1, got {shape}")
+    bands, H, W = (int(v) for v in shape)
+    if H > MAX_SLIC_SIDE or W > MAX_SLIC_SIDE:
+        raise ValueError(f"the scene must have H, W < 2^31, got {H} x {W}")
+    if not 4 <= int(cell) <= 256:
+        raise ValueError(f"cell must be in 4..256, got {cell}")
+    if not 0 <= int(compactness) <= 255:
+        raise ValueError(f"compactness must be in 0..255, got {compactness}")
+    if int(iters) < 0:
+        raise ValueError(f"iters must be >= 0, got {iters}")
+    min_size = max(1, int(cell) * int(cell) // 4) if min_size is None else int(min_size)
+    if not 1 <= min_size < 1 << 31:
+        raise ValueError(f"min_size must be in 1..2^31-1, got {min_size}")
+    if int(resident_bytes) < 0:
+        raise ValueError(f"resident_bytes must be >= 0, got {resident_bytes}")
+    cell = int(cell)
+    K = ((H + cell - 1) // cell) * ((W + cell - 1) // cell)
+    if K >= MAX_SLIC_CENTRES:
+        raise ValueError(f"the scene's grid must have fewer than 2^31 centres, got {K} (cell = {cell}); use a larger cell")
+    tiles = tile_grid(H, W, tile)
+    th, tw = tiles[0][1] - tiles[0][0], tiles[0][3] - tiles[0][2]          # the first core is the largest
+    if th * tw >= 1 << 31:
+        raise ValueError(f"a core must have fewer than 2^31 pixels, got {th} x {tw}")
+    if out is None:
+        out = np.empty((H, W), dtype=np.int32)
+    elif not isinstance(out, np.ndarray) or out.dtype != np.int32 or out.shape != (H, W) or not out.flags.writeable:
+        raise ValueError(f"{out_name} must be a writable int32 [{H},{W}] numpy array or memmap")
+    return bands, H, W, K, min_size, tiles, out
+
+
+class _Cores:
+    """The scene's cores as uint8 [nb,h,w] on the device (nb = min(bands, 4): what the rule uses), for several passes: they stay on
+    the device between passes while their total is within `budget` bytes, otherwise every pass reads them again from the source.
+    Iterating yields (i, (y0, y1, x0, x1), core)."""
+
+    def __init__(self, source, tiles: List[Core], bands: int, H: int, W: int, budget: int, dev, clock: _Clock):
+        self.source, self.tiles, self.nb, self.dev, self.clock = source, tiles, min(bands, 4), dev, clock
+        self.resident = self.nb * H * W <= int(budget)
+        self.held: Dict[int, torch.Tensor] = {}
+        self.reads = 0
+
+    def __iter__(self):
+        for i, core in enumerate(self.tiles):
+            t = self.held.get(i)
+            if t is None:
+                t = _read(self.source, core, torch.uint8, 3, self.dev)[:self.nb].contiguous()
+                rag._need_cuda(t)
+                self.reads += 1
+                if self.resident:
+                    self.held[i] = t
+            self.clock.lap("read + copy")
+            yield i, core, t
+
+
+def _assigned_cores(cores: _Cores, H: int, W: int, K: int, cell: int, compactness: int, iters: int, clock: _Clock):
+    """Steps 1-3 on the scene: init over every core, `iters` rounds of (assignment pass with sums over every core, one update), then
+    the last pass, which yields (i, core, assigned int32 [h,w] on the device) per core; `centres` int32 [K,6] is yielded first.  No
+    readback."""
+    lib, dev = _lib.lib(), cores.dev
+    centres = torch.empty((K, 6), dtype=torch.int32, device=dev)
+    sums = torch.empty((K, 7), dtype=torch.int64, device=dev)
+    place = lambda t, c: (t.data_ptr(), cores.nb, c[1] - c[0], c[3] - c[2], c[0], c[2], H, W, cell)
+    for i, c, t in cores:                                        # every centre before any assignment
+        check(lib.dm_scene_slic_init(*place(t, c), centres.data_ptr(), sums.data_ptr(), _stream()), "dm_scene_slic_init")
+        clock.lap("assignment passes")
+    for _ in range(iters):
+        for i, c, t in cores:
+            check(lib.dm_scene_slic_pass(*place(t, c), compactness, centres.data_ptr(), sums.data_ptr(), None, _stream()), "dm_scene_slic_pass")
+            clock.lap("assignment passes")
+        check(lib.dm_scene_slic_update(K, centres.data_ptr(), sums.data_ptr(), _stream()), "dm_scene_slic_update")
+    yield centres
+    for i, c, t in cores:
+        assigned = torch.empty((c[1] - c[0], c[3] - c[2]), dtype=torch.int32, device=dev)
+        check(lib.dm_scene_slic_pass(*place(t, c), compactness, centres.data_ptr(), None, assigned.data_ptr(), _stream()), "dm_scene_slic_pass")
+        clock.lap("assignment passes")
+        yield i, c, assigned
+
+
+def slic_assign(source, tile=4096, cell: int = 29, compactness: int = 10, iters: int = 10, assigned_out=None,
+                resident_bytes: int = 8 << 30, device="cuda:0", stage_times: Optional[dict] = None) -> Tuple[np.ndarray, torch.Tensor]:
+    """Steps 1-3 of the SLIC rule on a scene: (assigned int32 [H,W] on the host: the centre id of every pixel; centres int32 [K,6]
+    on the device), both equal to `rag.slic_assign(whole scene)` whatever the tile size.  Arguments as `slic_labels` takes them;
+    assigned_out: a writable int32 [H,W] array or memmap, allocated if None."""
+    source = _as_source(source)
+    bands, H, W, K, _, tiles, out = _check_scene_slic(source, tile, cell, compactness, iters, None, assigned_out, "assigned_out", resident_bytes)
+    dev = torch.device(device)
+    clock = _Clock(stage_times, dev)
+    stream = _assigned_cores(_Cores(source, tiles, bands, H, W, resident_bytes, dev, clock), H, W, K, int(cell), int(compactness), int(iters), clock)
+    centres = next(stream)
+    for i, (y0, y1, x0, x1), assigned in stream:
+        out[y0:y1, x0:x1] = assigned.cpu().numpy()
+        clock.lap("relabel + write")
+    return out, centres
+
+
+def _components(assigned: torch.Tensor) -> Tuple[torch.Tensor, int, torch.Tensor]:
+    """`rag.connected_labels(assigned)` and, from the same call's parent table, first int64 [n]: the linear index in the raster of
+    every component's first pixel (a component's root is its first pixel; the roots in raster order are the ids in order)."""
+    h, w = assigned.shape
+    dev, i32 = assigned.device, torch.int32
+    parent = torch.empty(h * w, dtype=i32, device=dev)
+    chunks = torch.empty((h * w + 4095) // 4096 + 1, dtype=i32, device=dev)
+    labels = torch.empty((h, w), dtype=i32, device=dev)
+    n = torch.empty(1, dtype=i32, device=dev)
+    check(_lib.lib().dm_connected_labels(assigned.data_ptr(), h, w, 0, 0, parent.data_ptr(), chunks.data_ptr(), labels.data_ptr(),
+                                         n.data_ptr(), _stream()), "dm_connected_labels")
+    first = torch.nonzero(parent == torch.arange(h * w, dtype=i32, device=dev)).view(-1)
+    return labels, int(n), first
+
+
+def _seam_pairs(strips: list, nx: int, ny: int, dev) -> Tuple[torch.Tensor, ...]:
+    """All seams of the scene, concatenated: for every seam position the entries of the two facing pixels, per field of the strips
+    (strips[i] = a tuple of fields, each (top, bottom, left, right)).  Returns (a, b) per field."""
+    fields = len(strips[0])
+    sa, sb = [[] for _ in range(fields)], [[] for _ in range(fields)]
+    for r in range(ny):
+        for c in range(nx):
+            for f in range(fields):
+                top, bottom, left, right = strips[r * nx + c][f]
+                if c + 1 < nx:
+                    sa[f].append(right); sb[f].append(strips[r * nx + c + 1][f][2])
+                if r + 1 < ny:
+                    sa[f].append(bottom); sb[f].append(strips[(r + 1) * nx + c][f][0])
+    empty = torch.empty(0, dtype=torch.int32, device=dev)
+    return tuple((torch.cat(sa[f]), torch.cat(sb[f])) if sa[f] else (empty, empty) for f in range(fields))
+
+
+def _fold_graph(mapping: torch.Tensor, n_new: int, area: torch.Tensor, edges: torch.Tensor, weights: torch.Tensor):
+    """The graph under a union: mapping int64 [n] -> 0..n_new-1; areas add, the edge keys are mapped, self edges dropped and the
+    weights of equal keys added.  area int64, edges int64 [E,2], weights int64 [E]; returns the same three, edges sorted by (a, b)."""
+    dev = mapping.device
+    area = torch.zeros(n_new, dtype=torch.int64, device=dev).index_add_(0, mapping, area)
+    a, b = mapping[edges[:, 0]], mapping[edges[:, 1]]
+    keep = a != b
+    a, b, weights = a[keep], b[keep], weights[keep]
+    uniq, inverse = torch.unique(torch.minimum(a, b) * n_new + torch.maximum(a, b), return_inverse=True)
+    weights = torch.zeros(uniq.numel(), dtype=torch.int64, device=dev).index_add_(0, inverse, weights)
+    if uniq.numel() > MAX_SLIC_EDGES:
+        raise ValueError(f"the component graph has 2^31 edges or more ({uniq.numel()}): edge counts are 32-bit")
+    if weights.numel() and int(weights.max()) >= MAX_SLIC_WEIGHT:
+        raise ValueError(f"two regions share a boundary of 2^31 pixel edges or more ({int(weights.max())}): weights are 32-bit")
+    return area, torch.stack((uniq // n_new, uniq % n_new), 1), weights
+
+
+def slic_labels(source, tile=4096, cell: int = 29, compactness: int = 10, iters: int = 10, min_size: Optional[int] = None,
+                labels_out=None, resident_bytes: int = 8 << 30, device="cuda:0", stage_times: Optional[dict] = None,
+                stats: Optional[dict] = None) -> Tuple[np.ndarray, int]:
+    """SLIC superpixels of a scene larger than one tile, regions crossing the tile seams: (labels int32 [H,W] on the host, n_labels),
+    equal to `rag.slic(whole scene, cell, compactness, iters, min_size)` bit for bit, whatever the tile size -- the raster
+    `segment_labels` takes (`segment_scene(..., cross_seams=True)` chains the two).
+
+    source: what `segment_scene` takes: uint8 [bands,H,W] as an array, an `np.memmap`, a CPU tensor, or anything with `.shape` and
+    `.read(y0, y1, x0, x1)`; tile: core side, an int or (th, tw); cell, compactness, iters, min_size: as `rag.slic` takes them;
+    labels_out: a writable int32 [H,W] array or memmap, allocated if None; resident_bytes: a budget -- the cores (uint8, the first
+    four bands) stay on the device between the passes while their total is within it, otherwise every pass reads them again from
+    the source (the image is read once, or iters + 2 times); the result does not depend on it; stage_times: seconds per stage
+    (synchronises at stage boundaries); stats: receives `provisional` (tile-local components), `seam_unions` (distinct pairs united
+    across seams), `components` (step 4's count), `rounds` (absorption rounds), `picks` (picked edges per round), `image_reads`.
+
+    One scene-wide table of centres; per round an assignment pass over every core and one update; in the last pass per core the
+    assigned raster, its tile-local components with provisional ids, their first pixels, areas, edges and border lines; then on
+    the component graph only: unions across seams where both sides hold the same centre id, numbering by scene-wide first pixel,
+    the absorption rounds on folded areas and edges; one relabel pass applies the composed mapping.
+    Limits, each a ValueError: H, W < 2^31; fewer than 2^31 centres; a core below 2^31 pixels, with at most 2^25 components
+    (`rag.rag_edges`' table of 32 slots per component ends at 2^30); fewer than 2^31 provisional components and fewer than 2^31
+    graph edges in the scene; a shared boundary below 2^31 pixel edges.  Areas are folded in 64 bits."""
+    source = _as_source(source)
+    bands, H, W, K, min_size, tiles, out = _check_scene_slic(source, tile, cell, compactness, iters, min_size, labels_out, "labels_out",
+                                                             resident_bytes)
+    dev, lib, i32, i64 = torch.device(device), _lib.lib(), torch.int32, torch.int64
+    nx = sum(1 for t in tiles if t[0] == 0)
+    ny = len(tiles) // nx
+    clock = _Clock(stage_times, dev)
+    cores = _Cores(source, tiles, bands, H, W, resident_bytes, dev, clock)
+    stream = _assigned_cores(cores, H, W, K, int(cell), int(compactness), int(iters), clock)
+    next(stream)                                                 # the centres: not needed here
+    base, first_parts, area_parts, edge_parts, weight_parts, strips = 0, [], [], [], [], []
+    for i, (y0, y1, x0, x1), assigned in stream:
+        comp, n, first = _components(assigned)
+        if base + n > MAX_SLIC_COMPONENTS:
+            raise ValueError(f"the scene has 2^31 tile-local components or more ({base + n} after tile {i} of {len(tiles)}): ids are "
+                             f"32-bit; use fewer, larger tiles or segment the scene in parts")
+        w = x1 - x0
+        first_parts.append((torch.div(first, w, rounding_mode="floor") + y0) * W + (first % w + x0))       # scene-wide, 64-bit
+        area_parts.append(rag.label_area(comp, n).long())
+        e, wgt = rag.rag_edges(comp, n)
+        edge_parts.append(e.long() + base)
+        weight_parts.append(wgt.long())
+        prov = comp + base
+        border = lambda r: (r[0].clone(), r[-1].clone(), r[:, 0].clone(), r[:, -1].clone())      # top, bottom, left, right
+        strips.append((border(assigned), border(prov)))
+        base += n
+        clock.lap("components + graph")
+        out[y0:y1, x0:x1] = prov.cpu().numpy()
+        clock.lap("relabel + write")
+    P = base
+    # seams: equal centre ids on both sides unite the two provisional components; different ones are an edge of the graph
+    (ca, cb), (pa, pb) = _seam_pairs(strips, nx, ny, dev)
+    same = ca == cb
+    pairs = torch.unique(pa[same].long() * P + pb[same].long())
+    if pairs.numel():
+        united = torch.stack((pairs // P, pairs % P), 1).to(i32).contiguous()
+        root = rag.merge_components(united, torch.ones(united.shape[0], dtype=torch.uint8, device=dev), P).long()
+    else:
+        root = torch.arange(P, dtype=i64, device=dev)
+    # (counted here, not by rag.seam_stitch: its ids end at 2^24, and a scene has more fragments than that before the absorption;
+    #  the seam positions are a perimeter, not an area)
+    da, db = pa[~same].long(), pb[~same].long()
+    seam_keys, seam_weights = torch.unique(torch.minimum(da, db) * P + torch.maximum(da, db), return_counts=True)
+    seam_edges = torch.stack((seam_keys // P, seam_keys % P), 1)
+    # numbering: a component is a union's root, its first pixel the minimum over its members
+    first = torch.full((P,), (1 << 63) - 1, dtype=i64, device=dev).scatter_reduce_(0, root, torch.cat(first_parts), "amin")
+    roots = torch.nonzero(root == torch.arange(P, dtype=i64, device=dev)).view(-1)
+    n = int(roots.numel())
+    rank = torch.empty(P, dtype=i64, device=dev)
+    rank[roots[torch.argsort(first[roots])]] = torch.arange(n, dtype=i64, device=dev)
+    mapping = rank[root]                                         # provisional id -> component, composed with every round below
+    area, edges, weights = _fold_graph(mapping, n, torch.cat(area_parts), torch.cat(edge_parts + [seam_edges]),
+                                       torch.cat(weight_parts + [seam_weights]))
+    components = n
+    clock.lap("seams")
+    # absorption on the graph only: the rounds of rag.absorb_small, the raster untouched
+    picks = []
+    while n > 1 and edges.shape[0]:
+        E = int(edges.shape[0])
+        e32, w32, a32 = edges.to(i32).contiguous(), weights.to(i32), area.clamp(max=(1 << 31) - 1).to(i32)   # `< min_size` survives the clamp
+        best = torch.empty(n, dtype=i64, device=dev)
+        merge = torch.empty(E, dtype=torch.uint8, device=dev)
+        picked = torch.empty(1, dtype=i32, device=dev)
+        check(lib.dm_slic_absorb_pick(e32.data_ptr(), w32.data_ptr(), E, a32.data_ptr(), n, min_size, best.data_ptr(), merge.data_ptr(),
+                                      picked.data_ptr(), _stream()), "dm_slic_absorb_pick")
+        if int(picked) == 0:
+            break
+        picks.append(int(picked))
+        root = rag.merge_components(e32, merge, n).long()
+        dense = torch.cumsum((root == torch.arange(n, device=dev)).to(i64), 0) - 1      # keeps the order: a union's first pixel is its smallest member's
+        step = dense[root]
+        n = int(dense[-1]) + 1
+        area, edges, weights = _fold_graph(step, n, area, edges, weights)
+        mapping = step[mapping]
+    clock.lap("absorption rounds")
+    # one relabel pass over the provisional raster
+    mapping = mapping.to(i32).contiguous()
+    for y0, y1, x0, x1 in tiles:
+        prov = torch.from_numpy(np.ascontiguousarray(out[y0:y1, x0:x1])).to(dev)
+        clock.lap("read + copy")
+        out[y0:y1, x0:x1] = rag.relabel_raster(prov, mapping).cpu().numpy()
+        clock.lap("relabel + write")
+    if stats is not None:
+        stats.update(provisional=P, seam_unions=int(pairs.numel()), components=components, rounds=len(picks), picks=picks,
+                     image_reads=cores.reads // len(tiles), resident=cores.resident, tiles=len(tiles), n_labels=n)
+    return out, n

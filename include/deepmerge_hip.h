@@ -742,6 +742,45 @@ int dm_label_area(const int32_t *labels, int32_t H, int32_t W, int32_t S, int32_
 int dm_slic_absorb_pick(const int32_t *edges, const int32_t *weights, int32_t E, const int32_t *area, int32_t S, int32_t min_size,
                         uint64_t *best, uint8_t *merge, int32_t *n_picked, void *stream);
 
+/* ---- SLIC on a scene larger than one tile: superpixels that cross tile seams (additive in ABI 7; csrc/dm_scene_slic.hip,
+ * csrc/dm_slic_pass.h, DESIGN.md 3.5.15, scene.slic_assign / scene.slic_labels) ------------------------------------------------------
+ * The rule above on an H x W scene that is streamed through the device core by core (a core: h x w pixels whose first pixel is
+ * (y0, x0) of the scene, uint8 [bands,h,w]); the result equals the tile form's on the whole scene bit for bit, whatever the cores.
+ * The scene form of the rule.
+ *   1. one table of K = ceil(H / cell) * ceil(W / cell) centres for the scene.  A centre starts at its scene position with the
+ *      colour read from the core that holds that pixel: dm_scene_slic_init once per core, all cores before any dm_scene_slic_pass.
+ *   2. a pixel's assignment depends on its colour, its scene position (y0 + y, x0 + x) and the up to 9 centres around its grid cell,
+ *      all of them rows of the table: a core needs no halo and no neighbour's labels.  Centre ids are the scene's j*gx + i.
+ *   3. the sums are integer adds, so the sums over the cores are the sums over the scene: per round dm_scene_slic_pass with `sums`
+ *      for every core, in any order, then dm_scene_slic_update once; after the rounds dm_scene_slic_pass with `labels` for every
+ *      core.  No readback inside the loop.
+ *   4.-5. components and absorption are finished on the component graph (scene.slic_labels): tile-local components
+ *      (dm_connected_labels) joined across a seam where the two facing pixels hold the same centre id, numbered by scene-wide first
+ *      pixel; areas and shared boundary lengths add under a union, so the rounds of step 5 run on the folded graph
+ *      (dm_slic_absorb_pick, dm_merge_round) and one dm_relabel_raster per core applies the composed mapping.
+ * Limits, each checked before any launch: bands >= 1; H, W < 2^31 (int32); 0 <= y0, y0 + h <= H, 0 <= x0, x0 + w <= W; a core has
+ * h*w < 2^31 pixels; 4 <= cell <= 256; K < 2^31; 0 <= compactness <= 255.  The sums are 64-bit: a centre owns at most (3 cell)^2
+ * pixels.  On the graph (scene.slic_labels checks them): fewer than 2^31 provisional components and fewer than 2^31 edges in the
+ * scene (dm_merge_round's and dm_slic_absorb_pick's int32 S and E); at most 2^25 components in one core (dm_rag_edges' table of 32
+ * slots per label ends at 2^30); a shared boundary shorter than 2^31 pixel edges (int32 weights); areas are folded in 64 bits and
+ * handed to dm_slic_absorb_pick clamped to 2^31 - 1, which `area < min_size` cannot tell from the area.  The pairs across the
+ * seams are counted by the caller with one sort over the seam positions (a perimeter's worth): dm_seam_stitch's ids end at
+ * 2^24, below the fragments a scene has before the absorption.
+ * Every entry point validates before any launch, launches on `stream`, never synchronises and never allocates.
+ *
+ * dm_scene_slic_init: the centres whose start pixel lies in the core (int32 [K,6] rows = y, x, band 0..3 in scene coordinates) and
+ *   their rows of sums int64 [K,7] (cleared).  Rows of other cores' centres are not touched.
+ * dm_scene_slic_pass: one assignment pass over the core against the table.  sums != NULL: the core's pixels are added to the rows
+ *   of the centres they take (n, sum y, sum x in scene coordinates, sum band 0..3).  labels != NULL: int32 [h,w] = the centre id of
+ *   every pixel of the core.  Either may be NULL, not both.  16-byte strip loads and stores when w % 16 == 0 and core / labels are
+ *   16-byte aligned, scalar otherwise; 32-bit distances where cell^2 (nb 255^2 + 18 compactness^2) < 2^32, 64-bit otherwise.
+ * dm_scene_slic_update: step 3 over the K rows: rounded means into centres, sums cleared. */
+int dm_scene_slic_init(const uint8_t *core, int32_t bands, int32_t h, int32_t w, int32_t y0, int32_t x0, int32_t H, int32_t W,
+                       int32_t cell, int32_t *centres, int64_t *sums, void *stream);
+int dm_scene_slic_pass(const uint8_t *core, int32_t bands, int32_t h, int32_t w, int32_t y0, int32_t x0, int32_t H, int32_t W,
+                       int32_t cell, int32_t compactness, const int32_t *centres, int64_t *sums, int32_t *labels, void *stream);
+int dm_scene_slic_update(int32_t K, int32_t *centres, int64_t *sums, void *stream);
+
 /* ---- polygon rings and boundary arcs from a label raster (additive in ABI 6; csrc/dm_vector.hip, DESIGN.md 3.5.5,
  * rag.polygons / rag.boundary_arcs) ----------------------------------------------------------------------------------------------
  * Produces, on the device, the geometry the reference reads from shapefiles written by external GIS software (the polygon layer,
