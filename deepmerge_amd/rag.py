@@ -846,10 +846,8 @@ def pair_flags(edges: torch.Tensor, overlap: Overlap, min_purity: float = 0.6) -
 
 
 # ---- SLIC superpixels and 4-connected components (csrc/dm_slic.hip; the rule: include/deepmerge_hip.h) ---------
-def connected_labels(raster: torch.Tensor, background: Optional[int] = None) -> Tuple[torch.Tensor, int]:
-    """(labels int32 [H,W], n): the 4-connected components of equal values of an int32 raster, numbered 0..n-1 in the order of
-    their first pixel in raster-scan order.  Pixels equal to `background` get -1 and belong to no component (a class raster's
-    "no object" value).  The input is not modified.  One readback (n)."""
+def _connected_labels(raster: torch.Tensor, background: Optional[int]) -> Tuple[torch.Tensor, int, torch.Tensor]:
+    """`connected_labels` and the call's parent table, int32 [H*W]: a component's root is its first pixel (scene._components)."""
     _need_cuda(raster)
     if raster.dtype != torch.int32 or raster.dim() != 2 or raster.numel() < 1:
         raise ValueError("raster must be int32 [H,W] with at least one pixel")
@@ -866,7 +864,25 @@ def connected_labels(raster: torch.Tensor, background: Optional[int] = None) -> 
     n = torch.empty(1, dtype=i32, device=dev)
     check(_lib.lib().dm_connected_labels(raster.data_ptr(), H, W, int(background is not None), int(background or 0), parent.data_ptr(),
                                          chunks.data_ptr(), labels.data_ptr(), n.data_ptr(), _stream()), "dm_connected_labels")
-    return labels, int(n)
+    return labels, int(n), parent
+
+
+def connected_labels(raster: torch.Tensor, background: Optional[int] = None) -> Tuple[torch.Tensor, int]:
+    """(labels int32 [H,W], n): the 4-connected components of equal values of an int32 raster, numbered 0..n-1 in the order of
+    their first pixel in raster-scan order.  Pixels equal to `background` get -1 and belong to no component (a class raster's
+    "no object" value).  The input is not modified.  One readback (n)."""
+    return _connected_labels(raster, background)[:2]
+
+
+def _slic_params(cell: int, compactness: int, iters: int, min_size: Optional[int]) -> int:
+    """The ranges of the rule's parameters, for a tile and for a scene; returns min_size with its default, its range left to the caller."""
+    if not 4 <= int(cell) <= 256:
+        raise ValueError(f"cell must be in 4..256, got {cell}")
+    if not 0 <= int(compactness) <= 255:
+        raise ValueError(f"compactness must be in 0..255, got {compactness}")
+    if int(iters) < 0:
+        raise ValueError(f"iters must be >= 0, got {iters}")
+    return max(1, int(cell) * int(cell) // 4) if min_size is None else int(min_size)
 
 
 def _check_slic(tile: torch.Tensor, cell: int, compactness: int, iters: int, min_size: Optional[int]) -> int:
@@ -875,13 +891,7 @@ def _check_slic(tile: torch.Tensor, cell: int, compactness: int, iters: int, min
         raise ValueError("tile must be uint8 [bands,H,W] with at least one band and one pixel")
     if tile.shape[1] * tile.shape[2] >= 1 << 31:
         raise ValueError(f"slic takes rasters of fewer than 2^31 pixels, got {tile.shape[1] * tile.shape[2]}")
-    if not 4 <= int(cell) <= 256:
-        raise ValueError(f"cell must be in 4..256, got {cell}")
-    if not 0 <= int(compactness) <= 255:
-        raise ValueError(f"compactness must be in 0..255, got {compactness}")
-    if int(iters) < 0:
-        raise ValueError(f"iters must be >= 0, got {iters}")
-    min_size = max(1, int(cell) * int(cell) // 4) if min_size is None else int(min_size)
+    min_size = _slic_params(cell, compactness, iters, min_size)
     if min_size < 1:
         raise ValueError(f"min_size must be >= 1, got {min_size}")
     return min_size
@@ -915,35 +925,45 @@ def label_area(labels: torch.Tensor, n_labels: int) -> torch.Tensor:
     return area
 
 
+def _absorb_round(edges: torch.Tensor, weights: torch.Tensor, area: torch.Tensor, n: int, min_size: int):
+    """One absorption round on a graph of n regions (int32 edges [E,2], weights [E], areas [n]): one 64-bit max per small region
+    (dm_slic_absorb_pick), merge_components over the picked edges, the dense renumbering.  Returns (step int64 [n]: region ->
+    0..n_new-1, n_new, picked edges), or None when nothing was picked (no edge, or no small region).  The numbering keeps the
+    order: a united region's first pixel is that of its smallest member."""
+    E, dev = edges.shape[0], edges.device
+    if E == 0:
+        return None
+    best = torch.empty(n, dtype=torch.int64, device=dev)
+    merge = torch.empty(E, dtype=torch.uint8, device=dev)
+    picked = torch.empty(1, dtype=torch.int32, device=dev)
+    check(_lib.lib().dm_slic_absorb_pick(edges.data_ptr(), weights.data_ptr(), E, area.data_ptr(), n, int(min_size), best.data_ptr(),
+                                         merge.data_ptr(), picked.data_ptr(), _stream()), "dm_slic_absorb_pick")
+    picked = int(picked)
+    if picked == 0:
+        return None
+    root = merge_components(edges, merge, n).long()
+    dense = torch.cumsum((root == torch.arange(n, device=dev)).to(torch.int64), 0) - 1
+    return dense[root], int(dense[-1]) + 1, picked
+
+
 def absorb_small(labels: torch.Tensor, n_labels: int, min_size: int, on_round=None) -> Tuple[torch.Tensor, int, int]:
     """Step 5 of the SLIC rule on a raster of connected regions 0..n_labels-1 numbered by first pixel: (labels, n, rounds).
-    Per round: rag_edges, one 64-bit max per small region (dm_slic_absorb_pick), merge_components over the picked edges,
-    relabel_raster; the areas are folded, not recounted.  A few small readbacks per round, as merge_regions has them.
+    Per round: rag_edges, one `_absorb_round`, relabel_raster; the areas are folded, not recounted.  A few small readbacks per
+    round, as merge_regions has them.
     on_round(round): called before every round (tools/mb_slic.py times the rounds with it)."""
-    n, rounds, dev, lib = int(n_labels), 0, labels.device, _lib.lib()
+    n, rounds, dev = int(n_labels), 0, labels.device
     area = label_area(labels, n)
     while n > 1:
         if on_round is not None:
             on_round(rounds)
         edges, weights = rag_edges(labels, n)
-        E = edges.shape[0]
-        if E == 0:
+        got = _absorb_round(edges, weights, area, n, min_size)
+        if got is None:
             break
-        best = torch.empty(n, dtype=torch.int64, device=dev)
-        merge = torch.empty(E, dtype=torch.uint8, device=dev)
-        picked = torch.empty(1, dtype=torch.int32, device=dev)
-        check(lib.dm_slic_absorb_pick(edges.data_ptr(), weights.data_ptr(), E, area.data_ptr(), n, int(min_size), best.data_ptr(),
-                                      merge.data_ptr(), picked.data_ptr(), _stream()), "dm_slic_absorb_pick")
-        if int(picked) == 0:
-            break
-        root = merge_components(edges, merge, n).long()
-        is_root = root == torch.arange(n, device=dev)
-        dense = torch.cumsum(is_root.to(torch.int64), 0) - 1      # a united region's first pixel is that of its smallest member
-        mapping = dense[root]
-        n_new = int(dense[-1]) + 1
-        area = torch.zeros(n_new, dtype=torch.int32, device=dev).index_add_(0, mapping, area)
+        mapping, n, _ = got
+        area = torch.zeros(n, dtype=torch.int32, device=dev).index_add_(0, mapping, area)
         labels = relabel_raster(labels, mapping.to(torch.int32))
-        n, rounds = n_new, rounds + 1
+        rounds += 1
     return labels, n, rounds
 
 

@@ -84,18 +84,6 @@ class ArraySource:
         return np.ascontiguousarray(self.array[..., y0:y1, x0:x1])
 
 
-def tile_grid(H: int, W: int, tile) -> List[Core]:
-    """The row-major list of (y0, y1, x0, x1) cores that cover an H x W scene in tiles of `tile` (an int or (th, tw)); the last
-    row and column are ragged, down to 1 pixel."""
-    th, tw = (tile, tile) if isinstance(tile, int) else tuple(tile)
-    th, tw, H, W = int(th), int(tw), int(H), int(W)
-    if th < 1 or tw < 1:
-        raise ValueError(f"tile must be >= 1, got {tile}")
-    if H < 1 or W < 1:
-        raise ValueError(f"the scene must have at least one pixel, got {H} x {W}")
-    return [(y, min(H, y + th), x, min(W, x + tw)) for y in range(0, H, th) for x in range(0, W, tw)]
-
-
 def halo_of(max_window: int) -> int:
     """Pixels a tile's window is grown by on every side: the crop of a window of side L <= max_window around (mx, my) starts at
     (2 mx - L) / 2 >= mx - (max_window + 1) // 2 and ends before mx + L / 2 + 1."""
@@ -106,6 +94,63 @@ def window_of(core: Core, H: int, W: int, halo: int) -> Core:
     """The core grown by `halo` on every side, clipped to the scene."""
     y0, y1, x0, x1 = core
     return max(0, y0 - halo), min(H, y1 + halo), max(0, x0 - halo), min(W, x1 + halo)
+
+
+@dataclass(frozen=True)
+class _Grid:
+    """The tile grid of one call, built once by `_Grid.of(H, W, tile)`: an H x W scene in ny x nx tiles of th x tw pixels (tile: an
+    int or (th, tw)), the last row and column ragged, down to 1 pixel; cores: the tiles' (y0, y1, x0, x1), row-major."""
+    H: int
+    W: int
+    th: int
+    tw: int
+    ny: int
+    nx: int
+    cores: List[Core]
+
+    @classmethod
+    def of(cls, H: int, W: int, tile) -> "_Grid":
+        th, tw = (tile, tile) if isinstance(tile, int) else tuple(tile)
+        th, tw, H, W = int(th), int(tw), int(H), int(W)
+        if th < 1 or tw < 1:
+            raise ValueError(f"tile must be >= 1, got {tile}")
+        if H < 1 or W < 1:
+            raise ValueError(f"the scene must have at least one pixel, got {H} x {W}")
+        cores = [(y, min(H, y + th), x, min(W, x + tw)) for y in range(0, H, th) for x in range(0, W, tw)]
+        return cls(H, W, th, tw, -(-H // th), -(-W // tw), cores)
+
+    def __len__(self) -> int:
+        return len(self.cores)
+
+    def window(self, i: int, halo: int) -> Tuple[Core, Core, Tuple[int, int]]:
+        """Tile i's window (`window_of` its core), the core's box in window coordinates, and the window's origin (oy, ox)."""
+        y0, y1, x0, x1 = self.cores[i]
+        wy0, wy1, wx0, wx1 = box = window_of(self.cores[i], self.H, self.W, halo)
+        return box, (y0 - wy0, y1 - wy0, x0 - wx0, x1 - wx0), (wy0, wx0)
+
+    def max_window(self, halo: int) -> Tuple[int, int]:
+        """(side_y, side_x): the largest height and width among the grid's windows.  A window's height depends on its tile row only
+        and its width on its column only; along either axis the windows grow while the halo is still clipped at the scene's start
+        (tile q with q t <= halo) and never after, so two tiles decide: the first two when halo < t."""
+        def side(n: int, t: int, count: int) -> int:
+            q = min(halo // t, count - 1)
+            return max(min(n, (r + 1) * t + halo) - max(0, r * t - halo) for r in (q, min(q + 1, count - 1)))
+        return side(self.H, self.th, self.ny), side(self.W, self.tw, self.nx)
+
+    def tile_of(self, xy: torch.Tensor) -> torch.Tensor:
+        """int64 [P]: the index in `cores` of the tile whose core holds every point (x, y) of xy [P,2]."""
+        return torch.div(xy[:, 1].long(), self.th, rounding_mode="floor") * self.nx + torch.div(xy[:, 0].long(), self.tw, rounding_mode="floor")
+
+
+def point_tiles(xy: torch.Tensor, W: int, tile) -> torch.Tensor:
+    """int64 [P]: the row-major index in `tile_grid(H, W, tile)` of the tile whose core holds every point (x, y) of xy [P,2]."""
+    return _Grid.of(1, W, tile).tile_of(xy)                      # (the index does not depend on H: one row of tiles will do)
+
+
+def tile_grid(H: int, W: int, tile) -> List[Core]:
+    """The row-major list of (y0, y1, x0, x1) cores that cover an H x W scene in tiles of `tile` (an int or (th, tw)); the last
+    row and column are ragged, down to 1 pixel."""
+    return _Grid.of(H, W, tile).cores
 
 
 def _as_source(source):
@@ -142,25 +187,69 @@ class _Clock:
             self.t = now
 
 
-def _check_scene(source, tile, max_window: int, labels_out):
+# ---- the limits the pipelines share: each a ValueError before any read ------------------------------------------------------------------
+def _image_shape(source) -> Tuple[int, int, int]:
     shape = tuple(source.shape)
     if len(shape) != 3 or min(shape) < 1:
         raise ValueError(f"source.shape must be (bands, H, W) with bands, H, W >= 1, got {shape}")
-    bands, H, W = (int(v) for v in shape)
+    return tuple(int(v) for v in shape)
+
+
+def _label_shape(source, name: str) -> Tuple[int, int]:
+    shape = tuple(source.shape)
+    if len(shape) != 2 or min(shape) < 1:
+        raise ValueError(f"{name}.shape must be (H, W) with H, W >= 1, got {shape}")
+    return tuple(int(v) for v in shape)
+
+
+def _out_raster(out, H: int, W: int, name: str) -> np.ndarray:
+    """`out`, allocated if None: the host raster a call writes into."""
+    if out is None:
+        return np.empty((H, W), dtype=np.int32)
+    if not isinstance(out, np.ndarray) or out.dtype != np.int32 or out.shape != (H, W) or not out.flags.writeable:
+        raise ValueError(f"{name} must be a writable int32 [{H},{W}] numpy array or memmap")
+    return out
+
+
+def _halo_grid(H: int, W: int, tile, max_window: int) -> Tuple[_Grid, int]:
+    """(grid, halo) of a call whose windows hold the encoder's crops: max_window, the tile, then every window below 2^31 pixels."""
     if not 1 <= int(max_window) <= rag.MAX_WINDOW:
         raise ValueError(f"max_window must be in 1..{rag.MAX_WINDOW}, got {max_window}")
-    tiles = tile_grid(H, W, tile)
-    halo = halo_of(max_window)
-    # a window's height depends on its tile row only, its width on its tile column only
-    side_y = max(min(H, y1 + halo) - max(0, y0 - halo) for y0, y1 in {c[:2] for c in tiles})
-    side_x = max(min(W, x1 + halo) - max(0, x0 - halo) for x0, x1 in {c[2:] for c in tiles})
+    grid, halo = _Grid.of(H, W, tile), halo_of(max_window)
+    side_y, side_x = grid.max_window(halo)
     if side_y * side_x >= 1 << 31:
         raise ValueError(f"a tile's window (core + halo of {halo}) must have fewer than 2^31 pixels, got {side_y} x {side_x}")
-    if labels_out is None:
-        labels_out = np.empty((H, W), dtype=np.int32)
-    elif not isinstance(labels_out, np.ndarray) or labels_out.dtype != np.int32 or labels_out.shape != (H, W) or not labels_out.flags.writeable:
-        raise ValueError(f"labels_out must be a writable int32 [{H},{W}] numpy array or memmap")
-    return bands, H, W, tiles, halo, labels_out
+    return grid, halo
+
+
+def _check_scene(source, tile, max_window: int, labels_out):
+    """Returns (bands, H, W, grid, halo, labels_out)."""
+    bands, H, W = _image_shape(source)
+    grid, halo = _halo_grid(H, W, tile, max_window)
+    return bands, H, W, grid, halo, _out_raster(labels_out, H, W, "labels_out")
+
+
+def _border(raster: torch.Tensor) -> Tuple[torch.Tensor, ...]:
+    """The (top, bottom, left, right) lines of a tile's raster, cloned: what `_seam_pairs` takes of it."""
+    return raster[0].clone(), raster[-1].clone(), raster[:, 0].clone(), raster[:, -1].clone()
+
+
+def _seam_pairs(strips: list, nx: int, ny: int, dev) -> Tuple[torch.Tensor, ...]:
+    """All seams of the scene, concatenated: for every seam position the entries of the two facing pixels (left / right of every
+    vertical seam, above / below every horizontal one), per field of the strips (strips[i] = a tuple of fields of tile i, each a
+    `_border`).  Returns (a, b) per field."""
+    fields = len(strips[0])
+    sa, sb = [[] for _ in range(fields)], [[] for _ in range(fields)]
+    for r in range(ny):
+        for c in range(nx):
+            for f in range(fields):
+                top, bottom, left, right = strips[r * nx + c][f]
+                if c + 1 < nx:
+                    sa[f].append(right); sb[f].append(strips[r * nx + c + 1][f][2])
+                if r + 1 < ny:
+                    sa[f].append(bottom); sb[f].append(strips[(r + 1) * nx + c][f][0])
+    empty = torch.empty(0, dtype=torch.int32, device=dev)
+    return tuple((torch.cat(sa[f]), torch.cat(sb[f])) if sa[f] else (empty, empty) for f in range(fields))
 
 
 def _scene_graph(source, tile=4096, segmenter: Optional[Callable] = None, k: int = 3, max_window: int = rag.MAX_WINDOW,
@@ -168,22 +257,17 @@ def _scene_graph(source, tile=4096, segmenter: Optional[Callable] = None, k: int
     """The first pass of `segment_scene`, everything but the encoder and the merge: per tile segment, statistics, edges, points;
     then the seam stitch, the edge sort and the designed features.  Returns the fields of a SceneResult that do not need a net."""
     source = _as_source(source)
-    bands, H, W, tiles, halo, labels_out = _check_scene(source, tile, max_window, labels_out)
+    bands, H, W, grid, halo, labels_out = _check_scene(source, tile, max_window, labels_out)
     segmenter = rag.slic if segmenter is None else segmenter
-    dev, i32 = torch.device(device), torch.int32
-    nx = sum(1 for t in tiles if t[0] == 0)
-    ny = len(tiles) // nx
+    dev, i32, tiles = torch.device(device), torch.int32, grid.cores
     clock = _Clock(stage_times, dev)
     offsets, point_offsets = [0], [0]
     stats_parts: Dict[str, list] = {key: [] for key in rag._STAT_KEYS}
     edge_parts, weight_parts, strips = [], [], []
     pt_parts: Dict[str, list] = {f: [] for f in ("xy", "label", "inner", "obj", "ptr", "bbox", "round")}
     nb = min(bands, 3)
-    for i, core in enumerate(tiles):
-        y0, y1, x0, x1 = core
-        # (the first pass needs the core only; the halo is what the encoder's crops reach into, in the second pass)
-        core_tile = _read(source, core, torch.uint8, 3, dev)
-        clock.lap("read + copy")
+    # (the first pass needs the core only; the halo is what the encoder's crops reach into, in the second pass)
+    for i, (y0, y1, x0, x1), core_tile, _, _ in _windows(source, grid, 0, torch.uint8, 3, dev, clock):
         labels, n = segmenter(core_tile)
         n = int(n)
         if labels.dtype != i32 or tuple(labels.shape) != (y1 - y0, x1 - x0) or n < 1:
@@ -213,7 +297,7 @@ def _scene_graph(source, tile=4096, segmenter: Optional[Callable] = None, k: int
         pt_parts["ptr"].append(pts.ptr[:-1] + point_offsets[-1])
         pt_parts["bbox"].append(torch.where(pts.bbox[:, 2:3] >= 0, pts.bbox + shift, pts.bbox))
         glob = torch.where(inside, local + off, local)
-        strips.append((glob[0].clone(), glob[-1].clone(), glob[:, 0].clone(), glob[:, -1].clone()))      # top, bottom, left, right
+        strips.append((_border(glob),))
         offsets.append(off + n)
         point_offsets.append(point_offsets[-1] + pts.xy.shape[0])
         clock.lap("graph")
@@ -222,17 +306,7 @@ def _scene_graph(source, tile=4096, segmenter: Optional[Callable] = None, k: int
     S, P = offsets[-1], point_offsets[-1]
     stats = {key: torch.cat(stats_parts[key]).contiguous() for key in rag._STAT_KEYS}
     stats["bands"] = nb
-    # all seams of the scene, concatenated: the pixels left / right of every vertical seam, above / below every horizontal one
-    sa, sb = [], []
-    for r in range(ny):
-        for c in range(nx):
-            top, bottom, left, right = strips[r * nx + c]
-            if c + 1 < nx:
-                sa.append(right); sb.append(strips[r * nx + c + 1][2])
-            if r + 1 < ny:
-                sa.append(bottom); sb.append(strips[(r + 1) * nx + c][0])
-    empty = torch.empty(0, dtype=i32, device=dev)
-    a, b = (torch.cat(sa), torch.cat(sb)) if sa else (empty, empty)
+    (a, b), = _seam_pairs(strips, grid.nx, grid.ny, dev)
     # (a seam position adds at most one distinct pair: the table is sized for the seams, not for the scene)
     seam_edges, seam_weights = rag.seam_stitch(a, b, S, stats["peri"], max_edges=max(1024, min(8 * S, int(a.numel()))))
     clock.lap("stitch")
@@ -247,7 +321,7 @@ def _scene_graph(source, tile=4096, segmenter: Optional[Callable] = None, k: int
     clock.lap("graph")
     return dict(n_labels=S, tiles=tiles, offsets=offsets, point_offsets=point_offsets, stats=stats, designed=designed, edges=edges,
                 weights=weights, points=points, labels=labels_out, halo=halo, n_seam=int(a.numel()), n_seam_edges=int(seam_edges.shape[0]),
-                source=source, device=dev)
+                source=source, device=dev, grid=grid)
 
 
 @dataclass
@@ -279,11 +353,7 @@ class SceneResult:
 
     def write_merged(self, out=None) -> np.ndarray:
         """Streams every tile of the merged raster into `out`, a writable int32 [H,W] numpy array or memmap (allocated if None)."""
-        H, W = (int(v) for v in self.labels.shape)
-        if out is None:
-            out = np.empty((H, W), dtype=np.int32)
-        elif not isinstance(out, np.ndarray) or out.dtype != np.int32 or out.shape != (H, W) or not out.flags.writeable:
-            raise ValueError(f"out must be a writable int32 [{H},{W}] numpy array or memmap")
+        out = _out_raster(out, *(int(v) for v in self.labels.shape), "out")
         for i, (y0, y1, x0, x1) in enumerate(self.tiles):
             out[y0:y1, x0:x1] = self.merged_tile(i).cpu().numpy()
         return out
@@ -412,28 +482,47 @@ def segment_scene(fio, source, tile=4096, segmenter: Optional[Callable] = None, 
     if n_labels is not None:
         raise ValueError("n_labels goes with labels")
     g = _scene_graph(source, tile, segmenter, k, max_window, labels_out, device=fio.device, stage_times=stage_times)
-    dev, pts, H, W = g["device"], g["points"], g["labels"].shape[0], g["labels"].shape[1]
-    clock = _Clock(stage_times, dev)
-    P = pts.xy.shape[0]
-    if P < 1:
+    clock = _Clock(stage_times, g["device"])
+    _need_points(g["points"])
+    offs = g["point_offsets"]
+    rows = [slice(lo, hi) if hi > lo else None for lo, hi in zip(offs, offs[1:])]
+    return _encode_and_merge(fio, g, rows, clock, margin, batch_size, merge_kwargs)
+
+
+def _need_points(pts: "rag.PointSamples"):
+    if pts.xy.shape[0] < 1:
         raise ValueError("the scene has no sample point (no pixel carries a superpixel id)")
-    features = torch.empty((P, 100), dtype=torch.float32, device=dev)
-    for i, core in enumerate(g["tiles"]):
-        lo, hi = g["point_offsets"][i], g["point_offsets"][i + 1]
-        if hi == lo:
-            continue
-        wy0, wy1, wx0, wx1 = box = window_of(core, H, W, g["halo"])
-        window = _read(g["source"], box, torch.uint8, 3, dev)
-        clock.lap("read + copy")
-        origin = torch.tensor([wx0, wy0], dtype=torch.int32, device=dev)
-        features[lo:hi] = fio.extract_features_from_tile(window, pts.xy[lo:hi] - origin, pts.inner[lo:hi], pts.obj[lo:hi],
-                                                         g["designed"][pts.label[lo:hi].long()], batch_size=batch_size)
+
+
+def _encode_and_merge(fio, g: dict, rows: list, clock: _Clock, margin: float, batch_size: int, merge_kwargs: dict) -> SceneResult:
+    """What `segment_scene` and `segment_labels` end in: the encoder over every tile's halo window, then the one merge.  g: the
+    graph dict; rows[i]: the rows of tile i's points in the points' tables, a slice or an index tensor, None for a tile without
+    points (it is not read)."""
+    dev, pts = g["device"], g["points"]
+    features = torch.empty((pts.xy.shape[0], 100), dtype=torch.float32, device=dev)
+    only = [i for i, r in enumerate(rows) if r is not None]
+    for i, _, window, _, (oy, ox) in _windows(g["source"], g["grid"], g["halo"], torch.uint8, 3, dev, clock, only):
+        r = rows[i]
+        origin = torch.tensor([ox, oy], dtype=torch.int32, device=dev)
+        features[r] = fio.extract_features_from_tile(window, pts.xy[r] - origin, pts.inner[r], pts.obj[r], g["designed"][pts.label[r].long()],
+                                                     batch_size=batch_size)
         clock.lap("encode")
     fio.features = features
     result = rag.merge_regions(features, pts.ptr, pts.idx, g["edges"], margin=margin, weights=g["weights"], stats=g["stats"], **merge_kwargs)
     clock.lap("merge")
     return SceneResult(result=result, n_labels=g["n_labels"], tiles=g["tiles"], offsets=g["offsets"], stats=g["stats"], designed=g["designed"],
                        edges=g["edges"], weights=g["weights"], points=pts, features=features, labels=g["labels"])
+
+
+def _windows(source, grid: _Grid, halo: int, dtype: torch.dtype, ndim: int, dev, clock: _Clock, only=None):
+    """The halo-window stream of every pipeline: per tile (i, core, window on the device, the core's box in window coordinates, the
+    window's origin (oy, ox) in the scene), the window being the core and `halo` pixels of its neighbours, clipped to the scene.
+    dtype, ndim: what the source must deliver; only: the tiles to read, default all."""
+    for i in range(len(grid)) if only is None else only:
+        wbox, box, origin = grid.window(i, halo)
+        window = _read(source, wbox, dtype, ndim, dev)
+        clock.lap("read + copy")
+        yield i, grid.cores[i], window, box, origin
 
 
 # ---- a scene from a label raster whose regions cross tile seams (DESIGN.md 3.5.14; csrc/dm_scene_points.hip) ------------------------
@@ -443,11 +532,8 @@ MAX_SCENE_SIDE = (1 << 31) - 1        # points and boxes are int32
 
 def _check_labels(labels, n_labels, k, max_window, tile, like: Optional[tuple] = None):
     """The limits of the calls below, each a ValueError before any device work.  labels: the label source; like: the (H, W) the
-    raster must have (the image's).  Returns (H, W, S, k, tiles, halo)."""
-    shape = tuple(labels.shape)
-    if len(shape) != 2 or min(shape) < 1:
-        raise ValueError(f"labels.shape must be (H, W) with H, W >= 1, got {shape}")
-    H, W = (int(v) for v in shape)
+    raster must have (the image's).  Returns (H, W, S, k, grid, halo)."""
+    H, W = _label_shape(labels, "labels")
     if like is not None and (H, W) != tuple(like):
         raise ValueError(f"labels must cover the scene: labels.shape = ({H}, {W}), the source has {like[0]} x {like[1]} pixels")
     if H > MAX_SCENE_SIDE or W > MAX_SCENE_SIDE or H * W > MAX_POINT_SCENE:
@@ -457,25 +543,7 @@ def _check_labels(labels, n_labels, k, max_window, tile, like: Optional[tuple] =
         raise ValueError(f"n_labels must be in 1..2^24, got {n_labels}")
     if not 1 <= int(k) <= rag.MAX_POINTS:
         raise ValueError(f"k must be in 1..{rag.MAX_POINTS}, got {k}")
-    if not 1 <= int(max_window) <= rag.MAX_WINDOW:
-        raise ValueError(f"max_window must be in 1..{rag.MAX_WINDOW}, got {max_window}")
-    th, tw = (tile, tile) if isinstance(tile, int) else tuple(tile)
-    if int(th) < 1 or int(tw) < 1:
-        raise ValueError(f"tile must be >= 1, got {tile}")
-    halo = halo_of(max_window)
-    # a window's height depends on its tile row only, its width on its column only
-    side = lambda n, t: max(min(n, y + int(t) + halo) - max(0, y - halo) for y in range(0, n, int(t)))
-    side_y, side_x = side(H, th), side(W, tw)
-    if side_y * side_x >= 1 << 31:
-        raise ValueError(f"a tile's window (core + halo of {halo}) must have fewer than 2^31 pixels, got {side_y} x {side_x}")
-    return H, W, S, int(k), tile_grid(H, W, tile), halo
-
-
-def point_tiles(xy: torch.Tensor, W: int, tile) -> torch.Tensor:
-    """int64 [P]: the row-major index in `tile_grid(H, W, tile)` of the tile whose core holds every point (x, y) of xy [P,2]."""
-    th, tw = (tile, tile) if isinstance(tile, int) else tuple(tile)
-    nx = (int(W) + int(tw) - 1) // int(tw)
-    return torch.div(xy[:, 1].long(), int(th), rounding_mode="floor") * nx + torch.div(xy[:, 0].long(), int(tw), rounding_mode="floor")
+    return (H, W, S, int(k), *_halo_grid(H, W, tile, max_window))
 
 
 def _compact_ids(labels: torch.Tensor, n_labels: int) -> Tuple[torch.Tensor, torch.Tensor]:
@@ -499,7 +567,7 @@ def sample_points(labels, n_labels: int, k: int = 3, max_window: int = rag.MAX_W
     label raster, because round j + 1 scores against round j's winners.  Limits, each a ValueError before any device work: H, W <
     2^31 and H W <= 2^48; n_labels in 1..2^24; k in 1..16; max_window in 1..384; every window below 2^31 pixels."""
     source = _as_source(labels)
-    H, W, S, k, tiles, halo = _check_labels(source, n_labels, k, max_window, tile)
+    H, W, S, k, grid, halo = _check_labels(source, n_labels, k, max_window, tile)
     dev, lib, i32 = torch.device(device), _lib.lib(), torch.int32
     clock = _Clock(stage_times, dev)
     best = torch.empty(S, dtype=torch.int64, device=dev)
@@ -508,17 +576,13 @@ def sample_points(labels, n_labels: int, k: int = 3, max_window: int = rag.MAX_W
     cnt = torch.empty(S, dtype=i32, device=dev)
     bbox = torch.empty((S, 4), dtype=i32, device=dev)
     for j in range(k):
-        for i, core in enumerate(tiles):
-            y0, y1, x0, x1 = core
-            wy0, wy1, wx0, wx1 = box = window_of(core, H, W, halo)
-            window = _read(source, box, i32, 2, dev).contiguous()
-            clock.lap("read + copy")
+        for i, _, window, box, (oy, ox) in _windows(source, grid, halo, i32, 2, dev, clock):
+            window = window.contiguous()
             clr = rag.clearance(window, max_window)
             if i == 0 and j == 0:                                # (behind the first read: a source of the wrong kind fails before any launch)
                 check(lib.dm_scene_point_init(best.data_ptr(), cnt.data_ptr(), bbox.data_ptr(), S, _stream()), "dm_scene_point_init")
-            check(lib.dm_scene_point_select(window.data_ptr(), clr.data_ptr(), wy1 - wy0, wx1 - wx0, y0 - wy0, y1 - wy0, x0 - wx0, x1 - wx0,
-                                            wy0, wx0, H, W, S, k, j, pts.data_ptr(), cnt.data_ptr(), best.data_ptr(), bbox.data_ptr(),
-                                            _stream()), "dm_scene_point_select")
+            check(lib.dm_scene_point_select(window.data_ptr(), clr.data_ptr(), *window.shape, *box, oy, ox, H, W, S, k, j, pts.data_ptr(),
+                                            cnt.data_ptr(), best.data_ptr(), bbox.data_ptr(), _stream()), "dm_scene_point_select")
             clock.lap(f"points round {j}")
         check(lib.dm_scene_point_commit(best.data_ptr(), H, W, S, k, pts.data_ptr(), pclr.data_ptr(), cnt.data_ptr(), _stream()),
               "dm_scene_point_commit")
@@ -545,14 +609,9 @@ def label_graph(source, labels, n_labels: int, tile=4096, k: int = 3, max_window
     weights of equal keys added (a pair can occur in several tiles and on seams), the designed features, and `sample_points`
     (points=False leaves it out: `mrs_labels`).  `n_edge_parts` is the number of edge rows before the fold."""
     source, lsource = _as_source(source), _as_source(labels)
-    shape = tuple(source.shape)
-    if len(shape) != 3 or min(shape) < 1:
-        raise ValueError(f"source.shape must be (bands, H, W) with bands, H, W >= 1, got {shape}")
-    bands = int(shape[0])
-    H, W, S, k, tiles, halo = _check_labels(lsource, n_labels, k, max_window, tile, like=(int(shape[1]), int(shape[2])))
-    dev, i32, i64 = torch.device(device), torch.int32, torch.int64
-    nx = sum(1 for t in tiles if t[0] == 0)
-    ny = len(tiles) // nx
+    bands, *like = _image_shape(source)
+    H, W, S, k, grid, halo = _check_labels(lsource, n_labels, k, max_window, tile, like=tuple(like))
+    dev, i32, i64, tiles = torch.device(device), torch.int32, torch.int64, grid.cores
     nb = min(bands, 3)
     clock = _Clock(stage_times, dev)
     stats = {"count": torch.zeros(S, dtype=i64, device=dev), "sum": torch.zeros((S, nb), dtype=i64, device=dev),
@@ -578,19 +637,10 @@ def label_graph(source, labels, n_labels: int, tile=4096, k: int = 3, max_window
             stats["bbox"][ids] = torch.cat((torch.minimum(seen[:, :2], box[:, :2]), torch.maximum(seen[:, 2:], box[:, 2:])), 1)
             key_parts.append(ids[e[:, 0].long()] * S + ids[e[:, 1].long()])               # ids ascend: a < b stays a < b
             weight_parts.append(w)
-        strips.append((glob[0].clone(), glob[-1].clone(), glob[:, 0].clone(), glob[:, -1].clone()))      # top, bottom, left, right
+        strips.append((_border(glob),))
         clock.lap("graph")
     stats["bands"] = nb
-    sa, sb = [], []
-    for r in range(ny):
-        for c in range(nx):
-            top, bottom, left, right = strips[r * nx + c]
-            if c + 1 < nx:
-                sa.append(right); sb.append(strips[r * nx + c + 1][2])
-            if r + 1 < ny:
-                sa.append(bottom); sb.append(strips[(r + 1) * nx + c][0])
-    empty = torch.empty(0, dtype=i32, device=dev)
-    a, b = (torch.cat(sa), torch.cat(sb)) if sa else (empty, empty)
+    (a, b), = _seam_pairs(strips, grid.nx, grid.ny, dev)
     seam_edges, seam_weights = rag.seam_stitch(a, b, S, stats["peri"], max_edges=max(1024, min(8 * S, int(a.numel()))))
     clock.lap("stitch")
     keys = torch.cat(key_parts + [seam_edges[:, 0].long() * S + seam_edges[:, 1].long()])
@@ -602,7 +652,7 @@ def label_graph(source, labels, n_labels: int, tile=4096, k: int = 3, max_window
     pts = sample_points(lsource, S, k=k, max_window=max_window, tile=tile, device=dev, stage_times=stage_times) if points else None
     return dict(n_labels=S, tiles=tiles, offsets=None, point_offsets=None, stats=stats, designed=designed, edges=edges, weights=weights,
                 points=pts, labels=labels if isinstance(labels, np.ndarray) else lsource, halo=halo, n_seam=int(a.numel()),
-                n_seam_edges=int(seam_edges.shape[0]), n_edge_parts=int(keys.numel()), source=source, device=dev)
+                n_seam_edges=int(seam_edges.shape[0]), n_edge_parts=int(keys.numel()), source=source, device=dev, grid=grid)
 
 
 def segment_labels(fio, source, labels, n_labels: int, tile=4096, k: int = 3, margin: float = 1.0, max_window: int = rag.MAX_WINDOW,
@@ -617,32 +667,13 @@ def segment_labels(fio, source, labels, n_labels: int, tile=4096, k: int = 3, ma
     by index, so the points stay sorted by (superpixel, round) scene-wide.  The result's `offsets` is None.  Limits: those of
     `sample_points`; an id that never occurs has count 0, the empty box and no points."""
     g = label_graph(source, labels, n_labels, tile=tile, k=k, max_window=max_window, device=fio.device, stage_times=stage_times)
-    dev, pts, tiles = g["device"], g["points"], g["tiles"]
-    H, W = tiles[-1][1], tiles[-1][3]
-    clock = _Clock(stage_times, dev)
-    P = pts.xy.shape[0]
-    if P < 1:
-        raise ValueError("the scene has no sample point (no pixel carries a superpixel id)")
-    tile_of = point_tiles(pts.xy, W, tile)
+    clock = _Clock(stage_times, g["device"])
+    _need_points(g["points"])
+    tile_of = g["grid"].tile_of(g["points"].xy)
     order = torch.argsort(tile_of, stable=True)                  # within a tile the rows keep their (superpixel, round) order
-    ends = torch.cumsum(torch.bincount(tile_of, minlength=len(tiles)), 0).tolist()
-    features = torch.empty((P, 100), dtype=torch.float32, device=dev)
-    for i, core in enumerate(tiles):
-        rows = order[(ends[i - 1] if i else 0):ends[i]]
-        if rows.numel() == 0:
-            continue
-        wy0, wy1, wx0, wx1 = box = window_of(core, H, W, g["halo"])
-        window = _read(g["source"], box, torch.uint8, 3, dev)
-        clock.lap("read + copy")
-        origin = torch.tensor([wx0, wy0], dtype=torch.int32, device=dev)
-        features[rows] = fio.extract_features_from_tile(window, pts.xy[rows] - origin, pts.inner[rows], pts.obj[rows],
-                                                        g["designed"][pts.label[rows].long()], batch_size=batch_size)
-        clock.lap("encode")
-    fio.features = features
-    result = rag.merge_regions(features, pts.ptr, pts.idx, g["edges"], margin=margin, weights=g["weights"], stats=g["stats"], **merge_kwargs)
-    clock.lap("merge")
-    return SceneResult(result=result, n_labels=g["n_labels"], tiles=tiles, offsets=None, stats=g["stats"], designed=g["designed"],
-                       edges=g["edges"], weights=g["weights"], points=pts, features=features, labels=g["labels"])
+    ends = torch.cumsum(torch.bincount(tile_of, minlength=len(g["tiles"])), 0).tolist()
+    rows = [order[lo:hi] if hi > lo else None for lo, hi in zip([0] + ends, ends)]
+    return _encode_and_merge(fio, g, rows, clock, margin, batch_size, merge_kwargs)
 
 
 def mrs_labels(source, labels, n_labels: int, scale: float, shape: float = 0.1, compactness: float = 0.5, band_weights=None,
@@ -663,11 +694,8 @@ MAX_TRACE_SCENE = 1 << 60             # DM_SCENE_VECTOR_MAX_PIXELS: dart ids 4 (
 MAX_DARTS = 1 << 31                   # slots are int32
 
 
-def _check_trace(source, n_labels, tile) -> Tuple[int, int, int, List[Core]]:
-    shape = tuple(source.shape)
-    if len(shape) != 2 or min(shape) < 1:
-        raise ValueError(f"source.shape must be (H, W) with H, W >= 1, got {shape}")
-    H, W = (int(v) for v in shape)
+def _check_trace(source, n_labels, tile) -> Tuple[int, int, int, _Grid]:
+    H, W = _label_shape(source, "source")
     if H >= MAX_TRACE_SIDE or W >= MAX_TRACE_SIDE:
         raise ValueError(f"H and W must be below 2^31 - 1, got {H} x {W}")
     if H * W > MAX_TRACE_SCENE:
@@ -675,15 +703,11 @@ def _check_trace(source, n_labels, tile) -> Tuple[int, int, int, List[Core]]:
     S = int(n_labels)
     if not 1 <= S < 1 << 31:
         raise ValueError(f"n_labels must be in 1..2^31-1, got {n_labels}")
-    th, tw = (tile, tile) if isinstance(tile, int) else tuple(tile)
-    if int(th) < 1 or int(tw) < 1:
-        raise ValueError(f"tile must be >= 1, got {tile}")
-    # a window's height depends on its tile row only, its width on its column only, and neither grows behind the second
-    side = lambda n, t: max(min(n, y + t + 1) - max(0, y - 1) for y in range(0, min(n, 2 * t), t))
-    side_y, side_x = side(H, int(th)), side(W, int(tw))
+    grid = _Grid.of(H, W, tile)
+    side_y, side_x = grid.max_window(1)
     if side_y * side_x > rag.MAX_TRACE_PIXELS:
         raise ValueError(f"a tile's window (core + 1 pixel on every side) must have at most 2^28 pixels, got {side_y} x {side_x}")
-    return H, W, S, tile_grid(H, W, tile)
+    return H, W, S, grid
 
 
 def _check_darts(total: int, i: int, n_tiles: int):
@@ -738,37 +762,28 @@ def _join(ids: torch.Tensor, succ: torch.Tensor, lab: torch.Tensor, other: torch
     return dart, nxt.to(torch.int32), lab[order], other[order], flags, (slot << 32) | slot
 
 
-def _windows(source, H: int, W: int, S: int, tiles: List[Core], dev, clock: _Clock):
-    """The tile stream of `trace_labels` and `simplify_labels`: per tile (i, window int32 on the device, the core's box in window
-    coordinates, the window's origin (oy, ox) in the scene), the window being the core and one pixel of apron, clipped to the scene,
-    with its ids checked."""
-    for i, core in enumerate(tiles):
-        y0, y1, x0, x1 = core
-        wy0, wy1, wx0, wx1 = box = window_of(core, H, W, 1)
-        window = _read(source, box, torch.int32, 2, dev)
-        clock.lap("read + copy")
+def _scene_table(source, grid: _Grid, S: int, dev, clock: _Clock, nodes: Optional[list] = None):
+    """One stream of the scene's windows (the core and one pixel of apron, ids checked) into the joined dart table
+    `rag._trace_table` takes.  nodes: a list that receives every tile's node records (`_tile_nodes`) from the same windows, so
+    that the scene is read once."""
+    H, W = grid.H, grid.W
+    parts, total, n_nodes = [], 0, 0
+    for i, _, window, box, origin in _windows(source, grid, 1, torch.int32, 2, dev, clock):
         lo, hi = (int(v) for v in torch.aminmax(window))
         if lo < 0 or hi >= S:
-            raise ValueError(f"labels must be in 0..n_labels-1 = 0..{S - 1}: the window of tile {i} (rows {wy0}..{wy1 - 1}, columns "
-                             f"{wx0}..{wx1 - 1}) holds {lo}..{hi}")
-        yield i, window, (y0 - wy0, y1 - wy0, x0 - wx0, x1 - wx0), (wy0, wx0)
-
-
-def _scene_table(source, H: int, W: int, S: int, tiles: List[Core], dev, clock: _Clock, nodes: Optional[list] = None):
-    """One stream of the scene's windows into the joined dart table `rag._trace_table` takes.  nodes: a list that receives every
-    tile's node records (`_tile_nodes`) from the same windows, so that the scene is read once."""
-    parts, total, n_nodes = [], 0, 0
-    for i, window, box, origin in _windows(source, H, W, S, tiles, dev, clock):
+            (oy, ox), (wh, ww) = origin, window.shape
+            raise ValueError(f"labels must be in 0..n_labels-1 = 0..{S - 1}: the window of tile {i} (rows {oy}..{oy + wh - 1}, columns "
+                             f"{ox}..{ox + ww - 1}) holds {lo}..{hi}")
         got = _tile_darts(window, box, origin, H, W)
         if got is not None:
             total += int(got[0].numel())
-            _check_darts(total, i, len(tiles))
+            _check_darts(total, i, len(grid))
             parts.append(got)
         if nodes is not None:
             own = _tile_nodes(window, box, origin, H, W)
             if own is not None:
                 n_nodes += int(own.numel())
-                _check_nodes(n_nodes, i, len(tiles))
+                _check_nodes(n_nodes, i, len(grid))
                 nodes.append(own)
         clock.lap("per-tile passes")
     ids, succ, lab, other, sflags = (torch.cat([p[k] for p in parts]) for k in range(5))
@@ -792,15 +807,10 @@ def trace_labels(source, n_labels: int, tile=4096, stats: Optional[dict] = None,
     boundaries).  Limits, each a ValueError: H, W < 2^31 - 1 and H W <= 2^60; every window (core + 1 pixel) at most 2^28 pixels;
     ids outside 0..n_labels-1 (-1 included) name their tile; fewer than 2^31 darts in the scene.
     Memory: one window's rasters at a time; 25 bytes per dart of the scene while the tiles stream."""
-    source = _as_source(source)
-    H, W, S, tiles = _check_trace(source, n_labels, tile)
-    dev = torch.device(device)
-    clock = _Clock(None if stats is None else stats.setdefault("stage_s", {}), dev)
-    table = _scene_table(source, H, W, S, tiles, dev, clock)
-    polys, arcs, info = rag._trace_table(*table, W, S, mark=lambda stage: clock.lap(_TRACE_STAGE.get(stage, "emit")), wide=True)
+    polys, arcs, _, _, _, _, info, n_tiles = _scene_tables(source, n_labels, tile, device, stats, with_nodes=False)
     if stats is not None:
         stats.update(D=info["D"], rings=info["R"], arcs=info["A"], vertices=info["V"], arc_vertices=int(info["arc_xy"].shape[0]),
-                     head_rounds=info["head_rounds"], rank_rounds=info["rank_rounds"], tiles=len(tiles))
+                     head_rounds=info["head_rounds"], rank_rounds=info["rank_rounds"], tiles=n_tiles)
     return polys, arcs
 
 
@@ -985,20 +995,20 @@ def _simplify_tables(polys: "rag.Polygons", arcs: "rag.Arcs", node_row: torch.Te
     return out_polys, out_arcs, arc_keep
 
 
-def _scene_tables(source, n_labels: int, tile, device, stats: Optional[dict]):
-    """What `simplify_labels` and `simplify_conflicts` share: one stream of the scene into its traced rings and arcs and its sorted
-    node list.  Returns (polys, arcs, node_row, H, W, clock, info, number of tiles)."""
+def _scene_tables(source, n_labels: int, tile, device, stats: Optional[dict], with_nodes: bool = True):
+    """What `trace_labels`, `simplify_labels` and `simplify_conflicts` share: one stream of the scene into its traced rings and arcs
+    and (with_nodes) its sorted node list.  Returns (polys, arcs, node_row, H, W, clock, info, number of tiles)."""
     source = _as_source(source)
-    H, W, S, tiles = _check_trace(source, n_labels, tile)
+    H, W, S, grid = _check_trace(source, n_labels, tile)
     dev = torch.device(device)
     clock = _Clock(None if stats is None else stats.setdefault("stage_s", {}), dev)
-    nodes: List[torch.Tensor] = []
-    table = _scene_table(source, H, W, S, tiles, dev, clock, nodes)
+    nodes: Optional[List[torch.Tensor]] = [] if with_nodes else None
+    table = _scene_table(source, grid, S, dev, clock, nodes)
     polys, arcs, info = rag._trace_table(*table, W, S, mark=lambda stage: clock.lap(_TRACE_STAGE.get(stage, "emit")), wide=True)
     del table
-    node_row = torch.sort(torch.cat(nodes)).values
+    node_row = torch.sort(torch.cat(nodes)).values if with_nodes else None
     del nodes
-    return polys, arcs, node_row, H, W, clock, info, len(tiles)
+    return polys, arcs, node_row, H, W, clock, info, len(grid)
 
 
 def _simplify_scene(source, n_labels: int, tolerance: float, tile, stats: Optional[dict], device, topology: bool, max_rounds: int = 64,
@@ -1077,20 +1087,11 @@ MAX_SLIC_WEIGHT = 1 << 31             # a shared boundary's length is int32 in d
 
 def _check_scene_slic(source, tile, cell, compactness, iters, min_size, out, out_name: str, resident_bytes):
     """The limits of `slic_assign` / `slic_labels`, each a ValueError before any device work.  Returns (bands, H, W, K, min_size,
-    tiles, out)."""
-    shape = tuple(source.shape)
-    if len(shape) != 3 or min(shape) < 1:
-        raise ValueError(f"source.shape must be (bands, H, W) with bands, H, W >= 1, got {shape}")
-    bands, H, W = (int(v) for v in shape)
+    grid, out)."""
+    bands, H, W = _image_shape(source)
     if H > MAX_SLIC_SIDE or W > MAX_SLIC_SIDE:
         raise ValueError(f"the scene must have H, W < 2^31, got {H} x {W}")
-    if not 4 <= int(cell) <= 256:
-        raise ValueError(f"cell must be in 4..256, got {cell}")
-    if not 0 <= int(compactness) <= 255:
-        raise ValueError(f"compactness must be in 0..255, got {compactness}")
-    if int(iters) < 0:
-        raise ValueError(f"iters must be >= 0, got {iters}")
-    min_size = max(1, int(cell) * int(cell) // 4) if min_size is None else int(min_size)
+    min_size = rag._slic_params(cell, compactness, iters, min_size)
     if not 1 <= min_size < 1 << 31:
         raise ValueError(f"min_size must be in 1..2^31-1, got {min_size}")
     if int(resident_bytes) < 0:
@@ -1099,15 +1100,11 @@ def _check_scene_slic(source, tile, cell, compactness, iters, min_size, out, out
     K = ((H + cell - 1) // cell) * ((W + cell - 1) // cell)
     if K >= MAX_SLIC_CENTRES:
         raise ValueError(f"the scene's grid must have fewer than 2^31 centres, got {K} (cell = {cell}); use a larger cell")
-    tiles = tile_grid(H, W, tile)
-    th, tw = tiles[0][1] - tiles[0][0], tiles[0][3] - tiles[0][2]          # the first core is the largest
+    grid = _Grid.of(H, W, tile)
+    th, tw = grid.max_window(0)                                  # the largest core
     if th * tw >= 1 << 31:
         raise ValueError(f"a core must have fewer than 2^31 pixels, got {th} x {tw}")
-    if out is None:
-        out = np.empty((H, W), dtype=np.int32)
-    elif not isinstance(out, np.ndarray) or out.dtype != np.int32 or out.shape != (H, W) or not out.flags.writeable:
-        raise ValueError(f"{out_name} must be a writable int32 [{H},{W}] numpy array or memmap")
-    return bands, H, W, K, min_size, tiles, out
+    return bands, H, W, K, min_size, grid, _out_raster(out, H, W, out_name)
 
 
 class _Cores:
@@ -1115,9 +1112,9 @@ class _Cores:
     the device between passes while their total is within `budget` bytes, otherwise every pass reads them again from the source.
     Iterating yields (i, (y0, y1, x0, x1), core)."""
 
-    def __init__(self, source, tiles: List[Core], bands: int, H: int, W: int, budget: int, dev, clock: _Clock):
-        self.source, self.tiles, self.nb, self.dev, self.clock = source, tiles, min(bands, 4), dev, clock
-        self.resident = self.nb * H * W <= int(budget)
+    def __init__(self, source, grid: _Grid, bands: int, budget: int, dev, clock: _Clock):
+        self.source, self.tiles, self.nb, self.dev, self.clock = source, grid.cores, min(bands, 4), dev, clock
+        self.resident = self.nb * grid.H * grid.W <= int(budget)
         self.held: Dict[int, torch.Tensor] = {}
         self.reads = 0
 
@@ -1164,10 +1161,10 @@ def slic_assign(source, tile=4096, cell: int = 29, compactness: int = 10, iters:
     on the device), both equal to `rag.slic_assign(whole scene)` whatever the tile size.  Arguments as `slic_labels` takes them;
     assigned_out: a writable int32 [H,W] array or memmap, allocated if None."""
     source = _as_source(source)
-    bands, H, W, K, _, tiles, out = _check_scene_slic(source, tile, cell, compactness, iters, None, assigned_out, "assigned_out", resident_bytes)
+    bands, H, W, K, _, grid, out = _check_scene_slic(source, tile, cell, compactness, iters, None, assigned_out, "assigned_out", resident_bytes)
     dev = torch.device(device)
     clock = _Clock(stage_times, dev)
-    stream = _assigned_cores(_Cores(source, tiles, bands, H, W, resident_bytes, dev, clock), H, W, K, int(cell), int(compactness), int(iters), clock)
+    stream = _assigned_cores(_Cores(source, grid, bands, resident_bytes, dev, clock), H, W, K, int(cell), int(compactness), int(iters), clock)
     centres = next(stream)
     for i, (y0, y1, x0, x1), assigned in stream:
         out[y0:y1, x0:x1] = assigned.cpu().numpy()
@@ -1178,33 +1175,9 @@ def slic_assign(source, tile=4096, cell: int = 29, compactness: int = 10, iters:
 def _components(assigned: torch.Tensor) -> Tuple[torch.Tensor, int, torch.Tensor]:
     """`rag.connected_labels(assigned)` and, from the same call's parent table, first int64 [n]: the linear index in the raster of
     every component's first pixel (a component's root is its first pixel; the roots in raster order are the ids in order)."""
-    h, w = assigned.shape
-    dev, i32 = assigned.device, torch.int32
-    parent = torch.empty(h * w, dtype=i32, device=dev)
-    chunks = torch.empty((h * w + 4095) // 4096 + 1, dtype=i32, device=dev)
-    labels = torch.empty((h, w), dtype=i32, device=dev)
-    n = torch.empty(1, dtype=i32, device=dev)
-    check(_lib.lib().dm_connected_labels(assigned.data_ptr(), h, w, 0, 0, parent.data_ptr(), chunks.data_ptr(), labels.data_ptr(),
-                                         n.data_ptr(), _stream()), "dm_connected_labels")
-    first = torch.nonzero(parent == torch.arange(h * w, dtype=i32, device=dev)).view(-1)
-    return labels, int(n), first
-
-
-def _seam_pairs(strips: list, nx: int, ny: int, dev) -> Tuple[torch.Tensor, ...]:
-    """All seams of the scene, concatenated: for every seam position the entries of the two facing pixels, per field of the strips
-    (strips[i] = a tuple of fields, each (top, bottom, left, right)).  Returns (a, b) per field."""
-    fields = len(strips[0])
-    sa, sb = [[] for _ in range(fields)], [[] for _ in range(fields)]
-    for r in range(ny):
-        for c in range(nx):
-            for f in range(fields):
-                top, bottom, left, right = strips[r * nx + c][f]
-                if c + 1 < nx:
-                    sa[f].append(right); sb[f].append(strips[r * nx + c + 1][f][2])
-                if r + 1 < ny:
-                    sa[f].append(bottom); sb[f].append(strips[(r + 1) * nx + c][f][0])
-    empty = torch.empty(0, dtype=torch.int32, device=dev)
-    return tuple((torch.cat(sa[f]), torch.cat(sb[f])) if sa[f] else (empty, empty) for f in range(fields))
+    labels, n, parent = rag._connected_labels(assigned, None)
+    first = torch.nonzero(parent == torch.arange(parent.numel(), dtype=torch.int32, device=parent.device)).view(-1)
+    return labels, n, first
 
 
 def _fold_graph(mapping: torch.Tensor, n_new: int, area: torch.Tensor, edges: torch.Tensor, weights: torch.Tensor):
@@ -1247,13 +1220,11 @@ def slic_labels(source, tile=4096, cell: int = 29, compactness: int = 10, iters:
     (`rag.rag_edges`' table of 32 slots per component ends at 2^30); fewer than 2^31 provisional components and fewer than 2^31
     graph edges in the scene; a shared boundary below 2^31 pixel edges.  Areas are folded in 64 bits."""
     source = _as_source(source)
-    bands, H, W, K, min_size, tiles, out = _check_scene_slic(source, tile, cell, compactness, iters, min_size, labels_out, "labels_out",
-                                                             resident_bytes)
-    dev, lib, i32, i64 = torch.device(device), _lib.lib(), torch.int32, torch.int64
-    nx = sum(1 for t in tiles if t[0] == 0)
-    ny = len(tiles) // nx
+    bands, H, W, K, min_size, grid, out = _check_scene_slic(source, tile, cell, compactness, iters, min_size, labels_out, "labels_out",
+                                                            resident_bytes)
+    dev, i32, i64, tiles = torch.device(device), torch.int32, torch.int64, grid.cores
     clock = _Clock(stage_times, dev)
-    cores = _Cores(source, tiles, bands, H, W, resident_bytes, dev, clock)
+    cores = _Cores(source, grid, bands, resident_bytes, dev, clock)
     stream = _assigned_cores(cores, H, W, K, int(cell), int(compactness), int(iters), clock)
     next(stream)                                                 # the centres: not needed here
     base, first_parts, area_parts, edge_parts, weight_parts, strips = 0, [], [], [], [], []
@@ -1269,15 +1240,14 @@ def slic_labels(source, tile=4096, cell: int = 29, compactness: int = 10, iters:
         edge_parts.append(e.long() + base)
         weight_parts.append(wgt.long())
         prov = comp + base
-        border = lambda r: (r[0].clone(), r[-1].clone(), r[:, 0].clone(), r[:, -1].clone())      # top, bottom, left, right
-        strips.append((border(assigned), border(prov)))
+        strips.append((_border(assigned), _border(prov)))
         base += n
         clock.lap("components + graph")
         out[y0:y1, x0:x1] = prov.cpu().numpy()
         clock.lap("relabel + write")
     P = base
     # seams: equal centre ids on both sides unite the two provisional components; different ones are an edge of the graph
-    (ca, cb), (pa, pb) = _seam_pairs(strips, nx, ny, dev)
+    (ca, cb), (pa, pb) = _seam_pairs(strips, grid.nx, grid.ny, dev)
     same = ca == cb
     pairs = torch.unique(pa[same].long() * P + pb[same].long())
     if pairs.numel():
@@ -1303,21 +1273,12 @@ def slic_labels(source, tile=4096, cell: int = 29, compactness: int = 10, iters:
     clock.lap("seams")
     # absorption on the graph only: the rounds of rag.absorb_small, the raster untouched
     picks = []
-    while n > 1 and edges.shape[0]:
-        E = int(edges.shape[0])
-        e32, w32, a32 = edges.to(i32).contiguous(), weights.to(i32), area.clamp(max=(1 << 31) - 1).to(i32)   # `< min_size` survives the clamp
-        best = torch.empty(n, dtype=i64, device=dev)
-        merge = torch.empty(E, dtype=torch.uint8, device=dev)
-        picked = torch.empty(1, dtype=i32, device=dev)
-        check(lib.dm_slic_absorb_pick(e32.data_ptr(), w32.data_ptr(), E, a32.data_ptr(), n, min_size, best.data_ptr(), merge.data_ptr(),
-                                      picked.data_ptr(), _stream()), "dm_slic_absorb_pick")
-        if int(picked) == 0:
+    while n > 1:                                                 # (`< min_size` survives the clamp of the 64-bit areas)
+        got = rag._absorb_round(edges.to(i32).contiguous(), weights.to(i32), area.clamp(max=(1 << 31) - 1).to(i32), n, min_size)
+        if got is None:
             break
-        picks.append(int(picked))
-        root = rag.merge_components(e32, merge, n).long()
-        dense = torch.cumsum((root == torch.arange(n, device=dev)).to(i64), 0) - 1      # keeps the order: a union's first pixel is its smallest member's
-        step = dense[root]
-        n = int(dense[-1]) + 1
+        step, n, picked = got
+        picks.append(picked)
         area, edges, weights = _fold_graph(step, n, area, edges, weights)
         mapping = step[mapping]
     clock.lap("absorption rounds")

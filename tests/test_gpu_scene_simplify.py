@@ -69,8 +69,8 @@ def gpu_nodes(labels, tile):
     from deepmerge_amd import scene
     H, W = labels.shape
     parts = []
-    for _, window, box, origin in scene._windows(scene.ArraySource(labels), H, W, 1 << 30, scene.tile_grid(H, W, tile), torch.device(DEV),
-                                                 scene._Clock(None, DEV)):
+    for _, _, window, box, origin in scene._windows(scene.ArraySource(labels), scene._Grid.of(H, W, tile), 1, torch.int32, 2, torch.device(DEV),
+                                                    scene._Clock(None, DEV)):
         own = scene._tile_nodes(window, box, origin, H, W)
         if own is not None:
             assert own.dtype == torch.int64

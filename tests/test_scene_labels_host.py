@@ -222,3 +222,48 @@ def test_every_point_belongs_to_the_one_tile_whose_core_holds_it():
     xy = torch.tensor([[231, 199], [224, 192], [223, 191], [0, 192], [224, 0]], dtype=torch.int32)
     assert point_tiles(xy, 232, (96, 112)).tolist() == [8, 8, 4, 6, 2]
     assert tiles[8] == (192, 200, 224, 232)
+
+
+# ---- the grid and the seam walk ---------------------------------------------------------------------------------------------------------
+def test_the_largest_window_of_a_grid_is_the_largest_of_its_cores_windows():
+    """`max_window` looks at two tile rows and two tile columns; the brute force looks at every core, also where the halo is wider
+    than a tile and the windows keep growing past the second one."""
+    from deepmerge_amd.scene import _Grid, window_of
+    for H, W, tile in ((200, 232, (96, 112)), (9, 17, (4, 8)), (7, 9, (3, 4)), (10, 20, 4096), (64, 64, 64), (100, 1, (7, 9)), (1000, 37, (10, 5))):
+        grid = _Grid.of(H, W, tile)
+        assert (grid.H, grid.W, grid.ny * grid.nx) == (H, W, len(grid.cores)) and (grid.th, grid.tw) == (tile if isinstance(tile, tuple) else (tile, tile))
+        for halo in (0, 1, 2, 3, 4, 5, 9, 10, 11, 32, 192):
+            windows = [window_of(c, H, W, halo) for c in grid.cores]
+            assert grid.max_window(halo) == (max(w[1] - w[0] for w in windows), max(w[3] - w[2] for w in windows)), (H, W, tile, halo)
+            for i, (core, w) in enumerate(zip(grid.cores, windows)):
+                box, inner, origin = grid.window(i, halo)
+                assert box == w and origin == (w[0], w[2])
+                assert (inner[0] + w[0], inner[1] + w[0], inner[2] + w[2], inner[3] + w[2]) == core
+
+
+def test_the_seam_walk_pairs_the_facing_pixels_of_every_seam_once():
+    """7 x 9 pixels in tiles of (3, 4): a 3 x 3 grid whose last row and last column are 1 pixel wide.  Two fields, so that the
+    walk is also checked to keep the fields apart."""
+    import torch
+    from deepmerge_amd.scene import _Grid, _border, _seam_pairs
+    H, W = 7, 9
+    raster = np.random.default_rng(5).permutation(H * W).reshape(H, W).astype(np.int32)       # every pixel its own value
+    grid = _Grid.of(H, W, (3, 4))
+    assert (grid.ny, grid.nx) == (3, 3) and grid.cores[-1] == (6, 7, 8, 9)
+    t = torch.from_numpy(raster)
+    strips = [(_border(t[y0:y1, x0:x1]), _border(t[y0:y1, x0:x1] + 100)) for y0, y1, x0, x1 in grid.cores]
+    assert strips[0][0][0].data_ptr() != t.data_ptr()             # clones: a strip does not keep its tile's raster alive
+    got = _seam_pairs(strips, grid.nx, grid.ny, torch.device("cpu"))
+    assert len(got) == 2
+    xs, ys = [c[2] for c in grid.cores[1:grid.nx]], [c[0] for c in grid.cores[grid.nx::grid.nx]]
+    assert xs == [4, 8] and ys == [3, 6]
+    want = [(raster[y, x - 1], raster[y, x]) for x in xs for y in range(H)] + [(raster[y - 1, x], raster[y, x]) for y in ys for x in range(W)]
+    for field, (a, b) in enumerate(got):
+        assert a.dtype == b.dtype == torch.int32 and len(a) == len(b) == (grid.nx - 1) * H + (grid.ny - 1) * W == 32
+        pairs = sorted(zip(a.tolist(), b.tolist()))
+        assert pairs == sorted((int(p) + 100 * field, int(q) + 100 * field) for p, q in want), field
+    one = _Grid.of(H, W, 4096)
+    got = _seam_pairs([(_border(t), _border(t + 100))], one.nx, one.ny, torch.device("cpu"))
+    assert len(got) == 2
+    for a, b in got:
+        assert a.dtype == b.dtype == torch.int32 and a.numel() == b.numel() == 0
