@@ -141,6 +141,14 @@ class FeatureIO:
         return call(source, n_labels, tolerance, device=self.device, **kw)
 
     @torch.no_grad()
+    def rasterize_scene(self, rings, H: int, W: int, **kw):
+        """Polygon rings (a rag.Rings or a rag.Polygons in scene coordinates) rasterised into the scene's int32 [H, W] label raster
+        on the host, tile by tile: `scene.rasterize_rings(rings, H, W, device=self.device, **kw)`, bit for bit `rag.rasterize` of
+        the whole raster.  `scene.RingSource(rings, H, W)` hands the same pixels to the scene calls with no host raster."""
+        from . import scene
+        return scene.rasterize_rings(rings, H, W, device=self.device, **kw)
+
+    @torch.no_grad()
     def _extract_local(self, tile, points_xy, inner, obj, region_features, batch_size):
         from .patches import point_batch_cols
         P = points_xy.shape[0]

@@ -231,6 +231,9 @@ SIGNATURES = {
     "dm_rasterize_count": (_I, [_P, _P, _P, _I, _I, _I, _I, _P, _P]),
     "dm_rasterize_emit": (_I, [_P, _P, _P, _P, _P, _I, _I, _L, _I, _I, _L, _P, _P]),
     "dm_rasterize_fill": (_I, [_P, _L, _I, _I, _I, _P, _P, _P]),
+    "dm_rasterize_count_rows": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P]),
+    "dm_rasterize_emit_rows": (_I, [_P, _P, _P, _P, _P, _I, _I, _L, _I, _I, _I, _I, _L, _P, _P]),
+    "dm_rasterize_fill_window": (_I, [_P, _L, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P]),
     "dm_simplify_nodes": (_I, [_P, _I, _I, _P, _P]),
     "dm_simplify_chains": (_I, [_P, _P, _I, _L, _I, _I, _I, _P, _P, _P]),
     "dm_simplify_arc_count": (_I, [_P, _P, _I, _L, _I, _I, _P, _P, _P]),

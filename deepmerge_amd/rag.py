@@ -1445,15 +1445,8 @@ class Rings:
     ring_label: torch.Tensor
 
 
-def rasterize(rings, H: int, W: int, fill: int = -1, stats: Optional[dict] = None) -> torch.Tensor:
-    """int32 [H,W]: the label raster of polygon rings, the exact inverse of `polygons`.  rings: a `Rings` (float64 coordinates,
-    quantised to 1/256 pixel: q = floor(256 v + 0.5)) or a `Polygons` (int32 corners, multiplied by 256 with no float step).
-
-    A pixel belongs to a label iff its centre is inside that label's rings by the even-odd rule (holes need no flag), with the
-    half-open tie rules of include/deepmerge_hip.h: polygons that share an edge partition the pixels along it.  A pixel inside
-    several labels gets the greatest, a pixel inside none gets `fill` < 0.  Integer arithmetic throughout, bit-equal to
-    tests/rasterize_ref.py.  The inputs are not modified.  Readbacks: the range check, the number of events N (it sizes the keys),
-    the error flag.  stats: a dict that receives N, the time per stage and the bytes of the passes (tools/mb_rasterize.py)."""
+def _ring_tensors(rings) -> tuple:
+    """(ring_ptr, xy, ring_label, R, V) of a `Rings` or a `Polygons`, contiguous, their dtypes and shapes checked."""
     ring_ptr, xy, ring_label = rings.ring_ptr, rings.xy, rings.ring_label
     _need_cuda(ring_ptr, xy, ring_label)
     if ring_ptr.dtype != torch.int64 or ring_ptr.dim() != 1 or ring_ptr.numel() < 1:
@@ -1463,25 +1456,13 @@ def rasterize(rings, H: int, W: int, fill: int = -1, stats: Optional[dict] = Non
         raise ValueError(f"ring_label must be int32 [R] with R = {R}")
     if xy.dtype not in (torch.float64, torch.int32) or xy.dim() != 2 or xy.shape[1] != 2:
         raise ValueError("xy must be float64 [V,2] (or int32 [V,2] corners, as Polygons.xy)")
-    H, W, fill = int(H), int(W), int(fill)
-    if H < 1 or W < 1 or H * W >= 1 << 31:
-        raise ValueError(f"need H, W >= 1 and H * W < 2^31, got {H} x {W}")
-    if not -(1 << 31) <= fill < 0:
-        raise ValueError(f"fill must be a negative int32, got {fill}")
-    V = xy.shape[0]
-    if V > MAX_EVENTS:
-        raise ValueError(f"rasterize takes at most 2^30 vertices, got {V}")
-    dev, lib, i32, i64 = xy.device, _lib.lib(), torch.int32, torch.int64
-    ring_ptr, xy, ring_label = ring_ptr.contiguous(), xy.contiguous(), ring_label.contiguous()
-    marks = []
+    return ring_ptr.contiguous(), xy.contiguous(), ring_label.contiguous(), R, xy.shape[0]
 
-    def mark(stage):                                             # stage boundaries for tools/mb_rasterize.py; nothing when stats is None
-        if stats is not None:
-            e = torch.cuda.Event(enable_timing=True)
-            e.record()
-            marks.append((stage, e))
-    mark("start")
-    # the range check: one readback of (coordinates out of range or not finite, ring_ptr not 0 .. V non-decreasing, label range)
+
+def _check_ring_values(ring_ptr: torch.Tensor, xy: torch.Tensor, ring_label: torch.Tensor, R: int, V: int) -> int:
+    """The range check: one readback of (coordinates out of range or not finite, ring_ptr not 0 .. V non-decreasing, label range).
+    Returns n_labels = the largest label + 1."""
+    dev, i32, i64 = xy.device, torch.int32, torch.int64
     bad_xy = ~((xy >= -MAX_COORDINATE) & (xy <= MAX_COORDINATE))            # NaN compares false: refused
     bad_ptr = (ring_ptr[0] != 0) | (ring_ptr[-1] != V)
     if R:
@@ -1497,13 +1478,48 @@ def rasterize(rings, H: int, W: int, fill: int = -1, stats: Optional[dict] = Non
         raise ValueError("coordinates must be finite and within +-2^20 pixels")
     if lo < 0 or hi > (1 << 31) - 2:
         raise ValueError(f"ring labels must be in 0 .. 2^31 - 2, found {lo} .. {hi}")
-    n_labels = hi + 1
+    return hi + 1
+
+
+def _quantised(ring_ptr: torch.Tensor, xy: torch.Tensor, V: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(q int32 [V,2], vert_ring int32 [V]): the fixed-point coordinates and the ring of every vertex."""
+    q = torch.floor(xy * SUBPIXEL + 0.5).to(torch.int32) if xy.dtype == torch.float64 else xy * SUBPIXEL
+    vert_ring = (torch.searchsorted(ring_ptr, torch.arange(V, dtype=torch.int64, device=xy.device), right=True) - 1).to(torch.int32)
+    return q, vert_ring
+
+
+def rasterize(rings, H: int, W: int, fill: int = -1, stats: Optional[dict] = None) -> torch.Tensor:
+    """int32 [H,W]: the label raster of polygon rings, the exact inverse of `polygons`.  rings: a `Rings` (float64 coordinates,
+    quantised to 1/256 pixel: q = floor(256 v + 0.5)) or a `Polygons` (int32 corners, multiplied by 256 with no float step).
+
+    A pixel belongs to a label iff its centre is inside that label's rings by the even-odd rule (holes need no flag), with the
+    half-open tie rules of include/deepmerge_hip.h: polygons that share an edge partition the pixels along it.  A pixel inside
+    several labels gets the greatest, a pixel inside none gets `fill` < 0.  Integer arithmetic throughout, bit-equal to
+    tests/rasterize_ref.py.  The inputs are not modified.  Readbacks: the range check, the number of events N (it sizes the keys),
+    the error flag.  stats: a dict that receives N, the time per stage and the bytes of the passes (tools/mb_rasterize.py)."""
+    ring_ptr, xy, ring_label, R, V = _ring_tensors(rings)
+    H, W, fill = int(H), int(W), int(fill)
+    if H < 1 or W < 1 or H * W >= 1 << 31:
+        raise ValueError(f"need H, W >= 1 and H * W < 2^31, got {H} x {W}")
+    if not -(1 << 31) <= fill < 0:
+        raise ValueError(f"fill must be a negative int32, got {fill}")
+    if V > MAX_EVENTS:
+        raise ValueError(f"rasterize takes at most 2^30 vertices, got {V}")
+    dev, lib, i32, i64 = xy.device, _lib.lib(), torch.int32, torch.int64
+    marks = []
+
+    def mark(stage):                                             # stage boundaries for tools/mb_rasterize.py; nothing when stats is None
+        if stats is not None:
+            e = torch.cuda.Event(enable_timing=True)
+            e.record()
+            marks.append((stage, e))
+    mark("start")
+    n_labels = _check_ring_values(ring_ptr, xy, ring_label, R, V)
     if n_labels * H * (W + 1) >= 1 << 63:
         raise ValueError(f"(largest label + 1) * H * (W + 1) must be below 2^63, got {n_labels} * {H} * {W + 1}")
     N = 0
     if R and V:
-        q = torch.floor(xy * SUBPIXEL + 0.5).to(i32) if xy.dtype == torch.float64 else xy * SUBPIXEL
-        vert_ring = (torch.searchsorted(ring_ptr, torch.arange(V, dtype=i64, device=dev), right=True) - 1).to(i32)
+        q, vert_ring = _quantised(ring_ptr, xy, V)
         count = torch.empty(V, dtype=i32, device=dev)
         check(lib.dm_rasterize_count(q.data_ptr(), ring_ptr.data_ptr(), vert_ring.data_ptr(), V, R, H, W, count.data_ptr(), _stream()),
               "dm_rasterize_count")

@@ -44,6 +44,11 @@ Topology-safe simplification.  `simplify_labels_topology` is 
 scene, bit for bit: the detection and repair rounds of 3.5.12 run on the byte per stored arc vertex, over a grid whose cell side
 grows with the scene (csrc/dm_scene_simplify_topology.hip); `simplify_conflicts` lists what the plain call breaks.
 
+Polygon rings as a label source.  `RingSource` stands for `rag.rasterize` of a scene's rings without building
+the raster: a read sorts the events of its band of rows once and fills its window of columns (csrc/dm_scene_rasterize.hip), bit
+for bit the whole-raster call's pixels, for any H, W < 2^31.  It goes wherever a label or truth source goes; `rasterize_rings`
+and `labels_from_shapefile` write the host raster tile by tile.
+
 Memory.  The scene's pixels are never on the device as a whole: one halo window at a time.  What is resident for the whole scene
 is per superpixel and per sample point: the statistics, the graph, the points and the [P,100] feature rows.  The scene-wide
 label raster lives on the host (`labels_out`, a numpy array or a memmap).  Every tile is read twice: once for the graph, once
@@ -1293,3 +1298,141 @@ def slic_labels(source, tile=4096, cell: int = 29, compactness: int = 10, iters:
         stats.update(provisional=P, seam_unions=int(pairs.numel()), components=components, rounds=len(picks), picks=picks,
                      image_reads=cores.reads // len(tiles), resident=cores.resident, tiles=len(tiles), n_labels=n)
     return out, n
+
+
+# ---- polygon rings as a scene's label source (csrc/dm_scene_rasterize.hip) ----------------------------------------
+MAX_WINDOW_PIXELS = 1 << 31           # a window's raster is indexed in int32, as every raster pass here
+
+
+class RingSource:
+    """Polygon rings as the label raster of an H x W scene that is never built: `.shape == (H, W)` and `.read(y0, y1, x0, x1)`,
+    so it goes wherever a scene call takes a label or truth source (`segment_scene(labels=)`, `label_graph`, `sample_points`,
+    `trace_labels`, `simplify_labels*`, `SceneResult.overlap`).
+
+    rings: a `rag.Rings` (float64, quantised once, here) or a `rag.Polygons` (int32 corners; what `trace_labels` returns), in
+    scene coordinates.  `read` returns the int32 device tensor [y1-y0, x1-x0] that is rows y0..y1-1, columns x0..x1-1 of
+    `rag.rasterize(rings, H, W, fill)`, bit for bit, also where H W >= 2^31 and that raster cannot exist (the rule in its band
+    and window form: include/deepmerge_hip.h, tests/scene_rasterize_ref.py).  `n_labels` is the largest label + 1.
+
+    The constructor makes `rag.rasterize`'s checks with its messages (one readback) and keeps the quantised vertices on the
+    device; the inputs are not modified.  A read counts, scans, emits and sorts the events of the band of rows [y0, y1) -- all V
+    edges are visited per band -- and fills the window from the band's sorted keys; the keys of the LAST band are kept, so the
+    scene loops, which are row-major and whose windows' rows depend on the tile row only, pay one event pass per row of tiles and
+    one fill per tile.  Readbacks per read: the band's event count (a new band only) and the error flag.
+    Limits, each a ValueError: coordinates within +-2^20 pixels; H, W < 2^31; a window below 2^31 pixels; at most 2^30 events per
+    band; (largest label + 1) (y1 - y0) (W + 1) < 2^63.  Rings that are not closed in a band raise RuntimeError for every box of
+    that band."""
+
+    def __init__(self, rings, H: int, W: int, fill: int = -1, device="cuda:0"):
+        dev = torch.device(device)
+        moved = rag.Rings(rings.ring_ptr.to(dev), rings.xy.to(dev), rings.ring_label.to(dev))
+        self.ring_ptr, xy, self.ring_label, self.R, self.V = rag._ring_tensors(moved)
+        H, W, fill = int(H), int(W), int(fill)
+        if H < 1 or W < 1 or H >= 1 << 31 or W >= 1 << 31:
+            raise ValueError(f"need 1 <= H, W < 2^31, got {H} x {W}")
+        if not -(1 << 31) <= fill < 0:
+            raise ValueError(f"fill must be a negative int32, got {fill}")
+        if self.V > rag.MAX_EVENTS:
+            raise ValueError(f"rasterize takes at most 2^30 vertices, got {self.V}")
+        self.n_labels = rag._check_ring_values(self.ring_ptr, xy, self.ring_label, self.R, self.V)
+        self.shape, self.fill, self.device = (H, W), fill, dev
+        self.q, self.vert_ring = rag._quantised(self.ring_ptr, xy, self.V) if self.R and self.V else (None, None)
+        self._band, self._keys = None, None
+        self.events: Dict[Tuple[int, int], int] = {}             # band -> its event count, for every band passed so far
+        self.clock = _Clock(None, dev)                           # `rasterize_rings(stats=)` puts its own here
+
+    def _event_pass(self, y0: int, y1: int) -> Optional[torch.Tensor]:
+        """The sorted keys of the band [y0, y1), None when it has no event."""
+        H, W = self.shape
+        if self.n_labels * (y1 - y0) * (W + 1) >= 1 << 63:
+            raise ValueError(f"(largest label + 1) * rows * (W + 1) must be below 2^63, got {self.n_labels} * {y1 - y0} * {W + 1}")
+        N = 0
+        if self.q is not None:
+            lib, V, R = _lib.lib(), self.V, self.R
+            count = torch.empty(V, dtype=torch.int32, device=self.device)
+            check(lib.dm_rasterize_count_rows(self.q.data_ptr(), self.ring_ptr.data_ptr(), self.vert_ring.data_ptr(), V, R, H, W, y0, y1,
+                                              count.data_ptr(), _stream()), "dm_rasterize_count_rows")
+            scan = torch.zeros(V + 1, dtype=torch.int64, device=self.device)
+            torch.cumsum(count, 0, dtype=torch.int64, out=scan[1:])
+            N = int(scan[-1])
+            self.clock.lap("count + scan")
+        self.events[(y0, y1)] = N
+        if N > rag.MAX_EVENTS:
+            raise ValueError(f"the rings cross {N} pixel-row centres in rows {y0}..{y1 - 1}; a band takes at most 2^30: use a lower tile")
+        if N == 0:
+            return None
+        keys = torch.empty(N, dtype=torch.int64, device=self.device)
+        check(lib.dm_rasterize_emit_rows(self.q.data_ptr(), self.ring_ptr.data_ptr(), self.vert_ring.data_ptr(), self.ring_label.data_ptr(),
+                                         scan.data_ptr(), V, R, N, H, W, y0, y1, self.n_labels, keys.data_ptr(), _stream()),
+              "dm_rasterize_emit_rows")
+        self.clock.lap("emit")
+        keys = torch.sort(keys).values
+        self.clock.lap("sort")
+        return keys
+
+    def read(self, y0: int, y1: int, x0: int, x1: int) -> torch.Tensor:
+        H, W = self.shape
+        y0, y1, x0, x1 = int(y0), int(y1), int(x0), int(x1)
+        if not (0 <= y0 < y1 <= H and 0 <= x0 < x1 <= W):
+            raise ValueError(f"the box must lie inside the scene: rows {y0}..{y1}, columns {x0}..{x1} of {H} x {W}")
+        if (y1 - y0) * (x1 - x0) >= MAX_WINDOW_PIXELS:
+            raise ValueError(f"a window must have fewer than 2^31 pixels, got {y1 - y0} x {x1 - x0}")
+        with torch.cuda.device(self.device):
+            if self._band != (y0, y1):
+                self._band, self._keys = None, None              # (a pass that raises leaves no band behind)
+                self._keys = self._event_pass(y0, y1)
+                self._band = (y0, y1)
+            if self._keys is None:
+                return torch.full((y1 - y0, x1 - x0), self.fill, dtype=torch.int32, device=self.device)
+            out = torch.empty((y1 - y0, x1 - x0), dtype=torch.int32, device=self.device)
+            error = torch.empty(1, dtype=torch.int32, device=self.device)
+            check(_lib.lib().dm_rasterize_fill_window(self._keys.data_ptr(), int(self._keys.numel()), H, W, y0, y1, x0, x1, self.fill,
+                                                      out.data_ptr(), error.data_ptr(), _stream()), "dm_rasterize_fill_window")
+            if int(error):
+                raise RuntimeError(f"rasterize: a pair of sorted events of rows {y0}..{y1 - 1} disagrees in (label, row): the rings are "
+                                   f"not closed (an odd number of crossings in a row)")
+            self.clock.lap("pre-set + fill")
+        return out
+
+
+def rasterize_rings(rings, H: int, W: int, tile=4096, fill: int = -1, labels_out=None, stats: Optional[dict] = None,
+                    device="cuda:0") -> np.ndarray:
+    """`rag.rasterize(rings, H, W, fill)` of a scene on the host, tile by tile: int32 [H,W], equal to the whole-raster call bit for
+    bit, whatever the tile size, and defined for H W >= 2^31 too.  rings: a `rag.Rings` or a `rag.Polygons` (or a `RingSource` of
+    H x W, whose own fill and device then hold); tile: an int or
+    (th, tw), a tile below 2^31 pixels; labels_out: a writable int32 [H,W] array or memmap, allocated if None; stats: receives the
+    seconds per stage (synchronises at stage boundaries), `events` (band -> event count) and `tiles`.  One event pass per row of
+    tiles, one fill per tile (`RingSource`); limits and errors as there."""
+    source = rings if isinstance(rings, RingSource) else RingSource(rings, H, W, fill, device)
+    if source.shape != (int(H), int(W)):
+        raise ValueError(f"the source has {source.shape[0]} x {source.shape[1]} pixels, not {H} x {W}")
+    H, W = source.shape
+    grid = _Grid.of(H, W, tile)
+    side_y, side_x = grid.max_window(0)
+    if side_y * side_x >= MAX_WINDOW_PIXELS:
+        raise ValueError(f"a tile must have fewer than 2^31 pixels, got {side_y} x {side_x}")
+    out = _out_raster(labels_out, H, W, "labels_out")
+    before, source.clock = source.clock, _Clock(stats, source.device)
+    try:
+        for y0, y1, x0, x1 in grid.cores:
+            out[y0:y1, x0:x1] = source.read(y0, y1, x0, x1).cpu().numpy()
+            source.clock.lap("copy + write")
+    finally:
+        source.clock = before
+    if stats is not None:
+        stats.update(events=dict(source.events), tiles=len(grid), vertices=source.V, rings=source.R)
+    return out
+
+
+def labels_from_shapefile(path: str, H: int, W: int, geotransform=None, label_field: Optional[str] = None, fill: int = -1, tile=4096,
+                          labels_out=None, device="cuda:0", as_source: bool = False):
+    """`rag.labels_from_shapefile` on a scene: (labels int32 [H,W] on the host, n_labels) from a polygon shapefile, through
+    `shpstore._read_rings` and `rasterize_rings`.  Record i is label i (n_labels = the record count), or the value of the integer
+    field `label_field` (n_labels = the largest + 1); geotransform: the six GDAL terms of the scene (None: X = x, Y = -y).
+    as_source=True: no host raster; the `RingSource` stands in its place, (source, n_labels), for the scene calls to read."""
+    from . import shpstore
+    ring_ptr, xy, ring_label, n_labels = shpstore._read_rings(path, geotransform, label_field)
+    source = RingSource(rag.Rings(*(torch.from_numpy(a) for a in (ring_ptr, xy, ring_label))), H, W, fill, device)
+    if as_source:
+        return source, n_labels
+    return rasterize_rings(source, H, W, tile=tile, labels_out=labels_out), n_labels

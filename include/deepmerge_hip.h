@@ -951,6 +951,32 @@ int dm_rasterize_emit(const int32_t *xy, const int64_t *ring_ptr, const int32_t 
                       int32_t V, int32_t R, int64_t N, int32_t H, int32_t W, int64_t n_labels, int64_t *keys, void *stream);
 int dm_rasterize_fill(const int64_t *keys, int64_t N, int32_t H, int32_t W, int32_t fill, int32_t *out, int32_t *error, void *stream);
 
+/* ---- the same rule on a scene: a band of rows, a window of columns (additive in ABI 7; csrc/dm_scene_rasterize.hip, DESIGN.md
+ * 3.5.16, scene.RingSource / scene.rasterize_rings; restated in numpy in tests/scene_rasterize_ref.py) ----------------------------
+ * H x W is the SCENE, H, W < 2^31, and H W may be 2^31 or more: no raster of it is ever built.  The rule above is unchanged; what
+ * changes is which rows an event pass covers and which columns a fill writes.
+ *   band: the pixel rows [r0, r1), 0 <= r0 < r1 <= H.  An edge has an event in row r of the band iff r0 <= r < r1 and
+ *     y0 <= 256 r + 128 < y1 (half-open at the band's first and last row as everywhere); cx as above, clamped to [0, W] SCENE-wide.
+ *   key: (label (r1 - r0) + (r - r0)) (W + 1) + cx, with n_labels (r1 - r0) (W + 1) < 2^63; at most 2^30 events per band.  It does
+ *     not depend on any window: one sort of a band's keys serves every window of that band.
+ *   window: the columns [x0, x1), 0 <= x0 < x1 <= W, (r1 - r0) (x1 - x0) < 2^31.  out int32 [r1 - r0, x1 - x0] is pre-set to fill
+ *     < 0, then every pair (2j, 2j+1) of the sorted keys writes max(label) over the columns [cx of 2j, cx of 2j+1) that lie in
+ *     [x0, x1), at (r - r0, c - x0).  A crossing left of the window is clamped to no less than 0 <= x0, so it still opens a span that
+ *     reaches into the window: the parity inside the window is the scene's.  Hence out equals rows [r0, r1), columns [x0, x1) of
+ *     the whole raster wherever that exists, and always equals the rule applied to the rings translated by (-256 x0, -256 r0) on a
+ *     raster (r1 - r0) x (x1 - x0): translation by whole pixels is exact in every formula above.
+ *   error[0] = 1 iff ANY pair of the band disagrees in (label, row), has a negative key or a label above 2^31 - 2, whether or not its
+ *     span meets the window (cleared by the call).
+ * dm_rasterize_count_rows / dm_rasterize_emit_rows: dm_rasterize_count / _emit on the band; the other arguments as there.
+ * dm_rasterize_fill_window: keys int64 [N] SORTED keys of the band [r0, r1), N even (N = 0: keys may be NULL). */
+int dm_rasterize_count_rows(const int32_t *xy, const int64_t *ring_ptr, const int32_t *vert_ring, int32_t V, int32_t R, int32_t H, int32_t W,
+                            int32_t r0, int32_t r1, int32_t *count, void *stream);
+int dm_rasterize_emit_rows(const int32_t *xy, const int64_t *ring_ptr, const int32_t *vert_ring, const int32_t *ring_label,
+                           const int64_t *scan, int32_t V, int32_t R, int64_t N, int32_t H, int32_t W, int32_t r0, int32_t r1,
+                           int64_t n_labels, int64_t *keys, void *stream);
+int dm_rasterize_fill_window(const int64_t *keys, int64_t N, int32_t H, int32_t W, int32_t r0, int32_t r1, int32_t x0, int32_t x1,
+                             int32_t fill, int32_t *out, int32_t *error, void *stream);
+
 /* ---- shared-boundary Douglas-Peucker on the traced rings and arcs (additive in ABI 6; csrc/dm_simplify.hip, DESIGN.md 3.5.7,
  * rag.simplify) ----------------------------------------------------------------------------------------------------------------
  * The tracing above leaves a pixel staircase.  Simplified per polygon, two neighbours would treat their common boundary
