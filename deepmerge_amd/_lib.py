@@ -209,6 +209,8 @@ SIGNATURES = {
     "dm_label_overlap": (_I, [_P, _P, _I, _I, _L, _L, _P, _P, _I, _P, _P, _I, _P, _P, _P]),
     "dm_overlap_reduce": (_I, [_P, _P, _I, _L, _L, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "dm_pair_flags": (_I, [_P, _I, _P, _P, _P, _I, _I, _P, _P]),
+    "dm_boundary_bits": (_I, [_P, _I, _I, _I, _P, _P, _P, _P]),
+    "dm_boundary_counts": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P]),
     "dm_slic_iterate": (_I, [_P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P]),
     "dm_connected_labels": (_I, [_P, _I, _I, _I, _I, _P, _P, _P, _P, _P]),
     "dm_label_area": (_I, [_P, _I, _I, _I, _P, _P]),

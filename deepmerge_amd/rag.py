@@ -8,6 +8,8 @@ The sample points, their `inner` / `object` window fields and point lists, which
 come from the label raster as well (csrc/dm_points.hip: `clearance`, `sample_points`; spec tests/points_ref.py).
 Against a ground-truth raster, `label_overlap` counts the overlap table once; `pair_flags` labels the RAG edges for training and
 `Overlap.coarsen(...).scores()` scores any merged partition (csrc/dm_truth.hip; spec tests/truth_ref.py).
+`boundary_scores` adds what region scores hide: boundary recall, precision and F at a pixel tolerance, from one bit per pixel
+(csrc/dm_boundary.hip; spec tests/boundary_ref.py).
 `polygons` and `boundary_arcs` trace a label raster into closed rings and boundary arcs, the geometry of the reference's polygon
 layer and `lines.shp` (csrc/dm_vector.hip; spec tests/vector_ref.py); deepmerge_amd/shpstore.py writes them as shapefiles.
 `rasterize` is the way back, for any polygon: rings to a label raster (csrc/dm_rasterize.hip; spec tests/rasterize_ref.py), and
@@ -258,6 +260,30 @@ class MergeResult:
         """The partition scored against a ground-truth map: `overlap` = label_overlap(superpixel raster, truth, S0, G), coarsened by
         the final map (round None) or the map after `round` rounds.  No pass over the raster."""
         return overlap.coarsen(self.region_of if round is None else self.region_of_at(round)).scores()
+
+    def boundary_scores(self, raster: torch.Tensor, truth: torch.Tensor, n_truth: int, tolerance: int = 2,
+                        rounds=None) -> List["BoundaryScores"]:
+        """One BoundaryScores per round of `rounds` (default 0..self.rounds, every round `region_of_at` accepts): the partition
+        after that round scored against the truth raster, the curve to pick a round or a margin from, next to `scores`.  raster:
+        the superpixel raster the merge started from.  The truth's bits are made once; every round is one pass over `raster` with
+        mapping = region_of_at(r), no relabelled raster is built; one readback (the counts of all rounds)."""
+        _need_cuda(raster, truth)
+        S0 = self.region_of.numel()
+        _check_boundary_raster(raster, S0, "raster")
+        _check_boundary_raster(truth, n_truth, "truth")
+        if raster.shape != truth.shape:
+            raise ValueError("raster and truth must cover the same raster")
+        (d,), _ = _tolerances([tolerance])
+        rounds = list(range(self.rounds + 1)) if rounds is None else [int(r) for r in rounds]
+        maps = [self.region_of_at(r).contiguous() for r in rounds]           # (raises for a round outside 0..self.rounds)
+        H, W = raster.shape
+        raster = raster.contiguous()
+        truth_edge, truth_valid = boundary_bits(truth.contiguous(), n_truth, valid=True)
+        counts = torch.zeros((len(rounds), 4), dtype=torch.int64, device=raster.device)
+        for i, mapping in enumerate(maps):
+            label_edge, _ = boundary_bits(raster, S0, mapping)
+            boundary_counts(label_edge, truth_edge, truth_valid, H, W, [d], (0, H, 0, W), counts[i:i + 1])
+        return [boundary_scores_of(d, c) for c in counts.tolist()]
 
 
 def relabel_raster(raster: torch.Tensor, mapping: torch.Tensor) -> torch.Tensor:
@@ -843,6 +869,127 @@ def pair_flags(edges: torch.Tensor, overlap: Overlap, min_purity: float = 0.6) -
                                    overlap.owner_count.data_ptr(), min(overlap.n_labels, (1 << 31) - 1), int(round(float(min_purity) * 1000)),
                                    flags.data_ptr() if E else None, _stream()), "dm_pair_flags")
     return flags
+
+
+# ---- boundary recall / precision / F against a ground-truth raster (csrc/dm_boundary.hip; the rule: include/deepmerge_hip.h,
+# DESIGN.md 3.5.17) ----
+MAX_TOLERANCE = 64                    # DM_BOUNDARY_MAX_TOLERANCE: a dilation reaches the neighbouring 64-pixel word only
+
+
+@dataclass
+class BoundaryScores:
+    """A partition's boundaries scored against a ground-truth map's at a tolerance of `tolerance` pixels (Chebyshev distance).
+
+    The four exact integers: n_truth_b = the truth's boundary pixels, hit_truth = those with a boundary pixel of the partition
+    within the tolerance, n_label_b = the partition's boundary pixels that lie on a labelled truth pixel or within the tolerance
+    of a truth boundary, hit_label = those within the tolerance of a truth boundary.  A boundary pixel is one whose right or
+    lower neighbour has another id (one pixel thick; the raster's frame is none).  Derived: recall = hit_truth / n_truth_b,
+    precision = hit_label / n_label_b, f = 2 P R / (P + R); NaN where a figure has a zero denominator."""
+    tolerance: int
+    n_truth_b: int
+    hit_truth: int
+    n_label_b: int
+    hit_label: int
+    recall: float
+    precision: float
+    f: float
+
+
+def boundary_scores_of(tolerance: int, counts) -> BoundaryScores:
+    """BoundaryScores from the four count integers (Python integer arithmetic until the final divisions)."""
+    n_t, h_t, n_l, h_l = (int(v) for v in counts)
+    nan = float("nan")
+    r = h_t / n_t if n_t else nan
+    p = h_l / n_l if n_l else nan
+    f = 2 * p * r / (p + r) if p + r > 0 else nan                # (a NaN operand compares false: f is NaN then)
+    return BoundaryScores(int(tolerance), n_t, h_t, n_l, h_l, r, p, f)
+
+
+def _tolerances(tolerance) -> Tuple[List[int], bool]:
+    """(the tolerances as a list, whether a single one was given); each an integer in 0..MAX_TOLERANCE."""
+    single = not isinstance(tolerance, (list, tuple))
+    ds = [tolerance] if single else list(tolerance)
+    for d in ds:
+        if isinstance(d, bool) or not isinstance(d, int) or not 0 <= d <= MAX_TOLERANCE:
+            raise ValueError(f"tolerance must be an integer in 0..{MAX_TOLERANCE} (or a sequence of them), got {d!r}")
+    if not ds:
+        raise ValueError("tolerance must not be an empty sequence")
+    return ds, single
+
+
+def _check_boundary_raster(raster: torch.Tensor, n_ids: int, name: str):
+    if raster.dtype != torch.int32 or raster.dim() != 2 or raster.numel() < 1:
+        raise ValueError(f"{name} must be int32 [H,W] with at least one pixel")
+    if raster.numel() >= 1 << 31:
+        raise ValueError(f"boundary_scores takes rasters of fewer than 2^31 pixels, got {raster.numel()}")
+    if not 1 <= int(n_ids) < 1 << 31:
+        raise ValueError(f"the number of ids of {name} must be in 1..2^31-1, got {n_ids}")
+
+
+def _check_mapping(mapping: Optional[torch.Tensor], n_labels: int):
+    if mapping is not None and (mapping.dtype != torch.int32 or tuple(mapping.shape) != (int(n_labels),)):
+        raise ValueError(f"mapping must be int32 [{int(n_labels)}]")
+
+
+def boundary_bits(raster: torch.Tensor, n_ids: int, mapping: Optional[torch.Tensor] = None, valid: bool = False):
+    """(edge, valid or None): one bit per pixel of an int32 raster [H,W], int64 [H, ceil(W/64)] words, bit x % 64 of word
+    (y, x // 64).  edge: the pixel's right or lower neighbour exists and has another canonical value (the id, or mapping[id],
+    inside [0, n_ids), -1 otherwise); valid: the canonical value is >= 0.  One read of the raster (dm_boundary_bits)."""
+    H, W = raster.shape
+    WW = (W + 63) // 64
+    edge = torch.empty((H, WW), dtype=torch.int64, device=raster.device)
+    ok = torch.empty((H, WW), dtype=torch.int64, device=raster.device) if valid else None
+    check(_lib.lib().dm_boundary_bits(raster.data_ptr(), H, W, int(n_ids), mapping.data_ptr() if mapping is not None else None,
+                                      edge.data_ptr(), ok.data_ptr() if valid else None, _stream()), "dm_boundary_bits")
+    return edge, ok
+
+
+def boundary_counts(label_edge: torch.Tensor, truth_edge: torch.Tensor, truth_valid: torch.Tensor, H: int, W: int, tolerances,
+                    box, counts: torch.Tensor):
+    """counts int64 [T,4] += the four counts of `box` = (y0, y1, x0, x1) at every tolerance, from the bit planes of an H x W
+    raster pair: one dm_boundary_counts launch per tolerance, no readback."""
+    for t, d in enumerate(tolerances):
+        check(_lib.lib().dm_boundary_counts(label_edge.data_ptr(), truth_edge.data_ptr(), truth_valid.data_ptr(), H, W, int(d),
+                                            *(int(v) for v in box), counts[t].data_ptr(), _stream()), "dm_boundary_counts")
+
+
+def _check_box(box, H: int, W: int):
+    if box is None:
+        return 0, H, 0, W
+    y0, y1, x0, x1 = (int(v) for v in box)
+    if not (0 <= y0 < y1 <= H and 0 <= x0 < x1 <= W):
+        raise ValueError(f"box = (y0, y1, x0, x1) must be a non-empty box inside the raster, got {tuple(box)} of {H} x {W}")
+    return y0, y1, x0, x1
+
+
+def boundary_scores(labels: torch.Tensor, truth: torch.Tensor, n_labels: int, n_truth: int, tolerance=2,
+                    mapping: Optional[torch.Tensor] = None, box=None):
+    """Boundary recall, precision and F of a label raster (region ids 0..n_labels-1) against a ground-truth raster (object ids
+    0..n_truth-1, any other value = unlabelled) at a tolerance of `tolerance` pixels, 0..64 (the rule: include/deepmerge_hip.h).
+
+    tolerance: an integer -> a BoundaryScores; a list or tuple -> a list of them (the bits of both rasters are made once, one
+    count pass per tolerance).  mapping int32 [n_labels]: scores the partition mapping[labels] -- the `region_of` or
+    `region_of_at(r)` of a MergeResult -- without building its raster (a negative entry means "no region").  box = (y0, y1, x0,
+    x1): count the boundary pixels inside the box only; what they match may lie anywhere in the raster.  One read of each raster;
+    one readback (the counts).  The inputs are not modified."""
+    _need_cuda(labels, truth)
+    _check_boundary_raster(labels, n_labels, "labels")
+    _check_boundary_raster(truth, n_truth, "truth")
+    if labels.shape != truth.shape:
+        raise ValueError("labels and truth must cover the same raster")
+    _check_mapping(mapping, n_labels)
+    if mapping is not None:
+        _need_cuda(mapping)
+        mapping = mapping.contiguous()
+    ds, single = _tolerances(tolerance)
+    H, W = labels.shape
+    box = _check_box(box, H, W)
+    label_edge, _ = boundary_bits(labels.contiguous(), n_labels, mapping)
+    truth_edge, truth_valid = boundary_bits(truth.contiguous(), n_truth, valid=True)
+    counts = torch.zeros((len(ds), 4), dtype=torch.int64, device=labels.device)
+    boundary_counts(label_edge, truth_edge, truth_valid, H, W, ds, box, counts)
+    out = [boundary_scores_of(d, c) for d, c in zip(ds, counts.tolist())]         # the one readback
+    return out[0] if single else out
 
 
 # ---- SLIC superpixels and 4-connected components (csrc/dm_slic.hip; the rule: include/deepmerge_hip.h, DESIGN.md 3.5.4) ---------

@@ -49,6 +49,10 @@ the raster: a read sorts the events of its band of rows once and fills its windo
 for bit the whole-raster call's pixels, for any H, W < 2^31.  It goes wherever a label or truth source goes; `rasterize_rings`
 and `labels_from_shapefile` write the host raster tile by tile.
 
+Boundary scores.  `boundary_scores` is `rag.boundary_scores` on a scene: every core read with a halo of the
+tolerance plus one pixel, the counts taken on the core and added over the cores, equal to the whole-raster call's whatever the
+tile size (csrc/dm_boundary.hip).  `SceneResult.boundary_scores` scores the scene's merged partition, or a round of it.
+
 Memory.  The scene's pixels are never on the device as a whole: one halo window at a time.  What is resident for the whole scene
 is per superpixel and per sample point: the statistics, the graph, the points and the [P,100] feature rows.  The scene-wide
 label raster lives on the host (`labels_out`, a numpy array or a memmap).  Every tile is read twice: once for the graph, once
@@ -449,6 +453,14 @@ class SceneResult:
         uniq, inverse = torch.unique(torch.cat(keys + [empty]), return_inverse=True)           # sorted
         folded = torch.zeros(uniq.numel(), dtype=torch.int32, device=dev).index_add_(0, inverse, torch.cat(counts + [empty.to(torch.int32)]))
         return rag._overlap_facts(uniq, folded, self.n_labels, G)
+
+    def boundary_scores(self, truth_source, n_truth: int, tolerance=2, round: Optional[int] = None):
+        """The boundaries of the scene's merged partition (round None), or of the partition after `round` rounds, scored against
+        a ground-truth source at `tolerance` pixels: `boundary_scores` of the superpixel raster with mapping = `result.region_of`
+        or `result.region_of_at(round)`, on the scene's own tile.  Equals `MergeResult.boundary_scores` on the assembled rasters."""
+        mapping = self.result.region_of if round is None else self.result.region_of_at(round)
+        return boundary_scores(self.labels, truth_source, self.n_labels, n_truth, tolerance=tolerance, tile=self._tile(),
+                               mapping=mapping, device=self.edges.device)
 
 
 def segment_scene(fio, source, tile=4096, segmenter: Optional[Callable] = None, k: int = 3, margin: float = 1.0,
@@ -1436,3 +1448,50 @@ def labels_from_shapefile(path: str, H: int, W: int, geotransform=None, label_fi
     if as_source:
         return source, n_labels
     return rasterize_rings(source, H, W, tile=tile, labels_out=labels_out), n_labels
+
+
+# ---- boundary recall / precision / F of a scene (csrc/dm_boundary.hip) ---------------------------------------------
+def boundary_scores(labels_source, truth_source, n_labels: int, n_truth: int, tolerance=2, tile=4096,
+                    mapping: Optional[torch.Tensor] = None, device="cuda:0", stage_times: Optional[dict] = None):
+    """`rag.boundary_scores` on a scene: the four counts, and so every figure, equal the whole-raster call's on the assembled
+    rasters, whatever the tile size (the rule: include/deepmerge_hip.h).
+
+    labels_source, truth_source: int32 [H,W] on the host -- an array, an `np.memmap`, a CPU tensor, or anything with `.shape ==
+    (H, W)` and `.read(y0, y1, x0, x1) -> int32 [y1-y0, x1-x0]`, a `RingSource` included: a truth `polygons.shp` is scored with no
+    host raster.  tolerance: an integer, or a list or tuple of them (a list is returned); mapping int32 [n_labels] on the device:
+    as in `rag.boundary_scores`.  Every core is read with a halo of max(tolerance) + 1 pixels: the tolerance for the match, and
+    one more so that every pixel within the tolerance of the core has its right and lower neighbour in the window; the bits of
+    both windows are made once, the counts are taken on the core's box for every tolerance and added over the cores on the
+    device.  One readback (the counts).  Limits, each a ValueError before any device work: H, W < 2^31; tolerance in 0..64; every
+    window below 2^31 pixels."""
+    labels_source, truth_source = _as_source(labels_source), _as_source(truth_source)
+    H, W = _label_shape(labels_source, "labels_source")
+    if _label_shape(truth_source, "truth_source") != (H, W):
+        raise ValueError(f"truth_source must cover the scene: its shape is {tuple(truth_source.shape)}, the labels have {H} x {W} pixels")
+    if H > MAX_SCENE_SIDE or W > MAX_SCENE_SIDE:
+        raise ValueError(f"the scene must have H, W < 2^31, got {H} x {W}")
+    if not 1 <= int(n_labels) < 1 << 31 or not 1 <= int(n_truth) < 1 << 31:
+        raise ValueError(f"n_labels and n_truth must be in 1..2^31-1, got {n_labels}, {n_truth}")
+    ds, single = rag._tolerances(tolerance)
+    rag._check_mapping(mapping, n_labels)
+    grid, halo = _Grid.of(H, W, tile), max(ds) + 1
+    side_y, side_x = grid.max_window(halo)
+    if side_y * side_x >= MAX_WINDOW_PIXELS:
+        raise ValueError(f"a tile's window (core + halo of {halo}) must have fewer than 2^31 pixels, got {side_y} x {side_x}")
+    dev, i32 = torch.device(device), torch.int32
+    if mapping is not None:
+        mapping = mapping.to(dev).contiguous()
+    clock = _Clock(stage_times, dev)
+    counts = torch.zeros((len(ds), 4), dtype=torch.int64, device=dev)
+    with torch.cuda.device(dev):
+        for (_, _, lab, box, _), (_, _, tru, _, _) in zip(_windows(labels_source, grid, halo, i32, 2, dev, clock),
+                                                          _windows(truth_source, grid, halo, i32, 2, dev, clock)):
+            wh, ww = lab.shape
+            label_edge, _ = rag.boundary_bits(lab.contiguous(), n_labels, mapping)
+            truth_edge, truth_valid = rag.boundary_bits(tru.contiguous(), n_truth, valid=True)
+            clock.lap("bits")
+            rag.boundary_counts(label_edge, truth_edge, truth_valid, wh, ww, ds, box, counts)
+            clock.lap("counts")
+        out = [rag.boundary_scores_of(d, c) for d, c in zip(ds, counts.tolist())]     # the one readback
+    clock.lap("readback")
+    return out[0] if single else out

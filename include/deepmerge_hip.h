@@ -699,6 +699,35 @@ int dm_overlap_reduce(const int64_t *cell_keys, const int32_t *cell_counts, int3
 int dm_pair_flags(const int32_t *edges, int32_t E, const int64_t *area, const int32_t *owner, const int32_t *owner_count, int32_t S,
                   int32_t purity_pm, int8_t *flags, void *stream);
 
+/* ---- boundary recall / precision of a label raster against a ground-truth raster at a pixel tolerance (additive in ABI 7;
+ * csrc/dm_boundary.hip, DESIGN.md 3.5.17, rag.boundary_scores / MergeResult.boundary_scores / scene.boundary_scores) ------------
+ * The region scores above say how well regions and objects overlap; these say where the partition's boundaries lie.  The rule is
+ * this build's (restated in numpy in tests/boundary_ref.py).  All arithmetic is on integers; results are bit-exact.
+ * The rule.  labels int32 [H,W]: region ids 0..S-1; truth int32 [H,W]: object ids 0..G-1; mapping (optional) int32 [S];
+ * tolerance 0 <= d <= 64; H*W < 2^31.
+ *   1. canonical value: v_L(p) = labels(p), or mapping[labels(p)] with a mapping, if 0 <= labels(p) < S, else -1 (a negative
+ *      mapping entry is -1 as well); v_T(p) = truth(p) if 0 <= truth(p) < G, else -1 = unlabelled.  Two different out-of-range
+ *      ids are therefore the same value.
+ *   2. boundary pixel: b(p) = 1 iff the right neighbour (y, x+1) lies inside the raster and has another canonical value, or the
+ *      lower neighbour (y+1, x) does.  The raster's frame is no boundary, and boundaries are one pixel thick (the 8-neighbour,
+ *      frame-included bits of the clearance rule above are another rule: a two-pixel boundary would match itself at d = 0).
+ *   3. match: m_X(p) = 1 iff some pixel q of the raster has b_X(q) = 1 and max(|dy|, |dx|) <= d.
+ *   4. four counts over the pixels p of a box [y0,y1) x [x0,x1) (q may lie anywhere in the raster):
+ *      n_truth_b = #{b_T(p)}, hit_truth = #{b_T(p) and m_L(p)}, n_label_b = #{b_L(p) and (v_T(p) >= 0 or m_T(p))},
+ *      hit_label = #{b_L(p) and m_T(p)}: an unmatched region boundary in unlabelled territory is not held against the partition.
+ *   recall = hit_truth / n_truth_b, precision = hit_label / n_label_b and F are the caller's.  Counts of disjoint boxes add.
+ * Every entry point validates before any launch, launches on `stream`, never synchronises and never allocates.
+ *
+ * dm_boundary_bits: one read of a raster [H,W] with ids 0..n_ids-1 (mapping: int32 [n_ids] or NULL): edge uint64 [H * ceil(W/64)],
+ *   bit x % 64 of word y * ceil(W/64) + x / 64 = b(y, x), bits behind x = W - 1 zero; valid (or NULL): the same layout, v >= 0.
+ * dm_boundary_counts: counts int64 [4] += (n_truth_b, hit_truth, n_label_b, hit_label) of the box at tolerance d, from the bits
+ *   of the labels and of the truth (zero counts before the first call; several boxes or tiles may add into the same four). */
+#define DM_BOUNDARY_MAX_TOLERANCE 64
+int dm_boundary_bits(const int32_t *raster, int32_t H, int32_t W, int32_t n_ids, const int32_t *mapping, uint64_t *edge,
+                     uint64_t *valid, void *stream);
+int dm_boundary_counts(const uint64_t *label_edge, const uint64_t *truth_edge, const uint64_t *truth_valid, int32_t H, int32_t W,
+                       int32_t d, int32_t y0, int32_t y1, int32_t x0, int32_t x1, int64_t *counts, void *stream);
+
 /* ---- SLIC superpixels from an image tile, 4-connected component labelling (additive in ABI 6; csrc/dm_slic.hip, DESIGN.md 3.5.4,
  * rag.slic / rag.connected_labels) ------------------------------------------------------------------------------------------------
  * Produces, on the device, the over-segmentation the reference reads from shapefiles written by external GIS software.  The
