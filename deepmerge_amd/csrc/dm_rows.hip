@@ -41,11 +41,13 @@ __device__ __forceinline__ f32x4 dm_widen4(bf16x4 v) { return (f32x4){(float)v[0
 // products: no fp32 y, no split pass).
 // CH = float4 chunks per lane per row (cols <= 256 CH); FULL: cols == 256 CH, every lane live in every chunk -- no lane predicate, so
 // no skip branches in the row loop and the waits in it are counted exactly (the encoder's 768 columns: CH = 3).
-template <typename TY, bool PAIR, int CH, bool FULL>
+// POOL (stage transition, dm_pool_layernorm_fwd): row r is the 2 x 2 token mean of four rows of x (token_pool_fwd_kernel's arithmetic),
+// formed in registers and also left in `pooled` for the backward pass; x is then the [.., side, side, cols] cube and rows counts pooled rows.
+template <typename TY, bool PAIR, int CH, bool FULL, bool POOL = false>
 __global__ __launch_bounds__(256) void layernorm_fwd_kernel(const float *__restrict__ x, const float *__restrict__ gamma,
                                                             const float *__restrict__ beta, TY *__restrict__ y,
                                                             float *__restrict__ mean_out, float *__restrict__ rstd_out,
-                                                            int rows, int cols, float eps) {
+                                                            int rows, int cols, float eps, float *__restrict__ pooled = nullptr, int pool_side = 0) {
   // gamma and beta wait in LDS: read from there they count on the LDS counter, and a wait for them cannot drain the next row's loads
   __shared__ f32x4 gb[2][CH * 64];
   const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);      // the row index stays scalar: branches on it are jumps
@@ -59,6 +61,24 @@ __global__ __launch_bounds__(256) void layernorm_fwd_kernel(const float *__restr
   int row = blockIdx.x * 4 + wave;
   if (row >= rows) return;
   auto request = [&](int r, f32x4(&dst)[CH]) __attribute__((always_inline)) {
+    if constexpr (POOL) {
+      const int half = pool_side >> 1, px = r % half, q = r / half, py = q % half, bs = q / half;      // (scalar: r is wave-uniform)
+      const float *src = x + (((long long)bs * pool_side + 2 * py) * pool_side + 2 * px) * cols;
+      const long long down = (long long)pool_side * cols;
+      float *pr = pooled + (long long)r * cols;
+#pragma unroll
+      for (int i = 0; i < CH; ++i) {
+        const int c = lane + 64 * i;
+        if (FULL || c < nch) {
+          const f32x4 a = dm_load4(src + 4 * c), b = dm_load4(src + cols + 4 * c), d = dm_load4(src + down + 4 * c), e = dm_load4(src + down + cols + 4 * c);
+          dst[i] = ((a + b) + (d + e)) * 0.25f;
+          dm_store4(pr + 4 * c, dst[i]);
+        } else {
+          dst[i] = (f32x4){0.f, 0.f, 0.f, 0.f};
+        }
+      }
+      return;
+    }
     const float *xr = x + (long long)r * cols;
 #pragma unroll
     for (int i = 0; i < CH; ++i) {
@@ -119,8 +139,9 @@ __global__ __launch_bounds__(256) void layernorm_fwd_kernel(const float *__restr
   // counted past the stores issued since (a loop that met the first row's request at its head would wait for everything each time round).
   // Other widths keep the plain loop: with lane predicates every wait in the loop comes out as a wait for everything, and the second
   // row of registers costs the bf16 instance its eighth wave per SIMD.
+  // (POOL: four source rows per row, and the transitions have no more rows than the grid has waves: the plain loop)
   f32x4 v[CH], nv[CH];
-  if constexpr (!FULL) {
+  if constexpr (!FULL || POOL) {
     for (; row < rows; row += stride) {
       request(row, v);
       finish(row, v);
@@ -147,12 +168,16 @@ __global__ __launch_bounds__(256) void layernorm_fwd_kernel(const float *__restr
 // CH = float4 chunks per lane per row: 3 for rows of up to 768 columns, 4 up to 1024.  FULL: cols == 256 CH (the encoder's 768), every
 // lane live in every chunk: no lane predicate, so no skip branches in the row loop and its waits are counted exactly.  Registers
 // (fp32 / bf16 dy): CH = 3 FULL 135 / 126, CH = 3 168 / 162, CH = 4 155 / 148 -- all within the 168 that three workgroups per CU allow.
-template <typename TDY, int CH, bool FULL>
+// POOL (stage transition, dm_pool_layernorm_bwd): the rows are pooled rows; 0.25 dx goes to the four rows of the [.., side, side, cols]
+// cube that were averaged into the row (token_pool_bwd_kernel's arithmetic), fp32 in dx and, rounded, bf16 in dx_lp -- both cube-sized.
+// rg_t > 0: row (b, s, t) of the bf16 copy is stored as row (s, b, t) -- the order the patch embeds' weight gradients read; dx is untouched.
+template <typename TDY, int CH, bool FULL, bool POOL = false>
 __global__ __launch_bounds__(256) void layernorm_bwd_kernel(const TDY *__restrict__ dy, const float *__restrict__ x,
                                                             const float *__restrict__ gamma, const float *__restrict__ mean,
                                                             const float *__restrict__ rstd, const float *__restrict__ dres,
                                                             float *__restrict__ dx, bf16_t *__restrict__ dx_lp,
-                                                            float *__restrict__ partial, int rows, int cols, long long lp_plane) {
+                                                            float *__restrict__ partial, int rows, int cols, long long lp_plane,
+                                                            int pool_side = 0, int rg_s = 0, int rg_t = 0) {
   // lp_plane > 0: dx_lp is the hi / lo plane pair of dx (lo plane lp_plane elements behind), not a rounded bf16 copy
   __shared__ float red[4][2][CH * 256];
   const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);      // the row index stays scalar: branches on it are jumps
@@ -228,6 +253,32 @@ __global__ __launch_bounds__(256) void layernorm_bwd_kernel(const TDY *__restric
       t2 += u2;
     }
     const float c1 = t1 / (float)cols, c2 = t2 / (float)cols;
+    if constexpr (POOL) {
+      const int half = pool_side >> 1, px = row % half, q = row / half, py = q % half, bs = q / half;      // (scalar: row is wave-uniform)
+      const long long base = (((long long)bs * pool_side + 2 * py) * pool_side + 2 * px) * cols, down = (long long)pool_side * cols;
+#pragma unroll
+      for (int i = 0; i < CH; ++i) {
+        const int c = lane + 64 * i;
+        if (FULL || c < nch) {
+          f32x4 o;
+#pragma unroll
+          for (int e = 0; e < 4; ++e) o[e] = rs * (g[i][e] - c1 - xh[i][e] * c2);
+          o = o * 0.25f;
+          const long long at[4] = {base, base + cols, base + down, base + down + cols};
+#pragma unroll
+          for (int k = 0; k < 4; ++k) {
+            dm_store4(dx + at[k] + 4 * c, o);
+            if (dx_lp) dm_store4(dx_lp + at[k] + 4 * c, o);
+          }
+        }
+      }
+      return;
+    }
+    long long off_lp = off;
+    if (rg_t > 0) {
+      const int st = rg_s * rg_t, b = row / st, rem = row - b * st, sc = rem / rg_t, t = rem - sc * rg_t;
+      off_lp = ((long long)(sc * (rows / st) + b) * rg_t + t) * cols;
+    }
 #pragma unroll
     for (int i = 0; i < CH; ++i) {
       const int c = lane + 64 * i;
@@ -248,7 +299,7 @@ __global__ __launch_bounds__(256) void layernorm_bwd_kernel(const TDY *__restric
             *reinterpret_cast<bf16x4 *>(dx_lp + off + 4 * c) = h;
             *reinterpret_cast<bf16x4 *>(dx_lp + lp_plane + off + 4 * c) = l;
           } else {
-            dm_store4(dx_lp + off + 4 * c, o);
+            dm_store4(dx_lp + off_lp + 4 * c, o);
           }
         }
       }
@@ -819,9 +870,10 @@ extern "C" int dm_layernorm_fwd(const float *x, const float *gamma, const float 
 extern "C" int64_t dm_layernorm_bwd_partial_floats(int32_t cols) { return (int64_t)ln_max_wg() * 2 * cols; }
 
 // main kernel of the LayerNorm backward: dx (+ dres), optional bf16 copy, one [dgamma | dbeta] partial row per workgroup; *n_partial rows
+// pool_side > 0: the stage-transition form (rows = pooled rows, dx / dx_lp the cube); rg_t > 0: the bf16 copy's rows regrouped (b, s, t) -> (s, b, t)
 static int ln_bwd_main(const void *dy, int32_t dy_dtype, const float *x, const float *gamma, const float *mean, const float *rstd,
                        const float *dres, float *dx, void *dx_lp, float *partial, int32_t rows, int32_t cols, int32_t *n_partial, hipStream_t s,
-                       const char *who, bool lp_pair = false) {
+                       const char *who, bool lp_pair = false, int pool_side = 0, int rg_s = 0, int rg_t = 0) {
   const long long lp_plane = lp_pair ? (long long)rows * cols : 0;
   DM_REQUIRE(!lp_pair || (dx_lp && cols <= MAXCH * 256), DM_ERR_UNSUPPORTED, "%s: the plane-pair copy needs dx_lp and cols <= %d", who, MAXCH * 256);
   DM_REQUIRE(rows > 0 && cols > 0 && cols % 4 == 0 && cols <= LN_WIDE_MAX, DM_ERR_BAD_SHAPE, "%s: rows=%d cols=%d", who, rows, cols);
@@ -836,11 +888,18 @@ static int ln_bwd_main(const void *dy, int32_t dy_dtype, const float *x, const f
   }
   const int grid = grid_for((long long)rows, 4, ln_max_wg());
   DM_REQUIRE(dy_dtype == DM_F32 || dy_dtype == DM_BF16, DM_ERR_BAD_DTYPE, "%s: bad dy_dtype %d", who, dy_dtype);
+  if (pool_side > 0) {
+    hipLaunchKernelGGL((layernorm_bwd_kernel<float, 3, true, true>), dim3(grid), dim3(256), 0, s, (const float *)dy, x, gamma, mean, rstd, (const float *)nullptr,
+                       dx, (bf16_t *)dx_lp, partial, rows, cols, 0LL, pool_side, 0, 0);
+    DM_LAUNCH_CHECK("dm_pool_layernorm_bwd");
+    *n_partial = grid;
+    return DM_OK;
+  }
   // FULL: every lane holds live columns in each of its CH chunks (the encoder's 768 columns): no lane predicate anywhere in the row loop
   const bool narrow = cols <= 768, full = cols == 768;
 #define DM_LN_BWD(T, CH_, FULL_)                                                                                                      \
   hipLaunchKernelGGL((layernorm_bwd_kernel<T, CH_, FULL_>), dim3(grid), dim3(256), 0, s, (const T *)dy, x, gamma, mean, rstd, dres, dx, \
-                     (bf16_t *)dx_lp, partial, rows, cols, lp_plane)
+                     (bf16_t *)dx_lp, partial, rows, cols, lp_plane, 0, rg_s, rg_t)
   if (dy_dtype == DM_F32) {
     if (full) DM_LN_BWD(float, 3, true);
     else if (narrow) DM_LN_BWD(float, 3, false);
@@ -880,6 +939,52 @@ extern "C" int dm_layernorm_bwd_partials_pair(const void *dy, int32_t dy_dtype, 
                                               int32_t cols, int32_t *n_partial, void *stream) {
   return ln_bwd_main(dy, dy_dtype, x, gamma, mean, rstd, dres, dx, dx_pair, partial, rows, cols, n_partial, reinterpret_cast<hipStream_t>(stream),
                      "dm_layernorm_bwd_partials_pair", true);
+}
+
+extern "C" int dm_layernorm_bwd_partials_regroup(const void *dy, int32_t dy_dtype, const float *x, const float *gamma, const float *mean,
+                                                 const float *rstd, const float *dres, float *dx, void *dx_lp, float *partial, int32_t rows,
+                                                 int32_t cols, int32_t S, int32_t T, int32_t *n_partial, void *stream) {
+  DM_REQUIRE(dx_lp && S > 0 && T > 0 && rows > 0 && rows % (S * T) == 0, DM_ERR_BAD_SHAPE,
+             "dm_layernorm_bwd_partials_regroup: rows=%d must be whole (S=%d, T=%d) groups, and dx_lp set", rows, S, T);
+  DM_REQUIRE(cols <= MAXCH * 256, DM_ERR_UNSUPPORTED, "dm_layernorm_bwd_partials_regroup: cols=%d (the register-resident widths only, <= %d)", cols, MAXCH * 256);
+  return ln_bwd_main(dy, dy_dtype, x, gamma, mean, rstd, dres, dx, dx_lp, partial, rows, cols, n_partial, reinterpret_cast<hipStream_t>(stream),
+                     "dm_layernorm_bwd_partials_regroup", false, 0, S, T);
+}
+
+extern "C" int dm_pool_layernorm_ok(int32_t cols) { return cols == 768; }
+
+extern "C" int dm_pool_layernorm_fwd(const float *x, const float *gamma, const float *beta, float *pooled, float *y, float *mean, float *rstd,
+                                     int32_t B, int32_t S, int32_t side, int32_t C, float eps, void *stream) {
+  DM_REQUIRE(B > 0 && S > 0 && side >= 2 && side % 2 == 0 && (long long)B * S * (side / 2) * (side / 2) < (1LL << 31), DM_ERR_BAD_SHAPE,
+             "dm_pool_layernorm_fwd: B=%d S=%d side=%d C=%d", B, S, side, C);
+  DM_REQUIRE(dm_pool_layernorm_ok(C), DM_ERR_UNSUPPORTED, "dm_pool_layernorm_fwd: C=%d (768 only: pool and normalise in two calls)", C);
+  DM_REQUIRE(x && gamma && beta && pooled && y && mean && rstd, DM_ERR_BAD_SHAPE, "dm_pool_layernorm_fwd: null pointer");
+  const int rows = B * S * (side / 2) * (side / 2);
+  hipLaunchKernelGGL((layernorm_fwd_kernel<float, false, 3, true, true>), dim3(grid_for((long long)rows, 4, 2048)), dim3(256), 0,
+                     reinterpret_cast<hipStream_t>(stream), x, gamma, beta, y, mean, rstd, rows, C, eps, pooled, side);
+  DM_LAUNCH_CHECK("dm_pool_layernorm_fwd");
+  return DM_OK;
+}
+
+extern "C" int dm_pool_layernorm_bwd(const float *dy, const float *pooled, const float *gamma, const float *mean, const float *rstd, float *dx,
+                                     void *dx_lp, float *dgamma, float *dbeta, int32_t accumulate_params, float *partial, int32_t *n_partial,
+                                     int32_t B, int32_t S, int32_t side, int32_t C, void *stream) {
+  DM_REQUIRE(B > 0 && S > 0 && side >= 2 && side % 2 == 0 && (long long)B * S * (side / 2) * (side / 2) < (1LL << 31), DM_ERR_BAD_SHAPE,
+             "dm_pool_layernorm_bwd: B=%d S=%d side=%d C=%d", B, S, side, C);
+  DM_REQUIRE(dm_pool_layernorm_ok(C), DM_ERR_UNSUPPORTED, "dm_pool_layernorm_bwd: C=%d (768 only: the three separate calls)", C);
+  DM_REQUIRE((dgamma != nullptr) == (dbeta != nullptr) && (dgamma || n_partial), DM_ERR_BAD_SHAPE,
+             "dm_pool_layernorm_bwd: dgamma and dbeta together, or n_partial for the partial rows alone");
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  const int rows = B * S * (side / 2) * (side / 2);
+  int32_t slices = 0;
+  if (const int rc = ln_bwd_main(dy, DM_F32, pooled, gamma, mean, rstd, nullptr, dx, dx_lp, partial, rows, C, &slices, s, "dm_pool_layernorm_bwd", false, side))
+    return rc;
+  if (n_partial) *n_partial = slices;
+  if (dgamma) {
+    hipLaunchKernelGGL(partial_reduce_kernel, dim3((2 * C + 15) / 16), dim3(256), 0, s, partial, dgamma, dbeta, slices, 2 * C, C, accumulate_params);
+    DM_LAUNCH_CHECK("dm_pool_layernorm_bwd(reduce)");
+  }
+  return DM_OK;
 }
 
 extern "C" int dm_partial_reduce_batch(const DmReduceItem *items, int32_t n, void *stream) {

@@ -317,8 +317,12 @@ class ShfitScaleFormer_v3(nn.Module):
     def designed_feature_embed(self, x):
         return self.feature_embed(x)
 
-    def _ln(self, x, out_dtype=torch.float32):
-        return ops.LayerNormFn.apply(x, self.norm.weight, self.norm.bias, self.norm.eps, out_dtype)
+    def _ln(self, x, out_dtype=torch.float32, grad_lp=None):
+        return ops.LayerNormFn.apply(x, self.norm.weight, self.norm.bias, self.norm.eps, out_dtype, grad_lp)
+
+    def _pool_ln(self, x, side):
+        """A stage transition: per-scale 2 x 2 token pooling, then the shared norm (one fused kernel each way where ops.pool_norm has one)."""
+        return ops.pool_norm(x, self.norm.weight, self.norm.bias, self.norm.eps, self.input_scales_num, side, self.numerics)
 
     _dp_cut = None      # set by PairTrainer for one forward pass: autograd cut points for the segmented (data-parallel) backward
 
@@ -329,9 +333,9 @@ class ShfitScaleFormer_v3(nn.Module):
         else:                                    # stage 0 holds ~55 % of the step: one backward segment per block
             for blk in self.blocks0:
                 x = self._dp_cut(blk(x), blk)
-        x = self._ln(ops.TokenPoolFn.apply(x, S, side))
+        x = self._pool_ln(x, side)
         x = self.blocks1(x)
-        x = self._ln(ops.TokenPoolFn.apply(x, S, side // 2))
+        x = self._pool_ln(x, side // 2)
         return self.blocks2(x)
 
     def _pooled_tokens(self, x):
@@ -339,7 +343,8 @@ class ShfitScaleFormer_v3(nn.Module):
         x = self.pos_drop(self.patch_embed(x))
         if self._dp_cut is not None:             # the patch embeds' gradients (17 MB at 4 scales x 4 ch) get a bucket of their own: the
             x = self._dp_cut(x, self.patch_embed_blocks)   # exchange of stage-0 block 0 then starts before their backward, not after it
-        x = self._ln(self.backbone(x))
+        # (the gradient that leaves the final norm is the operand of the last block's backward products: bf16 there, the kernel writes that copy too)
+        x = self._ln(self.backbone(x), grad_lp=ops.act_dtype(self.numerics) if len(self.blocks2) else None)
         g = x.shape[1] // self.input_scales_num
         return ops.GroupMeanFn.apply(x, g).view(B, -1)
 

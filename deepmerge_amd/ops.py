@@ -471,10 +471,23 @@ def _queue_reduce(part, out0, out1, nrows, width, split, accumulate) -> None:
         _flush_queued = True
 
 
-def layernorm_bwd(dy, x, gamma, mean, rstd, dres=None, dgamma=None, dbeta=None, accumulate=False, want_lp=False, defer=False, want_pair=False):
+def _reduce_partials(part, dgamma, dbeta, n_part, cols, accumulate, deferred) -> None:
+    """[dgamma | dbeta] from the partial rows a LayerNorm backward left: queued for the end of the backward pass, or one launch now."""
+    if deferred:
+        _queue_reduce(part, dgamma, dbeta, n_part, 2 * cols, cols, accumulate)
+        return
+    item = (_lib.DmReduceItem * 1)()
+    item[0].partial, item[0].out0, item[0].out1 = part.data_ptr(), dgamma.data_ptr(), dbeta.data_ptr()
+    item[0].nrows, item[0].width, item[0].split, item[0].accumulate = n_part, 2 * cols, cols, int(bool(accumulate))
+    check(_lib.lib().dm_partial_reduce_batch(item, 1, _stream()), "dm_partial_reduce_batch")
+
+
+def layernorm_bwd(dy, x, gamma, mean, rstd, dres=None, dgamma=None, dbeta=None, accumulate=False, want_lp=False, defer=False, want_pair=False,
+                  regroup=None):
     """Returns (dx, dgamma, dbeta) or, with want_lp, (dx, dx_bf16, dgamma, dbeta); with want_pair, (dx, Planes(dx), dgamma, dbeta).
     defer=True (only with caller-provided dgamma / dbeta, inside a backward pass): their reduction is queued for the end of the pass
-    (`flush_reductions`); dx is complete on return."""
+    (`flush_reductions`); dx is complete on return.
+    regroup=(S, T) (with want_lp; rows = B * S * T): dx_bf16 comes back as [S, B, T, cols], row (b, s, t) stored as row (s, b, t)."""
     _need_cuda(dy, x)
     if not (dy.is_contiguous() and x.is_contiguous()) or dy.numel() != x.numel():
         raise ValueError("layernorm_bwd: dy and x must be contiguous and of the same size (an expanded gradient has no rows to read)")
@@ -503,6 +516,20 @@ def layernorm_bwd(dy, x, gamma, mean, rstd, dres=None, dgamma=None, dbeta=None, 
             item[0].nrows, item[0].width, item[0].split, item[0].accumulate = n_part.value, 2 * cols, cols, int(bool(accumulate))
             check(_lib.lib().dm_partial_reduce_batch(item, 1, _stream()), "dm_partial_reduce_batch")
         return dx, Planes(pair), dgamma, dbeta
+    if regroup is not None:
+        S, T = regroup
+        if not want_lp or rows % (S * T) or cols > _PAIR_LN_MAX_COLS:
+            raise ValueError("layernorm_bwd: regroup needs want_lp, rows in whole (S, T) groups and a register-resident width")
+        dx_lp = torch.empty((S, rows // (S * T), T, cols), dtype=torch.bfloat16, device=x.device)
+        deferred = defer and _DEFER_REDUCTIONS and _in_backward()
+        part = (torch.empty(_lib.lib().dm_layernorm_bwd_partial_floats(cols), dtype=torch.float32, device=x.device) if deferred
+                else workspace(_lib.lib().dm_layernorm_bwd_partial_floats(cols) * 4, x.device, "partial").view(torch.float32))
+        n_part = C.c_int32(0)
+        check(_lib.lib().dm_layernorm_bwd_partials_regroup(dy.data_ptr(), _dt(dy), x.data_ptr(), gamma.data_ptr(), mean.data_ptr(), rstd.data_ptr(),
+                                                           _ptr(dres), dx.data_ptr(), dx_lp.data_ptr(), part.data_ptr(), rows, cols, S, T,
+                                                           C.byref(n_part), _stream()), "dm_layernorm_bwd_partials_regroup")
+        _reduce_partials(part, dgamma, dbeta, n_part.value, cols, accumulate, deferred)
+        return dx, dx_lp, dgamma, dbeta
     if defer and _DEFER_REDUCTIONS and _in_backward():
         part = torch.empty(_lib.lib().dm_layernorm_bwd_partial_floats(cols), dtype=torch.float32, device=x.device)
         n_part = C.c_int32(0)
@@ -519,6 +546,10 @@ def layernorm_bwd(dy, x, gamma, mean, rstd, dres=None, dgamma=None, dbeta=None, 
 
 
 _DEFER_REDUCTIONS = os.environ.get("DM_DEFER_REDUCTIONS", "1") != "0"      # A/B switch
+# A/B switch for the launches between the blocks: the stage transitions as one kernel each way (PoolNormFn), the bf16 gradient copies the
+# final norm and block 0 write for their consumers (LayerNormFn's grad_lp, the regrouped rows PatchEmbedCatFn.backward reads).  0 = the
+# separate launches; results are bit-identical either way.
+_FUSED_GLUE = os.environ.get("DM_FUSED_GLUE", "1") != "0"
 
 
 def relpos_bias_gather(table: torch.Tensor, index32: torch.Tensor, N: int, transposed: bool = False):
@@ -1106,6 +1137,8 @@ class PatchEmbedCatFn(torch.autograd.Function):
         ctx.save_for_backward(*cols, *ws)
         ctx.cfg = (S, T, B, Cc)
         ctx.params = (weights, biases)
+        if _FUSED_GLUE:
+            cube._dm_lp_rows = (S, T)      # a fused block that gets this very tensor leaves its gradient's bf16 rows in [S, B, T, C] order (backward below)
         return cube
 
     @staticmethod
@@ -1118,7 +1151,14 @@ class PatchEmbedCatFn(torch.autograd.Function):
         grads_w, grads_b = [], []
         # every scale's gradient rows in the operands' dtype, [S, B * T, C]: ONE strided cast-copy for all scales when they share a dtype
         same = all(c.dtype == cols[0].dtype for c in cols)
-        dys = torch.empty((S, B, T, Cc), dtype=cols[0].dtype, device=dcube.device).copy_(dcube.contiguous().view(B, S, T, Cc).transpose(0, 1)) if same else None
+        # block 0's LayerNorm backward has already written exactly those rows next to this very gradient (tag still current: nothing was
+        # summed into it since) -- else the strided cast-copy
+        rg = getattr(dcube, "_dm_lp_regrouped", None)
+        if (rg is not None and same and rg[1] == _grad_tag(dcube) and rg[2] == (S, T) and rg[0].dtype == cols[0].dtype
+                and tuple(rg[0].shape) == (S, B, T, Cc) and tuple(dcube.shape) == (B, S * T, Cc)):
+            dys = rg[0]
+        else:
+            dys = torch.empty((S, B, T, Cc), dtype=cols[0].dtype, device=dcube.device).copy_(dcube.contiguous().view(B, S, T, Cc).transpose(0, 1)) if same else None
         for i in range(S):
             c = cols[i]
             K = c.shape[1]
@@ -1176,25 +1216,33 @@ class LayerNormFn(torch.autograd.Function):
     """nn.LayerNorm over the last dim, fp32 in, `out_dtype` out (nets/ShfitScaleFormer.py:173, :177, :856)."""
 
     @staticmethod
-    def forward(ctx, x, gamma, beta, eps, out_dtype):
+    def forward(ctx, x, gamma, beta, eps, out_dtype, grad_lp=None):
+        """grad_lp = torch.bfloat16: the consumer of dx is a bf16 fused block -- the backward kernel also writes dx's bf16 copy, which
+        rides on dx as `_dm_lp_copy` the way BlockFn.backward's does (the caller states the dtype; nothing is guessed here)."""
         x = x.contiguous()
         y, mean, rstd = layernorm_fwd(x, gamma, beta, eps, out_dtype)
         ctx.save_for_backward(x, gamma, mean, rstd)
         ctx.params = (gamma, beta)
+        ctx.want_lp = grad_lp == torch.bfloat16 and _FUSED_GLUE
         return y
 
     @staticmethod
     def backward(ctx, dy):
         x, gamma, mean, rstd = ctx.saved_tensors
         C = gamma.numel()
+        lp = ctx.want_lp
         gs, bs = _multi_use_sink(ctx.params[0], (C,)), _multi_use_sink(ctx.params[1], (C,))
         if gs is not None and bs is not None and ctx.needs_input_grad[1] and ctx.needs_input_grad[2]:
             acc = _acc(ctx.params[0], True)
             _acc(ctx.params[1], True)
-            r = layernorm_bwd(dy.contiguous(), x, gamma, mean, rstd, dgamma=gs, dbeta=bs, accumulate=acc)
-            return r[0], None, None, None, None
-        dx, dg, db = layernorm_bwd(dy.contiguous(), x, gamma, mean, rstd)
-        return dx, dg, db, None, None
+            r = layernorm_bwd(dy.contiguous(), x, gamma, mean, rstd, dgamma=gs, dbeta=bs, accumulate=acc, want_lp=lp)
+            dx, dg, db = r[0], None, None
+        else:
+            r = layernorm_bwd(dy.contiguous(), x, gamma, mean, rstd, want_lp=lp)
+            dx, dg, db = r[0], r[-2], r[-1]
+        if lp:
+            dx._dm_lp_copy = (r[1], _grad_tag(dx))
+        return dx, dg, db, None, None, None
 
 
 class AttentionFn(torch.autograd.Function):
@@ -1346,6 +1394,79 @@ class TokenPoolFn(torch.autograd.Function):
         dx = torch.empty((B, S * side * side, Cc), dtype=torch.float32, device=dy.device)
         check(_lib.lib().dm_token_pool_bwd(dy.data_ptr(), dx.data_ptr(), B, S, side, Cc, _stream()), "dm_token_pool_bwd")
         return dx, None, None
+
+
+def pool_norm_fused(x: torch.Tensor, numerics: str) -> bool:
+    """Whether a stage transition on x [B, N, C] runs as PoolNormFn: the switch is on, the width is one the fused kernels hold in
+    registers, and the mode is not "bf16x3" (whose blocks exchange plane pairs, not bf16 copies)."""
+    return (_FUSED_GLUE and numerics != "bf16x3" and x.is_cuda and x.dtype == torch.float32
+            and bool(_lib.lib().dm_pool_layernorm_ok(x.shape[-1])))
+
+
+def pool_norm(x, gamma, beta, eps, S, side, numerics):
+    """LayerNorm(TokenPool(x)): one launch each way where pool_norm_fused() holds, else the two Functions."""
+    if pool_norm_fused(x, numerics):
+        return PoolNormFn.apply(x, gamma, beta, eps, S, side, act_dtype(numerics))
+    return LayerNormFn.apply(TokenPoolFn.apply(x, S, side), gamma, beta, eps, torch.float32)
+
+
+class PoolNormFn(torch.autograd.Function):
+    """A stage transition, LayerNorm(AvgPool2d(2,2) per scale) (nets/ShfitScaleFormer.py:892-915), as one kernel each way:
+    dm_pool_layernorm_fwd / _bwd, bit-identical to TokenPoolFn + LayerNormFn (+ the bf16 cast of the gradient in the next
+    BlockFn.backward).  grad_lp = torch.bfloat16: the gradient's bf16 copy rides on it as `_dm_lp_copy`."""
+
+    @staticmethod
+    def forward(ctx, x, gamma, beta, eps, S, side, grad_lp):
+        x = x.contiguous()
+        B, N, Cc = x.shape
+        if N != S * side * side:
+            raise ValueError(f"PoolNormFn: {N} tokens are not {S} scales of {side} x {side}")
+        n = S * (side // 2) ** 2
+        pooled = torch.empty((B, n, Cc), dtype=torch.float32, device=x.device)
+        y = torch.empty((B, n, Cc), dtype=torch.float32, device=x.device)
+        mean = torch.empty(B * n, dtype=torch.float32, device=x.device)
+        rstd = torch.empty(B * n, dtype=torch.float32, device=x.device)
+        check(_lib.lib().dm_pool_layernorm_fwd(x.data_ptr(), gamma.data_ptr(), beta.data_ptr(), pooled.data_ptr(), y.data_ptr(), mean.data_ptr(),
+                                               rstd.data_ptr(), B, S, side, Cc, eps, _stream()), "dm_pool_layernorm_fwd")
+        ctx.save_for_backward(pooled, gamma, mean, rstd)
+        ctx.dims = (B, S, side, Cc)
+        ctx.params = (gamma, beta)
+        ctx.want_lp = grad_lp == torch.bfloat16
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        pooled, gamma, mean, rstd = ctx.saved_tensors
+        B, S, side, Cc = ctx.dims
+        dy = dy.contiguous()
+        if dy.dtype != torch.float32 or dy.numel() != pooled.numel():
+            raise ValueError("PoolNormFn.backward: the gradient must be fp32 and of the pooled rows' size")
+        dev = dy.device
+        dx = torch.empty((B, S * side * side, Cc), dtype=torch.float32, device=dev)
+        dx_lp = torch.empty(dx.shape, dtype=torch.bfloat16, device=dev) if ctx.want_lp else None
+        gs, bs = _multi_use_sink(ctx.params[0], (Cc,)), _multi_use_sink(ctx.params[1], (Cc,))
+        sinks = gs is not None and bs is not None and ctx.needs_input_grad[1] and ctx.needs_input_grad[2]
+        if sinks:
+            dg, db, acc = gs, bs, _acc(ctx.params[0], True)
+            _acc(ctx.params[1], True)
+        else:
+            dg, db, acc = torch.empty(Cc, dtype=torch.float32, device=dev), torch.empty(Cc, dtype=torch.float32, device=dev), False
+        nfl = _lib.lib().dm_layernorm_bwd_partial_floats(Cc)
+        if sinks and _DEFER_REDUCTIONS and _in_backward():
+            part = torch.empty(nfl, dtype=torch.float32, device=dev)
+            n_part = C.c_int32(0)
+            check(_lib.lib().dm_pool_layernorm_bwd(dy.data_ptr(), pooled.data_ptr(), gamma.data_ptr(), mean.data_ptr(), rstd.data_ptr(), dx.data_ptr(),
+                                                   _ptr(dx_lp), None, None, 0, part.data_ptr(), C.byref(n_part), B, S, side, Cc, _stream()),
+                  "dm_pool_layernorm_bwd")
+            _queue_reduce(part, dg, db, n_part.value, 2 * Cc, Cc, acc)
+        else:
+            part = workspace(nfl * 4, dev, "partial")
+            check(_lib.lib().dm_pool_layernorm_bwd(dy.data_ptr(), pooled.data_ptr(), gamma.data_ptr(), mean.data_ptr(), rstd.data_ptr(), dx.data_ptr(),
+                                                   _ptr(dx_lp), dg.data_ptr(), db.data_ptr(), int(acc), part.data_ptr(), None, B, S, side, Cc, _stream()),
+                  "dm_pool_layernorm_bwd")
+        if dx_lp is not None:
+            dx._dm_lp_copy = (dx_lp, _grad_tag(dx))
+        return dx, (None if sinks else dg), (None if sinks else db), None, None, None, None
 
 
 class GroupMeanFn(torch.autograd.Function):
@@ -1614,6 +1735,9 @@ class BlockFn(torch.autograd.Function):
     def forward(ctx, x, n1w, n1b, table, index32, qkv_w, qkv_b, proj_w, proj_b, n2w, n2b, fc1_w, fc1_b, fc2_w, fc2_b,
                 heads, eps, scale, dtype):
         _save_products(ctx)
+        # the patch embeds' cube (PatchEmbedCatFn.forward tags it): they read this block's input gradient as bf16 rows in [S, B, T, C] order
+        lp_rows = getattr(x, "_dm_lp_rows", None)
+        ctx.lp_rows = lp_rows if (lp_rows is not None and x.dim() == 3 and lp_rows[0] * lp_rows[1] == x.shape[1]) else None
         x = x.contiguous()
         B, N, Cc = x.shape
         M, Hd, D = B * N, fc1_w.shape[0], Cc // heads
@@ -1792,8 +1916,9 @@ class BlockFn(torch.autograd.Function):
             dg1, dbt1, k_n1, k_n1b = torch.empty(Cc, device=dev), torch.empty(Cc, device=dev), False, False
         a_n1 = _acc(P_n1w, k_n1)
         _acc(P_n1b, k_n1b)
+        regroup = ctx.lp_rows if (lp and dtype == torch.bfloat16 and _FUSED_GLUE and Cc <= _PAIR_LN_MAX_COLS) else None
         r = layernorm_bwd(dy1, x, n1w, mean1, rstd1, dres=dx1, dgamma=dg1, dbeta=dbt1, accumulate=a_n1, want_lp=lp, defer=bool(k_n1 and k_n1b),
-                          want_pair=planes)
+                          want_pair=planes, regroup=regroup)
         if side is not None:
             torch.cuda.current_stream().wait_stream(side)          # join: every weight gradient of this block is complete
         if pending:
@@ -1801,7 +1926,9 @@ class BlockFn(torch.autograd.Function):
         if late:
             gemm_grouped(late)
         dx = r[0].view(B, N, Cc)
-        if lp:
+        if regroup is not None:      # (under its own name: in this row order it is of use to PatchEmbedCatFn.backward alone)
+            dx._dm_lp_regrouped = (r[1], _grad_tag(dx), regroup)
+        elif lp:
             # The bf16 copy the LayerNorm backward wrote rides on the tensor object autograd hands to the next node (the
             # engine preserves the Python object); a consumer that gets some other tensor, or this one after an in-place sum, simply casts.
             dx._dm_lp_copy = (r[1], _grad_tag(dx))

@@ -256,6 +256,12 @@ int dm_layernorm_bwd_partials(const void *dy, int32_t dy_dtype, const float *x, 
 int dm_layernorm_bwd_partials_pair(const void *dy, int32_t dy_dtype, const float *x, const float *gamma,
                                    const float *mean, const float *rstd, const float *dres, float *dx, void *dx_pair, float *partial,
                                    int32_t rows, int32_t cols, int32_t *n_partial, void *stream);
+/* dm_layernorm_bwd_partials with the rows of the bf16 copy REGROUPED: rows = B * S * T, row (b, s, t) of dx is stored as row (s, b, t)
+ * of dx_lp (bf16 [S, B, T, cols], required) -- the order in which the per-scale patch embeds read the token cube's gradient.  dx itself
+ * and the partial rows are those of dm_layernorm_bwd_partials.  cols <= 1024. */
+int dm_layernorm_bwd_partials_regroup(const void *dy, int32_t dy_dtype, const float *x, const float *gamma,
+                                      const float *mean, const float *rstd, const float *dres, float *dx, void *dx_lp, float *partial,
+                                      int32_t rows, int32_t cols, int32_t S, int32_t T, int32_t *n_partial, void *stream);
 /* One job of dm_partial_reduce_batch: out0[j] (+)= sum_r partial[r][j] for j < split, out1[j - split] (+)= ... for split <= j < width;
  * rows are summed in a fixed order (deterministic).  Jobs of one batch must not share output elements. */
 typedef struct DmReduceItem {
@@ -270,6 +276,19 @@ int dm_partial_reduce_batch(const DmReduceItem *items, int32_t n, void *stream);
  * nets/ShfitScaleFormer.py:892-901, :905-914): x [B, S*side*side, C] -> y [B, S*(side/2)^2, C], fp32. */
 int dm_token_pool_fwd(const float *x, float *y, int32_t B, int32_t S, int32_t side, int32_t C, void *stream);
 int dm_token_pool_bwd(const float *dy, float *dx, int32_t B, int32_t S, int32_t side, int32_t C, void *stream);
+/* A stage transition, LayerNorm(pool(x)) (nets/ShfitScaleFormer.py:892-915), in ONE launch each way (additive entry points, ABI 7).
+ * Forward: pooled [B, S*(side/2)^2, C] (kept for the backward pass), y = LayerNorm(pooled) fp32, mean / rstd per pooled row --
+ * bit-identical to dm_token_pool_fwd followed by dm_layernorm_fwd(DM_F32).
+ * Backward: dy fp32 [pooled rows, C] -> dx fp32 [B, S*side*side, C] and, when dx_lp is set, the same values rounded to bf16 --
+ * bit-identical to dm_layernorm_bwd, dm_token_pool_bwd, dm_cast(DM_BF16).  dgamma / dbeta set: reduced here ((+)= with
+ * accumulate_params); NULL: `*n_partial` partial rows are left in `partial` for dm_partial_reduce_batch, as dm_layernorm_bwd_partials
+ * leaves them (same rows, same layout).  Only the widths dm_pool_layernorm_ok(C) accepts (768); others: DM_ERR_UNSUPPORTED. */
+int dm_pool_layernorm_ok(int32_t C);
+int dm_pool_layernorm_fwd(const float *x, const float *gamma, const float *beta, float *pooled, float *y, float *mean, float *rstd,
+                          int32_t B, int32_t S, int32_t side, int32_t C, float eps, void *stream);
+int dm_pool_layernorm_bwd(const float *dy, const float *pooled, const float *gamma, const float *mean, const float *rstd, float *dx,
+                          void *dx_lp, float *dgamma, float *dbeta, int32_t accumulate_params, float *partial, int32_t *n_partial,
+                          int32_t B, int32_t S, int32_t side, int32_t C, void *stream);
 /* Mean over groups of `g` consecutive rows (AdaptiveAvgPool1d(1) per scale, :930-938):
  * x [rows*g, C] -> y [rows, C]; backward broadcasts dy/g. */
 int dm_group_mean_fwd(const float *x, float *y, int32_t rows, int32_t g, int32_t C, void *stream);
