@@ -65,7 +65,7 @@ def train(net, margin, train_bs, lr_init, normMean, normStd, lamda, belta, is_re
           dataset: PairDataset = None, num_epochs: int = NUM_EPOCHS, milestones: Sequence[int] = (40, 80), gamma: float = 0.2,
           model_paras_path: str = MODEL_PARAS_PATH, val_dataset: Optional[PairDataset] = None, val_batch: int = 1000,
           val_thresholds: Optional[Sequence[float]] = None, log_dir: Optional[str] = None,
-          val_history: Optional[list] = None) -> Tuple[List[int], List[float]]:
+          val_history: Optional[list] = None, augment: Optional[str] = None) -> Tuple[List[int], List[float]]:
     """`Train_SMT.train` with the reference's positional signature (normMean / normStd are unused, as upstream; lamda / belta go
     to Loss).  `dataset` replaces the reference's hard-coded shapefile folders; the draw's seed is the dataset's.  Returns
     (epoch indices, per-epoch mean loss = sum of step losses / number of steps), one entry per epoch run.
@@ -73,7 +73,11 @@ def train(net, margin, train_bs, lr_init, normMean, normStd, lamda, belta, is_re
     val_dataset: a held-out PairDataset (not `dataset` itself: a dataset reuses one table buffer), evaluated after every epoch by
     evaluate.PairEvaluator(net, val_dataset, val_batch, margin, val_thresholds); `(epoch, PairEvalResult)` is appended to
     `val_history` when given.  log_dir: a callbacks.LossHistory there gets (mean train loss, val loss, F at the margin) per epoch --
-    without val_dataset, what upstream writes: (mean loss, mean loss, elapsed seconds rounded to 2 places)."""
+    without val_dataset, what upstream writes: (mean loss, mean loss, elapsed seconds rounded to 2 places).
+
+    augment: None, "flips" or "d4" -- handed to dataset.epoch: every pair of every epoch is fed at a dihedral orientation keyed by
+    (dataset seed, epoch, pair), both of its crops alike, so a resumed run sees the same views.  The
+    validation pass never augments."""
     if dataset is None:
         raise ValueError("train() needs dataset=PairDataset.from_arrays(...) (the reference's hard-coded folders are not portable)")
     if val_dataset is not None and val_dataset is dataset:
@@ -83,6 +87,8 @@ def train(net, margin, train_bs, lr_init, normMean, normStd, lamda, belta, is_re
         raise NotImplementedError("train() runs on one GPU; data-parallel sharding of the epoch is not implemented")
     if int(train_bs) < 1:
         raise ValueError(f"train_bs must be >= 1, got {train_bs}")
+    if augment is not None and augment not in ops.ORIENT_MASKS:
+        raise ValueError(f"augment must be None, 'flips' or 'd4', got {augment!r}")
     scales = [int(s) for s in getattr(net, "input_image_scales", ())]
     if not scales:
         raise ValueError(f"{type(net).__name__} has no input_image_scales: train() feeds patch pyramids")
@@ -119,7 +125,7 @@ def train(net, margin, train_bs, lr_init, normMean, normStd, lamda, belta, is_re
     for epoch in range(start_epoch, num_epochs):
         lr = epoch_lr(lr0, epoch - start_epoch, milestones, gamma)
         trainer.lr = lr                         # what the optimizer holds this epoch (checkpoint.optimizer_state_dict writes it)
-        table = dataset.epoch(epoch, B)
+        table = dataset.epoch(epoch, B, augment=augment)
         total = torch.zeros((), dtype=torch.float32, device=dev)
         for s in range(len(table)):
             if s < n_full:

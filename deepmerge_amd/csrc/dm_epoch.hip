@@ -10,6 +10,8 @@
 //                     cycle-walked until the value is < N
 //   draw              r = philox((src, epoch, 1, 0)): left point = poly_pts[poly_off[pl] + umulhi(r[0], cnt_l)], right point
 //                     likewise with r[1] -- keyed by the pair, so shuffle and draw are independent
+//   orient            dm_pair_epoch_orient: philox((src, epoch, 3, 0))[0] & mask (7: the dihedral group D4, 3: flips only), the
+//                     augmentation of dm_pair_batch_gather_oriented, written to both rows of the pair
 // One thread per position: integer VALU work plus a gather of the two 80-byte point rows.  A pair whose polygon id, point list or
 // point id is out of range (the host validates them once, at dataset construction) reads nothing out of range: its sample gets
 // point_id -1, tile id -1 (which the feed's gather flags) and zeros.
@@ -92,7 +94,45 @@ __global__ __launch_bounds__(256) void pair_epoch_draw_kernel(DmPairDraw a, int 
   a.flag[j] = (float)a.pair_flag[src];
 }
 
+// the dihedral orientation of every pair of the epoch: counter word 3, a stream neither the draw (1) nor the shuffle (2) uses;
+// keyed by the pair like the draw, and written to both of the pair's rows
+__global__ __launch_bounds__(256) void pair_epoch_orient_kernel(uint64_t seed, int32_t epoch_, int32_t n_pairs, int32_t batch_, uint32_t mask,
+                                                                int32_t *__restrict__ orient, int h) {
+  const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= n_pairs) return;
+  const uint32_t k0 = (uint32_t)(seed & 0xffffffffull), k1 = (uint32_t)(seed >> 32);
+  const uint32_t epoch = (uint32_t)epoch_;
+  const uint32_t src = epoch_perm((uint32_t)j, (uint32_t)n_pairs, h, epoch, k0, k1);
+  const int32_t o = (int32_t)(philox4x32_10(src, epoch, 3u, 0u, k0, k1)[0] & mask);
+  const int64_t batch = batch_, s = j / batch;
+  const int64_t b_s = min(batch, (int64_t)n_pairs - s * batch);
+  const int64_t row_l = s * batch + j;
+  orient[row_l] = o;
+  orient[row_l + b_s] = o;
+}
+
+// ceil(log2 N), rounded up to even, >= 2: the width of the shuffle's Feistel network
+int feistel_bits(int32_t n_pairs) {
+  int b = 2;
+  while ((1ll << b) < (long long)n_pairs) b += 2;
+  return b;
+}
+
 }  // namespace
+
+extern "C" int dm_pair_epoch_orient(uint64_t seed, int32_t epoch, int32_t n_pairs, int32_t batch, int32_t mask, int32_t *orient, void *stream) {
+  DM_REQUIRE(mask == 3 || mask == 7, DM_ERR_BAD_SHAPE, "dm_pair_epoch_orient: mask %d (3: flips, 7: d4)", mask);
+  DM_REQUIRE(n_pairs >= 1 && n_pairs <= (1 << 30), DM_ERR_BAD_SHAPE, "dm_pair_epoch_orient: %d pairs (1 .. 2^30)", n_pairs);
+  DM_REQUIRE(batch >= 1, DM_ERR_BAD_SHAPE, "dm_pair_epoch_orient: batch %d < 1", batch);
+  DM_REQUIRE(epoch >= 0, DM_ERR_BAD_SHAPE, "dm_pair_epoch_orient: epoch %d < 0", epoch);
+  DM_REQUIRE(orient != nullptr, DM_ERR_BAD_SHAPE, "dm_pair_epoch_orient: bad arguments (null output)");
+  const int threads = 256;
+  const int blocks = (int)((n_pairs + threads - 1) / threads);
+  hipLaunchKernelGGL(pair_epoch_orient_kernel, dim3(blocks), dim3(threads), 0, reinterpret_cast<hipStream_t>(stream), seed, epoch, n_pairs, batch,
+                     (uint32_t)mask, orient, feistel_bits(n_pairs) / 2);
+  DM_LAUNCH_CHECK("dm_pair_epoch_orient");
+  return DM_OK;
+}
 
 extern "C" int dm_pair_epoch_draw(const DmPairDraw *args, void *stream) {
   DM_REQUIRE(args != nullptr, DM_ERR_BAD_SHAPE, "dm_pair_epoch_draw: null arguments");
@@ -105,8 +145,7 @@ extern "C" int dm_pair_epoch_draw(const DmPairDraw *args, void *stream) {
   DM_REQUIRE(a.pairs && a.pair_flag && a.poly_off && a.poly_pts && a.pt_tile && a.pt_xy && a.pt_inner && a.pt_obj && a.pt_region,
              DM_ERR_BAD_SHAPE, "dm_pair_epoch_draw: bad arguments (null input)");
   DM_REQUIRE(a.tile_id && a.xy && a.inner && a.obj && a.region && a.flag, DM_ERR_BAD_SHAPE, "dm_pair_epoch_draw: bad arguments (null output)");
-  int b = 2;
-  while ((1ll << b) < (long long)a.n_pairs) b += 2;      // ceil(log2 N), rounded up to even, >= 2
+  const int b = feistel_bits(a.n_pairs);
   const int threads = 256;
   const int blocks = (int)((a.n_pairs + threads - 1) / threads);
   hipLaunchKernelGGL(pair_epoch_draw_kernel, dim3(blocks), dim3(threads), 0, reinterpret_cast<hipStream_t>(stream), a, b / 2);

@@ -104,15 +104,20 @@ __device__ __forceinline__ int cv_area_pixel(const unsigned char *win, int L, in
 // is cut from, its inner / object window sides -- the four window sides of MyUtils1.py:130-156 are derived here, `scale_index` picks
 // one -- and, in the blocks of band 0, the designed-feature row [15 region attributes | 4 scale factors] (MyUtils1.py:60-77).  A sample
 // whose tile id or window is out of range gets zeros and raises `err[0]` (read back by the host every few steps, not per step).
+// `orient` (dm_pair_batch_gather_oriented, read by the ORIENT instantiations only): the sample's dihedral orientation 0..7; any
+// other value is fed as zeros and flagged like a bad tile id.
 struct BatchTable {
-  const int *tile_id, *inner, *obj;
+  const int *tile_id, *inner, *obj, *orient;
   const float *region;
   float *designed;
   int *err;
   int n_tiles, scale_index, max_window;
 };
 
-template <int TLOG2, typename OUT, bool COLS>
+// ORIENT: the staged window is crop' = D4 element orient[p] applied to the zero-padded crop (bit 1: rows mirrored, bit 0: columns
+// mirrored, then bit 2: transposed) -- crop'[j][i] = crop[fy(a)][fx(b)] with (a, b) = (i, j) under bit 2 and (j, i) otherwise --
+// and everything after the staging runs on crop' unchanged.  ORIENT = false compiles to the code this kernel had without the flag.
+template <int TLOG2, typename OUT, bool COLS, bool ORIENT>
 __global__ __launch_bounds__(256) void patch_pyramid_kernel(const unsigned char *__restrict__ tile, int bands, int H, int W,
                                                             const int *__restrict__ xy, const int *__restrict__ wins,
                                                             int Trt, int G, OUT *__restrict__ out, int rule, const BatchTable bt) {
@@ -120,18 +125,19 @@ __global__ __launch_bounds__(256) void patch_pyramid_kernel(const unsigned char 
   const int T = TLOG2 >= 0 ? (1 << TLOG2) : Trt;
   auto divT = [&](int v) { return TLOG2 >= 0 ? (v >> TLOG2) : v / T; };
   const int p = blockIdx.x, c = blockIdx.y, t = threadIdx.x;
-  int L, tid = 0;
+  int L, tid = 0, orient = 0;
   if (bt.inner) {
     const int in = bt.inner[p], ob = bt.obj[p], iv = ob - in;
     L = bt.scale_index == 0 ? in : ob + (bt.scale_index - 1) * iv;
     tid = bt.tile_id ? bt.tile_id[p] : 0;
+    if constexpr (ORIENT) orient = bt.orient[p];
     if (c == 0 && bt.designed && t < 19) {
       const int k = t - 15;
       const float wk = (float)(k == 0 ? in : ob + (k - 1) * iv);
       const float sk = k == 0 ? 32.f : k == 1 ? 64.f : k == 2 ? 128.f : 1.f;          // config.py:32 (patches.CONFIG_SCALES)
       bt.designed[(long long)p * 19 + t] = t < 15 ? bt.region[(long long)p * 15 + t] : __fdiv_rn(wk, sk);
     }
-    if (L <= 0 || L > bt.max_window || tid < 0 || tid >= bt.n_tiles) {                 // (uniform per block)
+    if (L <= 0 || L > bt.max_window || tid < 0 || tid >= bt.n_tiles || (ORIENT && (unsigned)orient > 7u)) {   // (uniform per block)
       if (t == 0 && bt.err) atomicOr(bt.err, 1);
       const int ps0 = COLS ? T / G : 1;
       const long long Kc0 = (long long)bands * ps0 * ps0;
@@ -159,13 +165,41 @@ __global__ __launch_bounds__(256) void patch_pyramid_kernel(const unsigned char 
   const int jA = gridDim.z > 1 ? max(0, (int)((long long)oyA * L / T) - 1) : 0;
   const int jB = gridDim.z > 1 ? min(L, (int)(((long long)oyB * L + T - 1) / T) + 2) : L;
   // window -> LDS, row by row: a wave walks along a row (coalesced bytes), no per-element division
-  for (int j = jA + (t >> 6); j < jB; j += 4) {
-    const int gy = y0 + j;
-    const bool rowin = gy >= 0 && gy < H;
-    const unsigned char *src = band + (long long)gy * W;
-    for (int i = t & 63; i < L; i += 64) {
-      const int gx = x0 + i;
-      win[j * L + i] = (rowin && gx >= 0 && gx < W) ? src[gx] : (unsigned char)0;
+  if constexpr (ORIENT) {
+    const bool flip_y = orient & 2, flip_x = orient & 1;
+    if (orient & 4) {
+      // crop'[j][i] = crop[fy(i)][fx(j)]: the band's rows [jA, jB) are COLUMNS of the raster window.  The lanes walk j, the index that
+      // moves along a raster row, so a wave still reads runs of consecutive bytes (nj = jB - jA per raster row, several raster rows
+      // per wave when the band is narrow) and pays for the transposition in the LDS byte writes, which are L apart.
+      const int nj = jB - jA, qi = 256 / nj, ri = 256 - qi * nj;        // thread t's next element is 256 further in (i, jj) order
+      int i = t / nj, jj = t - i * nj;
+      while (i < L) {
+        const int j = jA + jj;
+        const int gy = y0 + (flip_y ? L - 1 - i : i), gx = x0 + (flip_x ? L - 1 - j : j);
+        win[j * L + i] = (gy >= 0 && gy < H && gx >= 0 && gx < W) ? band[(long long)gy * W + gx] : (unsigned char)0;
+        i += qi; jj += ri;
+        if (jj >= nj) { jj -= nj; ++i; }
+      }
+    } else {
+      for (int j = jA + (t >> 6); j < jB; j += 4) {
+        const int gy = y0 + (flip_y ? L - 1 - j : j);
+        const bool rowin = gy >= 0 && gy < H;
+        const unsigned char *src = band + (long long)gy * W;
+        for (int i = t & 63; i < L; i += 64) {
+          const int gx = x0 + (flip_x ? L - 1 - i : i);
+          win[j * L + i] = (rowin && gx >= 0 && gx < W) ? src[gx] : (unsigned char)0;
+        }
+      }
+    }
+  } else {
+    for (int j = jA + (t >> 6); j < jB; j += 4) {
+      const int gy = y0 + j;
+      const bool rowin = gy >= 0 && gy < H;
+      const unsigned char *src = band + (long long)gy * W;
+      for (int i = t & 63; i < L; i += 64) {
+        const int gx = x0 + i;
+        win[j * L + i] = (rowin && gx >= 0 && gx < W) ? src[gx] : (unsigned char)0;
+      }
     }
   }
   __syncthreads();
@@ -215,34 +249,38 @@ __global__ __launch_bounds__(256) void patch_pyramid_kernel(const unsigned char 
 }  // namespace
 
 namespace {
-template <typename OUT, bool COLS>
+template <typename OUT, bool COLS, bool ORIENT = false>
 void launch_pyramid(dim3 grid, size_t lds, hipStream_t s, const uint8_t *tile, int bands, int H, int W, const int32_t *xy, const int32_t *windows,
                     int target, int G, OUT *out, int rule, const BatchTable bt = BatchTable{}) {
   switch (target) {
-    case 32: hipLaunchKernelGGL((patch_pyramid_kernel<5, OUT, COLS>), grid, dim3(256), lds, s, tile, bands, H, W, xy, windows, target, G, out, rule, bt); break;
-    case 64: hipLaunchKernelGGL((patch_pyramid_kernel<6, OUT, COLS>), grid, dim3(256), lds, s, tile, bands, H, W, xy, windows, target, G, out, rule, bt); break;
-    case 128: hipLaunchKernelGGL((patch_pyramid_kernel<7, OUT, COLS>), grid, dim3(256), lds, s, tile, bands, H, W, xy, windows, target, G, out, rule, bt); break;
-    case 256: hipLaunchKernelGGL((patch_pyramid_kernel<8, OUT, COLS>), grid, dim3(256), lds, s, tile, bands, H, W, xy, windows, target, G, out, rule, bt); break;
-    default: hipLaunchKernelGGL((patch_pyramid_kernel<-1, OUT, COLS>), grid, dim3(256), lds, s, tile, bands, H, W, xy, windows, target, G, out, rule, bt); break;
+    case 32: hipLaunchKernelGGL((patch_pyramid_kernel<5, OUT, COLS, ORIENT>), grid, dim3(256), lds, s, tile, bands, H, W, xy, windows, target, G, out, rule, bt); break;
+    case 64: hipLaunchKernelGGL((patch_pyramid_kernel<6, OUT, COLS, ORIENT>), grid, dim3(256), lds, s, tile, bands, H, W, xy, windows, target, G, out, rule, bt); break;
+    case 128: hipLaunchKernelGGL((patch_pyramid_kernel<7, OUT, COLS, ORIENT>), grid, dim3(256), lds, s, tile, bands, H, W, xy, windows, target, G, out, rule, bt); break;
+    case 256: hipLaunchKernelGGL((patch_pyramid_kernel<8, OUT, COLS, ORIENT>), grid, dim3(256), lds, s, tile, bands, H, W, xy, windows, target, G, out, rule, bt); break;
+    default: hipLaunchKernelGGL((patch_pyramid_kernel<-1, OUT, COLS, ORIENT>), grid, dim3(256), lds, s, tile, bands, H, W, xy, windows, target, G, out, rule, bt); break;
   }
 }
 }  // namespace
 
 // One scale of a TRAINING batch straight from resident tiles and a device sample table: no host-side window arithmetic, no per-tile
 // launches, nothing to synchronise on (Train_SMT.py:212-262 draws a batch from the loaders of MyUtils1.py:41-77 on the host).
-extern "C" int dm_pair_batch_gather(const uint8_t *tiles, int32_t n_tiles, int32_t bands, int32_t H, int32_t W, const int32_t *tile_id,
-                                    const int32_t *xy, const int32_t *inner, const int32_t *obj, int32_t scale_index, int32_t max_window,
-                                    int32_t P, int32_t target, int32_t grid, int32_t resize_rule, void *out, int32_t dtype,
-                                    const float *region_features, float *designed, int32_t *error_flag, void *stream) {
-  DM_REQUIRE(resize_rule == DM_RESIZE_OPENCV || resize_rule == DM_RESIZE_EXACT_AREA, DM_ERR_UNSUPPORTED, "dm_pair_batch_gather: unknown resize rule %d", resize_rule);
+namespace {
+template <bool ORIENT>
+int pair_batch_gather(const char *what, const uint8_t *tiles, int32_t n_tiles, int32_t bands, int32_t H, int32_t W, const int32_t *tile_id,
+                      const int32_t *xy, const int32_t *inner, const int32_t *obj, const int32_t *orient, int32_t scale_index,
+                      int32_t max_window, int32_t P, int32_t target, int32_t grid, int32_t resize_rule, void *out, int32_t dtype,
+                      const float *region_features, float *designed, int32_t *error_flag, void *stream) {
+  DM_REQUIRE(resize_rule == DM_RESIZE_OPENCV || resize_rule == DM_RESIZE_EXACT_AREA, DM_ERR_UNSUPPORTED, "%s: unknown resize rule %d", what, resize_rule);
   DM_REQUIRE(tiles && xy && inner && obj && out && n_tiles > 0 && bands > 0 && H > 0 && W > 0 && P > 0 && target > 0, DM_ERR_BAD_SHAPE,
-             "dm_pair_batch_gather: bad arguments");
-  DM_REQUIRE(scale_index >= 0 && scale_index < 4, DM_ERR_BAD_SHAPE, "dm_pair_batch_gather: scale index %d outside 0..3", scale_index);
-  DM_REQUIRE(grid >= 0 && (grid == 0 || target % grid == 0), DM_ERR_BAD_SHAPE, "dm_pair_batch_gather: target %d is not a multiple of the token grid %d", target, grid);
-  DM_REQUIRE(max_window > 0 && max_window <= MAX_WINDOW, DM_ERR_UNSUPPORTED, "dm_pair_batch_gather: window bound %d outside 1..%d", max_window, MAX_WINDOW);
-  DM_REQUIRE(bands <= 65535, DM_ERR_BAD_SHAPE, "dm_pair_batch_gather: too many bands");
-  DM_REQUIRE((designed == nullptr) == (region_features == nullptr), DM_ERR_BAD_SHAPE, "dm_pair_batch_gather: designed rows need the region features (and vice versa)");
+             "%s: bad arguments", what);
+  DM_REQUIRE(scale_index >= 0 && scale_index < 4, DM_ERR_BAD_SHAPE, "%s: scale index %d outside 0..3", what, scale_index);
+  DM_REQUIRE(grid >= 0 && (grid == 0 || target % grid == 0), DM_ERR_BAD_SHAPE, "%s: target %d is not a multiple of the token grid %d", what, target, grid);
+  DM_REQUIRE(max_window > 0 && max_window <= MAX_WINDOW, DM_ERR_UNSUPPORTED, "%s: window bound %d outside 1..%d", what, max_window, MAX_WINDOW);
+  DM_REQUIRE(bands <= 65535, DM_ERR_BAD_SHAPE, "%s: too many bands", what);
+  DM_REQUIRE((designed == nullptr) == (region_features == nullptr), DM_ERR_BAD_SHAPE, "%s: designed rows need the region features (and vice versa)", what);
+  DM_REQUIRE(!ORIENT || orient, DM_ERR_BAD_SHAPE, "%s: null orient", what);
   BatchTable bt;
+  bt.orient = orient;
   bt.tile_id = tile_id; bt.inner = inner; bt.obj = obj; bt.region = region_features; bt.designed = designed; bt.err = error_flag;
   bt.n_tiles = n_tiles; bt.scale_index = scale_index; bt.max_window = max_window;
   // <= 32 output pixels per thread while the grid stays small (a batch of 64 samples x 4 bands at target 256: 8 blocks per pair)
@@ -252,17 +290,37 @@ extern "C" int dm_pair_batch_gather(const uint8_t *tiles, int32_t n_tiles, int32
   const size_t lds = (size_t)max_window * max_window;
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   if (grid == 0) {
-    DM_REQUIRE(dtype == DM_F32, DM_ERR_BAD_DTYPE, "dm_pair_batch_gather: planar patches are fp32");
-    launch_pyramid<float, false>(g, lds, s, tiles, bands, H, W, xy, nullptr, target, 1, reinterpret_cast<float *>(out), resize_rule, bt);
+    DM_REQUIRE(dtype == DM_F32, DM_ERR_BAD_DTYPE, "%s: planar patches are fp32", what);
+    launch_pyramid<float, false, ORIENT>(g, lds, s, tiles, bands, H, W, xy, nullptr, target, 1, reinterpret_cast<float *>(out), resize_rule, bt);
   } else if (dtype == DM_BF16) {
-    launch_pyramid<bf16_t, true>(g, lds, s, tiles, bands, H, W, xy, nullptr, target, grid, reinterpret_cast<bf16_t *>(out), resize_rule, bt);
+    launch_pyramid<bf16_t, true, ORIENT>(g, lds, s, tiles, bands, H, W, xy, nullptr, target, grid, reinterpret_cast<bf16_t *>(out), resize_rule, bt);
   } else if (dtype == DM_F32) {
-    launch_pyramid<float, true>(g, lds, s, tiles, bands, H, W, xy, nullptr, target, grid, reinterpret_cast<float *>(out), resize_rule, bt);
+    launch_pyramid<float, true, ORIENT>(g, lds, s, tiles, bands, H, W, xy, nullptr, target, grid, reinterpret_cast<float *>(out), resize_rule, bt);
   } else {
-    DM_REQUIRE(false, DM_ERR_BAD_DTYPE, "dm_pair_batch_gather: bad dtype %d", dtype);
+    DM_REQUIRE(false, DM_ERR_BAD_DTYPE, "%s: bad dtype %d", what, dtype);
   }
-  DM_LAUNCH_CHECK("dm_pair_batch_gather");
+  DM_LAUNCH_CHECK(what);
   return DM_OK;
+}
+}  // namespace
+
+extern "C" int dm_pair_batch_gather(const uint8_t *tiles, int32_t n_tiles, int32_t bands, int32_t H, int32_t W, const int32_t *tile_id,
+                                    const int32_t *xy, const int32_t *inner, const int32_t *obj, int32_t scale_index, int32_t max_window,
+                                    int32_t P, int32_t target, int32_t grid, int32_t resize_rule, void *out, int32_t dtype,
+                                    const float *region_features, float *designed, int32_t *error_flag, void *stream) {
+  return pair_batch_gather<false>("dm_pair_batch_gather", tiles, n_tiles, bands, H, W, tile_id, xy, inner, obj, nullptr, scale_index, max_window, P,
+                                  target, grid, resize_rule, out, dtype, region_features, designed, error_flag, stream);
+}
+
+// The same gather with a dihedral orientation per sample (training augmentation): orient[p] in 0..7 picks the D4
+// element applied to the zero-padded crop before the resize; the designed rows do not depend on it.
+extern "C" int dm_pair_batch_gather_oriented(const uint8_t *tiles, int32_t n_tiles, int32_t bands, int32_t H, int32_t W, const int32_t *tile_id,
+                                             const int32_t *xy, const int32_t *inner, const int32_t *obj, const int32_t *orient,
+                                             int32_t scale_index, int32_t max_window, int32_t P, int32_t target, int32_t grid,
+                                             int32_t resize_rule, void *out, int32_t dtype, const float *region_features, float *designed,
+                                             int32_t *error_flag, void *stream) {
+  return pair_batch_gather<true>("dm_pair_batch_gather_oriented", tiles, n_tiles, bands, H, W, tile_id, xy, inner, obj, orient, scale_index,
+                                 max_window, P, target, grid, resize_rule, out, dtype, region_features, designed, error_flag, stream);
 }
 
 extern "C" int dm_patch_pyramid(const uint8_t *tile, int32_t bands, int32_t H, int32_t W, const int32_t *xy, const int32_t *windows,

@@ -13,7 +13,7 @@ All ids are checked once, on the host, when the dataset is built (`build_host`, 
 from __future__ import annotations
 
 from dataclasses import dataclass
-from typing import Dict, List, Sequence
+from typing import Dict, List, Optional, Sequence
 
 import numpy as np
 import torch
@@ -198,7 +198,8 @@ class EpochTable:
         c = self.cols
         return PairTable(tile_id=c["tile_id"][lo:lo + 2 * b], xy=c["xy"][lo:lo + 2 * b], inner=c["inner"][lo:lo + 2 * b],
                          obj=c["obj"][lo:lo + 2 * b], region=c["region"][lo:lo + 2 * b],
-                         flag=c["flag"][s * self.batch:s * self.batch + b])
+                         flag=c["flag"][s * self.batch:s * self.batch + b],
+                         orient=c["orient"][lo:lo + 2 * b] if "orient" in c else None)
 
     def __iter__(self):
         return (self.step(s) for s in range(len(self)))
@@ -221,6 +222,7 @@ class PairDataset:
         self._cols = {"tile_id": i32(2 * N), "xy": i32(2 * N, 2), "inner": i32(2 * N), "obj": i32(2 * N),
                       "region": torch.empty((2 * N, 15), dtype=torch.float32, device=dev),
                       "flag": torch.empty((N,), dtype=torch.float32, device=dev), "point_id": i32(2 * N)}
+        self._orient = None         # int32 [2N], allocated by the first epoch(augment=...) and kept
 
     @classmethod
     def from_arrays(cls, images: Sequence[Dict], seed: int = 0, n_scales: int = 3, device="cuda:0") -> "PairDataset":
@@ -300,13 +302,23 @@ class PairDataset:
             raise ValueError(f"the dataset was validated for {self.host.n_scales} scales, not {n_scales}")
         return self.host.max_windows[:n_scales]
 
-    def epoch(self, e: int, batch: int) -> EpochTable:
-        """Draw epoch e (one launch, nothing read back); the table's `point_id` column holds the drawn global point ids."""
+    def epoch(self, e: int, batch: int, augment: Optional[str] = None) -> EpochTable:
+        """Draw epoch e (one launch, nothing read back); the table's `point_id` column holds the drawn global point ids.
+        augment: None, "flips" or "d4" -- with one more launch, every pair of the epoch also draws a dihedral orientation keyed by
+        (seed, epoch, pair) ("flips": the four without the transposition), the table's `orient` column, which
+        PairFeed.fill applies to both of the pair's crops.  None: the tables carry orient=None."""
         if batch < 1:
             raise ValueError("batch must be >= 1")
+        if augment is not None and augment not in ops.ORIENT_MASKS:
+            raise ValueError(f"augment must be None, 'flips' or 'd4', got {augment!r}")
         c = self._cols
         with torch.cuda.device(self.device):
             ops.pair_epoch_draw(self.pairs, self.flag, self.poly_off, self.poly_pts, self.pt_tile, self.pt_xy, self.pt_inner, self.pt_obj,
                                 self.pt_region, self.seed, e, batch, c["tile_id"], c["xy"], c["inner"], c["obj"], c["region"], c["flag"],
                                 point_id=c["point_id"])
+            if augment is not None:
+                if self._orient is None:
+                    self._orient = torch.empty((2 * len(self),), dtype=torch.int32, device=self.device)
+                ops.pair_epoch_orient(self.seed, e, len(self), batch, ops.ORIENT_MASKS[augment], self._orient)
+                c = dict(c, orient=self._orient)
         return EpochTable(c, len(self), batch, e)

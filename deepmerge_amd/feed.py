@@ -29,11 +29,16 @@ class PairTable:
     obj: torch.Tensor           # int32 [2B]      object window side
     region: torch.Tensor        # float32 [2B, 15] region attributes (MyUtils1.py:79-114)
     flag: torch.Tensor          # [B]             1 = same object (merge), 0 = different
+    orient: Optional[torch.Tensor] = None   # int32 [2B] dihedral orientation 0..7 of each sample's crop, the same on both sides of a
+    #                                         pair (ops.pair_batch_gather); None: no augmentation
 
     @staticmethod
     def stack(left: "PairTable", right: "PairTable") -> "PairTable":
+        orient = None
+        if left.orient is not None and right.orient is not None:
+            orient = torch.cat((left.orient, right.orient), 0).contiguous()
         return PairTable(*(torch.cat((getattr(left, f), getattr(right, f)), 0).contiguous() for f in ("tile_id", "xy", "inner", "obj", "region")),
-                         flag=left.flag)
+                         flag=left.flag, orient=orient)
 
 
 class PairFeed:
@@ -91,15 +96,15 @@ class PairFeed:
             first = i == 0
             ops.pair_batch_gather(self.tiles, table.tile_id, table.xy, table.inner, table.obj, i, s, self.max_window[i], out,
                                   grid=self.grid if self.rows else 0, resize=self.resize, region_features=table.region if first else None,
-                                  designed=self.dboth if first else None, error_flag=self.error_flag)
+                                  designed=self.dboth if first else None, error_flag=self.error_flag, orient=table.orient)
         self.flag.copy_(table.flag, non_blocking=True)
         left, right = [t[:B] for t in self.both], [t[B:] for t in self.both]
         return left, self.dboth[:B], right, self.dboth[B:], self.flag
 
     def check(self):
         """Host read of the error flag (synchronises: call it where the loss is read, every k steps).  Raises if any sample since the
-        last check had a tile id or window side out of range -- those samples were fed as zeros."""
+        last check had a tile id, window side or orientation out of range -- those samples were fed as zeros."""
         if int(self.error_flag.item()) != 0:
             self.error_flag.zero_()
             raise ValueError("PairFeed: a sample's tile id or window side was out of range (tile_id outside [0, T), or a window side "
-                             "outside 1..max_window); it was fed as zeros")
+                             "outside 1..max_window), or its orientation was outside 0..7; it was fed as zeros")

@@ -824,13 +824,15 @@ def cat_batch(a, b):
 def pair_batch_gather(tiles: torch.Tensor, tile_id: Optional[torch.Tensor], xy: torch.Tensor, inner: torch.Tensor, obj: torch.Tensor,
                       scale_index: int, target: int, max_window: int, out: torch.Tensor, grid: int = 0, resize: str = "opencv",
                       region_features: Optional[torch.Tensor] = None, designed: Optional[torch.Tensor] = None,
-                      error_flag: Optional[torch.Tensor] = None) -> None:
+                      error_flag: Optional[torch.Tensor] = None, orient: Optional[torch.Tensor] = None) -> None:
     """One scale of a training batch, gathered into `out` from resident tiles and a device sample table (dm_pair_batch_gather):
     no host-side window arithmetic, no synchronisation.  tiles uint8 [T, bands, H, W]; tile_id / inner / obj int32 [P]; xy int32
     [P, 2]; out: float32 [P, bands, target, target] (grid = 0) or the patch-embed rows [P * grid^2, bands * (target / grid)^2]
     (bf16 / fp32) -- e.g. the trainer's static step inputs.  region_features [P, 15] + designed [P, 1, 19]: also writes the
-    designed-feature rows.  error_flag int32 [1]: set when a sample's tile id / window is out of range (read it with the loss)."""
-    _need_cuda(tiles, tile_id, xy, inner, obj, out, region_features, designed, error_flag)
+    designed-feature rows.  error_flag int32 [1]: set when a sample's tile id / window is out of range (read it with the loss).
+    orient int32 [P] in 0..7: the dihedral orientation of each sample's crop (dm_pair_batch_gather_oriented; bit 1 mirrors the rows,
+    bit 0 the columns, then bit 2 transposes; a value outside 0..7 is fed as zeros and flagged).  None: the plain gather."""
+    _need_cuda(tiles, tile_id, xy, inner, obj, out, region_features, designed, error_flag, orient)
     if tiles.dtype != torch.uint8 or tiles.dim() != 4 or not tiles.is_contiguous():
         raise ValueError("tiles must be a contiguous uint8 [T, bands, H, W] tensor")
     for name, t in (("tile_id", tile_id), ("xy", xy), ("inner", inner), ("obj", obj), ("error_flag", error_flag)):
@@ -845,9 +847,32 @@ def pair_batch_gather(tiles: torch.Tensor, tile_id: Optional[torch.Tensor], xy: 
     if designed is not None and (designed.dtype != torch.float32 or designed.numel() != P * 19 or not designed.is_contiguous()
                                  or region_features.dtype != torch.float32 or region_features.numel() != P * 15 or not region_features.is_contiguous()):
         raise ValueError("region_features must be contiguous float32 [P, 15] and designed contiguous float32 [P, 1, 19]")
+    if orient is not None:
+        if orient.dtype != torch.int32 or not orient.is_contiguous() or tuple(orient.shape) != (P,):
+            raise ValueError(f"orient must be a contiguous int32 [{P}] tensor, got {orient.dtype} {tuple(orient.shape)}")
+        check(_lib.lib().dm_pair_batch_gather_oriented(tiles.data_ptr(), T, bands, H, W, _ptr(tile_id), xy.data_ptr(), inner.data_ptr(),
+                                                       obj.data_ptr(), orient.data_ptr(), scale_index, max_window, P, target, grid,
+                                                       _resize_rule(resize), out.data_ptr(), _dt(out), _ptr(region_features), _ptr(designed),
+                                                       _ptr(error_flag), _stream()), "dm_pair_batch_gather_oriented")
+        return
     check(_lib.lib().dm_pair_batch_gather(tiles.data_ptr(), T, bands, H, W, _ptr(tile_id), xy.data_ptr(), inner.data_ptr(), obj.data_ptr(),
                                           scale_index, max_window, P, target, grid, _resize_rule(resize), out.data_ptr(), _dt(out),
                                           _ptr(region_features), _ptr(designed), _ptr(error_flag), _stream()), "dm_pair_batch_gather")
+
+
+ORIENT_MASKS = {"flips": 3, "d4": 7}      # augment name -> mask of the orientation draw (3: no transposition)
+
+
+def pair_epoch_orient(seed: int, epoch: int, n_pairs: int, batch: int, mask: int, out: torch.Tensor) -> None:
+    """One epoch's orientation column in one launch (dm_pair_epoch_orient): the pair at shuffled position j gets
+    philox((perm(j), epoch, 3, 0))[0] & mask (7: "d4", 3: "flips"), written to both of its rows in the blocked layout of
+    `pair_epoch_draw`.  out: int32 [2 n_pairs] on the device."""
+    _need_cuda(out)
+    if out.dtype != torch.int32 or not out.is_contiguous() or out.numel() != 2 * int(n_pairs):
+        raise ValueError(f"pair_epoch_orient: out must be a contiguous int32 tensor of {2 * int(n_pairs)} elements, got {out.dtype} {tuple(out.shape)}")
+    with torch.cuda.device(out.device):
+        check(_lib.lib().dm_pair_epoch_orient(int(seed) & 0xFFFFFFFFFFFFFFFF, int(epoch), int(n_pairs), int(batch), int(mask), out.data_ptr(),
+                                              _stream()), "dm_pair_epoch_orient")
 
 
 def pair_epoch_draw(pairs: torch.Tensor, pair_flag: torch.Tensor, poly_off: torch.Tensor, poly_pts: torch.Tensor, pt_tile: torch.Tensor,

@@ -47,7 +47,7 @@ int dm_abi_version(void);   /* 2: dm_patch_pyramid / dm_patch_pyramid_cols take 
                              * 4: DmGemmArgs.k_fold / a_fold / b_fold, dm_split_bf16_planes (round 4); 5: dm_pair_batch_gather (round 5); 6: dm_gemm_grouped (round 5);
                              * 7: dm_gemm_grouped(args, n, stream) without a group workspace, its workspace query removed;
                              * additive in 6: dm_pairwise_distance, dm_pair_epoch_draw, dm_contrastive_terms, dm_pair_eval_summary;
-                             * additive in 7: dm_region_merge_cost, dm_pixel_regions */
+                             * additive in 7: dm_region_merge_cost, dm_pixel_regions, dm_pair_batch_gather_oriented, dm_pair_epoch_orient */
 const char *dm_last_error(void);
 /* Name of the code object architecture the library was built for ("gfx950"). */
 const char *dm_arch(void);
@@ -419,6 +419,18 @@ int dm_pair_batch_gather(const uint8_t *tiles, int32_t n_tiles, int32_t bands, i
                          const int32_t *xy, const int32_t *inner, const int32_t *obj, int32_t scale_index, int32_t max_window,
                          int32_t P, int32_t target, int32_t grid, int32_t resize_rule, void *out, int32_t dtype,
                          const float *region_features, float *designed, int32_t *error_flag, void *stream);
+/* Dihedral augmentation (additive in ABI 7): dm_pair_batch_gather with one orientation per sample, orient int32 [P] in 0..7 (not
+ * NULL; both sides of a pair carry the same value).  With crop the zero-padded L x L window exactly as above,
+ *   crop' = crop;  bit 1 set: crop' = crop'[::-1, :];  bit 0 set: crop' = crop'[:, ::-1];  bit 2 set: crop' = crop'.T
+ * i.e. crop'[j][i] = crop[fy(a)][fx(b)] with (a, b) = (i, j) when bit 2 is set and (j, i) otherwise, fy mirroring (L - 1 - .) when
+ * bit 1 is set and fx when bit 0 is set.  The resize (either rule) and / 255 then run on crop' unchanged: `out` is what
+ * dm_pair_batch_gather writes for a tile whose window content is crop'.  The designed rows are not touched by the orientation (the 15
+ * attributes are D4-invariant, the scale factors depend on window sides only); orient[p] == 0 is dm_pair_batch_gather's result.  A
+ * sample whose orient is outside 0..7 is treated like a bad tile id: zeros, error_flag[0] |= 1, its designed row still written. */
+int dm_pair_batch_gather_oriented(const uint8_t *tiles, int32_t n_tiles, int32_t bands, int32_t H, int32_t W, const int32_t *tile_id,
+                                  const int32_t *xy, const int32_t *inner, const int32_t *obj, const int32_t *orient, int32_t scale_index,
+                                  int32_t max_window, int32_t P, int32_t target, int32_t grid, int32_t resize_rule, void *out,
+                                  int32_t dtype, const float *region_features, float *designed, int32_t *error_flag, void *stream);
 
 /* ---- per-epoch pair draw: the epoch's whole sample table in one launch (additive in ABI 6) ---------------------------------
  * Replaces the dataset rebuild of every epoch (MyUtils1.py:275-293: for each pair of the positive / negative lists, one sample
@@ -444,6 +456,13 @@ typedef struct {
   int32_t n_pairs, n_poly, n_poly_pts, n_pts, epoch, batch;
 } DmPairDraw;
 int dm_pair_epoch_draw(const DmPairDraw *args, void *stream);
+/* The epoch's orientation column for dm_pair_batch_gather_oriented (additive in ABI 7), in the same blocked layout: the pair at
+ * shuffled position j, src = perm(j), gets philox4x32_10((src, epoch, 3, 0), key)[0] & mask -- key and perm as in
+ * dm_pair_epoch_draw, counter word 3 a stream neither the draw (1) nor the shuffle (2) uses -- written to both of its rows,
+ * row_l and row_l + b_s.  mask: 7 (the dihedral group D4) or 3 (flips only, no transposition).  Keyed by (seed, epoch, pair): a
+ * resumed run sees the same orientations.  orient int32 [2 n_pairs].  Refused before any launch: another mask, n_pairs outside
+ * 1 .. 2^30, batch < 1, epoch < 0, a null pointer. */
+int dm_pair_epoch_orient(uint64_t seed, int32_t epoch, int32_t n_pairs, int32_t batch, int32_t mask, int32_t *orient, void *stream);
 
 /* ---- held-out pair evaluation (additive in ABI 6; deepmerge_amd/evaluate.py) ---------------------------
  * Per-pair contrastive terms -- the per-pair form of the reference's contrastive loss (Losses.py:34-38, before its mean):

@@ -3,7 +3,7 @@
 epoch, FRESH pairs every step generated on the device -- patch pyramids cut from resident uint8 tiles by the sync-free feed
 (deepmerge_amd/feed.py: one dm_pair_batch_gather launch per scale straight into the captured step's inputs), positives = two
 jittered windows of the same spot, negatives = spots of different tiles -- through PairTrainer (hipGraph replay).  Prints a loss curve; BASELINE configs[4] shape by default (depth [6,4,2], 4 scales x 4 ch,
-120 pairs per GPU).        python tools/train_synth.py [--epochs 3] [--steps-per-epoch 20] [--pairs 120] [--depth 6,4,2]
+120 pairs per GPU).        python tools/train_synth.py [--epochs 3] [--steps-per-epoch 20] [--pairs 120] [--depth 6,4,2] [--augment d4]
 """
 import argparse
 import json
@@ -47,12 +47,18 @@ def draw_pairs(n_tiles, size, B, g):
     return tl, tr, xy_l, xy_r, inner, obj, feats_l, feats_r, flag
 
 
-def pair_table(draw):
-    """deepmerge_amd.feed.PairTable of a draw: [left rows; right rows], int32 columns -- device ops only, nothing read back."""
+def pair_table(draw, orient=None):
+    """deepmerge_amd.feed.PairTable of a draw: [left rows; right rows], int32 columns -- device ops only, nothing read back.
+    orient: int32 [B] dihedral orientations, one per pair (both sides get it), or None."""
     tl, tr, xy_l, xy_r, inner, obj, feats_l, feats_r, flag = draw
     i32 = lambda a, b: torch.cat((a, b), 0).to(torch.int32)
     return PairTable(tile_id=i32(tl, tr), xy=i32(xy_l, xy_r), inner=i32(inner, inner), obj=i32(obj, obj),
-                     region=torch.cat((feats_l, feats_r), 0), flag=flag)
+                     region=torch.cat((feats_l, feats_r), 0), flag=flag, orient=None if orient is None else i32(orient, orient))
+
+
+def draw_orient(B, augment, g):
+    """One orientation per pair from a generator of its own, so that the data stream is the same with and without --augment."""
+    return torch.randint(0, {"flips": 4, "d4": 8}[augment], (B,), generator=g, device=DEV)
 
 
 MAX_WINDOW = [64, 112, 160, 208]       # bounds of (inner, obj, obj + interval, obj + 2 interval) for the ranges drawn above
@@ -93,12 +99,17 @@ def main():  # noqa: C901
     ap.add_argument("--feed", type=str, default="rows", choices=["rows", "patches", "looped"],
                     help="rows: deepmerge_amd.feed.PairFeed writing the patch-embed operand rows (default); patches: the same feed writing "
                          "fp32 patch tensors; looped: the per-tile Python loop of rounds 1-4")
+    ap.add_argument("--augment", type=str, default=None, choices=["flips", "d4"],
+                    help="feed every pair at a random dihedral orientation (both sides alike; rows / patches feeds only)")
     ap.add_argument("--loss-every", type=int, default=0, help="read the loss back every k steps (0 = once per epoch)")
     args = ap.parse_args()
+    if args.augment and args.feed == "looped":
+        ap.error("--augment needs the sync-free feed (--feed rows or patches)")
     scales, bands = [32, 64, 128, 256], 4
     depth = [int(d) for d in args.depth.split(",")]
     ms = tuple(int(m) for m in args.milestones.split(","))
     g = torch.Generator(device=DEV); g.manual_seed(0)
+    g_orient = torch.Generator(device=DEV); g_orient.manual_seed(1)
     torch.manual_seed(0)
     tiles = smooth_tiles(6, bands, 1024, g)
     net = ShfitScaleFormer_v3(cube_size=[8, 8], input_image_scales=list(scales), depth=depth, in_c=bands, numerics=args.numerics).to(DEV)
@@ -120,7 +131,8 @@ def main():  # noqa: C901
             if feed is None:
                 batch = make_pairs_looped(tiles, args.pairs, scales, g)
             else:
-                batch = feed.fill(pair_table(draw_pairs(tiles.shape[0], tiles.shape[2], args.pairs, g)))
+                orient = draw_orient(args.pairs, args.augment, g_orient) if args.augment else None
+                batch = feed.fill(pair_table(draw_pairs(tiles.shape[0], tiles.shape[2], args.pairs, g), orient))
             tot += tr.step(*batch, lr=lr)                    # (device-side sum: the reference's per-step .item(), Train_SMT.py:301, is a sync)
             if args.loss_every and (k + 1) % args.loss_every == 0:
                 float(tot)
@@ -131,7 +143,7 @@ def main():  # noqa: C901
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     n = args.epochs * args.steps_per_epoch
-    print(json.dumps({"tool": "train_synth", "feed": args.feed, "numerics": args.numerics, "depth": depth, "pairs_per_step": args.pairs, "steps": n,
+    print(json.dumps({"tool": "train_synth", "feed": args.feed, "augment": args.augment, "numerics": args.numerics, "depth": depth, "pairs_per_step": args.pairs, "steps": n,
                       "loss_curve": curve, "hip_graph": tr.graph_error is None, "pairs_per_s_incl_data_generation": round(n * args.pairs / dt, 1),
                       "pairs_per_s_steady_incl_data_generation": None if t_warm is None else round((n - WARM) * args.pairs / (t0 + dt - t_warm), 1),
                       "steady_note": f"after the first {WARM} steps (eager warm-up + hipGraph capture)"}))
