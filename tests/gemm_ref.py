@@ -3,7 +3,8 @@
 Shared by tests/test_gemm_host.py (no GPU: pins the spec, the exactness of the data and the constants of the bounds) and
 tests/test_gpu_gemm_epilogues.py (every kernel family's epilogue against the spec).  numpy / torch float64 only.
 The weight gradient (DM_TN) has its own section below FAMILIES: families and shapes, the library's split rules restated, data, spec and
-frames of tests/test_gpu_gemm_wgrad.py.
+frames of tests/test_gpu_gemm_wgrad.py.  The K loop of the forward / dgrad products (NT, NN) has the last section: contraction lengths per family,
+plane-pair products and their frames, the tile walk -- the case table of tests/test_gpu_gemm_mainloop.py.
 
 Spec (the order of dm_gemm_emit, deepmerge_amd/csrc/dm_gemm_common.h): v = acc + bias; GELU (the pre-activation v is saved first), GELU_GRAD (gelu'(v)
 is saved), DGELU (v *= gelu'(aux)) or MUL (v *= aux); + residual; + old C; rounding to c_dtype (DM_BF16_PAIR: hi = bf16(v),
@@ -70,7 +71,7 @@ SPECIALISED_KEYS = (0, 1 | (1 << 3), 1 << 3, (1 << 1) | (1 << 3), 1 << 4, 2 << 1
 # nearest shape that does is taken and the reason stands next to it.  `wave` = (rows, columns) of a wave's block, `tile` = (rows, columns)
 # of the workgroup's tile, `bk` = the K step.  `env`: the switches read_switches (deepmerge_amd/csrc/dm_gemm.hip) reads on every call; a key set to
 # None is removed from the environment.  `codes`: the `_t<code>` of the family's profiler row (prof_family_code), () = no row at all.
-_OFF = {"DM_GEMM_W4": "0", "DM_GEMM_Q4": "0", "DM_GEMM_RING": "0", "DM_GEMM_256": "0", "DM_GEMM_FORCE_TILE": "0", "DM_GEMM_RING_WM": None}
+_OFF = {"DM_GEMM_W4": "0", "DM_GEMM_Q4": "0", "DM_GEMM_T96": "0", "DM_GEMM_RING": "0", "DM_GEMM_256": "0", "DM_GEMM_FORCE_TILE": "0", "DM_GEMM_RING_WM": None}
 _Q4_SKIPS = {
     "bias_res_acc_f32": "dm_gemm_q4.hip dm_gemm_q4_plan: `if (!dm_epi_key_specialised(dm_epi_lean_key(p, 64))) return false` (residual + accumulate has no straight-line instance)",
     "gelu_save_f32": "dm_gemm_q4.hip dm_gemm_q4_plan: `if (!dm_epi_key_specialised(...)) return false` (fp32 aux written)",
@@ -78,6 +79,21 @@ _Q4_SKIPS = {
     "pair_gelu": "dm_gemm_q4.hip dm_gemm_q4_plan: `... || p.c_dtype == DM_BF16_PAIR) return false`",
     "grouped41": "dm_gemm_q4.hip dm_gemm_q4_plan: `if (!dm_epi_key_specialised(...)) return false` (grouped rows: dm_epi_lean_key is -1)",
     "grouped41_gelugrad": "dm_gemm_q4.hip dm_gemm_q4_plan: `if (!dm_epi_key_specialised(...)) return false` (grouped rows: dm_epi_lean_key is -1)",
+}
+_T96_EPI = "dm_gemm_t96.hip dm_gemm_t96_plan: `if (p.epilogue != DM_EPI_NONE || p.accumulate) return false`"
+_T96_KEY = "dm_gemm_t96.hip dm_gemm_t96_plan: `if (!(key == 0 || key == (1 << 3) || key == (1 | (1 << 3)))) return false`"
+_T96_SKIPS = {
+    "acc_f32": _T96_EPI + " (accumulate)",
+    "bias_res_acc_f32": _T96_EPI + " (accumulate)",
+    "gelu_bf16_nosave": _T96_EPI + " (GELU; its lean key is 0)",
+    "gelu_save_bf16": _T96_EPI + " (GELU)",
+    "gelugrad_save_bf16": _T96_EPI + " (GELU_GRAD)",
+    "gelu_save_f32": _T96_EPI + " (GELU)",
+    "mul_bf16": _T96_EPI + " (MUL)",
+    "dgelu_f32_res": _T96_EPI + " (DGELU)",
+    "pair_gelu": "dm_gemm_t96.hip dm_gemm_t96_plan: `... || p.k_fold > 0 || p.c_dtype == DM_BF16_PAIR) return false`",
+    "grouped41": _T96_KEY + " (grouped rows: dm_epi_lean_key is -1)",
+    "grouped41_gelugrad": _T96_EPI + " (GELU_GRAD; grouped rows: dm_epi_lean_key is -1)",
 }
 _PAIR_F32 = {"pair_gelu": "dm_gemm.hip gemm_prepare: `a plane-pair result needs an NT / NN bf16 product ...` (ab_dtype == DM_BF16)"}
 _GENERIC_SKIPS = {name: "dm_gemm.hip gemm_generic: `a->ab_dtype == DM_F32 && a->c_dtype == DM_F32 && (a->aux == nullptr || a->aux_dtype == DM_F32)` (the generic path is fp32-only)"
@@ -109,6 +125,11 @@ FAMILIES = {
     # full, 320 .. 383 past M; only the straight-line epilogues
     "q4": dict(ab=BF16, shape=(320, 200, 192), layouts=("NT", "NN"), tile=(128, 128), wave=(64, 64), bk=64, codes=(1284,), fast=True,
                env=dict(_OFF, DM_GEMM_Q4="2"), skips=_Q4_SKIPS),
+    # one-round DMA-ring tiles, 128 x 96, a wave owns 64 x 48 (STAGES = 4 K tiles in LDS).  dm_gemm_t96_plan: `if (p.M % 64 != 0) return false` -> the
+    # proposal's M = 320 = 2 * 128 + 64: rows 256 .. 319 full, 320 .. 383 past M; N = 200 = 2 * 96 + 8: three column tiles, the tail inside the
+    # first wave's 48 columns.  Only none_f32, none_bf16 and bias_res_f32 have an instance (lean keys 1 << 3, 0 and 1 | 1 << 3)
+    "t96": dict(ab=BF16, shape=(320, 200, 192), layouts=("NT", "NN"), tile=(128, 96), wave=(64, 48), bk=64, codes=(12896,), fast=True,
+                env=dict(_OFF, DM_GEMM_T96="2"), skips=_T96_SKIPS),
     # 4-wave persistent kernel, 256 x 192 tiles, a wave pair owns 128 rows x 192 columns.  dm_gemm_w4_plan: `k_eff % (2 * bk_eff) != 0 || p.N % TN != 0`
     # return 0 -> N = 384 (two tiles, no N tail exists for this family), K = 256 (four K steps, the smallest even count above two)
     "w4": dict(ab=BF16, shape=(328, 384, 256), layouts=("NT", "NN"), tile=(256, 192), wave=(128, 192), bk=64, codes=(1924,), fast=True,
@@ -810,3 +831,214 @@ def bounds(cfg, ref, acc, fast, consts=None):
 def family_cases(family):
     """(layout, config name) of everything a family runs."""
     return [(lay, n) for lay in FAMILIES[family]["layouts"] for n in family_configs(family)]
+
+
+# ---- the main loop of the forward / dgrad products (NT, NN): K-step counts and plane pairs ------------------------------------------------
+# tests/test_gpu_gemm_mainloop.py runs every family of FAMILIES at M, N of its shape over a list of contraction lengths (ML_K), the families
+# with a FOLD instance over hi / lo plane pairs with one, two and three K tiles per segment (ML_FOLD), and once on a tile walk of eleven row
+# tiles (ML_WALK).  Everything is EXACT: the data of operands() / wg_data() sums exactly in float32 in any order (tests/test_gemm_host.py),
+# so C is compared bit for bit.
+ML_K = {
+    # one to five K steps of 64: touch_at = max(0, nk - 4) of gemm_kernel on both sides of nk - 4 (bias_res_f32 has the residual that arms it);
+    # an 8-wide K tail alone (8), behind one (72) and behind two (136) full steps
+    "t64": (8, 64, 72, 128, 136, 192, 256, 320),
+    "t128": (8, 64, 72, 128, 136, 192, 256, 320),
+    # fp32 operands: the K step is 32, the tail 4 wide
+    "f32_t64": (4, 32, 36, 64, 96, 128, 160),
+    "f32_t128": (4, 32, 36, 64, 96, 128, 160),
+    # dm_gemm_ring.hip: two A buffers, one B buffer, the `more` branch -> 1 .. 5 steps (depth 2 + 3)
+    "ring8": (64, 128, 192, 256, 320),
+    "ring4": (64, 128, 192, 256, 320),
+    # dm_gemm_q4.hip: "one LDS stage" -> depth 1
+    "q4": (64, 128, 192, 256, 320),
+    # dm_gemm256.hip: `LDS256 = 2 * BUF_BYTES`: two K-tile buffers, the prologue stages tile 0 and most of tile 1 -> depth 2
+    "p256": (64, 128, 192, 256, 320),
+    # dm_gemm_t96.hip: `STAGES = 4` -> 1 .. STAGES + 2 steps
+    "t96": (64, 128, 192, 256, 320, 384),
+    # dm_gemm_w4.hip: `LDS_BYTES = 2 * BUF_BYTES + ...`: two buffers; dm_gemm_w4_plan: `k_eff % (2 * bk_eff) != 0 ... return 0` -> K % 128 == 0:
+    # 2, 4, 6, 8 steps
+    "w4": (128, 256, 384, 512),
+    # plan_fwd_split: 1536 -> two slices of 768; 1600 -> 832 + 768; 2048 -> four slices of 512
+    "kslices": (1536, 1600, 2048),
+    # sgemm_small_kernel: four waves share K in pieces of 32: one wave with one product, one wave short, two waves (32 + 1)
+    "generic": (1, 19, 33),
+}
+ML_DEPTH = {"t64": 2, "t128": 2, "f32_t64": 2, "f32_t128": 2, "ring8": 2, "ring4": 2, "q4": 1, "p256": 2, "t96": 4, "w4": 2}   # K tiles in flight / in LDS
+# (family, K) a plan refuses, with the refusing line: none of the listed K is refused (tests/test_gemm_host.py restates each plan's K rule)
+ML_K_SKIPS = {}
+
+# plane pairs: k_fold = 64, 128, 192 -> one, two, three K tiles per segment, the seams at K tiles 1|2, 2|4, 3|6: both buffer parities
+# (4-wave kernel: 2, 4, 6 steps of 32 positions per segment).  kslices: k_fold = 512 -> K = 1536, slices [0, 768) and [768, 1536): the seam at
+# 512 inside slice 0, the one at 1024 inside slice 1; k_fold = 576 -> K = 1728, slices [0, 896) and [896, 1728), seams at 576 and 1152
+ML_FOLD = {"t64": (64, 128, 192), "t128": (64, 128, 192), "ring8": (64, 128, 192), "ring4": (64, 128, 192), "p256": (64, 128, 192),
+           "w4": (64, 128, 192), "kslices": (512, 576)}
+# The families without a FOLD instance.  "dm_gemm": the call is refused before any launch (status 3 of the child).  "plan": the family's plan
+# returns false and dm_gemm_plan goes on to the register-staged tiles, which do have one -- dm_gemm itself does not refuse; the child
+# requires the row of another family and then ends with status 3 like a refusal.
+ML_FOLD_REFUSED = {
+    "q4": ("plan", "dm_gemm_q4.hip dm_gemm_q4_plan: `if (p.K % dmq4::BK != 0 || p.N % 8 != 0 || p.k_fold > 0 || p.c_dtype == DM_BF16_PAIR) return false`"),
+    "t96": ("plan", "dm_gemm_t96.hip dm_gemm_t96_plan: `if (p.K % dmt96::BK != 0 || p.N % 8 != 0 || p.k_fold > 0 || p.c_dtype == DM_BF16_PAIR) return false`"),
+    "f32_t64": ("dm_gemm", "dm_gemm.hip k_fold_fault: `if (!(a.ab_dtype == DM_BF16 && a.K == 3 * a.k_fold && a.k_fold % 64 == 0)) return 1`"),
+    "f32_t128": ("dm_gemm", "dm_gemm.hip k_fold_fault: `if (!(a.ab_dtype == DM_BF16 && a.K == 3 * a.k_fold && a.k_fold % 64 == 0)) return 1`"),
+    "generic": ("dm_gemm", "dm_gemm.hip k_fold_fault: `if (!(a.ab_dtype == DM_BF16 && a.K == 3 * a.k_fold && a.k_fold % 64 == 0)) return 1` (gemm_prepare asks it before the generic path is chosen)"),
+}
+ML_REFUSED_K_FOLD = 64
+PLACEMENTS = ("dense", "far")
+FAR_GAP = 8 * 37        # elements of NaN between the planes of a "far" pair: a weight's mirror pair (Planes.t.stride(0) is not rows * cols)
+
+PAIR_NONE = dict(id=15, name="pair_none", epi="none", bias=False, res=False, aux=None, c=PAIR, acc=False, grouped=False)   # lean key 1 << 8
+ML_CONFIG = {n: CONFIG[n] for n in ("none_f32", "none_bf16", "bias_res_f32")}
+ML_CONFIG["pair_none"] = PAIR_NONE
+ML_PLAIN_CONFIGS = ("none_f32", "none_bf16", "bias_res_f32")
+ML_FOLD_CONFIGS = ("none_f32", "none_bf16", "bias_res_f32", "pair_none")     # gemm_prepare allows a pair result for every NT / NN bf16 product
+
+
+def ml_configs(family, fold):
+    """The configurations a family runs in the main-loop tests (the generic path is fp32 throughout: no none_bf16)."""
+    names = ML_FOLD_CONFIGS if fold else ML_PLAIN_CONFIGS
+    return tuple(n for n in names if n not in FAMILIES[family]["skips"] or n == "pair_none")
+
+
+def ml_cases(family):
+    """Every product of a family, in the order the child runs them: dict(kind = "plain" | "fold", layout, K (plain) or k_fold, placement
+    (None for plain), config)."""
+    f = FAMILIES[family]
+    out = []
+    for K in ML_K[family]:
+        if (family, K) in ML_K_SKIPS:
+            continue
+        for lay in f["layouts"]:
+            for name in ml_configs(family, False):
+                out.append(dict(kind="plain", layout=lay, K=K, placement=None, config=name))
+    for kf in ML_FOLD.get(family, ()):
+        for lay in f["layouts"]:
+            for name in ml_configs(family, True):
+                for pl in PLACEMENTS:
+                    out.append(dict(kind="fold", layout=lay, K=kf, placement=pl, config=name))
+    return out
+
+
+def ml_slices(family, K, M=None, N=None):
+    """The K slices of a product of the kslices family: [(k0, k1)]; [(0, K)] for every other family.  M, N: the family's unless given (the walk)."""
+    if family != "kslices":
+        return [(0, K)]
+    if M is None:
+        M, N, _ = FAMILIES[family]["shape"]
+    split, tile = plan_fwd_split(M, N, K)
+    return k_slices(K, *_slices(K, split, 64))
+
+
+def ml_data(M, N, K, fold=False):
+    """Plain: operands(M, N, K) as it is.  Plane pairs (K = k_fold): as wg_data -- a_hi, a_lo [M, K], b_hi, b_lo [N, K] with hi = +-i, i in {1, 2}
+    and lo = +-j / 1024, j in 0 .. 3, the lo planes of A and B drawn independently; acc = Ah Bh^T + Ah Bl^T + Al Bh^T (the order of the
+    segments: left operand hi, hi, lo, right operand hi, lo, hi).  The omitted Al Bl^T is a multiple of 2^-20, off the 2^-10 grid of the spec.
+    bias [N] and res [M, N] on the 2^-6 grid.  The planes go to the kernel as given (ops.Planes): they are not the split of anything."""
+    if not fold:
+        return operands(M, N, K)
+    key = (M, N, K)
+    if key in _ML_DATA:
+        return _ML_DATA[key]
+    rng = np.random.default_rng(11 + 1000003 * M + 1009 * N + K)
+    d = {}
+    for nm, rows in (("a", M), ("b", N)):
+        sign = rng.integers(0, 2, size=(rows, K)).astype(np.float64) * 2 - 1
+        d[nm + "_hi"] = sign * rng.integers(1, 3, size=(rows, K)).astype(np.float64)
+        d[nm + "_lo"] = sign * rng.integers(0, 4, size=(rows, K)).astype(np.float64) / 1024.0
+    d["acc"] = d["a_hi"] @ d["b_hi"].T + d["a_hi"] @ d["b_lo"].T + d["a_lo"] @ d["b_hi"].T
+    d["bias"] = rng.integers(-128, 129, size=(N,)).astype(np.float64) / 64.0
+    d["res"] = rng.integers(-128, 129, size=(M, N)).astype(np.float64) / 64.0
+    for v in d.values():
+        v.setflags(write=False)
+    _ML_DATA[key] = d
+    return d
+
+
+_ML_DATA = {}
+FOLD_SEGMENTS = (("a_hi", "b_hi"), ("a_hi", "b_lo"), ("a_lo", "b_hi"))      # a_fold = (0, 0, plane), b_fold = (0, plane, 0): ops._gemm_args
+
+
+def ml_case(cfg, d):
+    """A main-loop configuration with the operand values it reads (the argument of epilogue_ref)."""
+    c = dict(cfg)
+    c["bias_v"] = d["bias"] if cfg["bias"] else None
+    c["res_v"] = d["res"] if cfg["res"] else None
+    c["old_c"] = None
+    c["aux_v"] = None
+    return c
+
+
+def ml_ref(d, cfg):
+    """The float64 spec of a main-loop product: epilogue_ref on the data's accumulator."""
+    return epilogue_ref(d["acc"], ml_case(cfg, d))
+
+
+def ml_terms(d, fold):
+    """The contraction as a list of terms, in the kernel's K order: [(A [M, k], B [N, k])] -- one term for a plain product, three for a pair."""
+    if not fold:
+        return [(d["a"], d["b"])]
+    return [(d[a], d[b]) for a, b in FOLD_SEGMENTS]
+
+
+def pair_frame(rows, cols, placement):
+    """A plane pair [2, rows, cols] inside one flat bf16 allocation, VIEW_OFFSET elements in, NaN before, behind and (far) between the planes:
+    dict(elems, ld, idx [2, rows, cols], plane).  dense: the planes rows * cols apart; far: rows * cols + FAR_GAP."""
+    plane = rows * cols + (FAR_GAP if placement == "far" else 0)
+    r = np.arange(rows, dtype=np.int64)[:, None]
+    c = np.arange(cols, dtype=np.int64)[None, :]
+    idx = VIEW_OFFSET + np.stack([r * cols + c, plane + r * cols + c])
+    return dict(elems=VIEW_OFFSET + plane + rows * cols + OPERAND_PAD_ROWS * cols, ld=cols, idx=idx, plane=plane)
+
+
+# The tile walk (dm_xcd_remap, bands of group_m = 8 row tiles): one K step, tiles_m = group_m + 3 = 11 with a ragged last tile (a last band
+# of three), three column tiles (the last 8 wide), none_f32.  The grid has exactly tiles_m * tiles_n workgroups, so a tile visited twice
+# leaves another unvisited: C is prefilled with NaN, and every element must be the spec's.  M = 11 * tile - 56; where the plan asks for
+# M % 64 == 0 (q4, t96) 11 * tile - 64.  Exceptions, each with its reason:
+#   f32_t64   gemm_prepare sends fp32 products with fewer than 16 tiles of 128 x 128 to the generic path: 6 x 2 = 12 at N = 136 -> N = 264
+#             (five column tiles of 64), 6 x 3 = 18
+#   kslices   a one-step product has no slices (plan_fwd_split: K >= 1536): K = 1536, two slices of twelve steps
+#   generic   16 x 16 outputs on a 2-D grid (no remap, no bands); K = 19
+#   w4        persistent: its own case, the shape depends on the CU count (ml_walk_w4)
+GROUP_M = 8             # dm_gemm.hip gemm_plan: `p.group_m = dm_gemm_tuning().group_m >= 0 ? ... : 8`
+
+
+def _walk(family):
+    f = FAMILIES[family]
+    tm, tn = f["tile"]
+    M = (GROUP_M + 3) * tm - (64 if family in ("q4", "t96") else 56)
+    N = 2 * tn + 8
+    K = f["bk"]
+    if family == "f32_t64":
+        N = 4 * tn + 8
+    if family == "kslices":
+        K = 1536
+    if family == "generic":
+        M, K = (GROUP_M + 3) * tm - 5, 19
+    return (M, N, K)
+
+
+ML_WALK = {fam: _walk(fam) for fam in FAMILIES if fam != "w4"}
+ML_WALK_W4_K = (128, 256)       # two and four K steps: the persistent pipeline crosses a tile boundary after two steps and after four
+
+
+def ml_walk_w4(cus):
+    """(M, N) of the 4-wave kernel's walk: cus + cus // 2 + 1 row tiles of 256 (the last ragged) in one column tile of 192, on min(tiles, cus)
+    persistent workgroups -> workgroups run two tiles or one."""
+    return 256 * (cus + cus // 2 + 1) - 56, 192
+
+
+def ml_walk_data(M, N, K):
+    """a [M, K], b [N, K] and acc of a walk: the integers of operands() without the M x N epilogue operands (the 4-wave walk is 98 504 rows)."""
+    key = (M, N, K)
+    if key not in _ML_WALK_DATA:
+        rng = np.random.default_rng(5 + 1000003 * M + 1009 * N + K)
+        a = rng.integers(-2, 3, size=(M, K)).astype(np.float64) * 2.0 ** -k_shift(K)
+        b = rng.integers(-2, 3, size=(N, K)).astype(np.float64)
+        d = dict(a=a, b=b, acc=a @ b.T)
+        for v in d.values():
+            v.setflags(write=False)
+        _ML_WALK_DATA.clear()           # one at a time: the large ones are used once
+        _ML_WALK_DATA[key] = d
+    return _ML_WALK_DATA[key]
+
+
+_ML_WALK_DATA = {}

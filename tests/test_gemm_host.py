@@ -9,6 +9,10 @@
   * the DM_GEMM_* switches the GPU test clears for its children are exactly the ones the library reads.
   * the weight-gradient tests (tests/test_gpu_gemm_wgrad.py): the restated split rules give the slice structure of every shape, the data
     sums exactly in float32 in adversarial orders and needs more than 8 significand bits, the frames guard every operand.
+  * the main-loop tests (tests/test_gpu_gemm_mainloop.py): every prefix sum of every contraction is a float32 in natural, reversed, per-tile,
+    per-segment and per-slice order; the accumulator restated under each fault of a K loop (a tile dropped or used twice, a segment read from
+    the wrong plane or computed as lo lo, a seam one tile off, a K tail dropped or read from the next row) differs from the spec in every
+    16 x 16 block; which family takes which K and k_fold, with the plan's line; the plane-pair frames.
 
 Worst err / tol of the restatements is printed ("[gemm_host] ..."; run with -s); the table is at the top of tests/test_gpu_gemm_epilogues.py.
 """
@@ -194,7 +198,7 @@ def test_case_table_is_well_formed():
         assert keys[name] >= 0 and keys[name] not in G.SPECIALISED_KEYS
     assert all(f in G.FAMILIES and G.FAMILIES[f]["tile"] == (64, 64) and n == "mul_bf16" for f, n in G.STRIP_ZERO_SIGN)
     assert keys["pair_gelu"] == 1 << 8 and keys["grouped41"] == -1 == keys["grouped41_gelugrad"]
-    assert set(G.FAMILIES) == {"t64", "t128", "f32_t64", "f32_t128", "ring8", "ring4", "q4", "w4", "p256", "kslices", "generic"}
+    assert set(G.FAMILIES) == {"t64", "t128", "f32_t64", "f32_t128", "ring8", "ring4", "q4", "t96", "w4", "p256", "kslices", "generic"}
 
     for fam, f in G.FAMILIES.items():
         M, N, K = f["shape"]
@@ -206,7 +210,7 @@ def test_case_table_is_well_formed():
         blocks = range(last, last + tm, wm)
         if fam != "generic":                                                                # (16 x 16 outputs, one per thread: no wave block)
             assert any(b >= M for b in blocks), fam                                         # a wave block that starts past M
-            if fam != "q4":                                                                 # (q4 takes M % 64 == 0: its guard)
+            if fam not in ("q4", "t96"):                                                    # (q4 and t96 take M % 64 == 0: their guard)
                 assert any(b < M < b + wm for b in blocks), fam                             # a partially filled wave block
                 assert M % 16 != 0, fam                                                     # ... that ends inside a 16-row MFMA tile
         assert N % 8 == 0
@@ -223,6 +227,11 @@ def test_case_table_is_well_formed():
         if fam == "q4":
             assert M % 64 == 0
             assert set(G.family_configs(fam)) == {c["name"] for c in G.CONFIGS if G.lean_key(c) in G.SPECIALISED_KEYS}
+        if fam == "t96":                                                                    # dm_gemm_t96_plan: no epilogue, no accumulate, three lean keys
+            assert M % 64 == 0 and f["codes"] == (12896,) and f["env"]["DM_GEMM_T96"] == "2" and f["layouts"] == ("NT", "NN")
+            assert set(G.family_configs(fam)) == {c["name"] for c in G.CONFIGS if c["epi"] == "none" and not c["acc"]
+                                                  and G.lean_key(c) in (0, 1 << 3, 1 | (1 << 3))} == {"none_f32", "none_bf16", "bias_res_f32"}
+        assert f["env"].get("DM_GEMM_T96") == ("2" if fam == "t96" else "0"), fam           # every other family switches it off
         if fam == "kslices":
             assert G.plan_fwd_split(M, N, K) == (2, 64) and "DM_GEMM_FORCE_TILE" in f["env"] and f["env"]["DM_GEMM_FORCE_TILE"] is None
         else:
@@ -458,3 +467,251 @@ def test_framed_operand_cases_of_the_epilogue_families():
     elems, ld, idx = G.framed_operand(328, 192)
     assert ld == 200 and idx.shape == (328, 192) and idx.min() == G.VIEW_OFFSET and idx[1, 0] - idx[0, 0] == ld
     assert elems - 1 - int(idx.max()) >= G.OPERAND_PAD_ROWS * ld and len(np.unique(idx)) == idx.size
+
+
+# ---- the main loop (NT / NN): tests/test_gpu_gemm_mainloop.py ----------------------------------------------------------------------------
+def _ml_datasets():
+    """(family, M, N, K or k_fold, fold, K step) of every product's data, each (shape, fold, step) once."""
+    seen, out = set(), []
+    for fam, f in G.FAMILIES.items():
+        M, N, _ = f["shape"]
+        for c in G.ml_cases(fam):
+            fold = c["kind"] == "fold"
+            bk = 32 if (fold and fam == "w4") else f["bk"]          # the 4-wave kernel's FOLD instances step through 32 positions
+            key = (M, N, c["K"], fold, bk)
+            if key not in seen:
+                seen.add(key)
+                out.append((fam,) + key)
+    return out
+
+
+def _tiles(K, bk):
+    return [(k0, min(K, k0 + bk)) for k0 in range(0, K, bk)]
+
+
+def test_mainloop_case_table():
+    assert set(G.ML_K) == set(G.FAMILIES) and set(G.ML_FOLD) | set(G.ML_FOLD_REFUSED) == set(G.FAMILIES) and not set(G.ML_FOLD) & set(G.ML_FOLD_REFUSED)
+    assert set(G.ML_FOLD) == {"t64", "t128", "ring8", "ring4", "p256", "w4", "kslices"}
+    for fam, f in G.FAMILIES.items():
+        steps = [(K + f["bk"] - 1) // f["bk"] for K in G.ML_K[fam]]
+        if fam in G.ML_DEPTH:                                       # one step (w4: two) up to the pipeline's depth + 2, every count between
+            assert min(steps) == (2 if fam == "w4" else 1) and max(steps) >= G.ML_DEPTH[fam] + 2, fam
+            assert set(range(min(steps), G.ML_DEPTH[fam] + 3, 2 if fam == "w4" else 1)) <= set(steps), fam
+        names = G.ml_configs(fam, False)
+        assert names == (("none_f32", "bias_res_f32") if fam == "generic" else ("none_f32", "none_bf16", "bias_res_f32")), fam
+        if fam in G.ML_FOLD:
+            assert G.ml_configs(fam, True) == ("none_f32", "none_bf16", "bias_res_f32", "pair_none") and f["ab"] == G.BF16
+        n_plain = len(G.ML_K[fam]) * len(f["layouts"]) * len(names)
+        n_fold = len(G.ML_FOLD.get(fam, ())) * len(f["layouts"]) * 4 * 2
+        assert len(G.ml_cases(fam)) == n_plain + n_fold, fam
+    for fam in ("t64", "t128"):                                     # touch_at = max(0, nk - 4): nk on both sides of 4; tails alone, after one and two stages
+        nk = sorted({(K + 63) // 64 for K in G.ML_K[fam]})
+        assert nk == [1, 2, 3, 4, 5] and {K % 64 for K in G.ML_K[fam]} == {0, 8} and {8, 72, 136} <= set(G.ML_K[fam])
+        assert G.CONFIG["bias_res_f32"]["res"]                      # ... and a configuration whose residual arms the touch
+    assert G.lean_key(G.PAIR_NONE) == 1 << 8 and G.PAIR_NONE["name"] not in G.CONFIG and G.is_exact(G.PAIR_NONE) == (True, False)
+    assert not [p for p in G.STRIP_ZERO_SIGN if p[1] in G.ML_CONFIG]          # every comparison of the main-loop tests is strict
+
+
+def test_mainloop_plans_restated():
+    """Which family takes which K and k_fold, each rule restated from its plan; the K slices through plan_fwd_split and k_slices."""
+    csrc = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "deepmerge_amd", "csrc")
+    assert G.ML_K_SKIPS == {}
+    for fam, f in G.FAMILIES.items():
+        M, N, _ = f["shape"]
+        for K in list(G.ML_K[fam]) + [3 * kf for kf in G.ML_FOLD.get(fam, ())]:
+            epc = 8 if f["ab"] == G.BF16 else 4
+            if fam == "generic":
+                assert K % 4 != 0                                   # gemm_prepare: `(a_inner % epc == 0)` fails -> gemm_generic
+                continue
+            assert K % epc == 0 and (K + 8) % epc == 0, (fam, K)    # mfma_ok with the framed leading dimension K + 8
+            if f["ab"] == G.F32:
+                assert ((M + 127) // 128) * ((N + 127) // 128) >= 16
+            if fam in ("ring8", "ring4", "q4", "t96"):              # `if (p.K % BK != 0 || p.N % 8 != 0 ...) return`
+                assert K % 64 == 0 and N % 8 == 0
+            if fam in ("q4", "t96"):
+                assert M % 64 == 0
+            if fam == "p256":                                       # `if (p.K < BK256) return false`, `if ((!am || !bm) && p.K % BK256 != 0) return false`
+                assert K >= 64 and K % 64 == 0 and N % 8 == 0
+            if fam == "w4":                                         # `if (k_eff < 2 * bk_eff || k_eff % (2 * bk_eff) != 0 || p.N % TN != 0) return 0`
+                assert N % 192 == 0 and (K % 128 == 0 and K >= 128 if K in G.ML_K[fam] else (K // 3) % 64 == 0 and K // 3 >= 64)
+            if fam == "kslices":
+                assert G.plan_fwd_split(M, N, K)[1] == 64
+            else:
+                assert G.plan_fwd_split(M, N, K) == (1, 0), (fam, K)
+    width = lambda sl: [b - a for a, b in sl]
+    assert width(G.ml_slices("kslices", 1536)) == [768, 768] and width(G.ml_slices("kslices", 1600)) == [832, 768]
+    assert width(G.ml_slices("kslices", 2048)) == [512] * 4 and G.ml_slices("t64", 320) == [(0, 320)]
+    # plane pairs: k_fold = 512 -> the seam at 512 inside slice 0 (and the one at 1024 inside slice 1); 576 -> one seam in each slice
+    assert G.ML_FOLD["kslices"] == (512, 576)
+    s = G.ml_slices("kslices", 3 * 512)
+    assert s == [(0, 768), (768, 1536)] and s[0][0] < 512 < s[0][1] and s[1][0] < 1024 < s[1][1]
+    s = G.ml_slices("kslices", 3 * 576)
+    assert s == [(0, 896), (896, 1728)] and s[0][0] < 576 < s[0][1] and s[1][0] < 1152 < s[1][1]
+    M, N, _ = G.FAMILIES["kslices"]["shape"]
+    assert all(4 * M * N * 4 >= len(G.ml_slices("kslices", K)) * M * N * 4 for K in (1536, 1600, 1728, 2048))      # dm_gemm_workspace_bytes: four slices of room
+    for fam, kfs in G.ML_FOLD.items():                              # k_fold_fault: `a.k_fold % 64 == 0`; one, two, three K tiles per segment
+        assert all(kf % 64 == 0 for kf in kfs) and (fam == "kslices" or [kf // 64 for kf in kfs] == [1, 2, 3])
+    # every refusal quotes a line that stands in the named file
+    quotes = [v[1] for v in G.ML_FOLD_REFUSED.values()] + [G._T96_EPI, G._T96_KEY]
+    for why in quotes:
+        name, line = why.split(" ", 1)[0], why[why.index("`") + 1:why.rindex("`")]
+        with open(os.path.join(csrc, name)) as fh:
+            assert line in fh.read(), why
+    assert {v[0] for v in G.ML_FOLD_REFUSED.values()} == {"plan", "dm_gemm"} and G.ML_REFUSED_K_FOLD % 64 == 0
+    # the walk: eleven row tiles, the last ragged and alone in a band of three; three column tiles, the last eight wide
+    assert G.GROUP_M == 8 and set(G.ML_WALK) == set(G.FAMILIES) - {"w4"}
+    for fam, (M, N, K) in G.ML_WALK.items():
+        tm, tn = G.FAMILIES[fam]["tile"]
+        assert (M + tm - 1) // tm == G.GROUP_M + 3 and M % tm != 0 and N % tn == 8, fam
+        assert (N + tn - 1) // tn == (5 if fam == "f32_t64" else 3), fam
+        assert K == {"kslices": 1536, "generic": 19}.get(fam, G.FAMILIES[fam]["bk"])
+        if G.FAMILIES[fam]["ab"] == G.F32 and fam != "generic":
+            assert ((M + 127) // 128) * ((N + 127) // 128) >= 16
+        assert (G.plan_fwd_split(M, N, K) == (2, 64)) == (fam == "kslices")
+        assert fam not in ("q4", "t96") or M % 64 == 0
+    M, N = G.ml_walk_w4(256)
+    assert (M, N) == (98504, 192) and (M + 255) // 256 == 385 and M % 256 == 200 and all(K % 128 == 0 for K in G.ML_WALK_W4_K)
+
+
+def test_mainloop_data_is_exact_in_every_order():
+    """What the bit comparison rests on: every prefix sum of the contraction in float32 is the float64 value -- in natural order, reversed, tile
+    by tile and (pairs) segment by segment, slice by slice with the partial sums added last -- and so is every step of the epilogue."""
+    bf = lambda x: torch.from_numpy(np.array(x)).float().bfloat16().double().numpy()
+    for fam, M, N, K, fold, bk in _ml_datasets():
+        d = G.ml_data(M, N, K, fold)
+        terms = G.ml_terms(d, fold)
+        for a, b in terms:
+            assert np.array_equal(bf(a), a) and np.array_equal(bf(b), b)                    # exact in bf16 (and so in fp32)
+        if fold:
+            assert 4.02 * K * 1024 < 2 ** 24 and np.abs(d["a_hi"]).max() == 2 and np.abs(d["b_lo"]).max() == 3 / 1024
+            assert not np.array_equal(d["a_lo"] * (d["a_hi"] != 0), d["b_lo"][:M] * (d["a_hi"] != 0)) if N >= M else True
+            lolo = d["a_lo"] @ d["b_lo"].T
+            assert np.array_equal(np.round(lolo * 2 ** 20), lolo * 2 ** 20) and (np.round(lolo * 1024) != lolo * 1024).mean() > 0.5      # off the 2^-10 grid
+            with_lolo = (d["acc"] + lolo).astype(np.float32).astype(np.float64)
+            assert (with_lolo != d["acc"]).mean() > 0.5                                     # a kernel that computes Al Bl cannot match
+        mi, ni = np.r_[0:8, M - 8:M], np.r_[0:8, N - 8:N]
+        prod64 = np.concatenate([(a[mi][:, None, :] * b[ni][None, :, :]).transpose(2, 0, 1) for a, b in terms])      # [K or 3 K, 16, 16]
+        prod = prod64.astype(np.float32)
+        assert np.array_equal(prod.astype(np.float64), prod64)
+        want = d["acc"][np.ix_(mi, ni)]
+        pre = lambda p: np.cumsum(p, axis=0, dtype=np.float32)
+        for name, p in (("natural", prod), ("reversed", prod[::-1])):
+            c32, c64 = pre(p), np.cumsum(p.astype(np.float64), axis=0)
+            assert c32.dtype == np.float32 and np.array_equal(c32.astype(np.float64), c64) and np.array_equal(c64[-1], want), (fam, K, fold, name)
+        # tile by tile (the K step), segment by segment, slice by slice: the partial sums, then their running sum
+        k_all = prod.shape[0]
+        cuts = {"tiles": _tiles(k_all, bk), "slices": G.ml_slices(fam, k_all)}
+        if fold:
+            cuts["segments"] = _tiles(k_all, K)
+        for name, cut in cuts.items():
+            parts = np.stack([pre(prod[k0:k1])[-1] for k0, k1 in cut])
+            assert np.array_equal(parts.astype(np.float64), np.stack([prod64[k0:k1].sum(0) for k0, k1 in cut])), (fam, K, fold, name)
+            assert np.array_equal(pre(parts)[-1].astype(np.float64), want) and np.array_equal(pre(parts[::-1])[-1].astype(np.float64), want)
+        # the epilogue of every configuration: exact in float32 in both orders, with and without fma; a pair's lo plane is an exact difference
+        assert np.array_equal(d["acc"].astype(np.float32).astype(np.float64), d["acc"])
+        for name in G.ml_configs(fam, fold):
+            cfg = G.ML_CONFIG[name]
+            c = G.ml_case(cfg, d)
+            ref = G.epilogue_ref(d["acc"], c)
+            for order in ("left", "right"):
+                for fma in (False, True):
+                    assert np.array_equal(G.restate32(d["acc"], c, True, order, fma)["v"].astype(np.float64), ref["v"]), (fam, K, name)
+            if cfg["c"] == G.PAIR:
+                hi = G.round_bf16(ref["v"])
+                assert np.array_equal((ref["v"].astype(np.float32) - hi.astype(np.float32)).astype(np.float64), ref["v"] - hi)
+                assert (ref["c_lo"] != 0).mean() > 0.5                                      # the lo plane carries information
+            if cfg["c"] == G.BF16 and fold:
+                assert (bf(ref["v"]) != ref["v"]).mean() > 0.5                              # the rounding to bf16 is a real one
+
+
+def _every_block_differs(got, want):
+    """Does `got` differ from `want` somewhere in every 16 x 16 block of the window (partial blocks at the edges included)?"""
+    diff = (got != want) | (np.signbit(got) != np.signbit(want))
+    rows = np.add.reduceat(diff.astype(np.int64), np.arange(0, diff.shape[0], 16), axis=0)
+    return bool((np.add.reduceat(rows, np.arange(0, diff.shape[1], 16), axis=1) > 0).all())
+
+
+def test_mainloop_net_is_tight():
+    """Without a GPU: the accumulator restated under the faults a K loop can have differs from the spec, in bits, in EVERY 16 x 16 block of
+    the M x N window -- as fp32 and after the rounding to bf16 (none_bf16).  So the bit comparison of the GPU test sees each of them in
+    whatever tile it happens."""
+    r32 = lambda x: x.astype(np.float32).astype(np.float64)
+    n_faults = 0
+    for fam, M, N, K, fold, bk in _ml_datasets():
+        d = G.ml_data(M, N, K, fold)
+        terms = G.ml_terms(d, fold)
+        acc = d["acc"]
+        faults = {}
+        T = lambda s, k0, k1: terms[s][0][:, k0:k1] @ terms[s][1][:, k0:k1].T
+        for s in range(len(terms)):
+            tl = _tiles(K, bk)
+            for t, (k0, k1) in enumerate(tl):
+                faults[f"segment {s} tile {t} dropped"] = acc - T(s, k0, k1)
+                if t + 1 < len(tl):                                 # the stale buffer: tile t once more where tile t + 1 belongs (both operands, and A alone)
+                    n0, n1 = tl[t + 1]
+                    w = n1 - n0
+                    faults[f"segment {s} tile {t} twice"] = acc - T(s, n0, n1) + T(s, k0, k0 + w)
+                    faults[f"segment {s} tile {t} of A twice"] = acc - T(s, n0, n1) + terms[s][0][:, k0:k0 + w] @ terms[s][1][:, n0:n1].T
+        if fold:
+            ah, al, bh, bl = d["a_hi"], d["a_lo"], d["b_hi"], d["b_lo"]
+            faults["segment 2 of A read from hi"] = acc - al @ bh.T + ah @ bh.T
+            faults["segment 1 of B read from hi"] = acc - ah @ bl.T + ah @ bh.T
+            faults["segment 2 computed as lo lo"] = acc - al @ bh.T + al @ bl.T
+            w = min(bk, K)
+            for s in range(3):                                      # a seam one tile off: the segment's first tile comes from a neighbour
+                for o in (s - 1, s + 1):
+                    if 0 <= o < 3:
+                        faults[f"segment {s}: first tile from segment {o}"] = acc - T(s, 0, w) + T(o, 0, w)
+        elif K % bk:
+            w = min(8, K % bk)                                      # the K tail's last 8 columns (fp32 operands: the tail is 4 wide)
+            a, b = terms[0]
+            faults["K tail dropped"] = acc - a[:, K - w:] @ b[:, K - w:].T
+            nxt = np.roll(a, -1, axis=0)[:, :w]                      # ... read as the next row's first columns
+            faults["K tail of A from the next row"] = acc - a[:, K - w:] @ b[:, K - w:].T + nxt @ b[:, K - w:].T
+            nxt = np.roll(b, -1, axis=0)[:, :w]
+            faults["K tail of B from the next row"] = acc - a[:, K - w:] @ b[:, K - w:].T + a[:, K - w:] @ nxt.T
+        want32, want16 = r32(acc), G.round_bf16(np.array(acc))
+        for name, v in faults.items():
+            n_faults += 1
+            assert _every_block_differs(r32(v), want32), (fam, K, fold, name, "fp32")
+            if fam != "generic":
+                assert _every_block_differs(G.round_bf16(v), want16), (fam, K, fold, name, "bf16")
+    assert n_faults > 500
+
+
+def test_mainloop_frames():
+    """No element of an allocation belongs to two windows; "far" planes do not overlap and have NaN between them; strides the kernels accept."""
+    for fam, M, N, K, fold, bk in _ml_datasets():
+        if not fold:
+            for rows, cols in ((M, K), (N, K), (K, N)):
+                elems, ld, idx = G.framed_operand(rows, cols)
+                assert ld == cols + 8 and len(np.unique(idx)) == idx.size and idx.min() == G.VIEW_OFFSET
+                assert elems - 1 - int(idx.max()) >= G.OPERAND_PAD_ROWS * ld
+            continue
+        for rows, cols in ((M, K), (N, K), (K, N)):
+            dense, far = G.pair_frame(rows, cols, "dense"), G.pair_frame(rows, cols, "far")
+            for fr in (dense, far):
+                idx = fr["idx"]
+                assert idx.shape == (2, rows, cols) and len(np.unique(idx)) == idx.size and idx.min() == G.VIEW_OFFSET       # no index in two planes
+                assert np.array_equal(idx[1] - idx[0], np.full((rows, cols), fr["plane"])) and fr["ld"] == cols
+                assert fr["plane"] % 8 == 0 and 0 < fr["plane"] < 1 << 30                                                      # k_fold_fault: offsets % 8, below 2^30
+                assert fr["elems"] - 1 - int(idx.max()) >= G.OPERAND_PAD_ROWS * cols and (G.VIEW_OFFSET * 2) % 16 == 0
+            assert dense["plane"] == rows * cols and far["plane"] == rows * cols + 8 * 37 == rows * cols + G.FAR_GAP
+            assert int(far["idx"][1].min()) - int(far["idx"][0].max()) - 1 == G.FAR_GAP                                        # NaN from plane to plane
+    for name, cfg in G.ML_CONFIG.items():
+        b = G.buffers(cfg, 328, 200)
+        assert b["c"]["elems"] - 1 - int(b["c"]["idx"].max()) - b["c"].get("plane", 0) >= G.PAD_ROWS * b["c"]["ld"]
+        assert (name == "pair_none") == ("plane" in b["c"]) and ("res" in b) == cfg["res"]
+
+
+def test_mainloop_switches():
+    """The main-loop module clears the same once-per-process switches as the epilogue module and sets only names read on every call."""
+    import test_gpu_gemm_mainloop as ML
+    import test_gpu_gemm_epilogues as EP
+    assert ML.ONCE_PER_PROCESS is EP.ONCE_PER_PROCESS and ML.TIMEOUT == EP.TIMEOUT == 60
+    with open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "deepmerge_amd", "csrc", "dm_gemm.hip")) as f:
+        src = f.read()
+    body = src[src.index("GemmSwitches read_switches()"):]
+    per_call = set(re.findall(r'getenv\(\s*"(DM_GEMM_\w+)"', body[:body.index("\n}\n")]))
+    for fam, f in G.FAMILIES.items():
+        assert set(f["env"]) <= per_call and "DM_GEMM_T96" in f["env"], fam

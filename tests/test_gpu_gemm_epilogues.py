@@ -37,7 +37,11 @@ The net is tight (three single-line changes on a scratch copy of the library, ea
                                                  here test_gemm_epilogues[bf16] and its ring / w4 forms fail too: 1.6e-2 does catch a lost sign
 
 Skipped configurations, each with the line of the plan that refuses it: gemm_ref.FAMILIES[family]["skips"] (q4: everything without a
-straight-line epilogue instance; fp32 operands: the plane pair; the generic path: everything that is not fp32 throughout, and grouped rows).
+straight-line epilogue instance; t96: everything with an epilogue or accumulate, or whose lean key is not 0, 1 << 3 or 1 | 1 << 3 -- none_f32,
+none_bf16 and bias_res_f32 remain; fp32 operands: the plane pair; the generic path: everything that is not fp32 throughout, and grouped rows).
+The t96 family (dm_gemm_t96.hip, code 12896; 128 x 96 tiles, a wave owns 64 x 48) joined after the table and the mutation record above were
+made: it runs at 320 x 200 x 192 (M % 64 == 0 as its plan demands, three column tiles, the 8-column tail inside a wave's 48 columns).
+The K loops of all these families are pinned by tests/test_gpu_gemm_mainloop.py.
 The parent asserts that exactly the remaining cases ran.  Run with -s for one line per product with its family code.
 """
 import json
