@@ -212,20 +212,29 @@ def split_planes(x: torch.Tensor, colsum_out: Optional[torch.Tensor] = None, col
         check(_lib.lib().dm_split_bf16_planes(x.data_ptr(), x.stride(0), rows, cols, out.data_ptr(), None, None, _stream()), "dm_split_bf16_planes")
         return Planes(out)
     n_part = _lib.lib().dm_split_colsum_partial_floats(rows, cols)
-    deferred = defer and _DEFER_REDUCTIONS and _in_backward()
+    deferred = _deferred(defer)
     part = (torch.empty(n_part, dtype=torch.float32, device=x.device) if deferred      # (alive until the batch launch: not a shared slot)
             else workspace(4 * n_part, x.device, "planes.partial").view(torch.float32))
     rows_out = C.c_int32(0)
     check(_lib.lib().dm_split_bf16_planes(x.data_ptr(), x.stride(0), rows, cols, out.data_ptr(), part.data_ptr(), C.byref(rows_out), _stream()),
           "dm_split_bf16_planes")
-    if deferred:
-        _queue_reduce(part, colsum_out, colsum_out, rows_out.value, cols, cols, colsum_accumulate)
-        return Planes(out)
-    item = (_lib.DmReduceItem * 1)()
-    item[0].partial, item[0].out0, item[0].out1 = part.data_ptr(), colsum_out.data_ptr(), colsum_out.data_ptr()
-    item[0].nrows, item[0].width, item[0].split, item[0].accumulate = rows_out.value, cols, cols, int(bool(colsum_accumulate))
-    check(_lib.lib().dm_partial_reduce_batch(item, 1, _stream()), "dm_partial_reduce_batch")
+    _reduce(part, colsum_out, colsum_out, rows_out.value, cols, cols, colsum_accumulate, deferred)
     return Planes(out)
+
+
+def _operand_shapes(layout: int, M: int, N: int, K: int):
+    """((rows, cols) of A, (rows, cols) of B): the operands of a product as row-major matrices."""
+    return ((M, K) if layout != DM_TN else (K, M)), ((N, K) if layout == DM_NT else (K, N))
+
+
+def _fold_planes(layout: int, A: Planes, B: Planes, M: int, N: int, K: int):
+    """The folded "bf16x3" product of two plane pairs as dm_gemm takes it: (A, B, lda, ldb, K, fold) -- one bf16 product over three K
+    segments (hi.hi + hi.lo + lo.hi) that re-read the planes in place."""
+    (a_rows, a_cols), (b_rows, b_cols) = _operand_shapes(layout, M, N, K)
+    if (A.rows, A.cols) != (a_rows, a_cols) or (B.rows, B.cols) != (b_rows, b_cols):
+        raise ValueError(f"plane pair shapes {(A.rows, A.cols)} / {(B.rows, B.cols)} do not match the product {(a_rows, a_cols)} / {(b_rows, b_cols)}")
+    # (plane stride: rows * cols for a split, the flat buffer's length for a weight's mirror pair)
+    return A.t, B.t, a_cols, b_cols, 3 * K, (K, A.t.stride(0), B.t.stride(0))
 
 
 def gemm(layout: int, A: torch.Tensor, B: torch.Tensor, C_out: torch.Tensor, M: int, N: int, K: int, *,
@@ -245,20 +254,15 @@ def gemm(layout: int, A: torch.Tensor, B: torch.Tensor, C_out: torch.Tensor, M: 
     if isinstance(A, Planes) or isinstance(B, Planes) or (
             _FP32_PRODUCTS == "bf16x3" and A.dtype == torch.float32 and M * N * K >= _SPLIT_MIN_WORK and planes_ok(M, K) and planes_ok(N, K)
             and (lda is None or lda % 4 == 0) and (ldb is None or ldb % 4 == 0) and A.data_ptr() % 16 == 0 and B.data_ptr() % 16 == 0):
-        # folded split-bf16 product: both operands as hi / lo plane pairs (split here unless the caller already holds the pair),
-        # one bf16 product over three K segments (hi.hi + hi.lo + lo.hi) that re-read the planes in place
-        a_rows, a_cols = (M, K) if layout != DM_TN else (K, M)
-        b_rows, b_cols = (N, K) if layout == DM_NT else (K, N)
+        # folded split-bf16 product: both operands as hi / lo plane pairs (split here unless the caller already holds the pair)
+        (a_rows, a_cols), (b_rows, b_cols) = _operand_shapes(layout, M, N, K)
         if not isinstance(A, Planes):
             A = split_planes(torch.as_strided(A, (a_rows, a_cols), (lda if lda is not None else a_cols, 1)), colsum_out, colsum_accumulate)
             colsum_out = None
         if not isinstance(B, Planes):
             B = split_planes(torch.as_strided(B, (b_rows, b_cols), (ldb if ldb is not None else b_cols, 1)))
-        if (A.rows, A.cols) != (a_rows, a_cols) or (B.rows, B.cols) != (b_rows, b_cols):
-            raise ValueError(f"plane pair shapes {(A.rows, A.cols)} / {(B.rows, B.cols)} do not match the product {(a_rows, a_cols)} / {(b_rows, b_cols)}")
         # (column sums of a pre-split left operand: dm_gemm sums the hi and the lo plane -- fused into the weight-gradient kernels)
-        fold = (K, A.t.stride(0), B.t.stride(0))      # (plane stride: rows * cols for a split, the flat buffer's length for a weight's mirror pair)
-        A, B, lda, ldb, K = A.t, B.t, a_cols, b_cols, 3 * K
+        A, B, lda, ldb, K, fold = _fold_planes(layout, A, B, M, N, K)
     _need_cuda(A, B, C_out, bias, residual, aux, colsum_out)
     if A.dtype != B.dtype:
         raise ValueError(f"A/B dtype mismatch: {A.dtype} vs {B.dtype}")
@@ -269,11 +273,10 @@ def gemm(layout: int, A: torch.Tensor, B: torch.Tensor, C_out: torch.Tensor, M: 
     if (_FP32_PRODUCTS == "bf16x3" and A.dtype == torch.float32 and M * N * K >= _SPLIT_MIN_WORK
             and M % 8 == 0 and N % 8 == 0 and K % 8 == 0 and lda % 4 == 0 and ldb % 4 == 0):     # 16-byte rows of the bf16 images
         # split-bf16: one bf16 product over a 3x longer contraction, [Ah | Ah | Al] . [Bh | Bl | Bh] (include/deepmerge_hip.h)
-        a_rows, a_cols = (M, K) if layout != DM_TN else (K, M)          # the operands as row-major matrices
-        b_rows, b_cols = (N, K) if layout == DM_NT else (K, N)
+        (a_rows, a_cols), (b_rows, b_cols) = _operand_shapes(layout, M, N, K)
         a_stack, b_stack = int(layout == DM_TN), int(layout != DM_NT)
-        A3 = workspace(6 * a_rows * a_cols, A.device, ws_slot + ".split_a").view(torch.bfloat16)    # per slot: the side stream
-        B3 = workspace(6 * b_rows * b_cols, A.device, ws_slot + ".split_b").view(torch.bfloat16)    # has its own images
+        A3 = workspace(6 * a_rows * a_cols, A.device, ws_slot + ".split_a").view(torch.bfloat16)    # per slot: a caller that names a slot
+        B3 = workspace(6 * b_rows * b_cols, A.device, ws_slot + ".split_b").view(torch.bfloat16)    # of its own gets images of its own
         # the fused split + column-sum pass has the vector kernel's preconditions (dm_rows.hip split_rows_ok: 16-byte aligned
         # source, ld % 4 == 0 -- required above -- and whole 8-column groups); an offset view of dy takes the two-pass route below
         fused_ok = colsum_out is not None and a_cols % 8 == 0 and A.data_ptr() % 16 == 0 and (a_rows * a_cols) % 8 == 0
@@ -283,10 +286,7 @@ def gemm(layout: int, A: torch.Tensor, B: torch.Tensor, C_out: torch.Tensor, M: 
             rows_out = C.c_int32(0)
             check(_lib.lib().dm_split_bf16_colsum(A.data_ptr(), lda, a_rows, a_cols, A3.data_ptr(), a_stack, 0b100, part.data_ptr(),
                                                   C.byref(rows_out), _stream()), "dm_split_bf16_colsum")
-            item = (_lib.DmReduceItem * 1)()
-            item[0].partial, item[0].out0, item[0].out1 = part.data_ptr(), colsum_out.data_ptr(), colsum_out.data_ptr()
-            item[0].nrows, item[0].width, item[0].split, item[0].accumulate = rows_out.value, a_cols, a_cols, int(bool(colsum_accumulate))
-            check(_lib.lib().dm_partial_reduce_batch(item, 1, _stream()), "dm_partial_reduce_batch")
+            _reduce(part, colsum_out, colsum_out, rows_out.value, a_cols, a_cols, colsum_accumulate)
         else:
             check(_lib.lib().dm_split_bf16(A.data_ptr(), lda, a_rows, a_cols, A3.data_ptr(), a_stack, 0b100, _stream()), "dm_split_bf16")
             if colsum_out is not None:       # column sums of the fp32 operand itself (the stacked image would count hi twice)
@@ -363,13 +363,8 @@ def gemm_grouped(calls) -> None:
     for i, (args, kw) in enumerate(calls):
         layout, A, B, C_out, M, N, K = args
         lda, ldb, fold = kw.get("lda"), kw.get("ldb"), None
-        if isinstance(A, Planes):            # as in gemm(): three K segments that re-read the planes in place
-            a_rows, a_cols = (M, K) if layout != DM_TN else (K, M)
-            b_rows, b_cols = (N, K) if layout == DM_NT else (K, N)
-            if (A.rows, A.cols) != (a_rows, a_cols) or (B.rows, B.cols) != (b_rows, b_cols):
-                raise ValueError(f"plane pair shapes {(A.rows, A.cols)} / {(B.rows, B.cols)} do not match the product {(a_rows, a_cols)} / {(b_rows, b_cols)}")
-            fold = (K, A.t.stride(0), B.t.stride(0))
-            A, B, lda, ldb, K = A.t, B.t, a_cols, b_cols, 3 * K
+        if isinstance(A, Planes):
+            A, B, lda, ldb, K, fold = _fold_planes(layout, A, B, M, N, K)
         _need_cuda(A, B, C_out, kw.get("colsum_out"))
         if A.dtype != B.dtype:
             raise ValueError(f"A/B dtype mismatch: {A.dtype} vs {B.dtype}")
@@ -471,15 +466,28 @@ def _queue_reduce(part, out0, out1, nrows, width, split, accumulate) -> None:
         _flush_queued = True
 
 
-def _reduce_partials(part, dgamma, dbeta, n_part, cols, accumulate, deferred) -> None:
-    """[dgamma | dbeta] from the partial rows a LayerNorm backward left: queued for the end of the backward pass, or one launch now."""
+def _deferred(defer: bool) -> bool:
+    """Whether a reduction the caller allows to wait (`defer`) does: the switch is on and a backward pass is running."""
+    return bool(defer and _DEFER_REDUCTIONS and _in_backward())
+
+
+def _reduce(part, out0, out1, nrows, width, split, accumulate, deferred=False) -> None:
+    """out0 | out1 (+)= the column sums of `nrows` partial rows ([dgamma | dbeta] of a LayerNorm backward: width = 2 * split; column sums
+    of one matrix: out0 is out1, width = split): queued for the end of the backward pass, or one launch now."""
     if deferred:
-        _queue_reduce(part, dgamma, dbeta, n_part, 2 * cols, cols, accumulate)
+        _queue_reduce(part, out0, out1, nrows, width, split, accumulate)
         return
     item = (_lib.DmReduceItem * 1)()
-    item[0].partial, item[0].out0, item[0].out1 = part.data_ptr(), dgamma.data_ptr(), dbeta.data_ptr()
-    item[0].nrows, item[0].width, item[0].split, item[0].accumulate = n_part, 2 * cols, cols, int(bool(accumulate))
+    item[0].partial, item[0].out0, item[0].out1 = part.data_ptr(), out0.data_ptr(), out1.data_ptr()
+    item[0].nrows, item[0].width, item[0].split, item[0].accumulate = nrows, width, split, int(bool(accumulate))
     check(_lib.lib().dm_partial_reduce_batch(item, 1, _stream()), "dm_partial_reduce_batch")
+
+
+def _partial_rows(cols: int, device, deferred: bool) -> torch.Tensor:
+    """The [dgamma | dbeta] partial rows of a LayerNorm backward over `cols` columns: a tensor of their own when the reduction is
+    deferred (alive until the batch launch), else the shared "partial" workspace."""
+    n = _lib.lib().dm_layernorm_bwd_partial_floats(cols)
+    return torch.empty(n, dtype=torch.float32, device=device) if deferred else workspace(n * 4, device, "partial").view(torch.float32)
 
 
 def layernorm_bwd(dy, x, gamma, mean, rstd, dres=None, dgamma=None, dbeta=None, accumulate=False, want_lp=False, defer=False, want_pair=False,
@@ -493,56 +501,40 @@ def layernorm_bwd(dy, x, gamma, mean, rstd, dres=None, dgamma=None, dbeta=None, 
         raise ValueError("layernorm_bwd: dy and x must be contiguous and of the same size (an expanded gradient has no rows to read)")
     rows, cols = x.numel() // x.shape[-1], x.shape[-1]
     dx = torch.empty(x.shape, dtype=torch.float32, device=x.device)
-    dx_lp = torch.empty(x.shape, dtype=torch.bfloat16, device=x.device) if want_lp else None
+    if want_pair:
+        lp_out = Planes(torch.empty((2, rows, cols), dtype=torch.bfloat16, device=x.device))
+    elif regroup is not None:
+        S, T = regroup
+        if not want_lp or rows % (S * T) or cols > _PAIR_LN_MAX_COLS:
+            raise ValueError("layernorm_bwd: regroup needs want_lp, rows in whole (S, T) groups and a register-resident width")
+        lp_out = torch.empty((S, rows // (S * T), T, cols), dtype=torch.bfloat16, device=x.device)
+    else:
+        lp_out = torch.empty(x.shape, dtype=torch.bfloat16, device=x.device) if want_lp else None
     if dgamma is None:
         dgamma = torch.empty(cols, dtype=torch.float32, device=x.device)
         dbeta = torch.empty(cols, dtype=torch.float32, device=x.device)
         accumulate = False
         defer = False
+    result = (dx, lp_out, dgamma, dbeta) if (want_lp or want_pair) else (dx, dgamma, dbeta)
+    deferred = _deferred(defer)
+    part = _partial_rows(cols, x.device, deferred)
+    head = (dy.data_ptr(), _dt(dy), x.data_ptr(), gamma.data_ptr(), mean.data_ptr(), rstd.data_ptr(), _ptr(dres), dx.data_ptr())
+    if not (want_pair or regroup is not None or deferred):      # the kernel reduces its partial rows itself (last workgroup)
+        check(_lib.lib().dm_layernorm_bwd(*head, _ptr(lp_out), dgamma.data_ptr(), dbeta.data_ptr(), int(accumulate), part.data_ptr(), rows, cols,
+                                          _stream()), "dm_layernorm_bwd")
+        return result
+    n_part = C.c_int32(0)
     if want_pair:
-        pair = torch.empty((2, rows, cols), dtype=torch.bfloat16, device=x.device)
-        deferred = defer and _DEFER_REDUCTIONS and _in_backward()
-        part = (torch.empty(_lib.lib().dm_layernorm_bwd_partial_floats(cols), dtype=torch.float32, device=x.device) if deferred
-                else workspace(_lib.lib().dm_layernorm_bwd_partial_floats(cols) * 4, x.device, "partial").view(torch.float32))
-        n_part = C.c_int32(0)
-        check(_lib.lib().dm_layernorm_bwd_partials_pair(dy.data_ptr(), _dt(dy), x.data_ptr(), gamma.data_ptr(), mean.data_ptr(), rstd.data_ptr(),
-                                                        _ptr(dres), dx.data_ptr(), pair.data_ptr(), part.data_ptr(), rows, cols, C.byref(n_part),
-                                                        _stream()), "dm_layernorm_bwd_partials_pair")
-        if deferred:
-            _queue_reduce(part, dgamma, dbeta, n_part.value, 2 * cols, cols, accumulate)
-        else:
-            item = (_lib.DmReduceItem * 1)()
-            item[0].partial, item[0].out0, item[0].out1 = part.data_ptr(), dgamma.data_ptr(), dbeta.data_ptr()
-            item[0].nrows, item[0].width, item[0].split, item[0].accumulate = n_part.value, 2 * cols, cols, int(bool(accumulate))
-            check(_lib.lib().dm_partial_reduce_batch(item, 1, _stream()), "dm_partial_reduce_batch")
-        return dx, Planes(pair), dgamma, dbeta
-    if regroup is not None:
-        S, T = regroup
-        if not want_lp or rows % (S * T) or cols > _PAIR_LN_MAX_COLS:
-            raise ValueError("layernorm_bwd: regroup needs want_lp, rows in whole (S, T) groups and a register-resident width")
-        dx_lp = torch.empty((S, rows // (S * T), T, cols), dtype=torch.bfloat16, device=x.device)
-        deferred = defer and _DEFER_REDUCTIONS and _in_backward()
-        part = (torch.empty(_lib.lib().dm_layernorm_bwd_partial_floats(cols), dtype=torch.float32, device=x.device) if deferred
-                else workspace(_lib.lib().dm_layernorm_bwd_partial_floats(cols) * 4, x.device, "partial").view(torch.float32))
-        n_part = C.c_int32(0)
-        check(_lib.lib().dm_layernorm_bwd_partials_regroup(dy.data_ptr(), _dt(dy), x.data_ptr(), gamma.data_ptr(), mean.data_ptr(), rstd.data_ptr(),
-                                                           _ptr(dres), dx.data_ptr(), dx_lp.data_ptr(), part.data_ptr(), rows, cols, S, T,
-                                                           C.byref(n_part), _stream()), "dm_layernorm_bwd_partials_regroup")
-        _reduce_partials(part, dgamma, dbeta, n_part.value, cols, accumulate, deferred)
-        return dx, dx_lp, dgamma, dbeta
-    if defer and _DEFER_REDUCTIONS and _in_backward():
-        part = torch.empty(_lib.lib().dm_layernorm_bwd_partial_floats(cols), dtype=torch.float32, device=x.device)
-        n_part = C.c_int32(0)
-        check(_lib.lib().dm_layernorm_bwd_partials(dy.data_ptr(), _dt(dy), x.data_ptr(), gamma.data_ptr(), mean.data_ptr(), rstd.data_ptr(),
-                                                   _ptr(dres), dx.data_ptr(), _ptr(dx_lp), part.data_ptr(), rows, cols, C.byref(n_part),
-                                                   _stream()), "dm_layernorm_bwd_partials")
-        _queue_reduce(part, dgamma, dbeta, n_part.value, 2 * cols, cols, accumulate)
-        return (dx, dx_lp, dgamma, dbeta) if want_lp else (dx, dgamma, dbeta)
-    part = workspace(_lib.lib().dm_layernorm_bwd_partial_floats(cols) * 4, x.device, "partial")
-    check(_lib.lib().dm_layernorm_bwd(dy.data_ptr(), _dt(dy), x.data_ptr(), gamma.data_ptr(), mean.data_ptr(), rstd.data_ptr(),
-                                      _ptr(dres), dx.data_ptr(), _ptr(dx_lp), dgamma.data_ptr(), dbeta.data_ptr(), int(accumulate),
-                                      part.data_ptr(), rows, cols, _stream()), "dm_layernorm_bwd")
-    return (dx, dx_lp, dgamma, dbeta) if want_lp else (dx, dgamma, dbeta)
+        check(_lib.lib().dm_layernorm_bwd_partials_pair(*head, lp_out.t.data_ptr(), part.data_ptr(), rows, cols, C.byref(n_part), _stream()),
+              "dm_layernorm_bwd_partials_pair")
+    elif regroup is not None:
+        check(_lib.lib().dm_layernorm_bwd_partials_regroup(*head, lp_out.data_ptr(), part.data_ptr(), rows, cols, S, T, C.byref(n_part), _stream()),
+              "dm_layernorm_bwd_partials_regroup")
+    else:
+        check(_lib.lib().dm_layernorm_bwd_partials(*head, _ptr(lp_out), part.data_ptr(), rows, cols, C.byref(n_part), _stream()),
+              "dm_layernorm_bwd_partials")
+    _reduce(part, dgamma, dbeta, n_part.value, 2 * cols, cols, accumulate, deferred)
+    return result
 
 
 _DEFER_REDUCTIONS = os.environ.get("DM_DEFER_REDUCTIONS", "1") != "0"      # A/B switch
@@ -574,30 +566,52 @@ def attention_fwd(qkv: torch.Tensor, bias: Optional[torch.Tensor], B: int, N: in
     return out, lse
 
 
-def _split_attention(table, index32, qkv, B, N, H, D):
-    """(use, cube): whether the forward runs on the split-bf16 attention kernels -- fp32 tensors inside a "bf16x3" scope, a shape they
-    take, and a bias that is either absent or the table of a token cube the module vouches for.  `qkv`: the tensor or its dtype."""
-    if (qkv if isinstance(qkv, torch.dtype) else qkv.dtype) != torch.float32 or _FP32_PRODUCTS != "bf16x3" or not _SPLIT_ATTENTION:
-        return False, None
-    cube = None if table is None else getattr(index32, "_dm_cube", None)
-    if table is not None and cube is None:
-        return False, None
-    return attention_split_ok(B, N, H, D, cube), cube
-
-
 _SPLIT_ATTENTION = os.environ.get("DM_ATTN_X3", "1") != "0"
-
-
-def _inkernel_cube(table, index32, B, N, H, D, dtype):
-    """The token cube if the forward kernel can form the bias from `table` itself (the module vouches for the index: `_dm_cube` on the
-    int32 index tensor is set only after comparing it with the closed form), else None."""
-    cube = None if table is None else getattr(index32, "_dm_cube", None)
-    if cube is None or _INKERNEL_TABLE is False or not relpos_inkernel(B, N, H, D, cube, dtype):
-        return None
-    return cube
-
-
 _INKERNEL_TABLE = os.environ.get("DM_ATTN_TABLE_IN_KERNEL", "1") != "0"      # A/B switch
+
+
+class _AttnRoute:
+    """Which kernels one attention call runs on, forward and backward, decided once from (table, index32, dtype, B, N, H, D):
+      "split"  fp32 tensors inside a "bf16x3" scope, a shape the split-bf16 kernels take, and a bias that is either absent or the table
+               of a token cube -- they read the table themselves;
+      "table"  the plain kernels form the bias from the table of a token cube themselves (relpos_inkernel);
+      "dense"  the bias, if any, as gathered dense rows.
+    `cube`: the token cube ("split" with a table, "table"), which the module vouches for: `_dm_cube` on the int32 index tensor is set
+    only after comparing it with the closed form."""
+    __slots__ = ("kind", "cube")
+
+    def __init__(self, table, index32, dtype, B, N, H, D):
+        cube = None if table is None else getattr(index32, "_dm_cube", None)
+        self.kind, self.cube = "dense", None
+        if (dtype == torch.float32 and _FP32_PRODUCTS == "bf16x3" and _SPLIT_ATTENTION and (table is None or cube is not None)
+                and attention_split_ok(B, N, H, D, cube)):
+            self.kind, self.cube = "split", cube
+        elif cube is not None and _INKERNEL_TABLE and relpos_inkernel(B, N, H, D, cube, dtype):
+            self.kind, self.cube = "table", cube
+
+
+def _attention_forward(qkv, table, index32, route: _AttnRoute, B, N, H, D, scale, out_pair: bool = False):
+    """-> (out, lse, keep, out_pair).  qkv: the packed tensor, or its Planes ("split" only).  keep: what the backward pass needs besides
+    qkv / out / lse -- the (hi, lo) images of qkv ("split") or the gathered (bias, bias_t) ("dense" with a table; else (None, None)).
+    out_pair ("split" only): the kernel also writes out as a plane pair; None elsewhere."""
+    table = None if table is None else table.contiguous()
+    if route.kind == "split":
+        r = attention_fwd_split(qkv, table, route.cube, B, N, H, D, scale, out_pair=out_pair)
+        return r[0], r[1], (r[2], r[3]), (r[4] if out_pair else None)
+    if route.kind == "table":
+        return attention_fwd_relpos(qkv, table, route.cube, B, N, H, D, scale) + ((None, None), None)
+    keep = (None, None) if table is None else relpos_bias_gather(table, index32, N, transposed=True)
+    return attention_fwd(qkv, keep[0], B, N, H, D, scale) + (keep, None)
+
+
+def _attention_backward(route: _AttnRoute, qkv, keep, table, out, dout, lse, index32, n_bins, B, N, H, D, scale, pair: bool = False):
+    """Backward of _attention_forward -> (dqkv, slab, info).  table: the bias table or None (read by the kernels of the "split" and "table"
+    routes); index32: None when no table gradient is wanted, else slab + info go to relpos_bias_scatter.  pair ("split" only): dqkv
+    as the Planes of the [B*N, 3*H*D] matrix."""
+    table = None if (table is None or route.kind == "dense") else table.contiguous()
+    if route.kind == "split":
+        return attention_bwd_split(keep[0], keep[1], table, route.cube, out, dout, lse, B, N, H, D, scale, index32, n_bins or 0, pair=pair)
+    return attention_bwd(qkv, keep[0], out, dout, lse, B, N, H, D, scale, index32, n_bins or 0, bias_t=keep[1], table=table, cube=route.cube)
 
 
 def relpos_inkernel(B: int, N: int, H: int, D: int, cube, dtype: torch.dtype) -> bool:
@@ -1079,30 +1093,84 @@ def _as_operand(t: torch.Tensor, dtype: torch.dtype) -> torch.Tensor:
     raise ValueError(f"cannot use a {t.dtype} gradient with {dtype} operands")
 
 
-def _linear_backward(x, w, dy, need_dx, need_dw, need_db, wshape, wparam=None, bparam=None):
+class _GradSlot:
+    """Where ONE parameter gradient of a backward pass goes.  `out` (shape `shape`, fp32): the view of the trainer's flat gradient buffer
+    when the parameter has a sink (`param._dm_grad_sink`; `direct`), else a fresh tensor.  `acc()`: the accumulate flag of one write into
+    `out`.  `grad()`: what autograd gets back -- None when the gradient went to the sink, else `out` in the parameter's shape.
+    The parameters of the generic Functions (Linear, Mlp, the norms) may be used several times per step (the shared `norm`, the aux
+    heads): their contributions add up in the sink.  (The data-parallel exchange works on whole backward segments, so it never needs
+    to know when one parameter is complete.)"""
+    __slots__ = ("param", "out", "direct")
+
+    def __init__(self, param, shape, device, use_sink: bool = True):
+        sink = getattr(param, "_dm_grad_sink", None) if use_sink else None
+        self.param, self.direct = param, sink is not None
+        self.out = sink.view(shape) if self.direct else torch.empty(shape, dtype=torch.float32, device=device)
+
+    def acc(self) -> bool:
+        """Call once per write.  Parameters the trainer tracks (`_dm_gw`, set by FlatParams for the parameters of the fused blocks) are not
+        zeroed at the start of a step: their FIRST write of the step stores, later ones (a block applied twice, gradient accumulation
+        over several backward passes) add.  Untracked parameters: the buffer was zeroed, always add.  A fresh tensor: store."""
+        if not self.direct:
+            return False
+        st = getattr(self.param, "_dm_gw", None)
+        if st is None or st[0]:
+            return True
+        st[0] = True
+        return False
+
+    def grad(self):
+        if self.direct:
+            return None
+        return self.out if self.out.shape == self.param.shape else self.out.view(self.param.shape)
+
+
+def _norm_slots(gamma, beta, cols: int, device, need: bool = True):
+    """(gamma slot, beta slot, accumulate) for a norm's two gradients, which ONE launch writes: both sinks or (mixed sinks, or a
+    gradient autograd does not ask for) neither, one accumulate flag, the first-write state of both bumped.  The reduction may be
+    deferred only into sinks: `defer=g.direct`."""
+    g = _GradSlot(gamma, (cols,), device, use_sink=need)
+    b = _GradSlot(beta, (cols,), device, use_sink=g.direct)
+    if b.direct != g.direct:
+        g = _GradSlot(gamma, (cols,), device, use_sink=False)
+    acc = g.acc()
+    b.acc()
+    return g, b, acc
+
+
+def attach(g: torch.Tensor, name: str, payload, *extra) -> None:
+    """Let `payload` (a bf16 copy of g: `_dm_lp_copy`, `_dm_lp_regrouped`; its plane pair: `_dm_planes`) ride on the gradient tensor g to
+    the next backward node -- the engine hands over the Python object -- as `(payload, _grad_tag(g), *extra)`."""
+    setattr(g, name, (payload, _grad_tag(g)) + extra)
+
+
+def attached(g: torch.Tensor, name: str, *extra):
+    """The payload `attach` left on g under `name` with these extras, while it is still current: a tag that no longer matches means the
+    engine summed another contribution into the tensor in place, and the copy is stale.  None otherwise; the consumer then makes its own."""
+    rider = getattr(g, name, None)
+    if rider is None or rider[1] != _grad_tag(g) or tuple(rider[2:]) != extra:
+        return None
+    return rider[0]
+
+
+def _linear_backward(x, w, dy, need_dx, need_dw, need_db, wparam, bparam):
     """dx = dy W (NN), dW = dy^T x (TN, split-K), db = column sums -- autograd of y = x W^T + b.
-    wparam / bparam: the nn.Parameters behind w / b; when they have a usable gradient sink the results are accumulated
-    there and None is returned for them."""
+    wparam / bparam: the nn.Parameters behind w / b (bparam None: need_db is false); when they have a gradient sink the results
+    are accumulated there and None is returned for them, else dW comes back in wparam's shape."""
     M, K = x.shape
     N = w.shape[0]
-    dx = dw = db = None
+    dx = None
     if need_dx:
         dx = torch.empty((M, K), dtype=x.dtype, device=x.device)
         gemm(DM_NN, dy, w, dx, M, K, N, lda=N, ldb=K, ldc=K)
-    wsink = _multi_use_sink(wparam, (N, K)) if need_dw else None
-    bsink = _multi_use_sink(bparam, (N,)) if need_db else None
-    if need_db:
-        db = bsink if bsink is not None else torch.empty(N, dtype=torch.float32, device=x.device)
+    bs = _GradSlot(bparam, (N,), x.device) if need_db else None
+    ws = _GradSlot(wparam, (N, K), x.device) if need_dw else None
     if need_dw:
-        dw = wsink if wsink is not None else torch.empty((N, K), dtype=torch.float32, device=x.device)
-        gemm(DM_TN, dy, x, dw, N, K, M, lda=N, ldb=K, ldc=K, accumulate=_acc(wparam, wsink is not None),
-             colsum_out=db, colsum_accumulate=_acc(bparam, bsink is not None))     # db rides on the wgrad when it can
-        dw = None if wsink is not None else dw.reshape(wshape)
+        gemm(DM_TN, dy, x, ws.out, N, K, M, lda=N, ldb=K, ldc=K, accumulate=ws.acc(),
+             colsum_out=bs.out if need_db else None, colsum_accumulate=bs.acc() if need_db else False)     # db rides on the wgrad when it can
     elif need_db:
-        colsum(dy, db, accumulate=_acc(bparam, bsink is not None))
-    if bsink is not None:
-        db = None
-    return dx, dw, db
+        colsum(dy, bs.out, accumulate=bs.acc())
+    return dx, (ws.grad() if need_dw else None), (bs.grad() if need_db else None)
 
 
 class LinearFn(torch.autograd.Function):
@@ -1123,7 +1191,7 @@ class LinearFn(torch.autograd.Function):
         gemm(DM_NT, x, w, y, M, N, K, lda=K, ldb=K, ldc=N, bias=bias,
              residual=None if residual is None else residual.contiguous())
         ctx.save_for_backward(x, w)
-        ctx.has_bias, ctx.wshape = bias is not None, weight.shape
+        ctx.has_bias = bias is not None
         ctx.params = (weight, bias)
         return y
 
@@ -1134,7 +1202,7 @@ class LinearFn(torch.autograd.Function):
         dres = dy if ctx.needs_input_grad[3] else None
         dyo = _as_operand(dy, x.dtype)
         dx, dw, db = _linear_backward(x, w, dyo, ctx.needs_input_grad[0], ctx.needs_input_grad[1],
-                                      ctx.has_bias and ctx.needs_input_grad[2], ctx.wshape, *ctx.params)
+                                      ctx.has_bias and ctx.needs_input_grad[2], *ctx.params)
         return dx, dw, db, dres, None
 
 
@@ -1178,10 +1246,9 @@ class PatchEmbedCatFn(torch.autograd.Function):
         same = all(c.dtype == cols[0].dtype for c in cols)
         # block 0's LayerNorm backward has already written exactly those rows next to this very gradient (tag still current: nothing was
         # summed into it since) -- else the strided cast-copy
-        rg = getattr(dcube, "_dm_lp_regrouped", None)
-        if (rg is not None and same and rg[1] == _grad_tag(dcube) and rg[2] == (S, T) and rg[0].dtype == cols[0].dtype
-                and tuple(rg[0].shape) == (S, B, T, Cc) and tuple(dcube.shape) == (B, S * T, Cc)):
-            dys = rg[0]
+        rg = attached(dcube, "_dm_lp_regrouped", (S, T))
+        if rg is not None and same and rg.dtype == cols[0].dtype and tuple(rg.shape) == (S, B, T, Cc) and tuple(dcube.shape) == (B, S * T, Cc):
+            dys = rg
         else:
             dys = torch.empty((S, B, T, Cc), dtype=cols[0].dtype, device=dcube.device).copy_(dcube.contiguous().view(B, S, T, Cc).transpose(0, 1)) if same else None
         for i in range(S):
@@ -1189,7 +1256,7 @@ class PatchEmbedCatFn(torch.autograd.Function):
             K = c.shape[1]
             dy = dys[i].view(B * T, Cc) if same else dcube[:, i * T:(i + 1) * T, :].to(c.dtype).reshape(B * T, Cc)
             need_w, need_b = ctx.needs_input_grad[2 + S + i], ctx.needs_input_grad[2 + 2 * S + i]
-            _, dw, db = _linear_backward(c, ws[i], dy, False, need_w, need_b and biases[i] is not None, weights[i].shape, weights[i], biases[i])
+            _, dw, db = _linear_backward(c, ws[i], dy, False, need_w, need_b and biases[i] is not None, weights[i], biases[i])
             grads_w.append(dw)
             grads_b.append(db)
         return (None, None) + (None,) * S + tuple(grads_w) + tuple(grads_b)
@@ -1215,7 +1282,6 @@ class MlpFn(torch.autograd.Function):
         gemm(DM_NT, h, w2c, y, M, N, Hd, lda=Hd, ldb=Hd, ldc=N, bias=b2,
              residual=None if residual is None else residual.contiguous())
         ctx.save_for_backward(x, w1c, w2c, pre, h)
-        ctx.shapes = (w1.shape, w2.shape)
         ctx.params = (w1, b1, w2, b2)
         return y
 
@@ -1230,10 +1296,10 @@ class MlpFn(torch.autograd.Function):
         dyo = _as_operand(dy, x.dtype)
         # fc2: dW2 = dy^T h, db2 = colsum(dy); dpre = (dy W2) * gelu'(pre)  (DGELU epilogue)
         w1, b1, w2, b2 = ctx.params         # (gradients go to the trainer's sinks when there are any, like LinearFn's)
-        _, dw2, db2 = _linear_backward(h, w2c, dyo, False, need[3], need[4], ctx.shapes[1], w2, b2)
+        _, dw2, db2 = _linear_backward(h, w2c, dyo, False, need[3], need[4], w2, b2)
         dpre = torch.empty((M, Hd), dtype=x.dtype, device=x.device)
         gemm(DM_NN, dyo, w2c, dpre, M, Hd, N, lda=N, ldb=Hd, ldc=Hd, epilogue=DM_EPI_MUL, aux=pre, ldaux=Hd)
-        dx, dw1, db1 = _linear_backward(x, w1c, dpre, need[0], need[1], need[2], ctx.shapes[0], w1, b1)
+        dx, dw1, db1 = _linear_backward(x, w1c, dpre, need[0], need[1], need[2], w1, b1)
         return dx, dw1, db1, dw2, db2, dres, None
 
 
@@ -1254,20 +1320,12 @@ class LayerNormFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dy):
         x, gamma, mean, rstd = ctx.saved_tensors
-        C = gamma.numel()
-        lp = ctx.want_lp
-        gs, bs = _multi_use_sink(ctx.params[0], (C,)), _multi_use_sink(ctx.params[1], (C,))
-        if gs is not None and bs is not None and ctx.needs_input_grad[1] and ctx.needs_input_grad[2]:
-            acc = _acc(ctx.params[0], True)
-            _acc(ctx.params[1], True)
-            r = layernorm_bwd(dy.contiguous(), x, gamma, mean, rstd, dgamma=gs, dbeta=bs, accumulate=acc, want_lp=lp)
-            dx, dg, db = r[0], None, None
-        else:
-            r = layernorm_bwd(dy.contiguous(), x, gamma, mean, rstd, want_lp=lp)
-            dx, dg, db = r[0], r[-2], r[-1]
-        if lp:
-            dx._dm_lp_copy = (r[1], _grad_tag(dx))
-        return dx, dg, db, None, None, None
+        g, b, acc = _norm_slots(*ctx.params, gamma.numel(), x.device, need=ctx.needs_input_grad[1] and ctx.needs_input_grad[2])
+        r = layernorm_bwd(dy.contiguous(), x, gamma, mean, rstd, dgamma=g.out, dbeta=b.out, accumulate=acc, want_lp=ctx.want_lp)
+        dx = r[0]
+        if ctx.want_lp:
+            attach(dx, "_dm_lp_copy", r[1])
+        return dx, g.grad(), b.grad(), None, None, None
 
 
 class AttentionFn(torch.autograd.Function):
@@ -1277,49 +1335,26 @@ class AttentionFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, qkv, table, index32, B, N, H, D, scale):
         qkv = qkv.contiguous()
-        bias = bias_t = None
-        cube = _inkernel_cube(table, index32, B, N, H, D, qkv.dtype)
-        split, scube = _split_attention(table, index32, qkv, B, N, H, D)
-        if split:                                            # "bf16x3": split-bf16 products on the matrix pipe, the table read in the kernel
-            out, lse, hi, lo = attention_fwd_split(qkv, None if table is None else table.contiguous(), scube, B, N, H, D, scale)
-            ctx.save_for_backward(hi, lo, out, lse, index32, table)
-            ctx.dims = (B, N, H, D, scale, None if table is None else table.shape[0])
-            ctx.split_cube = (scube,)
-            return out
-        elif cube is not None:                               # the kernel reads the table itself: no dense rows in the forward pass
-            out, lse = attention_fwd_relpos(qkv, table.contiguous(), cube, B, N, H, D, scale)
-        else:
-            if table is not None:
-                bias, bias_t = relpos_bias_gather(table.contiguous(), index32, N, transposed=True)
-            out, lse = attention_fwd(qkv, bias, B, N, H, D, scale)
-        ctx.save_for_backward(qkv, out, lse, bias, bias_t, index32, table if cube is not None else None)
+        route = _AttnRoute(table, index32, qkv.dtype, B, N, H, D)
+        out, lse, keep, _ = _attention_forward(qkv, table, index32, route, B, N, H, D, scale)
+        # ("split": its images stand in for qkv; the table only where the backward kernels read it themselves)
+        ctx.save_for_backward(None if route.kind == "split" else qkv, out, lse, *keep, index32, None if route.kind == "dense" else table)
         ctx.dims = (B, N, H, D, scale, None if table is None else table.shape[0])
+        ctx.route = route
         return out
 
     @staticmethod
     def backward(ctx, dout):
         B, N, H, D, scale, n_bins = ctx.dims
-        if getattr(ctx, "split_cube", None) is not None:
-            hi, lo, out, lse, index32, table = ctx.saved_tensors
-            want_table = table is not None and ctx.needs_input_grad[1]
-            dqkv, slab, rows = attention_bwd_split(hi, lo, None if table is None else table.contiguous(), ctx.split_cube[0], out,
-                                                   dout.contiguous().float(), lse, B, N, H, D, scale, index32 if want_table else None, n_bins or 0)
-            dtable = None
-            if want_table:
-                dtable = torch.empty((n_bins, H), dtype=torch.float32, device=hi.device)
-                relpos_bias_scatter(slab, dtable, B, H, rows, n_bins)
-            return dqkv, dtable, None, None, None, None, None, None
-        qkv, out, lse, bias, bias_t, index32, table = ctx.saved_tensors
-        cube = None
-        if table is not None:
-            table, cube = table.contiguous(), index32._dm_cube      # (saved only where both backward passes read it themselves: relpos_inkernel)
-        want_table = (bias is not None or table is not None) and ctx.needs_input_grad[1]
-        dqkv, slab, rows = attention_bwd(qkv, bias, out, _as_operand(dout, qkv.dtype), lse, B, N, H, D, scale,
-                                         index32 if want_table else None, n_bins or 0, bias_t=bias_t, table=table, cube=cube)
+        qkv, out, lse, k0, k1, index32, table = ctx.saved_tensors
+        want_table = n_bins is not None and ctx.needs_input_grad[1]
+        dout = dout.contiguous().float() if ctx.route.kind == "split" else _as_operand(dout, qkv.dtype)
+        dqkv, slab, info = _attention_backward(ctx.route, qkv, (k0, k1), table, out, dout, lse, index32 if want_table else None, n_bins,
+                                               B, N, H, D, scale)
         dtable = None
         if want_table:
-            dtable = torch.empty((n_bins, H), dtype=torch.float32, device=qkv.device)
-            relpos_bias_scatter(slab, dtable, B, H, rows, n_bins)
+            dtable = torch.empty((n_bins, H), dtype=torch.float32, device=out.device)
+            relpos_bias_scatter(slab, dtable, B, H, info, n_bins)
         return dqkv, dtable, None, None, None, None, None, None
 
 
@@ -1387,17 +1422,12 @@ class BatchNormReluFn(torch.autograd.Function):
         rows_per_sample, training, relu = ctx.cfg
         M, Cc = x.shape
         dx = torch.empty_like(x)
-        gs, bs = _multi_use_sink(ctx.params[0], (Cc,)), _multi_use_sink(ctx.params[1], (Cc,))
-        direct = gs is not None and bs is not None
-        dg = gs if direct else torch.empty(Cc, dtype=torch.float32, device=x.device)
-        db = bs if direct else torch.empty(Cc, dtype=torch.float32, device=x.device)
+        g, b, acc = _norm_slots(*ctx.params, Cc, x.device)
         ws = workspace(_lib.lib().dm_batchnorm_workspace_bytes(M, Cc), x.device, "bn")
-        acc = _acc(ctx.params[0], direct)
-        _acc(ctx.params[1], direct)
         check(_lib.lib().dm_batchnorm_bwd(dy.float().contiguous().data_ptr(), x.data_ptr(), y.data_ptr(), gamma.data_ptr(), _ptr(mask), rows_per_sample,
-                                          mean.data_ptr(), rstd.data_ptr(), dx.data_ptr(), dg.data_ptr(), db.data_ptr(), int(acc), M, Cc,
+                                          mean.data_ptr(), rstd.data_ptr(), dx.data_ptr(), g.out.data_ptr(), b.out.data_ptr(), int(acc), M, Cc,
                                           int(training), int(relu), ws.data_ptr(), _stream()), "dm_batchnorm_bwd")
-        return dx, (None if direct else dg), (None if direct else db), None, None, None, None, None, None, None, None
+        return dx, g.grad(), b.grad(), None, None, None, None, None, None, None, None
 
 
 class TokenPoolFn(torch.autograd.Function):
@@ -1469,29 +1499,19 @@ class PoolNormFn(torch.autograd.Function):
         dev = dy.device
         dx = torch.empty((B, S * side * side, Cc), dtype=torch.float32, device=dev)
         dx_lp = torch.empty(dx.shape, dtype=torch.bfloat16, device=dev) if ctx.want_lp else None
-        gs, bs = _multi_use_sink(ctx.params[0], (Cc,)), _multi_use_sink(ctx.params[1], (Cc,))
-        sinks = gs is not None and bs is not None and ctx.needs_input_grad[1] and ctx.needs_input_grad[2]
-        if sinks:
-            dg, db, acc = gs, bs, _acc(ctx.params[0], True)
-            _acc(ctx.params[1], True)
-        else:
-            dg, db, acc = torch.empty(Cc, dtype=torch.float32, device=dev), torch.empty(Cc, dtype=torch.float32, device=dev), False
-        nfl = _lib.lib().dm_layernorm_bwd_partial_floats(Cc)
-        if sinks and _DEFER_REDUCTIONS and _in_backward():
-            part = torch.empty(nfl, dtype=torch.float32, device=dev)
-            n_part = C.c_int32(0)
-            check(_lib.lib().dm_pool_layernorm_bwd(dy.data_ptr(), pooled.data_ptr(), gamma.data_ptr(), mean.data_ptr(), rstd.data_ptr(), dx.data_ptr(),
-                                                   _ptr(dx_lp), None, None, 0, part.data_ptr(), C.byref(n_part), B, S, side, Cc, _stream()),
-                  "dm_pool_layernorm_bwd")
-            _queue_reduce(part, dg, db, n_part.value, 2 * Cc, Cc, acc)
-        else:
-            part = workspace(nfl * 4, dev, "partial")
-            check(_lib.lib().dm_pool_layernorm_bwd(dy.data_ptr(), pooled.data_ptr(), gamma.data_ptr(), mean.data_ptr(), rstd.data_ptr(), dx.data_ptr(),
-                                                   _ptr(dx_lp), dg.data_ptr(), db.data_ptr(), int(acc), part.data_ptr(), None, B, S, side, Cc, _stream()),
-                  "dm_pool_layernorm_bwd")
+        g, b, acc = _norm_slots(*ctx.params, Cc, dev, need=ctx.needs_input_grad[1] and ctx.needs_input_grad[2])
+        deferred = _deferred(g.direct)
+        part = _partial_rows(Cc, dev, deferred)
+        n_part = C.c_int32(0)
+        # (deferred: the kernel leaves the partial rows and their count; else it reduces them into dgamma / dbeta itself)
+        sums = (None, None, 0, part.data_ptr(), C.byref(n_part)) if deferred else (g.out.data_ptr(), b.out.data_ptr(), int(acc), part.data_ptr(), None)
+        check(_lib.lib().dm_pool_layernorm_bwd(dy.data_ptr(), pooled.data_ptr(), gamma.data_ptr(), mean.data_ptr(), rstd.data_ptr(), dx.data_ptr(),
+                                               _ptr(dx_lp), *sums, B, S, side, Cc, _stream()), "dm_pool_layernorm_bwd")
+        if deferred:
+            _reduce(part, g.out, b.out, n_part.value, 2 * Cc, Cc, acc, deferred)
         if dx_lp is not None:
-            dx._dm_lp_copy = (dx_lp, _grad_tag(dx))
-        return dx, (None if sinks else dg), (None if sinks else db), None, None, None, None
+            attach(dx, "_dm_lp_copy", dx_lp)
+        return dx, g.grad(), b.grad(), None, None, None, None
 
 
 class GroupMeanFn(torch.autograd.Function):
@@ -1683,69 +1703,40 @@ def _operand_grad(dy: torch.Tensor, dtype: torch.dtype, lp: Optional[torch.Tenso
     return _as_operand(dy, dtype)
 
 
-def _grad_out(param: torch.Tensor, shape, device):
-    """Where a parameter gradient should be written: straight into the trainer's flat gradient buffer
-    (`param._dm_grad_sink`, accumulate) when there is one, else a fresh tensor handed back to autograd."""
-    sink = getattr(param, "_dm_grad_sink", None)
-    if sink is not None:
-        return sink.view(shape), True
-    return torch.empty(shape, dtype=torch.float32, device=device), False
-
-
-def _acc(param, direct) -> bool:
-    """`accumulate` flag for a gradient write into `param`'s sink.  Parameters the trainer tracks (`_dm_gw`, set by FlatParams for the
-    parameters of the fused blocks) are not zeroed at the start of a step: their FIRST write of the step stores, later ones (a block
-    applied twice, gradient accumulation over several backward passes) add.  Untracked parameters: the buffer was zeroed, always add."""
-    if not direct:
-        return False
-    st = getattr(param, "_dm_gw", None)
-    if st is None or st[0]:
-        return True
-    st[0] = True
-    return False
-
-
-def _multi_use_sink(param, shape):
-    """Gradient sink for the generic Functions (Linear, Mlp, LayerNorm), whose parameters may be used several times per step
-    (the shared `norm`, the aux heads): their contributions accumulate into the trainer's flat buffer directly.  (The
-    data-parallel exchange works on whole backward segments, so it never needs to know when one parameter is complete.)"""
-    if param is None:
-        return None
-    sink = getattr(param, "_dm_grad_sink", None)
-    return None if sink is None else sink.view(shape)
-
-
-def _grad_done(param: torch.Tensor, g: torch.Tensor, direct: bool):
-    """Value to return to autograd for this parameter (None when it went to the sink)."""
-    if not direct:
-        return g.view(param.shape) if g.shape != param.shape else g
-    return None
-
-
-# Weight-gradient GEMMs of a block do not feed anything else in that block's backward: with DM_WGRAD_STREAM=<max tokens> they are
-# enqueued on a side stream (own split-K workspace) next to the dgrad chain for blocks of at most that many tokens, and joined
-# before the block's backward returns.  Meant for the small stages, whose kernels cannot fill the chip on their own.
-# Measured under graph replay: 6.96 ms/step with the 4096-token stages on the side stream, 6.75 ms with every block, 6.75 ms
-# without -- the fork / join edges cost what the overlap gains, so the default is off (0).  Round 4, faster kernels, same verdict:
-# 5.71-5.73 ms off, 5.88 ms with every block on the side stream, 5.87 ms with ONE join per backward pass instead of one per block,
-# 5.85 ms with only the <= 4096-token stages (the large kernels own a CU's whole LDS / register file, so nothing co-resides).
-_WGRAD_SIDE_TOKENS = int(os.environ.get("DM_WGRAD_STREAM", "0"))
-# The same independence, used the other way round (round 5): for blocks of at most DM_WGRAD_GROUP tokens the four weight gradients are
-# collected and issued at the END of the block's backward as ONE dm_gemm_grouped call -- 144 tiles in one launch of the 4-wave kernel, no K
-# slices, no slab, no reduction launches (tools/mb_grouped_estimate.py: 78 -> 34 us per block at 1024 tokens, 142 -> 85 us at 4096,
-# 250 -> 206 us at 12288; in the step the 16384-token blocks gain nothing -- every product fills the chip with its own slices).  Headline
-# step 5.28 -> 5.12 ms, "bf16x3" 11.03 -> 10.89 ms (same box, tools/ab_grouped.sh).  bf16 operands or plane pairs ("bf16x3"); 0 = off.
+# Weight-gradient GEMMs of a block do not feed anything else in that block's backward: for blocks of at most DM_WGRAD_GROUP tokens the
+# four weight gradients are collected and issued at the END of the block's backward as ONE dm_gemm_grouped call -- 144 tiles in one
+# launch of the 4-wave kernel, no K slices, no slab, no reduction launches (tools/mb_grouped_estimate.py: 78 -> 34 us per block at 1024
+# tokens, 142 -> 85 us at 4096, 250 -> 206 us at 12288; in the step the 16384-token blocks gain nothing -- every product fills the chip
+# with its own slices).  Headline step 5.28 -> 5.12 ms, "bf16x3" 11.03 -> 10.89 ms (same box, tools/ab_grouped.sh).  bf16 operands or
+# plane pairs ("bf16x3"); 0 = off.  (Running them on a second stream next to the dgrad chain instead was measured twice and never
+# won: DESIGN.md, next to the grouped weight gradients.)
 _WGRAD_GROUP_TOKENS = int(os.environ.get("DM_WGRAD_GROUP", "12288"))
 _WGRAD_PAIR = os.environ.get("DM_WGRAD_PAIR", "1") != "0"      # larger blocks: the proj and qkv gradients in one sliced launch
-_side_streams = {}
 
 
-def _side_stream(device):
-    key = torch.device(device).index
-    st = _side_streams.get(key)
-    if st is None:
-        st = _side_streams[key] = torch.cuda.Stream(device=device)
-    return st
+class _WgradQueue:
+    """When the weight-gradient products of one block's backward are issued.  fused (bf16 operands or plane pairs) and at most
+    _WGRAD_GROUP_TOKENS rows: all of them at the end, one grouped launch.  Larger fused blocks: every product fills the chip with its
+    own K slices, except the small proj gradient (12 tiles: 16 short slices) -- it waits for the qkv gradient and the two (`pair=True`)
+    share one sliced launch (dm_gemm_grouped's sliced form).  Everything else: at once."""
+
+    def __init__(self, fused: bool, M: int):
+        self.grouped = [] if (fused and 0 < M <= _WGRAD_GROUP_TOKENS) else None
+        self.late = [] if (self.grouped is None and fused and _WGRAD_PAIR) else None
+
+    def add(self, *a, pair: bool = False, **kw) -> None:
+        """One product, arguments as for gemm()."""
+        if self.grouped is not None:
+            self.grouped.append((a, kw))
+        elif self.late is not None and pair:
+            self.late.append((a, kw))
+        else:
+            gemm(*a, **kw)
+
+    def flush(self) -> None:
+        for calls in (self.grouped, self.late):
+            if calls:
+                gemm_grouped(calls)
 
 
 class BlockFn(torch.autograd.Function):
@@ -1781,29 +1772,17 @@ class BlockFn(torch.autograd.Function):
         if planes:      # (the optimizer's mirror pairs when a trainer keeps them: no per-step split of the weights)
             wq, wp, w1, w2 = (pair_weight(P, w) for P, w in ((qkv_w, wq), (proj_w, wp), (fc1_w, w1), (fc2_w, w2)))
         y1, mean1, rstd1 = layernorm_fwd(x2d, n1w, n1b, eps, dtype, pair=planes)
-        split, scube = _split_attention(table, index32, dtype, B, N, heads, D)
-        # (plane pairs + the split-bf16 attention: the qkv product writes the two images the attention kernels read)
+        route = _AttnRoute(table, index32, dtype, B, N, heads, D)
+        split = route.kind == "split"
+        # (plane pairs + the split-bf16 attention: the qkv product writes the two images the attention kernels read, and they write
+        # their result as a pair too)
         qkv = (Planes(torch.empty((2, M, 3 * Cc), dtype=torch.bfloat16, device=dev)) if (planes and split)
                else torch.empty((M, 3 * Cc), dtype=dtype, device=dev))
         gemm(DM_NT, y1, wq, qkv, M, 3 * Cc, Cc, lda=Cc, ldb=Cc, ldc=3 * Cc, bias=qkv_b)
-        bias = bias_t = None
-        cube = _inkernel_cube(table, index32, B, N, heads, D, dtype)
-        split_imgs = None
-        if split:
-            o_op = None
-            if planes:
-                o, lse, hi, lo, o_op = attention_fwd_split(qkv, None if table is None else table.contiguous(), scube, B, N, heads, D, scale, out_pair=True)
-            else:
-                o, lse, hi, lo = attention_fwd_split(qkv, None if table is None else table.contiguous(), scube, B, N, heads, D, scale)
-            split_imgs = (hi, lo, scube)
-        elif cube is not None:
-            o, lse = attention_fwd_relpos(qkv, table.contiguous(), cube, B, N, heads, D, scale)
-        else:
-            if table is not None:
-                bias, bias_t = relpos_bias_gather(table.contiguous(), index32, N, transposed=True)
-            o, lse = attention_fwd(qkv, bias, B, N, heads, D, scale)
+        o, lse, keep, o_op = _attention_forward(qkv, table, index32, route, B, N, heads, D, scale, out_pair=planes and split)
+        bias, bias_t = (None, None) if split else keep
         x1 = torch.empty((M, Cc), dtype=torch.float32, device=dev)
-        if not (planes and split):
+        if o_op is None:
             o_op = split_planes(o.view(M, Cc)) if planes else o.view(M, Cc)
         gemm(DM_NT, o_op, wp, x1, M, Cc, Cc, lda=Cc, ldb=Cc, ldc=Cc, bias=proj_b, residual=x2d)
         y2, mean2, rstd2 = layernorm_fwd(x1, n2w, n2b, eps, dtype, pair=planes)
@@ -1824,10 +1803,12 @@ class BlockFn(torch.autograd.Function):
         ctx.save_for_backward(x2d, mean1, rstd1, y1, qkv, o, lse, bias, bias_t, index32, x1, mean2, rstd2, y2, pre, h,
                               wq, wp, w1, w2, n1w, n2w, o_op if planes else None)
         ctx.dims = (B, N, Cc, heads, D, Hd, scale, None if table is None else table.shape[0])
-        ctx.table_in_kernel = cube is not None
-        ctx.split_imgs = split_imgs         # (two bf16 tensors of qkv's size, alive until this node's backward has run)
+        ctx.route = route
+        ctx.split_imgs = keep if split else None         # (two bf16 tensors of qkv's size, alive until this node's backward has run)
         ctx.params = (n1w, n1b, table, qkv_w, qkv_b, proj_w, proj_b, n2w, n2b, fc1_w, fc1_b, fc2_w, fc2_b)
         return x2.view(B, N, Cc)
+
+    _PARAMS = ("n1w", "n1b", "table", "qkv_w", "qkv_b", "proj_w", "proj_b", "n2w", "n2b", "fc1_w", "fc1_b", "fc2_w", "fc2_b")      # names of ctx.params
 
     @staticmethod
     @_replay_products
@@ -1837,132 +1818,81 @@ class BlockFn(torch.autograd.Function):
         planes = ctx.planes
         if planes:
             y1, y2, h, wq, wp, w1, w2, o_op = (Planes(t_) for t_ in (y1, y2, h, wq, wp, w1, w2, o_op))
-        (P_n1w, P_n1b, P_table, P_qkv_w, P_qkv_b, P_proj_w, P_proj_b, P_n2w, P_n2b, P_fc1_w, P_fc1_b, P_fc2_w, P_fc2_b) = ctx.params
+        P = dict(zip(BlockFn._PARAMS, ctx.params))
         B, N, Cc, heads, D, Hd, scale, n_bins = ctx.dims
         M = B * N
         dtype, dev = (torch.float32 if planes else y1.dtype), x.device
         lp = dtype != torch.float32
-        # the bf16 copy / the plane pair the LayerNorm backward of the NEXT block wrote next to this very tensor: one rule for both --
-        # (copy, _grad_tag at the time it was attached); a tag that no longer matches means the engine summed another contribution
-        # into the tensor in place, and the copy is stale
-        lp_copy = getattr(dx2, "_dm_lp_copy", None)
-        dy_pair = getattr(dx2, "_dm_planes", None)
-        lp_copy = lp_copy[0] if (lp_copy is not None and lp_copy[1] == _grad_tag(dx2)) else None
-        dy_pair = dy_pair[0] if (dy_pair is not None and dy_pair[1] == _grad_tag(dx2)) else None
+        slots = {}                                  # parameter name -> _GradSlot of every gradient this pass writes
+        wgrads = _WgradQueue(lp or planes, M)
+
+        def linear_grads(name, g2d, inp, n_out, n_in, pair=False):
+            """Layer `name`, y = inp W^T + b, given g2d = dy: the weight gradient g2d^T inp (queued) with the bias gradient riding on it
+            as the column sums of g2d -- of a plane pair: colsum(hi) + colsum(lo), whether the pair came from its producer or from the
+            split pass here, so the bias gradient does not depend on which of the two happened (a segmented backward hands over plain
+            tensors at its cuts).  Returns g2d as the operand of the two products that read it."""
+            w = slots[name + "_w"] = _GradSlot(P[name + "_w"], (n_out, n_in), dev)
+            b = slots[name + "_b"] = _GradSlot(P[name + "_b"], (n_out,), dev)
+            if planes and not isinstance(g2d, Planes):
+                g2d = split_planes(g2d)
+            wgrads.add(DM_TN, g2d, inp, w.out, n_out, n_in, M, lda=n_out, ldb=n_in, ldc=n_in, accumulate=w.acc(),
+                       colsum_out=b.out, colsum_accumulate=b.acc(), pair=pair)
+            return g2d
+
+        def norm_grads(name, dy_, x_, gamma, mean, rstd, dres, regroup=None):
+            """LayerNorm `name` backward with the residual gradient added: layernorm_bwd's result, dx with its bf16 copy / plane pair."""
+            g, b, acc = _norm_slots(P[name + "w"], P[name + "b"], Cc, dev)
+            slots[name + "w"], slots[name + "b"] = g, b
+            return layernorm_bwd(dy_, x_, gamma, mean, rstd, dres=dres, dgamma=g.out, dbeta=b.out, accumulate=acc, want_lp=lp, defer=g.direct,
+                                 want_pair=planes, regroup=regroup)
+
+        # the incoming gradient as an operand: the bf16 copy / the plane pair the LayerNorm backward of the NEXT block left on this very
+        # tensor while it is current, else a cast / a split (in linear_grads) here
+        lp_copy, dy_pair = attached(dx2, "_dm_lp_copy"), attached(dx2, "_dm_planes")
         dx2 = dx2.contiguous().view(M, Cc)
         dy = _operand_grad(dx2, dtype, lp_copy)
         if planes and isinstance(dy_pair, Planes) and (dy_pair.rows, dy_pair.cols) == (M, Cc):
             dy = dy_pair
-        # ---- MLP ---------------------------------------------------------------------------
-        dw2, k_w2 = _grad_out(P_fc2_w, (Cc, Hd), dev)
-        db2, k_b2 = _grad_out(P_fc2_b, (Cc,), dev)
-        side = _side_stream(dev) if 0 < M <= _WGRAD_SIDE_TOKENS else None
-
-        pending = [] if (side is None and (lp or planes) and 0 < M <= _WGRAD_GROUP_TOKENS) else None
-        # larger blocks: every product fills the chip with its own K slices, except the small proj gradient (12 tiles: 16 short slices) --
-        # it waits for the qkv gradient and the two share one sliced launch (dm_gemm_grouped's sliced form)
-        late = [] if (pending is None and side is None and (lp or planes) and _WGRAD_PAIR) else None
-
-        def wgrad(*a, pair=False, **kw):
-            if pending is not None:           # issued together at the end of this backward (gemm_grouped)
-                pending.append((a, kw))
-                return None
-            if late is not None and pair:
-                late.append((a, kw))
-                return None
-            if side is None:
-                return gemm(*a, **kw)
-            side.wait_stream(torch.cuda.current_stream())          # the operands' producers
-            with torch.cuda.stream(side):
-                return gemm(*a, ws_slot="gemm_side", **kw)
-
-        def bias_grad(g2d, db, acc_b, direct):
-            """(operand for the two products that read the gradient g2d, kwargs that make the weight-gradient call produce db).
-            The column sums always ride on the weight gradient -- of a plane pair: colsum(hi) + colsum(lo), whether the pair came
-            from its producer or from the split pass here, so the bias gradient does not depend on which of the two happened
-            (a segmented backward hands over plain tensors at its cuts)."""
-            if planes and not isinstance(g2d, Planes):
-                g2d = split_planes(g2d)
-            return g2d, dict(colsum_out=db, colsum_accumulate=acc_b)
-        dy, cs = bias_grad(dy, db2, _acc(P_fc2_b, k_b2), k_b2)
-        wgrad(DM_TN, dy, h, dw2, Cc, Hd, M, lda=Cc, ldb=Hd, ldc=Hd, accumulate=_acc(P_fc2_w, k_w2), **cs)
+        # ---- fc2, GELU' (in the dgrad epilogue) -----------------------------------------------
+        dy = linear_grads("fc2", dy, h, Cc, Hd)
         dpre = Planes(torch.empty((2, M, Hd), dtype=torch.bfloat16, device=dev)) if planes else torch.empty((M, Hd), dtype=dtype, device=dev)
         gemm(DM_NN, dy, w2, dpre, M, Hd, Cc, lda=Cc, ldb=Hd, ldc=None if planes else Hd, epilogue=DM_EPI_MUL, aux=pre, ldaux=Hd)
-        dw1, k_w1 = _grad_out(P_fc1_w, (Hd, Cc), dev)
-        db1, k_b1 = _grad_out(P_fc1_b, (Hd,), dev)
-        dpre, cs = bias_grad(dpre, db1, _acc(P_fc1_b, k_b1), k_b1)
-        wgrad(DM_TN, dpre, y2, dw1, Hd, Cc, M, lda=Hd, ldb=Cc, ldc=Cc, accumulate=_acc(P_fc1_w, k_w1), **cs)
+        # ---- fc1 ------------------------------------------------------------------------------
+        dpre = linear_grads("fc1", dpre, y2, Hd, Cc)
         dy2 = torch.empty((M, Cc), dtype=dtype, device=dev)
         gemm(DM_NN, dpre, w1, dy2, M, Cc, Hd, lda=Hd, ldb=Cc, ldc=Cc)
-        dg2, k_n2 = _grad_out(P_n2w, (Cc,), dev)
-        dbt2, k_n2b = _grad_out(P_n2b, (Cc,), dev)
-        if k_n2 != k_n2b:      # mixed sinks: fall back to fresh tensors for both
-            dg2, dbt2, k_n2, k_n2b = torch.empty(Cc, device=dev), torch.empty(Cc, device=dev), False, False
-        a_n2 = _acc(P_n2w, k_n2)
-        _acc(P_n2b, k_n2b)                              # (gamma and beta are written by the same launch)
-        r = layernorm_bwd(dy2, x1, n2w, mean2, rstd2, dres=dx2, dgamma=dg2, dbeta=dbt2, accumulate=a_n2, want_lp=lp, defer=bool(k_n2 and k_n2b),
-                          want_pair=planes)
-        dx1, dx1_lp = (r[0], r[1]) if (lp or planes) else (r[0], r[0])      # (planes: r[1] is the plane pair of dx1)
-        # ---- attention -----------------------------------------------------------------------
-        dwp, k_wp = _grad_out(P_proj_w, (Cc, Cc), dev)
-        dbp, k_bp = _grad_out(P_proj_b, (Cc,), dev)
-        dx1_op, cs = bias_grad(dx1_lp, dbp, _acc(P_proj_b, k_bp), k_bp)
-        wgrad(DM_TN, dx1_op, o_op if planes else o.view(M, Cc), dwp, Cc, Cc, M, lda=Cc, ldb=Cc, ldc=Cc, accumulate=_acc(P_proj_w, k_wp), pair=True, **cs)
+        # ---- LN2 (+ dx2, the residual's gradient) ---------------------------------------------
+        r = norm_grads("n2", dy2, x1, n2w, mean2, rstd2, dx2)
+        dx1, dx1_op = r[0], (r[1] if (lp or planes) else r[0])      # (the operand: dx1's bf16 copy, its plane pair, or dx1 itself)
+        # ---- proj -----------------------------------------------------------------------------
+        dx1_op = linear_grads("proj", dx1_op, o_op if planes else o.view(M, Cc), Cc, Cc, pair=True)
         do = torch.empty((M, Cc), dtype=dtype, device=dev)
         gemm(DM_NN, dx1_op, wp, do, M, Cc, Cc, lda=Cc, ldb=Cc, ldc=Cc)
-        tab, cube = None, None
-        if ctx.split_imgs is not None:                       # "bf16x3": the split-bf16 backward kernels (table read in the kernel, slab included)
-            hi, lo, scube = ctx.split_imgs
-            ctx.split_imgs = None
-            want_table = P_table is not None
-            dqkv, slab, rows = attention_bwd_split(hi, lo, None if P_table is None else P_table.detach().contiguous(), scube, o.view(B, N, Cc),
-                                                   do.view(B, N, Cc), lse, B, N, heads, D, scale, index32 if want_table else None, n_bins or 0,
-                                                   pair=planes)
-        else:
-            if ctx.table_in_kernel:                          # the forward kernel read the table itself; so do both backward passes
-                tab, cube = P_table.detach().contiguous(), index32._dm_cube
-            want_table = bias is not None or tab is not None
-            dqkv, slab, rows = attention_bwd(qkv, bias, o, do, lse, B, N, heads, D, scale,
-                                             index32 if want_table else None, n_bins or 0, bias_t=bias_t, table=tab, cube=cube)
-        dtable, k_t = None, False
+        # ---- attention ------------------------------------------------------------------------
+        keep = ctx.split_imgs if ctx.route.kind == "split" else (bias, bias_t)
+        ctx.split_imgs = None
+        want_table = P["table"] is not None
+        dqkv, slab, info = _attention_backward(ctx.route, qkv, keep, P["table"].detach() if want_table else None, o, do.view(B, N, Cc), lse,
+                                               index32 if want_table else None, n_bins, B, N, heads, D, scale, pair=planes)
         if want_table:
-            dtable, k_t = _grad_out(P_table, (n_bins, heads), dev)
-            relpos_bias_scatter(slab, dtable, B, heads, rows, n_bins, accumulate=_acc(P_table, k_t))
-        dqkv2 = dqkv if isinstance(dqkv, Planes) else dqkv.view(M, 3 * Cc)
-        dwq, k_wq = _grad_out(P_qkv_w, (3 * Cc, Cc), dev)
-        dbq, k_bq = _grad_out(P_qkv_b, (3 * Cc,), dev)
-        dqkv_op, cs = bias_grad(dqkv2, dbq, _acc(P_qkv_b, k_bq), k_bq)
-        wgrad(DM_TN, dqkv_op, y1, dwq, 3 * Cc, Cc, M, lda=3 * Cc, ldb=Cc, ldc=Cc, accumulate=_acc(P_qkv_w, k_wq), pair=True, **cs)
+            t = slots["table"] = _GradSlot(P["table"], (n_bins, heads), dev)
+            relpos_bias_scatter(slab, t.out, B, heads, info, n_bins, accumulate=t.acc())
+        # ---- qkv ------------------------------------------------------------------------------
+        dqkv = linear_grads("qkv", dqkv if isinstance(dqkv, Planes) else dqkv.view(M, 3 * Cc), y1, 3 * Cc, Cc, pair=True)
         dy1 = torch.empty((M, Cc), dtype=dtype, device=dev)
-        gemm(DM_NN, dqkv_op, wq, dy1, M, Cc, 3 * Cc, lda=3 * Cc, ldb=Cc, ldc=Cc)
-        dg1, k_n1 = _grad_out(P_n1w, (Cc,), dev)
-        dbt1, k_n1b = _grad_out(P_n1b, (Cc,), dev)
-        if k_n1 != k_n1b:
-            dg1, dbt1, k_n1, k_n1b = torch.empty(Cc, device=dev), torch.empty(Cc, device=dev), False, False
-        a_n1 = _acc(P_n1w, k_n1)
-        _acc(P_n1b, k_n1b)
+        gemm(DM_NN, dqkv, wq, dy1, M, Cc, 3 * Cc, lda=3 * Cc, ldb=Cc, ldc=Cc)
+        # ---- LN1 (+ dx1) ----------------------------------------------------------------------
         regroup = ctx.lp_rows if (lp and dtype == torch.bfloat16 and _FUSED_GLUE and Cc <= _PAIR_LN_MAX_COLS) else None
-        r = layernorm_bwd(dy1, x, n1w, mean1, rstd1, dres=dx1, dgamma=dg1, dbeta=dbt1, accumulate=a_n1, want_lp=lp, defer=bool(k_n1 and k_n1b),
-                          want_pair=planes, regroup=regroup)
-        if side is not None:
-            torch.cuda.current_stream().wait_stream(side)          # join: every weight gradient of this block is complete
-        if pending:
-            gemm_grouped(pending)
-        if late:
-            gemm_grouped(late)
+        r = norm_grads("n1", dy1, x, n1w, mean1, rstd1, dx1, regroup=regroup)
+        wgrads.flush()
         dx = r[0].view(B, N, Cc)
+        # what the LayerNorm backward wrote next to dx rides on the tensor object autograd hands to the next node; a consumer that gets
+        # some other tensor, or this one after an in-place sum, simply casts / splits
         if regroup is not None:      # (under its own name: in this row order it is of use to PatchEmbedCatFn.backward alone)
-            dx._dm_lp_regrouped = (r[1], _grad_tag(dx), regroup)
+            attach(dx, "_dm_lp_regrouped", r[1], regroup)
         elif lp:
-            # The bf16 copy the LayerNorm backward wrote rides on the tensor object autograd hands to the next node (the
-            # engine preserves the Python object); a consumer that gets some other tensor, or this one after an in-place sum, simply casts.
-            dx._dm_lp_copy = (r[1], _grad_tag(dx))
+            attach(dx, "_dm_lp_copy", r[1])
         if planes:
-            dx._dm_planes = (r[1], _grad_tag(dx))      # likewise the plane pair ("bf16x3"); a consumer that gets another tensor splits
-        return (dx, _grad_done(P_n1w, dg1, k_n1), _grad_done(P_n1b, dbt1, k_n1b),
-                _grad_done(P_table, dtable, k_t) if want_table else None, None,
-                _grad_done(P_qkv_w, dwq, k_wq), _grad_done(P_qkv_b, dbq, k_bq),
-                _grad_done(P_proj_w, dwp, k_wp), _grad_done(P_proj_b, dbp, k_bp),
-                _grad_done(P_n2w, dg2, k_n2), _grad_done(P_n2b, dbt2, k_n2b),
-                _grad_done(P_fc1_w, dw1, k_w1), _grad_done(P_fc1_b, db1, k_b1),
-                _grad_done(P_fc2_w, dw2, k_w2), _grad_done(P_fc2_b, db2, k_b2), None, None, None, None)
+            attach(dx, "_dm_planes", r[1])
+        grads = [slots[n].grad() if n in slots else None for n in BlockFn._PARAMS]
+        return (dx, *grads[:3], None, *grads[3:], None, None, None, None)      # (forward's arguments: index32 sits between the table and qkv_w)

@@ -55,7 +55,7 @@ class FlatParams:
                  pair_mirror: bool = False):
         """first_write (default: on unless DM_GRAD_FIRST_WRITE=0): for models whose fused blocks are the only writers of their
         parameters' gradients (`_dm_first_write_blocks` on the model class, `_dm_fused_block` on the block class) those gradients
-        are not zeroed at the start of a step; the first write of the step stores instead (ops._acc).  Saves the 195 MB memset and
+        are not zeroed at the start of a step; the first write of the step stores instead (ops._GradSlot.acc).  Saves the 195 MB memset and
         the read of every weight gradient by its own first accumulation."""
         params = [p for p in module.parameters() if p.requires_grad]
         params.reverse()                      # backward order: last-used parameters first
@@ -84,7 +84,7 @@ class FlatParams:
             if self.flat_pair is not None:
                 p._dm_pair_src = (self.flat_pair, o)
             if dev.type == "cuda":
-                # fused backward kernels accumulate straight into the flat gradient buffer (ops._grad_out)
+                # fused backward kernels accumulate straight into the flat gradient buffer (ops._GradSlot)
                 p._dm_grad_sink = self.grad[o:o + n].view_as(p)
         # ---- first-write gradient sinks ----------------------------------------------------------------------------------
         if first_write is None:
