@@ -65,7 +65,7 @@ def train(net, margin, train_bs, lr_init, normMean, normStd, lamda, belta, is_re
           dataset: PairDataset = None, num_epochs: int = NUM_EPOCHS, milestones: Sequence[int] = (40, 80), gamma: float = 0.2,
           model_paras_path: str = MODEL_PARAS_PATH, val_dataset: Optional[PairDataset] = None, val_batch: int = 1000,
           val_thresholds: Optional[Sequence[float]] = None, log_dir: Optional[str] = None,
-          val_history: Optional[list] = None, augment: Optional[str] = None) -> Tuple[List[int], List[float]]:
+          val_history: Optional[list] = None, augment: Optional[str] = None, radiometric=None) -> Tuple[List[int], List[float]]:
     """`Train_SMT.train` with the reference's positional signature (normMean / normStd are unused, as upstream; lamda / belta go
     to Loss).  `dataset` replaces the reference's hard-coded shapefile folders; the draw's seed is the dataset's.  Returns
     (epoch indices, per-epoch mean loss = sum of step losses / number of steps), one entry per epoch run.
@@ -77,7 +77,11 @@ def train(net, margin, train_bs, lr_init, normMean, normStd, lamda, belta, is_re
 
     augment: None, "flips" or "d4" -- handed to dataset.epoch: every pair of every epoch is fed at a dihedral orientation keyed by
     (dataset seed, epoch, pair), both of its crops alike, so a resumed run sees the same views.  The
-    validation pass never augments."""
+    validation pass never augments.
+
+    radiometric: None, an ops.Radiometric or a (contrast, brightness, colour) triple -- handed to dataset.epoch: every pair of every
+    epoch is fed with a gain and an offset per band keyed by (dataset seed, epoch, pair), both of its crops and designed rows alike
+    (DESIGN.md 3.8 / 3.9).  Independent of `augment`; resumes like it; never applied in validation."""
     if dataset is None:
         raise ValueError("train() needs dataset=PairDataset.from_arrays(...) (the reference's hard-coded folders are not portable)")
     if val_dataset is not None and val_dataset is dataset:
@@ -89,6 +93,7 @@ def train(net, margin, train_bs, lr_init, normMean, normStd, lamda, belta, is_re
         raise ValueError(f"train_bs must be >= 1, got {train_bs}")
     if augment is not None and augment not in ops.ORIENT_MASKS:
         raise ValueError(f"augment must be None, 'flips' or 'd4', got {augment!r}")
+    radiometric = ops.Radiometric.of(radiometric)
     scales = [int(s) for s in getattr(net, "input_image_scales", ())]
     if not scales:
         raise ValueError(f"{type(net).__name__} has no input_image_scales: train() feeds patch pyramids")
@@ -125,7 +130,7 @@ def train(net, margin, train_bs, lr_init, normMean, normStd, lamda, belta, is_re
     for epoch in range(start_epoch, num_epochs):
         lr = epoch_lr(lr0, epoch - start_epoch, milestones, gamma)
         trainer.lr = lr                         # what the optimizer holds this epoch (checkpoint.optimizer_state_dict writes it)
-        table = dataset.epoch(epoch, B, augment=augment)
+        table = dataset.epoch(epoch, B, augment=augment, radiometric=radiometric)
         total = torch.zeros((), dtype=torch.float32, device=dev)
         for s in range(len(table)):
             if s < n_full:

@@ -12,6 +12,8 @@
 //                     likewise with r[1] -- keyed by the pair, so shuffle and draw are independent
 //   orient            dm_pair_epoch_orient: philox((src, epoch, 3, 0))[0] & mask (7: the dihedral group D4, 3: flips only), the
 //                     augmentation of dm_pair_batch_gather_oriented, written to both rows of the pair
+//   radiometric       dm_pair_epoch_radiometric: counter word 4 -- a gain and an offset per pair, a gain deviation per band (the table of
+//                     dm_pair_batch_gather_augmented), written to both rows of the pair
 // One thread per position: integer VALU work plus a gather of the two 80-byte point rows.  A pair whose polygon id, point list or
 // point id is out of range (the host validates them once, at dataset construction) reads nothing out of range: its sample gets
 // point_id -1, tile id -1 (which the feed's gather flags) and zeros.
@@ -111,6 +113,39 @@ __global__ __launch_bounds__(256) void pair_epoch_orient_kernel(uint64_t seed, i
   orient[row_l + b_s] = o;
 }
 
+// uniform on -s .. s from one random word (0 when s = 0)
+__device__ __forceinline__ int32_t sym_draw(uint32_t r, int32_t s) { return (int32_t)__umulhi(r, 2u * (uint32_t)s + 1u) - s; }
+
+// the radiometric table of every pair of the epoch: counter word 4, keyed by the pair like the orientation.  A common gain and offset
+// from block 0, one gain deviation per band from blocks 1 + c / 4, the offset pivoting the contrast about mid-grey (128); written to both
+// of the pair's rows as [row][band][gain, offset]
+__global__ __launch_bounds__(256) void pair_epoch_radiometric_kernel(uint64_t seed, int32_t epoch_, int32_t n_pairs, int32_t batch_, int32_t bands,
+                                                                     int32_t gain_span, int32_t band_span, int32_t offset_span,
+                                                                     int32_t *__restrict__ radio, int h) {
+  const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= n_pairs) return;
+  const uint32_t k0 = (uint32_t)(seed & 0xffffffffull), k1 = (uint32_t)(seed >> 32);
+  const uint32_t epoch = (uint32_t)epoch_;
+  const uint32_t src = epoch_perm((uint32_t)j, (uint32_t)n_pairs, h, epoch, k0, k1);
+  const u32x4 A = philox4x32_10(src, epoch, 4u, 0u, k0, k1);
+  const int32_t g0 = 256 + sym_draw(A[0], gain_span), b0 = sym_draw(A[1], offset_span);
+  const int64_t batch = batch_, s = j / batch;
+  const int64_t b_s = min(batch, (int64_t)n_pairs - s * batch);
+  const int64_t row_l = s * batch + j;
+  int32_t *left = radio + row_l * bands * 2, *right = radio + (row_l + b_s) * bands * 2;
+  for (int c0 = 0; c0 < bands; c0 += 4) {
+    const u32x4 B = philox4x32_10(src, epoch, 4u, 1u + (uint32_t)(c0 >> 2), k0, k1);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const int c = c0 + k;
+      if (c >= bands) break;
+      const int32_t gain = g0 + sym_draw(B[k], band_span), offset = b0 - 128 * (gain - 256);
+      left[2 * c] = gain; left[2 * c + 1] = offset;
+      right[2 * c] = gain; right[2 * c + 1] = offset;
+    }
+  }
+}
+
 // ceil(log2 N), rounded up to even, >= 2: the width of the shuffle's Feistel network
 int feistel_bits(int32_t n_pairs) {
   int b = 2;
@@ -131,6 +166,27 @@ extern "C" int dm_pair_epoch_orient(uint64_t seed, int32_t epoch, int32_t n_pair
   hipLaunchKernelGGL(pair_epoch_orient_kernel, dim3(blocks), dim3(threads), 0, reinterpret_cast<hipStream_t>(stream), seed, epoch, n_pairs, batch,
                      (uint32_t)mask, orient, feistel_bits(n_pairs) / 2);
   DM_LAUNCH_CHECK("dm_pair_epoch_orient");
+  return DM_OK;
+}
+
+extern "C" int dm_pair_epoch_radiometric(uint64_t seed, int32_t epoch, int32_t n_pairs, int32_t batch, int32_t bands, int32_t gain_span,
+                                         int32_t band_span, int32_t offset_span, int32_t *radio, void *stream) {
+  DM_REQUIRE(gain_span >= 0 && gain_span <= DM_RADIO_MAX_GAIN_SPAN, DM_ERR_BAD_SHAPE, "dm_pair_epoch_radiometric: gain span %d outside 0..%d",
+             gain_span, DM_RADIO_MAX_GAIN_SPAN);
+  DM_REQUIRE(band_span >= 0 && band_span <= DM_RADIO_MAX_BAND_SPAN, DM_ERR_BAD_SHAPE, "dm_pair_epoch_radiometric: band span %d outside 0..%d",
+             band_span, DM_RADIO_MAX_BAND_SPAN);
+  DM_REQUIRE(offset_span >= 0 && offset_span <= DM_RADIO_MAX_OFFSET_SPAN, DM_ERR_BAD_SHAPE,
+             "dm_pair_epoch_radiometric: offset span %d outside 0..%d", offset_span, DM_RADIO_MAX_OFFSET_SPAN);
+  DM_REQUIRE(bands >= 1 && bands <= 16, DM_ERR_BAD_SHAPE, "dm_pair_epoch_radiometric: %d bands (1 .. 16)", bands);
+  DM_REQUIRE(n_pairs >= 1 && n_pairs <= (1 << 30), DM_ERR_BAD_SHAPE, "dm_pair_epoch_radiometric: %d pairs (1 .. 2^30)", n_pairs);
+  DM_REQUIRE(batch >= 1, DM_ERR_BAD_SHAPE, "dm_pair_epoch_radiometric: batch %d < 1", batch);
+  DM_REQUIRE(epoch >= 0, DM_ERR_BAD_SHAPE, "dm_pair_epoch_radiometric: epoch %d < 0", epoch);
+  DM_REQUIRE(radio != nullptr, DM_ERR_BAD_SHAPE, "dm_pair_epoch_radiometric: bad arguments (null output)");
+  const int threads = 256;
+  const int blocks = (int)((n_pairs + threads - 1) / threads);
+  hipLaunchKernelGGL(pair_epoch_radiometric_kernel, dim3(blocks), dim3(threads), 0, reinterpret_cast<hipStream_t>(stream), seed, epoch, n_pairs,
+                     batch, bands, gain_span, band_span, offset_span, radio, feistel_bits(n_pairs) / 2);
+  DM_LAUNCH_CHECK("dm_pair_epoch_radiometric");
   return DM_OK;
 }
 

@@ -106,8 +106,10 @@ __device__ __forceinline__ int cv_area_pixel(const unsigned char *win, int L, in
 // whose tile id or window is out of range gets zeros and raises `err[0]` (read back by the host every few steps, not per step).
 // `orient` (dm_pair_batch_gather_oriented, read by the ORIENT instantiations only): the sample's dihedral orientation 0..7; any
 // other value is fed as zeros and flagged like a bad tile id.
+// `radio` (dm_pair_batch_gather_augmented, read by the RADIO instantiations only): int32 [P, bands, 2], the (gain, offset) of every
+// (sample, band); a sample with any value out of range is fed as zeros and flagged, its designed row written untransformed.
 struct BatchTable {
-  const int *tile_id, *inner, *obj, *orient;
+  const int *tile_id, *inner, *obj, *orient, *radio;
   const float *region;
   float *designed;
   int *err;
@@ -117,7 +119,12 @@ struct BatchTable {
 // ORIENT: the staged window is crop' = D4 element orient[p] applied to the zero-padded crop (bit 1: rows mirrored, bit 0: columns
 // mirrored, then bit 2: transposed) -- crop'[j][i] = crop[fy(a)][fx(b)] with (a, b) = (i, j) under bit 2 and (j, i) otherwise --
 // and everything after the staging runs on crop' unchanged.  ORIENT = false compiles to the code this kernel had without the flag.
-template <int TLOG2, typename OUT, bool COLS, bool ORIENT>
+// RADIO (instantiated with ORIENT only; a null `orient` is then orientation 0): every staged byte v that lies inside the raster becomes
+// min(255, max(0, (gain v + offset + 128) >> 8)) -- gain Q8 in 0..1023, offset in 1/256 grey levels in -65535..65535, both per (sample,
+// band), the shift arithmetic -- and the padding stays 0; per pixel, so it commutes with the index map above.  The designed row moves
+// with it to first order (include/deepmerge_hip.h states the fp32 sequence).  RADIO = false compiles to the code without the flag.
+constexpr int RADIO_GAIN_MAX = 1023, RADIO_OFFSET_MAX = 65535;
+template <int TLOG2, typename OUT, bool COLS, bool ORIENT, bool RADIO = false>
 __global__ __launch_bounds__(256) void patch_pyramid_kernel(const unsigned char *__restrict__ tile, int bands, int H, int W,
                                                             const int *__restrict__ xy, const int *__restrict__ wins,
                                                             int Trt, int G, OUT *__restrict__ out, int rule, const BatchTable bt) {
@@ -125,19 +132,56 @@ __global__ __launch_bounds__(256) void patch_pyramid_kernel(const unsigned char 
   const int T = TLOG2 >= 0 ? (1 << TLOG2) : Trt;
   auto divT = [&](int v) { return TLOG2 >= 0 ? (v >> TLOG2) : v / T; };
   const int p = blockIdx.x, c = blockIdx.y, t = threadIdx.x;
-  int L, tid = 0, orient = 0;
+  int L, tid = 0, orient = 0, gain = 256, offset = 0;
+  bool radio_bad = false;
   if (bt.inner) {
     const int in = bt.inner[p], ob = bt.obj[p], iv = ob - in;
     L = bt.scale_index == 0 ? in : ob + (bt.scale_index - 1) * iv;
     tid = bt.tile_id ? bt.tile_id[p] : 0;
-    if constexpr (ORIENT) orient = bt.orient[p];
+    if constexpr (ORIENT && !RADIO) orient = bt.orient[p];
+    if constexpr (RADIO) {
+      static_assert(ORIENT, "RADIO is instantiated together with ORIENT");
+      orient = bt.orient ? bt.orient[p] : 0;
+      const int *rp = bt.radio + (long long)p * bands * 2;
+      gain = rp[2 * c]; offset = rp[2 * c + 1];
+      // one bad band zero-fills the whole sample.  Every wave reads the sample's row across its lanes and votes: one load in flight
+      // beside the scalar ones above, where a loop over the bands would be a chain of dependent round trips in every block's prologue
+      bool lane_bad = false;
+      for (int k = t & 63; k < 2 * bands; k += 64) {
+        const int v = rp[k];
+        lane_bad |= (k & 1) ? (v < -RADIO_OFFSET_MAX || v > RADIO_OFFSET_MAX) : ((unsigned)v > (unsigned)RADIO_GAIN_MAX);
+      }
+      radio_bad = __any(lane_bad);
+    }
     if (c == 0 && bt.designed && t < 19) {
       const int k = t - 15;
       const float wk = (float)(k == 0 ? in : ob + (k - 1) * iv);
       const float sk = k == 0 ? 32.f : k == 1 ? 64.f : k == 2 ? 128.f : 1.f;          // config.py:32 (patches.CONFIG_SCALES)
-      bt.designed[(long long)p * 19 + t] = t < 15 ? bt.region[(long long)p * 15 + t] : __fdiv_rn(wk, sk);
+      float d = t < 15 ? bt.region[(long long)p * 15 + t] : __fdiv_rn(wk, sk);
+      if constexpr (RADIO) {
+        // oracle/rag.py's attribute order: std at 5..7, means at 8..10, bright at 13; bands beyond the third carry no attribute
+        const int nb = min(bands, 3);
+        const float *reg = bt.region + (long long)p * 15;
+        const int *rp = bt.radio + (long long)p * bands * 2;
+        auto gf = [&](int b) { return __fdiv_rn((float)rp[2 * b], 256.f); };
+        auto moved_mean = [&](int b) {
+          float m = __fadd_rn(__fmul_rn(gf(b), reg[8 + b]), __fdiv_rn((float)rp[2 * b + 1], 256.f));
+          m = m < 0.f ? 0.f : m;
+          return m > 255.f ? 255.f : m;
+        };
+        if (!radio_bad) {
+          if (t >= 5 && t < 5 + nb) d = __fmul_rn(gf(t - 5), d);
+          else if (t >= 8 && t < 8 + nb) d = moved_mean(t - 8);
+          else if (t == 13) {
+            float sum = __fsub_rn(moved_mean(0), reg[8]);
+            for (int b = 1; b < nb; ++b) sum = __fadd_rn(sum, __fsub_rn(moved_mean(b), reg[8 + b]));
+            d = __fadd_rn(d, __fdiv_rn(sum, (float)nb));
+          }
+        }
+      }
+      bt.designed[(long long)p * 19 + t] = d;
     }
-    if (L <= 0 || L > bt.max_window || tid < 0 || tid >= bt.n_tiles || (ORIENT && (unsigned)orient > 7u)) {   // (uniform per block)
+    if (L <= 0 || L > bt.max_window || tid < 0 || tid >= bt.n_tiles || (ORIENT && (unsigned)orient > 7u) || (RADIO && radio_bad)) {   // (uniform per block)
       if (t == 0 && bt.err) atomicOr(bt.err, 1);
       const int ps0 = COLS ? T / G : 1;
       const long long Kc0 = (long long)bands * ps0 * ps0;
@@ -165,7 +209,50 @@ __global__ __launch_bounds__(256) void patch_pyramid_kernel(const unsigned char 
   const int jA = gridDim.z > 1 ? max(0, (int)((long long)oyA * L / T) - 1) : 0;
   const int jB = gridDim.z > 1 ? min(L, (int)(((long long)oyB * L + T - 1) / T) + 2) : L;
   // window -> LDS, row by row: a wave walks along a row (coalesced bytes), no per-element division
-  if constexpr (ORIENT) {
+  if constexpr (RADIO) {
+    // The rule sits between a byte's load and its LDS write, and the staging loops below keep one byte per thread in flight: the
+    // multiply-add (24-bit: gain < 2^10, v < 2^8), shift, clamp and the pad's zero, selected after the transform, would lengthen that
+    // chain for every byte.  So this form stages two bytes per thread and trip -- rows j and j + 4, or two steps of the transposed
+    // walk -- with both loads issued before either transform.
+    const int bias = offset + 128;
+    auto rule = [&](bool in, int v) -> unsigned char { return (unsigned char)(in ? min(255, max(0, (__mul24(gain, v) + bias) >> 8)) : 0); };
+    auto stage2 = [&](bool inA, const unsigned char *atA, int dA, bool hasB, bool inB, const unsigned char *atB, int dB) {
+      inB = inB && hasB;
+      const int va = inA ? (int)*atA : 0, vb = inB ? (int)*atB : 0;
+      win[dA] = rule(inA, va);
+      if (hasB) win[dB] = rule(inB, vb);
+    };
+    const bool flip_y = orient & 2, flip_x = orient & 1;
+    if (orient & 4) {
+      const int nj = jB - jA, qi = 256 / nj, ri = 256 - qi * nj;        // (the walk of the ORIENT form below)
+      int i = t / nj, jj = t - i * nj;
+      while (i < L) {
+        int i2 = i + qi, jj2 = jj + ri;
+        if (jj2 >= nj) { jj2 -= nj; ++i2; }
+        const bool hasB = i2 < L;
+        const int ja = jA + jj, jb = jA + jj2;
+        const int gyA = y0 + (flip_y ? L - 1 - i : i), gxA = x0 + (flip_x ? L - 1 - ja : ja);
+        const int gyB = y0 + (flip_y ? L - 1 - i2 : i2), gxB = x0 + (flip_x ? L - 1 - jb : jb);
+        stage2(gyA >= 0 && gyA < H && gxA >= 0 && gxA < W, band + ((long long)gyA * W + gxA), ja * L + i, hasB,
+               gyB >= 0 && gyB < H && gxB >= 0 && gxB < W, band + ((long long)gyB * W + gxB), jb * L + i2);
+        i = i2 + qi; jj = jj2 + ri;
+        if (jj >= nj) { jj -= nj; ++i; }
+      }
+    } else {
+      for (int j = jA + (t >> 6); j < jB; j += 8) {
+        const int jb = j + 4;
+        const bool hasB = jb < jB;                               // (uniform per wave)
+        const int gyA = y0 + (flip_y ? L - 1 - j : j), gyB = y0 + (flip_y ? L - 1 - jb : jb);
+        const bool rowA = gyA >= 0 && gyA < H, rowB = gyB >= 0 && gyB < H;
+        const unsigned char *srcA = band + (long long)gyA * W, *srcB = band + (long long)gyB * W;
+        for (int i = t & 63; i < L; i += 64) {
+          const int gx = x0 + (flip_x ? L - 1 - i : i);
+          const bool col = gx >= 0 && gx < W;
+          stage2(rowA && col, srcA + gx, j * L + i, hasB, rowB && col, srcB + gx, jb * L + i);
+        }
+      }
+    }
+  } else if constexpr (ORIENT) {
     const bool flip_y = orient & 2, flip_x = orient & 1;
     if (orient & 4) {
       // crop'[j][i] = crop[fy(i)][fx(j)]: the band's rows [jA, jB) are COLUMNS of the raster window.  The lanes walk j, the index that
@@ -249,15 +336,15 @@ __global__ __launch_bounds__(256) void patch_pyramid_kernel(const unsigned char 
 }  // namespace
 
 namespace {
-template <typename OUT, bool COLS, bool ORIENT = false>
+template <typename OUT, bool COLS, bool ORIENT = false, bool RADIO = false>
 void launch_pyramid(dim3 grid, size_t lds, hipStream_t s, const uint8_t *tile, int bands, int H, int W, const int32_t *xy, const int32_t *windows,
                     int target, int G, OUT *out, int rule, const BatchTable bt = BatchTable{}) {
   switch (target) {
-    case 32: hipLaunchKernelGGL((patch_pyramid_kernel<5, OUT, COLS, ORIENT>), grid, dim3(256), lds, s, tile, bands, H, W, xy, windows, target, G, out, rule, bt); break;
-    case 64: hipLaunchKernelGGL((patch_pyramid_kernel<6, OUT, COLS, ORIENT>), grid, dim3(256), lds, s, tile, bands, H, W, xy, windows, target, G, out, rule, bt); break;
-    case 128: hipLaunchKernelGGL((patch_pyramid_kernel<7, OUT, COLS, ORIENT>), grid, dim3(256), lds, s, tile, bands, H, W, xy, windows, target, G, out, rule, bt); break;
-    case 256: hipLaunchKernelGGL((patch_pyramid_kernel<8, OUT, COLS, ORIENT>), grid, dim3(256), lds, s, tile, bands, H, W, xy, windows, target, G, out, rule, bt); break;
-    default: hipLaunchKernelGGL((patch_pyramid_kernel<-1, OUT, COLS, ORIENT>), grid, dim3(256), lds, s, tile, bands, H, W, xy, windows, target, G, out, rule, bt); break;
+    case 32: hipLaunchKernelGGL((patch_pyramid_kernel<5, OUT, COLS, ORIENT, RADIO>), grid, dim3(256), lds, s, tile, bands, H, W, xy, windows, target, G, out, rule, bt); break;
+    case 64: hipLaunchKernelGGL((patch_pyramid_kernel<6, OUT, COLS, ORIENT, RADIO>), grid, dim3(256), lds, s, tile, bands, H, W, xy, windows, target, G, out, rule, bt); break;
+    case 128: hipLaunchKernelGGL((patch_pyramid_kernel<7, OUT, COLS, ORIENT, RADIO>), grid, dim3(256), lds, s, tile, bands, H, W, xy, windows, target, G, out, rule, bt); break;
+    case 256: hipLaunchKernelGGL((patch_pyramid_kernel<8, OUT, COLS, ORIENT, RADIO>), grid, dim3(256), lds, s, tile, bands, H, W, xy, windows, target, G, out, rule, bt); break;
+    default: hipLaunchKernelGGL((patch_pyramid_kernel<-1, OUT, COLS, ORIENT, RADIO>), grid, dim3(256), lds, s, tile, bands, H, W, xy, windows, target, G, out, rule, bt); break;
   }
 }
 }  // namespace
@@ -265,9 +352,9 @@ void launch_pyramid(dim3 grid, size_t lds, hipStream_t s, const uint8_t *tile, i
 // One scale of a TRAINING batch straight from resident tiles and a device sample table: no host-side window arithmetic, no per-tile
 // launches, nothing to synchronise on (Train_SMT.py:212-262 draws a batch from the loaders of MyUtils1.py:41-77 on the host).
 namespace {
-template <bool ORIENT>
+template <bool ORIENT, bool RADIO = false>
 int pair_batch_gather(const char *what, const uint8_t *tiles, int32_t n_tiles, int32_t bands, int32_t H, int32_t W, const int32_t *tile_id,
-                      const int32_t *xy, const int32_t *inner, const int32_t *obj, const int32_t *orient, int32_t scale_index,
+                      const int32_t *xy, const int32_t *inner, const int32_t *obj, const int32_t *orient, const int32_t *radio, int32_t scale_index,
                       int32_t max_window, int32_t P, int32_t target, int32_t grid, int32_t resize_rule, void *out, int32_t dtype,
                       const float *region_features, float *designed, int32_t *error_flag, void *stream) {
   DM_REQUIRE(resize_rule == DM_RESIZE_OPENCV || resize_rule == DM_RESIZE_EXACT_AREA, DM_ERR_UNSUPPORTED, "%s: unknown resize rule %d", what, resize_rule);
@@ -278,9 +365,10 @@ int pair_batch_gather(const char *what, const uint8_t *tiles, int32_t n_tiles, i
   DM_REQUIRE(max_window > 0 && max_window <= MAX_WINDOW, DM_ERR_UNSUPPORTED, "%s: window bound %d outside 1..%d", what, max_window, MAX_WINDOW);
   DM_REQUIRE(bands <= 65535, DM_ERR_BAD_SHAPE, "%s: too many bands", what);
   DM_REQUIRE((designed == nullptr) == (region_features == nullptr), DM_ERR_BAD_SHAPE, "%s: designed rows need the region features (and vice versa)", what);
-  DM_REQUIRE(!ORIENT || orient, DM_ERR_BAD_SHAPE, "%s: null orient", what);
+  DM_REQUIRE(!ORIENT || RADIO || orient, DM_ERR_BAD_SHAPE, "%s: null orient", what);
+  DM_REQUIRE(!RADIO || radio, DM_ERR_BAD_SHAPE, "%s: null radio", what);
   BatchTable bt;
-  bt.orient = orient;
+  bt.orient = orient; bt.radio = radio;
   bt.tile_id = tile_id; bt.inner = inner; bt.obj = obj; bt.region = region_features; bt.designed = designed; bt.err = error_flag;
   bt.n_tiles = n_tiles; bt.scale_index = scale_index; bt.max_window = max_window;
   // <= 32 output pixels per thread while the grid stays small (a batch of 64 samples x 4 bands at target 256: 8 blocks per pair)
@@ -291,11 +379,11 @@ int pair_batch_gather(const char *what, const uint8_t *tiles, int32_t n_tiles, i
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   if (grid == 0) {
     DM_REQUIRE(dtype == DM_F32, DM_ERR_BAD_DTYPE, "%s: planar patches are fp32", what);
-    launch_pyramid<float, false, ORIENT>(g, lds, s, tiles, bands, H, W, xy, nullptr, target, 1, reinterpret_cast<float *>(out), resize_rule, bt);
+    launch_pyramid<float, false, ORIENT, RADIO>(g, lds, s, tiles, bands, H, W, xy, nullptr, target, 1, reinterpret_cast<float *>(out), resize_rule, bt);
   } else if (dtype == DM_BF16) {
-    launch_pyramid<bf16_t, true, ORIENT>(g, lds, s, tiles, bands, H, W, xy, nullptr, target, grid, reinterpret_cast<bf16_t *>(out), resize_rule, bt);
+    launch_pyramid<bf16_t, true, ORIENT, RADIO>(g, lds, s, tiles, bands, H, W, xy, nullptr, target, grid, reinterpret_cast<bf16_t *>(out), resize_rule, bt);
   } else if (dtype == DM_F32) {
-    launch_pyramid<float, true, ORIENT>(g, lds, s, tiles, bands, H, W, xy, nullptr, target, grid, reinterpret_cast<float *>(out), resize_rule, bt);
+    launch_pyramid<float, true, ORIENT, RADIO>(g, lds, s, tiles, bands, H, W, xy, nullptr, target, grid, reinterpret_cast<float *>(out), resize_rule, bt);
   } else {
     DM_REQUIRE(false, DM_ERR_BAD_DTYPE, "%s: bad dtype %d", what, dtype);
   }
@@ -308,7 +396,7 @@ extern "C" int dm_pair_batch_gather(const uint8_t *tiles, int32_t n_tiles, int32
                                     const int32_t *xy, const int32_t *inner, const int32_t *obj, int32_t scale_index, int32_t max_window,
                                     int32_t P, int32_t target, int32_t grid, int32_t resize_rule, void *out, int32_t dtype,
                                     const float *region_features, float *designed, int32_t *error_flag, void *stream) {
-  return pair_batch_gather<false>("dm_pair_batch_gather", tiles, n_tiles, bands, H, W, tile_id, xy, inner, obj, nullptr, scale_index, max_window, P,
+  return pair_batch_gather<false>("dm_pair_batch_gather", tiles, n_tiles, bands, H, W, tile_id, xy, inner, obj, nullptr, nullptr, scale_index, max_window, P,
                                   target, grid, resize_rule, out, dtype, region_features, designed, error_flag, stream);
 }
 
@@ -319,8 +407,21 @@ extern "C" int dm_pair_batch_gather_oriented(const uint8_t *tiles, int32_t n_til
                                              int32_t scale_index, int32_t max_window, int32_t P, int32_t target, int32_t grid,
                                              int32_t resize_rule, void *out, int32_t dtype, const float *region_features, float *designed,
                                              int32_t *error_flag, void *stream) {
-  return pair_batch_gather<true>("dm_pair_batch_gather_oriented", tiles, n_tiles, bands, H, W, tile_id, xy, inner, obj, orient, scale_index,
+  return pair_batch_gather<true>("dm_pair_batch_gather_oriented", tiles, n_tiles, bands, H, W, tile_id, xy, inner, obj, orient, nullptr, scale_index,
                                  max_window, P, target, grid, resize_rule, out, dtype, region_features, designed, error_flag, stream);
+}
+
+// The oriented gather with a radiometric table (training augmentation): radio[p][c] = (gain, offset) applied to every
+// staged byte of band c of sample p, and to the first min(bands, 3) standard deviations and means and `bright` of its designed row.
+// orient may be null (orientation 0).
+extern "C" int dm_pair_batch_gather_augmented(const uint8_t *tiles, int32_t n_tiles, int32_t bands, int32_t H, int32_t W, const int32_t *tile_id,
+                                              const int32_t *xy, const int32_t *inner, const int32_t *obj, const int32_t *orient,
+                                              const int32_t *radio, int32_t scale_index, int32_t max_window, int32_t P, int32_t target,
+                                              int32_t grid, int32_t resize_rule, void *out, int32_t dtype, const float *region_features,
+                                              float *designed, int32_t *error_flag, void *stream) {
+  return pair_batch_gather<true, true>("dm_pair_batch_gather_augmented", tiles, n_tiles, bands, H, W, tile_id, xy, inner, obj, orient, radio,
+                                       scale_index, max_window, P, target, grid, resize_rule, out, dtype, region_features, designed, error_flag,
+                                       stream);
 }
 
 extern "C" int dm_patch_pyramid(const uint8_t *tile, int32_t bands, int32_t H, int32_t W, const int32_t *xy, const int32_t *windows,

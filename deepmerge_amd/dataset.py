@@ -199,7 +199,8 @@ class EpochTable:
         return PairTable(tile_id=c["tile_id"][lo:lo + 2 * b], xy=c["xy"][lo:lo + 2 * b], inner=c["inner"][lo:lo + 2 * b],
                          obj=c["obj"][lo:lo + 2 * b], region=c["region"][lo:lo + 2 * b],
                          flag=c["flag"][s * self.batch:s * self.batch + b],
-                         orient=c["orient"][lo:lo + 2 * b] if "orient" in c else None)
+                         orient=c["orient"][lo:lo + 2 * b] if "orient" in c else None,
+                         radio=c["radio"][lo:lo + 2 * b] if "radio" in c else None)
 
     def __iter__(self):
         return (self.step(s) for s in range(len(self)))
@@ -223,6 +224,7 @@ class PairDataset:
                       "region": torch.empty((2 * N, 15), dtype=torch.float32, device=dev),
                       "flag": torch.empty((N,), dtype=torch.float32, device=dev), "point_id": i32(2 * N)}
         self._orient = None         # int32 [2N], allocated by the first epoch(augment=...) and kept
+        self._radio = None          # int32 [2N, bands, 2], allocated by the first epoch(radiometric=...) and kept
 
     @classmethod
     def from_arrays(cls, images: Sequence[Dict], seed: int = 0, n_scales: int = 3, device="cuda:0") -> "PairDataset":
@@ -302,15 +304,19 @@ class PairDataset:
             raise ValueError(f"the dataset was validated for {self.host.n_scales} scales, not {n_scales}")
         return self.host.max_windows[:n_scales]
 
-    def epoch(self, e: int, batch: int, augment: Optional[str] = None) -> EpochTable:
+    def epoch(self, e: int, batch: int, augment: Optional[str] = None, radiometric=None) -> EpochTable:
         """Draw epoch e (one launch, nothing read back); the table's `point_id` column holds the drawn global point ids.
         augment: None, "flips" or "d4" -- with one more launch, every pair of the epoch also draws a dihedral orientation keyed by
         (seed, epoch, pair) ("flips": the four without the transposition), the table's `orient` column, which
-        PairFeed.fill applies to both of the pair's crops.  None: the tables carry orient=None."""
+        PairFeed.fill applies to both of the pair's crops.  None: the tables carry orient=None.
+        radiometric: None, an ops.Radiometric or a (contrast, brightness, colour) triple -- with one more launch, every pair also
+        draws a gain and an offset per band keyed by (seed, epoch, pair), the table's `radio` column, applied by
+        PairFeed.fill to both of the pair's crops and designed rows.  Independent of `augment`.  None: radio=None."""
         if batch < 1:
             raise ValueError("batch must be >= 1")
         if augment is not None and augment not in ops.ORIENT_MASKS:
             raise ValueError(f"augment must be None, 'flips' or 'd4', got {augment!r}")
+        radiometric = ops.Radiometric.of(radiometric)
         c = self._cols
         with torch.cuda.device(self.device):
             ops.pair_epoch_draw(self.pairs, self.flag, self.poly_off, self.poly_pts, self.pt_tile, self.pt_xy, self.pt_inner, self.pt_obj,
@@ -321,4 +327,10 @@ class PairDataset:
                     self._orient = torch.empty((2 * len(self),), dtype=torch.int32, device=self.device)
                 ops.pair_epoch_orient(self.seed, e, len(self), batch, ops.ORIENT_MASKS[augment], self._orient)
                 c = dict(c, orient=self._orient)
+            if radiometric is not None:
+                bands = int(self.tiles.shape[1])
+                if self._radio is None:
+                    self._radio = torch.empty((2 * len(self), bands, 2), dtype=torch.int32, device=self.device)
+                ops.pair_epoch_radiometric(self.seed, e, len(self), batch, bands, *radiometric.spans(), self._radio)
+                c = dict(c, radio=self._radio)
         return EpochTable(c, len(self), batch, e)

@@ -11,7 +11,7 @@ that neither the fp32 patch tensors nor the im2col pass exist in the training st
 """
 from __future__ import annotations
 
-from dataclasses import dataclass
+from dataclasses import dataclass, field
 from typing import List, Optional, Sequence, Union
 
 import torch
@@ -29,16 +29,17 @@ class PairTable:
     obj: torch.Tensor           # int32 [2B]      object window side
     region: torch.Tensor        # float32 [2B, 15] region attributes (MyUtils1.py:79-114)
     flag: torch.Tensor          # [B]             1 = same object (merge), 0 = different
+    # int32 [2B, bands, 2] (gain Q8, offset in 1/256 grey levels) of each sample's crop, the same on both sides of a pair
+    # (ops.pair_batch_gather); None: no radiometric jitter.  Keyword-only: the positional fields end with `orient`, as before.
+    radio: Optional[torch.Tensor] = field(default=None, kw_only=True)
     orient: Optional[torch.Tensor] = None   # int32 [2B] dihedral orientation 0..7 of each sample's crop, the same on both sides of a
     #                                         pair (ops.pair_batch_gather); None: no augmentation
 
     @staticmethod
     def stack(left: "PairTable", right: "PairTable") -> "PairTable":
-        orient = None
-        if left.orient is not None and right.orient is not None:
-            orient = torch.cat((left.orient, right.orient), 0).contiguous()
+        both = lambda a, b: None if a is None or b is None else torch.cat((a, b), 0).contiguous()
         return PairTable(*(torch.cat((getattr(left, f), getattr(right, f)), 0).contiguous() for f in ("tile_id", "xy", "inner", "obj", "region")),
-                         flag=left.flag, orient=orient)
+                         flag=left.flag, orient=both(left.orient, right.orient), radio=both(left.radio, right.radio))
 
 
 class PairFeed:
@@ -96,15 +97,16 @@ class PairFeed:
             first = i == 0
             ops.pair_batch_gather(self.tiles, table.tile_id, table.xy, table.inner, table.obj, i, s, self.max_window[i], out,
                                   grid=self.grid if self.rows else 0, resize=self.resize, region_features=table.region if first else None,
-                                  designed=self.dboth if first else None, error_flag=self.error_flag, orient=table.orient)
+                                  designed=self.dboth if first else None, error_flag=self.error_flag, orient=table.orient, radio=table.radio)
         self.flag.copy_(table.flag, non_blocking=True)
         left, right = [t[:B] for t in self.both], [t[B:] for t in self.both]
         return left, self.dboth[:B], right, self.dboth[B:], self.flag
 
     def check(self):
         """Host read of the error flag (synchronises: call it where the loss is read, every k steps).  Raises if any sample since the
-        last check had a tile id, window side or orientation out of range -- those samples were fed as zeros."""
+        last check had a tile id, window side, orientation or radiometric value out of range -- those samples were fed as zeros."""
         if int(self.error_flag.item()) != 0:
             self.error_flag.zero_()
             raise ValueError("PairFeed: a sample's tile id or window side was out of range (tile_id outside [0, T), or a window side "
-                             "outside 1..max_window), or its orientation was outside 0..7; it was fed as zeros")
+                             "outside 1..max_window), or its orientation was outside 0..7, or a radiometric gain outside 0..1023 or "
+                             "offset outside -65535..65535; it was fed as zeros")

@@ -16,7 +16,8 @@ from __future__ import annotations
 import os
 
 import ctypes as C
-from typing import Optional
+from dataclasses import dataclass
+from typing import Optional, Tuple
 
 import torch
 
@@ -838,15 +839,20 @@ def cat_batch(a, b):
 def pair_batch_gather(tiles: torch.Tensor, tile_id: Optional[torch.Tensor], xy: torch.Tensor, inner: torch.Tensor, obj: torch.Tensor,
                       scale_index: int, target: int, max_window: int, out: torch.Tensor, grid: int = 0, resize: str = "opencv",
                       region_features: Optional[torch.Tensor] = None, designed: Optional[torch.Tensor] = None,
-                      error_flag: Optional[torch.Tensor] = None, orient: Optional[torch.Tensor] = None) -> None:
+                      error_flag: Optional[torch.Tensor] = None, orient: Optional[torch.Tensor] = None,
+                      radio: Optional[torch.Tensor] = None) -> None:
     """One scale of a training batch, gathered into `out` from resident tiles and a device sample table (dm_pair_batch_gather):
     no host-side window arithmetic, no synchronisation.  tiles uint8 [T, bands, H, W]; tile_id / inner / obj int32 [P]; xy int32
     [P, 2]; out: float32 [P, bands, target, target] (grid = 0) or the patch-embed rows [P * grid^2, bands * (target / grid)^2]
     (bf16 / fp32) -- e.g. the trainer's static step inputs.  region_features [P, 15] + designed [P, 1, 19]: also writes the
     designed-feature rows.  error_flag int32 [1]: set when a sample's tile id / window is out of range (read it with the loss).
     orient int32 [P] in 0..7: the dihedral orientation of each sample's crop (dm_pair_batch_gather_oriented; bit 1 mirrors the rows,
-    bit 0 the columns, then bit 2 transposes; a value outside 0..7 is fed as zeros and flagged).  None: the plain gather."""
-    _need_cuda(tiles, tile_id, xy, inner, obj, out, region_features, designed, error_flag, orient)
+    bit 0 the columns, then bit 2 transposes; a value outside 0..7 is fed as zeros and flagged).  None: the plain gather.
+    radio int32 [P, bands, 2]: the (gain, offset) of every (sample, band) -- gain Q8 in 0..1023, offset in 1/256 grey levels in
+    -65535..65535 (dm_pair_batch_gather_augmented, with or without orient): every crop pixel inside the raster becomes
+    min(255, max(0, (gain v + offset + 128) >> 8)) before the orientation and the resize, and the designed row's standard deviations,
+    means and `bright` move with it; a sample with a value out of range is fed as zeros and flagged."""
+    _need_cuda(tiles, tile_id, xy, inner, obj, out, region_features, designed, error_flag, orient, radio)
     if tiles.dtype != torch.uint8 or tiles.dim() != 4 or not tiles.is_contiguous():
         raise ValueError("tiles must be a contiguous uint8 [T, bands, H, W] tensor")
     for name, t in (("tile_id", tile_id), ("xy", xy), ("inner", inner), ("obj", obj), ("error_flag", error_flag)):
@@ -861,9 +867,17 @@ def pair_batch_gather(tiles: torch.Tensor, tile_id: Optional[torch.Tensor], xy: 
     if designed is not None and (designed.dtype != torch.float32 or designed.numel() != P * 19 or not designed.is_contiguous()
                                  or region_features.dtype != torch.float32 or region_features.numel() != P * 15 or not region_features.is_contiguous()):
         raise ValueError("region_features must be contiguous float32 [P, 15] and designed contiguous float32 [P, 1, 19]")
+    if orient is not None and (orient.dtype != torch.int32 or not orient.is_contiguous() or tuple(orient.shape) != (P,)):
+        raise ValueError(f"orient must be a contiguous int32 [{P}] tensor, got {orient.dtype} {tuple(orient.shape)}")
+    if radio is not None:
+        if radio.dtype != torch.int32 or not radio.is_contiguous() or tuple(radio.shape) != (P, bands, 2):
+            raise ValueError(f"radio must be a contiguous int32 [{P}, {bands}, 2] tensor, got {radio.dtype} {tuple(radio.shape)}")
+        check(_lib.lib().dm_pair_batch_gather_augmented(tiles.data_ptr(), T, bands, H, W, _ptr(tile_id), xy.data_ptr(), inner.data_ptr(),
+                                                        obj.data_ptr(), _ptr(orient), radio.data_ptr(), scale_index, max_window, P, target,
+                                                        grid, _resize_rule(resize), out.data_ptr(), _dt(out), _ptr(region_features),
+                                                        _ptr(designed), _ptr(error_flag), _stream()), "dm_pair_batch_gather_augmented")
+        return
     if orient is not None:
-        if orient.dtype != torch.int32 or not orient.is_contiguous() or tuple(orient.shape) != (P,):
-            raise ValueError(f"orient must be a contiguous int32 [{P}] tensor, got {orient.dtype} {tuple(orient.shape)}")
         check(_lib.lib().dm_pair_batch_gather_oriented(tiles.data_ptr(), T, bands, H, W, _ptr(tile_id), xy.data_ptr(), inner.data_ptr(),
                                                        obj.data_ptr(), orient.data_ptr(), scale_index, max_window, P, target, grid,
                                                        _resize_rule(resize), out.data_ptr(), _dt(out), _ptr(region_features), _ptr(designed),
@@ -887,6 +901,50 @@ def pair_epoch_orient(seed: int, epoch: int, n_pairs: int, batch: int, mask: int
     with torch.cuda.device(out.device):
         check(_lib.lib().dm_pair_epoch_orient(int(seed) & 0xFFFFFFFFFFFFFFFF, int(epoch), int(n_pairs), int(batch), int(mask), out.data_ptr(),
                                               _stream()), "dm_pair_epoch_orient")
+
+
+@dataclass(frozen=True)
+class Radiometric:
+    """The strength of the feed's radiometric jitter, as fractions: `contrast` is the half width of the
+    pair's gain about 1.0 (0 .. 0.5), `brightness` the half width of its offset as a fraction of the 0..255 range (0 .. 0.25),
+    `colour` the half width of each band's own gain deviation (0 .. 0.25)."""
+    contrast: float = 0.2
+    brightness: float = 0.1
+    colour: float = 0.05
+
+    def __post_init__(self):
+        for name, top in (("contrast", 0.5), ("brightness", 0.25), ("colour", 0.25)):
+            v = getattr(self, name)
+            if isinstance(v, bool) or not isinstance(v, (int, float)) or not 0.0 <= float(v) <= top:
+                raise ValueError(f"Radiometric: {name} must be a number in 0 .. {top}, got {v!r}")
+
+    def spans(self) -> Tuple[int, int, int]:
+        """(gain_span, band_span, offset_span) of dm_pair_epoch_radiometric: Q8 gains, offsets in 1/256 grey levels."""
+        return int(round(256 * self.contrast)), int(round(256 * self.colour)), int(round(255 * 256 * self.brightness))
+
+    @staticmethod
+    def of(value) -> Optional["Radiometric"]:
+        """None, a Radiometric or a (contrast, brightness, colour) triple -> None or a Radiometric."""
+        if value is None or isinstance(value, Radiometric):
+            return value
+        if isinstance(value, (tuple, list)) and len(value) == 3:
+            return Radiometric(*value)
+        raise ValueError(f"radiometric must be None, an ops.Radiometric or a (contrast, brightness, colour) triple, got {value!r}")
+
+
+def pair_epoch_radiometric(seed: int, epoch: int, n_pairs: int, batch: int, bands: int, gain_span: int, band_span: int, offset_span: int,
+                           out: torch.Tensor) -> None:
+    """One epoch's radiometric table in one launch (dm_pair_epoch_radiometric): the pair at shuffled position j draws
+    a gain and an offset, and each band a gain deviation, from Philox counter word 4; (gain_c, offset_c) is written to both of its
+    rows in the blocked layout of `pair_epoch_draw`.  out: int32 [2 n_pairs, bands, 2] on the device."""
+    _need_cuda(out)
+    if out.dtype != torch.int32 or not out.is_contiguous() or out.numel() != 4 * int(n_pairs) * int(bands):
+        raise ValueError(f"pair_epoch_radiometric: out must be a contiguous int32 tensor of {4 * int(n_pairs) * int(bands)} elements "
+                         f"([2 n_pairs, bands, 2]), got {out.dtype} {tuple(out.shape)}")
+    with torch.cuda.device(out.device):
+        check(_lib.lib().dm_pair_epoch_radiometric(int(seed) & 0xFFFFFFFFFFFFFFFF, int(epoch), int(n_pairs), int(batch), int(bands),
+                                                   int(gain_span), int(band_span), int(offset_span), out.data_ptr(), _stream()),
+              "dm_pair_epoch_radiometric")
 
 
 def pair_epoch_draw(pairs: torch.Tensor, pair_flag: torch.Tensor, poly_off: torch.Tensor, poly_pts: torch.Tensor, pt_tile: torch.Tensor,

@@ -47,7 +47,8 @@ int dm_abi_version(void);   /* 2: dm_patch_pyramid / dm_patch_pyramid_cols take 
                              * 4: DmGemmArgs.k_fold / a_fold / b_fold, dm_split_bf16_planes (round 4); 5: dm_pair_batch_gather (round 5); 6: dm_gemm_grouped (round 5);
                              * 7: dm_gemm_grouped(args, n, stream) without a group workspace, its workspace query removed;
                              * additive in 6: dm_pairwise_distance, dm_pair_epoch_draw, dm_contrastive_terms, dm_pair_eval_summary;
-                             * additive in 7: dm_region_merge_cost, dm_pixel_regions, dm_pair_batch_gather_oriented, dm_pair_epoch_orient */
+                             * additive in 7: dm_region_merge_cost, dm_pixel_regions, dm_pair_batch_gather_oriented, dm_pair_epoch_orient,
+                             *   dm_pair_batch_gather_augmented, dm_pair_epoch_radiometric */
 const char *dm_last_error(void);
 /* Name of the code object architecture the library was built for ("gfx950"). */
 const char *dm_arch(void);
@@ -431,6 +432,29 @@ int dm_pair_batch_gather_oriented(const uint8_t *tiles, int32_t n_tiles, int32_t
                                   const int32_t *xy, const int32_t *inner, const int32_t *obj, const int32_t *orient, int32_t scale_index,
                                   int32_t max_window, int32_t P, int32_t target, int32_t grid, int32_t resize_rule, void *out,
                                   int32_t dtype, const float *region_features, float *designed, int32_t *error_flag, void *stream);
+/* Radiometric jitter (additive in ABI 7): dm_pair_batch_gather_oriented with one (gain, offset) per (sample, band) on top.
+ *   radio   int32 [P, bands, 2], not NULL: gain is Q8 in 0 .. 1023 (256 = 1.0), offset is in 1/256 grey levels in -65535 .. 65535.
+ *           Both sides of a pair carry the same values (two views of one scene under one illumination).
+ *   orient  as above, or NULL: every orientation 0.
+ * Pixels.  Every pixel v of the zero-padded L x L crop that lies inside the raster becomes
+ *   v' = min(255, max(0, (gain v + offset + 128) >> 8))        (int32; the shift is arithmetic: floor for negative sums)
+ * and padding pixels stay 0 whatever the offset.  |gain v + offset + 128| < 2^19.  The rule is per pixel, so it commutes with the
+ * dihedral index map; orientation, either resize rule and / 255 then run on the transformed crop unchanged.
+ * Designed row (written when region_features / designed are given).  With the attributes in oracle/rag.py's order -- std at 5..7,
+ * means at 8..10, bright at 13 -- nb = min(bands, 3), and for c < nb, in fp32, round to nearest, no contraction:
+ *   gf = (float)gain_c / 256,  bf = (float)offset_c / 256                       (both exact)
+ *   mean_c' = min(255, max(0, gf mean_c + bf)),   std_c' = gf std_c
+ *   bright' = bright + (((mean_0' - mean_0) + (mean_1' - mean_1)) + (mean_2' - mean_2)) / (float)nb     (left to right over c < nb)
+ * Attributes of bands >= nb, the other ten attributes and the four scale factors are not touched.  The identity table (256, 0)
+ * leaves the row bit for bit as dm_pair_batch_gather_oriented writes it.  First order: pixels that clamp are not accounted for in
+ * std'; the attributes are taken to be on the 0..255 scale of the tile bytes (rag.label_stats).
+ * A sample with a gain or an offset of any band outside its range is treated like a bad orientation: zeros in every band,
+ * error_flag[0] |= 1, its designed row written from the untransformed attributes; no other sample is affected. */
+int dm_pair_batch_gather_augmented(const uint8_t *tiles, int32_t n_tiles, int32_t bands, int32_t H, int32_t W, const int32_t *tile_id,
+                                   const int32_t *xy, const int32_t *inner, const int32_t *obj, const int32_t *orient,
+                                   const int32_t *radio, int32_t scale_index, int32_t max_window, int32_t P, int32_t target, int32_t grid,
+                                   int32_t resize_rule, void *out, int32_t dtype, const float *region_features, float *designed,
+                                   int32_t *error_flag, void *stream);
 
 /* ---- per-epoch pair draw: the epoch's whole sample table in one launch (additive in ABI 6) ---------------------------------
  * Replaces the dataset rebuild of every epoch (MyUtils1.py:275-293: for each pair of the positive / negative lists, one sample
@@ -463,6 +487,20 @@ int dm_pair_epoch_draw(const DmPairDraw *args, void *stream);
  * resumed run sees the same orientations.  orient int32 [2 n_pairs].  Refused before any launch: another mask, n_pairs outside
  * 1 .. 2^30, batch < 1, epoch < 0, a null pointer. */
 int dm_pair_epoch_orient(uint64_t seed, int32_t epoch, int32_t n_pairs, int32_t batch, int32_t mask, int32_t *orient, void *stream);
+/* The epoch's radiometric table for dm_pair_batch_gather_augmented (additive in ABI 7), radio int32 [2 n_pairs, bands, 2] in the same
+ * blocked layout, drawn from counter word 4 (neither the draw's, the shuffle's nor the orientation's).  With src = perm(j) and
+ *   sym(r, s) = (int32)umulhi(r, 2 s + 1) - s                                   (uniform on -s .. s; 0 when s = 0)
+ *   A = philox4x32_10((src, epoch, 4, 0), key):   g0 = 256 + sym(A[0], gain_span),   b0 = sym(A[1], offset_span)
+ *   band c:  B = philox4x32_10((src, epoch, 4, 1 + c / 4), key)[c % 4],   gain_c = g0 + sym(B, band_span),
+ *            offset_c = b0 - 128 (gain_c - 256)                                  (the contrast pivots about mid-grey)
+ * (gain_c, offset_c) goes to both rows of the pair, row_l and row_l + b_s.  Within the span limits below every gain lies in
+ * 64 .. 448 and every |offset| <= 40896: in range by construction.  Refused before any launch: a span below 0 or over its limit,
+ * bands outside 1 .. 16, n_pairs outside 1 .. 2^30, batch < 1, epoch < 0, a null pointer. */
+#define DM_RADIO_MAX_GAIN_SPAN 128
+#define DM_RADIO_MAX_BAND_SPAN 64
+#define DM_RADIO_MAX_OFFSET_SPAN 16320
+int dm_pair_epoch_radiometric(uint64_t seed, int32_t epoch, int32_t n_pairs, int32_t batch, int32_t bands, int32_t gain_span,
+                              int32_t band_span, int32_t offset_span, int32_t *radio, void *stream);
 
 /* ---- held-out pair evaluation (additive in ABI 6; deepmerge_amd/evaluate.py) ---------------------------
  * Per-pair contrastive terms -- the per-pair form of the reference's contrastive loss (Losses.py:34-38, before its mean):

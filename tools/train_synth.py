@@ -3,7 +3,7 @@
 epoch, FRESH pairs every step generated on the device -- patch pyramids cut from resident uint8 tiles by the sync-free feed
 (deepmerge_amd/feed.py: one dm_pair_batch_gather launch per scale straight into the captured step's inputs), positives = two
 jittered windows of the same spot, negatives = spots of different tiles -- through PairTrainer (hipGraph replay).  Prints a loss curve; BASELINE configs[4] shape by default (depth [6,4,2], 4 scales x 4 ch,
-120 pairs per GPU).        python tools/train_synth.py [--epochs 3] [--steps-per-epoch 20] [--pairs 120] [--depth 6,4,2] [--augment d4]
+120 pairs per GPU).        python tools/train_synth.py [--epochs 3] [--steps-per-epoch 20] [--pairs 120] [--depth 6,4,2] [--augment d4] [--radiometric 0.2,0.1,0.05]
 """
 import argparse
 import json
@@ -15,6 +15,7 @@ import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+from deepmerge_amd import ops  # noqa: E402
 from deepmerge_amd.nets.ShfitScaleFormer import ShfitScaleFormer_v3  # noqa: E402
 from deepmerge_amd.feed import PairFeed, PairTable  # noqa: E402
 from deepmerge_amd.patches import point_batch  # noqa: E402
@@ -47,18 +48,25 @@ def draw_pairs(n_tiles, size, B, g):
     return tl, tr, xy_l, xy_r, inner, obj, feats_l, feats_r, flag
 
 
-def pair_table(draw, orient=None):
+def pair_table(draw, orient=None, radio=None):
     """deepmerge_amd.feed.PairTable of a draw: [left rows; right rows], int32 columns -- device ops only, nothing read back.
-    orient: int32 [B] dihedral orientations, one per pair (both sides get it), or None."""
+    orient: int32 [B] dihedral orientations, one per pair (both sides get it), or None.  radio: int32 [2B, bands, 2] or None."""
     tl, tr, xy_l, xy_r, inner, obj, feats_l, feats_r, flag = draw
     i32 = lambda a, b: torch.cat((a, b), 0).to(torch.int32)
     return PairTable(tile_id=i32(tl, tr), xy=i32(xy_l, xy_r), inner=i32(inner, inner), obj=i32(obj, obj),
-                     region=torch.cat((feats_l, feats_r), 0), flag=flag, orient=None if orient is None else i32(orient, orient))
+                     region=torch.cat((feats_l, feats_r), 0), flag=flag, orient=None if orient is None else i32(orient, orient), radio=radio)
 
 
 def draw_orient(B, augment, g):
     """One orientation per pair from a generator of its own, so that the data stream is the same with and without --augment."""
     return torch.randint(0, {"flips": 4, "d4": 8}[augment], (B,), generator=g, device=DEV)
+
+
+def draw_radio(B, bands, radiometric, step, out):
+    """One (gain, offset) table per pair of step `step`, on both of its rows (ops.pair_epoch_radiometric with the step as the epoch:
+    one step is one block of the blocked layout, [left B; right B]); a stream of its own, like the orientations."""
+    ops.pair_epoch_radiometric(1, step, B, B, bands, *radiometric.spans(), out)
+    return out
 
 
 MAX_WINDOW = [64, 112, 160, 208]       # bounds of (inner, obj, obj + interval, obj + 2 interval) for the ranges drawn above
@@ -101,10 +109,19 @@ def main():  # noqa: C901
                          "fp32 patch tensors; looped: the per-tile Python loop of rounds 1-4")
     ap.add_argument("--augment", type=str, default=None, choices=["flips", "d4"],
                     help="feed every pair at a random dihedral orientation (both sides alike; rows / patches feeds only)")
+    ap.add_argument("--radiometric", type=str, default=None, metavar="C,B,K",
+                    help="feed every pair under a random gain / offset per band: contrast, brightness, colour half widths, e.g. 0.2,0.1,0.05 "
+                         "(both sides alike; rows / patches feeds only)")
     ap.add_argument("--loss-every", type=int, default=0, help="read the loss back every k steps (0 = once per epoch)")
     args = ap.parse_args()
     if args.augment and args.feed == "looped":
         ap.error("--augment needs the sync-free feed (--feed rows or patches)")
+    if args.radiometric and args.feed == "looped":
+        ap.error("--radiometric needs the sync-free feed (--feed rows or patches)")
+    try:
+        radiometric = ops.Radiometric(*(float(v) for v in args.radiometric.split(","))) if args.radiometric else None
+    except (TypeError, ValueError) as e:
+        ap.error(f"--radiometric C,B,K: {e}")
     scales, bands = [32, 64, 128, 256], 4
     depth = [int(d) for d in args.depth.split(",")]
     ms = tuple(int(m) for m in args.milestones.split(","))
@@ -116,6 +133,7 @@ def main():  # noqa: C901
     tr = PairTrainer(net, margin=1.0, lr=args.lr)
     tr.enable_graph(warmup=1)
     feed = None if args.feed == "looped" else PairFeed(tiles, scales, args.pairs, MAX_WINDOW, rows=args.feed == "rows", numerics=args.numerics, trainer=tr)
+    radio_buf = torch.empty((2 * args.pairs, bands, 2), dtype=torch.int32, device=DEV) if radiometric else None
     curve = []
     torch.cuda.synchronize()
     t0 = time.perf_counter()
@@ -132,7 +150,8 @@ def main():  # noqa: C901
                 batch = make_pairs_looped(tiles, args.pairs, scales, g)
             else:
                 orient = draw_orient(args.pairs, args.augment, g_orient) if args.augment else None
-                batch = feed.fill(pair_table(draw_pairs(tiles.shape[0], tiles.shape[2], args.pairs, g), orient))
+                radio = draw_radio(args.pairs, bands, radiometric, done, radio_buf) if radiometric else None
+                batch = feed.fill(pair_table(draw_pairs(tiles.shape[0], tiles.shape[2], args.pairs, g), orient, radio))
             tot += tr.step(*batch, lr=lr)                    # (device-side sum: the reference's per-step .item(), Train_SMT.py:301, is a sync)
             if args.loss_every and (k + 1) % args.loss_every == 0:
                 float(tot)
@@ -143,7 +162,7 @@ def main():  # noqa: C901
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     n = args.epochs * args.steps_per_epoch
-    print(json.dumps({"tool": "train_synth", "feed": args.feed, "augment": args.augment, "numerics": args.numerics, "depth": depth, "pairs_per_step": args.pairs, "steps": n,
+    print(json.dumps({"tool": "train_synth", "feed": args.feed, "augment": args.augment, "radiometric": args.radiometric, "numerics": args.numerics, "depth": depth, "pairs_per_step": args.pairs, "steps": n,
                       "loss_curve": curve, "hip_graph": tr.graph_error is None, "pairs_per_s_incl_data_generation": round(n * args.pairs / dt, 1),
                       "pairs_per_s_steady_incl_data_generation": None if t_warm is None else round((n - WARM) * args.pairs / (t0 + dt - t_warm), 1),
                       "steady_note": f"after the first {WARM} steps (eager warm-up + hipGraph capture)"}))
