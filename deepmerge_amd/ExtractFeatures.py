@@ -89,8 +89,8 @@ class FeatureIO:
         """From an image tile (uint8 [bands, H, W]) and its segmentation (labels int32 [H, W], ids 0..n_labels-1) to the merged
         partition: label_stats -> designed_features -> rag_edges -> sample_points -> extract_features_from_tile ->
         merge_regions(weights=, stats=), nothing else.  Returns (MergeResult, PointSamples); `result.labels(labels)` is the merged
-        raster.  `merge_kwargs` go to merge_regions (max_rounds, min_regions).  Under a process group the encode is sharded by
-        extract_features_from_tile and the graph stages run replicated."""
+        raster.  `merge_kwargs` go to merge_regions (max_rounds, min_regions, min_area).  Under a process group the encode is
+        sharded by extract_features_from_tile and the graph stages run replicated."""
         from . import rag
         stats = rag.label_stats(labels, tile, n_labels)
         designed = rag.designed_features(stats)
@@ -104,8 +104,9 @@ class FeatureIO:
     def segment_tile(self, tile: torch.Tensor, cell: int = 29, compactness: int = 10, iters: int = 10, min_size: Optional[int] = None,
                      **merge_tile_kwargs):
         """From an image tile alone to the merged partition: rag.slic(tile, cell, compactness, iters, min_size) followed by
-        merge_tile(tile, labels, n_labels, **merge_tile_kwargs).  Returns (MergeResult, PointSamples, labels, n_labels), where
-        labels / n_labels are the SLIC superpixels the merge started from."""
+        merge_tile(tile, labels, n_labels, **merge_tile_kwargs) (min_area among them; SLIC's min_size is the other thing, the
+        size below which a fragment of a superpixel is absorbed before any scoring).  Returns (MergeResult, PointSamples, labels,
+        n_labels), where labels / n_labels are the SLIC superpixels the merge started from."""
         from . import rag
         labels, n_labels = rag.slic(tile, cell=cell, compactness=compactness, iters=iters, min_size=min_size)
         result, pts = self.merge_tile(tile, labels, n_labels, **merge_tile_kwargs)
@@ -117,7 +118,8 @@ class FeatureIO:
         / memmap) to the merged partition: `scene.segment_scene(self, source, **kw)`.  Returns a `scene.SceneResult`.
         `labels=, n_labels=` bring the scene's superpixels along as a label raster on the host whose regions may cross tile seams
         (`scene.segment_labels`); they go with no `segmenter`.  `cross_seams=True, slic={...}` makes such superpixels here
-        (`scene.slic_labels`, then `scene.segment_labels`); it goes with neither."""
+        (`scene.slic_labels`, then `scene.segment_labels`); it goes with neither.  `merge_regions`' keywords (max_rounds,
+        min_regions, min_area) reach the scene's one merge on each of these paths."""
         from . import scene
         return scene.segment_scene(self, source, **kw)
 

@@ -201,6 +201,8 @@ SIGNATURES = {
     "dm_seam_stitch": (_I, [_P, _P, _L, _L, _P, _P, _P, _I, _P, _P, _I, _P, _P, _P]),
     "dm_merge_round": (_I, [_P, _P, _I, _I, _P, _P, _I, _P]),
     "dm_merge_best": (_I, [_P, _P, _I, _I, _F, _P, _P]),
+    "dm_merge_best_small": (_I, [_P, _P, _I, _I, _P, _L, _P, _P]),
+    "dm_merge_accept": (_I, [_P, _P, _I, _I, _P, _L, _P, _P]),
     "dm_merge_match": (_I, [_P, _P, _I, _I, _P, _P, _P, _P, _P]),
     "dm_merge_fold_regions": (_I, [C.POINTER(DmMergeFold), _P]),
     "dm_merge_edge_keys": (_I, [_P, _P, _P, _I, _I, _P, _P]),

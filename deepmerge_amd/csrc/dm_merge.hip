@@ -2,6 +2,8 @@
 // merged label raster (the rule is stated in include/deepmerge_hip.h and restated in numpy in
 // tests/merge_ref.py).  A round is: score (dm_segment_mean + dm_edge_similarity, unchanged) -> dm_merge_best ->
 // dm_merge_match -> dm_merge_fold_regions -> dm_merge_edge_keys -> sort of the 64-bit keys -> dm_merge_fold_edges.
+// An elimination round (min_area: regions below it propose, their neighbours accept) has dm_merge_best_small + dm_merge_accept
+// in the place of dm_merge_best and is the same round from dm_merge_match on.
 //
 // Every quantity produced here is an integer (or a float copied bit for bit), and every reduction is an integer min or
 // add, so the result does not depend on the order in which threads arrive: the GPU and the numpy spec agree bit for bit.
@@ -31,7 +33,23 @@ __global__ void best_clear_kernel(unsigned long long *__restrict__ best, int C) 
 // tie goes to the smaller neighbour id.  The edge list is sorted by (a, b), so the lanes of a wave that share `a` are
 // neighbours: their keys are min-reduced across the run with shuffles and the run's first lane issues ONE atomic for `a`
 // (a grown region has tens of edges); the `b` side is scattered and takes one atomic per candidate edge.
-__global__ __launch_bounds__(256) void best_kernel(const int *__restrict__ edges, const float *__restrict__ simi, int E, int C, float margin,
+//
+// Who may take which edge is the kernel's template parameter: `edge(s)` says whether an edge of score s is a candidate at all,
+// `side(r)` whether region r chooses among its candidate edges.
+struct MarginRule {                                     // the mutual-best rounds: every region chooses among the edges below the margin
+  float margin;
+  __device__ __forceinline__ bool edge(float s) const { return s < margin; }                   // NaN is no candidate
+  __device__ __forceinline__ bool side(int) const { return true; }
+};
+struct SmallRule {                                      // the elimination rounds: a small region proposes over every edge that has a score
+  const long long *__restrict__ count;
+  long long min_area;
+  __device__ __forceinline__ bool edge(float s) const { return s == s; }                       // NaN is never usable
+  __device__ __forceinline__ bool side(int r) const { return count[r] < min_area; }
+};
+
+template <typename Rule>
+__global__ __launch_bounds__(256) void best_kernel(const int *__restrict__ edges, const float *__restrict__ simi, int E, int C, Rule rule,
                                                    unsigned long long *__restrict__ best) {
   const int lane = threadIdx.x & 63;
   const long long stride = (long long)gridDim.x * blockDim.x;
@@ -42,10 +60,12 @@ __global__ __launch_bounds__(256) void best_kernel(const int *__restrict__ edges
     if (e < E) {
       a = edges[2 * e]; b = edges[2 * e + 1];
       const float s = simi[e];
-      if (s < margin && (unsigned)a < (unsigned)C && (unsigned)b < (unsigned)C) {             // NaN is no candidate
+      if (rule.edge(s) && (unsigned)a < (unsigned)C && (unsigned)b < (unsigned)C) {
         const unsigned long long hi = (unsigned long long)__float_as_uint(s) << 32;
-        ka = hi | (unsigned)b;
-        atomicMin(best + b, hi | (unsigned)a);
+        const bool mine = rule.side(a);
+        if (mine) ka = hi | (unsigned)b;
+        if (rule.side(b)) atomicMin(best + b, hi | (unsigned)a);
+        if (!mine) a = -1;
       } else {
         a = -1;
       }
@@ -59,6 +79,25 @@ __global__ __launch_bounds__(256) void best_kernel(const int *__restrict__ edges
       if (lane + o < 64 && oa == a && ok < ka) ka = ok;
     }
     if (head && a >= 0 && ka != NO_BEST) atomicMin(best + a, ka);
+  }
+}
+
+// ---- accept (elimination rounds) ------------------------------------------------------------------------------------------
+// A non-small region takes the smallest key (bits(simi) << 32) | s over the small regions s that proposed to it.  The kernel
+// reads best[] only at small regions and writes it only at non-small ones, and the proposals of the small regions were all
+// written by the launch before this one: every value read here is final when the kernel starts, whatever the thread order.
+__global__ __launch_bounds__(256) void accept_kernel(const int *__restrict__ edges, const float *__restrict__ simi, int E, int C,
+                                                     const long long *__restrict__ count, long long min_area,
+                                                     unsigned long long *best) {
+  for (long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x; e < E; e += (long long)gridDim.x * blockDim.x) {
+    const int a = edges[2 * e], b = edges[2 * e + 1];
+    if ((unsigned)a >= (unsigned)C || (unsigned)b >= (unsigned)C) continue;
+    const bool sa = count[a] < min_area, sb = count[b] < min_area;
+    if (sa == sb) continue;                             // two small regions settle it between themselves; two large ones have nothing to settle
+    const int s = sa ? a : b, t = sa ? b : a;
+    const unsigned long long bs = best[s];
+    if (bs != NO_BEST && (unsigned)bs == (unsigned)t)   // edges are unique: the proposal that names t came over this edge
+      atomicMin(best + t, ((unsigned long long)__float_as_uint(simi[e]) << 32) | (unsigned)s);
   }
 }
 
@@ -306,8 +345,33 @@ extern "C" int dm_merge_best(const int32_t *edges, const float *simi, int32_t E,
   DM_REQUIRE(E > 0 && C > 0 && C <= (1 << 24), DM_ERR_BAD_SHAPE, "dm_merge_best: bad sizes (E=%d C=%d; need E >= 1, 1 <= C <= 2^24)", E, C);
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   hipLaunchKernelGGL(best_clear_kernel, dim3((C + 255) / 256), dim3(256), 0, s, (unsigned long long *)best, C);
-  hipLaunchKernelGGL(best_kernel, dim3(grid_for(E)), dim3(256), 0, s, edges, simi, E, C, margin, (unsigned long long *)best);
+  hipLaunchKernelGGL(best_kernel<MarginRule>, dim3(grid_for(E)), dim3(256), 0, s, edges, simi, E, C, MarginRule{margin},
+                     (unsigned long long *)best);
   DM_LAUNCH_CHECK("dm_merge_best");
+  return DM_OK;
+}
+
+extern "C" int dm_merge_best_small(const int32_t *edges, const float *simi, int32_t E, int32_t C, const int64_t *count, int64_t min_area,
+                                   uint64_t *best, void *stream) {
+  DM_REQUIRE(edges && simi && count && best, DM_ERR_BAD_SHAPE, "dm_merge_best_small: null pointer");
+  DM_REQUIRE(E > 0 && C > 0 && C <= (1 << 24), DM_ERR_BAD_SHAPE, "dm_merge_best_small: bad sizes (E=%d C=%d; need E >= 1, 1 <= C <= 2^24)", E, C);
+  DM_REQUIRE(min_area >= 1, DM_ERR_BAD_SHAPE, "dm_merge_best_small: min_area = %lld, need >= 1", (long long)min_area);
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  hipLaunchKernelGGL(best_clear_kernel, dim3((C + 255) / 256), dim3(256), 0, s, (unsigned long long *)best, C);
+  hipLaunchKernelGGL(best_kernel<SmallRule>, dim3(grid_for(E)), dim3(256), 0, s, edges, simi, E, C,
+                     SmallRule{(const long long *)count, (long long)min_area}, (unsigned long long *)best);
+  DM_LAUNCH_CHECK("dm_merge_best_small");
+  return DM_OK;
+}
+
+extern "C" int dm_merge_accept(const int32_t *edges, const float *simi, int32_t E, int32_t C, const int64_t *count, int64_t min_area,
+                               uint64_t *best, void *stream) {
+  DM_REQUIRE(edges && simi && count && best, DM_ERR_BAD_SHAPE, "dm_merge_accept: null pointer");
+  DM_REQUIRE(E > 0 && C > 0 && C <= (1 << 24), DM_ERR_BAD_SHAPE, "dm_merge_accept: bad sizes (E=%d C=%d; need E >= 1, 1 <= C <= 2^24)", E, C);
+  DM_REQUIRE(min_area >= 1, DM_ERR_BAD_SHAPE, "dm_merge_accept: min_area = %lld, need >= 1", (long long)min_area);
+  hipLaunchKernelGGL(accept_kernel, dim3(grid_for(E)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), edges, simi, E, C,
+                     (const long long *)count, (long long)min_area, (unsigned long long *)best);
+  DM_LAUNCH_CHECK("dm_merge_accept");
   return DM_OK;
 }
 

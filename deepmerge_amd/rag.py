@@ -25,6 +25,7 @@ from __future__ import annotations
 
 import ctypes
 import math
+import operator
 from dataclasses import dataclass, field
 from typing import Dict, List, Optional, Tuple
 
@@ -207,7 +208,10 @@ class MergeResult:
     (weights / stats None when none were given); pooled [C,D], simi [E]: the scoring of the final partition; rep int32 [C]: the
     smallest original superpixel id of each region (regions are numbered in that order); rounds: rounds applied; history int32
     [M,3] = (round, rep of the surviving region, rep of the absorbed one) with history_simi float32 [M], in merge order;
-    regions_per_round: region count before round 1 and after every applied round (rounds + 1 entries)."""
+    regions_per_round: region count before round 1 and after every applied round (rounds + 1 entries); small_rounds: how many of
+    the rounds, the last ones, were elimination rounds (`min_area`): the margin rounds ended after `rounds - small_rounds`, and
+    history / history_simi / regions_per_round / merges_per_round run on through both kinds (an elimination round's history_simi
+    may be >= margin)."""
     region_of: torch.Tensor
     ptr: torch.Tensor
     idx: torch.Tensor
@@ -222,6 +226,7 @@ class MergeResult:
     history_simi: torch.Tensor
     regions_per_round: List[int]
     merges_per_round: List[int] = field(default_factory=list)
+    small_rounds: int = 0
 
     def labels(self, raster: torch.Tensor) -> torch.Tensor:
         """Merged label raster: out[y,x] = region_of[raster[y,x]] (int32 [H,W]; ids outside [0, S0) are copied through)."""
@@ -323,9 +328,22 @@ def _check_merge_inputs(features, ptr, idx, edges, S0):
             raise ValueError(f"merge_regions: {msg}")
 
 
+def _check_min_area(min_area, have_stats: bool = True) -> int:
+    """`min_area` of `merge_regions`, `mrs` and `mrs_graph`: a ValueError before any device work."""
+    try:
+        area = operator.index(min_area)
+    except TypeError:
+        raise ValueError(f"min_area must be an integer number of pixels, got {min_area!r}") from None
+    if not 0 <= area < 1 << 63:
+        raise ValueError(f"min_area must be >= 0 (and fit int64), got {area}")
+    if area and not have_stats:
+        raise ValueError("min_area needs stats: a region's area is stats['count']")
+    return area
+
+
 def merge_regions(features: torch.Tensor, ptr: torch.Tensor, idx: torch.Tensor, edges: torch.Tensor, *, margin: float = 1.0,
                   weights: Optional[torch.Tensor] = None, stats: Optional[Dict[str, torch.Tensor]] = None,
-                  max_rounds: Optional[int] = None, min_regions: int = 0) -> MergeResult:
+                  max_rounds: Optional[int] = None, min_regions: int = 0, min_area: int = 0) -> MergeResult:
     """Mutual-best-neighbour region merging on the device, from the sweep's inputs to the final partition.
 
     features fp32 [P,D]; ptr int32 [S0+1] / idx int32 [P']: the superpixels' point lists; edges int32 [E,2], a < b, sorted by
@@ -335,7 +353,16 @@ def merge_regions(features: torch.Tensor, ptr: torch.Tensor, idx: torch.Tensor, 
     (smallest simi, then smallest id), merge the pairs that chose each other, and fold point lists, edges, weights, statistics.
     Stops when a round merges nothing (then no edge has simi < margin), after `max_rounds` rounds, or before a round that would
     leave fewer than `min_regions` regions (that round is not applied, so more regions than asked may remain).
+    min_area > 0 (pixels; needs stats) adds the minimum mapping unit: once a round has merged nothing -- not when max_rounds or
+    min_regions ended the rounds -- elimination rounds follow, in which every region with stats["count"] < min_area proposes to the
+    neighbour it resembles most (smallest simi over its edges, NaN excepted, no margin; then smallest id), every other region
+    accepts the best of its proposers, and mutual choices merge as above.  They end when no small region has a scored edge left
+    (or at max_rounds, which counts all rounds, or min_regions); `result.small_rounds` counts them and the history runs on through
+    them.  They do not go back to the margin rule: a merge can pull a region's pooled mean below the margin to a neighbour, the
+    result's `simi` shows such edges, and a caller who wants them merged calls again.  min_area = 0: no such rounds, nothing else
+    changes.
     The inputs are not modified.  One small readback per round; everything else stays on the device."""
+    min_area = _check_min_area(min_area, stats is not None)
     _need_cuda(features, ptr, idx, edges, weights, *((stats or {}).get(k) for k in _STAT_KEYS))
     if features.dtype != torch.float32 or features.dim() != 2 or features.shape[1] < 1:
         raise ValueError("features must be float32 [P,D]")
@@ -376,16 +403,17 @@ def merge_regions(features: torch.Tensor, ptr: torch.Tensor, idx: torch.Tensor, 
             check(lib.dm_edge_similarity(pooled.data_ptr(), cur["edges"].data_ptr(), simi.data_ptr(), None, E, D, margin, stream),
                   "dm_edge_similarity")
 
-    return _merge_loop(score, margin, pooled, ptr, idx, edges, weights, stats, nb, max_rounds, min_regions)
+    return _merge_loop(score, margin, pooled, ptr, idx, edges, weights, stats, nb, max_rounds, min_regions, min_area)
 
 
 def _merge_loop(score, margin: float, pooled: torch.Tensor, ptr: torch.Tensor, idx: torch.Tensor, edges: torch.Tensor,
                 weights: Optional[torch.Tensor], stats: Optional[Dict[str, torch.Tensor]], nb: int, max_rounds: Optional[int],
-                min_regions: int) -> MergeResult:
+                min_regions: int, min_area: int = 0) -> MergeResult:
     """The rounds of the mutual-best merge (include/deepmerge_hip.h) around a pluggable score step, for `merge_regions` and `mrs`.
     score(cur, C, E, simi, stream) writes simi[:E] for the partition `cur` (the dict of its device arrays) and whatever it keeps of
     its own (`pooled [S0,D]`, whose first C rows go into the result); an edge is a candidate iff simi < margin.  The inputs are
-    checked and contiguous.  P = len(idx) may be 0: then no point list is read or written."""
+    checked and contiguous.  P = len(idx) may be 0: then no point list is read or written.  min_area > 0 (checked; stats given):
+    after the first round that picks nothing, the elimination rounds of the header's rule, which differ in how `best` is made."""
     S0, P, E0 = ptr.numel() - 1, idx.numel(), edges.shape[0]
     dev, lib, i32 = ptr.device, _lib.lib(), torch.int32
 
@@ -416,13 +444,21 @@ def _merge_loop(score, margin: float, pooled: torch.Tensor, ptr: torch.Tensor, i
 
     C, E, rounds, n_hist = S0, E0, 0, 0
     regions, merges = [S0], []
+    small, small_rounds, scored = False, 0, False                # small: the elimination rounds have begun
     while True:
         stream = _stream()
-        score(cur, C, E, simi, stream)
+        if not scored:
+            score(cur, C, E, simi, stream)
+        scored = False
         if E == 0 or C <= max(min_regions, 1) or (max_rounds is not None and rounds >= max_rounds):
             break
         nxt = spare[rounds & 1]
-        check(lib.dm_merge_best(cur["edges"].data_ptr(), simi.data_ptr(), E, C, margin, best.data_ptr(), stream), "dm_merge_best")
+        if small:
+            args = (cur["edges"].data_ptr(), simi.data_ptr(), E, C, cur["count"].data_ptr(), min_area, best.data_ptr(), stream)
+            check(lib.dm_merge_best_small(*args), "dm_merge_best_small")
+            check(lib.dm_merge_accept(*args), "dm_merge_accept")
+        else:
+            check(lib.dm_merge_best(cur["edges"].data_ptr(), simi.data_ptr(), E, C, margin, best.data_ptr(), stream), "dm_merge_best")
         check(lib.dm_merge_match(cur["edges"].data_ptr(), best.data_ptr(), E, C, picked.data_ptr(), root.data_ptr(), pick.data_ptr(),
                                  meta.data_ptr(), stream), "dm_merge_match")
         f = _lib.DmMergeFold()
@@ -440,11 +476,15 @@ def _merge_loop(score, margin: float, pooled: torch.Tensor, ptr: torch.Tensor, i
         check(lib.dm_merge_fold_edges(skeys.data_ptr(), order.data_ptr(), ptr_of(cur["weights"]), E, nxt["edges"].data_ptr(),
                                       ptr_of(nxt["weights"]), meta[2:].data_ptr(), stream), "dm_merge_fold_edges")
         n_pick, C_new, E_new = meta.tolist()
+        if n_pick == 0 and min_area and not small:               # the margin rounds are over: the same partition, the same scores,
+            small = scored = True                                # now by the elimination rule
+            continue
         if n_pick == 0 or C_new < min_regions:                   # nothing merged / the round would go too far: it is dropped whole
             break
         cur = {k: (None if v is None else v[:C_new + 1] if k == "ptr" else v[:E_new] if k in ("edges", "weights") else
                    v if k in ("idx", "region_of") else v[:C_new]) for k, v in nxt.items()}
         C, E, rounds, n_hist = C_new, E_new, rounds + 1, n_hist + n_pick
+        small_rounds += small
         regions.append(C)
         merges.append(n_pick)
 
@@ -455,7 +495,8 @@ def _merge_loop(score, margin: float, pooled: torch.Tensor, ptr: torch.Tensor, i
     return MergeResult(region_of=cur["region_of"].clone(), ptr=cur["ptr"].clone(), idx=cur["idx"].clone(), edges=cur["edges"].clone(),
                        weights=None if weights is None else cur["weights"].clone(), stats=out_stats, pooled=pooled[:C].clone(),
                        simi=simi[:E].clone(), rep=cur["rep"].clone(), rounds=rounds, history=history[:n_hist].clone(),
-                       history_simi=history_simi[:n_hist].clone(), regions_per_round=regions, merges_per_round=merges)
+                       history_simi=history_simi[:n_hist].clone(), regions_per_round=regions, merges_per_round=merges,
+                       small_rounds=small_rounds)
 
 
 # ---- multiresolution region merging (csrc/dm_mrs.hip; the rule: include/deepmerge_hip.h; spec tests/mrs_ref.py) ----
@@ -554,7 +595,7 @@ def pixel_regions(tile: torch.Tensor) -> Tuple[Dict[str, torch.Tensor], torch.Te
 
 def mrs(tile: torch.Tensor, scale: float, shape: float = 0.1, compactness: float = 0.5, band_weights=None,
         labels: Optional[torch.Tensor] = None, n_labels: Optional[int] = None, max_rounds: Optional[int] = None,
-        min_regions: int = 0) -> MergeResult:
+        min_regions: int = 0, min_area: int = 0) -> MergeResult:
     """Multiresolution segmentation: mutual-best region merging by `region_merge_cost`, the classical baseline of the learned
     merge and a second source of superpixels.
 
@@ -564,8 +605,10 @@ def mrs(tile: torch.Tensor, scale: float, shape: float = 0.1, compactness: float
     (labels None: S0 = H * W <= 2^24 and `result.region_of.view(H, W)` is the label raster) or from a label raster (labels int32
     [H,W] with every id in [0, n_labels) present: `result.labels(labels)` is the raster).  The result has pooled [C,0], ptr zeros,
     idx empty, simi = the cost of the final partition's edges; `labels()`, `polygons()`, `simplified()`, `scores()` and
-    `region_of_at()` work as on any MergeResult.  Stops as `merge_regions` does.  The inputs are not modified; one small readback per
-    round."""
+    `region_of_at()` work as on any MergeResult.  Stops as `merge_regions` does; min_area > 0 (pixels) adds its elimination rounds,
+    with the cost as the score: what `scale` leaves below that area (single pixels and specks from a pixel start) joins its
+    cheapest neighbour.  The inputs are not modified; one small readback per round."""
+    min_area = _check_min_area(min_area)
     _check_tile(tile)
     bands, H, W = tile.shape
     _mrs_check(scale, min(bands, 3), shape, compactness, band_weights, max_rounds)
@@ -582,7 +625,8 @@ def mrs(tile: torch.Tensor, scale: float, shape: float = 0.1, compactness: float
         stats = label_stats(labels, tile, int(n_labels))
         _check_no_empty_region(stats)                            # (the one readback before round 1)
         edges, weights = rag_edges(labels, int(n_labels))
-    return mrs_graph(stats, edges, weights, scale, shape, compactness, band_weights, max_rounds, min_regions, _checked=True)
+    return mrs_graph(stats, edges, weights, scale, shape, compactness, band_weights, max_rounds, min_regions, min_area=min_area,
+                     _checked=True)
 
 
 def _mrs_check(scale, nb: int, shape, compactness, band_weights, max_rounds) -> Tuple[float, float, float, List[float]]:
@@ -603,11 +647,12 @@ def _check_no_empty_region(stats: Dict[str, torch.Tensor]):
 
 def mrs_graph(stats: Dict[str, torch.Tensor], edges: torch.Tensor, weights: torch.Tensor, scale: float, shape: float = 0.1,
               compactness: float = 0.5, band_weights=None, max_rounds: Optional[int] = None, min_regions: int = 0,
-              _checked: bool = False) -> MergeResult:
+              min_area: int = 0, _checked: bool = False) -> MergeResult:
     """The rounds of `mrs` on a graph that is already built: stats as `label_stats` returns them (every region with count > 0,
     else ValueError), edges int32 [E,2] with a < b, sorted and unique, weights int32 [E] as `rag_edges` returns them.  `mrs` builds
-    its graph from one raster and calls this; `scene.mrs_labels` builds it from a scene's label raster tile by tile.  The inputs
-    are not modified."""
+    its graph from one raster and calls this; `scene.mrs_labels` builds it from a scene's label raster tile by tile.  min_area: as
+    `mrs` takes it.  The inputs are not modified."""
+    min_area = _check_min_area(min_area)
     _on_device(edges, weights, *(stats[k] for k in _STAT_KEYS))
     S0 = stats["count"].numel()
     nb = _check_stats(stats, S0)
@@ -627,12 +672,13 @@ def mrs_graph(stats: Dict[str, torch.Tensor], edges: torch.Tensor, weights: torc
 
     return _merge_loop(score, scale * scale, torch.empty((S0, 0), dtype=torch.float32, device=dev),
                        torch.zeros(S0 + 1, dtype=torch.int32, device=dev), torch.empty(0, dtype=torch.int32, device=dev), edges, weights,
-                       stats, nb, max_rounds, min_regions)
+                       stats, nb, max_rounds, min_regions, min_area)
 
 
 def mrs_segment(tile: torch.Tensor, scale: float, **kw) -> Tuple[torch.Tensor, int]:
     """(labels int32 [H,W] with dense ids 0..n-1, n): `mrs` as a segmenter, the pair `slic` returns, so that
-    `FeatureIO.merge_tile(tile, *mrs_segment(tile, scale))` is the pipeline on multiresolution superpixels."""
+    `FeatureIO.merge_tile(tile, *mrs_segment(tile, scale))` is the pipeline on multiresolution superpixels.  kw: `mrs`'s keywords
+    (min_area among them: no superpixel below that many pixels)."""
     res = mrs(tile, scale, **kw)
     start = kw.get("labels")
     raster = res.region_of.view(tile.shape[1], tile.shape[2]).clone() if start is None else res.labels(start)

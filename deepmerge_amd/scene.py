@@ -473,8 +473,9 @@ def segment_scene(fio, source, tile=4096, segmenter: Optional[Callable] = None, 
     array or a CPU tensor), or an array / memmap / CPU tensor, which is wrapped in an ArraySource; tile: core side, an int or
     (th, tw); segmenter(core_tile uint8 [bands,th,tw] on the device) -> (labels int32 [th,tw], n), default `rag.slic` with its
     defaults (ids outside [0, n) are written as -1, "no superpixel"); k, max_window: as `rag.sample_points` takes them; margin,
-    merge_kwargs: as `rag.merge_regions` takes them; labels_out: a writable int32 [H,W] numpy array or memmap for the scene-wide
-    superpixel raster, allocated if None; stage_times: a dict that receives seconds per stage (synchronises at stage boundaries).
+    merge_kwargs: as `rag.merge_regions` takes them (max_rounds, min_regions, min_area; they reach the one merge on every path
+    below); labels_out: a writable int32 [H,W] numpy array or memmap for the scene-wide superpixel raster, allocated if None;
+    stage_times: a dict that receives seconds per stage (synchronises at stage boundaries).
     labels, n_labels: the scene's superpixels brought along as a label raster on the host, whose regions may cross seams: the call
     is `segment_labels(fio, source, labels, n_labels, ...)` (no segmenter and no labels_out go with it: ValueError).
     cross_seams=True makes the superpixels here and lets them cross the seams: `slic_labels(source, tile, **(slic or {}),
@@ -695,14 +696,17 @@ def segment_labels(fio, source, labels, n_labels: int, tile=4096, k: int = 3, ma
 
 def mrs_labels(source, labels, n_labels: int, scale: float, shape: float = 0.1, compactness: float = 0.5, band_weights=None,
                max_rounds: Optional[int] = None, min_regions: int = 0, tile=4096, device="cuda:0",
-               stage_times: Optional[dict] = None) -> "rag.MergeResult":
+               stage_times: Optional[dict] = None, min_area: int = 0) -> "rag.MergeResult":
     """The classical baseline on a scene's graph: `rag.mrs(whole scene, scale, labels=whole raster, n_labels=n_labels, ...)` bit
     for bit, whatever the tile size -- `label_graph` without points, then `rag.mrs_graph`.  Every id in [0, n_labels) must occur
-    (the same ValueError).  A pixel start on a scene stays out of scope: a merge takes at most 2^24 regions."""
+    (the same ValueError).  min_area: as `rag.mrs` takes it.  A pixel start on a scene stays out of scope: a merge takes at most
+    2^24 regions."""
+    min_area = rag._check_min_area(min_area)
     shape3 = tuple(_as_source(source).shape)
     rag._mrs_check(scale, min(int(shape3[0]), 3) if len(shape3) == 3 and shape3[0] >= 1 else 1, shape, compactness, band_weights, max_rounds)
     g = label_graph(source, labels, n_labels, tile=tile, k=1, device=device, stage_times=stage_times, points=False)
-    return rag.mrs_graph(g["stats"], g["edges"], g["weights"], scale, shape, compactness, band_weights, max_rounds, min_regions)
+    return rag.mrs_graph(g["stats"], g["edges"], g["weights"], scale, shape, compactness, band_weights, max_rounds, min_regions,
+                         min_area=min_area)
 
 
 # ---- rings and arcs across tile seams (DESIGN.md 3.5.10; csrc/dm_scene_vector.hip) ---------------------------------------------------

@@ -594,7 +594,24 @@ int dm_merge_round(const int32_t *edges, const uint8_t *merge, int32_t E, int32_
  * All results are integers or floats copied bit for bit; every reduction is an integer min / add (order-independent).
  * Every entry point validates before any launch, launches on `stream`, never synchronises and never allocates.
  *
+ * The elimination rule (minimum region area, additive in ABI 7; spec tests/merge_small_ref.py).  With min_area = A >= 1 the rounds
+ * above run until one picks nothing; only then (not after max_rounds or min_regions ended them) elimination rounds follow.  Region
+ * r is small iff count[r] < A (int64; count 0 is small, count == A is not).  A round replaces step 2 by:
+ *   2a. propose: an edge is usable iff simi == simi (NaN never is; there is no margin).  Every small region s takes best[s] = the
+ *       smallest key (bits(simi) << 32) | other_id over its usable edges, whatever the size of the other end; a non-small region
+ *       gets all-ones.
+ *   2b. accept: a non-small region t takes best[t] = the smallest key (bits(simi) << 32) | s over the small regions s whose best[s]
+ *       names t, all-ones if there is none.
+ * Steps 1 and 3 to 5 are unchanged: an edge is picked iff its two regions name each other, so two small regions merge only when
+ * they propose to each other, and a small region whose choice proposed or accepted elsewhere waits a round.  best[r] is still one
+ * value per region, so the picks are a matching.  The rounds stop when one picks nothing (then no small region has a usable edge),
+ * at max_rounds (which counts both kinds of round), or before a round that would leave fewer than min_regions regions.  They do
+ * not go back to the margin rule.
+ *
  * dm_merge_best: best uint64 [C] (cleared by the call), one pass over the E >= 1 edges.  1 <= C <= 2^24.
+ * dm_merge_best_small: step 2a; count int64 [C], min_area >= 1; best is cleared by the call.  dm_merge_accept: step 2b, in place on
+ *   the best that dm_merge_best_small left, in a launch after it on the same stream (it reads entries of small regions and writes
+ *   entries of non-small ones only).
  * dm_merge_match: picked uint8 [E]; root int32 [C] (root[b] = a for a picked edge, else the identity); pick int32 [C] = index of
  *   the picked edge at its surviving region a, else -1; n_picked[0] = number of picked edges.  All (re)initialised by the call.
  * dm_merge_fold_regions: step 4 for regions and step 5 (see DmMergeFold).  dm_merge_edge_keys + dm_merge_fold_edges: step 4 for
@@ -622,6 +639,10 @@ typedef struct {
   int32_t C, P, E, S0, bands, round, hist_base, hist_cap;
 } DmMergeFold;
 int dm_merge_best(const int32_t *edges, const float *simi, int32_t E, int32_t C, float margin, uint64_t *best, void *stream);
+int dm_merge_best_small(const int32_t *edges, const float *simi, int32_t E, int32_t C, const int64_t *count, int64_t min_area,
+                        uint64_t *best, void *stream);
+int dm_merge_accept(const int32_t *edges, const float *simi, int32_t E, int32_t C, const int64_t *count, int64_t min_area,
+                    uint64_t *best, void *stream);
 int dm_merge_match(const int32_t *edges, const uint64_t *best, int32_t E, int32_t C, uint8_t *picked, int32_t *root, int32_t *pick,
                    int32_t *n_picked, void *stream);
 int dm_merge_fold_regions(const DmMergeFold *args, void *stream);
