@@ -530,7 +530,10 @@ int dm_pair_eval_summary(const float *term, const float *simi, const float *flag
  *   labels int32 [H,W] (superpixel id, ids outside [0,S) are ignored); tile uint8 [bands,H,W].
  * dm_label_stats: count[S], sum / sumsq [S, min(bands,3)] (int64), bbox int32 [S,4] = xmin,ymin,xmax,ymax
  *   (INT_MAX,INT_MAX,-1,-1 for an id that never occurs), peri int64 [S,2] = pixel edges shared with another label /
- *   lying on the raster border.  All outputs are (re)initialised by the call.
+ *   lying on the raster border.  All outputs are (re)initialised by the call.  The id -2 is RESERVED: it is the pass's own
+ *   marker for "outside the raster", so a pixel that carries it is ignored like every id outside [0,S), and the pixel edges
+ *   its four neighbours share with it count as raster border (column 1), not as shared with another label.  The raster is
+ *   not searched for it.
  * dm_label_features: float32 [S,15] = area, peri, len, width, smooth, std0..2, mean0..2, shapeness, compact, bright,
  *   border (the attribute order of MyUtils1.py:79-114).
  * dm_rag_edges: unique unordered 4-neighbour label pairs a < b as keys a*S+b with the number of shared pixel edges.

@@ -6,6 +6,8 @@ border) from shapefiles produced by external GIS software, whose formulas it doe
 an on-device replacement with a spec of the build's own; this file IS that spec:
 
   4-neighbourhood on the pixel grid; ids outside [0, S) are ignored.
+  The id -2 is reserved: it marks "outside the raster", so a pixel edge whose other side carries -2 counts as border, not
+  as inner (every other id outside [0, S), -1 included, is "a different id").  Rasters are not searched for it.
   edge (a < b)      : some pixel of a is a 4-neighbour of a pixel of b; weight = number of such pixel edges
   area              : pixel count
   peri              : pixel edges whose other side is a different id (inner) or outside the raster (border)
