@@ -28,7 +28,7 @@ import torch.distributed as dist
 from . import ops
 from .callbacks import LossHistory
 from .checkpoint import load_checkpoint, save_checkpoint
-from .dataset import PairDataset
+from .dataset import MAX_HARDNESS, MAX_WEIGHT_TOTAL, PairDataset, balance_weights, hardness_weights
 from .evaluate import PairEvaluator, format_result
 from .ExtractFeatures import Euclidean_distance  # noqa: F401  (Train_SMT.Euclidean_distance, Train_SMT.py:115-131)
 from .feed import PairFeed
@@ -65,7 +65,8 @@ def train(net, margin, train_bs, lr_init, normMean, normStd, lamda, belta, is_re
           dataset: PairDataset = None, num_epochs: int = NUM_EPOCHS, milestones: Sequence[int] = (40, 80), gamma: float = 0.2,
           model_paras_path: str = MODEL_PARAS_PATH, val_dataset: Optional[PairDataset] = None, val_batch: int = 1000,
           val_thresholds: Optional[Sequence[float]] = None, log_dir: Optional[str] = None,
-          val_history: Optional[list] = None, augment: Optional[str] = None, radiometric=None) -> Tuple[List[int], List[float]]:
+          val_history: Optional[list] = None, augment: Optional[str] = None, radiometric=None, balance: Optional[float] = None,
+          mining: Optional[ops.Mining] = None, draws: Optional[int] = None) -> Tuple[List[int], List[float]]:
     """`Train_SMT.train` with the reference's positional signature (normMean / normStd are unused, as upstream; lamda / belta go
     to Loss).  `dataset` replaces the reference's hard-coded shapefile folders; the draw's seed is the dataset's.  Returns
     (epoch indices, per-epoch mean loss = sum of step losses / number of steps), one entry per epoch run.
@@ -81,7 +82,23 @@ def train(net, margin, train_bs, lr_init, normMean, normStd, lamda, belta, is_re
 
     radiometric: None, an ops.Radiometric or a (contrast, brightness, colour) triple -- handed to dataset.epoch: every pair of every
     epoch is fed with a gain and an offset per band keyed by (dataset seed, epoch, pair), both of its crops and designed rows alike
-    (DESIGN.md 3.8 / 3.9).  Independent of `augment`; resumes like it; never applied in validation."""
+    (DESIGN.md 3.8 / 3.9).  Independent of `augment`; resumes like it; never applied in validation.
+
+    balance: None or the share p of positive pairs the model should see -- every epoch is `draws` pairs sampled with replacement
+    under dataset.balance_weights(flag, p) (dataset.epoch(weights=)): a draw is positive with probability exactly
+    round(65536 p) / 65536 whatever the list's ratio.  The weights are a function of the list alone, so a resumed run equals the
+    uninterrupted one bit for bit, always.
+
+    mining: None or an ops.Mining(every=k, cap=c[, floor_share=f]) -- at the start of the run's first epoch and of every epoch e with
+    e % k == 0, dataset.pair_terms(net, val_batch, margin, key=e) evaluates the loss term of every training pair with the model as it
+    stands, and dataset.hardness_weights(term, f, c) turns it into weights (times the balance weights when both are given) that the
+    epochs up to the next refresh are sampled with.  The weights are not in the checkpoint (its format is the reference's): a resumed
+    run recomputes them at its first epoch, from the restored model.  So it equals the uninterrupted run bit for bit iff the resume
+    epoch is a refresh epoch of that run; checkpoints fall after epochs 5, 10, ..., so `every` in {1, 5} qualifies.  Other values
+    train correctly but resume on fresher weights than the uninterrupted run had at that epoch.
+
+    draws: the epoch length in pairs when balance or mining is given (default: len(dataset)); the steps, the captured graph and the
+    partial last batch follow it.  All three None: nothing of the above runs."""
     if dataset is None:
         raise ValueError("train() needs dataset=PairDataset.from_arrays(...) (the reference's hard-coded folders are not portable)")
     if val_dataset is not None and val_dataset is dataset:
@@ -94,6 +111,13 @@ def train(net, margin, train_bs, lr_init, normMean, normStd, lamda, belta, is_re
     if augment is not None and augment not in ops.ORIENT_MASKS:
         raise ValueError(f"augment must be None, 'flips' or 'd4', got {augment!r}")
     radiometric = ops.Radiometric.of(radiometric)
+    if mining is not None and not isinstance(mining, ops.Mining):
+        raise ValueError(f"mining must be None or an ops.Mining, got {mining!r}")
+    sampled = balance is not None or mining is not None
+    if draws is not None and not sampled:
+        raise ValueError("draws needs balance= or mining=: an unweighted epoch is every pair exactly once")
+    if draws is not None and not 1 <= int(draws) <= 2 ** 30:
+        raise ValueError(f"draws must be in 1 .. 2^30, got {draws}")
     scales = [int(s) for s in getattr(net, "input_image_scales", ())]
     if not scales:
         raise ValueError(f"{type(net).__name__} has no input_image_scales: train() feeds patch pyramids")
@@ -112,6 +136,12 @@ def train(net, margin, train_bs, lr_init, normMean, normStd, lamda, belta, is_re
         lr0 = float(trainer.lr)                 # optimizer.load_state_dict brings the saved lr back (Train_SMT.py:196-197)
 
     B, N = int(train_bs), len(dataset)
+    class_w = weights = None
+    if sampled:
+        N = len(dataset) if draws is None else int(draws)          # the epoch length
+        class_w = weights = balance_weights(dataset.host.flag, balance).to(dev) if balance is not None else None
+        if mining is not None and class_w is not None and int(class_w.sum()) * MAX_HARDNESS >= MAX_WEIGHT_TOTAL:
+            raise ValueError("balance with mining: the total weight could reach 2^62")    # at h = 256: whatever the model says
     n_full, tail = N // B, N % B
     feed = tail_feed = None
     if n_full:
@@ -123,14 +153,20 @@ def train(net, margin, train_bs, lr_init, normMean, normStd, lamda, belta, is_re
         if val_dataset is not None else None
     history = LossHistory(log_dir) if log_dir is not None else None
     name = getattr(net, "name", type(net).__name__)
-    print(N, dataset.positive_pair_number, dataset.negative_pair_number)
+    print(len(dataset), dataset.positive_pair_number, dataset.negative_pair_number)
     iteration_history_train, loss_history_train = [], []
     previous_time = 0.0
     start_time = time.time()
     for epoch in range(start_epoch, num_epochs):
         lr = epoch_lr(lr0, epoch - start_epoch, milestones, gamma)
         trainer.lr = lr                         # what the optimizer holds this epoch (checkpoint.optimizer_state_dict writes it)
-        table = dataset.epoch(epoch, B, augment=augment, radiometric=radiometric)
+        if mining is not None and (epoch == start_epoch or epoch % mining.every == 0):
+            term = dataset.pair_terms(net, val_batch, margin, key=epoch)
+            weights = hardness_weights(term, mining.floor_share, mining.cap, class_weights=class_w)
+        if sampled:
+            table = dataset.epoch(epoch, B, augment=augment, radiometric=radiometric, weights=weights, draws=N)
+        else:
+            table = dataset.epoch(epoch, B, augment=augment, radiometric=radiometric)
         total = torch.zeros((), dtype=torch.float32, device=dev)
         for s in range(len(table)):
             if s < n_full:

@@ -192,6 +192,10 @@ SIGNATURES = {
     "dm_pair_epoch_draw": (_I, [C.POINTER(DmPairDraw), _P]),
     "dm_pair_epoch_orient": (_I, [C.c_uint64, _I, _I, _I, _I, _P, _P]),
     "dm_pair_epoch_radiometric": (_I, [C.c_uint64, _I, _I, _I, _I, _I, _I, _I, _P, _P]),
+    "dm_pair_epoch_select": (_I, [_P, _I, _I, C.c_uint64, _I, _P, _P]),
+    "dm_pair_epoch_draw_src": (_I, [C.POINTER(DmPairDraw), _P, _I, _P]),
+    "dm_pair_epoch_orient_src": (_I, [C.c_uint64, _I, _I, _I, _I, _P, _P]),
+    "dm_pair_epoch_radiometric_src": (_I, [C.c_uint64, _I, _I, _I, _I, _I, _I, _I, _P, _P]),
     "dm_contrastive_terms": (_I, [_P, _P, _P, _F, _P, _P, _I, _I, _P]),
     "dm_pair_eval_workspace_bytes": (_L, [_L, _I]),
     "dm_pair_eval_summary": (_I, [_P, _P, _P, _L, _P, _I, _P, _P, _P, _P, _P]),

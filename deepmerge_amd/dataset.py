@@ -12,8 +12,9 @@ All ids are checked once, on the host, when the dataset is built (`build_host`, 
 """
 from __future__ import annotations
 
+import math
 from dataclasses import dataclass
-from typing import Dict, List, Optional, Sequence
+from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
@@ -23,6 +24,8 @@ from .feed import PairTable
 from .patches import geo_to_pixel
 
 MAX_WINDOW = 384        # the gather's LDS staging limit (csrc/dm_patches.hip MAX_WINDOW)
+MAX_WEIGHT_TOTAL = 1 << 62   # the sum of an epoch's pair weights stays below this (dm_pair_epoch_select)
+MAX_HARDNESS = 256           # hardness_weights' values are 1 .. MAX_HARDNESS
 
 
 def read_pair_list(path: str) -> np.ndarray:
@@ -178,9 +181,72 @@ def holdout_hash(seed: int, image: int, a, b) -> np.ndarray:
     return k
 
 
+def balance_class_weights(n_pos: int, n_neg: int, positive_share: float) -> Tuple[int, int]:
+    """(weight of a positive pair, weight of a negative pair), Python ints, such that a weighted draw is positive with probability
+    exactly P / 65536, P = round(65536 positive_share): P n_neg and (65536 - P) n_pos, both divided by their gcd.  Raises ValueError
+    when P is outside 1 .. 65535, a class is empty, or the total weight n_pos w_pos + n_neg w_neg would reach 2^62."""
+    share = float(positive_share)
+    P = int(round(65536 * share)) if math.isfinite(share) else 0
+    if not 1 <= P <= 65535:
+        raise ValueError(f"positive_share must round to 1/65536 .. 65535/65536, got {positive_share!r}")
+    n_pos, n_neg = int(n_pos), int(n_neg)
+    if n_pos < 1 or n_neg < 1:
+        raise ValueError(f"balance needs pairs of both classes, got {n_pos} positive and {n_neg} negative")
+    w_pos, w_neg = P * n_neg, (65536 - P) * n_pos
+    g = math.gcd(w_pos, w_neg)
+    w_pos, w_neg = w_pos // g, w_neg // g
+    if n_pos * w_pos + n_neg * w_neg >= MAX_WEIGHT_TOTAL:
+        raise ValueError(f"balance: the total weight of {n_pos} positive and {n_neg} negative pairs reaches 2^62")
+    return w_pos, w_neg
+
+
+def balance_weights(flag, positive_share: float) -> torch.Tensor:
+    """int64 [N] pair weights (on flag's device) for PairDataset.epoch(weights=) under which a draw is a positive pair (flag 1) with
+    probability exactly round(65536 positive_share) / 65536, whatever the list's own ratio; see `balance_class_weights`.  flag: the
+    pairs' 0 / 1 flags, a tensor or an array (the class counts are one host read when it lives on the device)."""
+    f = flag if isinstance(flag, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(flag))
+    f = f.reshape(-1)
+    n_pos = int((f == 1).sum())
+    w_pos, w_neg = balance_class_weights(n_pos, f.numel() - n_pos, positive_share)
+    return torch.where(f == 1, w_pos, w_neg).to(torch.int64)
+
+
+def hardness_weights(term: torch.Tensor, floor_share: float = 1.0 / 16.0, cap: float = 1.0,
+                     class_weights: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """int64 [N] pair weights from the per-pair loss terms (PairDataset.pair_terms): an integer hardness h in 1 .. 256, linear in the
+    term and saturating at `cap`, by a fixed fp32 sequence (tests/sampling_ref.py pins it; term fp32, every step an fp32 one):
+      scale = 255.0f / (float)cap         x = term * scale         x = 0 where x is NaN         x = min(255.0f, max(0.0f, x))
+      h = 1 + (int32)x  (truncation)      h = max(h, F),  F = min(256, max(1, round(256 floor_share)))
+    so a term of 0 (or -0, a negative one, NaN) gives the floor and a term >= cap gives 256.  floor_share in (0, 1]: the least
+    weight as a share of the greatest -- pairs the model already separates keep being seen.  class_weights: int64 [N] (e.g.
+    balance_weights') to compose with by multiplication, w = class_w h; refused (one host read) when sum(class_w) * 256 reaches 2^62,
+    a bound that does not depend on the terms.  No kernel: elementwise torch on the terms' device."""
+    cap32 = np.float32(cap)
+    if not (np.isfinite(cap32) and cap32 > 0):
+        raise ValueError(f"hardness_weights: cap must be a finite number > 0 in float32, got {cap!r}")
+    if not 0.0 < float(floor_share) <= 1.0:
+        raise ValueError(f"hardness_weights: floor_share must be in (0, 1], got {floor_share!r}")
+    if term.dtype != torch.float32 or term.dim() != 1:
+        raise ValueError(f"hardness_weights: term must be a float32 [N] tensor, got {term.dtype} {tuple(term.shape)}")
+    floor = min(MAX_HARDNESS, max(1, int(round(MAX_HARDNESS * float(floor_share)))))
+    scale = float(np.float32(255.0) / cap32)                 # fp32 quotient; exact as a Python float, and exact again as an fp32 scalar
+    x = term * torch.tensor(scale, dtype=torch.float32, device=term.device)
+    x = torch.where(x != x, torch.zeros_like(x), x).clamp_(0.0, 255.0)
+    h = (x.to(torch.int32) + 1).clamp_(min=floor).to(torch.int64)
+    if class_weights is None:
+        return h
+    if class_weights.dtype != torch.int64 or tuple(class_weights.shape) != tuple(term.shape):
+        raise ValueError(f"hardness_weights: class_weights must be int64 {tuple(term.shape)}, got {class_weights.dtype} {tuple(class_weights.shape)}")
+    lo, total = (int(v) for v in torch.stack((class_weights.min(), class_weights.sum())).cpu())
+    if lo < 0 or not 0 < total < MAX_WEIGHT_TOTAL // MAX_HARDNESS:
+        raise ValueError(f"hardness_weights: class_weights must be >= 0 with 0 < sum * {MAX_HARDNESS} < 2^62, got min {lo}, sum {total}")
+    return class_weights * h
+
+
 class EpochTable:
     """One epoch's sample table on the device, in the per-step blocked layout: `len()` steps, step s is a feed.PairTable of
-    b_s = min(batch, N - s batch) pairs made of views (rows [2 s batch, 2 s batch + 2 b_s), flags [s batch, s batch + b_s))."""
+    b_s = min(batch, N - s batch) pairs made of views (rows [2 s batch, 2 s batch + 2 b_s), flags [s batch, s batch + b_s)).
+    A sampled epoch (PairDataset.epoch(weights=)) has n_pairs = its number of draws and a `src` column: the pair of each position."""
 
     def __init__(self, cols: Dict[str, torch.Tensor], n_pairs: int, batch: int, epoch: int):
         self.cols, self.n_pairs, self.batch, self.epoch = cols, n_pairs, batch, epoch
@@ -225,6 +291,10 @@ class PairDataset:
                       "flag": torch.empty((N,), dtype=torch.float32, device=dev), "point_id": i32(2 * N)}
         self._orient = None         # int32 [2N], allocated by the first epoch(augment=...) and kept
         self._radio = None          # int32 [2N, bands, 2], allocated by the first epoch(radiometric=...) and kept
+        self._sampled = None        # the sampled epoch's own columns (2 draws rows + src), allocated by the first epoch(weights=...)
+        self._sampled_rows = 0      # ... and reallocated only when `draws` grows
+        self._terms = None          # pair_terms' own columns and arange, allocated by its first call
+        self._term_feeds = {}       # ... and its feeds, per (model input form, batch)
 
     @classmethod
     def from_arrays(cls, images: Sequence[Dict], seed: int = 0, n_scales: int = 3, device="cuda:0") -> "PairDataset":
@@ -304,19 +374,78 @@ class PairDataset:
             raise ValueError(f"the dataset was validated for {self.host.n_scales} scales, not {n_scales}")
         return self.host.max_windows[:n_scales]
 
-    def epoch(self, e: int, batch: int, augment: Optional[str] = None, radiometric=None) -> EpochTable:
+    def _draw_inputs(self):
+        return (self.pairs, self.flag, self.poly_off, self.poly_pts, self.pt_tile, self.pt_xy, self.pt_inner, self.pt_obj, self.pt_region)
+
+    def _empty_cols(self, rows: int, **extra) -> Dict[str, torch.Tensor]:
+        """Uninitialised table columns for `rows` positions (2 rows samples)."""
+        dev = self.device
+        i32 = lambda *shape: torch.empty(shape, dtype=torch.int32, device=dev)
+        cols = {"tile_id": i32(2 * rows), "xy": i32(2 * rows, 2), "inner": i32(2 * rows), "obj": i32(2 * rows),
+                "region": torch.empty((2 * rows, 15), dtype=torch.float32, device=dev),
+                "flag": torch.empty((rows,), dtype=torch.float32, device=dev), "point_id": i32(2 * rows)}
+        cols.update(extra)
+        return cols
+
+    def _epoch_sampled(self, e: int, batch: int, augment, radiometric, weights: torch.Tensor, draws: Optional[int]) -> EpochTable:
+        N = len(self)
+        M = N if draws is None else int(draws)
+        if not 1 <= M <= 2 ** 30:
+            raise ValueError(f"draws must be in 1 .. 2^30, got {draws}")
+        if not isinstance(weights, torch.Tensor) or weights.dtype != torch.int64 or tuple(weights.shape) != (N,) or weights.device != self.device:
+            raise ValueError(f"weights must be an int64 [{N}] tensor on {self.device}, got "
+                             f"{getattr(weights, 'dtype', type(weights).__name__)} {tuple(getattr(weights, 'shape', ()))}")
+        bands = int(self.tiles.shape[1])
+        cum = torch.cumsum(weights.contiguous(), 0)
+        # the one readback of a sampled epoch.  A sum that wraps int64 leaves a negative prefix behind (each weight is < 2^63)
+        lo, cum_lo, total = (int(v) for v in torch.stack((weights.min(), cum.min(), cum[-1])).cpu())
+        if lo < 0:
+            raise ValueError(f"weights must be >= 0, the smallest is {lo}")
+        if cum_lo < 0 or not 0 < total < MAX_WEIGHT_TOTAL:
+            raise ValueError("weights: the total must be in 1 .. 2^62 - 1" + (" (every weight is 0)" if total == 0 and cum_lo == 0 else
+                                                                               f", got {total if cum_lo >= 0 else 'an int64 overflow'}"))
+        with torch.cuda.device(self.device):
+            if M > self._sampled_rows:
+                i32 = lambda *shape: torch.empty(shape, dtype=torch.int32, device=self.device)
+                self._sampled = self._empty_cols(M, src=i32(M), orient=i32(2 * M), radio=i32(2 * M, bands, 2))
+                self._sampled_rows = M
+            c = {k: v[:(M if k in ("flag", "src") else 2 * M)] for k, v in self._sampled.items()}
+            orient, radio = c.pop("orient"), c.pop("radio")
+            ops.pair_epoch_select(cum, self.seed, e, c["src"])
+            ops.pair_epoch_draw(*self._draw_inputs(), self.seed, e, batch, c["tile_id"], c["xy"], c["inner"], c["obj"], c["region"], c["flag"],
+                                point_id=c["point_id"], src=c["src"])
+            if augment is not None:
+                ops.pair_epoch_orient(self.seed, e, M, batch, ops.ORIENT_MASKS[augment], orient, by_position=True)
+                c["orient"] = orient
+            if radiometric is not None:
+                ops.pair_epoch_radiometric(self.seed, e, M, batch, bands, *radiometric.spans(), radio, by_position=True)
+                c["radio"] = radio
+        return EpochTable(c, M, batch, e)
+
+    def epoch(self, e: int, batch: int, augment: Optional[str] = None, radiometric=None, *, weights: Optional[torch.Tensor] = None,
+              draws: Optional[int] = None) -> EpochTable:
         """Draw epoch e (one launch, nothing read back); the table's `point_id` column holds the drawn global point ids.
         augment: None, "flips" or "d4" -- with one more launch, every pair of the epoch also draws a dihedral orientation keyed by
         (seed, epoch, pair) ("flips": the four without the transposition), the table's `orient` column, which
         PairFeed.fill applies to both of the pair's crops.  None: the tables carry orient=None.
         radiometric: None, an ops.Radiometric or a (contrast, brightness, colour) triple -- with one more launch, every pair also
         draws a gain and an offset per band keyed by (seed, epoch, pair), the table's `radio` column, applied by
-        PairFeed.fill to both of the pair's crops and designed rows.  Independent of `augment`.  None: radio=None."""
+        PairFeed.fill to both of the pair's crops and designed rows.  Independent of `augment`.  None: radio=None.
+        weights: None, or an int64 [N] device tensor of pair weights (>= 0, total in 1 .. 2^62 - 1; `balance_weights`,
+        `hardness_weights`) -- the epoch is then `draws` (default N) pairs sampled WITH replacement, pair i with probability
+        w_i / sum(w), by dm_pair_epoch_select: a function of (seed, e, position, weights), with the point draw,
+        orientation and jitter keyed by the position, so a pair drawn twice is seen at two samples.  The weights are checked on the
+        host with one readback per call; the table has n_pairs = draws and a `src` column, and lives in buffers of its own (sized by
+        the largest `draws` so far), so the unweighted table of an earlier call stays as it was.  draws without weights: ValueError."""
         if batch < 1:
             raise ValueError("batch must be >= 1")
         if augment is not None and augment not in ops.ORIENT_MASKS:
             raise ValueError(f"augment must be None, 'flips' or 'd4', got {augment!r}")
         radiometric = ops.Radiometric.of(radiometric)
+        if weights is None and draws is not None:
+            raise ValueError("draws needs weights: an unweighted epoch is every pair exactly once")
+        if weights is not None:
+            return self._epoch_sampled(e, batch, augment, radiometric, weights, draws)
         c = self._cols
         with torch.cuda.device(self.device):
             ops.pair_epoch_draw(self.pairs, self.flag, self.poly_off, self.poly_pts, self.pt_tile, self.pt_xy, self.pt_inner, self.pt_obj,
@@ -334,3 +463,54 @@ class PairDataset:
                 ops.pair_epoch_radiometric(self.seed, e, len(self), batch, bands, *radiometric.spans(), self._radio)
                 c = dict(c, radio=self._radio)
         return EpochTable(c, len(self), batch, e)
+
+    def pair_terms(self, net, batch: int, margin: float, key: int = 0) -> torch.Tensor:
+        """fp32 [N] (a new tensor): the contrastive loss term of every pair IN PAIR ORDER under `net` as it stands -- what
+        `hardness_weights` turns into mining weights.  The pairs are fed through the sampled draw with src = arange(N)
+        (dm_pair_epoch_draw_src: position = pair id, epoch word = `key`, so the sample points are a function of (seed, key, pair)),
+        without augmentation, `batch` pairs per eval-mode forward under no_grad, then ops.contrastive_terms at `margin`.  Its table
+        columns and feeds are its own: neither epoch()'s tables nor a training feed are touched, and no RNG is read."""
+        from .feed import PairFeed
+        from .trainer import stacked_pair_inputs
+        N, B = len(self), int(batch)
+        if B < 1:
+            raise ValueError("batch must be >= 1")
+        scales = [int(s) for s in getattr(net, "input_image_scales", ())]
+        if not scales:
+            raise ValueError(f"{type(net).__name__} has no input_image_scales: pair_terms feeds patch pyramids")
+        rows, numerics = stacked_pair_inputs(net), getattr(net, "numerics", ops.get_numerics())
+        term = torch.empty(N, dtype=torch.float32, device=self.device)
+        d2 = torch.empty(N, dtype=torch.float32, device=self.device)
+        with torch.cuda.device(self.device):
+            if self._terms is None:
+                self._terms = self._empty_cols(N, src=torch.arange(N, dtype=torch.int32, device=self.device))
+            c = self._terms
+            ops.pair_epoch_draw(*self._draw_inputs(), self.seed, key, B, c["tile_id"], c["xy"], c["inner"], c["obj"], c["region"], c["flag"],
+                                point_id=c["point_id"], src=c["src"])
+            table = EpochTable({k: v for k, v in c.items() if k != "src"}, N, B, int(key))
+            feeds = []
+            for b in sorted({table.pairs_in_step(0), table.pairs_in_step(len(table) - 1)}):
+                k = (tuple(scales), bool(rows), str(numerics), b)
+                if k not in self._term_feeds:
+                    self._term_feeds[k] = PairFeed(self.tiles, scales, b, self.max_window(len(scales)), rows=rows, numerics=numerics)
+                feeds.append(self._term_feeds[k])
+            by_size = {f.pairs: f for f in feeds}
+            was_training = net.training
+            net.eval()
+            try:
+                with torch.no_grad():
+                    for s in range(len(table)):
+                        b, off = table.pairs_in_step(s), s * B
+                        feed = by_size[b]
+                        _, _, _, _, flag = feed.fill(table.step(s))
+                        F = net(feed.both, feed.dboth)
+                        if not (isinstance(F, torch.Tensor) and F.dim() == 2 and F.shape[0] == 2 * b and F.dtype == torch.float32):
+                            raise ValueError(f"the model's eval output must be a float32 [{2 * b}, D] tensor, got "
+                                             f"{getattr(F, 'dtype', type(F).__name__)} {tuple(getattr(F, 'shape', ()))}")
+                        F = F.contiguous()
+                        ops.contrastive_terms(F[:b], F[b:], flag, float(margin), d2=d2[off:off + b], term=term[off:off + b])
+            finally:
+                net.train(was_training)
+            for f in feeds:
+                f.check()
+        return term

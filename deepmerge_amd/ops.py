@@ -891,16 +891,19 @@ def pair_batch_gather(tiles: torch.Tensor, tile_id: Optional[torch.Tensor], xy: 
 ORIENT_MASKS = {"flips": 3, "d4": 7}      # augment name -> mask of the orientation draw (3: no transposition)
 
 
-def pair_epoch_orient(seed: int, epoch: int, n_pairs: int, batch: int, mask: int, out: torch.Tensor) -> None:
+def pair_epoch_orient(seed: int, epoch: int, n_pairs: int, batch: int, mask: int, out: torch.Tensor, by_position: bool = False) -> None:
     """One epoch's orientation column in one launch (dm_pair_epoch_orient): the pair at shuffled position j gets
     philox((perm(j), epoch, 3, 0))[0] & mask (7: "d4", 3: "flips"), written to both of its rows in the blocked layout of
-    `pair_epoch_draw`.  out: int32 [2 n_pairs] on the device."""
+    `pair_epoch_draw`.  out: int32 [2 n_pairs] on the device.
+    by_position: the sampled epoch's column (dm_pair_epoch_orient_src) -- `n_pairs` is the number of draws, and position j gets
+    philox((j, epoch, 19, 0))[0] & mask."""
     _need_cuda(out)
     if out.dtype != torch.int32 or not out.is_contiguous() or out.numel() != 2 * int(n_pairs):
         raise ValueError(f"pair_epoch_orient: out must be a contiguous int32 tensor of {2 * int(n_pairs)} elements, got {out.dtype} {tuple(out.shape)}")
     with torch.cuda.device(out.device):
-        check(_lib.lib().dm_pair_epoch_orient(int(seed) & 0xFFFFFFFFFFFFFFFF, int(epoch), int(n_pairs), int(batch), int(mask), out.data_ptr(),
-                                              _stream()), "dm_pair_epoch_orient")
+        name = "dm_pair_epoch_orient_src" if by_position else "dm_pair_epoch_orient"
+        check(getattr(_lib.lib(), name)(int(seed) & 0xFFFFFFFFFFFFFFFF, int(epoch), int(n_pairs), int(batch), int(mask), out.data_ptr(), _stream()),
+              name)
 
 
 @dataclass(frozen=True)
@@ -933,50 +936,95 @@ class Radiometric:
 
 
 def pair_epoch_radiometric(seed: int, epoch: int, n_pairs: int, batch: int, bands: int, gain_span: int, band_span: int, offset_span: int,
-                           out: torch.Tensor) -> None:
+                           out: torch.Tensor, by_position: bool = False) -> None:
     """One epoch's radiometric table in one launch (dm_pair_epoch_radiometric): the pair at shuffled position j draws
     a gain and an offset, and each band a gain deviation, from Philox counter word 4; (gain_c, offset_c) is written to both of its
-    rows in the blocked layout of `pair_epoch_draw`.  out: int32 [2 n_pairs, bands, 2] on the device."""
+    rows in the blocked layout of `pair_epoch_draw`.  out: int32 [2 n_pairs, bands, 2] on the device.
+    by_position: the sampled epoch's table (dm_pair_epoch_radiometric_src) -- `n_pairs` is the number of draws, and the stream is
+    keyed by the position j on counter word 20."""
     _need_cuda(out)
     if out.dtype != torch.int32 or not out.is_contiguous() or out.numel() != 4 * int(n_pairs) * int(bands):
         raise ValueError(f"pair_epoch_radiometric: out must be a contiguous int32 tensor of {4 * int(n_pairs) * int(bands)} elements "
                          f"([2 n_pairs, bands, 2]), got {out.dtype} {tuple(out.shape)}")
     with torch.cuda.device(out.device):
-        check(_lib.lib().dm_pair_epoch_radiometric(int(seed) & 0xFFFFFFFFFFFFFFFF, int(epoch), int(n_pairs), int(batch), int(bands),
-                                                   int(gain_span), int(band_span), int(offset_span), out.data_ptr(), _stream()),
-              "dm_pair_epoch_radiometric")
+        name = "dm_pair_epoch_radiometric_src" if by_position else "dm_pair_epoch_radiometric"
+        check(getattr(_lib.lib(), name)(int(seed) & 0xFFFFFFFFFFFFFFFF, int(epoch), int(n_pairs), int(batch), int(bands), int(gain_span),
+                                        int(band_span), int(offset_span), out.data_ptr(), _stream()), name)
 
 
 def pair_epoch_draw(pairs: torch.Tensor, pair_flag: torch.Tensor, poly_off: torch.Tensor, poly_pts: torch.Tensor, pt_tile: torch.Tensor,
                     pt_xy: torch.Tensor, pt_inner: torch.Tensor, pt_obj: torch.Tensor, pt_region: torch.Tensor, seed: int, epoch: int, batch: int,
                     tile_id: torch.Tensor, xy: torch.Tensor, inner: torch.Tensor, obj: torch.Tensor, region: torch.Tensor, flag: torch.Tensor,
-                    point_id: Optional[torch.Tensor] = None) -> None:
+                    point_id: Optional[torch.Tensor] = None, src: Optional[torch.Tensor] = None) -> None:
     """One epoch's sample table in ONE launch (dm_pair_epoch_draw): the shuffled per-pair point draw keyed by
     (seed, epoch), written into the caller's tensors in the per-step blocked layout (step s = rows [2 s batch, 2 s batch + 2 b_s),
     [left b_s; right b_s]).  Inputs: pairs int32 [N, 2], pair_flag int32 [N], the polygon -> points CSR poly_off int32 [n_poly + 1] /
     poly_pts int32, the point table pt_tile / pt_inner / pt_obj int32 [n_pts], pt_xy int32 [n_pts, 2], pt_region float32 [n_pts, 15].
-    Outputs: tile_id / inner / obj int32 [2N], xy int32 [2N, 2], region float32 [2N, 15], flag float32 [N], point_id int32 [2N] or None."""
+    Outputs: tile_id / inner / obj int32 [2N], xy int32 [2N, 2], region float32 [2N, 15], flag float32 [N], point_id int32 [2N] or None.
+    src: int32 [M] -- the sampled epoch (dm_pair_epoch_draw_src): position j of M takes pair src[j] (`pair_epoch_select`'s column),
+    the point draw is keyed by the position on counter word 17, and the outputs hold M where they held N.  An entry outside [0, N)
+    gives that position the out-of-range row (point id -1, tile id -1, zeros)."""
     if pairs.dim() != 2 or pairs.shape[1] != 2:
         raise ValueError(f"pair_epoch_draw: pairs must be [N, 2], got {tuple(pairs.shape)}")
-    N, n_pts = pairs.shape[0], pt_tile.numel()
-    cols = {"pairs": (pairs, torch.int32, 2 * N), "pair_flag": (pair_flag, torch.int32, N), "poly_off": (poly_off, torch.int32, poly_off.numel()),
+    n_list, n_pts = pairs.shape[0], pt_tile.numel()
+    if src is not None and (src.dim() != 1 or src.numel() < 1):
+        raise ValueError(f"pair_epoch_draw: src must be a non-empty int32 [M], got {tuple(src.shape)}")
+    N = n_list if src is None else src.numel()              # positions
+    cols = {"pairs": (pairs, torch.int32, 2 * n_list), "pair_flag": (pair_flag, torch.int32, n_list), "poly_off": (poly_off, torch.int32, poly_off.numel()),
             "poly_pts": (poly_pts, torch.int32, poly_pts.numel()), "pt_tile": (pt_tile, torch.int32, n_pts), "pt_xy": (pt_xy, torch.int32, 2 * n_pts),
             "pt_inner": (pt_inner, torch.int32, n_pts), "pt_obj": (pt_obj, torch.int32, n_pts), "pt_region": (pt_region, torch.float32, 15 * n_pts),
             "tile_id": (tile_id, torch.int32, 2 * N), "xy": (xy, torch.int32, 4 * N), "inner": (inner, torch.int32, 2 * N),
             "obj": (obj, torch.int32, 2 * N), "region": (region, torch.float32, 30 * N), "flag": (flag, torch.float32, N),
             "point_id": (point_id, torch.int32, 2 * N)}
-    _need_cuda(*(t for t, _, _ in cols.values()))
-    for name, (t, dtype, numel) in cols.items():
+    _need_cuda(*(t for t, _, _ in cols.values()), src)
+    for name, (t, dtype, numel) in list(cols.items()) + [("src", (src, torch.int32, N))]:
         if t is not None and (t.dtype != dtype or not t.is_contiguous() or t.numel() != numel):
             raise ValueError(f"pair_epoch_draw: {name} must be a contiguous {dtype} tensor of {numel} elements, got {t.dtype} {tuple(t.shape)}")
     a = _lib.DmPairDraw()
     for name, (t, _, _) in cols.items():
         setattr(a, name, _ptr(t))
     a.seed = int(seed) & 0xFFFFFFFFFFFFFFFF
-    a.n_pairs, a.n_poly, a.n_poly_pts, a.n_pts = N, poly_off.numel() - 1, poly_pts.numel(), n_pts
+    a.n_pairs, a.n_poly, a.n_poly_pts, a.n_pts = n_list, poly_off.numel() - 1, poly_pts.numel(), n_pts
     a.epoch, a.batch = int(epoch), int(batch)
     with torch.cuda.device(pairs.device):
-        check(_lib.lib().dm_pair_epoch_draw(C.byref(a), _stream()), "dm_pair_epoch_draw")
+        if src is not None:
+            check(_lib.lib().dm_pair_epoch_draw_src(C.byref(a), src.data_ptr(), N, _stream()), "dm_pair_epoch_draw_src")
+        else:
+            check(_lib.lib().dm_pair_epoch_draw(C.byref(a), _stream()), "dm_pair_epoch_draw")
+
+
+def pair_epoch_select(cum: torch.Tensor, seed: int, epoch: int, out: torch.Tensor) -> None:
+    """One epoch's weighted selection in one launch (dm_pair_epoch_select): with cum int64 [N] the inclusive prefix
+    sums of the pairs' integer weights and T = cum[N - 1], position j of M = len(out) draws u = umul64hi(R_j, T) from Philox counter
+    word 5 and takes out[j] = the smallest i with cum[i] > u.  out: int32 [M].  The weights are the caller's to validate (>= 0,
+    0 < T < 2^62: dataset.PairDataset.epoch does); nothing is read back here."""
+    _need_cuda(cum, out)
+    if cum.dtype != torch.int64 or cum.dim() != 1 or not cum.is_contiguous() or cum.numel() < 1:
+        raise ValueError(f"pair_epoch_select: cum must be a contiguous non-empty int64 [N] tensor, got {cum.dtype} {tuple(cum.shape)}")
+    if out.dtype != torch.int32 or out.dim() != 1 or not out.is_contiguous() or out.numel() < 1:
+        raise ValueError(f"pair_epoch_select: out must be a contiguous non-empty int32 [M] tensor, got {out.dtype} {tuple(out.shape)}")
+    with torch.cuda.device(cum.device):
+        check(_lib.lib().dm_pair_epoch_select(cum.data_ptr(), cum.numel(), out.numel(), int(seed) & 0xFFFFFFFFFFFFFFFF, int(epoch),
+                                              out.data_ptr(), _stream()), "dm_pair_epoch_select")
+
+
+@dataclass(frozen=True)
+class Mining:
+    """Loss-driven pair weights for Train_SMT.train(mining=): every `every` epochs the loss term of every training pair is
+    recomputed (PairDataset.pair_terms) and turned into an integer hardness 1 .. 256 that saturates at `cap`
+    (dataset.hardness_weights); the epochs until the next refresh are sampled with it."""
+    every: int = 5
+    cap: float = 1.0
+    floor_share: float = 1.0 / 16.0       # the least weight as a share of the greatest (dataset.hardness_weights)
+
+    def __post_init__(self):
+        if isinstance(self.floor_share, bool) or not isinstance(self.floor_share, (int, float)) or not 0.0 < float(self.floor_share) <= 1.0:
+            raise ValueError(f"Mining: floor_share must be a number in (0, 1], got {self.floor_share!r}")
+        if isinstance(self.every, bool) or not isinstance(self.every, int) or self.every < 1:
+            raise ValueError(f"Mining: every must be an integer >= 1, got {self.every!r}")
+        c = self.cap
+        if isinstance(c, bool) or not isinstance(c, (int, float)) or not (float(c) > 0.0 and float(c) < float("inf")):
+            raise ValueError(f"Mining: cap must be a finite number > 0, got {c!r}")
 
 
 def patch_pyramid_cols(tile: torch.Tensor, xy: torch.Tensor, windows: torch.Tensor, target: int, grid: int = 8,

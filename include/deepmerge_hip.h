@@ -48,7 +48,8 @@ int dm_abi_version(void);   /* 2: dm_patch_pyramid / dm_patch_pyramid_cols take 
                              * 7: dm_gemm_grouped(args, n, stream) without a group workspace, its workspace query removed;
                              * additive in 6: dm_pairwise_distance, dm_pair_epoch_draw, dm_contrastive_terms, dm_pair_eval_summary;
                              * additive in 7: dm_region_merge_cost, dm_pixel_regions, dm_pair_batch_gather_oriented, dm_pair_epoch_orient,
-                             *   dm_pair_batch_gather_augmented, dm_pair_epoch_radiometric */
+                             *   dm_pair_batch_gather_augmented, dm_pair_epoch_radiometric, dm_pair_epoch_select, dm_pair_epoch_draw_src,
+                             *   dm_pair_epoch_orient_src, dm_pair_epoch_radiometric_src */
 const char *dm_last_error(void);
 /* Name of the code object architecture the library was built for ("gfx950"). */
 const char *dm_arch(void);
@@ -501,6 +502,31 @@ int dm_pair_epoch_orient(uint64_t seed, int32_t epoch, int32_t n_pairs, int32_t 
 #define DM_RADIO_MAX_OFFSET_SPAN 16320
 int dm_pair_epoch_radiometric(uint64_t seed, int32_t epoch, int32_t n_pairs, int32_t batch, int32_t bands, int32_t gain_span,
                               int32_t band_span, int32_t offset_span, int32_t *radio, void *stream);
+/* Weighted pair sampling with replacement (additive in ABI 7; DESIGN.md 3.9, tests/sampling_ref.py restates it in numpy).
+ * w int64 [N] weights, all >= 0 and not all 0; cum = the inclusive prefix sums of w (int64 [N]); T = cum[N - 1], 1 <= T < 2^62 (the
+ * caller validates w and T; deepmerge_amd.dataset does, with one readback per epoch).  M draws, 1 <= M <= 2^30; N <= 2^30.
+ * Select -- counter word 5, which the draw (1), shuffle (2), orientation (3) and jitter (4) do not use.  For position j in [0, M):
+ *   r = philox4x32_10((j, epoch, 5, 0), key),   R = (uint64)r[0] << 32 | r[1],   u = umul64hi(R, T)        (0 <= u < T)
+ *   src[j] = #{i : cum[i] <= u} = the smallest i with cum[i] > u
+ * so a pair of weight 0 is never selected wherever it sits.  src int32 [M].  One thread per position, a binary search whose index
+ * stays in [0, N) for ANY cum: a table that breaks the contract reads nothing out of range and yields values in [0, N] (N: see
+ * below).  Refused before any launch: a null pointer, n_pairs or n_draws outside 1 .. 2^30, epoch < 0. */
+int dm_pair_epoch_select(const int64_t *cum, int32_t n_pairs, int32_t n_draws, uint64_t seed, int32_t epoch, int32_t *src, void *stream);
+/* The sampled epoch: position j of n_draws takes pair src[j] (src int32 [n_draws], e.g. dm_pair_epoch_select's).  A pair can be drawn
+ * twice in one epoch, and must not show the same sample points, orientation and exposure twice, so the three streams are keyed by
+ * the POSITION j, on counter words of their own (the unsampled word + 16):
+ *   point draw   r = philox4x32_10((j, epoch, 17, 0), key), r[0] / r[1] used as dm_pair_epoch_draw uses them
+ *   orientation  philox4x32_10((j, epoch, 19, 0), key)[0] & mask
+ *   radiometric  A = philox4x32_10((j, epoch, 20, 0), key),  B = philox4x32_10((j, epoch, 20, 1 + c / 4), key), sym and limits as above
+ * Everything is a function of (seed, epoch, j, w): independent of the batch size, the same after a resume given the same weights.
+ * Layout: the blocked layout above with n_draws in place of N (b_s = min(batch, n_draws - s batch)); flag[j] = pair_flag[src[j]].
+ * args->n_pairs stays the list length N; the outputs hold 2 n_draws rows and n_draws flags.  An src entry outside [0, N) reads
+ * nothing out of range: both samples of the position get point_id -1, tile id -1 and zeros, and flag[j] = 0.  The same kernels as
+ * the unsampled entry points, instantiated on the key rule; refusals as theirs, plus a null src and n_draws outside 1 .. 2^30. */
+int dm_pair_epoch_draw_src(const DmPairDraw *args, const int32_t *src, int32_t n_draws, void *stream);
+int dm_pair_epoch_orient_src(uint64_t seed, int32_t epoch, int32_t n_draws, int32_t batch, int32_t mask, int32_t *orient, void *stream);
+int dm_pair_epoch_radiometric_src(uint64_t seed, int32_t epoch, int32_t n_draws, int32_t batch, int32_t bands, int32_t gain_span,
+                                  int32_t band_span, int32_t offset_span, int32_t *radio, void *stream);
 
 /* ---- held-out pair evaluation (additive in ABI 6; deepmerge_amd/evaluate.py) ---------------------------
  * Per-pair contrastive terms -- the per-pair form of the reference's contrastive loss (Losses.py:34-38, before its mean):

@@ -4,6 +4,10 @@ epoch, FRESH pairs every step generated on the device -- patch pyramids cut from
 (deepmerge_amd/feed.py: one dm_pair_batch_gather launch per scale straight into the captured step's inputs), positives = two
 jittered windows of the same spot, negatives = spots of different tiles -- through PairTrainer (hipGraph replay).  Prints a loss curve; BASELINE configs[4] shape by default (depth [6,4,2], 4 scales x 4 ch,
 120 pairs per GPU).        python tools/train_synth.py [--epochs 3] [--steps-per-epoch 20] [--pairs 120] [--depth 6,4,2] [--augment d4] [--radiometric 0.2,0.1,0.05]
+--balance P / --mining EVERY[,CAP]: instead of fresh pairs every step, a fixed pool of steps-per-epoch x pairs pairs is drawn once and
+every epoch samples it with replacement by integer weights (dataset.balance_weights / hardness_weights, one
+ops.pair_epoch_select launch per epoch); each step gathers its rows of the pool by index.  Mining evaluates the pool's loss terms with
+the model as it stands at the first epoch and every EVERY-th.
 """
 import argparse
 import json
@@ -17,6 +21,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from deepmerge_amd import ops  # noqa: E402
 from deepmerge_amd.nets.ShfitScaleFormer import ShfitScaleFormer_v3  # noqa: E402
+from deepmerge_amd.dataset import balance_weights, hardness_weights  # noqa: E402
 from deepmerge_amd.feed import PairFeed, PairTable  # noqa: E402
 from deepmerge_amd.patches import point_batch  # noqa: E402
 from deepmerge_amd.trainer import PairTrainer, multistep_lr  # noqa: E402
@@ -69,6 +74,21 @@ def draw_radio(B, bands, radiometric, step, out):
     return out
 
 
+def pool_terms(net, feed, pool, B, margin=1.0):
+    """fp32 [len(pool)]: the contrastive term of every pair of the pool in pool order, B pairs per eval forward (a feed of its own)."""
+    n = pool[-1].shape[0]
+    term, d2 = torch.empty(n, device=DEV), torch.empty(n, device=DEV)
+    was_training = net.training
+    net.eval()
+    with torch.no_grad():
+        for lo in range(0, n, B):
+            _, _, _, _, flag = feed.fill(pair_table(tuple(t[lo:lo + B] for t in pool)))
+            F = net(feed.both, feed.dboth).contiguous()
+            ops.contrastive_terms(F[:B], F[B:], flag, margin, d2=d2[lo:lo + B], term=term[lo:lo + B])
+    net.train(was_training)
+    return term
+
+
 MAX_WINDOW = [64, 112, 160, 208]       # bounds of (inner, obj, obj + interval, obj + 2 interval) for the ranges drawn above
 
 
@@ -112,8 +132,22 @@ def main():  # noqa: C901
     ap.add_argument("--radiometric", type=str, default=None, metavar="C,B,K",
                     help="feed every pair under a random gain / offset per band: contrast, brightness, colour half widths, e.g. 0.2,0.1,0.05 "
                          "(both sides alike; rows / patches feeds only)")
+    ap.add_argument("--balance", type=float, default=None, metavar="P",
+                    help="sample a fixed pool of pairs with replacement so that a share P of what the model sees is positive pairs")
+    ap.add_argument("--mining", type=str, default=None, metavar="EVERY[,CAP]",
+                    help="sample the pool by loss-driven weights refreshed every EVERY epochs, saturating at a term of CAP (default 1.0)")
     ap.add_argument("--loss-every", type=int, default=0, help="read the loss back every k steps (0 = once per epoch)")
     args = ap.parse_args()
+    sampled = args.balance is not None or args.mining is not None
+    if sampled and args.feed == "looped":
+        ap.error("--balance / --mining need the sync-free feed (--feed rows or patches)")
+    try:
+        mining = None
+        if args.mining:
+            every, _, cap = args.mining.partition(",")
+            mining = ops.Mining(every=int(every), cap=float(cap) if cap else 1.0)
+    except (TypeError, ValueError) as e:
+        ap.error(f"--mining EVERY[,CAP]: {e}")
     if args.augment and args.feed == "looped":
         ap.error("--augment needs the sync-free feed (--feed rows or patches)")
     if args.radiometric and args.feed == "looped":
@@ -134,6 +168,19 @@ def main():  # noqa: C901
     tr.enable_graph(warmup=1)
     feed = None if args.feed == "looped" else PairFeed(tiles, scales, args.pairs, MAX_WINDOW, rows=args.feed == "rows", numerics=args.numerics, trainer=tr)
     radio_buf = torch.empty((2 * args.pairs, bands, 2), dtype=torch.int32, device=DEV) if radiometric else None
+    pool = src = weights = class_w = eval_feed = None
+    if sampled:                                              # the pool: one epoch's worth of pairs, drawn once
+        n_pool = args.steps_per_epoch * args.pairs
+        pool = draw_pairs(tiles.shape[0], tiles.shape[2], n_pool, g)
+        src = torch.empty(n_pool, dtype=torch.int32, device=DEV)
+        try:
+            class_w = weights = balance_weights(pool[-1], args.balance) if args.balance is not None else None
+        except ValueError as e:
+            ap.error(f"--balance P: {e}")
+        if mining is not None:
+            if n_pool % args.pairs:
+                ap.error("--mining evaluates the pool in batches of --pairs")
+            eval_feed = PairFeed(tiles, scales, args.pairs, MAX_WINDOW, rows=args.feed == "rows", numerics=args.numerics)
     curve = []
     torch.cuda.synchronize()
     t0 = time.perf_counter()
@@ -142,6 +189,10 @@ def main():  # noqa: C901
     for epoch in range(args.epochs):
         lr = multistep_lr(args.lr, epoch, ms)
         tot = torch.zeros((), device=DEV)
+        if sampled:
+            if mining is not None and epoch % mining.every == 0:
+                weights = hardness_weights(pool_terms(net, eval_feed, pool, args.pairs), mining.floor_share, mining.cap, class_weights=class_w)
+            ops.pair_epoch_select(torch.cumsum(weights, 0), 0, epoch, src)
         for k in range(args.steps_per_epoch):
             if done == WARM:
                 torch.cuda.synchronize(); t_warm = time.perf_counter()
@@ -151,7 +202,12 @@ def main():  # noqa: C901
             else:
                 orient = draw_orient(args.pairs, args.augment, g_orient) if args.augment else None
                 radio = draw_radio(args.pairs, bands, radiometric, done, radio_buf) if radiometric else None
-                batch = feed.fill(pair_table(draw_pairs(tiles.shape[0], tiles.shape[2], args.pairs, g), orient, radio))
+                if sampled:
+                    idx = src[k * args.pairs:(k + 1) * args.pairs].long()
+                    draw = tuple(t[idx] for t in pool)
+                else:
+                    draw = draw_pairs(tiles.shape[0], tiles.shape[2], args.pairs, g)
+                batch = feed.fill(pair_table(draw, orient, radio))
             tot += tr.step(*batch, lr=lr)                    # (device-side sum: the reference's per-step .item(), Train_SMT.py:301, is a sync)
             if args.loss_every and (k + 1) % args.loss_every == 0:
                 float(tot)
@@ -162,7 +218,7 @@ def main():  # noqa: C901
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     n = args.epochs * args.steps_per_epoch
-    print(json.dumps({"tool": "train_synth", "feed": args.feed, "augment": args.augment, "radiometric": args.radiometric, "numerics": args.numerics, "depth": depth, "pairs_per_step": args.pairs, "steps": n,
+    print(json.dumps({"tool": "train_synth", "feed": args.feed, "augment": args.augment, "radiometric": args.radiometric, "balance": args.balance, "mining": args.mining, "numerics": args.numerics, "depth": depth, "pairs_per_step": args.pairs, "steps": n,
                       "loss_curve": curve, "hip_graph": tr.graph_error is None, "pairs_per_s_incl_data_generation": round(n * args.pairs / dt, 1),
                       "pairs_per_s_steady_incl_data_generation": None if t_warm is None else round((n - WARM) * args.pairs / (t0 + dt - t_warm), 1),
                       "steady_note": f"after the first {WARM} steps (eager warm-up + hipGraph capture)"}))
