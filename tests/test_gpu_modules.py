@@ -5,6 +5,7 @@ oracle is pinned with, so these read like the reference's own per-module tests w
 Parity (fp32) mode gate: 1e-3 relative; typical observed error ~1e-5.
 Throughput (bf16) mode: drift is measured and bounded loosely (the reference itself under bf16
 autocast drifts 6.6e-3 on embeddings / 2.6e-2 on gradients).
+The per-tensor gate of the whole model in bf16 (every gradient against fp64 truth) is tests/test_gpu_model_oracle.py.
 """
 import numpy as np
 import pytest
